@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Glow-TTS training hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5dec|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5dec|cfg5] [--dump-outputs DIR] [--full]
 
 One "step" = one full training step of the hot path (zero_grad, TextEncoder + FlowSpecDecoder forward, logp + MAS,
 mle + duration loss [+ pitch / energy predictor losses for cfg 5], backward, gradient all-reduce, grad-norm, AdamW) on one
@@ -14,16 +14,31 @@ collective is the RCCL gradient all-reduce.
 
 Prints ONE JSON line on rank 0:
   value            = valid mel-frames / s over all ranks (BASELINE.json metric, first half); wall clock of exactly K steps
+  ms_per_step      = that wall clock / K
   step_ms_median   = median of the K per-step times (HIP events recorded on the step's stream, read after the region)
+
+A plain run does only that: set-up, W warm-up steps, K timed steps, the line.  --full adds what takes extra work:
   mas              = MAS alignments / s of gt_mas_f32 alone on the step's own lattice shape (second half) + its CPU baselines
                      (reference Cython core on 1 core — what the reference uses — and the C restatement on all cores)
   roofline         = the dominant kernel family by time, the whole-WaveNet forward kernel (gt_wn_stack_fwd: 4 x (k=5 conv + gate) +
                      3 x residual 1x1 in one launch; the per-layer gt_wn_layer_fwd where a batch's rows take that path):
                      algorithmic FLOPs / its duration INSIDE the replayed graph (device-side begin / end stamps of every one of
-                     its launches in the timed steps; `profiles/` holds the rocprofv3 summary of the same command), plus
-                     `step` = whole-step FLOP/s over the bf16 MFMA peak
+                     its launches in the timed steps, written only under --full; `profiles/` holds the rocprofv3 summary of the
+                     same command), plus `step` = whole-step FLOP/s over the bf16 MFMA peak
   cpu_baseline     = the oracle's training step (PyTorch-CPU fp32 restatement of the reference, oracle/glowtts_ref.py +
-                     reference Cython MAS from oracle/_ref) on a bounded sample
+                     reference Cython MAS from oracle/_ref) on a bounded sample (--no-cpu-baseline leaves it out)
+
+--dump-outputs DIR writes what the last timed step handed its caller, as float32 .npy files (rank 0): loss.npy and
+mle_loss.npy (the two values step() returns), grad_norm.npy, and the model the step updated in place: params.npy (the flat
+parameter buffer after the optimizer) and grads.npy (the flat gradient buffer it applied), each a fixed seeded sample of
+DUMP_SAMPLE elements when the buffer is larger.
+
+Same arguments, same results: the batches and the initial weights are seeded, and every step (warm-up and timed) runs AdamW
+at learning rate BENCH_LR = 0.  The optimizer kernel still reads the gradients and moments, updates the moments and
+rewrites every parameter (p * (1 - lr * wd) - lr * ..., the same work at any lr), but the weights stay the seeded ones, so
+each step computes from the same inputs and two runs differ only by the rounding of that one step's float atomics.  With a
+non-zero rate every step would start from weights that carry the rounding of all the steps before it, and training
+amplifies it: two runs of 1000 steps then end with different gradients.
 """
 import argparse
 import json
@@ -40,6 +55,8 @@ import torch  # noqa: E402
 MFMA_BF16_PEAK_TFLOPS = 2500.0   # MI355X_MICROARCH.md: ~2.5 PF dense bf16
 HBM_PEAK_GBS = 8000.0
 N_BATCHES = 8                     # distinct batches the timed region rotates over
+DUMP_SAMPLE = 1 << 22              # --dump-outputs: elements kept of a flat buffer larger than this (16 MiB in fp32)
+BENCH_LR = 0.0                     # the steps' AdamW learning rate: the full update runs, the weights stay the seeded ones
 
 CFG5_MODEL = dict(hidden_channels=192, filter_channels=768, filter_channels_dp=256, kernel_size=3, p_dropout=0.1, n_blocks_dec=12,
                   n_layers_enc=10, n_heads=2, p_dropout_dec=0.05, dilation_rate=1, kernel_size_dec=5, n_block_layers=4, n_sqz=2,
@@ -227,13 +244,33 @@ def step_flops(wl, batch):
     return 3.0 * (dec * fr + enc * tok) + 2.0 * 2.0 * 80.0 * cells
 
 
+def dump_outputs(out_dir, tr, loss, mle):
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy (float32).  The flat parameter and gradient buffers are
+    sampled at the same DUMP_SAMPLE indices (seed 0, sorted) when they are larger than that."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss, "mle_loss": mle, "grad_norm": tr.grad_norm}
+    flat_p, flat_g = tr.opt.flat_p, tr.buckets.flat
+    n = flat_p.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))).to(flat_p.device)
+    for name, t in (("params", flat_p), ("grads", flat_g)):
+        arrays[name] = t if idx is None else t.index_select(0, idx)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().reshape(-1).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also measure the MAS leg, the in-graph roofline (device-side kernel stamps in "
+                    "the timed steps) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--late-adam", action="store_true", help="dev: the optimizer's pass over the decoder's parameters after the whole backward "
                     "(Trainer(early_decoder_adam=False)) instead of right behind the decoder's weight gradients")
     ap.add_argument("--head-pack", action="store_true", help="dev: pack all weights at the head of the step (Trainer(pack_in_tail=False)) "
@@ -249,6 +286,8 @@ def main():
     ap.add_argument("--grad-wire", default="fp32", choices=["fp32", "bf16"],
                     help="N > 1: gradient exchange in fp32 (the reference's DDP all-reduce; default) or bf16 on the wire with fp32 accumulation")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -276,7 +315,7 @@ def main():
         for p in model.parameters():
             torch.distributed.broadcast(p.data, 0)
     use_graph = not args.no_graph
-    tr = train.Trainer(model, world=world, graph=use_graph, kernel_stamps=True, grad_wire=args.grad_wire,
+    tr = train.Trainer(model, lr=BENCH_LR, world=world, graph=use_graph, kernel_stamps=args.full, grad_wire=args.grad_wire,
                        split_graph=None if args.split_graph is None else bool(args.split_graph),
                        early_decoder_adam=not args.late_adam, pack_in_tail=not args.head_pack, split_roots=not args.join_roots)
     nb = 1 if args.one_batch else N_BATCHES
@@ -294,7 +333,10 @@ def main():
         _ops = import_module(train.__name__.rsplit(".", 1)[0] + ".ops")
         _ops.MARKS = _ops.Marks(dev)
     if tr.stamps is not None:                       # every step (eager warm-ups of the captures included) takes a row of stamp slots
-        assert args.steps + args.warmup + 3 * len(batches) + 8 <= tr.stamps.max_steps, "raise KernelStamps(max_steps=) for this many steps"
+        need = args.steps + args.warmup + 3 * len(batches) + 8
+        if need > tr.stamps.max_steps:              # a longer run than the trainer's default buffer holds: a larger one, before any capture
+            from glow_tts_amd import ops
+            tr.stamps = tr.cfg.stamps = ops.KernelStamps(dev, tr.stamps.per_step, max_steps=need)
     t_cap = time.perf_counter()
     tr.precapture([(b["ids"], b["t_x"], b["y"], b["t_y"], b["lh"], b["cond"]) for b in batches])
     torch.cuda.synchronize(dev)
@@ -327,10 +369,11 @@ def main():
     if args.marks and rank == 0:
         for us, name in _ops.MARKS.report():
             print(f"  {us:9.1f} us  {name}", file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, loss, mle)
 
     if rank == 0:
         ms_per_step = wall / args.steps * 1e3
-        flops_step = sum(step_flops(wl, batches[i % nb]) for i in range(args.steps)) / args.steps
         rows_keys = sorted({tr._rows_key(-(-b["ids"].shape[1] // tr.pad_tx) * tr.pad_tx, -(-b["y"].shape[2] // tr.pad_ty) * tr.pad_ty, b["lh"])
                             for b in batches})
         line = {
@@ -359,73 +402,75 @@ def main():
             "step_ms_median": step_ms[len(step_ms) // 2], "step_ms_min": step_ms[0], "step_ms_max": step_ms[-1],
             "padded_frames_per_sec": world * wl["B"] * wl["T_y"] / (wall / args.steps),
         }
-        # ---- roofline: the fused WaveNet-layer forward kernel, timed INSIDE the replayed graphs by its own device stamps
-        roof = {"bound": "mfma", "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "traffic": None}
-        if tr.stamps is not None:
-            d = tr.stamps.durations_ticks()[steps0:steps0 + args.steps].double()          # [K, slots per step] in 10-ns ticks
-            nl = model.decoder.n_layers
-            rows_valid = (valid_total / args.steps) / 2.0                                 # squeezed frames
-            # which kernel stamped which slot of a step (ops.KernelStamps.kinds): the whole-WaveNet launches (csrc/wn_stack.hip), or —
-            # for row counts whose extra workgroups would not fit one round of CUs — the per-layer launches (csrc/wn_layer.hip).
-            # The family with the larger share of the stamped time is the roofline kernel; slots nobody wrote in a step stay 0.
-            kinds = tr.stamps.kinds
-            fam = {"stack": [k for k, v in kinds.items() if v == {f"stack{nl}"}], "layer": [k for k, v in kinds.items() if v == {"layer"}],
-                   "layer_last": [k for k, v in kinds.items() if v == {"layer_last"}]}
-            mixed = sorted(k for k, v in kinds.items() if len(v) > 1)
-            tot = {f: float(d[:, sl].sum()) if sl else 0.0 for f, sl in fam.items()}
-            if tot["stack"] >= tot["layer"] + tot["layer_last"]:
-                used = d[:, fam["stack"]]
-                used = used[used > 0]
-                us = used.mean().item() / 100.0                                           # wall_clock64: 100 MHz
-                flops_launch = 2.0 * rows_valid * (nl * 384 * 192 * 5 + (nl - 1) * 192 * 192)
-                name = (f"gt_wn_stack_fwd_kernel (a whole WaveNet forward in one launch: {nl} x (k=5 conv 192->384 + gate) + {nl - 1} x "
-                        f"residual 1x1, halo recomputed per 52-row tile; {used.numel() / args.steps:.1f} launches per step)")
-                extra, n_l = {}, used.numel()
-                pmc_name = "r03_decoder_pmc.json"
-            else:
-                used = d[:, fam["layer"]]
-                used = used[used > 0]
-                us = used.mean().item() / 100.0
-                flops_launch = 2.0 * rows_valid * (384 * 192 * 5 + 192 * 192)
-                name = ("gt_wn_layer_fwd_kernel<true> (WaveNet layer: k=5 conv 192->384 + gate + residual 1x1, one launch; "
-                        f"{used.numel() / args.steps:.1f} launches per step)")
-                last = d[:, fam["layer_last"]]
-                extra, n_l = {"launch_us_last_layer_variant": last[last > 0].mean().item() / 100.0 if fam["layer_last"] else None}, used.numel()
-                pmc_name = "r02_wn_layer_pmc.json"
-            extra["stamped_us_per_step"] = {f: v / 100.0 / args.steps for f, v in tot.items()}
-            if mixed:
-                extra["slots_with_both_kernel_families"] = mixed                          # (different row buckets routed differently)
-            tf = flops_launch / (us * 1e-6) / 1e12
-            roof.update({"achieved": tf, "frac": tf / MFMA_BF16_PEAK_TFLOPS, "kernel": name,
-                         "algorithmic_flops_per_launch": flops_launch, "launch_us": us, **extra,
-                         "how": "device-side begin / end stamps (wall_clock64, 100 MHz) written by every launch of the kernel inside the "
-                                "replayed HIP graphs of the timed steps: max(end) - min(start) per launch, mean over "
-                                f"{n_l} launches; FLOPs count the VALID squeezed frames only (the recomputed halo rows are not counted)",
-                         "profile": "profiles/r03_v3_trainstep_summary.txt (rocprofv3 --kernel-trace --stats of the same command)"})
-            pmc = os.path.join(ROOT, "profiles", pmc_name)
-            if os.path.exists(pmc):
-                with open(pmc) as f:
-                    pj = json.load(f)
-                if "kernels" in pj:                                   # tools/decoder_pmc.py: the decoder's four fused kernels
-                    kj = pj["kernels"].get("wn_stack_fwd", {})
-                    roof["traffic"] = kj.get("hbm_bytes_per_launch")
-                    roof["mfma_busy_fraction"] = kj.get("mfma_busy_fraction_of_wave_lifetime")   # SQ_VALU_MFMA_BUSY_CYCLES / wave lifetime
-                    roof["traffic_source"] = pj.get("source")
+        if args.full:
+            # ---- roofline: the fused WaveNet-layer forward kernel, timed INSIDE the replayed graphs by its own device stamps
+            flops_step = sum(step_flops(wl, batches[i % nb]) for i in range(args.steps)) / args.steps
+            roof = {"bound": "mfma", "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "traffic": None}
+            if tr.stamps is not None:
+                d = tr.stamps.durations_ticks()[steps0:steps0 + args.steps].double()          # [K, slots per step] in 10-ns ticks
+                nl = model.decoder.n_layers
+                rows_valid = (valid_total / args.steps) / 2.0                                 # squeezed frames
+                # which kernel stamped which slot of a step (ops.KernelStamps.kinds): the whole-WaveNet launches (csrc/wn_stack.hip), or —
+                # for row counts whose extra workgroups would not fit one round of CUs — the per-layer launches (csrc/wn_layer.hip).
+                # The family with the larger share of the stamped time is the roofline kernel; slots nobody wrote in a step stay 0.
+                kinds = tr.stamps.kinds
+                fam = {"stack": [k for k, v in kinds.items() if v == {f"stack{nl}"}], "layer": [k for k, v in kinds.items() if v == {"layer"}],
+                       "layer_last": [k for k, v in kinds.items() if v == {"layer_last"}]}
+                mixed = sorted(k for k, v in kinds.items() if len(v) > 1)
+                tot = {f: float(d[:, sl].sum()) if sl else 0.0 for f, sl in fam.items()}
+                if tot["stack"] >= tot["layer"] + tot["layer_last"]:
+                    used = d[:, fam["stack"]]
+                    used = used[used > 0]
+                    us = used.mean().item() / 100.0                                           # wall_clock64: 100 MHz
+                    flops_launch = 2.0 * rows_valid * (nl * 384 * 192 * 5 + (nl - 1) * 192 * 192)
+                    name = (f"gt_wn_stack_fwd_kernel (a whole WaveNet forward in one launch: {nl} x (k=5 conv 192->384 + gate) + {nl - 1} x "
+                            f"residual 1x1, halo recomputed per 52-row tile; {used.numel() / args.steps:.1f} launches per step)")
+                    extra, n_l = {}, used.numel()
+                    pmc_name = "r03_decoder_pmc.json"
                 else:
-                    roof["traffic"] = pj.get("hbm_bytes_per_launch")
-                    roof["traffic_source"] = pj.get("source")
-        roof["step"] = {"algorithmic_flops_per_step": flops_step, "achieved": flops_step / (wall / args.steps) / 1e12,
-                        "frac": flops_step / (wall / args.steps) / 1e12 / MFMA_BF16_PEAK_TFLOPS,
-                        "how": "SURVEY §8d: 3 x forward FLOPs over the valid frames / tokens of the rotated batches, / wall time per step"}
-        line["roofline"] = roof
-        m = mas_leg(dev, wl, rank)
-        line["mas"] = {"metric": "mas_alignments_per_sec", "value": world * m["alignments_per_sec"], "unit": "alignments/s",
-                       "ms_per_batch": m["ms_per_batch"], "cpu_baseline": m.get("cpu"),
-                       "roofline": {"bound": "hbm", "achieved": m["achieved_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                    "frac": m["hbm_frac"], "traffic": None, "kernel": "gt_mas_dp_kernel + gt_mas_expand_kernel",
-                                    "algorithmic_bytes_per_launch": m["algorithmic_bytes"]}}
-        if not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(batches[0], model, wl)
+                    used = d[:, fam["layer"]]
+                    used = used[used > 0]
+                    us = used.mean().item() / 100.0
+                    flops_launch = 2.0 * rows_valid * (384 * 192 * 5 + 192 * 192)
+                    name = ("gt_wn_layer_fwd_kernel<true> (WaveNet layer: k=5 conv 192->384 + gate + residual 1x1, one launch; "
+                            f"{used.numel() / args.steps:.1f} launches per step)")
+                    last = d[:, fam["layer_last"]]
+                    extra, n_l = {"launch_us_last_layer_variant": last[last > 0].mean().item() / 100.0 if fam["layer_last"] else None}, used.numel()
+                    pmc_name = "r02_wn_layer_pmc.json"
+                extra["stamped_us_per_step"] = {f: v / 100.0 / args.steps for f, v in tot.items()}
+                if mixed:
+                    extra["slots_with_both_kernel_families"] = mixed                          # (different row buckets routed differently)
+                tf = flops_launch / (us * 1e-6) / 1e12
+                roof.update({"achieved": tf, "frac": tf / MFMA_BF16_PEAK_TFLOPS, "kernel": name,
+                             "algorithmic_flops_per_launch": flops_launch, "launch_us": us, **extra,
+                             "how": "device-side begin / end stamps (wall_clock64, 100 MHz) written by every launch of the kernel inside the "
+                                    "replayed HIP graphs of the timed steps: max(end) - min(start) per launch, mean over "
+                                    f"{n_l} launches; FLOPs count the VALID squeezed frames only (the recomputed halo rows are not counted)",
+                             "profile": "profiles/r03_v3_trainstep_summary.txt (rocprofv3 --kernel-trace --stats of the same command)"})
+                pmc = os.path.join(ROOT, "profiles", pmc_name)
+                if os.path.exists(pmc):
+                    with open(pmc) as f:
+                        pj = json.load(f)
+                    if "kernels" in pj:                                   # tools/decoder_pmc.py: the decoder's four fused kernels
+                        kj = pj["kernels"].get("wn_stack_fwd", {})
+                        roof["traffic"] = kj.get("hbm_bytes_per_launch")
+                        roof["mfma_busy_fraction"] = kj.get("mfma_busy_fraction_of_wave_lifetime")   # SQ_VALU_MFMA_BUSY_CYCLES / wave lifetime
+                        roof["traffic_source"] = pj.get("source")
+                    else:
+                        roof["traffic"] = pj.get("hbm_bytes_per_launch")
+                        roof["traffic_source"] = pj.get("source")
+            roof["step"] = {"algorithmic_flops_per_step": flops_step, "achieved": flops_step / (wall / args.steps) / 1e12,
+                            "frac": flops_step / (wall / args.steps) / 1e12 / MFMA_BF16_PEAK_TFLOPS,
+                            "how": "SURVEY §8d: 3 x forward FLOPs over the valid frames / tokens of the rotated batches, / wall time per step"}
+            line["roofline"] = roof
+            m = mas_leg(dev, wl, rank)
+            line["mas"] = {"metric": "mas_alignments_per_sec", "value": world * m["alignments_per_sec"], "unit": "alignments/s",
+                           "ms_per_batch": m["ms_per_batch"], "cpu_baseline": m.get("cpu"),
+                           "roofline": {"bound": "hbm", "achieved": m["achieved_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                        "frac": m["hbm_frac"], "traffic": None, "kernel": "gt_mas_dp_kernel + gt_mas_expand_kernel",
+                                        "algorithmic_bytes_per_launch": m["algorithmic_bytes"]}}
+            if not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(batches[0], model, wl)
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.barrier()

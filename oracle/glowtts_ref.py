@@ -5,7 +5,7 @@ reference's state_dict names.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this; the
 product package glow-tts_amd/ never does.
 
-Parity status: PINNED to the reference's own modules — tests/golden/float_golden.npz holds
+Parity status: PINNED to the reference's own modules — tests/golden/float_golden/ holds
 inputs/outputs/gradients produced by importing /root/reference (modules.py, attentions.py,
 models.py) with closed-form weights (tests/golden/fill.py, tests/golden/make_float_golden.py);
 tests/test_float_oracle.py checks every function here against it (fp32, rtol 1e-5).

@@ -1,4 +1,4 @@
-"""Generate tests/golden/float_golden.npz by IMPORTING the reference's Python modules
+"""Generate tests/golden/float_golden/ by IMPORTING the reference's Python modules
 (/root/reference: modules.py, attentions.py, models.py, commons.py) in the build container.
 
     make -C oracle && python tests/golden/make_float_golden.py
@@ -27,6 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 
 from fill import fill_module  # noqa: E402
+import shards  # noqa: E402
 from oracle import mas as omas  # noqa: E402
 
 
@@ -357,9 +358,9 @@ def main():
                full_attn=attn5, full_l_length=ll5, full_l_pitch=lp5, full_l_energy=le5, full_l_mle=lmle5, full_loss=loss5,
                **{"full_g_" + n: (v if v is not None else torch.zeros_like(pg[n])) for n, v in zip(full_names, gfull)})
 
-    path = os.path.join(HERE, "float_golden.npz")
-    np.savez_compressed(path, **{k: v.detach().cpu().numpy() for k, v in out.items()})
-    print("wrote", path, len(out), "arrays", os.path.getsize(path), "bytes")
+    path = os.path.join(HERE, "float_golden")
+    n = shards.save(path, {k: v.detach().cpu().numpy() for k, v in out.items()})
+    print("wrote", path, len(out), "arrays in", n, "shards")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 """GPU parity tests: flow-decoder HIP path (through the C-ABI, glow_tts_amd modules) vs the float
-oracle (oracle/glowtts_ref.py, CPU fp32, pinned to the reference by tests/golden/float_golden.npz).
+oracle (oracle/glowtts_ref.py, CPU fp32, pinned to the reference by tests/golden/float_golden/).
 
 Tolerances (stated, north_star "stated fp tolerance"): GEMMs run in bf16 with fp32 accumulation and
 bf16 hidden activations, so z / gradients are compared at 3e-2 of the tensor's max-abs (observed
@@ -172,7 +172,7 @@ def test_decoder_two_blocks_fwd_bwd(built):
 
 
 def test_decoder_sigmoid_scale(built):
-    """sigmoid_scale=True (attentions.py:172-173; oracle pinned by cbs_* in float_golden.npz): forward, log-det, gradients."""
+    """sigmoid_scale=True (attentions.py:172-173; oracle pinned by cbs_* in float_golden/): forward, log-det, gradients."""
     _run_decoder_case(2, 2, 48, [48, 26], seed=5, check_params=True, sigmoid_scale=True)
 
 
@@ -266,7 +266,7 @@ def test_decoder_pitch_energy_speaker_conditioning(built, ragged, pitch_only):
     """cfg 5's decoder: every coupling block runs wn(g) -> wn_energy(energy) -> wn_pitch(pitch) (attentions.py:152-154),
     the latter two modules.WNP with per-frame conditioning (the gate kernel's per-row cond).  Forward, log-det, input
     gradient, EVERY parameter gradient (cond_layer1 affine maps included), the gradient of g, and the reverse direction
-    against the oracle (pinned to the imported reference: decp_* in float_golden.npz); pitch alone leaves wn_energy the
+    against the oracle (pinned to the imported reference: decp_* in float_golden/); pitch alone leaves wn_energy the
     identity."""
     from glow_tts_amd import models, ops
     n_blocks, B, T, lens = 2, 3, 50, [50, 27, 12]
@@ -365,7 +365,7 @@ def test_coupling_block_standalone_reverse_and_prosody(built):
 def test_actnorm_ddi_initialises_block_after_block(built):
     """ActNorm data-dependent init (modules.py:588-590, 607-619; configs/base.json "ddi": true): set_ddi(True) on every
     ActNorm, one forward — each layer takes logs / bias from the masked statistics of the input IT sees; later forwards
-    leave them alone.  vs the oracle's restatement (pinned by ddi_* in float_golden.npz)."""
+    leave them alone.  vs the oracle's restatement (pinned by ddi_* in float_golden/)."""
     from glow_tts_amd import models, modules
     dec = fill_module(models.FlowSpecDecoder(80, 192, 5, 1, 3, 4, p_dropout=0.05), "decoder.").eval()
     P = cpu_state(dec, "decoder.")

@@ -1,6 +1,6 @@
 """GPU parity tests: text encoder, rel-pos attention, logp, prior expansion, mle loss and the whole
 training forward/backward (glow_tts_amd, HIP through the C-ABI) vs the float oracle
-(oracle/glowtts_ref.py, pinned to the reference by tests/golden/float_golden.npz).
+(oracle/glowtts_ref.py, pinned to the reference by tests/golden/float_golden/).
 
 Tolerances: bf16 GEMM operands / bf16 hidden activations -> 3e-2 of max-abs on activations,
 6e-2 on parameter gradients; fp32-only kernels (logp, expansion, loss) 1e-4."""
@@ -106,7 +106,7 @@ def test_encoder_stack_fwd_bwd(built):
 
 def test_encoder_speaker_conditioning_fwd_bwd(built):
     """Encoder.cond_g (attentions.py:66-67): the speaker vector added before layer index 2 — output, input gradient, the
-    gradient of g and of cond_g's parameters against the oracle (pinned to the reference by float_golden.npz: encg_*)."""
+    gradient of g and of cond_g's parameters against the oracle (pinned to the reference by float_golden/: encg_*)."""
     from glow_tts_amd import attentions
     enc = fill_module(attentions.Encoder(192, 768, 2, 3, 3, 0.1, window_size=4, gin_channels=256), "enc.").eval()
     P = cpu_state(enc, "enc.")

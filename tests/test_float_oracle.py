@@ -11,9 +11,10 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
 from fill import closed_form, filled_state  # noqa: E402
+import shards  # noqa: E402
 from oracle import glowtts_ref as R  # noqa: E402
 
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "float_golden.npz"))
+G = shards.load(os.path.join(os.path.dirname(__file__), "golden", "float_golden"))
 
 
 def t(name):
@@ -143,7 +144,7 @@ def test_glue_logp_mas_mle(built):
 
 def test_reverse_flow_and_generate_path_match_reference_golden(built):
     """Inference direction: FlowSpecDecoder(reverse=True) and commons.generate_path of the imported reference
-    (fixtures appended to float_golden.npz by make_float_golden.py) against the oracle restatement; and the restated
+    (fixtures appended to float_golden/ by make_float_golden.py) against the oracle restatement; and the restated
     reverse undoes the restated forward."""
     from glow_tts_amd import models
     P = module_state(models.FlowSpecDecoder(80, 192, 5, 1, 2, 4, p_dropout=0.05), "decoder.")
@@ -302,7 +303,7 @@ def test_dds_conv_elementwise_affine_conv_flow(built):
 
 
 def _grad_names(prefix):
-    return [k[len(prefix):] for k in G.files if k.startswith(prefix)]
+    return [k[len(prefix):] for k in G if k.startswith(prefix)]
 
 
 def test_stochastic_predictors(built):

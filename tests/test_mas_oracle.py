@@ -1,15 +1,14 @@
 """CPU tests: the oracle (oracle/mas_oracle.c) against the reference's own MAS.
 
 Pins: (1) tests/golden/mas_golden.npz — produced by the compiled reference core.pyx
-(tests/golden/make_mas_golden.py); (2) when oracle/_ref is present (build container, and the
-GPU box via the prebuilt .so) a direct comparison on 320 random lattices.
+(tests/golden/make_mas_golden.py); (2) the same reference's paths on 320 seeded random lattices,
+recorded as digests in that golden, and compared directly as well when oracle/_ref is built.
 """
 import hashlib
 import os
 import sys
 
 import numpy as np
-import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
 from oracle import mas as omas  # noqa: E402
@@ -60,25 +59,19 @@ def test_oracle_wrapper_semantics(built):
         assert p[i, 0, 0] == 1 and p[i, t_x[i] - 1, t_y[i] - 1] == 1
 
 
-@pytest.mark.skipif(omas.ref_module() is None, reason="oracle/_ref (compiled reference core.pyx) absent")
 def test_oracle_vs_compiled_reference_random(built):
-    rng = np.random.default_rng(99)
-    n = 0
-    for trial in range(40):
-        b = 8
-        T_x = int(rng.integers(1, 70)); T_y = int(rng.integers(T_x, 140))
-        t_x = rng.integers(1, T_x + 1, size=b).astype(np.int32)
-        t_y = np.array([rng.integers(t_x[i], T_y + 1) for i in range(b)], dtype=np.int32)
-        t_x[0], t_y[0] = T_x, T_y
-        if trial % 3 == 0:
-            v = rng.integers(-2, 2, size=(b, T_x, T_y)).astype(np.float32)     # tie-heavy
-        elif trial % 3 == 1:
-            v = rng.normal(-100, 5, size=(b, T_x, T_y)).astype(np.float32)
-        else:
-            v = rng.normal(-3e8, 2e8, size=(b, T_x, T_y)).astype(np.float32)   # crosses -1e9
+    """320 random lattices against the compiled reference core.pyx: the SHA-256 digests of its paths recorded in the golden
+    (make_mas_golden.py), and the live module as well where oracle/_ref is built."""
+    recorded = [str(d) for d in np.load(GOLD)["random_sha256"]]
+    live = omas.ref_module() is not None
+    n = trials = 0
+    for trial, (v, t_x, t_y) in enumerate(mk.random_lattices()):
         got = oracle_paths(v, t_x, t_y)
-        vv = v.copy(); want = np.zeros(v.shape, dtype=np.int32)
-        omas.ref_maximum_path_c(want, vv, t_x, t_y)
-        assert np.array_equal(got, want), trial
-        n += b
-    assert n >= 300
+        assert mk.path_digest(got) == recorded[trial], trial
+        if live:
+            vv = v.copy(); want = np.zeros(v.shape, dtype=np.int32)
+            omas.ref_maximum_path_c(want, vv, t_x, t_y)
+            assert np.array_equal(got, want), trial
+        n += len(v)
+        trials += 1
+    assert trials == len(recorded) and n >= 300

@@ -1,7 +1,7 @@
 """GPU parity tests of SURVEY §8 f1 and the cfg-5 drop-in: DilatedDepthSeparableConv, ConvFlow + rational-quadratic
 spline, the stochastic duration / pitch / energy predictors (HIP kernels of csrc/predictor_ops.hip through the C-ABI)
 and the full FlowGenerator of configs/base_blank_emo_lang_pitch.json, against the float oracle (oracle/glowtts_ref.py,
-pinned to the reference's own modules by tests/golden/float_golden.npz: dds_*, sp_*, cf_*, sdp_*, spp_*, sep_*, full_*).
+pinned to the reference's own modules by tests/golden/float_golden/: dds_*, sp_*, cf_*, sdp_*, spp_*, sep_*, full_*).
 
 Tolerances: the 192x192 1x1 convs run in bf16 with fp32 accumulation, everything else (depthwise convs, LayerNorms, GELU,
 the 29-row proj, the spline, the likelihood sums) in fp32: activations 2e-2 of max-abs, nll 1e-2 relative, parameter
@@ -15,10 +15,11 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
 from fill import fill_module  # noqa: E402
+import shards  # noqa: E402
 from oracle import glowtts_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "float_golden.npz"))
+G = shards.load(os.path.join(os.path.dirname(__file__), "golden", "float_golden"))
 
 
 def t(name):
@@ -327,7 +328,7 @@ def test_cfg5_full_model_against_the_reference_golden(built):
     assert abs(loss.item() - t("full_loss").item()) < 2e-2 * abs(t("full_loss").item()) + 1e-2
     params = dict(gen.named_parameters())
     checked = 0
-    for k in G.files:
+    for k in G:
         if not k.startswith("full_g_"):
             continue
         name, ref = k[len("full_g_"):], t(k)

@@ -4,9 +4,9 @@
 cd "$(dirname "$0")/.." || exit 1
 ROOT=$PWD; OUT=$ROOT/gpurun_out; mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py --steps 30 --warmup 5 > $OUT/r03_trainstep_bench.json 2> $OUT/r03_trainstep_bench.err || exit 1
+python bench.py --steps 30 --warmup 5 --full > $OUT/r03_trainstep_bench.json 2> $OUT/r03_trainstep_bench.err || exit 1
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --marks > /dev/null 2> $OUT/r03_trainstep_marks.txt || exit 1
-(cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/r03_prof -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/r03_prof.log 2>&1) || exit 1
+(cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/r03_prof -- python3 $ROOT/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/r03_prof.log 2>&1) || exit 1
 python tools/prof_summary.py $OUT/r03_prof 25 50 --csv $OUT/r03_trainstep_kernel_stats.csv > $OUT/r03_trainstep_summary.txt 2>&1
 python tools/timeline.py $OUT/r03_prof >> $OUT/r03_trainstep_summary.txt 2>&1
 rm -rf $OUT/r03_prof
@@ -17,7 +17,7 @@ done
 python tools/decoder_pmc.py --parse $OUT/r03_pmc_f $OUT/r03_pmc_w $OUT/r03_pmc_s > $OUT/r03_decoder_pmc.json 2> $OUT/r03_decoder_pmc.err
 rm -rf $OUT/r03_pmc_f $OUT/r03_pmc_w $OUT/r03_pmc_s
 for wl in cfg3 cfg4 cfg5; do
-  python bench.py --workload $wl --steps 20 --warmup 5 --no-cpu-baseline > $OUT/r03_${wl}_bench.json 2> $OUT/r03_${wl}_bench.err || echo "$wl failed"
+  python bench.py --workload $wl --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/r03_${wl}_bench.json 2> $OUT/r03_${wl}_bench.err || echo "$wl failed"
 done
 python bench.py --workload cfg5 --steps 10 --warmup 3 --no-cpu-baseline --marks > /dev/null 2> $OUT/r03_cfg5_marks.txt
 echo done
