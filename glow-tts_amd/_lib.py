@@ -67,6 +67,7 @@ PROTOTYPES = {
     "gt_attn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                             c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_u32, c_void_p, c_void_p]),
     "gt_attn_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gt_attn_mfma_shape": (c_int, [c_int, c_int, c_int]),
     "gt_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                             c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                             c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_u32, c_void_p, c_void_p]),
@@ -98,6 +99,7 @@ PROTOTYPES = {
                                 c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "gt_wn_stack_fwd": (c_int, [c_void_p, c_void_p]),
     "gt_wn_stack_rows_per_workgroup": (c_int, [c_int]),
+    "gt_wn_stack_row_blocks": (c_int, [c_int, c_int, c_int]),
     "gt_cond_affine_grads": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gt_wn_stack_bwd": (c_int, [c_void_p, c_void_p]),
     "gt_wn_boundary_fwd": (c_int, [c_void_p, c_void_p]),

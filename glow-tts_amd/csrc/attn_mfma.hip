@@ -911,12 +911,16 @@ size_t gt_attn_bwd_mfma_ws_bytes(int B, int T, int H)
   return (size_t)2 * B * H * T * TI * 2;
 }
 
+// The shapes the MFMA kernels take, in both directions (the generic kernels of encoder_ops.hip take the rest): the one predicate both
+// dispatchers below use, exported so that a caller can tell which kernels a launch runs.
+extern "C" int gt_attn_mfma_shape(int T, int Dh, int win) { return Dh == D && win == WIN && T <= 384; }
+
 int gt_attn_bwd_mfma_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
                           const int32_t* lens, const void* dout, int lddo, const float* P, void* ws, size_t ws_bytes,
                           void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
                           int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
 {
-  if (Dh != D || win != WIN || T > 384 || (ld & 7) || (lddo & 7) || (lddq & 3)) return 1;
+  if (!gt_attn_mfma_shape(T, Dh, win) || (ld & 7) || (lddo & 7) || (lddq & 3)) return 1;
   if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)ws) & 15) return 1;
   if (ws_bytes < gt_attn_bwd_mfma_ws_bytes(B, T, H)) return 1;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -939,7 +943,7 @@ int gt_attn_fwd_mfma_impl(const void* q, const void* k, const void* v, int ld, c
                           const int32_t* lens, void* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win,
                           uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
 {
-  if (Dh != D || win != WIN || T > 384 || (ld & 7) || (ldo & 3)) return 1;
+  if (!gt_attn_mfma_shape(T, Dh, win) || (ld & 7) || (ldo & 3)) return 1;
   if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return 1;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bf16_t* qq = static_cast<const bf16_t*>(q); const bf16_t* kk = static_cast<const bf16_t*>(k); const bf16_t* vv = static_cast<const bf16_t*>(v);

@@ -875,6 +875,7 @@ static int stack_row_blocks(int R, int n_layers, bool fwd = false)
   return (own1 >= 8 && (R + own2 - 1) / own2 <= (fwd ? WNS_SMALL_TILE_MAX_WGS_FWD : WNS_SMALL_TILE_MAX_WGS)) ? 1 : 2;
 }
 extern "C" int gt_wn_stack_rows_per_workgroup(int n_layers) { return BM - 4 * (n_layers - 1); }
+extern "C" int gt_wn_stack_row_blocks(int R, int n_layers, int fwd) { return stack_row_blocks(R, n_layers, fwd != 0); }
 
 extern "C" int gt_wn_stack_fwd(const gt_wn_stack_fwd_args* args, void* stream)
 {

@@ -300,11 +300,15 @@ int gt_param_partials_reduce(const gt_partials_args* args, void* stream);
  *   out_i = sum_j dropout(softmax)[i,j] v_j + sum_{|j-i|<=win} dropout(softmax)[i,j] Ev[j-i+win].
  * q,k,v,out: bf16 rows [B*Tp, H*D]; Ek,Ev: [2*win+1, D] fp32 shared by heads; P: [B,H,T,T] fp32
  * (softmax before dropout, kept for the backward); workspace: gt_attn_bwd_workspace_bytes(B,T,H) bytes of
- * scratch, 16-byte aligned; dEk/dEv ACCUMULATE.  D = 96, win = 4, T <= 256 run on bf16 MFMA. */
+ * scratch, 16-byte aligned; dEk/dEv ACCUMULATE.  D = 96, win = 4, T <= 384 run on bf16 MFMA (gt_attn_mfma_shape), the rest
+ * on the generic kernels. */
 int gt_attn_fwd(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
                 const int32_t* lens, void* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, int D, int win,
                 float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream);
 size_t gt_attn_bwd_workspace_bytes(int B, int T, int H);
+/* 1 if gt_attn_fwd / gt_attn_bwd run a (T, D, win) shape on the MFMA kernels, 0 if on the generic ones (the dispatchers' own test;
+ * operands laid out as the rows layout leaves them) */
+int gt_attn_mfma_shape(int T, int D, int win);
 int gt_attn_bwd(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
                 const int32_t* lens, const void* dout, int lddo, const float* P, void* workspace, size_t workspace_bytes,
                 void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
@@ -449,6 +453,8 @@ typedef struct gt_wn_stack_fwd_args {
 int gt_cond_affine_grads(const void* dpre0, const void* dpre1, const void* dpre2, const void* dpre3, int lddp, const float* sig,
                          float* dw, float* db, int R, int H, int n_layers, void* stream);
 int gt_wn_stack_rows_per_workgroup(int n_layers);
+/* 32-row (1) or 64-row (2) blocks per tile that gt_wn_stack_fwd (fwd = 1) / gt_wn_stack_bwd (fwd = 0) choose for R rows */
+int gt_wn_stack_row_blocks(int R, int n_layers, int fwd);
 int gt_wn_stack_fwd(const gt_wn_stack_fwd_args* args, void* stream);
 /* gt_wn_stack_bwd: the data-gradient chain of the same WaveNet in one launch (what n_layers - 1 calls of gt_wn_layer_bwd, the
  * bottom call without a second stage and gt_gate_bwd for the top layer compute; bit-identical):

@@ -123,21 +123,30 @@ def invconv_fwd(P, pre, x, x_mask, n_split=4):
     return z, logdet
 
 
+def _drop(drop, key, x):
+    """Dropout site `key` (the reference nn.Dropout's module path, ':', call ordinal): x * drop[key] (keep * 1/(1-p),
+    oracle/dropmask.py), or x itself with drop=None (eval mode).  A missing key is an error, never a silent no-op."""
+    if drop is None:
+        return x
+    return x * drop[key]
+
+
 def gate(a, b, n):
     """commons.fused_add_tanh_sigmoid_multiply (commons.py:61-68)"""
     s = a + b
     return torch.tanh(s[:, :n]) * torch.sigmoid(s[:, n:])
 
 
-def wn_fwd(P, pre, x, x_mask, g=None, n_layers=4, hidden=192, kernel_size=5, dilation_rate=1):
-    """modules.WN.forward (modules.py:144-171), eval mode (dropout off)."""
+def wn_fwd(P, pre, x, x_mask, g=None, n_layers=4, hidden=192, kernel_size=5, dilation_rate=1, drop=None):
+    """modules.WN.forward (modules.py:144-171); eval mode (dropout off), or train mode with drop=: self.drop on the
+    in_layer output, before the conditioning g_l is added (modules.py:152-156)."""
     output = torch.zeros_like(x)
     if g is not None:
         g = conv1d(P, pre + "cond_layer", g)
     for i in range(n_layers):
         d = dilation_rate ** i
         pad = int((kernel_size * d - d) / 2)
-        x_in = conv1d(P, pre + f"in_layers.{i}", x, padding=pad, dilation=d)
+        x_in = _drop(drop, pre + f"drop:{i}", conv1d(P, pre + f"in_layers.{i}", x, padding=pad, dilation=d))
         g_l = g[:, i * 2 * hidden:(i + 1) * 2 * hidden] if g is not None else torch.zeros_like(x_in)
         acts = gate(x_in, g_l, hidden)
         rs = conv1d(P, pre + f"res_skip_layers.{i}", acts)
@@ -149,9 +158,10 @@ def wn_fwd(P, pre, x, x_mask, g=None, n_layers=4, hidden=192, kernel_size=5, dil
     return output * x_mask
 
 
-def wnp_fwd(P, pre, x, x_mask, g1=None, n_layers=4, hidden=192, kernel_size=5, dilation_rate=1, n_sqz=2):
+def wnp_fwd(P, pre, x, x_mask, g1=None, n_layers=4, hidden=192, kernel_size=5, dilation_rate=1, n_sqz=2, drop=None):
     """modules.WNP.forward (modules.py:316-343) + WNP.squeeze (modules.py:353-362), eval mode: the identity when the
-    contour g1 [b,1,t_unsqueezed] is None; else WN's loop with per-frame conditioning cond_layer1(g1), squeezed."""
+    contour g1 [b,1,t_unsqueezed] is None; else WN's loop with per-frame conditioning cond_layer1(g1), squeezed.
+    drop=: train mode, self.drop before g_l1 is added (modules.py:332-333)."""
     if g1 is None:
         return x
     g = conv1d(P, pre + "cond_layer1", g1)
@@ -162,7 +172,7 @@ def wnp_fwd(P, pre, x, x_mask, g1=None, n_layers=4, hidden=192, kernel_size=5, d
     for i in range(n_layers):
         d = dilation_rate ** i
         pad = int((kernel_size * d - d) / 2)
-        x_in = conv1d(P, pre + f"in_layers.{i}", x, padding=pad, dilation=d)
+        x_in = _drop(drop, pre + f"drop:{i}", conv1d(P, pre + f"in_layers.{i}", x, padding=pad, dilation=d))
         acts = gate(x_in, g[:, i * 2 * hidden:(i + 1) * 2 * hidden], hidden)
         rs = conv1d(P, pre + f"res_skip_layers.{i}", acts)
         if i < n_layers - 1:
@@ -173,22 +183,22 @@ def wnp_fwd(P, pre, x, x_mask, g1=None, n_layers=4, hidden=192, kernel_size=5, d
     return output * x_mask
 
 
-def _coupling_net(P, pre, x0, x_mask, g, pitch, energy, n_layers, hidden, kernel_size):
+def _coupling_net(P, pre, x0, x_mask, g, pitch, energy, n_layers, hidden, kernel_size, drop=None):
     """start -> wn -> wn_energy -> wn_pitch -> end (attentions.py:144-155)"""
     h = conv1d(P, pre + "start", x0) * x_mask
-    h = wn_fwd(P, pre + "wn.", h, x_mask, g, n_layers, hidden, kernel_size)
-    h = wnp_fwd(P, pre + "wn_energy.", h, x_mask, energy, n_layers, hidden, kernel_size)
-    h = wnp_fwd(P, pre + "wn_pitch.", h, x_mask, pitch, n_layers, hidden, kernel_size)
+    h = wn_fwd(P, pre + "wn.", h, x_mask, g, n_layers, hidden, kernel_size, drop=drop)
+    h = wnp_fwd(P, pre + "wn_energy.", h, x_mask, energy, n_layers, hidden, kernel_size, drop=drop)
+    h = wnp_fwd(P, pre + "wn_pitch.", h, x_mask, pitch, n_layers, hidden, kernel_size, drop=drop)
     return conv1d(P, pre + "end", h)
 
 
 def coupling_fwd(P, pre, x, x_mask, g=None, n_layers=4, hidden=192, kernel_size=5, sigmoid_scale=False,
-                 pitch=None, energy=None):
+                 pitch=None, energy=None, drop=None):
     """attentions.CouplingBlock.forward (attentions.py:132-186); with pitch=energy=None
     wn_energy / wn_pitch return their input (modules.WNP.forward, modules.py:323-324)."""
     c = x.shape[1]
     x0, x1 = x[:, :c // 2], x[:, c // 2:]
-    out = _coupling_net(P, pre, x0, x_mask, g, pitch, energy, n_layers, hidden, kernel_size)
+    out = _coupling_net(P, pre, x0, x_mask, g, pitch, energy, n_layers, hidden, kernel_size, drop)
     m, logs = out[:, :c // 2], out[:, c // 2:]
     if sigmoid_scale:
         logs = torch.log(1e-6 + torch.sigmoid(logs + 2))
@@ -198,16 +208,16 @@ def coupling_fwd(P, pre, x, x_mask, g=None, n_layers=4, hidden=192, kernel_size=
 
 
 def decoder_fwd(P, pre, x, x_mask, g=None, n_blocks=12, n_layers=4, hidden=192, kernel_size=5,
-                n_split=4, n_sqz=2, sigmoid_scale=False, pitch=None, energy=None):
+                n_split=4, n_sqz=2, sigmoid_scale=False, pitch=None, energy=None, drop=None):
     """models.FlowSpecDecoder.forward (models.py:765-785), reverse=False.  pitch / energy: [b,1,t] contours at the
-    un-squeezed frame rate (cfg 5) or None."""
+    un-squeezed frame rate (cfg 5) or None.  drop=: train-mode masks of every WaveNet (oracle/dropmask.py)."""
     x, m = squeeze(x, x_mask, n_sqz)
     logdet_tot = 0
     for b in range(n_blocks):
         x, ld = actnorm_fwd(P, pre + f"flows.{3 * b}.", x, m); logdet_tot = logdet_tot + ld
         x, ld = invconv_fwd(P, pre + f"flows.{3 * b + 1}.", x, m, n_split); logdet_tot = logdet_tot + ld
         x, ld = coupling_fwd(P, pre + f"flows.{3 * b + 2}.", x, m, g, n_layers, hidden, kernel_size, sigmoid_scale,
-                             pitch, energy)
+                             pitch, energy, drop)
         logdet_tot = logdet_tot + ld
     x, _ = unsqueeze(x, m, n_sqz)
     return x, logdet_tot
@@ -264,10 +274,12 @@ def generate_path(duration, mask):
 
 
 # ----------------------------------------------------------------------------- text encoder
-def mha_fwd(P, pre, x, c, attn_mask, n_heads=2, window_size=4):
-    """attentions.MultiHeadAttention.forward/attention (attentions.py:231-272), eval mode, restated
+def mha_fwd(P, pre, x, c, attn_mask, n_heads=2, window_size=4, drop=None):
+    """attentions.MultiHeadAttention.forward/attention (attentions.py:231-272), restated
     with the 9-diagonal band the pad/reshape skew of :292-336 amounts to:
-    scores[i,j] += q_i . E_k[j-i+w] / sqrt(d),  out_i += sum_j p[i,j] E_v[j-i+w]  for |j-i| <= w."""
+    scores[i,j] += q_i . E_k[j-i+w] / sqrt(d),  out_i += sum_j p[i,j] E_v[j-i+w]  for |j-i| <= w.
+    Eval mode, or train mode with drop=: the DROPPED p_attn feeds both matmul(p_attn, v) and the relative-value term, and
+    is what the function returns (attentions.py:265-272)."""
     q = conv1d(P, pre + "conv_q", x)
     k = conv1d(P, pre + "conv_k", c)
     v = conv1d(P, pre + "conv_v", c)
@@ -288,7 +300,7 @@ def mha_fwd(P, pre, x, c, attn_mask, n_heads=2, window_size=4):
         bias = torch.gather(qe, 3, relc[None, None].expand(b, n_heads, t, t)) * band
         scores = scores + bias / math.sqrt(dk)
     scores = scores.masked_fill(attn_mask == 0, -1e4)
-    p = F.softmax(scores, dim=-1)
+    p = _drop(drop, pre + "drop:0", F.softmax(scores, dim=-1))
     out = torch.matmul(p, v)
     if window_size is not None:
         pw = torch.zeros(b, n_heads, t, 2 * window_size + 1, dtype=p.dtype)
@@ -298,42 +310,45 @@ def mha_fwd(P, pre, x, c, attn_mask, n_heads=2, window_size=4):
     return conv1d(P, pre + "conv_o", out), p
 
 
-def ffn_fwd(P, pre, x, x_mask, kernel_size=3):
-    """attentions.FFN.forward (attentions.py:364-372), relu, eval mode."""
+def ffn_fwd(P, pre, x, x_mask, kernel_size=3, drop=None):
+    """attentions.FFN.forward (attentions.py:364-372), relu; eval mode, or drop= after the ReLU (:370)."""
     x = conv1d(P, pre + "conv_1", x * x_mask, padding=kernel_size // 2)
-    x = torch.relu(x)
+    x = _drop(drop, pre + "drop:0", torch.relu(x))
     x = conv1d(P, pre + "conv_2", x * x_mask, padding=kernel_size // 2)
     return x * x_mask
 
 
-def encoder_fwd(P, pre, x, x_mask, g=None, n_layers=6, n_heads=2, window_size=4, kernel_size=3):
-    """attentions.Encoder.forward (attentions.py:56-86), eval mode."""
+def encoder_fwd(P, pre, x, x_mask, g=None, n_layers=6, n_heads=2, window_size=4, kernel_size=3, drop=None):
+    """attentions.Encoder.forward (attentions.py:56-86); eval mode, or drop=: self.drop on the attention output (call 2i,
+    :79) and on the FFN output (call 2i+1, :83), plus the attention's and the FFN's own sites."""
     attn_mask = x_mask.unsqueeze(2) * x_mask.unsqueeze(-1)
     x = x * x_mask
     for i in range(n_layers):
         if i == 3 - 1 and g is not None:
             x = x + F.linear(g.transpose(2, 1), P[pre + "cond_g.weight"], P[pre + "cond_g.bias"]).transpose(2, 1)
-        y, _ = mha_fwd(P, pre + f"attn_layers.{i}.", x, x, attn_mask, n_heads, window_size)
+        y, _ = mha_fwd(P, pre + f"attn_layers.{i}.", x, x, attn_mask, n_heads, window_size, drop)
+        y = _drop(drop, pre + f"drop:{2 * i}", y)
         x = layer_norm_c(x + y, P[pre + f"norm_layers_1.{i}.gamma"], P[pre + f"norm_layers_1.{i}.beta"])
-        y = ffn_fwd(P, pre + f"ffn_layers.{i}.", x, x_mask, kernel_size)
+        y = _drop(drop, pre + f"drop:{2 * i + 1}", ffn_fwd(P, pre + f"ffn_layers.{i}.", x, x_mask, kernel_size, drop))
         x = layer_norm_c(x + y, P[pre + f"norm_layers_2.{i}.gamma"], P[pre + f"norm_layers_2.{i}.beta"])
     return x * x_mask
 
 
-def conv_relu_norm_fwd(P, pre, x, x_mask, n_layers=3, kernel_size=5):
-    """modules.ConvReluNorm.forward (modules.py:95-102), eval mode."""
+def conv_relu_norm_fwd(P, pre, x, x_mask, n_layers=3, kernel_size=5, drop=None):
+    """modules.ConvReluNorm.forward (modules.py:95-102); eval mode, or drop= after the ReLU (relu_drop, modules.py:86-88)."""
     x_org = x
     for i in range(n_layers):
         x = conv1d(P, pre + f"conv_layers.{i}", x * x_mask, padding=kernel_size // 2)
         x = layer_norm_c(x, P[pre + f"norm_layers.{i}.gamma"], P[pre + f"norm_layers.{i}.beta"])
-        x = torch.relu(x)
+        x = _drop(drop, pre + f"relu_drop.1:{i}", torch.relu(x))
     x = x_org + conv1d(P, pre + "proj", x)
     return x * x_mask
 
 
 def text_encoder_fwd(P, pre, ids, x_lengths, g=None, hidden=192, n_layers=6, n_heads=2, window_size=4,
-                     kernel_size=3, prenet=True, mean_only=True, l=None):
-    """models.TextEncoder.forward (models.py:692-716), eval mode.  l [b, lin, 1]: language vector concatenated to every
+                     kernel_size=3, prenet=True, mean_only=True, l=None, drop=None):
+    """models.TextEncoder.forward (models.py:692-716); eval mode, or train mode with drop= (the prenet's and the encoder's
+    sites, oracle/dropmask.py).  l [b, lin, 1]: language vector concatenated to every
     position of the (lin channels narrower) token embedding (models.py:698-699)."""
     x = F.embedding(ids, P[pre + "emb.weight"]) * math.sqrt(hidden)
     if l is not None:
@@ -341,25 +356,25 @@ def text_encoder_fwd(P, pre, ids, x_lengths, g=None, hidden=192, n_layers=6, n_h
     x = x.transpose(1, -1)
     x_mask = sequence_mask(x_lengths, x.size(2)).unsqueeze(1).to(x.dtype)
     if prenet:
-        x = conv_relu_norm_fwd(P, pre + "pre.", x, x_mask)
-    x = encoder_fwd(P, pre + "encoder.", x, x_mask, g, n_layers, n_heads, window_size, kernel_size)
+        x = conv_relu_norm_fwd(P, pre + "pre.", x, x_mask, drop=drop)
+    x = encoder_fwd(P, pre + "encoder.", x, x_mask, g, n_layers, n_heads, window_size, kernel_size, drop)
     x_m = conv1d(P, pre + "proj_m", x) * x_mask
     x_logs = conv1d(P, pre + "proj_s", x) * x_mask if not mean_only else torch.zeros_like(x_m)
     return x, x_m, x_logs, x_mask
 
 
-def duration_predictor_fwd(P, pre, x, x_mask, kernel_size=3, g=None, l=None):
+def duration_predictor_fwd(P, pre, x, x_mask, kernel_size=3, g=None, l=None, drop=None):
     """models.DurationPredictor.forward (models.py:585-612), l=emo=None, eval mode; g [b,gin,1] is detached and
-    added through the 1x1 `cond` conv (models.py:587-589)."""
+    added through the 1x1 `cond` conv (models.py:587-589).  drop=: self.drop after norm_1 / norm_2 (models.py:606,610)."""
     x = x.detach()
     if g is not None:
         x = x + conv1d(P, pre + "cond", g.detach())
     if l is not None:                                     # models.py:595-597
         x = x + conv1d(P, pre + "cond_lang", l.detach())
     x = conv1d(P, pre + "conv_1", x * x_mask, padding=kernel_size // 2)
-    x = layer_norm_c(torch.relu(x), P[pre + "norm_1.gamma"], P[pre + "norm_1.beta"])
+    x = _drop(drop, pre + "drop:0", layer_norm_c(torch.relu(x), P[pre + "norm_1.gamma"], P[pre + "norm_1.beta"]))
     x = conv1d(P, pre + "conv_2", x * x_mask, padding=kernel_size // 2)
-    x = layer_norm_c(torch.relu(x), P[pre + "norm_2.gamma"], P[pre + "norm_2.beta"])
+    x = _drop(drop, pre + "drop:1", layer_norm_c(torch.relu(x), P[pre + "norm_2.gamma"], P[pre + "norm_2.beta"]))
     x = conv1d(P, pre + "proj", x * x_mask)
     return x * x_mask
 
@@ -370,8 +385,9 @@ def layer_norm2(x, gamma, beta, eps=1e-5):
     return F.layer_norm(x.transpose(1, -1), (x.shape[1],), gamma, beta, eps).transpose(1, -1)
 
 
-def dds_conv(P, pre, x, x_mask, g=None, kernel_size=3, num_layers=3):
-    """modules.DilatedDepthSeparableConv.forward (modules.py:718-735), eval mode (dropout off)."""
+def dds_conv(P, pre, x, x_mask, g=None, kernel_size=3, num_layers=3, drop=None):
+    """modules.DilatedDepthSeparableConv.forward (modules.py:718-735); eval mode (dropout off), or drop= after the second
+    GELU (modules.py:733)."""
     if g is not None:
         x = x + g
     for i in range(num_layers):
@@ -382,7 +398,7 @@ def dds_conv(P, pre, x, x_mask, g=None, kernel_size=3, num_layers=3):
         y = F.gelu(layer_norm2(y, P[pre + f"norms_1.{i}.gamma"], P[pre + f"norms_1.{i}.beta"]))
         y = F.conv1d(y, P[pre + f"convs_1x1.{i}.weight"], P[pre + f"convs_1x1.{i}.bias"])
         y = F.gelu(layer_norm2(y, P[pre + f"norms_2.{i}.gamma"], P[pre + f"norms_2.{i}.beta"]))
-        x = x + y
+        x = x + _drop(drop, pre + f"dropout:{i}", y)
     return x * x_mask
 
 
@@ -593,7 +609,7 @@ def contour_norm(c, y_max):
     return n.unsqueeze(1)
 
 
-def train_forward(P, ids, x_lengths, y, y_lengths, maximum_path, hp, g=None, pitch=None, energy=None, l=None):
+def train_forward(P, ids, x_lengths, y, y_lengths, maximum_path, hp, g=None, pitch=None, energy=None, l=None, drop=None):
     """The upstream-equivalent live sub-graph of models.FlowGenerator.forward
     (models.py:1050-1119) for the base configs (the fork's FlowGenerator does not
     construct for them): TextEncoder -> FlowSpecDecoder -> logp -> MAS -> duration loss
@@ -602,11 +618,12 @@ def train_forward(P, ids, x_lengths, y, y_lengths, maximum_path, hp, g=None, pit
     g [b,gin,1]: the speaker vector of the multi-speaker configs as it reaches the encoder / duration predictor /
     decoder (models.py:1046,1075,1090).  pitch / energy: raw contours [b,1,t_y] of cfg 5 into the decoder's WNPs (their
     predictor losses, SURVEY §8 f1, are not part of this sub-graph).  l [b, lin, 1]: the language vector emb_l(lang id)
-    (models.py:1011-1012) into the text encoder and the duration predictor."""
+    (models.py:1011-1012) into the text encoder and the duration predictor.  drop=: train-mode masks of every dropout site
+    ("encoder.…", "decoder.…", "encoder.proj_w.…"; oracle/dropmask.py)."""
     n_sqz = hp.get("n_sqz", 2)
     x, x_m, x_logs, x_mask = text_encoder_fwd(P, "encoder.", ids, x_lengths, g, hp["hidden_channels"],
                                               hp["n_layers_enc"], hp["n_heads"], hp["window_size"],
-                                              hp["kernel_size"], hp["prenet"], hp["mean_only"], l=l)
+                                              hp["kernel_size"], hp["prenet"], hp["mean_only"], l=l, drop=drop)
     y_max = (y.size(2) // n_sqz) * n_sqz                                     # models.py:1248-1253
     y = y[:, :, :y_max]
     y_lengths = (y_lengths // n_sqz) * n_sqz
@@ -614,13 +631,13 @@ def train_forward(P, ids, x_lengths, y, y_lengths, maximum_path, hp, g=None, pit
     attn_mask = x_mask.unsqueeze(-1) * z_mask.unsqueeze(2)
     z, logdet = decoder_fwd(P, "decoder.", y, z_mask, g, hp["n_blocks_dec"], hp["n_block_layers"],
                             hp["hidden_channels"], hp["kernel_size_dec"], 4, n_sqz,
-                            pitch=contour_norm(pitch, y_max), energy=contour_norm(energy, y_max))
+                            pitch=contour_norm(pitch, y_max), energy=contour_norm(energy, y_max), drop=drop)
     with torch.no_grad():
         logp = logp_lattice(x_m, x_logs, z)
         attn = maximum_path(logp, attn_mask.squeeze(1)).unsqueeze(1).detach()
     w = attn.squeeze(1).sum(2).unsqueeze(1)
     logw_ = torch.log(w + 1e-8) * x_mask
-    logw = duration_predictor_fwd(P, "encoder.proj_w.", x, x_mask, hp["kernel_size"], g, l)
+    logw = duration_predictor_fwd(P, "encoder.proj_w.", x, x_mask, hp["kernel_size"], g, l, drop)
     l_length = torch.sum((logw - logw_) ** 2, [1, 2]) / torch.sum(x_mask)
     z_m = torch.matmul(attn.squeeze(1).transpose(1, 2), x_m.transpose(1, 2)).transpose(1, 2)
     z_logs = torch.matmul(attn.squeeze(1).transpose(1, 2), x_logs.transpose(1, 2)).transpose(1, 2)
