@@ -57,8 +57,10 @@ constexpr int RING = WNS_RING;
 #define WNS_PHASES 0                          // dev: per-phase shader-clock stamps of wave 0 (tools/wn_stack_phases.py), 0 in every build that ships
 #endif
 #if WNS_PHASES
-__device__ unsigned long long g_wns_ph[1024 * 48];
-#define PH(i) do { if (threadIdx.x == 0 && blockIdx.x < 1024) g_wns_ph[blockIdx.x * 48 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+// [1024 workgroups][48] of wave 0, then (8-wave backward only) the same of wave 4, its SIMD partner
+__device__ unsigned long long g_wns_ph[2 * 1024 * 48];
+#define PH(i) do { if ((threadIdx.x == 0 || threadIdx.x == 256) && blockIdx.x < 1024)                                                \
+                     g_wns_ph[((threadIdx.x >> 8) * 1024 + blockIdx.x) * 48 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define PH(i) do { } while (0)
 #endif
@@ -493,10 +495,19 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
 // gradient of in_layer_j on the d pre_j tile -> dX_j (+ the residual-path gradient dX_{j+1}, * mask), and below it the
 // residual 1x1's data gradient + skip-path gradient + gate backward -> d pre_{j-1}.  The first conv reads an exact 68-row
 // tile, each of the other n-1 loses 2 rows per side: the workgroup owns the same 64 - 4 (n-1) rows as the forward.
-//   stage 1: N = 192, K = 5 * 384: 2 (column halves) x 2 (K halves) waves x 64 rows, partial sums exchanged through LDS
-//   stage 2: N = 192, K = 192 on the dX tile: 2 x 2 waves x (32 rows x 96 columns)
+//   stage 1: N = 192, K = 5 * 384: 12 accumulation streams (6 blocks of 32 columns x 2 K parities, all rows of the tile), 3 per SIMD;
+//            the partial sums of the two parities are exchanged through LDS
+//   stage 2: N = 192, K = 192 on the dX tile: per SIMD (row half, column half) = 32 rows x 96 columns
+// 512 threads, 8 waves, two per SIMD (the LDS tiles allow one workgroup per CU).  Waves w and w + 4 (SIMD partners in practice)
+// split their SIMD's 3 column blocks 2 + 1: wave w takes blocks 0, 1 of the SIMD's column half, wave w + 4 block 2, both on the same
+// K parity, so one LDS operand read feeds 2 blocks and every weight fragment is still fetched ONCE per workgroup (a row-block split
+// would fetch each fragment twice: the L2 -> VGPR weight stream costs as much vector-memory issue as the MFMAs, wn_layer.hip).  Every
+// output element is the same MFMA chain in the same order as with 4 waves (and as the per-layer kernels): bit-identical results.
+// Each wave then fits in 256 VGPR + AGPR; with one wave per SIMD nothing hid the exchange, the epilogues or the copy loops.  Measured at
+// cfg 2's rows (tools/wn_layer_bench.py stack, back to back): 88.1 -> 74.5-75.2 us per launch; in the step 90.0 -> 74.4 us.
+constexpr int BWD_THREADS = 512;
 constexpr int DP = 2 * H + 8;                 // d pre tile pitch (halfs): 784 B = 16 mod 128
-constexpr int EX_BYTES = 4 * 3 * 16 * 64 * 4; // partial-sum exchange [4 waves][3 blocks][16][64 lanes] fp32: aliases the d pre tile
+constexpr int EX_BYTES = 4 * 3 * 16 * 64 * 4; // partial-sum exchange [4 SIMDs][3 blocks][16][64 lanes] fp32: aliases the d pre tile
 constexpr int BWD_DT = XR * DP * 2;           // 53 312 B
 static_assert(EX_BYTES <= BWD_DT, "the exchange buffer lives in the d pre tile");
 constexpr int SBWD_LDS = BWD_DT + 4 * BM * AP * 2;       // d pre tile | dX tile | skip-gradient, tanh, sigmoid staging tiles = 155 712 B
@@ -521,54 +532,66 @@ __device__ __forceinline__ void gate_bwd4(const float (&dd)[4], const float (&t)
   pt = pack4(gt[0], gt[1], gt[2], gt[3]); ps = pack4(gs[0], gs[1], gs[2], gs[3]);
 }
 
-constexpr int RB = 2 * RING - 1;               // backward ring: half the fragments per step, twice the depth for the same registers
+#ifndef WNS_RB
+#define WNS_RB (2 * WNS_RING - 1)
+#endif
+constexpr int RB = WNS_RB;                     // backward ring depth (64-row form)
 constexpr int B_NS = 2 * H / 64, B_NIT = B_NS * TAPS, B_KS = 2 * H / 16, B_NBT = H / 32;  // 6 slices, 30 steps, 24 k-steps per tap, 6 blocks
 
-// step `it` of a data-gradient conv's weight stream: this wave's column half (wn) and K half (wk)
-__device__ __forceinline__ void bwd_w_load(const bf16_t* W1, int it, int wn, int wk, int lane, uint4 (&dst)[2][3])
+// NB column blocks per wave: 2 (waves 0-3, blocks 0 and 1 of the SIMD's column half) or 1 (waves 4-7, block 2)
+template <int NB> constexpr int bwd_b0() { return NB == 2 ? 0 : 2; }
+
+// step `it` of a data-gradient conv's weight stream: this SIMD's column half (wn) and K parity (wk), this wave's NB blocks
+template <int NB>
+__device__ __forceinline__ void bwd_w_load(const bf16_t* W1, int it, int wn, int wk, int lane, uint4 (&dst)[2][NB])
 {
   const int slice = it / TAPS, tap = it - slice * TAPS;
-  const bf16_t* Wt = pinned(W1 + (size_t)((tap * B_NBT + 3 * wn) * B_KS + slice * 4 + 2 * wk) * 512);
+  const bf16_t* Wt = pinned(W1 + (size_t)((tap * B_NBT + 3 * wn + bwd_b0<NB>()) * B_KS + slice * 4 + 2 * wk) * 512);
 #pragma unroll
   for (int k2 = 0; k2 < 2; ++k2)
 #pragma unroll
-    for (int bn = 0; bn < 3; ++bn) dst[k2][bn] = ldfrag(Wt, bn * B_KS + k2, lane);
+    for (int bn = 0; bn < NB; ++bn) dst[k2][bn] = ldfrag(Wt, bn * B_KS + k2, lane);
 }
 // the first RB - 1 steps: issued by the PREVIOUS step (or the kernel's head) ahead of its stores — vmcnt retires in order, so a
 // wait for these fragments would otherwise also wait for every store issued before them (see the forward kernel)
-template <int RBv>
-__device__ __forceinline__ void bwd_ring_prologue(const void* w, int lane, uint4 (&ring)[RBv][2][3])
+template <int RBv, int NB>
+__device__ __forceinline__ void bwd_ring_prologue(const void* w, int lane, uint4 (&ring)[RBv][2][NB])
 {
-  const int wave = wave_scalar(), wn = wave & 1, wk = wave >> 1;
+  const int simd = wave_scalar() & 3, wn = simd & 1, wk = simd >> 1;
   const bf16_t* W1 = pinned(static_cast<const bf16_t*>(w));
 #pragma unroll
-  for (int p = 0; p < RBv - 1; ++p) bwd_w_load(W1, p, wn, wk, lane, ring[p]);
+  for (int p = 0; p < RBv - 1; ++p) bwd_w_load<NB>(W1, p, wn, wk, lane, ring[p]);
 }
 
 // one step j of the chain (compile-time j: every pointer is a kernel argument, every fragment address is formed where it is used)
-template <int J, bool COND, bool DROP, int NBM>
+template <int J, bool COND, bool DROP, int NBM, int NB>
 __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t drop_thresh, float drop_scale, uint32_t seed_x,
-                                         bf16_t* Dt, float* Ex, bf16_t* At, int s0, int halo, int lane, int wave,
-                                         uint4 (&ring)[NBM == 1 ? WNS_RB1 : RB][2][3], float rm)
+                                         bf16_t* Dt, float* Ex, bf16_t* At, int s0, int halo,
+                                         uint4 (&ring)[NBM == 1 ? WNS_RB1 : RB][2][NB], float rm)
 {
-  const int r = lane & 31, h = lane >> 5;
-  wave = wave_scalar();
-  const int wn = wave & 1, wk = wave >> 1;     // stage 1: column half, K half;  afterwards wk doubles as the row half
+  // the thread index as a value formed HERE (see the forward's tid_e): formed once for the kernel, the per-lane addresses derived
+  // from it are carried (spilled) from step to step
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63, r = lane & 31, h = lane >> 5;
+  const int simd = wave_scalar() & 3;
+  const int wn = simd & 1, wk = simd >> 1;     // stage 1: column half, K parity;  afterwards wk doubles as the row half
+  constexpr int B0 = bwd_b0<NB>();             // this wave's first block of the column half
   constexpr int BMv = 32 * NBM;                // rows of the tile (NBM: see the forward kernel)
   constexpr int RBv = NBM == 1 ? WNS_RB1 : RB;
-  const bool act = wk < NBM;                   // NBM = 1: one row block — the waves of K half 1 hand their sums over and sit the rest out
+  const bool act = wk < NBM;                   // NBM = 1: one row block — the waves of K parity 1 hand their sums over and sit the rest out
   const int n_layers = a.n_layers, R = a.R;
   const bf16_t* via = static_cast<const bf16_t*>(a.via_skip);
   constexpr int NIT = B_NIT;
   const bf16_t* W1 = pinned(static_cast<const bf16_t*>(a.w_in_d[J]));
-  f32x16_t acc[3][NBM];
+  f32x16_t acc[NB][NBM];
 #pragma unroll
-  for (int bn = 0; bn < 3; ++bn)
+  for (int bn = 0; bn < NB; ++bn)
 #pragma unroll
     for (int bm = 0; bm < NBM; ++bm)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[bn][bm][e] = 0.0f;
-  auto w_load = [&](int it, uint4 (&dst)[2][3]) { bwd_w_load(W1, it, wn, wk, lane, dst); };
+  auto w_load = [&](int it, uint4 (&dst)[2][NB]) { bwd_w_load<NB>(W1, it, wn, wk, lane, dst); };
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int slice = it / TAPS, tap = it - slice * TAPS;
@@ -581,7 +604,7 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
 #pragma unroll
       for (int bm = 0; bm < NBM; ++bm) bx[bm] = *reinterpret_cast<const bf16x8_t*>(xsb + 32 * bm * DP + k2 * 16);
 #pragma unroll
-      for (int bn = 0; bn < 3; ++bn)
+      for (int bn = 0; bn < NB; ++bn)
 #pragma unroll
         for (int bm = 0; bm < NBM; ++bm)
           acc[bn][bm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(asfrag(ring[it % RBv][k2][bn]), bx[bm], acc[bn][bm], 0, 0, 0);
@@ -589,28 +612,33 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
     __builtin_amdgcn_sched_barrier(0);
   }
   PH(2 + 8 * (3 - J));
-  // second-stage weights (the layer below): this wave's 96 columns (wn), rows 32*wk
+  // second-stage weights (the layer below): this wave's NB blocks of the SIMD's 96 columns (wn), rows 32*wk
   constexpr int JL = J > 0 ? J - 1 : 0;
   const bf16_t* W2 = pinned(static_cast<const bf16_t*>(a.w_res_d[JL]));
-  uint4 ring2[KK2][3];                         // all of them now: reloaded inside the 36-MFMA loop they arrived after it needed them
-  if (J > 0 && act) {
+  // All of them before the stage-2 loop (reloaded inside it they arrived after it needed them): the first half now, the second once
+  // the stage-1 accumulators are dead (all at once, next to those and the gate operands below, they spill)
+  uint4 ring2[KK2][NB];
+  auto w2_load = [&](int k0, int k1) {
+    if (J > 0 && act) {
 #pragma unroll
-    for (int kk = 0; kk < KK2; ++kk)
+      for (int kk = k0; kk < k1; ++kk)
 #pragma unroll
-      for (int bn = 0; bn < 3; ++bn) ring2[kk][bn] = ldfrag(W2, (3 * wn + bn) * KK2 + kk, lane);
-  }
+        for (int bn = 0; bn < NB; ++bn) ring2[kk][bn] = ldfrag(W2, (3 * wn + B0 + bn) * KK2 + kk, lane);
+    }
+  };
+  w2_load(0, KK2 / 2);
   // the gate backward's three row operands (skip-path gradient, saved tanh, saved sigmoid of layer j-1, all 64 rows of the tile) are
   // fetched as whole rows — read in the MFMA layout, every load instruction touched 16 bytes in each of 32 rows — and handed to the
   // epilogue through LDS; they are issued here, ahead of this step's stores
   constexpr int JLp = J > 0 ? J - 1 : 0;
-  constexpr int NPRE = (BM * CPR + 255) / 256;                       // 6 chunks per thread and operand
+  constexpr int NPRE = (BM * CPR + BWD_THREADS - 1) / BWD_THREADS;   // 3 chunks per thread and operand
   uint4 pre[3][NPRE];
   if (J > 0) {
     const bf16_t* Tg = static_cast<const bf16_t*>(a.gate_t[JLp]);
     const bf16_t* Sg = static_cast<const bf16_t*>(a.gate_s[JLp]);
 #pragma unroll
     for (int i = 0; i < NPRE; ++i) {
-      const int idx = threadIdx.x + 256 * i, row = idx / CPR, c8 = idx - row * CPR, mm = s0 + row;
+      const int idx = tid + BWD_THREADS * i, row = idx / CPR, c8 = idx - row * CPR, mm = s0 + row;
       pre[0][i] = pre[1][i] = pre[2][i] = make_uint4(0, 0, 0, 0);
       if (row < BMv && mm >= 0 && mm < R) {
         pre[0][i] = *reinterpret_cast<const uint4*>(via + (size_t)mm * a.ldvs + JLp * H + c8 * 8);
@@ -621,33 +649,34 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
   }
   WNS_BARRIER();                            // every wave is done with the d pre tile: the exchange buffer may overwrite it
 
-  // K halves meet: a wave keeps row block bm == wk and hands the other one to its partner (same columns, other K half)
+  // K parities meet: a wave keeps row block bm == wk and hands the other one to the wave of the same blocks and the other parity
   if (NBM == 2 || wk) {
-    float* mine = Ex + wave * (3 * 16 * 64);
+    float* mine = Ex + (simd * 3 + B0) * (16 * 64);
 #pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
+    for (int bn = 0; bn < NB; ++bn)
 #pragma unroll
       for (int e = 0; e < 16; ++e) mine[(bn * 16 + e) * 64 + lane] = (NBM == 2 && !wk) ? acc[bn][NBM - 1][e] : acc[bn][0][e];
   }
   WNS_BARRIER();
-  f32x16_t sum[3];
+  f32x16_t sum[NB];
   if (act) {
-    const float* theirs = Ex + (wave ^ 2) * (3 * 16 * 64);
+    const float* theirs = Ex + ((simd ^ 2) * 3 + B0) * (16 * 64);
 #pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
+    for (int bn = 0; bn < NB; ++bn)
 #pragma unroll
       for (int e = 0; e < 16; ++e) sum[bn][e] = ((NBM == 2 && wk) ? acc[bn][NBM - 1][e] : acc[bn][0][e]) + theirs[(bn * 16 + e) * 64 + lane];
   }
+  w2_load(KK2 / 2, KK2);
   PH(3 + 8 * (3 - J));
   // dX_j = (conv^T(d pre_j) + dX_{j+1}) * mask -> HBM (owned rows) and the stage-2 tile (which still holds dX_{j+1})
   const int t = 32 * wk + r, m = s0 + t;
   const bool mine_row = act && t >= halo && t < BMv - halo && m < R;
   if (act) {
 #pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
+    for (int bn = 0; bn < NB; ++bn)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
+        const int n = 32 * (3 * wn + B0 + bn) + 8 * g + 4 * h;
         float ad[4] = {};
         if (J < n_layers - 1) unpack4(*reinterpret_cast<const uint2*>(At + t * AP + n), ad);
         const uint2 v = pack4((sum[bn][4 * g] + ad[0]) * rm, (sum[bn][4 * g + 1] + ad[1]) * rm,
@@ -661,17 +690,17 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
     // dX_j of the owned rows leaves as whole rows from the finished tile (the MFMA layout gives a store 16 bytes in each of 32 rows)
     bf16_t* dx = static_cast<bf16_t*>(a.dx[J]);
     const int own = BMv - 2 * halo;
-    constexpr int NC = (BM * CPR + 255) / 256;
+    constexpr int NC = (BM * CPR + BWD_THREADS - 1) / BWD_THREADS;
     uint4 vx[NC];
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
-      const int idx = threadIdx.x + 256 * i, row = idx / CPR, c8 = idx - row * CPR;
+      const int idx = tid + BWD_THREADS * i, row = idx / CPR, c8 = idx - row * CPR;
       vx[i] = make_uint4(0, 0, 0, 0);
       if (idx < own * CPR) vx[i] = *reinterpret_cast<const uint4*>(At + (halo + row) * AP + c8 * 8);
     }
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
-      const int idx = threadIdx.x + 256 * i, row = idx / CPR, c8 = idx - row * CPR, mm = s0 + halo + row;
+      const int idx = tid + BWD_THREADS * i, row = idx / CPR, c8 = idx - row * CPR, mm = s0 + halo + row;
       if (idx < own * CPR && mm < R) *reinterpret_cast<uint4*>(dx + (size_t)mm * H + c8 * 8) = vx[i];
     }
   };
@@ -679,9 +708,9 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
 
   // d acts_{j-1} = dX_j W_res + skip-path gradient -> gate backward -> d pre_{j-1}: the next tile (+ HBM for the owned rows)
   bf16_t* Vl = At + BM * AP; bf16_t* Tl = Vl + BM * AP; bf16_t* Sl = Tl + BM * AP;
-  f32x16_t acc2[3];
+  f32x16_t acc2[NB];
 #pragma unroll
-  for (int bn = 0; bn < 3; ++bn)
+  for (int bn = 0; bn < NB; ++bn)
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc2[bn][e] = 0.0f;
   if (act) {
@@ -690,17 +719,17 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
     for (int kk = 0; kk < KK2; ++kk) {
       const bf16x8_t bfm = *reinterpret_cast<const bf16x8_t*>(ab + kk * 16);
 #pragma unroll
-      for (int bn = 0; bn < 3; ++bn) {
+      for (int bn = 0; bn < NB; ++bn) {
         acc2[bn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(asfrag(ring2[kk][bn]), bfm, acc2[bn], 0, 0, 0);
       }
     }
   }
   PH(5 + 8 * (3 - J));
-  bwd_ring_prologue(a.w_in_d[JL], lane, ring);                      // the next step's first fragments, then this step's stores
+  bwd_ring_prologue<RBv, NB>(a.w_in_d[JL], lane, ring);            // the next step's first fragments, then this step's stores
   store_dx();                                                       // (the dX tile stays as it is until the next step's epilogue)
 #pragma unroll
   for (int i = 0; i < NPRE; ++i) {
-    const int idx = threadIdx.x + 256 * i, row = idx / CPR, c8 = idx - row * CPR;
+    const int idx = tid + BWD_THREADS * i, row = idx / CPR, c8 = idx - row * CPR;
     if (row >= BMv) continue;
     *reinterpret_cast<uint4*>(Vl + row * AP + c8 * 8) = pre[0][i];
     *reinterpret_cast<uint4*>(Tl + row * AP + c8 * 8) = pre[1][i];
@@ -713,10 +742,10 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
     const uint32_t seed = (a.drop_seed + (uint32_t)JL) ^ seed_x;
     const bool in = m >= 0 && m < R;
 #pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
+    for (int bn = 0; bn < NB; ++bn)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
+        const int n = 32 * (3 * wn + B0 + bn) + 8 * g + 4 * h;
         uint2 pt = make_uint2(0, 0), ps = pt, ct = pt, cs = pt;
         if (in) {
           float vs[4], tt[4], sg[4], dd[4];
@@ -742,19 +771,19 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
     // d pre_{j-1} of the owned rows: whole 768-byte rows from the tile (read-only until the next step's exchange, which follows a barrier)
     bf16_t* dpre = static_cast<bf16_t*>(a.dpre[JL]);
     const int own = BMv - 2 * halo;
-    constexpr int CPR2 = 2 * H / 8, NC = (BM * CPR2 + 255) / 256, NP = 4;      // 12 chunks per thread, in passes of NP
+    constexpr int CPR2 = 2 * H / 8, NC = (BM * CPR2 + BWD_THREADS - 1) / BWD_THREADS, NP = 3;   // 6 chunks per thread, in passes of NP
 #pragma unroll
     for (int i0 = 0; i0 < NC; i0 += NP) {
       uint4 vx[NP];
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
-        const int idx = threadIdx.x + 256 * (i0 + i), row = idx / CPR2, c8 = idx - row * CPR2;
+        const int idx = tid + BWD_THREADS * (i0 + i), row = idx / CPR2, c8 = idx - row * CPR2;
         vx[i] = make_uint4(0, 0, 0, 0);
         if (idx < own * CPR2) vx[i] = *reinterpret_cast<const uint4*>(Dt + (halo + row + 2) * DP + c8 * 8);
       }
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
-        const int idx = threadIdx.x + 256 * (i0 + i), row = idx / CPR2, c8 = idx - row * CPR2, mm = s0 + halo + row;
+        const int idx = tid + BWD_THREADS * (i0 + i), row = idx / CPR2, c8 = idx - row * CPR2, mm = s0 + halo + row;
         if (idx < own * CPR2 && mm < R) *reinterpret_cast<uint4*>(dpre + (size_t)mm * 2 * H + c8 * 8) = vx[i];
       }
     }
@@ -762,14 +791,15 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
   PH(9 + 8 * (3 - J));
 }
 
-template <bool COND, bool DROP, int NBM>
-__global__ __launch_bounds__(256) void gt_wn_stack_bwd_kernel(gt_wn_stack_bwd_args a, uint32_t drop_thresh, float drop_scale)
+// the whole launch as one wave sees it: NB (2 or 1) column blocks per stage (see the section's header)
+template <bool COND, bool DROP, int NBM, int NB>
+__device__ __forceinline__ void bwd_wave(const gt_wn_stack_bwd_args& a, uint32_t drop_thresh, float drop_scale)
 {
   constexpr int BMv = 32 * NBM, XRv = BMv + TAPS - 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   PH(0);
   const uint32_t seed_x = a.seed_dev ? *a.seed_dev : 0u;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, simd = (threadIdx.x >> 6) & 3;
   const int n_layers = a.n_layers, R = a.R;
   const int halo = 2 * (n_layers - 1), own = BMv - 2 * halo;
   const int s0 = blockIdx.x * own - halo;
@@ -778,11 +808,11 @@ __global__ __launch_bounds__(256) void gt_wn_stack_bwd_kernel(gt_wn_stack_bwd_ar
   bf16_t* At = reinterpret_cast<bf16_t*>(smem + BWD_DT);
   const bf16_t* via = static_cast<const bf16_t*>(a.via_skip);
   constexpr int RBv = NBM == 1 ? WNS_RB1 : RB;
-  uint4 ring[RBv][2][3];
-  bwd_ring_prologue(pick(a.w_in_d, n_layers - 1), lane, ring);      // ahead of the head's d pre stores
+  uint4 ring[RBv][2][NB];
+  bwd_ring_prologue<RBv, NB>(pick(a.w_in_d, n_layers - 1), lane, ring);   // ahead of the head's d pre stores
   float rm;                                                         // the row mask of the row this lane finishes in every dX epilogue
   {
-    const int m = s0 + 32 * (wave >> 1) + (lane & 31);
+    const int m = s0 + 32 * (simd >> 1) + (lane & 31);
     rm = (m >= 0 && m < R) ? a.rowmask[m] : 0.0f;
   }
 
@@ -796,11 +826,11 @@ __global__ __launch_bounds__(256) void gt_wn_stack_bwd_kernel(gt_wn_stack_bwd_ar
     bf16_t* dpre = static_cast<bf16_t*>(pick(a.dpre, L));
     bf16_t* dpre_c = static_cast<bf16_t*>(pick(a.dpre_c, L));
     const uint32_t seed = (a.drop_seed + (uint32_t)L) ^ seed_x;
-    constexpr int NH = (XR * CPR + 255) / 256;                       // 7 chunks of 8 channels per thread
+    constexpr int NH = (XR * CPR + BWD_THREADS - 1) / BWD_THREADS;   // 4 chunks of 8 channels per thread
     uint4 hv[3][NH];
 #pragma unroll
     for (int i = 0; i < NH; ++i) {
-      const int idx = threadIdx.x + 256 * i, u = idx / CPR, c8 = idx - u * CPR, m = s0 - 2 + u;
+      const int idx = threadIdx.x + BWD_THREADS * i, u = idx / CPR, c8 = idx - u * CPR, m = s0 - 2 + u;
       hv[0][i] = hv[1][i] = hv[2][i] = make_uint4(0, 0, 0, 0);
       if (u < XRv && m >= 0 && m < R) {
         hv[0][i] = *reinterpret_cast<const uint4*>(via + (size_t)m * a.ldvs + L * H + c8 * 8);
@@ -810,7 +840,7 @@ __global__ __launch_bounds__(256) void gt_wn_stack_bwd_kernel(gt_wn_stack_bwd_ar
     }
 #pragma unroll
     for (int i = 0; i < NH; ++i) {
-      const int idx = threadIdx.x + 256 * i, u = idx / CPR, c8 = idx - u * CPR, m = s0 - 2 + u, n = c8 * 8;
+      const int idx = threadIdx.x + BWD_THREADS * i, u = idx / CPR, c8 = idx - u * CPR, m = s0 - 2 + u, n = c8 * 8;
       if (u >= XRv) continue;
       uint2 pt[2], ps[2], ct[2], cs[2];
       pt[0] = pt[1] = ps[0] = ps[1] = ct[0] = ct[1] = cs[0] = cs[1] = make_uint2(0, 0);
@@ -839,11 +869,20 @@ __global__ __launch_bounds__(256) void gt_wn_stack_bwd_kernel(gt_wn_stack_bwd_ar
   WNS_BARRIER();
   PH(1);
   // the chain, top to bottom (workgroup-uniform branches; each step is its own straight-line code)
-  if (n_layers > 3) bwd_step<3, COND, DROP, NBM>(a, drop_thresh, drop_scale, seed_x, Dt, Ex, At, s0, halo, lane, wave, ring, rm);
-  if (n_layers > 2) bwd_step<2, COND, DROP, NBM>(a, drop_thresh, drop_scale, seed_x, Dt, Ex, At, s0, halo, lane, wave, ring, rm);
-  if (n_layers > 1) bwd_step<1, COND, DROP, NBM>(a, drop_thresh, drop_scale, seed_x, Dt, Ex, At, s0, halo, lane, wave, ring, rm);
-  bwd_step<0, COND, DROP, NBM>(a, drop_thresh, drop_scale, seed_x, Dt, Ex, At, s0, halo, lane, wave, ring, rm);
+  if (n_layers > 3) bwd_step<3, COND, DROP, NBM, NB>(a, drop_thresh, drop_scale, seed_x, Dt, Ex, At, s0, halo, ring, rm);
+  if (n_layers > 2) bwd_step<2, COND, DROP, NBM, NB>(a, drop_thresh, drop_scale, seed_x, Dt, Ex, At, s0, halo, ring, rm);
+  if (n_layers > 1) bwd_step<1, COND, DROP, NBM, NB>(a, drop_thresh, drop_scale, seed_x, Dt, Ex, At, s0, halo, ring, rm);
+  bwd_step<0, COND, DROP, NBM, NB>(a, drop_thresh, drop_scale, seed_x, Dt, Ex, At, s0, halo, ring, rm);
   PH(40);
+}
+
+// Both halves run the same sequence of barriers; the branch is on a wave-uniform scalar.  A static s_setprio 1 for waves 4-7 (the
+// arbitration losers of an 8-wave workgroup) measured slower: 78.5 against 74.5 us per launch back to back at cfg 2's rows.
+template <bool COND, bool DROP, int NBM>
+__global__ __launch_bounds__(BWD_THREADS) void gt_wn_stack_bwd_kernel(gt_wn_stack_bwd_args a, uint32_t drop_thresh, float drop_scale)
+{
+  if (wave_scalar() < 4) bwd_wave<COND, DROP, NBM, 2>(a, drop_thresh, drop_scale);
+  else bwd_wave<COND, DROP, NBM, 1>(a, drop_thresh, drop_scale);
 }
 
 inline bool al16(const void* p) { return !((uintptr_t)p & 15); }
@@ -858,7 +897,8 @@ extern "C" int gt_dev_wns_phases(void* dst, size_t bytes)
 #endif
 
 #ifndef WNS_SMALL_TILE_MAX_WGS
-#define WNS_SMALL_TILE_MAX_WGS 80             // 64-row tiles give at most this many workgroups -> 32-row tiles (needs n_layers <= 4: 20 owned rows)
+#define WNS_SMALL_TILE_MAX_WGS 80             // 64-row tiles give at most this many workgroups -> 32-row tiles (needs n_layers <= 4: 20 owned rows);
+                                              // re-checked with the 8-wave backward: 98 gives cfg 4 4.29 vs 4.31 ms, cfg 5 15.09 vs 13.74 ms
 #endif
 // 32-row blocks per tile for a launch over R rows: 2, or 1 when the 64-row tiling would leave two thirds of the 256 CUs idle.  Measured
 // back to back (tools/wn_layer_bench.py stack, WN_BENCH_TY=..., round 3; forward / backward us per launch, 64-row -> 32-row tiles):
@@ -962,7 +1002,7 @@ extern "C" int gt_wn_stack_bwd(const gt_wn_stack_bwd_args* args, void* stream)
   }
   const int nbm = stack_row_blocks(a.R, a.n_layers);
   const int own = 32 * nbm - 4 * (a.n_layers - 1);
-  const dim3 grid((a.R + own - 1) / own), block(256);
+  const dim3 grid((a.R + own - 1) / own), block(BWD_THREADS);
   hipLaunchKernelGGL(kerns[(nbm == 1 ? 4 : 0) + (cond ? 2 : 0) + (thresh ? 1 : 0)], grid, block, SBWD_LDS, static_cast<hipStream_t>(stream), a, thresh, scale);
   return gt_launch_status(__func__);
 }

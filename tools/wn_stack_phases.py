@@ -1,4 +1,5 @@
-"""dev: where a WaveNet stack launch spends its time — shader-clock stamps of wave 0 of every workgroup (a -DWNS_PHASES=1 build of
+"""dev: where a WaveNet stack launch spends its time — shader-clock stamps of wave 0 (and, in the 8-wave backward, of wave 4, its
+SIMD partner) of every workgroup (a -DWNS_PHASES=1 build of
 csrc/wn_stack.hip made by tools/exp_variant.py), median over workgroups, in cycles and as a share of the launch.
 
     python tools/exp_variant.py ph wn_stack -DWNS_PHASES=1
@@ -27,16 +28,16 @@ via_all = (torch.randn(R, n * H, device=dev) * rc.rowmask[:, None] * 0.1).to(tor
 nwg = (R + 51) // 52
 
 
-def phases(label, names):
+def phases(label, names, half=0):
     torch.cuda.synchronize()
-    buf = np.zeros(1024 * 48, dtype=np.uint64)
+    buf = np.zeros(2 * 1024 * 48, dtype=np.uint64)
     assert raw.gt_dev_wns_phases(buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)) == 0
-    ph = buf.reshape(1024, 48)[:nwg].astype(np.int64)
+    ph = buf.reshape(2, 1024, 48)[half, :nwg].astype(np.int64)
     idx = [i for i, _ in names]
     t = ph[:, idx] - ph[:, [0]]
     med = np.median(t, axis=0)
     total = med[-1]
-    print(f"-- {label}: {nwg} workgroups, launch = {total:.0f} cycles of wave 0 (median); start skew p5..p95 = "
+    print(f"-- {label}: {nwg} workgroups, launch = {total:.0f} cycles of wave {4 * half} (median); start skew p5..p95 = "
           f"{np.percentile(ph[:, 0] - ph[:, 0].min(), [5, 95])}")
     prev = 0.0
     for (i, nm), m in zip(names, med):
@@ -62,9 +63,10 @@ for _ in range(3):
 bn = [(1, "head: top-layer gate backward on 68 rows + barrier")]
 for J in (3, 2, 1, 0):
     b = 8 * (3 - J)
-    bn += [(2 + b, f"J{J} conv^T loop (180 MFMA / wave)"), (3 + b, f"J{J} barrier, K-half exchange through LDS, sum"), (4 + b, f"J{J} dX epilogue -> tile, barrier")]
+    bn += [(2 + b, f"J{J} conv^T loop (240 | 120 MFMA, wave 0 | 4)"), (3 + b, f"J{J} barrier, K-parity exchange through LDS, sum"), (4 + b, f"J{J} dX epilogue -> tile, barrier")]
     if J > 0:
-        bn += [(5 + b, f"J{J} residual 1x1^T (36 MFMA / wave)"), (6 + b, f"J{J} next ring, dX stores, operands -> LDS, barrier"),
+        bn += [(5 + b, f"J{J} residual 1x1^T (24 | 12 MFMA)"), (6 + b, f"J{J} next ring, dX stores, operands -> LDS, barrier"),
                (7 + b, f"J{J} gate backward epilogue"), (8 + b, f"J{J} barrier"), (9 + b, f"J{J} d pre stores issued")]
 bn += [(40, "dX_0 stores issued, end")]
-phases("backward", bn)
+phases("backward, wave 0", bn)
+phases("backward, wave 4", bn, half=1)
