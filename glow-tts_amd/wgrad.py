@@ -129,6 +129,14 @@ def choose_slabs(base_tiles, R, part_bytes):
     return min(S for cost, S in costs if cost <= 1.05 * best)
 
 
+def single_slabs(R, Cin, Cout, taps):
+    """Row slabs of the single-conv weight gradient (gt_conv_wgrad_bf16, flow_impl.conv_param_grads outside a queue) for R rows."""
+    import ctypes
+    S = ctypes.c_int(0)
+    _lib.lib().gt_conv_wgrad_workspace_bytes(R, Cin, Cout, taps, ctypes.byref(S))
+    return S.value
+
+
 def _side_stream(dev):
     key = str(dev)
     if key not in _SIDE:
@@ -216,6 +224,17 @@ class WgradQueue:
         if db is not None:
             out[conv.bias] = db
         self.params_done.extend(out.keys())
+        return out
+
+    def slab_plan(self):
+        """[(S, slab_rows)] per queued conv, in queue order: how many row slabs of how many rows the next flush splits each conv's
+        rows into (every dY piece of a conv gets the same split)."""
+        jobs, _, wnbs, *_ = self._plan()
+        i_s, i_rows = WNB.names.index("S"), JOB.names.index("slab_rows")
+        out, j = [], 0
+        for item, w in zip(self.items, wnbs):
+            out.append((int(w[i_s]), int(jobs[j][i_rows])))
+            j += len(item[2])
         return out
 
     def add_ln(self, partials, dst_a, dst_b):
