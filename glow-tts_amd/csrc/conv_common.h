@@ -19,7 +19,7 @@ struct ConvArgs {
   uint32_t drop_thresh, drop_seed; float drop_scale;   // gate dropout (modules.py:153)
   uint32_t gb_thresh;                                  // gatebwd: dropout threshold replayed on the gradient
   const uint32_t* seed_dev;                            // optional device word XOR-ed into drop_seed (graph replay)
-  int exp_;                                            // EXPERIMENT bits (dev only)
+  int reserved_;                                       // always 0; stays: dropping it regroups the scalar argument loads and re-allocates every kernel of conv_gemm.hip
   int y16;                                             // Y rows allow 16-byte bf16 stores (ldy % 8 == 0, base 16-B aligned)
   int maskbwd;                                         // epilogue = ReLU / dropout backward: Tout is the SAVED activation, Y = acc * scale where it is non-zero
   int gatebwd;                                         // epilogue = WaveNet-gate backward: Tout/Sout are the SAVED tanh/sigmoid, Y = d pre [R, 2N]

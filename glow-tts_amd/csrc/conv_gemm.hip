@@ -20,9 +20,10 @@
 // (conflict-free ds_read_b128 for 16 distinct rows), weights and activations double-buffered
 // in LDS with register prefetch (global loads of step i+1 fly under the MFMAs of step i), one
 // barrier per (K-slice, tap) step, 2 workgroups per CU.
-#include <stdlib.h>
 #include "common.h"
 #include "conv_common.h"
+#include "internal.h"
+#include "mfma_frag.h"
 #include "../../include/glowtts_hip.h"
 
 namespace {
@@ -31,7 +32,6 @@ using gtconv::ConvArgs;
 constexpr int BK = 64;
 constexpr int LDP = 72;                       // halfs per LDS row (64 + 8 pad)
 constexpr int MAXTAPS = 5;
-
 
 // BM x BN tile: 128 x {128|64} (2 workgroups per CU), or 256 x 64 (1 per CU): the weight tile is re-streamed from L2
 // once per ROW tile, so for a wide-N, many-tap conv (in_layer: 737 KB of weights) the tall tile halves the L2->LDS
@@ -121,12 +121,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void gt_conv_gemm_kernel(Co
     const int nxt = it + 1;
     const bool has = nxt < NIT;
     const bool newslice = has && (tap == taps - 1);
-#ifdef GT_DEV_EXPERIMENTS
-    const bool ld_ok = !(a.exp_ & 2);
-#else
-    constexpr bool ld_ok = true;
-#endif
-    if (has && ld_ok) { load_W(nxt); if (newslice) load_X(slice + 1); }
+    if (has) { load_W(nxt); if (newslice) load_X(slice + 1); }
 
     const bf16_t* wsb = &Ws[it & 1][(32 * NB * wn + r) * LDP + 8 * h];
     const bf16_t* xsb = &Xs[slice & 1][(mrow0 + r + tap) * LDP + 8 * h];
@@ -144,7 +139,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void gt_conv_gemm_kernel(Co
           acc[bn][bm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[bn], bfm[bm], acc[bn][bm], 0, 0, 0);
     }
 
-    if (has && ld_ok) { store_W(nxt & 1); if (newslice) store_X((slice + 1) & 1); }
+    if (has) { store_W(nxt & 1); if (newslice) store_X((slice + 1) & 1); }
     __syncthreads();
   }
 
@@ -158,19 +153,6 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void gt_conv_gemm_kernel(Co
   // so bias / cond / addend loads and all stores are 16-32 B per lane and whole 128-B lines per row — the MFMA
   // layout itself gives only 8 B per lane with a row stride between lanes.
   float* es = reinterpret_cast<float*>(smem);
-#ifdef GT_DEV_EXPERIMENTS
-  if (a.exp_ & 1) {
-    float sacc = 0.f;
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-#pragma unroll
-      for (int j = 0; j < MB; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sacc += acc[i][j][e];
-    if (sacc == 123.456f) static_cast<bf16_t*>(a.Y)[tid] = 1;
-    return;
-  }
-#endif
 #pragma unroll
   for (int bm = 0; bm < MB; ++bm)
 #pragma unroll
@@ -191,8 +173,6 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void gt_conv_gemm_kernel(Co
 // step then costs one L2 round trip that nothing hides (47 us for the 768 -> 192, k = 3 FFN conv whose MFMAs take 2 us).
 // One stage = the activation slice + the AT weight tiles of that slice, so the same loads are in flight AT at a time and
 // the step count falls to Kp / 64.
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-
 template <int AT>
 __global__ __launch_bounds__(256, AT == 3 ? 2 : 1) void gt_conv_gemm_taps_kernel(ConvArgs a)
 {
@@ -361,9 +341,7 @@ __device__ __forceinline__ size_t pk_index(bool frag, int t, int nrow, int k, in
   return frag ? ((((size_t)t * (Np >> 5) + (nrow >> 5)) * (Kp >> 4) + (k >> 4)) * 64 + (nrow & 31) + 32 * ((k & 15) >> 3)) * 8 + (k & 7)
               : ((size_t)t * Np + nrow) * Kp + k;
 }
-#ifndef PK_THREADS
-#define PK_THREADS 256
-#endif
+constexpr int PK_THREADS = 256;
 constexpr int PK_RPW = 8 / (PK_THREADS / 64);       // rows per wave
 constexpr int PK8_SMALLN = 1024;                    // the row length the small form holds: 16 KB of LDS and 32 row registers instead of
                                                     // 36 KB and 72, twice the resident workgroups (the decoder's convs: 960; 90 % of the step's weights)
@@ -387,9 +365,6 @@ __device__ __forceinline__ void pack_rows8(
     for (int j = 0; j < MAXN / 256; ++j) {
       const int i = lane + 64 * j;
       x[k][j] = make_float4(0.f, 0.f, 0.f, 0.f);
-#ifdef PK_EXP
-      if (PK_EXP & 4) { x[k][j] = make_float4(0.001f * i, 0.5f, 0.25f, 1.f); continue; }
-#endif
       if (i < n4) {
         if (al) x[k][j] = *reinterpret_cast<const float4*>(vr + 4 * i);
         else    x[k][j] = make_float4(vr[4 * i], vr[4 * i + 1], vr[4 * i + 2], vr[4 * i + 3]);
@@ -422,10 +397,6 @@ __device__ __forceinline__ void pack_rows8(
   __syncthreads();
   const bool ffrag = gate & 2, dfrag = gate & 4;
   const int C8 = Cin >> 3;
-#ifdef PK_EXP
-  if (PK_EXP & 1) Pf = nullptr;
-  if (PK_EXP & 2) Pd = nullptr;
-#endif
   if (Pf) {
     for (int q = tid; q < 8 * taps * C8; q += PK_THREADS) {
       // the 8 rows of the group are the fastest index: their 16-byte pieces are neighbours in the packed image (whole 128-byte lines per store)
@@ -519,17 +490,12 @@ extern "C" int gt_conv_gemm_bf16(const void* X, int ldx, const void* Wp, const f
   a.row0 = row0; a.B = B;
   a.out_f32 = out_f32; a.relu = relu;
   a.y16 = !(ldy & 7);
-  a.exp_ = 0;
-#ifdef GT_DEV_EXPERIMENTS                    // tools/conv_exp.py builds its own library with this flag; never in the product build
-  { const char* e = getenv("GT_CONV_EXP"); a.exp_ = e ? atoi(e) : 0; }
-#endif
-  a.drop_thresh = 0; a.drop_seed = drop_seed; a.drop_scale = 1.0f; a.seed_dev = seed_dev;
+  a.reserved_ = 0;
+  a.drop_seed = drop_seed; a.seed_dev = seed_dev;
   a.gatebwd = (gate == 2); a.gb_thresh = 0;
   a.maskbwd = (gate == 3);
-  if (drop_p > 0.0f) {
-    if (drop_p >= 1.0f) return GT_E_UNSUPPORTED;
-    a.drop_thresh = (uint32_t)((double)drop_p * 4294967296.0); a.drop_scale = 1.0f / (1.0f - drop_p);
-  }
+  if (drop_p >= 1.0f) return GT_E_UNSUPPORTED;
+  gt_drop_params(drop_p, &a.drop_thresh, &a.drop_scale);
   if (a.gatebwd) {                            // the dropout belongs to the gate's forward: replay it on the gradient only
     if (!gate_t || !gate_s || out_f32 || relu || (N & 7) || (ldts & 7) || (ldy & 7)) return GT_E_INVAL;
     if (((uintptr_t)gate_t | (uintptr_t)gate_s) & 15) return GT_E_ALIGN;

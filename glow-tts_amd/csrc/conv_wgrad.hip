@@ -14,39 +14,14 @@
 // maps dW to (dv, dg) or to a plain dw in the parameter's own [Cout, Cin, taps] layout.
 #include <stdlib.h>
 #include "common.h"
+#include "mfma_frag.h"
 #include "../../include/glowtts_hip.h"
 
 namespace {
 
-// Per tap count: rows per ring stage (KB), ring depth (NST), input-channel groups of 64 per workgroup tile (NJ).
-// (measured on the decoder's 48 k = 5 jobs of 8.9 k rows, `profiles/r03_wgrad_variants.txt`: 32-row stages x 5 deep 336-355 us, 64-row
-//  stages x 3 deep 310-316 us — half the barriers; reading the fragments of k-step i + 1 ahead of the MFMAs of k-step i changed nothing
-//  with two workgroups per CU and was dropped)
-#ifndef WG5_KB
-#define WG5_KB 64
-#endif
-#ifndef WG5_NST
-#define WG5_NST 3
-#endif
-#ifndef WG3_KB
-#define WG3_KB 64
-#endif
-#ifndef WG3_NST
-#define WG3_NST 3
-#endif
-#ifndef WG1_KB
-#define WG1_KB 32
-#endif
-#ifndef WG1_NST
-#define WG1_NST 3
-#endif
-#ifndef WG1_NJ
-#define WG1_NJ 3
-#endif
 constexpr int SLAB_Q = 64;                    // slab_rows is a multiple of this (host planners), so only a job's LAST slab ends ragged
 
 typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4_t;
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned lds_off(const void* p) { return (unsigned)reinterpret_cast<uintptr_t>(p); }
 
@@ -277,9 +252,13 @@ __device__ __forceinline__ void wgrad_tile(
 }
 
 template <int TAPS> struct WgSel;
-template <> struct WgSel<5> { static constexpr int NJ = 1, KB = WG5_KB, NST = WG5_NST; };
-template <> struct WgSel<3> { static constexpr int NJ = 1, KB = WG3_KB, NST = WG3_NST; };
-template <> struct WgSel<1> { static constexpr int NJ = WG1_NJ, KB = WG1_KB, NST = WG1_NST; };
+// Per tap count: rows per ring stage (KB), ring depth (NST), input-channel groups of 64 per workgroup tile (NJ).
+// (measured on the decoder's 48 k = 5 jobs of 8.9 k rows, `profiles/r03_wgrad_variants.txt`: 32-row stages x 5 deep 336-355 us, 64-row
+//  stages x 3 deep 310-316 us — half the barriers; reading the fragments of k-step i + 1 ahead of the MFMAs of k-step i changed nothing
+//  with two workgroups per CU and was dropped)
+template <> struct WgSel<5> { static constexpr int NJ = 1, KB = 64, NST = 3; };
+template <> struct WgSel<3> { static constexpr int NJ = 1, KB = 64, NST = 3; };
+template <> struct WgSel<1> { static constexpr int NJ = 3, KB = 32, NST = 3; };
 template <int TAPS> using WgGeoT = WgGeo<TAPS, WgSel<TAPS>::NJ, WgSel<TAPS>::KB, WgSel<TAPS>::NST>;
 
 template <int TAPS>

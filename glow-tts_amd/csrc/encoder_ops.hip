@@ -142,9 +142,6 @@ __global__ __launch_bounds__(64 * LNB_WAVES) void gt_layernorm_bwd_kernel(LnBwdA
     float tg = 0.f, tb = 0.f;
 #pragma unroll
     for (int i = 0; i < LNB_WAVES; ++i) { tg += sg[i][c]; tb += sb[i][c]; }
-#ifdef LNB_EXP
-    if (LNB_EXP & 1) { if (tg == 1.2345f) q.dgamma[c] = tb; return; }
-#endif
     if (q.partials) {
       q.partials[(size_t)blockIdx.x * 2 * p.C + c] = tg;
       q.partials[(size_t)blockIdx.x * 2 * p.C + p.C + c] = tb;
@@ -832,12 +829,6 @@ __global__ void gt_duration_loss_bwd_kernel(const float* __restrict__ logw, cons
 #define GT_ST(s) static_cast<hipStream_t>(s)
 #define GT_RET() return gt_launch_status(__func__)
 
-static void fill_drop(float p, uint32_t seed, uint32_t& th, uint32_t& sd, float& sc)
-{
-  th = 0; sd = seed; sc = 1.0f;
-  if (p > 0.f) { th = (uint32_t)((double)p * 4294967296.0); sc = 1.0f / (1.0f - p); }
-}
-
 static int fill_ln(LnArgs& p, const float* a, const void* y, int ldy, const float* gamma, const float* beta, const float* rowmask,
                    float* out_f32, void* out_bf16, int ldo, float* mean, float* rstd, int R, int C, float eps,
                    float p_in, uint32_t seed_in, float p_out, uint32_t seed_out, int relu, const uint32_t* seed_dev)
@@ -847,8 +838,9 @@ static int fill_ln(LnArgs& p, const float* a, const void* y, int ldy, const floa
   p.a = a; p.y = static_cast<const bf16_t*>(y); p.ldy = ldy; p.gamma = gamma; p.beta = beta; p.rowmask = rowmask;
   p.out_f32 = out_f32; p.out_bf16 = static_cast<bf16_t*>(out_bf16); p.ldo = ldo; p.mean = mean; p.rstd = rstd;
   p.R = R; p.C = C; p.eps = eps; p.relu = relu; p.seed_dev = seed_dev;
-  fill_drop(p_in, seed_in, p.din_thresh, p.din_seed, p.din_scale);
-  fill_drop(p_out, seed_out, p.dout_thresh, p.dout_seed, p.dout_scale);
+  p.din_seed = seed_in; p.dout_seed = seed_out;
+  gt_drop_params(p_in, &p.din_thresh, &p.din_scale);
+  gt_drop_params(p_out, &p.dout_thresh, &p.dout_scale);
   return GT_OK;
 }
 
@@ -878,12 +870,6 @@ extern "C" int gt_layernorm_bwd(const float* a, const void* y, int ldy, const fl
   q.da = da; q.dy = static_cast<bf16_t*>(dy); q.lddy = lddy; q.dgamma = dgamma; q.dbeta = dbeta; q.partials = nullptr;
   // geometry: 16 waves x 32 rows per workgroup (the gamma / beta partials are folded in LDS before the atomics) while
   // that still gives >= 64 workgroups; short inputs fall back to 4 waves x 16 rows so the chip is not left idle
-#ifdef LNB_EXP
-  if (LNB_EXP & 2) { q.rows_per_block = 64; hipLaunchKernelGGL(gt_layernorm_bwd_kernel<16>, dim3((R + 63) / 64), dim3(1024), 0, GT_ST(stream), q); GT_RET(); }
-  if (LNB_EXP & 4) { q.rows_per_block = 32; hipLaunchKernelGGL(gt_layernorm_bwd_kernel<8>, dim3((R + 31) / 32), dim3(512), 0, GT_ST(stream), q); GT_RET(); }
-  if (LNB_EXP & 8) { q.rows_per_block = 16; hipLaunchKernelGGL(gt_layernorm_bwd_kernel<4>, dim3((R + 15) / 16), dim3(256), 0, GT_ST(stream), q); GT_RET(); }
-  if (LNB_EXP & 16) { q.rows_per_block = 16; hipLaunchKernelGGL(gt_layernorm_bwd_kernel<16>, dim3((R + 15) / 16), dim3(1024), 0, GT_ST(stream), q); GT_RET(); }
-#endif
   if (R >= 64 * 32) {
     q.rows_per_block = 32;
     hipLaunchKernelGGL(gt_layernorm_bwd_kernel<16>, dim3((R + 31) / 32), dim3(1024), 0, GT_ST(stream), q);
@@ -942,21 +928,19 @@ extern "C" int gt_attn_fwd(const void* q, const void* k, const void* v, int ld, 
 {
   if (!q || !k || !v || !Ek || !Ev || !lens || !out || !P || B <= 0 || T <= 0 || H <= 0) return GT_E_INVAL;
   if (D > AT_MAXD || (D & 1) || win < 0 || drop_p >= 1.f) return GT_E_UNSUPPORTED;
+  uint32_t th; float sc;
+  gt_drop_params(drop_p, &th, &sc);
   {
-    uint32_t th, sd; float sc; fill_drop(drop_p, drop_seed, th, sd, sc);
-    {
-      const int rc = gt_attn_fwd_mfma_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, P, B, T, Tp, row0, H, D, win, th, sd, sc, seed_dev, stream);
-      if (rc != 1) return rc;                      // handled (or failed loudly) on the MFMA path
-    }
+    const int rc = gt_attn_fwd_mfma_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, P, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
+    if (rc != 1) return rc;                        // handled (or failed loudly) on the MFMA path
   }
   const size_t lds = attn_lds(T, D, win, (size_t)4 * D + (size_t)AT_QT * T);
   if (lds > 160 * 1024) return GT_E_UNSUPPORTED;
   static bool attr = false;
   if (!attr) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH; attr = true; }
-  uint32_t th, sd; float sc; fill_drop(drop_p, drop_seed, th, sd, sc);
   hipLaunchKernelGGL(gt_attn_fwd_kernel, dim3((T + AT_QT - 1) / AT_QT, H, B), dim3(256), lds, GT_ST(stream),
                      static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
-                     static_cast<bf16_t*>(out), ldo, P, T, Tp, row0, H, D, win, th, sd, sc, seed_dev);
+                     static_cast<bf16_t*>(out), ldo, P, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev);
   GT_RET();
 }
 
@@ -977,13 +961,12 @@ extern "C" int gt_attn_bwd(const void* q, const void* k, const void* v, int ld, 
   if (D > AT_MAXD || (D & 1) || win < 0 || drop_p >= 1.f) return GT_E_UNSUPPORTED;
   if (workspace_bytes < gt_attn_bwd_workspace_bytes(B, T, H)) return GT_E_INVAL;
   float* dS_ws = static_cast<float*>(workspace);
+  uint32_t th; float sc;
+  gt_drop_params(drop_p, &th, &sc);
   {
-    uint32_t th, sd; float sc; fill_drop(drop_p, drop_seed, th, sd, sc);
-    {
-      const int rc = gt_attn_bwd_mfma_impl(q, k, v, ld, Ek, Ev, lens, dout, lddo, P, workspace, workspace_bytes, dq, dk, dv, lddq,
-                                           dEk, dEv, B, T, Tp, row0, H, D, win, th, sd, sc, seed_dev, stream);
-      if (rc != 1) return rc;
-    }
+    const int rc = gt_attn_bwd_mfma_impl(q, k, v, ld, Ek, Ev, lens, dout, lddo, P, workspace, workspace_bytes, dq, dk, dv, lddq,
+                                         dEk, dEv, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
+    if (rc != 1) return rc;
   }
   const size_t lds1 = attn_lds(T, D, win, (size_t)2 * (2 * win + 1) * D + (size_t)AT_QT * 2 * D + (size_t)AT_QT * T);
   size_t halfs2 = (size_t)T * (D + 2); halfs2 += halfs2 & 1;
@@ -995,15 +978,14 @@ extern "C" int gt_attn_bwd(const void* q, const void* k, const void* v, int ld, 
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_bwd_kv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH;
     attr = true;
   }
-  uint32_t th, sd; float sc; fill_drop(drop_p, drop_seed, th, sd, sc);
   const dim3 grid((T + AT_QT - 1) / AT_QT, H, B);
   hipLaunchKernelGGL(gt_attn_bwd_q_kernel, grid, dim3(256), lds1, GT_ST(stream),
                      static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
                      static_cast<const bf16_t*>(dout), lddo, P, dS_ws, static_cast<bf16_t*>(dq), lddq, dEk, dEv,
-                     T, Tp, row0, H, D, win, th, sd, sc, seed_dev);
+                     T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev);
   hipLaunchKernelGGL(gt_attn_bwd_kv_kernel, grid, dim3(256), lds2, GT_ST(stream),
                      static_cast<const bf16_t*>(q), ld, static_cast<const bf16_t*>(dout), lddo, P, dS_ws, lens,
-                     static_cast<bf16_t*>(dk), static_cast<bf16_t*>(dv), lddq, T, Tp, row0, H, D, th, sd, sc, seed_dev);
+                     static_cast<bf16_t*>(dk), static_cast<bf16_t*>(dv), lddq, T, Tp, row0, H, D, th, drop_seed, sc, seed_dev);
   GT_RET();
 }
 

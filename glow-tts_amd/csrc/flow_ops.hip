@@ -6,6 +6,7 @@
 // All fp32 math; bf16 only where a tensor feeds an MFMA GEMM.
 #include <stdlib.h>
 #include "common.h"
+#include "internal.h"
 #include "../../include/glowtts_hip.h"
 
 namespace {
@@ -608,8 +609,8 @@ extern "C" int gt_gate_bwd(const void* dacts, int ldd, const void* T, const void
                            int R, int half, float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream)
 {
   if (!dacts || !T || !S || !dpre || R <= 0 || (half & 3) || (ldd & 3) || (ldts & 3) || (ldp & 3)) return GT_E_INVAL;
-  uint32_t th = 0; float sc = 1.0f;
-  if (drop_p > 0.f) { th = (uint32_t)((double)drop_p * 4294967296.0); sc = 1.0f / (1.0f - drop_p); }
+  uint32_t th; float sc;
+  gt_drop_params(drop_p, &th, &sc);
   hipLaunchKernelGGL(gt_gate_bwd_kernel, dim3((R * (half / 4) + 255) / 256), dim3(256), 0, GT_ST(stream),
                      static_cast<const bf16_t*>(dacts), ldd, static_cast<const bf16_t*>(T), static_cast<const bf16_t*>(S), ldts,
                      static_cast<bf16_t*>(dpre), ldp, static_cast<bf16_t*>(dpre_cond), R, half, th, drop_seed, sc, seed_dev);

@@ -2,6 +2,17 @@
 #pragma once
 #include <stdint.h>
 
+static inline bool al16(const void* p) { return !((uintptr_t)p & 15); }   // NULL counts as aligned: optional pointers pass
+
+// Dropout probability -> what the kernels take: keep an element when its 32-bit hash >= thresh = p * 2^32 (common.h drop_keep),
+// then scale by 1 / (1 - p); p <= 0 is no dropout (0, 1).  oracle/dropmask.py restates this rule: every kernel must agree with it.
+// p >= 1 is the caller's to refuse.
+static inline void gt_drop_params(float p, uint32_t* thresh, float* scale)
+{
+  *thresh = 0; *scale = 1.0f;
+  if (p > 0.0f) { *thresh = (uint32_t)((double)p * 4294967296.0); *scale = 1.0f / (1.0f - p); }
+}
+
 // MFMA attention forward for the configuration every reference config uses (D = 96, window 4) and
 // T <= 256; returns 1 when the shape is not handled (caller falls back to the generic kernel).
 int gt_attn_fwd_mfma_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,

@@ -86,29 +86,14 @@ __device__ __forceinline__ unsigned lds_off(const void* p) {
 // Wait states (gfx950): VALU write -> DPP read of q needs 2 (v_addc + ds_write sit between);
 // VALU write of vcc -> VALU read as carry needs 2 (v_add + v_max sit between).  The leading
 // s_nop 1 covers a compiler-generated VALU write of q directly in front of the statement.
-#ifndef MAS_DPP
-#define MAS_DPP "wave_shr:1"
-#endif
-#ifdef MAS_DIAG_NODSW
-#define MAS_DSW(O) "s_nop 0\n\t"
-#else
-#define MAS_DSW(O) "ds_write_b32 %[ba], %[q] offset:" O "\n\t"
-#endif
-#ifdef MAS_DIAG_NOBIT
-#define MAS_CMP(P) "s_nop 0\n\t"
-#define MAS_ADDC "s_nop 0\n\t"
-#else
-#define MAS_CMP(P) "v_cmp_lt_f32_e32 vcc, %[q], " P "\n\t"
-#define MAS_ADDC "v_addc_co_u32_e32 %[d], vcc, %[d], %[d], vcc\n\t"
-#endif
 #define MAS_COL(P, V, O)                                                        \
-  "v_mov_b32_dpp " P ", %[q] " MAS_DPP " row_mask:0xf bank_mask:0xf\n\t"       \
+  "v_mov_b32_dpp " P ", %[q] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"        \
   "v_add_f32_e32 %[ta], %[q], " V "\n\t"                                        \
-  MAS_CMP(P)                                                                    \
+  "v_cmp_lt_f32_e32 vcc, %[q], " P "\n\t"                                       \
   "v_add_f32_e32 %[tb], " P ", " V "\n\t"                                       \
   "v_max_f32_e32 %[q], %[ta], %[tb]\n\t"                                        \
-  MAS_ADDC                                                                      \
-  MAS_DSW(O)
+  "v_addc_co_u32_e32 %[d], vcc, %[d], %[d], vcc\n\t"                            \
+  "ds_write_b32 %[ba], %[q] offset:" O "\n\t"
 
 template <int J0>   // J0 = first column of the group inside the chunk (0,4,...,28)
 __device__ __forceinline__ void mas_cols4(float& Q, unsigned& dir, float4& B, const float4& V, unsigned bout_addr)

@@ -14,20 +14,16 @@
 // the 29-row proj of a ConvFlow is an exact-fp32 VALU product fused with the spline (its parameters feed a softmax and a
 // bin search, so they stay fp32).  All statistics, the spline and the likelihood sums are fp32.
 #include "common.h"
+#include "internal.h"
 #include "../../include/glowtts_hip.h"
 
 namespace {
 
 constexpr int PC = 192;                       // channels of every predictor network (filter_channels = in_channels, models.py:223)
 constexpr int NC = PC / 64;                   // channels per lane
-#ifndef DDS_RPW
-#define DDS_RPW 2                             // (cfg 5 step: 16.2 ms at 8 rows per wave, 15.5 at 4, 15.0-15.2 at 2, 15.1 at 1)
-#endif
-constexpr int RPW = DDS_RPW;                  // rows per wave per workgroup (forward kernels)
-#ifndef DDS_RPB
-#define DDS_RPB 2                             // (cfg 5 step, with the partial-row reduce: 18.05 ms at 8 rows per wave, 17.5 at 4; 14.9 at 2 with DDS_RPW 2)
-#endif
-constexpr int RPB = DDS_RPB;                  // ... of the backward kernels that also accumulate parameter gradients
+constexpr int RPW = 2;                        // rows per wave per workgroup (forward kernels); cfg 5 step: 16.2 ms at 8, 15.5 at 4, 15.0-15.2 at 2, 15.1 at 1
+constexpr int RPB = 2;                        // ... of the backward kernels that also accumulate parameter gradients; cfg 5 step, with the
+                                              // partial-row reduce: 18.05 ms at 8, 17.5 at 4, 14.9 at 2 (with RPW = 2)
 
 // parameter-gradient partial of this lane -> ONE atomic per address per workgroup: the four waves' values are folded in LDS
 // first (same-address float atomics serialise at L2, ~25-50 ns each; with one per wave they were most of these kernels)
@@ -835,7 +831,6 @@ __global__ __launch_bounds__(256) void gt_rows_split3_kernel(const void* __restr
 #define GT_RET() return gt_launch_status(__func__)
 inline int wg_rows(int R) { return (R + 4 * RPW - 1) / (4 * RPW); }
 inline int wg_rows_b(int R) { return (R + 4 * RPB - 1) / (4 * RPB); }
-inline void fill_drop(float p, uint32_t& th, float& sc) { th = p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u; sc = p > 0.f ? 1.0f / (1.0f - p) : 1.0f; }
 
 }  // namespace
 
@@ -859,7 +854,7 @@ extern "C" int gt_dds_out_fwd(const float* h2, const float* x, int ldx, const fl
 {
   if (!h2 || !x || !gamma || !beta || !rowmask || !out || R <= 0 || drop_p < 0.f || drop_p >= 1.f) return GT_E_INVAL;
   if (C != PC) return GT_E_UNSUPPORTED;
-  uint32_t th; float sc; fill_drop(drop_p, th, sc);
+  uint32_t th; float sc; gt_drop_params(drop_p, &th, &sc);
   hipLaunchKernelGGL(gt_dds_out_fwd_kernel, dim3(wg_rows(R)), dim3(256), 0, GT_ST(stream), h2, x, ldx, gamma, beta, rowmask, out,
                      static_cast<bf16_t*>(out_bf16), R, eps, th, seed, seed_dev, sc);
   GT_RET();
@@ -871,7 +866,7 @@ extern "C" int gt_dds_out_bwd(const float* h2, const float* dy, const float* gam
 {
   if (!h2 || !dy || !gamma || !beta || !rowmask || !dh2_bf16 || (!partials && (!dgamma || !dbeta)) || R <= 0 || drop_p < 0.f || drop_p >= 1.f) return GT_E_INVAL;
   if (C != PC) return GT_E_UNSUPPORTED;
-  uint32_t th; float sc; fill_drop(drop_p, th, sc);
+  uint32_t th; float sc; gt_drop_params(drop_p, &th, &sc);
   hipLaunchKernelGGL(gt_dds_out_bwd_kernel, dim3(wg_rows_b(R)), dim3(256), 0, GT_ST(stream), h2, dy, gamma, beta, rowmask,
                      static_cast<bf16_t*>(dh2_bf16), dgamma, dbeta, partials, R, eps, th, seed, seed_dev, sc);
   GT_RET();

@@ -23,6 +23,8 @@
 // are row r, column 32 * block + 8g + 4h + j.  What leaves for HBM is what the batched weight gradients and the next
 // pass read anyway (wn_out, y0, d out, d wn_out) plus the fp32 flow state.
 #include "common.h"
+#include "internal.h"
+#include "mfma_frag.h"
 #include "../../include/glowtts_hip.h"
 
 namespace {
@@ -32,20 +34,9 @@ constexpr int BM = 64;
 constexpr int AP = H + 8;                     // bf16 tile pitch (halfs): 400 B = 16 mod 128 -> conflict-free ds_read_b128
 constexpr int XP = 136;                       // y0 tile pitch (halfs): K = 80 -> 5 k-steps; 272 B = 16 mod 128
 constexpr int ZP = C + 4;                     // fp32 tile pitch (floats)
-#ifndef WNB_EXP
-#define WNB_EXP 0                             // dev experiments (bit mask), 0 in every build that ships
-#endif
 constexpr int RD = 8;                         // weight-fragment ring: k-steps in flight per wave
-#ifndef WNB_LDSBAR
-#define WNB_LDSBAR 0                          // 1: barriers wait for LDS traffic only (common.h lds_barrier) instead of __syncthreads()'s
-                                              // vmcnt(0).  Measured (round 3, back to back): 28.3 vs 28.1 us forward, 28.9 vs 28.7 us backward:
-                                              // the drains are not what the phases wait for
-#endif
-#if WNB_LDSBAR
-#define WNB_BARRIER() lds_barrier()
-#else
-#define WNB_BARRIER() __syncthreads()
-#endif
+// Barriers are __syncthreads().  One that waits for LDS traffic only (no vmcnt(0)) measured (round 3, back to back) 28.3 vs 28.1 us
+// forward, 28.9 vs 28.7 us backward: the drains are not what the phases wait for.
 #ifndef WNB_PHASES
 #define WNB_PHASES 0                          // dev: per-phase shader-clock stamps of wave 0 (tools/wn_stack_phases.py), 0 in every build that ships
 #endif
@@ -55,24 +46,6 @@ __device__ unsigned long long g_wnb_ph[1024 * 48];
 #else
 #define PH(i) do { } while (0)
 #endif
-
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));   // plain vector: staging arrays of it stay in registers
-
-__device__ __forceinline__ uint4 ldfrag(const bf16_t* __restrict__ W, int f, int lane)
-{
-  return *reinterpret_cast<const uint4*>(W + ((size_t)f * 64 + lane) * 8);
-}
-__device__ __forceinline__ bf16x8_t asfrag(const uint4& u) { return __builtin_bit_cast(bf16x8_t, u); }
-__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) { return make_uint2(pack2bf(a, b), pack2bf(c, d)); }
-
-template <int NB>
-__device__ __forceinline__ void acc_zero(f32x16_t (&acc)[NB])
-{
-#pragma unroll
-  for (int bn = 0; bn < NB; ++bn)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[bn][e] = 0.0f;
-}
 
 // acc[bn] += W[block nb0 + bn][k-steps 0 .. KK) x Bt: W in fragment order with KS k-steps per block row; Brow points at
 // (this lane's row, 8h) of the bf16 LDS tile, k-step kk is 16 halfs further.  The first ring of fragments is fetched by
@@ -142,7 +115,7 @@ __device__ __forceinline__ void skip_slice(const u32x4_t (&xr)[6], bf16_t* As, c
     const int chunk = threadIdx.x + 256 * i, row = chunk / 24, c8 = chunk - row * 24;
     *reinterpret_cast<u32x4_t*>(As + (L * BM + row) * AP + c8 * 8) = xr[i];
   }
-  WNB_BARRIER();
+  __syncthreads();
   const bf16_t* brow = As + (L * BM + 32 * wm + r) * AP + 8 * h;
   constexpr int CH = 4;
 #pragma unroll
@@ -153,7 +126,7 @@ __device__ __forceinline__ void skip_slice(const u32x4_t (&xr)[6], bf16_t* As, c
 #pragma unroll
       for (int bn = 0; bn < 3; ++bn) acc[bn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(asfrag(ring[(kbase + k2) % RD][bn]), bfm, acc[bn], 0, 0, 0);
     }
-    if (kbase + k0 + RD < KK && !(WNB_EXP & 8)) {
+    if (kbase + k0 + RD < KK) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int k2 = k0; k2 < k0 + CH; ++k2)
@@ -199,10 +172,7 @@ __device__ __forceinline__ void coop_store_rows(bf16_t* __restrict__ dst, int ld
 // on a forward launch, + 9 us on a backward one, all of it gone once the images are back in the cache (tools/wn_layer_bench.py,
 // WN_BENCH_COLD).  A boundary launch runs 152 workgroups on 256 CUs: PF_WGS extra workgroups (blockIdx >= the row tiles) read
 // those images once, on CUs that were idle, and retire within a few microseconds.
-#ifndef WNB_PF_WGS
-#define WNB_PF_WGS 64
-#endif
-constexpr int PF_WGS = WNB_PF_WGS;
+constexpr int PF_WGS = 64;
 __device__ __forceinline__ void prefetch_images(const void* const (&ptr)[16], const uint32_t (&bytes)[16], int wg, uint32_t* sink)
 {
   uint32_t acc = 0;
@@ -268,15 +238,14 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
     const bf16_t* acts = static_cast<const bf16_t*>(a.acts);
     const bf16_t* Wskip = static_cast<const bf16_t*>(a.w_skip);
     // the tile's gated activations, all four layers: 6 x 16 B per thread per layer slice, in flight together
-    u32x4_t xr[NL][6];
+    u32x4_t xr[NL][6];                                      // (plain vector: staging arrays of it stay in registers)
 #pragma unroll
     for (int l = 0; l < NL; ++l)
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
         const int chunk = threadIdx.x + 256 * i, row = chunk / 24, c8 = chunk - row * 24;
         const int gm = m0 + row < R ? m0 + row : R - 1;
-        if (WNB_EXP & 1) xr[l][i] = u32x4_t{(uint32_t)gm, 0u, 0u, 0u};
-        else xr[l][i] = *reinterpret_cast<const u32x4_t*>(acts + (size_t)gm * a.ldacts + l * H + c8 * 8);
+        xr[l][i] = *reinterpret_cast<const u32x4_t*>(acts + (size_t)gm * a.ldacts + l * H + c8 * 8);
       }
     if (threadIdx.x < BM) rowsum[threadIdx.x] = 0.0f;
     // skip GEMM: wn_out = (acts @ Wskip^T + b) * mask;  wave (wm, wn): rows 32 wm .., column blocks 3 wn ..
@@ -289,12 +258,10 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
 #pragma unroll
       for (int bn = 0; bn < 3; ++bn) ring[p][bn] = ldfrag(Wskip, (3 * wn + bn) * KK + p, lane);
     PH(1);
-    if (!(WNB_EXP & 2)) {
     skip_slice<0>(xr[0], As, Wskip, wm, wn, r, h, lane, ring, acc);
     skip_slice<1>(xr[1], As, Wskip, wm, wn, r, h, lane, ring, acc);
     skip_slice<2>(xr[2], As, Wskip, wm, wn, r, h, lane, ring, acc);
     skip_slice<3>(xr[3], As, Wskip, wm, wn, r, h, lane, ring, acc);
-    } else { acc[0][0] = __uint_as_float(xr[0][0].x ^ xr[1][1].x ^ xr[2][2].x ^ xr[3][3].x ^ ring[0][0].x); WNB_BARRIER(); }
     PH(2);
     // the end conv's first weight fragments fly under this epilogue
     WRing<3, H / 16> ring2;
@@ -311,9 +278,9 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
                               (acc[bn][4 * g + 2] + b4.z) * rm_l, (acc[bn][4 * g + 3] + b4.w) * rm_l);
         *reinterpret_cast<uint2*>(As + (32 * wm + r) * AP + n) = v;
       }
-    WNB_BARRIER();
+    __syncthreads();
     PH(3);
-    if (!(WNB_EXP & 4)) coop_store_rows(wn_out, H, As, m0, R);       // whole rows from the tile (see coop_store_rows)
+    coop_store_rows(wn_out, H, As, m0, R);                           // whole rows from the tile (see coop_store_rows)
     // end conv: [m | logs] = wn_out @ Wend^T + b   (N = 160: blocks 0..4, block 5 is the image's zero padding)
     // the coupling's inputs (this block's y, written by the previous launch) fly under the end conv
     float4 cy0[5], cy1[5];
@@ -340,7 +307,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
               make_float4(acc2[bn][4 * g] + b4.x, acc2[bn][4 * g + 1] + b4.y, acc2[bn][4 * g + 2] + b4.z, acc2[bn][4 * g + 3] + b4.w);
         }
       }
-    WNB_BARRIER();
+    __syncthreads();
     PH(5);
     // affine coupling on (row, 4 channels): z = [y0 | (m + exp(logs) y1) mask]
 #pragma unroll
@@ -360,7 +327,6 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
         }
         z1 = make_float4((mm.x + __expf(lg[0]) * y1.x) * rm, (mm.y + __expf(lg[1]) * y1.y) * rm,
                          (mm.z + __expf(lg[2]) * y1.z) * rm, (mm.w + __expf(lg[3]) * y1.w) * rm);
-        if (!(WNB_EXP & 4)) {
         if (a.z) {
           *reinterpret_cast<float4*>(a.z + (size_t)gm * C + c) = z0;
           *reinterpret_cast<float4*>(a.z + (size_t)gm * C + HALF + c) = z1;
@@ -370,7 +336,6 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
           if (t >= 0 && t < a.len[b]) { sq_scatter4(a.z_bct, b, t, c, a.T, z0); sq_scatter4(a.z_bct, b, t, HALF + c, a.T, z1); }
         }
         *reinterpret_cast<float4*>(a.logs_raw + (size_t)gm * HALF + c) = lr;       // the backward needs logs only
-        }
         const float s = (lg[0] + lg[1] + lg[2] + lg[3]) * rm;
         if (s != 0.0f) atomicAdd(rowsum + row, s);
       }
@@ -379,7 +344,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
         *reinterpret_cast<float4*>(Zt + row * ZP + HALF + c) = z1;
       }
     }
-    WNB_BARRIER();
+    __syncthreads();
     PH(6);
     // (the per-utterance log-det atomics are issued at the very end of the kernel: vector-memory operations retire in order, and a
     // float atomic takes microseconds to come back — issued here, every later wait for a load waited for them too)
@@ -403,7 +368,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
       }
       *reinterpret_cast<float4*>(Zt + row * ZP + c) = v;
     }
-    WNB_BARRIER();
+    __syncthreads();
   }
   if (!HEAD) return;
 
@@ -446,7 +411,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
       }
     }
   }
-  WNB_BARRIER();
+  __syncthreads();
   PH(8);
   // start conv: h = (y0 @ Wstart^T + b) * mask   (K = 80: 5 k-steps)
   {
@@ -466,7 +431,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
             pack4((acc3[bn][4 * g] + b4.x) * rm_l, (acc3[bn][4 * g + 1] + b4.y) * rm_l,
                   (acc3[bn][4 * g + 2] + b4.z) * rm_l, (acc3[bn][4 * g + 3] + b4.w) * rm_l);
       }
-    WNB_BARRIER();
+    __syncthreads();
     PH(10);
     coop_store_rows(h0, H, Hst, m0, R);
   }
@@ -552,7 +517,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
     }
     WRing<2, H / 16> ring1;
     gemm_prefetch<2, H / 16>(static_cast<const bf16_t*>(a.w_start_d), a.ks_start_d, 2 * wn, lane, ring1);
-    WNB_BARRIER();
+    __syncthreads();
     PH(1);
     f32x16_t acc[2];
     acc_zero<2>(acc);
@@ -565,7 +530,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
         if (n < HALF)
           *reinterpret_cast<float4*>(Dt + (32 * wm + r) * ZP + n) = make_float4(acc[bn][4 * g], acc[bn][4 * g + 1], acc[bn][4 * g + 2], acc[bn][4 * g + 3]);
       }
-    WNB_BARRIER();
+    __syncthreads();
     PH(2);
     // ActNorm + InvConvNear backward: wave = row phase (rows ph, ph + 4, ..), lane = channel group
     float* sL = reinterpret_cast<float*>(smem + B_RED);
@@ -578,7 +543,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
       for (int b = threadIdx.x; b < a.B; b += 256) sv += a.dlogdet[b] * (float)a.len[b];
       sv = wave_sum(sv);
       if (lane == 0) sred[wave] = sv;
-      WNB_BARRIER();
+      __syncthreads();
       sv = sred[0] + sred[1] + sred[2] + sred[3];
       if (a.pg_partial) extra = sv;
       else {
@@ -658,7 +623,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
 #pragma unroll
       for (int i = 0; i < 16; ++i) sW[ph * 16 + i] = accW[i];
     }
-    WNB_BARRIER();
+    __syncthreads();
     // The workgroup's 336 parameter-gradient atomics (152 workgroups add to the same 336 addresses: they serialise at L2 and take
     // microseconds to retire) are issued at the END of the kernel: vector-memory operations retire in order, so issued here every
     // later wait for a load — the coupling's operands, the next weight fragments — waited for them too (10 k of the launch's 58 k
@@ -683,7 +648,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
       }
       *reinterpret_cast<float4*>(Dt + row * ZP + c) = v;
     }
-    WNB_BARRIER();
+    __syncthreads();
   }
 
   // coupling backward on (row, 4 channels): d x = [d z0 | d z1 exp(logs)], d m = d z1, d logs = d z1 exp(logs) y1 + d logdet
@@ -732,7 +697,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
       *reinterpret_cast<uint2*>(Dout + row * AP + HALF + c) = pl;
     }
   }
-  WNB_BARRIER();
+  __syncthreads();
   PH(5);
   // end conv data gradient: d wn_out = (d out @ Wend) * mask   (K = 160: 10 k-steps)
   bf16_t* At = Dh;                                           // the d h tile is dead
@@ -757,7 +722,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
         *reinterpret_cast<uint2*>(At + (32 * wm + r) * AP + n) = v;
       }
   }
-  WNB_BARRIER();
+  __syncthreads();
   PH(7);
   coop_store_rows(static_cast<bf16_t*>(a.dwn_out), H, At, m0, R);
   PH(8);
@@ -798,7 +763,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
         const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
         *reinterpret_cast<uint2*>(Vst + (32 * wm + r) * AP + n) = pack4(acc[bn][4 * g], acc[bn][4 * g + 1], acc[bn][4 * g + 2], acc[bn][4 * g + 3]);
       }
-    WNB_BARRIER();
+    __syncthreads();
     coop_store_rows(via + l * H, a.ldvs, Vst, m0, R);
     PH(9 + l);
   }
@@ -824,8 +789,6 @@ __global__ __launch_bounds__(384) void gt_boundary_param_reduce_kernel(const flo
   float* d = t < C ? dst[3 * b] + t : (t < 2 * C ? dst[3 * b + 1] + (t - C) : dst[3 * b + 2] + (t - 2 * C));
   atomicAdd(d, (s0 + s1) + (s2 + s3));
 }
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <typename K>
 int opt_in_lds(K kernel, int bytes)

@@ -29,6 +29,8 @@
 //
 // The skip half of res_skip stays what round 1 made it: ONE K = n*H GEMM per WaveNet over the layers' gated activations.
 #include "common.h"
+#include "internal.h"
+#include "mfma_frag.h"
 #include "../../include/glowtts_hip.h"
 
 namespace {
@@ -41,10 +43,7 @@ constexpr int TAPS = 5;
 constexpr int XROWS = BM + TAPS - 1;          // 68 activation rows per slice
 constexpr int XCH = (XROWS * 8 + 255) / 256;  // 16-byte activation chunks per thread per slice
 constexpr int AP = H + 8;                     // pitch (halfs) of the stage-2 activation tile
-#ifndef WN_RING
-#define WN_RING 3
-#endif
-constexpr int RING = WN_RING;                 // weight-fragment register ring: (slice, tap) steps in flight per wave
+constexpr int RING = 3;                       // weight-fragment register ring: (slice, tap) steps in flight per wave
 
 struct WnArgs {
   const bf16_t* X; int ldx;                   // stage-1 operand rows (fwd: layer input [R, H]; bwd: d pre of the next layer [R, 2H])
@@ -65,32 +64,6 @@ struct WnArgs {
   // live timing of the dominant kernel inside a captured graph (bench.py): stamps[2*slot] = min start, [2*slot+1] = max end
   unsigned long long* stamps; int stamp_slot; const int32_t* stamp_base;     // slot = stamp_slot + *stamp_base (a per-step device counter)
 };
-
-// workgroup 0's start (kept in a register, stored at the end) and an atomicMax of every workgroup's end, issued after its last wait:
-// an atomic at the kernel's start sits in front of every later wait for a load (vector-memory operations retire in order)
-__device__ __forceinline__ unsigned long long stamp_begin(const WnArgs& a)
-{
-  return (a.stamps && threadIdx.x == 0 && blockIdx.x == 0) ? (unsigned long long)wall_clock64() : 0ull;
-}
-__device__ __forceinline__ void stamp_end(const WnArgs& a, unsigned long long t_begin)
-{
-  if (a.stamps && threadIdx.x == 0) {
-    unsigned long long* slot = a.stamps + 2 * (a.stamp_slot + (a.stamp_base ? *a.stamp_base : 0));
-    if (blockIdx.x == 0) slot[0] = t_begin;
-    atomicMax(slot + 1, (unsigned long long)wall_clock64());
-  }
-}
-
-__device__ __forceinline__ uint4 ldfrag(const bf16_t* __restrict__ W, int f, int lane)
-{
-  return *reinterpret_cast<const uint4*>(W + ((size_t)f * 64 + lane) * 8);
-}
-__device__ __forceinline__ bf16x8_t asfrag(const uint4& u) { return __builtin_bit_cast(bf16x8_t, u); }
-__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) { return make_uint2(pack2bf(a, b), pack2bf(c, d)); }
-__device__ __forceinline__ void unpack4(const uint2& u, float (&v)[4])
-{
-  v[0] = bf2f(u.x & 0xffff); v[1] = bf2f(u.x >> 16); v[2] = bf2f(u.y & 0xffff); v[3] = bf2f(u.y >> 16);
-}
 
 // activation slice `slice` (64 channels) of rows m0 - 2 .. m0 + 65 -> registers -> LDS
 __device__ __forceinline__ void x_load(const bf16_t* __restrict__ X, int ldx, int Kx, int R, int m0, int slice, uint4 (&xr)[XCH])
@@ -128,10 +101,7 @@ __device__ __forceinline__ void s2_gemm(const bf16_t* __restrict__ W2, const bf1
                                         uint4 (&ring)[KK2 / 2][3], f32x16_t (&acc)[3])
 {
   const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int bn = 0; bn < 3; ++bn)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[bn][e] = 0.0f;
+  acc_zero(acc);
   const bf16_t* ab = At + (32 * wm + r) * AP + 8 * h;
 #pragma unroll
   for (int kk = 0; kk < KK2; ++kk) {
@@ -162,7 +132,7 @@ __global__ __launch_bounds__(256) void gt_wn_layer_fwd_kernel(WnArgs a)
   bf16_t* Sl = Tl + BM * AP;
   constexpr int NS = H / BK, NIT = NS * TAPS, KS = H / 16, NBT = 2 * H / 32;  // 3 slices, 15 steps, 12 k-steps per tap, 12 column blocks
 
-  f32x16_t acc[3][2];
+  f32x16_t acc[3][2];                          // (written out: through acc_zero these two kernels come out scheduled differently)
 #pragma unroll
   for (int bn = 0; bn < 3; ++bn)
 #pragma unroll
@@ -173,9 +143,6 @@ __global__ __launch_bounds__(256) void gt_wn_layer_fwd_kernel(WnArgs a)
   // weight fragments of step `it` (slice, tap): 4 k-steps x this wave's 3 column blocks
   uint4 ring[RING][4][3];
   auto w_load = [&](int it, uint4 (&dst)[4][3]) {
-#ifdef WN_EXP_NOLOAD
-    if (it > RING) return;
-#endif
     const int slice = it / TAPS, tap = it - slice * TAPS;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
@@ -204,12 +171,8 @@ __global__ __launch_bounds__(256) void gt_wn_layer_fwd_kernel(WnArgs a)
         const bf16x8_t b1 = *reinterpret_cast<const bf16x8_t*>(xsb + 32 * LDP + ks * 16);
 #pragma unroll
         for (int bn = 0; bn < 3; ++bn) {
-#ifdef WN_EXP_NOMFMA
-          acc[bn][0][0] += __uint_as_float(ring[it % RING][ks][bn].x) + b0[0]; acc[bn][1][1] += __uint_as_float(ring[it % RING][ks][bn].w) + b1[1];
-#else
           acc[bn][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(asfrag(ring[it % RING][ks][bn]), b0, acc[bn][0], 0, 0, 0);
           acc[bn][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(asfrag(ring[it % RING][ks][bn]), b1, acc[bn][1], 0, 0, 0);
-#endif
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -253,11 +216,7 @@ __global__ __launch_bounds__(256) void gt_wn_layer_fwd_kernel(WnArgs a)
               vs = ks ? vs * a.drop_scale : 0.0f;
             }
             vt += ctv[j]; vs += csv[j];
-#ifdef WN_EXP_NOEPI
-            tt[j] = vt; ss[j] = vs; aa[j] = vt + vs;
-#else
             tt[j] = tanhf_(vt); ss[j] = sigmoidf_(vs); aa[j] = tt[j] * ss[j];
-#endif
           }
         }
         // T, S and acts leave as whole rows through LDS tiles (wn_stack.hip, DESIGN 4.9: the accumulator layout gives a store
@@ -326,7 +285,7 @@ __global__ __launch_bounds__(256) void gt_wn_layer_bwd_kernel(WnArgs a)
   bf16_t* At = reinterpret_cast<bf16_t*>(smem + (EX_BYTES > BWD_XS ? EX_BYTES : BWD_XS));
   constexpr int NS = 2 * H / BK, NIT = NS * TAPS, KS = 2 * H / 16, NBT = H / 32;  // 6 slices, 30 steps, 24 k-steps per tap, 6 column blocks
 
-  f32x16_t acc[3][2];
+  f32x16_t acc[3][2];                          // (written out: through acc_zero these two kernels come out scheduled differently)
 #pragma unroll
   for (int bn = 0; bn < 3; ++bn)
 #pragma unroll
@@ -460,14 +419,11 @@ __global__ __launch_bounds__(256) void gt_wn_layer_bwd_kernel(WnArgs a)
 
 int fill_drop(WnArgs& a, float drop_p, uint32_t seed, const uint32_t* seed_dev)
 {
-  a.drop_thresh = 0; a.drop_seed = seed; a.drop_scale = 1.0f; a.seed_dev = seed_dev;
-  if (drop_p > 0.0f) {
-    if (drop_p >= 1.0f) return GT_E_UNSUPPORTED;
-    a.drop_thresh = (uint32_t)((double)drop_p * 4294967296.0); a.drop_scale = 1.0f / (1.0f - drop_p);
-  }
+  a.drop_seed = seed; a.seed_dev = seed_dev;
+  if (drop_p >= 1.0f) return GT_E_UNSUPPORTED;
+  gt_drop_params(drop_p, &a.drop_thresh, &a.drop_scale);
   return GT_OK;
 }
-inline bool al16(const void* p) { return !((uintptr_t)p & 15); }
 
 }  // namespace
 

@@ -15,6 +15,8 @@
 // fragments L2 -> registers (3-step ring), activations = MFMA-B from the LDS tile; gate epilogue in registers (bias, dropout,
 // cond, tanh * sigmoid; T, S, acts -> HBM for the owned rows, acts -> LDS); stage 2  x_next = (x + acts @ W_res^T + b) * mask.
 #include "common.h"
+#include "internal.h"
+#include "mfma_frag.h"
 #include "../../include/glowtts_hip.h"
 
 namespace {
@@ -23,36 +25,16 @@ constexpr int H = 192, TAPS = 5, NLMAX = 4;
 constexpr int BM = 64;                        // rows computed per layer
 constexpr int AP = H + 8;                     // LDS pitch (halfs): 400 B = 16 mod 128 -> conflict-free ds_read_b128
 constexpr int XR = BM + TAPS - 1;             // 68 input rows
-#ifndef WNS_PIN_STEP
-#define WNS_PIN_STEP 1
-#endif
-#ifndef WNS_EXP
-#define WNS_EXP 0                             // dev experiments (bit mask), 0 in every build that ships
-#endif
-#ifndef WNS_RING
-#define WNS_RING 3
-#endif
-#ifndef WNS_LDSBAR
-#define WNS_LDSBAR 0                          // 1: barriers wait for LDS traffic only (common.h lds_barrier) instead of __syncthreads()'s
-                                              // vmcnt(0).  Measured (round 3, back to back): backward 86.6 us either way, forward 71.2 vs
-                                              // 67.9 us — the activation stores then sit in front of the next layer's weight loads on
-                                              // the in-order vmcnt counter and stall the conv loop instead of the barrier
-#endif
-#if WNS_LDSBAR
-#define WNS_BARRIER() lds_barrier()
-#else
-#define WNS_BARRIER() __syncthreads()
-#endif
-#ifndef WNS_FIXA
-#define WNS_FIXA 1                            // loads ahead of stores (see the forward kernel)
-#endif
-constexpr int RING = WNS_RING;
-#ifndef WNS_RING1
-#define WNS_RING1 WNS_RING                    // weight ring depths of the 32-row form (NBM = 1).  Its spare accumulator registers could pay for
-#endif                                        // deeper rings; measured at 5 120 rows (round 3): forward 56.6 / 58.4 / 58.4 us at depth 4 / 5 / 3,
-#ifndef WNS_RB1                               // backward 73.7 / 68.2 us at depth 9 / 5 — what the 256 workgroups wait for is the L2 itself
-#define WNS_RB1 (2 * WNS_RING - 1)            // (each streams all 3.2 MB of weights: 0.8 GB per launch), not a ring step's round trip
-#endif
+// Weight ring depths.  64-row form: forward 3 steps, backward 2 * 3 - 1 = 5 (half the fragments per step: twice the depth for the
+// same registers).  Measured and settled (round 3) for the
+// 32-row form (NBM = 1), whose spare accumulator registers could pay for deeper rings, at 5 120 rows: forward 56.6 / 58.4 / 58.4 us
+// at depth 4 / 5 / 3, backward 73.7 / 68.2 us at depth 9 / 5 — what the 256 workgroups wait for is the L2 itself (each streams
+// all 3.2 MB of weights: 0.8 GB per launch), not a ring step's round trip: the 32-row form keeps the 64-row depths.
+constexpr int RING = 3, RING1 = RING;
+constexpr int RB = 2 * RING - 1, RB1 = RB;
+// Barriers are __syncthreads() (vmcnt(0) as well as lgkmcnt(0)).  One that waits for LDS traffic only measured (round 3, back to
+// back) backward 86.6 us either way, forward 71.2 vs 67.9 us: the activation stores then sit in front of the next layer's weight
+// loads on the in-order vmcnt counter and stall the conv loop instead of the barrier.
 #ifndef WNS_PHASES
 #define WNS_PHASES 0                          // dev: per-phase shader-clock stamps of wave 0 (tools/wn_stack_phases.py), 0 in every build that ships
 #endif
@@ -72,21 +54,6 @@ constexpr int STACK_FWD_LDS = STACK_LDS + 2 * BM * AP * 2 + FWD_BIAS_FLOATS * 4;
 constexpr int STACK_FWD_LDS_AFF = STACK_FWD_LDS + FWD_AFF_FLOATS * 4;              // + 6 144 B
 constexpr int CPR = H / 8;                                              // 16-byte chunks per row
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-// through an explicit GLOBAL pointer: a pointer that went through `pinned` is generic to the compiler, and flat loads count on
-// lgkmcnt as well as vmcnt — every LDS wait would then drain the weight prefetch
-__device__ __forceinline__ uint4 ldfrag(const bf16_t* __restrict__ W, int f, int lane)
-{
-  typedef const u32x4_t __attribute__((address_space(1)))* gptr_t;
-  const u32x4_t v = *reinterpret_cast<gptr_t>(reinterpret_cast<uintptr_t>(W + ((size_t)f * 64 + lane) * 8));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ bf16x8_t asfrag(const uint4& u) { return __builtin_bit_cast(bf16x8_t, u); }
-__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) { return make_uint2(pack2bf(a, b), pack2bf(c, d)); }
-__device__ __forceinline__ void unpack4(const uint2& u, float (&v)[4])
-{
-  v[0] = bf2f(u.x & 0xffff); v[1] = bf2f(u.x >> 16); v[2] = bf2f(u.y & 0xffff); v[3] = bf2f(u.y >> 16);
-}
 // A pointer the optimiser cannot see through: the 180 fragment addresses of a layer depend only on a kernel argument and the
 // lane, so LLVM hoists them to the kernel's entry block — 360 registers that then live (spilled) across every earlier layer.
 template <typename T>
@@ -125,13 +92,10 @@ template <int COND, bool DROP, int NBM>
 __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_args a, uint32_t drop_thresh, float drop_scale)
 {
   constexpr int BMv = 32 * NBM, XRv = BMv + TAPS - 1;
-  constexpr int RINGv = NBM == 1 ? WNS_RING1 : RING;
+  constexpr int RINGv = NBM == 1 ? RING1 : RING;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  // bench.py's live timing: workgroup 0's start (the first dispatched) is kept in a register and stored at the end, every workgroup's
-  // end goes into one atomicMax AFTER its last wait — an atomicMin here, 188 workgroups on one address, sat in front of every
-  // weight fragment's wait (vector-memory operations retire in order)
-  unsigned long long t_begin = 0;
-  if (a.stamps && threadIdx.x == 0 && blockIdx.x == 0) t_begin = (unsigned long long)wall_clock64();
+  // (an atomicMin here, 188 workgroups on one address, sat in front of every weight fragment's wait)
+  const unsigned long long t_begin = stamp_begin(a);
   PH(0);
   const uint32_t seed_x = a.seed_dev ? *a.seed_dev : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -164,10 +128,9 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
   // longer than the MFMA it was meant to hide behind): tools/stack_variants.sh, round 3.
   auto w_frag = [&](const bf16_t* W, int it, int ks, int bn) {
     const int kg = it / TAPS, tap = it - kg * TAPS;
-    return ldfrag(W, (tap * NBT + 3 * wave + bn) * KS + kg * 4 + ks, lane);
+    return ldfrag_global(W, (tap * NBT + 3 * wave + bn) * KS + kg * 4 + ks, lane);
   };
   auto w_load_l = [&](const bf16_t* W, int it, uint4 (&dst)[4][3]) {
-    if ((WNS_EXP & 2) && it > RINGv) return;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
@@ -214,13 +177,11 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
       const int m = s0 + 32 * (wave >> 1) + r;
       rm2 = (m >= 0 && m < R) ? a.rowmask[m] : 0.0f;
     }
-#if WNS_FIXA
     {
       const bf16_t* W10 = static_cast<const bf16_t*>(a.w_in[0]);
 #pragma unroll
       for (int p = 0; p < RINGv - 1; ++p) w_load_l(W10, p, ring[p]);
     }
-#endif
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
       const int chunk = threadIdx.x + 256 * i, u = chunk / CPR, c8 = chunk - u * CPR;
@@ -243,7 +204,7 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
       *reinterpret_cast<uint4*>(Xn + u * AP + c8 * 8) = make_uint4(0, 0, 0, 0);
     }
   }
-  WNS_BARRIER();
+  __syncthreads();
   PH(1);
 
   // per-utterance conditioning: the utterance of this lane's two rows (one binary search each, once per launch)
@@ -276,18 +237,9 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
     const uint32_t seed = (a.drop_seed + (uint32_t)layer) ^ seed_x;
 
     f32x16_t acc[3][NBM];
-#pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
-#pragma unroll
-      for (int bm = 0; bm < NBM; ++bm)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[bn][bm][e] = 0.0f;
+    acc_zero(acc);
 
     auto w_load = [&](int it, uint4 (&dst)[4][3]) { w_load_l(W1, it, dst); };
-#if !WNS_FIXA
-#pragma unroll
-    for (int p = 0; p < RINGv - 1; ++p) w_load(p, ring[p]);
-#endif
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int kg = it / TAPS, tap = it - kg * TAPS;
@@ -323,7 +275,7 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
 #pragma unroll
       for (int kk = 0; kk < R2; ++kk)
 #pragma unroll
-        for (int bn = 0; bn < 3; ++bn) ring2[kk][bn] = ldfrag(W2, (3 * wn2 + bn) * KK2 + kk, lane);
+        for (int bn = 0; bn < 3; ++bn) ring2[kk][bn] = ldfrag_global(W2, (3 * wn2 + bn) * KK2 + kk, lane);
     }
 
     // gate epilogue in registers (see wn_layer.hip): block 3*wave + bn holds [16 tanh | 16 sigmoid] of channels 16*(3*wave+bn)..+15
@@ -361,14 +313,14 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             float vt = acc[bn][bm][4 * g + j] + btv[j], vs = acc[bn][bm][4 * g + j + 8] + bsv[j];
-            if (DROP && !(WNS_EXP & 4)) {                              // x_in = drop(conv(x)) (modules.py:153)
+            if (DROP) {                              // x_in = drop(conv(x)) (modules.py:153)
               bool kt, ks;
               drop_keep_gate(seed, m, c + j, drop_thresh16(drop_thresh), kt, ks);
               vt = kt ? vt * drop_scale : 0.0f;
               vs = ks ? vs * drop_scale : 0.0f;
             }
             vt += ctv[j]; vs += csv[j];
-            if (WNS_EXP & 4) { tt[j] = vt; ss[j] = vs; aa[j] = vt + vs; } else { tt[j] = tanhf_(vt); ss[j] = sigmoidf_(vs); aa[j] = tt[j] * ss[j]; }
+            tt[j] = tanhf_(vt); ss[j] = sigmoidf_(vs); aa[j] = tt[j] * ss[j];
           }
           // T, S and acts leave through LDS: straight from the MFMA layout a store instruction writes 16 bytes to each of 32
           // rows (2.6 M partial-line requests per launch, the "17 us of stores" of DESIGN 4.9); the tiles below go out as whole rows
@@ -378,10 +330,9 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
         }
       }
     PH(3 + 6 * layer);
-    WNS_BARRIER();                                                   // At, Tl, Sl complete
+    __syncthreads();                                                   // At, Tl, Sl complete
     PH(4 + 6 * layer);
     auto store_gate_tiles = [&]() {
-      if (WNS_EXP & 1) return;
       // the rows this workgroup owns are ONE contiguous block of T / S (and 384-byte pieces of the acts rows): 16 bytes per lane,
       // consecutive lanes on consecutive addresses; all the LDS reads first, then the stores (as a rolled loop every chunk paid its
       // own LDS round trip)
@@ -409,15 +360,12 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
         }
       }
     };
-    if (!WNS_FIXA || last) store_gate_tiles();
+    if (last) store_gate_tiles();
     if (last) break;
 
     // stage 2: x_next = (x + acts @ W_res^T + b_res) * mask -> the next layer's LDS tile (+ HBM for the owned rows)
     f32x16_t acc2[3];
-#pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc2[bn][e] = 0.0f;
+    acc_zero(acc2);
     if (st2) {
       const bf16_t* ab = At + (32 * wm2 + r) * AP + 8 * h;
 #pragma unroll
@@ -426,19 +374,17 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
 #pragma unroll
         for (int bn = 0; bn < 3; ++bn) {
           acc2[bn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(asfrag(ring2[kk % R2][bn]), bfm, acc2[bn], 0, 0, 0);
-          if (R2 < KK2 && kk + R2 < KK2) ring2[kk % R2][bn] = ldfrag(W2, (3 * wn2 + bn) * KK2 + kk + R2, lane);
+          if (R2 < KK2 && kk + R2 < KK2) ring2[kk % R2][bn] = ldfrag_global(W2, (3 * wn2 + bn) * KK2 + kk + R2, lane);
         }
       }
     }
     PH(5 + 6 * layer);
-#if WNS_FIXA
     {                                          // the next layer's first ring steps, ahead of the x_next stores
       const bf16_t* W1n = static_cast<const bf16_t*>(pick(a.w_in, layer + 1));
 #pragma unroll
       for (int p = 0; p < RINGv - 1; ++p) w_load_l(W1n, p, ring[p]);
     }
     store_gate_tiles();                        // T, S, acts: the tiles are untouched until the next layer's epilogue
-#endif
     if (st2) {
       const int t = 32 * wm2 + r;
       const float rm = rm2;
@@ -455,10 +401,10 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
           *reinterpret_cast<uint2*>(Xn + (t + 2) * AP + n) = v;
         }
     }
-    WNS_BARRIER();                                                   // the next layer's input is complete; Xc and At are free
+    __syncthreads();                                                   // the next layer's input is complete; Xc and At are free
     PH(6 + 6 * layer);
     bf16_t* tmp = Xc; Xc = Xn; Xn = tmp;
-    if (!(WNS_EXP & 1)) {                                              // x_next of the owned rows, whole rows from the finished tile
+    {                                                                // x_next of the owned rows, whole rows from the finished tile
       constexpr int NC = (BM * CPR + 255) / 256, NP = 3;
 #pragma unroll 1
       for (int i0 = 0; i0 < NC; i0 += NP) {
@@ -483,11 +429,7 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
     PH(7 + 6 * layer);
   }
   PH(40);
-  if (a.stamps && threadIdx.x == 0) {
-    unsigned long long* slot = a.stamps + 2 * (a.stamp_slot + (a.stamp_base ? *a.stamp_base : 0));
-    if (blockIdx.x == 0) slot[0] = t_begin;
-    atomicMax(slot + 1, (unsigned long long)wall_clock64());
-  }
+  stamp_end(a, t_begin);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -532,10 +474,6 @@ __device__ __forceinline__ void gate_bwd4(const float (&dd)[4], const float (&t)
   pt = pack4(gt[0], gt[1], gt[2], gt[3]); ps = pack4(gs[0], gs[1], gs[2], gs[3]);
 }
 
-#ifndef WNS_RB
-#define WNS_RB (2 * WNS_RING - 1)
-#endif
-constexpr int RB = WNS_RB;                     // backward ring depth (64-row form)
 constexpr int B_NS = 2 * H / 64, B_NIT = B_NS * TAPS, B_KS = 2 * H / 16, B_NBT = H / 32;  // 6 slices, 30 steps, 24 k-steps per tap, 6 blocks
 
 // NB column blocks per wave: 2 (waves 0-3, blocks 0 and 1 of the SIMD's column half) or 1 (waves 4-7, block 2)
@@ -550,7 +488,7 @@ __device__ __forceinline__ void bwd_w_load(const bf16_t* W1, int it, int wn, int
 #pragma unroll
   for (int k2 = 0; k2 < 2; ++k2)
 #pragma unroll
-    for (int bn = 0; bn < NB; ++bn) dst[k2][bn] = ldfrag(Wt, bn * B_KS + k2, lane);
+    for (int bn = 0; bn < NB; ++bn) dst[k2][bn] = ldfrag_global(Wt, bn * B_KS + k2, lane);
 }
 // the first RB - 1 steps: issued by the PREVIOUS step (or the kernel's head) ahead of its stores — vmcnt retires in order, so a
 // wait for these fragments would otherwise also wait for every store issued before them (see the forward kernel)
@@ -567,7 +505,7 @@ __device__ __forceinline__ void bwd_ring_prologue(const void* w, int lane, uint4
 template <int J, bool COND, bool DROP, int NBM, int NB>
 __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t drop_thresh, float drop_scale, uint32_t seed_x,
                                          bf16_t* Dt, float* Ex, bf16_t* At, int s0, int halo,
-                                         uint4 (&ring)[NBM == 1 ? WNS_RB1 : RB][2][NB], float rm)
+                                         uint4 (&ring)[NBM == 1 ? RB1 : RB][2][NB], float rm)
 {
   // the thread index as a value formed HERE (see the forward's tid_e): formed once for the kernel, the per-lane addresses derived
   // from it are carried (spilled) from step to step
@@ -578,13 +516,13 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
   const int wn = simd & 1, wk = simd >> 1;     // stage 1: column half, K parity;  afterwards wk doubles as the row half
   constexpr int B0 = bwd_b0<NB>();             // this wave's first block of the column half
   constexpr int BMv = 32 * NBM;                // rows of the tile (NBM: see the forward kernel)
-  constexpr int RBv = NBM == 1 ? WNS_RB1 : RB;
+  constexpr int RBv = NBM == 1 ? RB1 : RB;
   const bool act = wk < NBM;                   // NBM = 1: one row block — the waves of K parity 1 hand their sums over and sit the rest out
   const int n_layers = a.n_layers, R = a.R;
   const bf16_t* via = static_cast<const bf16_t*>(a.via_skip);
   constexpr int NIT = B_NIT;
   const bf16_t* W1 = pinned(static_cast<const bf16_t*>(a.w_in_d[J]));
-  f32x16_t acc[NB][NBM];
+  f32x16_t acc[NB][NBM];                       // (written out: through acc_zero this kernel comes out scheduled differently)
 #pragma unroll
   for (int bn = 0; bn < NB; ++bn)
 #pragma unroll
@@ -623,7 +561,7 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
 #pragma unroll
       for (int kk = k0; kk < k1; ++kk)
 #pragma unroll
-        for (int bn = 0; bn < NB; ++bn) ring2[kk][bn] = ldfrag(W2, (3 * wn + B0 + bn) * KK2 + kk, lane);
+        for (int bn = 0; bn < NB; ++bn) ring2[kk][bn] = ldfrag_global(W2, (3 * wn + B0 + bn) * KK2 + kk, lane);
     }
   };
   w2_load(0, KK2 / 2);
@@ -647,7 +585,7 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
       }
     }
   }
-  WNS_BARRIER();                            // every wave is done with the d pre tile: the exchange buffer may overwrite it
+  __syncthreads();                            // every wave is done with the d pre tile: the exchange buffer may overwrite it
 
   // K parities meet: a wave keeps row block bm == wk and hands the other one to the wave of the same blocks and the other parity
   if (NBM == 2 || wk) {
@@ -657,7 +595,7 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
 #pragma unroll
       for (int e = 0; e < 16; ++e) mine[(bn * 16 + e) * 64 + lane] = (NBM == 2 && !wk) ? acc[bn][NBM - 1][e] : acc[bn][0][e];
   }
-  WNS_BARRIER();
+  __syncthreads();
   f32x16_t sum[NB];
   if (act) {
     const float* theirs = Ex + ((simd ^ 2) * 3 + B0) * (16 * 64);
@@ -684,7 +622,7 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
         *reinterpret_cast<uint2*>(At + t * AP + n) = v;
       }
   }
-  WNS_BARRIER();
+  __syncthreads();
   PH(4 + 8 * (3 - J));
   auto store_dx = [&]() {
     // dX_j of the owned rows leaves as whole rows from the finished tile (the MFMA layout gives a store 16 bytes in each of 32 rows)
@@ -709,10 +647,7 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
   // d acts_{j-1} = dX_j W_res + skip-path gradient -> gate backward -> d pre_{j-1}: the next tile (+ HBM for the owned rows)
   bf16_t* Vl = At + BM * AP; bf16_t* Tl = Vl + BM * AP; bf16_t* Sl = Tl + BM * AP;
   f32x16_t acc2[NB];
-#pragma unroll
-  for (int bn = 0; bn < NB; ++bn)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc2[bn][e] = 0.0f;
+  acc_zero(acc2);
   if (act) {
     const bf16_t* ab = At + (32 * wk + r) * AP + 8 * h;
 #pragma unroll
@@ -735,7 +670,7 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
     *reinterpret_cast<uint4*>(Tl + row * AP + c8 * 8) = pre[1][i];
     *reinterpret_cast<uint4*>(Sl + row * AP + c8 * 8) = pre[2][i];
   }
-  WNS_BARRIER();
+  __syncthreads();
   PH(6 + 8 * (3 - J));
   if (act) {
     bf16_t* dpre_c = static_cast<bf16_t*>(a.dpre_c[JL]);
@@ -765,7 +700,7 @@ __device__ __forceinline__ void bwd_step(const gt_wn_stack_bwd_args& a, uint32_t
       }
   }
   PH(7 + 8 * (3 - J));
-  WNS_BARRIER();                                                   // the next conv's input tile is complete
+  __syncthreads();                                                   // the next conv's input tile is complete
   PH(8 + 8 * (3 - J));
   {
     // d pre_{j-1} of the owned rows: whole 768-byte rows from the tile (read-only until the next step's exchange, which follows a barrier)
@@ -807,7 +742,7 @@ __device__ __forceinline__ void bwd_wave(const gt_wn_stack_bwd_args& a, uint32_t
   float* Ex = reinterpret_cast<float*>(smem);
   bf16_t* At = reinterpret_cast<bf16_t*>(smem + BWD_DT);
   const bf16_t* via = static_cast<const bf16_t*>(a.via_skip);
-  constexpr int RBv = NBM == 1 ? WNS_RB1 : RB;
+  constexpr int RBv = NBM == 1 ? RB1 : RB;
   uint4 ring[RBv][2][NB];
   bwd_ring_prologue<RBv, NB>(pick(a.w_in_d, n_layers - 1), lane, ring);   // ahead of the head's d pre stores
   float rm;                                                         // the row mask of the row this lane finishes in every dX epilogue
@@ -866,7 +801,7 @@ __device__ __forceinline__ void bwd_wave(const gt_wn_stack_bwd_args& a, uint32_t
       *reinterpret_cast<uint4*>(Dt + u * DP + H + n) = make_uint4(ps[0].x, ps[0].y, ps[1].x, ps[1].y);
     }
   }
-  WNS_BARRIER();
+  __syncthreads();
   PH(1);
   // the chain, top to bottom (workgroup-uniform branches; each step is its own straight-line code)
   if (n_layers > 3) bwd_step<3, COND, DROP, NBM, NB>(a, drop_thresh, drop_scale, seed_x, Dt, Ex, At, s0, halo, ring, rm);
@@ -884,8 +819,6 @@ __global__ __launch_bounds__(BWD_THREADS) void gt_wn_stack_bwd_kernel(gt_wn_stac
   if (wave_scalar() < 4) bwd_wave<COND, DROP, NBM, 2>(a, drop_thresh, drop_scale);
   else bwd_wave<COND, DROP, NBM, 1>(a, drop_thresh, drop_scale);
 }
-
-inline bool al16(const void* p) { return !((uintptr_t)p & 15); }
 
 }  // namespace
 
@@ -938,11 +871,9 @@ extern "C" int gt_wn_stack_fwd(const gt_wn_stack_fwd_args* args, void* stream)
     if (a.cond || !a.aff_w || !a.aff_b || !a.aff_sig || ((H * a.n_layers) % (2 * H))) return GT_E_INVAL;   // (O must hold whole layers: n even)
     if (!al16(a.aff_w) || !al16(a.aff_b) || ((uintptr_t)a.aff_sig & 7)) return GT_E_ALIGN;
   }
-  uint32_t thresh = 0; float scale = 1.0f;
-  if (a.drop_p > 0.0f) {
-    if (a.drop_p >= 1.0f) return GT_E_UNSUPPORTED;
-    thresh = (uint32_t)((double)a.drop_p * 4294967296.0); scale = 1.0f / (1.0f - a.drop_p);
-  }
+  if (a.drop_p >= 1.0f) return GT_E_UNSUPPORTED;
+  uint32_t thresh; float scale;
+  gt_drop_params(a.drop_p, &thresh, &scale);
   typedef void (*kern_t)(gt_wn_stack_fwd_args, uint32_t, float);
   static const kern_t kerns[12] = {gt_wn_stack_fwd_kernel<0, false, 2>, gt_wn_stack_fwd_kernel<0, true, 2>, gt_wn_stack_fwd_kernel<1, false, 2>,
                                    gt_wn_stack_fwd_kernel<1, true, 2>, gt_wn_stack_fwd_kernel<2, false, 2>, gt_wn_stack_fwd_kernel<2, true, 2>,
@@ -980,11 +911,9 @@ extern "C" int gt_wn_stack_bwd(const gt_wn_stack_bwd_args* args, void* stream)
     if (!al16(a.w_in_d[i]) || !al16(a.gate_t[i]) || !al16(a.gate_s[i]) || !al16(a.dpre[i]) || !al16(a.dpre_c[i]) || !al16(a.dx[i]) ||
         !al16(a.w_res_d[i])) return GT_E_ALIGN;
   }
-  uint32_t thresh = 0; float scale = 1.0f;
-  if (a.drop_p > 0.0f) {
-    if (a.drop_p >= 1.0f) return GT_E_UNSUPPORTED;
-    thresh = (uint32_t)((double)a.drop_p * 4294967296.0); scale = 1.0f / (1.0f - a.drop_p);
-  }
+  if (a.drop_p >= 1.0f) return GT_E_UNSUPPORTED;
+  uint32_t thresh; float scale;
+  gt_drop_params(a.drop_p, &thresh, &scale);
   bool cond = false;                           // d cond outputs: all layers or none
   for (int i = 0; i < a.n_layers; ++i) cond = cond || a.dpre_c[i];
   for (int i = 0; i < a.n_layers; ++i) if (cond && !a.dpre_c[i]) return GT_E_INVAL;

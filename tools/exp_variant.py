@@ -1,6 +1,6 @@
 """dev: build an experiment variant of the library: ONE source recompiled with extra -D flags, linked with the shipped objects.
 
-    python tools/exp_variant.py NAME SOURCE[,SOURCE...] -DWNS_EXP=2 ...   ->  glow-tts_amd/build/exp/libglowtts_NAME.so
+    python tools/exp_variant.py NAME SOURCE[,SOURCE...] -DWNS_PHASES=1 ...   ->  glow-tts_amd/build/exp/libglowtts_NAME.so
 
 The bench tools take the library path as an argument (tools/wn_layer_bench.py quick <lib.so>)."""
 import os, subprocess, sys
