@@ -105,6 +105,8 @@ PROTOTYPES = {
     "gt_wn_boundary_fwd": (c_int, [c_void_p, c_void_p]),
     "gt_wn_boundary_bwd": (c_int, [c_void_p, c_void_p]),
     "gt_boundary_param_partials": (c_int, []),
+    "gt_wn_boundary_rev": (c_int, [c_void_p, c_void_p]),
+    "gt_boundary_rev_args_size": (c_int, []),
     "gt_boundary_param_reduce": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "gt_rows_split3": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "gt_dds_sep_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
@@ -230,6 +232,17 @@ class BoundaryBwdArgs(ctypes.Structure):
                 ("pg_partial", c_void_p), ("pf_ptr", c_void_p * 16), ("pf_bytes", c_u32 * 16)]
 
 
+class BoundaryRevArgs(ctypes.Structure):
+    """struct gt_boundary_rev_args (include/glowtts_hip.h); its size is checked against gt_boundary_rev_args_size() (tests/test_synthesis_cabi.py)"""
+    _fields_ = [("acts", c_void_p), ("ldacts", c_int), ("w_skip", c_void_p), ("b_skip", c_void_p),
+                ("w_end", c_void_p), ("b_end", c_void_p), ("ks_end", c_int), ("z", c_void_p), ("sigmoid_scale", c_int),
+                ("an_logs", c_void_p), ("an_bias", c_void_p), ("scal", c_void_p), ("x", c_void_p),
+                ("x_in", c_void_p), ("w_start", c_void_p), ("b_start", c_void_p), ("ks_start", c_int), ("h_next", c_void_p),
+                ("rowmask", c_void_p), ("R", c_int), ("H", c_int), ("C", c_int), ("n_layers", c_int),
+                ("z_bct", c_void_p), ("x_bct", c_void_p), ("T", c_int), ("rowbatch", c_void_p), ("rowframe", c_void_p), ("len", c_void_p),
+                ("pf_ptr", c_void_p * 16), ("pf_bytes", c_u32 * 16)]
+
+
 def fill_args(cls, **kw):
     """ctypes struct from keyword arguments: tensors become device pointers, None stays NULL, ints stay ints."""
     a = cls()
@@ -302,6 +315,39 @@ class _Traced:
             self._f.seek(0); self._f.write(f"{self._n} {name} returned".ljust(96) + "\n"); self._f.flush()
             return rc
         return call
+
+
+class _Recording:
+    """the library with the name of every gt_* entry appended to `names` before the call (record_calls)"""
+
+    def __init__(self, L, names):
+        self._L, self._names = L, names
+
+    def __getattr__(self, name):
+        fn = getattr(self._L, name)
+        if not name.startswith("gt_"):
+            return fn
+
+        def call(*a):
+            self._names.append(name)
+            return fn(*a)
+        return call
+
+
+class record_calls:
+    """dev: `with _lib.record_calls() as names:` — the C-ABI entries called inside the block, in order (a test and tools/synth_bench.py
+    count the launches of one pass with it).  Nothing is recorded, and nothing kept, outside such a block."""
+
+    def __enter__(self):
+        global _LIB
+        self._prev, self.names = lib(), []
+        _LIB = _Recording(self._prev, self.names)
+        return self.names
+
+    def __exit__(self, *exc):
+        global _LIB
+        _LIB = self._prev
+        return False
 
 
 def check(rc, what):

@@ -1,4 +1,5 @@
-// Everything BETWEEN two WaveNets of the flow decoder as one kernel, forward and backward, gfx950.
+// Everything BETWEEN two WaveNets of the flow decoder as one kernel, forward and backward (and, further down, the reverse
+// direction that synthesis runs), gfx950.
 //
 // reference, per flow block b (models.py:765-785 runs ActNorm, InvConvNear, CouplingBlock in turn):
 //     y      = InvConvNear(ActNorm(x))                                        modules.py:584-599, 635-665
@@ -790,6 +791,219 @@ __global__ __launch_bounds__(384) void gt_boundary_param_reduce_kernel(const flo
   atomicAdd(d, (s0 + s1) + (s2 + s3));
 }
 
+// ------------------------------------------------------------------------------------------------ reverse (synthesis)
+// The mirror of the forward kernel for the inverse maps (models.py:765-785 with reverse=True): going from block b to block b-1,
+//   [tail of block b]    acts [64, 4H] -> skip GEMM -> wn_out (bf16, LDS only) -> end conv -> m | logs -> coupling^-1 on the flow
+//                        state z -> u -> InvConvNear^-1, ActNorm^-1 -> x (HBM: the flow state the next launch's tail reads)
+//   [head of block b-1]  x0 = bf16(x[:, :C/2]) -> start conv (K = 80) -> h (HBM: the next WaveNet's input)
+// No log-det and nothing kept for a backward: wn_out, m | logs and x0 never leave LDS.  Same tiles, pitches, weight rings and
+// rounding points (bf16 acts, wn_out, x0) as the forward kernel and as the launch sequence it replaces (gt_conv_gemm_bf16 x 3,
+// gt_coupling_rev, gt_actnorm_invconv_rev), whose elementwise formulas are restated here term by term.
+constexpr int REV_LDS = FWD_LDS;               // the forward's layout: acts slices / At / x0 tile, m | logs tile, u tile, biases, row mask
+
+template <bool TAIL, bool HEAD>
+__global__ __launch_bounds__(256) void gt_wn_boundary_rev_kernel(gt_boundary_rev_args a)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int n_tiles = (a.R + BM - 1) / BM;
+  if ((int)blockIdx.x >= n_tiles) { prefetch_images(a.pf_ptr, a.pf_bytes, blockIdx.x - n_tiles, nullptr); return; }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
+  const int m0 = blockIdx.x * BM, R = a.R;
+  bf16_t* As = reinterpret_cast<bf16_t*>(smem + F_AS);
+  float* Ot = reinterpret_cast<float*>(smem + F_O);
+  float* Zt = reinterpret_cast<float*>(smem + F_Z);
+  bf16_t* X0t = reinterpret_cast<bf16_t*>(smem + F_AS);      // the x0 tile takes At's place once the end conv is done
+  const int mrow = m0 + 32 * wm + r;                        // this lane's row in the MFMA epilogues
+  const float rm_l = mrow < R ? a.rowmask[mrow] : 0.0f;
+  float* Bs = reinterpret_cast<float*>(smem + F_BIAS);       // b_skip [192] | b_end [160 (+ 32 zero)] | b_start [192], staged once
+  if (threadIdx.x < 3 * H / 4) {
+    const int which = threadIdx.x / (H / 4), o = threadIdx.x - which * (H / 4);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (which == 0) { if (TAIL) v = reinterpret_cast<const float4*>(a.b_skip)[o]; }
+    else if (which == 1) { if (TAIL && o < C / 4) v = reinterpret_cast<const float4*>(a.b_end)[o]; }
+    else if (HEAD) v = reinterpret_cast<const float4*>(a.b_start)[o];
+    reinterpret_cast<float4*>(Bs)[threadIdx.x] = v;
+  }
+  float* Rm = Bs + 3 * H;                                    // the tile's row mask
+  if (threadIdx.x >= 192) {
+    const int row = threadIdx.x - 192;
+    Rm[row] = m0 + row < R ? a.rowmask[m0 + row] : 0.0f;
+  }
+  WRing<3, HALF / 16> ring3;                                 // the start conv's weights: they depend on nothing computed here
+
+  if (TAIL) {
+    const bf16_t* acts = static_cast<const bf16_t*>(a.acts);
+    const bf16_t* Wskip = static_cast<const bf16_t*>(a.w_skip);
+    u32x4_t xr[NL][6];                                      // the tile's gated activations, all four layers, in flight together
+#pragma unroll
+    for (int l = 0; l < NL; ++l)
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const int chunk = threadIdx.x + 256 * i, row = chunk / 24, c8 = chunk - row * 24;
+        const int gm = m0 + row < R ? m0 + row : R - 1;
+        xr[l][i] = *reinterpret_cast<const u32x4_t*>(acts + (size_t)gm * a.ldacts + l * H + c8 * 8);
+      }
+    // skip GEMM: wn_out = bf16((acts @ Wskip^T + b) * mask);  wave (wm, wn): rows 32 wm .., column blocks 3 wn ..
+    f32x16_t acc[3];
+    acc_zero<3>(acc);
+    constexpr int KK = NL * H / 16;                         // 48 k-steps
+    uint4 ring[RD][3];
+#pragma unroll
+    for (int p = 0; p < RD; ++p)
+#pragma unroll
+      for (int bn = 0; bn < 3; ++bn) ring[p][bn] = ldfrag(Wskip, (3 * wn + bn) * KK + p, lane);
+    skip_slice<0>(xr[0], As, Wskip, wm, wn, r, h, lane, ring, acc);
+    skip_slice<1>(xr[1], As, Wskip, wm, wn, r, h, lane, ring, acc);
+    skip_slice<2>(xr[2], As, Wskip, wm, wn, r, h, lane, ring, acc);
+    skip_slice<3>(xr[3], As, Wskip, wm, wn, r, h, lane, ring, acc);
+    WRing<3, H / 16> ring2;                                 // the end conv's first weight fragments fly under this epilogue
+    gemm_prefetch<3, H / 16>(static_cast<const bf16_t*>(a.w_end), a.ks_end, 3 * wn, lane, ring2);
+    // every wave is past slices 0..2 (the barrier before slice 3): At = slice 0's region
+#pragma unroll
+    for (int bn = 0; bn < 3; ++bn)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
+        const float4 b4 = *reinterpret_cast<const float4*>(Bs + n);
+        *reinterpret_cast<uint2*>(As + (32 * wm + r) * AP + n) =
+            pack4((acc[bn][4 * g] + b4.x) * rm_l, (acc[bn][4 * g + 1] + b4.y) * rm_l,
+                  (acc[bn][4 * g + 2] + b4.z) * rm_l, (acc[bn][4 * g + 3] + b4.w) * rm_l);
+      }
+    __syncthreads();
+    // the coupling's input (the flow state the previous launch wrote) flies under the end conv
+    // (written out item by item: as an array filled in a loop the ten values were given a stack slot)
+    auto z_load = [&](int k, int half) {
+      const int item = threadIdx.x + 256 * k, row = item / 20, c = 4 * (item - row * 20), gm = m0 + row < R ? m0 + row : R - 1;
+      return *reinterpret_cast<const float4*>(a.z + (size_t)gm * C + half * HALF + c);
+    };
+    const float4 za0 = z_load(0, 0), za1 = z_load(1, 0), za2 = z_load(2, 0), za3 = z_load(3, 0), za4 = z_load(4, 0);
+    const float4 zb0 = z_load(0, 1), zb1 = z_load(1, 1), zb2 = z_load(2, 1), zb3 = z_load(3, 1), zb4 = z_load(4, 1);
+    // end conv: [m | logs] = wn_out @ Wend^T + b   (N = 160: blocks 0..4, block 5 is the image's zero padding)
+    f32x16_t acc2[3];
+    acc_zero<3>(acc2);
+    gemm_run<3, H / 16>(static_cast<const bf16_t*>(a.w_end), a.ks_end, 3 * wn, As + (32 * wm + r) * AP + 8 * h, lane, ring2, acc2);
+    if (HEAD) gemm_prefetch<3, HALF / 16>(static_cast<const bf16_t*>(a.w_start), a.ks_start, 3 * wn, lane, ring3);
+    // z into the u tile (the acts slices under it are dead: every wave is past the skip GEMM); the coupling below works in place,
+    // every thread on the items it writes here
+    auto z_put = [&](int k, const float4& v0, const float4& v1) {
+      const int item = threadIdx.x + 256 * k, row = item / 20, c = 4 * (item - row * 20);
+      *reinterpret_cast<float4*>(Zt + row * ZP + c) = v0;
+      *reinterpret_cast<float4*>(Zt + row * ZP + HALF + c) = v1;
+    };
+    z_put(0, za0, zb0); z_put(1, za1, zb1); z_put(2, za2, zb2); z_put(3, za3, zb3); z_put(4, za4, zb4);
+#pragma unroll
+    for (int bn = 0; bn < 3; ++bn)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
+        if (n < C) {
+          const float4 b4 = *reinterpret_cast<const float4*>(Bs + H + n);
+          *reinterpret_cast<float4*>(Ot + (32 * wm + r) * ZP + n) =
+              make_float4(acc2[bn][4 * g] + b4.x, acc2[bn][4 * g + 1] + b4.y, acc2[bn][4 * g + 2] + b4.z, acc2[bn][4 * g + 3] + b4.w);
+        }
+      }
+    __syncthreads();
+    // inverse coupling on (row, 4 channels): u = [z0 | (z1 - m) exp(-logs) mask]   (attentions.py:178-180, as gt_coupling_rev)
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      const int item = threadIdx.x + 256 * k, row = item / 20, c = 4 * (item - row * 20);
+      const float rm = Rm[row];
+      const float4 mm = *reinterpret_cast<const float4*>(Ot + row * ZP + c);
+      const float4 lr = *reinterpret_cast<const float4*>(Ot + row * ZP + HALF + c);
+      float lg[4] = {lr.x, lr.y, lr.z, lr.w};
+      if (a.sigmoid_scale) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lg[j] = __logf(1e-6f + sigmoidf_(lg[j] + 2.0f));
+      }
+      const float4 z1 = *reinterpret_cast<const float4*>(Zt + row * ZP + HALF + c);
+      *reinterpret_cast<float4*>(Zt + row * ZP + HALF + c) =
+          make_float4((z1.x - mm.x) * __expf(-lg[0]) * rm, (z1.y - mm.y) * __expf(-lg[1]) * rm,
+                      (z1.z - mm.z) * __expf(-lg[2]) * rm, (z1.w - mm.w) * __expf(-lg[3]) * rm);
+    }
+    __syncthreads();
+    // InvConvNear^-1 then ActNorm^-1 on (row, channel group g), members {2g, 2g+1, 80+2g, 80+2g+1} (modules.py:647-652, 592-594, as
+    // gt_actnorm_invconv_rev): x = ((W^-1 u) mask - bias) exp(-logs) mask, W^-1[k][j] = scal[2 + 4 j + k].  thread = (group, row
+    // phase): the group's sixteen weights, four scales and four biases are formed once per thread
+    {
+      constexpr int NPH = 256 / G;                             // 6 row phases of 40 threads (16 threads idle)
+      const int g = threadIdx.x % G, ph = threadIdx.x / G;
+      if (ph < NPH) {
+        float Wi[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) Wi[i] = a.scal[2 + i];
+        const float e0 = __expf(-a.an_logs[2 * g]), e1 = __expf(-a.an_logs[2 * g + 1]);
+        const float e2 = __expf(-a.an_logs[HALF + 2 * g]), e3 = __expf(-a.an_logs[HALF + 2 * g + 1]);
+        const float c0 = a.an_bias[2 * g], c1 = a.an_bias[2 * g + 1], c2 = a.an_bias[HALF + 2 * g], c3 = a.an_bias[HALF + 2 * g + 1];
+#pragma unroll
+        for (int k = 0; k < (BM + NPH - 1) / NPH; ++k) {
+          const int row = ph + NPH * k, gm = m0 + row;
+          if (row < BM) {
+            const float rm = Rm[row];
+            const float2 ua = *reinterpret_cast<const float2*>(Zt + row * ZP + 2 * g);
+            const float2 ub = *reinterpret_cast<const float2*>(Zt + row * ZP + HALF + 2 * g);
+            float o[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = (Wi[q] * ua.x + Wi[4 + q] * ua.y + Wi[8 + q] * ub.x + Wi[12 + q] * ub.y) * rm;
+            o[0] = (o[0] - c0) * e0 * rm; o[1] = (o[1] - c1) * e1 * rm; o[2] = (o[2] - c2) * e2 * rm; o[3] = (o[3] - c3) * e3 * rm;
+            if (gm < R) {
+              if (a.x) {
+                *reinterpret_cast<float2*>(a.x + (size_t)gm * C + 2 * g) = make_float2(o[0], o[1]);
+                *reinterpret_cast<float2*>(a.x + (size_t)gm * C + HALF + 2 * g) = make_float2(o[2], o[3]);
+              }
+              if (!HEAD && a.x_bct) {                                // the unsqueeze: straight into [B, 80, T] (pre-zeroed by the caller)
+                const int b = (int)a.rowbatch[gm], t = a.rowframe[gm];
+                if (t >= 0 && t < a.len[b]) {
+                  float* d0 = a.x_bct + ((size_t)b * HALF + 2 * g) * a.T + 2 * t;
+                  d0[0] = o[0]; d0[(size_t)a.T] = o[1]; d0[1] = o[2]; d0[(size_t)a.T + 1] = o[3];
+                }
+              }
+            }
+            if (HEAD) *reinterpret_cast<uint32_t*>(X0t + row * XP + 2 * g) = pack2bf(o[0], o[1]);
+          }
+        }
+      }
+    }
+  } else {
+    // first launch of the pass: the squeezed latent rows are the flow state; only the start conv of the last block runs
+    gemm_prefetch<3, HALF / 16>(static_cast<const bf16_t*>(a.w_start), a.ks_start, 3 * wn, lane, ring3);
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      const int item = threadIdx.x + 256 * k, row = item / 40, c = 4 * (item - row * 40), gm = m0 + row;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (gm < R) {
+        if (a.z_bct) {                                             // the squeeze: straight from [B, 80, T]
+          const int b = (int)a.rowbatch[gm], t = a.rowframe[gm];
+          if (t >= 0 && t < a.len[b]) v = sq_gather4(a.z_bct, b, t, c, a.T);
+          *reinterpret_cast<float4*>(a.x + (size_t)gm * C + c) = v;  // the squeezed rows: what the next launch's tail reads
+        } else v = *reinterpret_cast<const float4*>(a.x_in + (size_t)gm * C + c);
+      }
+      if (c < HALF) *reinterpret_cast<uint2*>(X0t + row * XP + c) = pack4(v.x, v.y, v.z, v.w);
+    }
+  }
+  if (!HEAD) return;
+  __syncthreads();
+  // start conv of block b-1: h = (x0 @ Wstart^T + b) * mask   (K = 80: 5 k-steps)
+  {
+    f32x16_t acc3[3];
+    acc_zero<3>(acc3);
+    gemm_run<3, HALF / 16>(static_cast<const bf16_t*>(a.w_start), a.ks_start, 3 * wn, X0t + (32 * wm + r) * XP + 8 * h, lane, ring3, acc3);
+    bf16_t* Hst = reinterpret_cast<bf16_t*>(smem + F_O);             // the m | logs tile is dead: the h tile on its way out
+#pragma unroll
+    for (int bn = 0; bn < 3; ++bn)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
+        const float4 b4 = *reinterpret_cast<const float4*>(Bs + 2 * H + n);
+        *reinterpret_cast<uint2*>(Hst + (32 * wm + r) * AP + n) =
+            pack4((acc3[bn][4 * g] + b4.x) * rm_l, (acc3[bn][4 * g + 1] + b4.y) * rm_l,
+                  (acc3[bn][4 * g + 2] + b4.z) * rm_l, (acc3[bn][4 * g + 3] + b4.w) * rm_l);
+      }
+    __syncthreads();
+    coop_store_rows(static_cast<bf16_t*>(a.h_next), H, Hst, m0, R);
+  }
+}
+
 template <typename K>
 int opt_in_lds(K kernel, int bytes)
 {
@@ -840,6 +1054,48 @@ extern "C" int gt_wn_boundary_fwd(const gt_boundary_fwd_args* args, void* stream
   if (tail && head) hipLaunchKernelGGL((gt_wn_boundary_fwd_kernel<true, true>), grid, block, FWD_LDS, st, a);
   else if (tail)    hipLaunchKernelGGL((gt_wn_boundary_fwd_kernel<true, false>), grid, block, FWD_LDS, st, a);
   else              hipLaunchKernelGGL((gt_wn_boundary_fwd_kernel<false, true>), grid, block, FWD_LDS, st, a);
+  return gt_launch_status(__func__);
+}
+
+extern "C" int gt_boundary_rev_args_size(void) { return (int)sizeof(gt_boundary_rev_args); }
+
+extern "C" int gt_wn_boundary_rev(const gt_boundary_rev_args* args, void* stream)
+{
+  if (!args) return GT_E_INVAL;
+  const gt_boundary_rev_args& a = *args;
+  if (a.R < 0) return GT_E_INVAL;
+  if (a.R == 0) return GT_OK;
+  if (a.H != H || a.C != C || a.n_layers != NL) return GT_E_INVAL;
+  const bool tail = a.acts != nullptr, head = a.h_next != nullptr;
+  if (!tail && !head) return GT_E_INVAL;
+  if (!a.rowmask) return GT_E_INVAL;
+  if ((a.z_bct || a.x_bct) && (!a.rowbatch || !a.rowframe || !a.len || a.T <= 0 || (a.T & 1))) return GT_E_INVAL;
+  if (tail) {
+    if (!a.w_skip || !a.b_skip || !a.w_end || !a.b_end || !a.z || !a.an_logs || !a.an_bias || !a.scal || (!a.x && !a.x_bct)) return GT_E_INVAL;
+    if (a.x_bct && head) return GT_E_INVAL;                 // the unsqueeze belongs to the last launch of a pass
+    if (head && !a.x) return GT_E_INVAL;
+    if (a.ldacts < NL * H || (a.ldacts & 7) || a.ks_end < H / 16) return GT_E_INVAL;
+    if (!al16(a.acts) || !al16(a.w_skip) || !al16(a.w_end) || !al16(a.b_skip) || !al16(a.b_end) || !al16(a.z) || !al16(a.x)) return GT_E_ALIGN;
+  } else {
+    if (a.z_bct ? !a.x : !a.x_in) return GT_E_INVAL;        // the squeezed rows are written out for the next launch's tail
+    if (!al16(a.x_in) || !al16(a.x)) return GT_E_ALIGN;
+  }
+  if (head) {
+    if (!a.w_start || !a.b_start || a.ks_start < HALF / 16) return GT_E_INVAL;
+    if (!al16(a.w_start) || !al16(a.b_start) || !al16(a.h_next)) return GT_E_ALIGN;
+  }
+  for (int i = 0; i < 16; ++i) if (a.pf_ptr[i] && (!al16(a.pf_ptr[i]) || (a.pf_bytes[i] & 15))) return GT_E_ALIGN;
+  static bool attr = false;                    // > 64 KB of LDS: opt in once per process
+  if (!attr) {
+    if (opt_in_lds(&gt_wn_boundary_rev_kernel<true, true>, REV_LDS) || opt_in_lds(&gt_wn_boundary_rev_kernel<true, false>, REV_LDS) ||
+        opt_in_lds(&gt_wn_boundary_rev_kernel<false, true>, REV_LDS)) return GT_E_LAUNCH;
+    attr = true;
+  }
+  const dim3 grid((a.R + BM - 1) / BM + (a.pf_ptr[0] ? PF_WGS : 0)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (tail && head) hipLaunchKernelGGL((gt_wn_boundary_rev_kernel<true, true>), grid, block, REV_LDS, st, a);
+  else if (tail)    hipLaunchKernelGGL((gt_wn_boundary_rev_kernel<true, false>), grid, block, REV_LDS, st, a);
+  else              hipLaunchKernelGGL((gt_wn_boundary_rev_kernel<false, true>), grid, block, REV_LDS, st, a);
   return gt_launch_status(__func__);
 }
 

@@ -88,7 +88,12 @@ __device__ __forceinline__ T pick(T const (&arr)[NLMAX], int i)        // scalar
 // 64-row tiles would leave most of the chip idle (cfg 4 / cfg 5's 4-5 k rows: 90 workgroups on 256 CUs): 2.6 x the workgroups, each
 // with half the MFMA rows but the same weight stream.  The LDS layout is the 64-row one either way; every row's arithmetic (K order,
 // dropout hash, epilogue) is the same, so the results are bit-identical between the two forms.
-template <int COND, bool DROP, int NBM>
+// SAVE: the saved tanh / sigmoid halves and every x_i go to HBM for a backward (training); false = synthesis: acts only (the tiles
+// those outputs pass through are then never written).  Built for COND 0 / 1 without dropout, where the arithmetic that produces acts
+// compiles to the same instructions either way (equality is tested).  NOT built for COND == 2: whether `b + contour * w` becomes one
+// fused operation or a multiply and an add is the compiler's choice per instantiation, and an acts-only <2, false, 2> differed from
+// the saving one in the last bf16 bit of 16 of 4.9 M acts — the affine WaveNets of a synthesis pass run the saving kernel.
+template <int COND, bool DROP, int NBM, bool SAVE = true>
 __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_args a, uint32_t drop_thresh, float drop_scale)
 {
   constexpr int BMv = 32 * NBM, XRv = BMv + TAPS - 1;
@@ -324,8 +329,10 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
           }
           // T, S and acts leave through LDS: straight from the MFMA layout a store instruction writes 16 bytes to each of 32
           // rows (2.6 M partial-line requests per launch, the "17 us of stores" of DESIGN 4.9); the tiles below go out as whole rows
-          *reinterpret_cast<uint2*>(Tl + t * AP + c) = pack4(tt[0], tt[1], tt[2], tt[3]);
-          *reinterpret_cast<uint2*>(Sl + t * AP + c) = pack4(ss[0], ss[1], ss[2], ss[3]);
+          if (SAVE) {
+            *reinterpret_cast<uint2*>(Tl + t * AP + c) = pack4(tt[0], tt[1], tt[2], tt[3]);
+            *reinterpret_cast<uint2*>(Sl + t * AP + c) = pack4(ss[0], ss[1], ss[2], ss[3]);
+          }
           *reinterpret_cast<uint2*>(At + t * AP + c) = pack4(aa[0], aa[1], aa[2], aa[3]);
         }
       }
@@ -345,7 +352,7 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
           const int idx = tid_e + 256 * (i0 + i), row = idx / CPR, c8 = idx - row * CPR, t = halo + row;
           vt[i] = vs[i] = va[i] = make_uint4(0, 0, 0, 0);
           if (idx < own * CPR) {
-            vt[i] = *reinterpret_cast<const uint4*>(Tl + t * AP + c8 * 8); vs[i] = *reinterpret_cast<const uint4*>(Sl + t * AP + c8 * 8);
+            if (SAVE) { vt[i] = *reinterpret_cast<const uint4*>(Tl + t * AP + c8 * 8); vs[i] = *reinterpret_cast<const uint4*>(Sl + t * AP + c8 * 8); }
             va[i] = *reinterpret_cast<const uint4*>(At + t * AP + c8 * 8);
           }
         }
@@ -353,8 +360,10 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
         for (int i = 0; i < NP; ++i) {
           const int idx = tid_e + 256 * (i0 + i), row = idx / CPR, c8 = idx - row * CPR, m = s0 + halo + row;
           if (idx < own * CPR && m < R) {
-            *reinterpret_cast<uint4*>(Tt + (size_t)m * H + c8 * 8) = vt[i];
-            *reinterpret_cast<uint4*>(Ss + (size_t)m * H + c8 * 8) = vs[i];
+            if (SAVE) {
+              *reinterpret_cast<uint4*>(Tt + (size_t)m * H + c8 * 8) = vt[i];
+              *reinterpret_cast<uint4*>(Ss + (size_t)m * H + c8 * 8) = vs[i];
+            }
             *reinterpret_cast<uint4*>(acts + (size_t)m * a.ldacts + c8 * 8) = va[i];
           }
         }
@@ -404,7 +413,7 @@ __global__ __launch_bounds__(256) void gt_wn_stack_fwd_kernel(gt_wn_stack_fwd_ar
     __syncthreads();                                                   // the next layer's input is complete; Xc and At are free
     PH(6 + 6 * layer);
     bf16_t* tmp = Xc; Xc = Xn; Xn = tmp;
-    {                                                                // x_next of the owned rows, whole rows from the finished tile
+    if (SAVE) {                                                      // x_next of the owned rows, whole rows from the finished tile
       constexpr int NC = (BM * CPR + 255) / 256, NP = 3;
 #pragma unroll 1
       for (int i0 = 0; i0 < NC; i0 += NP) {
@@ -859,9 +868,17 @@ extern "C" int gt_wn_stack_fwd(const gt_wn_stack_fwd_args* args, void* stream)
   if (a.H != H || a.taps != TAPS || a.n_layers < 1 || a.n_layers > NLMAX) return GT_E_UNSUPPORTED;
   if (!a.x0 || !a.rowmask || !a.acts || a.ldacts < a.n_layers * H || (a.ldacts & 7) || (a.cond && (a.ldc & 3))) return GT_E_INVAL;
   if (!al16(a.x0) || !al16(a.acts) || !al16(a.cond)) return GT_E_ALIGN;
+  // the backward's saves (gate_t, gate_s, x_out): every one of them, or none (synthesis: acts only)
+  int n_save = 0, n_given = 0;
   for (int i = 0; i < a.n_layers; ++i) {
-    if (!a.w_in[i] || !a.b_in[i] || !a.gate_t[i] || !a.gate_s[i]) return GT_E_INVAL;
-    if (i < a.n_layers - 1 && (!a.w_res[i] || !a.b_res[i] || !a.x_out[i])) return GT_E_INVAL;
+    n_save += 2 + (i < a.n_layers - 1);
+    n_given += (a.gate_t[i] != nullptr) + (a.gate_s[i] != nullptr) + (i < a.n_layers - 1 && a.x_out[i] != nullptr);
+  }
+  if (n_given != 0 && n_given != n_save) return GT_E_INVAL;
+  const bool save = n_given != 0;
+  for (int i = 0; i < a.n_layers; ++i) {
+    if (!a.w_in[i] || !a.b_in[i]) return GT_E_INVAL;
+    if (i < a.n_layers - 1 && (!a.w_res[i] || !a.b_res[i])) return GT_E_INVAL;
     if (!al16(a.w_in[i]) || !al16(a.b_in[i]) || !al16(a.gate_t[i]) || !al16(a.gate_s[i]) || !al16(a.w_res[i]) || !al16(a.b_res[i]) ||
         !al16(a.x_out[i])) return GT_E_ALIGN;
   }
@@ -879,11 +896,18 @@ extern "C" int gt_wn_stack_fwd(const gt_wn_stack_fwd_args* args, void* stream)
                                    gt_wn_stack_fwd_kernel<1, true, 2>, gt_wn_stack_fwd_kernel<2, false, 2>, gt_wn_stack_fwd_kernel<2, true, 2>,
                                    gt_wn_stack_fwd_kernel<0, false, 1>, gt_wn_stack_fwd_kernel<0, true, 1>, gt_wn_stack_fwd_kernel<1, false, 1>,
                                    gt_wn_stack_fwd_kernel<1, true, 1>, gt_wn_stack_fwd_kernel<2, false, 1>, gt_wn_stack_fwd_kernel<2, true, 1>};
+  // acts only (the synthesis direction: no dropout; no affine conditioning, see SAVE), [row form][COND]
+  static const kern_t kerns_nosave[4] = {gt_wn_stack_fwd_kernel<0, false, 2, false>, gt_wn_stack_fwd_kernel<1, false, 2, false>,
+                                         gt_wn_stack_fwd_kernel<0, false, 1, false>, gt_wn_stack_fwd_kernel<1, false, 1, false>};
+  if (!save && (thresh || affine)) return GT_E_UNSUPPORTED;
   static bool attr = false;                    // > 64 KB of LDS: opt in once per process
   if (!attr) {
     for (int i = 0; i < 12; ++i)
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(kerns[i]), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (i % 6) >= 4 ? STACK_FWD_LDS_AFF : STACK_FWD_LDS) != hipSuccess)
+        return GT_E_LAUNCH;
+    for (int i = 0; i < 4; ++i)
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kerns_nosave[i]), hipFuncAttributeMaxDynamicSharedMemorySize, STACK_FWD_LDS) != hipSuccess)
         return GT_E_LAUNCH;
     attr = true;
   }
@@ -891,8 +915,8 @@ extern "C" int gt_wn_stack_fwd(const gt_wn_stack_fwd_args* args, void* stream)
   const int own = 32 * nbm - 4 * (a.n_layers - 1);
   const dim3 grid((a.R + own - 1) / own), block(256);
   const int mode = affine ? 2 : (a.cond ? 1 : 0);
-  hipLaunchKernelGGL(kerns[(nbm == 1 ? 6 : 0) + 2 * mode + (thresh ? 1 : 0)], grid, block, affine ? STACK_FWD_LDS_AFF : STACK_FWD_LDS,
-                     static_cast<hipStream_t>(stream), a, thresh, scale);
+  const kern_t kern = save ? kerns[(nbm == 1 ? 6 : 0) + 2 * mode + (thresh ? 1 : 0)] : kerns_nosave[(nbm == 1 ? 2 : 0) + mode];
+  hipLaunchKernelGGL(kern, grid, block, affine ? STACK_FWD_LDS_AFF : STACK_FWD_LDS, static_cast<hipStream_t>(stream), a, thresh, scale);
   return gt_launch_status(__func__);
 }
 

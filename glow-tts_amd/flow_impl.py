@@ -159,7 +159,7 @@ def _stack_pays(R, n, dev):
     return rounds(own) <= rounds(64)
 
 
-def wn_fwd(rc, wn, h0, cond, train, seed, cond_per_row=False, layers_only=False, affine=None):
+def wn_fwd(rc, wn, h0, cond, train, seed, cond_per_row=False, layers_only=False, affine=None, save=True):
     """modules.WN.forward on rows.  h0: [R,H] bf16 (masked).  cond: [B, 2*H*n_layers] fp32 or None; with cond_per_row
     it is [R, 2*H*n_layers] — the per-frame conditioning of modules.WNP.forward (modules.py:316-343), whose loop is WN's.
     Returns out [R,H] bf16 (= skip sum * mask) and saved activations.
@@ -169,7 +169,10 @@ def wn_fwd(rc, wn, h0, cond, train, seed, cond_per_row=False, layers_only=False,
     single K = n*H GEMM at the end instead of n read-modify-write passes over an fp32 accumulator.
     affine = (sig [R, 2], w [O], b [O]): modules.WNP's per-frame conditioning in its affine form (cond_layer1 has one input channel):
     the whole-WaveNet kernel forms it from the row's two contour values (no [R, 2*H*n] fp32 rows); the per-layer path
-    materialises it (cond_rows) as before."""
+    materialises it (cond_rows) as before.
+    save=False (synthesis, no dropout): the whole-WaveNet kernel stores the gated activations only — no tanh / sigmoid halves, no x_i
+    (the saved tuple then holds empty lists for them); the per-layer kernels always write them, and so does the whole-WaveNet kernel
+    under affine conditioning (its acts-only form is built for cond / no conditioning only: csrc/wn_stack.hip, SAVE)."""
     L = _lib.lib()
     R, H = h0.shape
     dev = h0.device
@@ -186,17 +189,19 @@ def wn_fwd(rc, wn, h0, cond, train, seed, cond_per_row=False, layers_only=False,
     if fused and getattr(wn, "stack_fwd", True) and n <= 4 and _stack_pays(R, n, dev):
         # all layers in ONE launch (csrc/wn_stack.hip: the 2-row halo between layers is recomputed, not exchanged)
         import ctypes
-        ts = [torch.empty(R, H, dtype=torch.bfloat16, device=dev) for _ in range(n)]
-        ss = [torch.empty(R, H, dtype=torch.bfloat16, device=dev) for _ in range(n)]
-        xs = [h0] + [torch.empty(R, H, dtype=torch.bfloat16, device=dev) for _ in range(n - 1)]
+        save = save or p > 0 or affine is not None
+        ts = [torch.empty(R, H, dtype=torch.bfloat16, device=dev) for _ in range(n)] if save else []
+        ss = [torch.empty(R, H, dtype=torch.bfloat16, device=dev) for _ in range(n)] if save else []
+        xs = [h0] + ([torch.empty(R, H, dtype=torch.bfloat16, device=dev) for _ in range(n - 1)] if save else [])
         pad = [None] * (4 - n)
+        nul = [None] * n
         args = _lib.fill_args(
             _lib.WnStackFwdArgs, x0=h0, w_in=[il.pc.fwd for il in wn.in_layers] + pad, b_in=[il.bias for il in wn.in_layers] + pad,
             w_res=[rs.pc_res.fwd for rs in wn.res_skip_layers[:n - 1]] + [None] + pad,
             b_res=[rs.bias for rs in wn.res_skip_layers[:n - 1]] + [None] + pad,
             cond=cond, ldc=0 if cond is None else cond.stride(0), row0=rc.row0 if (cond is not None and not cond_per_row) else None,
             B=0 if (cond_per_row or cond is None) else rc.B, Tp=rc.Tp, rowmask=rc.rowmask, acts=acts_all, ldacts=acts_all.stride(0),
-            gate_t=ts + pad, gate_s=ss + pad, x_out=xs[1:] + [None] + pad, R=R, H=H, taps=wn.kernel_size, n_layers=n,
+            gate_t=(ts or nul) + pad, gate_s=(ss or nul) + pad, x_out=(xs[1:] or nul[1:]) + [None] + pad, R=R, H=H, taps=wn.kernel_size, n_layers=n,
             drop_p=float(p), drop_seed=int(seed), seed_dev=seed_word(dev) if p > 0 else None,
             stamps=stamps.buf if stamps else None, stamp_slot=stamps.take(f"stack{n}") if stamps else 0, stamp_base=stamps.base if stamps else None,
             **(dict(aff_w=aff_w, aff_b=aff_b, aff_sig=aff_sig) if affine is not None else {}))
@@ -775,3 +780,66 @@ def coupling_rev(rc, cb, z, z0_bf16, cond, econd=None, pcond=None):
     _lib.check(L.gt_coupling_rev(_lib.ptr(out), _lib.ptr(z), _lib.ptr(x), _lib.ptr(rc.rowmask), R, C, int(cb.sigmoid_scale),
                                  _st(dev)), "gt_coupling_rev")
     return x
+
+
+def decoder_rev_fused(rc, dec, rows, conds, z_bct=None, x_bct=None, esig=None, eaff=None, psig=None, paff=None):
+    """The mirror of decoder_fwd_fused for synthesis: ONE kernel between consecutive WaveNets (gt_wn_boundary_rev: the inverse maps
+    of block b — skip GEMM, end conv, coupling^-1, InvConvNear^-1, ActNorm^-1 — and block b-1's start conv) and the WaveNets in
+    acts-only mode: n_blocks + 1 boundary launches (head-only, n_blocks - 1 with both halves, tail-only) + one launch per WaveNet.
+    rows [R, C] fp32 (the squeezed latent), conds[b]: [B, 2*H*n] or None.  Returns the decoder's input-side rows x [R, C].
+    z_bct / x_bct ([B, C/2, T] fp32, T even, x_bct pre-zeroed): the public boundary — the first launch then squeezes (rows = None),
+    the last one unsqueezes (None is returned).  With pitch / energy contours a block is a chain of up to three WaveNets (block_chain):
+    the boundary kernel sits behind the last one, a skip GEMM (conv_rows) between two of them; the affine-conditioned ones run the
+    saving form of the WaveNet kernel (wn_fwd).  The flow scalars are
+    FlowSpecDecoder.store_inverse's cache when there is one."""
+    import ctypes
+    L = _lib.lib()
+    dev = rc.rowmask.device
+    R, C = rc.R, 2 * dec.in_channels
+    H, nb, n = dec.hidden_channels, dec.n_blocks, dec.n_layers
+    scal = dec._inv_cache if dec._inv_cache is not None else flow_scalars_all(dec)[0]
+    f32 = dict(dtype=torch.float32, device=dev)
+    state = rows                                           # the flow state the next launch's tail reads
+    acts_all, last_wn = None, None
+    for k in range(nb + 1):
+        bt, bh = nb - k, nb - 1 - k                        # tail of block bt (k > 0), head of block bh (k < nb)
+        kw = dict(rowmask=rc.rowmask, R=R, H=H, C=C, n_layers=n)
+        x = None
+        if k > 0:
+            an, cb = dec.flows[3 * bt], dec.flows[3 * bt + 2]
+            last_out = k == nb and x_bct is not None
+            x = None if last_out else torch.empty(R, C, **f32)
+            kw.update(acts=acts_all, ldacts=acts_all.stride(0), w_skip=last_wn.pc_skipcat_frag.fwd, b_skip=last_wn.skip_bias,
+                      w_end=cb.end.pc_frag.fwd, b_end=cb.end.bias, ks_end=cb.end.pc_frag.Kp_f // 16, z=state,
+                      sigmoid_scale=int(cb.sigmoid_scale), an_logs=an.logs, an_bias=an.bias, scal=scal[bt], x=x)
+            if last_out:
+                kw.update(x_bct=x_bct, T=x_bct.shape[2], rowbatch=rc.rowbatch, rowframe=rc.rowframe, len=rc.lengths)
+        elif rows is None:
+            x = torch.empty(R, C, **f32)                   # the first launch writes the squeezed rows
+            kw.update(z_bct=z_bct, T=z_bct.shape[2], rowbatch=rc.rowbatch, rowframe=rc.rowframe, len=rc.lengths, x=x)
+        else:
+            kw.update(x_in=rows)
+            x = rows
+        h0 = None
+        if k < nb:
+            cb = dec.flows[3 * bh + 2]
+            h0 = torch.empty(R, H, dtype=torch.bfloat16, device=dev)
+            kw.update(w_start=cb.start.pc_frag.fwd, b_start=cb.start.bias, ks_start=cb.start.pc_frag.Kp_f // 16, h_next=h0)
+            if _fused_ok(cb.wn):                           # the WaveNet launch that follows: its images are read once by this launch's spare CUs
+                kw["pf_ptr"], kw["pf_bytes"] = _prefetch_list(cb.wn, "fwd")
+        args = _lib.fill_args(_lib.BoundaryRevArgs, **kw)
+        if BOUNDARY_TRACE is not None:
+            BOUNDARY_TRACE.append(("gt_wn_boundary_rev", args, kw))
+        _ev = KERNEL_TIMER.start("wn_boundary_rev")
+        rcode = L.gt_wn_boundary_rev(ctypes.byref(args), _st(dev))
+        KERNEL_TIMER.stop(_ev)
+        _lib.check(rcode, "gt_wn_boundary_rev")
+        state = x
+        if k < nb:
+            chain = block_chain(dec.flows[3 * bh + 2], conds[bh], esig, None if eaff is None else eaff[bh], psig, None if paff is None else paff[bh])
+            h = h0
+            for j, (w, c, aff) in enumerate(chain):
+                last = j == len(chain) - 1
+                h, sv = wn_fwd(rc, w, h, c, False, 0, layers_only=last, affine=aff, save=False)
+            acts_all, last_wn = sv[3], chain[-1][0]
+    return state

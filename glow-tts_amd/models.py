@@ -34,6 +34,7 @@ class FlowSpecDecoder(nn.Module):
         self._step = 0
         self._inv_cache = None
         self.fused_boundary = False
+        self.fused_reverse = False
         self.set_fused_boundary(True)
 
     def set_fused_boundary(self, on):
@@ -47,11 +48,25 @@ class FlowSpecDecoder(nn.Module):
                 self.flows[3 * b + 2].set_boundary_fused(False)
         return self.fused_boundary
 
-    def store_inverse(self):
+    def set_fused_reverse(self, on=True):
+        """Synthesis (reverse=True) with ONE kernel between consecutive WaveNets (gt_wn_boundary_rev, csrc/wn_boundary.hip) and the
+        WaveNets in acts-only mode (flow_impl.decoder_rev_fused): n_blocks + 1 boundary launches + one per WaveNet instead of six
+        launches per block.  Returns whether the fused path takes effect: it reads the fragment-ordered images of the fused forward
+        boundary, so it needs set_fused_boundary on and the shape those kernels are built for (C = 160, H = 192, 4 layers).  Off
+        (the default) = round 1's launch sequence, the path the fused one is tested against.  Reverse calls with pitch / energy
+        contours run the fused path too (a skip GEMM between the chained WaveNets of a block, the reverse kernel behind the last; the
+        affine-conditioned WaveNets keep the saving form of their kernel);
+        a decoder whose ActNorm still waits for its data-dependent init falls back to the launch sequence for that call."""
+        self.fused_reverse = bool(on) and self.fused_boundary
+        return self.fused_reverse
+
+    def store_inverse(self, fused_reverse=None):
         """models.py:787-789 -> modules.py:667-668 / attentions.py:188-194: freeze the decoder for synthesis.  The
         reference caches W^-1 and folds the weight norms away; here the packed bf16 weight images and every block's flow
         scalars (sum logs, logdet W, W^-T) are computed ONCE and reverse calls reuse them (no per-call re-pack) until
-        `clear_inverse()` or a training-mode forward."""
+        `clear_inverse()` or a training-mode forward.  fused_reverse (True / False): also set_fused_reverse; None leaves the switch."""
+        if fused_reverse is not None:
+            self.set_fused_reverse(fused_reverse)
         for f in self.flows:
             f.store_inverse()
         prepare_all(self)
@@ -181,18 +196,28 @@ class _DecoderRunner:
         len_sq = (_mask_lengths(self.x_mask) // 2).to(torch.int32)
         rc = ops.make_ctx(len_sq, T2, "y", div=2, cfg=self.cfg)
         zin = z.float().contiguous()
-        cur = torch.empty(rc.R, 2 * C, dtype=torch.float32, device=dev)
         st = _lib.current_stream(dev)
-        _lib.check(L.gt_squeeze_rows_f32(_lib.ptr(zin), _lib.ptr(cur), _lib.ptr(rc.lengths), B, C, T, rc.Tp, _lib.ptr(rc.row0), st), "gt_squeeze_rows_f32")
-        x0 = torch.empty(rc.R, C, dtype=torch.bfloat16, device=dev)
-        _lib.check(L.gt_rows_f32_to_bf16(_lib.ptr(cur), 2 * C, _lib.ptr(x0), C, None, rc.R, C, st), "gt_rows_f32_to_bf16")
         esig, psig = self._contour_rows(rc, self.energy, B, T2 * 2), self._contour_rows(rc, self.pitch, B, T2 * 2)
-        for b in reversed(range(dec.n_blocks)):
-            an, ic, cb = dec.flows[3 * b], dec.flows[3 * b + 1], dec.flows[3 * b + 2]
-            cur = flow_impl.coupling_rev(rc, cb, cur, x0, conds[b], econd=self._cond_rows(esig, None if eaff is None else eaff[b]),
-                                         pcond=self._cond_rows(psig, None if paff is None else paff[b]))
-            cur, x0 = flow_impl.actnorm_invconv_rev(rc, cur, an.logs, an.bias, ic.weight, want_x0=b > 0,
-                                                    scal=None if dec._inv_cache is None else dec._inv_cache[b])
+        # one kernel between consecutive WaveNets (FlowSpecDecoder.set_fused_reverse) unless a block still waits for its ActNorm init
+        fused = dec.fused_reverse and dec.fused_boundary and all(dec.flows[3 * b].initialized for b in range(dec.n_blocks))
+        pros = dict(esig=esig, eaff=eaff, psig=psig, paff=paff)
+        if fused and T == T2 * 2 and getattr(rc, "rowbatch", None) is not None:     # squeeze / unsqueeze ride in its first / last launch
+            x = ops.zeros_big((B, C, T), torch.float32, dev)
+            flow_impl.decoder_rev_fused(rc, dec, None, conds, z_bct=zin, x_bct=x, **pros)
+            return x.to(z.dtype)
+        cur = torch.empty(rc.R, 2 * C, dtype=torch.float32, device=dev)
+        _lib.check(L.gt_squeeze_rows_f32(_lib.ptr(zin), _lib.ptr(cur), _lib.ptr(rc.lengths), B, C, T, rc.Tp, _lib.ptr(rc.row0), st), "gt_squeeze_rows_f32")
+        if fused:
+            cur = flow_impl.decoder_rev_fused(rc, dec, cur, conds, **pros)
+        else:
+            x0 = torch.empty(rc.R, C, dtype=torch.bfloat16, device=dev)
+            _lib.check(L.gt_rows_f32_to_bf16(_lib.ptr(cur), 2 * C, _lib.ptr(x0), C, None, rc.R, C, st), "gt_rows_f32_to_bf16")
+            for b in reversed(range(dec.n_blocks)):
+                an, ic, cb = dec.flows[3 * b], dec.flows[3 * b + 1], dec.flows[3 * b + 2]
+                cur = flow_impl.coupling_rev(rc, cb, cur, x0, conds[b], econd=self._cond_rows(esig, None if eaff is None else eaff[b]),
+                                             pcond=self._cond_rows(psig, None if paff is None else paff[b]))
+                cur, x0 = flow_impl.actnorm_invconv_rev(rc, cur, an.logs, an.bias, ic.weight, want_x0=b > 0,
+                                                        scal=None if dec._inv_cache is None else dec._inv_cache[b])
         x = torch.empty(B, C, T2 * 2, dtype=torch.float32, device=dev)
         _lib.check(L.gt_unsqueeze_rows_f32(_lib.ptr(cur), _lib.ptr(x), _lib.ptr(rc.lengths), B, C, T2 * 2, rc.Tp, _lib.ptr(rc.row0), st), "gt_unsqueeze_rows_f32")
         return x.to(z.dtype)

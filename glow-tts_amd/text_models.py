@@ -492,10 +492,14 @@ class FlowGenerator(nn.Module):
         emosty = self.emosty_layer_norm(F.softplus(torch.cat((emos_proj, style), dim=-1)))
         return torch.cat((g, intens + emosty), dim=-1).unsqueeze(-1)
 
-    def store_inverse(self):
-        """models.py:1255-1256: freeze the model for synthesis (weights packed once, flow scalars cached)."""
+    def store_inverse(self, fused_reverse=None):
+        """models.py:1255-1256: freeze the model for synthesis (weights packed once, flow scalars cached).  fused_reverse = True / False:
+        the decoder's reverse passes (infer, the second half of voice_conversion) run one kernel between consecutive WaveNets
+        (FlowSpecDecoder.set_fused_reverse) or the launch sequence; None (as in FlowSpecDecoder.store_inverse) leaves the switch as it
+        is — off on a new model.  Returns whether the fused path is in effect."""
         self.prepare()
-        self.decoder.store_inverse()
+        self.decoder.store_inverse(fused_reverse)
+        return self.decoder.fused_reverse
 
     @torch.no_grad()
     def infer(self, x, x_lengths, y=None, y_lengths=None, g=None, emo=None, emo_cartesian=None, l=None, gst_token=None,

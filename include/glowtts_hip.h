@@ -438,6 +438,9 @@ typedef struct gt_wn_stack_fwd_args {
   void* acts; int ldacts;                       /* out: bf16 [R, >= n_layers * H], layer i in columns [H i, H (i+1)) */
   void* gate_t[4]; void* gate_s[4];             /* out: bf16 [R, H] per layer (saved tanh / sigmoid halves) */
   void* x_out[4];                               /* out: x_out[i] = input of layer i+1, bf16 [R, H], i < n_layers-1 */
+  /* gate_t / gate_s / x_out are what a BACKWARD reads.  All of them NULL (every layer): the kernel stores acts only — the
+   * synthesis direction, where they are 2/3 of the launch's writes; acts is bit-identical either way.  Needs drop_p == 0 and no
+   * affine conditioning (aff_*) (GT_E_UNSUPPORTED otherwise); a mix of NULL and non-NULL among them is GT_E_INVAL. */
   int R, H, taps, n_layers;
   float drop_p; uint32_t drop_seed; const uint32_t* seed_dev;
   unsigned long long* stamps; int stamp_slot; const int32_t* stamp_base;   /* as gt_wn_layer_fwd */
@@ -553,6 +556,45 @@ int gt_wn_boundary_bwd(const gt_boundary_bwd_args* args, void* stream);
  * [n_blocks][n_wg][gt_boundary_param_partials()], dst = DEVICE array of 3 * n_blocks pointers {d_an_logs, d_an_bias, d_w_ic} per block;
  * every destination element gets += the sum over the block's n_wg rows (modules.py:584-599, 635-665 parameter gradients) */
 int gt_boundary_param_partials(void);
+/* gt_wn_boundary_rev — the same for the REVERSE (synthesis) direction, models.py:765-785 with reverse=True: everything between the
+ * WaveNet of block b and the WaveNet of block b-1 as one launch.  No log-det, nothing kept for a backward: wn_out, [m | logs] and
+ * x0 stay in LDS; HBM receives the fp32 flow state x and the bf16 rows h_next only.
+ *   [tail of block b] when acts != NULL (acts = gt_wn_stack_fwd's gated activations of block b's last WaveNet):
+ *     wn_out = bf16((acts @ Wskipcat^T + b_skip) * mask)                         modules.py:168-171
+ *     [m | logs] = wn_out @ Wend^T + b_end;  sigmoid_scale: logs = log(1e-6 + sigmoid(logs + 2))      attentions.py:162-165, 172-173
+ *     u = [z0 | (z1 - m) * exp(-logs) * mask]                                    attentions.py:178-180 (as gt_coupling_rev)
+ *     x = ((W^-1 u) * mask - an_bias) * exp(-an_logs) * mask                     modules.py:647-652, 592-594 (as gt_actnorm_invconv_rev;
+ *                                                                                scal = the block's gt_flow_scalars, holds W^-T)
+ *   [head of block b-1] when h_next != NULL (input: the x tile, or x_in / z_bct when there is no tail):
+ *     x0 = bf16(x[:, :C/2]);  h_next = bf16((x0 @ Wstart^T + b_start) * mask)    attentions.py:147
+ * A pass over n blocks is n + 1 launches: head-only (block n-1's start conv), n - 1 with both halves, tail-only (block 0).
+ * Same contract as the forward: plain device pointers, asynchronous on the stream, no allocation, rows of either layout.
+ * GT_E_INVAL on a NULL required pointer or a shape other than H = 192, C = 160, n_layers = 4; GT_E_ALIGN on a pointer that is
+ * not 16-byte aligned.  Rows whose rowmask is 0 come out as zero in x and h_next. */
+typedef struct gt_boundary_rev_args {
+  /* tail */
+  const void* acts; int ldacts;                 /* bf16 [R, >= n_layers*H] gated activations of block b's (last) WaveNet */
+  const void* w_skip; const float* b_skip;      /* fragment-ordered forward image of the skip-cat GEMM; bias = sum of skip biases */
+  const void* w_end; const float* b_end; int ks_end;
+  const float* z;                               /* [R, C]: the flow state at block b's output (x of the previous launch) */
+  int sigmoid_scale;
+  const float* an_logs; const float* an_bias;   /* block b's ActNorm parameters [C] */
+  const float* scal;                            /* block b's flow scalars [18] (gt_flow_scalars): scal[2 ..] = W^-T */
+  float* x;                                     /* out: [R, C] the flow state at block b's input (optional with x_bct) */
+  /* head */
+  const float* x_in;                            /* head-only variant: the flow state [R, C] */
+  const void* w_start; const float* b_start; int ks_start;   /* block b-1's start conv */
+  void* h_next;                                 /* out: bf16 [R, H] */
+  const float* rowmask; int R, H, C, n_layers;
+  /* optional: commons.squeeze / unsqueeze folded into the first / last launch of the pass (T even) — z_bct (head-only variant,
+   * instead of x_in): the decoder's input [B, C/2, T] fp32, x then receives the squeezed rows; x_bct (tail-only variant, instead
+   * of or besides x): its output [B, C/2, T] fp32, pre-zeroed by the caller; rowbatch (int64) / rowframe (int32): gt_rows_ctx_fill's
+   * tables; len: int32 [B] squeezed lengths */
+  const float* z_bct; float* x_bct; int T; const int64_t* rowbatch; const int32_t* rowframe; const int32_t* len;
+  const void* pf_ptr[16]; uint32_t pf_bytes[16];  /* optional prefetch list (the next WaveNet's weight images), as in the forward */
+} gt_boundary_rev_args;
+int gt_wn_boundary_rev(const gt_boundary_rev_args* args, void* stream);
+int gt_boundary_rev_args_size(void);            /* sizeof(gt_boundary_rev_args): lets a binding check its mirror of the struct */
 int gt_boundary_param_reduce(const float* partials, int n_wg, int n_blocks, float* const* dst, void* stream);
 
 /* ---- One WaveNet layer as ONE kernel (modules.WN.forward, one loop iteration, modules.py:151-170; csrc/wn_layer.hip).

@@ -1,0 +1,135 @@
+"""dev: synthesis time of the flow decoder, reverse=True, launch sequence vs fused path (FlowSpecDecoder.set_fused_reverse).
+
+A cfg 2 decoder (12 blocks x 4 layers, H = 192) after store_inverse; `dec(z, mask, reverse=True)` with the switch off and on,
+alternating in the same process, every shape warmed up first, device events around >= 0.5 s of calls per variant and a
+synchronise behind them, two repeats.  Two shapes: the bench batch (B = 32, train.synth_batch lengths, T_y <= 800) and one
+utterance of 800 frames (the latency case).  The rows context of a shape is built once and reused by both variants
+(RowsConfig.prebuilt), so neither pays for the pinned staging buffer of a ragged context inside the timed loop.
+Per variant: time per call, C-ABI launches per call, HBM bytes per call computed from the shapes below (activations read and
+written by every launch + each launch's weight images once; L2 hits and halo re-reads are not modelled).
+
+    python tools/synth_bench.py [--json out.json] [--seconds 0.5] [--repeats 2] [--shape both|batch|single]
+
+Kernel times come from separate runs, one per shape, under
+`rocprofv3 --kernel-trace --stats -- python tools/synth_bench.py --seconds 0.1 --repeats 1 --shape batch` (or `single`)."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+from glow_tts_amd import _lib, models, ops, train  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--json", default=None)
+ap.add_argument("--seconds", type=float, default=0.5)
+ap.add_argument("--repeats", type=int, default=2)
+ap.add_argument("--shape", choices=["both", "batch", "single"], default="both", help="one shape only (a kernel-trace run per shape)")
+opt = ap.parse_args()
+
+dev = torch.device("cuda:0")
+NB, NL, H, C = 12, 4, 192, 160
+torch.manual_seed(0)
+dec = models.FlowSpecDecoder(80, H, 5, 1, NB, NL, p_dropout=0.05).to(dev).eval()
+for b in range(NB):                                                    # a coupling that does something (end is zero-initialised)
+    torch.nn.init.normal_(dec.flows[3 * b + 2].end.weight, std=0.01)
+dec.store_inverse()
+
+
+def numel_bytes(t):
+    return t.numel() * t.element_size()
+
+
+def weight_bytes():
+    """bytes of the packed images one block's launches read: (WaveNet, skip-cat, end, start)"""
+    cb = dec.flows[2]
+    wn = cb.wn
+    wnb = sum(numel_bytes(il.pc.fwd) for il in wn.in_layers) + sum(numel_bytes(rs.pc_res.fwd) for rs in wn.res_skip_layers[:NL - 1])
+    return wnb, numel_bytes(wn.pc_skipcat_frag.fwd), numel_bytes(cb.end.pc_frag.fwd), numel_bytes(cb.start.pc_frag.fwd)
+
+
+def hbm_bytes(R, B, T, fused):
+    """HBM bytes of one reverse pass from the shapes: every launch's activation reads + writes and its weight images once (ragged rows,
+    even T: the fused path's first / last launch squeeze / unsqueeze)."""
+    wn_w, skip_w, end_w, start_w = weight_bytes()
+    f32row, bct = R * C * 4, B * 80 * T * 4
+    h, x0, acts = R * H * 2, R * 80 * 2, R * NL * H * 2
+    if not fused:
+        per_block = (x0 + start_w + h) \
+            + (h + wn_w + acts + 2 * NL * h + (NL - 1) * h) \
+            + (acts + skip_w + h) \
+            + (h + end_w + f32row) \
+            + (2 * f32row + f32row) \
+            + (f32row + f32row + x0)
+        return NB * per_block + (bct + f32row) + (f32row // 2 + x0) + (f32row + bct)
+    wn = h + wn_w + acts                                               # acts only
+    full = acts + skip_w + end_w + f32row + f32row + start_w + h
+    head = bct + f32row + start_w + h
+    tail = acts + skip_w + end_w + f32row + bct
+    return NB * wn + (NB - 1) * full + head + tail
+
+
+def shape(name, lens, T):
+    B = len(lens)
+    m = (torch.arange(T)[None, :] < torch.tensor(lens)[:, None]).unsqueeze(1).float().to(dev)
+    z = torch.randn(B, 80, T, device=dev) * m
+    sq = [v // 2 for v in lens]
+    rc = ops.RowsCtx(torch.tensor(sq, dtype=torch.int32, device=dev), T // 2, lengths_host=sq, round_to=128)
+    return dict(name=name, B=B, T=T, z=z, m=m, rc=rc)
+
+
+def run(sh, on, n):
+    dec.set_fused_reverse(on)
+    for _ in range(n):
+        dec(sh["z"], sh["m"], reverse=True)
+
+
+def main():
+    _, _, _, t_y = train.synth_batch(32, 150, 800, 0, "cpu")
+    shapes = ([shape("bench batch: B = 32, T_y <= 800", [int(v) for v in t_y], 800)] if opt.shape != "single" else []) + \
+        ([shape("one utterance, 800 frames", [800], 800)] if opt.shape != "batch" else [])
+    out = dict(device=torch.cuda.get_device_name(0), decoder="cfg 2: 12 blocks x 4 layers, H = 192, eval, store_inverse", rows_ctx="prebuilt, ragged, round 128",
+               seconds_per_variant=opt.seconds, shapes=[])
+    dec.rows_cfg = ops.RowsConfig(ragged=True)
+    for sh in shapes:
+        dec.rows_cfg.prebuilt["y"] = sh["rc"]
+        rec = dict(name=sh["name"], B=sh["B"], T=sh["T"], rows=sh["rc"].R, workgroups_per_boundary_launch=(sh["rc"].R + 63) // 64, variants={})
+        xs = {}
+        for on in (False, True):                                       # warm-up, launch count, result
+            assert dec.set_fused_reverse(on) == on
+            run(sh, on, 3)
+            with _lib.record_calls() as names:
+                xs[on], _ = dec(sh["z"], sh["m"], reverse=True)
+            torch.cuda.synchronize()
+            rec["variants"]["fused" if on else "launch_sequence"] = dict(
+                launches_per_call=len(names), launches={k: names.count(k) for k in sorted(set(names))},
+                hbm_bytes_per_call=hbm_bytes(sh["rc"].R, sh["B"], sh["T"], on), ms_per_call=[])
+        rec["max_abs_difference"] = (xs[True] - xs[False]).abs().max().item()
+        rec["max_abs_output"] = xs[False].abs().max().item()
+        for rep in range(opt.repeats):
+            for on in (False, True):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); run(sh, on, 5); e1.record(); torch.cuda.synchronize()
+                n = max(5, int(opt.seconds * 1e3 / (e0.elapsed_time(e1) / 5)) + 1)
+                e0.record(); run(sh, on, n); e1.record(); torch.cuda.synchronize()
+                rec["variants"]["fused" if on else "launch_sequence"]["ms_per_call"].append(round(e0.elapsed_time(e1) / n, 4))
+        for v in rec["variants"].values():
+            t = v["ms_per_call"]
+            v["ms_mean"], v["ms_spread"] = round(sum(t) / len(t), 4), round(max(t) - min(t), 4)
+        a, b = rec["variants"]["launch_sequence"], rec["variants"]["fused"]
+        rec["fused_over_launch_sequence_time"] = round(b["ms_mean"] / a["ms_mean"], 4)
+        print(f'{sh["name"]}: rows {sh["rc"].R}; launch sequence {a["ms_mean"]:.3f} ms (+- {a["ms_spread"]:.3f}), {a["launches_per_call"]} launches, '
+              f'{a["hbm_bytes_per_call"] / 1e6:.1f} MB; fused {b["ms_mean"]:.3f} ms (+- {b["ms_spread"]:.3f}), {b["launches_per_call"]} launches, '
+              f'{b["hbm_bytes_per_call"] / 1e6:.1f} MB', flush=True)
+        out["shapes"].append(rec)
+    dec.rows_cfg = ops.RowsConfig()
+    dec.set_fused_reverse(False)
+    if opt.json:
+        os.makedirs(os.path.dirname(os.path.abspath(opt.json)), exist_ok=True)
+        with open(opt.json, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
+main()
