@@ -133,6 +133,10 @@ PROTOTYPES = {
     "gt_pack_conv_weights_multi": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "gt_pack_conv_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                      c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gt_synth_lengths": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gt_synth_prior": (c_int, [c_void_p, c_void_p]),
+    "gt_synth_prior_args_size": (c_int, []),
+    "gt_randn_rows": (c_int, [c_void_p, c_int, c_int, c_u32, c_u32, c_float, c_void_p]),
 }
 
 
@@ -241,6 +245,14 @@ class BoundaryRevArgs(ctypes.Structure):
                 ("rowmask", c_void_p), ("R", c_int), ("H", c_int), ("C", c_int), ("n_layers", c_int),
                 ("z_bct", c_void_p), ("x_bct", c_void_p), ("T", c_int), ("rowbatch", c_void_p), ("rowframe", c_void_p), ("len", c_void_p),
                 ("pf_ptr", c_void_p * 16), ("pf_bytes", c_u32 * 16)]
+
+
+class SynthPriorArgs(ctypes.Structure):
+    """struct gt_synth_prior_args (include/glowtts_hip.h); its size is checked against gt_synth_prior_args_size() (tests/test_synthesis_noise.py)"""
+    _fields_ = [("x_m", c_void_p), ("x_logs", c_void_p), ("cum", c_void_p), ("x_len", c_void_p), ("y_len", c_void_p),
+                ("row0", c_void_p), ("Tp", c_int), ("R", c_int), ("rows", c_void_p), ("z_m", c_void_p), ("z_logs", c_void_p),
+                ("frame2token", c_void_p), ("attn", c_void_p), ("B", c_int), ("C", c_int), ("Tx", c_int), ("Ty", c_int),
+                ("seed", c_u32), ("noise_scale", c_float)]
 
 
 def fill_args(cls, **kw):

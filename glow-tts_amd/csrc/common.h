@@ -41,6 +41,25 @@ __device__ __forceinline__ void drop_keep_gate(uint32_t seed, uint32_t row, uint
   keep_t = (hsh & 0xffffu) >= thresh16; keep_s = (hsh >> 16) >= thresh16;
 }
 
+// Counter-based Gaussian generator of the synthesis front end (csrc/synth_front.hip): two standard normals per
+// (seed, stream, b, s, c), restated on the host by tests/synth_noise_host.py.  The seed is hashed first, so consecutive user seeds do
+// not give shifted copies of one stream; `stream` separates the draws of one call (0 prior, 1 duration, 2 pitch, 3 energy predictor).
+// u = ((h >> 9) + 0.5) * 2^-23 lies in (0, 1) and is exact in fp32 (a 24-bit form is not), so |e| <= sqrt(-2 ln 2^-24) = 5.77.
+// Accurate logf / sqrtf / sincospif: the host restatement is held to 1e-5, which the fast intrinsics do not keep.
+__device__ __forceinline__ uint32_t randn_key(uint32_t seed, uint32_t stream, uint32_t b) {
+  return hash_u32(hash_u32(seed) + b * 0x9E3779B1U + stream * 0x85EBCA6BU);
+}
+__device__ __forceinline__ void randn_pair(uint32_t key, uint32_t s, uint32_t c, float& e0, float& e1) {
+  const uint32_t h1 = hash_u32(key + s * 0x9E3779B1U + c * 0x85EBCA6BU);
+  const uint32_t h2 = hash_u32(h1 + 0x632BE5ABU);
+  const float u1 = ((float)(h1 >> 9) + 0.5f) * 1.1920928955078125e-7f;
+  const float u2 = ((float)(h2 >> 9) + 0.5f) * 1.1920928955078125e-7f;
+  const float r = sqrtf(-2.0f * logf(u1));
+  float sn, cs;
+  sincospif(2.0f * u2, &sn, &cs);
+  e0 = r * cs; e1 = r * sn;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

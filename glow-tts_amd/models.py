@@ -105,6 +105,20 @@ class FlowSpecDecoder(nn.Module):
         z, logdet = _RowsFn.apply(runner, 2, x, *conds, *affs, *runner.params)
         return z, logdet
 
+    @torch.no_grad()
+    def reverse_rows(self, rc, rows, g=None, pitch=None, energy=None):
+        """forward(reverse=True, prepared=True) from the squeezed latent in the rows layout: rc = ops.RowsCtx of the squeezed mel axis,
+        rows [rc.R, 2 * in_channels] fp32 (what commons.squeeze + the rows packing of z would give: zero halo / padding rows)
+        -> the mel [b, in_channels, 2 * rc.T] fp32, zero past every utterance's length.  The caller has prepared the weights."""
+        if (pitch is not None or energy is not None) and not hasattr(self.flows[2], "wn_pitch"):
+            raise ValueError("pitch / energy conditioning needs FlowSpecDecoder(with_prosody_wn=True)")
+        pitch = pitch.unsqueeze(1) if (pitch is not None and pitch.dim() == 2) else pitch
+        energy = energy.unsqueeze(1) if (energy is not None and energy.dim() == 2) else energy
+        wns = [self.flows[3 * b + 2].wn for b in range(self.n_blocks)]
+        conds = _wn_cond_all(wns, g)
+        runner = _DecoderRunner(self, None, g is not None, False, 0, energy, pitch)
+        return runner.reverse_rows(rc, rows, conds, self._prosody_affine("wn_energy", energy), self._prosody_affine("wn_pitch", pitch))
+
     def _prosody_affine(self, which, contour):
         """cond_layer1 of every block's wn_energy / wn_pitch as (effective weight, bias) pairs [n_blocks, 2, 2*H*n/n_sqz]:
         with one input channel the weight-normed 1x1 conv (modules.py:289-291,320) is the per-frame affine map
@@ -207,6 +221,15 @@ class _DecoderRunner:
             return x.to(z.dtype)
         cur = torch.empty(rc.R, 2 * C, dtype=torch.float32, device=dev)
         _lib.check(L.gt_squeeze_rows_f32(_lib.ptr(zin), _lib.ptr(cur), _lib.ptr(rc.lengths), B, C, T, rc.Tp, _lib.ptr(rc.row0), st), "gt_squeeze_rows_f32")
+        return self._rows_to_x(rc, cur, B, C, T2, conds, fused, pros).to(z.dtype)
+
+    def _rows_to_x(self, rc, cur, B, C, T2, conds, fused, pros):
+        """squeezed latent rows [R, 2C] fp32 -> x [B, C, 2*T2] fp32: the fused pass or the launch sequence, then unsqueeze"""
+        L = _lib.lib()
+        dec = self.dec
+        dev = cur.device
+        st = _lib.current_stream(dev)
+        esig, psig, eaff, paff = pros["esig"], pros["psig"], pros["eaff"], pros["paff"]
         if fused:
             cur = flow_impl.decoder_rev_fused(rc, dec, cur, conds, **pros)
         else:
@@ -220,7 +243,22 @@ class _DecoderRunner:
                                                         scal=None if dec._inv_cache is None else dec._inv_cache[b])
         x = torch.empty(B, C, T2 * 2, dtype=torch.float32, device=dev)
         _lib.check(L.gt_unsqueeze_rows_f32(_lib.ptr(cur), _lib.ptr(x), _lib.ptr(rc.lengths), B, C, T2 * 2, rc.Tp, _lib.ptr(rc.row0), st), "gt_unsqueeze_rows_f32")
-        return x.to(z.dtype)
+        return x
+
+    def reverse_rows(self, rc, rows, conds, eaff=None, paff=None):
+        """reverse() for a caller that already holds the squeezed latent in the rows layout (FlowGenerator.infer with the device front
+        end): rc = the RowsCtx of the squeezed mel axis, rows [rc.R, 2C] fp32 with zero halo / padding rows -> x [B, C, 2 * rc.T] fp32.
+        On ragged rows the fused pass unsqueezes in its last launch."""
+        dec = self.dec
+        B, C, T2 = rc.B, dec.in_channels, rc.T
+        esig, psig = self._contour_rows(rc, self.energy, B, T2 * 2), self._contour_rows(rc, self.pitch, B, T2 * 2)
+        fused = dec.fused_reverse and dec.fused_boundary and all(dec.flows[3 * b].initialized for b in range(dec.n_blocks))
+        pros = dict(esig=esig, eaff=eaff, psig=psig, paff=paff)
+        if fused and getattr(rc, "rowbatch", None) is not None:
+            x = ops.zeros_big((B, C, 2 * T2), torch.float32, rows.device)
+            flow_impl.decoder_rev_fused(rc, dec, rows, conds, x_bct=x, **pros)
+            return x
+        return self._rows_to_x(rc, rows, B, C, T2, conds, fused, pros)
 
     def backward(self, saved_all, dz, dlogdet):
         L = _lib.lib()

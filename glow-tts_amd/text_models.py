@@ -461,6 +461,8 @@ class FlowGenerator(nn.Module):
             from .predictors import StochasticEnergyPredictor
             self.proj_energy = StochasticEnergyPredictor(henc, 256, 3, 0.1, 4, gin_channels=gin_channels)
         self._step = 0
+        self.synthesis_front = False                                 # set_synthesis_front: infer's device front end (opt-in)
+        self._front_pin = self._front_last = None
         # rows-layout state of THIS model (ragged packing, row rounding, the batch's host-side lengths): shared with the
         # encoder / decoder runners; train.Trainer configures it — nothing process-global
         self.rows_cfg = self.encoder.rows_cfg = self.decoder.rows_cfg = ops.RowsConfig()
@@ -492,23 +494,43 @@ class FlowGenerator(nn.Module):
         emosty = self.emosty_layer_norm(F.softplus(torch.cat((emos_proj, style), dim=-1)))
         return torch.cat((g, intens + emosty), dim=-1).unsqueeze(-1)
 
-    def store_inverse(self, fused_reverse=None):
+    def set_synthesis_front(self, on=True):
+        """Opt-in device front end of infer (csrc/synth_front.hip): gt_synth_lengths turns the durations into lengths,
+        ONE device-to-host copy brings all of them back, gt_synth_prior writes the sampled, squeezed latent straight into the RAGGED rows
+        layout the reverse decoder reads (padded frames then cost nothing, and the fused reverse pass unsqueezes in its last launch),
+        and every draw of the call — the prior's and the stochastic predictors' — comes from a counter-hash Gaussian generator that the
+        host can restate from `infer(..., seed=)` alone.  Off (the default): infer is torch.randn and the uniform rows layout.  Returns
+        what is in effect."""
+        self.synthesis_front = bool(on)
+        return self.synthesis_front
+
+    def store_inverse(self, fused_reverse=None, device_front=None):
         """models.py:1255-1256: freeze the model for synthesis (weights packed once, flow scalars cached).  fused_reverse = True / False:
         the decoder's reverse passes (infer, the second half of voice_conversion) run one kernel between consecutive WaveNets
         (FlowSpecDecoder.set_fused_reverse) or the launch sequence; None (as in FlowSpecDecoder.store_inverse) leaves the switch as it
-        is — off on a new model.  Returns whether the fused path is in effect."""
+        is — off on a new model.  device_front = True / False: set_synthesis_front; None leaves that switch as it is.  Returns whether
+        the fused path is in effect — and, when device_front was given, the pair (fused path, device front end) in effect."""
         self.prepare()
         self.decoder.store_inverse(fused_reverse)
-        return self.decoder.fused_reverse
+        if device_front is None:
+            return self.decoder.fused_reverse
+        return self.decoder.fused_reverse, self.set_synthesis_front(device_front)
 
     @torch.no_grad()
     def infer(self, x, x_lengths, y=None, y_lengths=None, g=None, emo=None, emo_cartesian=None, l=None, gst_token=None,
               noise_scale=1., noise_scale_w=1., f0_noise_scale=1., energy_noise_scale=1., length_scale=1., pitch_scale=1.0,
-              energy_scale=1.0):
+              energy_scale=1.0, seed=None):
         """Synthesis (reference FlowGenerator.infer, models.py:1135-1231): text -> durations (deterministic predictor, or the
         stochastic one run in reverse) -> expanded prior -> [predicted pitch / energy] -> z = z_m + noise ->
         decoder(reverse=True) -> mel.  Returns ((y, z_m, z_logs, None, z_mask), (x_m, x_logs, x_mask), (attn, logw, logw_),
-        (pitch, energy)).  The output length is data dependent, so this reads the predicted lengths back from the device once."""
+        (pitch, energy)).  The output length is data dependent, so this reads the predicted lengths back from the device once.
+        seed (set_synthesis_front only): the call's noise is a function of this integer alone; None draws one from torch's default
+        CPU generator, so torch.manual_seed still governs the call."""
+        if self.synthesis_front:
+            return self._infer_front(x, x_lengths, g, emo, emo_cartesian, l, noise_scale, noise_scale_w, f0_noise_scale,
+                                     energy_noise_scale, length_scale, pitch_scale, energy_scale, seed)
+        if seed is not None:
+            raise ValueError("infer(seed=) needs the device front end: call set_synthesis_front() (or store_inverse(device_front=True)) first")
         if self.decoder._inv_cache is None:
             self.prepare()
         self.rows_cfg.host_lengths.clear()
@@ -567,6 +589,87 @@ class FlowGenerator(nn.Module):
                 energy = rcf.from_rows(self.proj_energy._reverse_rows(rcf, xf, self.proj_energy.cond_vec(g), nz)[:, None].contiguous()).squeeze(1) * energy_scale
         yo, logdet = self.decoder(z, z_mask, g=g, pitch=pitch, energy=energy, reverse=True, prepared=True)
         return (yo, z_m, z_logs, logdet, z_mask), (x_m, x_logs, x_mask), (attn, logw, logw_), (pitch, energy)
+
+    def _infer_front(self, x, x_lengths, g, emo, emo_cartesian, l, noise_scale, noise_scale_w, f0_noise_scale, energy_noise_scale,
+                     length_scale, pitch_scale, energy_scale, seed):
+        """infer with the device front end (set_synthesis_front): same return structure, shapes and dtypes."""
+        import ctypes
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())           # torch's default CPU generator
+        seed = int(seed) & 0xFFFFFFFF
+        if self.decoder._inv_cache is None:
+            self.prepare()
+        self.rows_cfg.host_lengths.clear()
+        dev = x.device
+        L = _lib.lib()
+        st = _lib.current_stream(dev)
+
+        def randn_rows(R, stream, scale):
+            nz = torch.empty(R, 2, dtype=torch.float32, device=dev)
+            _lib.check(L.gt_randn_rows(_lib.ptr(nz), R, 2, seed, stream, float(scale), st), "gt_randn_rows")
+            return nz
+
+        g = self.condition(g, emo, emo_cartesian)
+        if l is not None:
+            l = self.emb_l(l).unsqueeze(-1)
+        xo, x_m, x_logs, x_mask = self.encoder(x, x_lengths, l=l, g=g, prepared=True)
+        rc, xb = self.encoder._last_rows
+        pw = self.encoder.proj_w
+        dvec = pw.cond_vec(g, l)
+        if self.use_sdp:
+            logw = rc.from_rows(pw._reverse_rows(rc, xb, dvec, randn_rows(rc.R, 1, noise_scale_w))[:, None].contiguous())
+        else:
+            runner = _DurationRunner(pw, rc, xb, False, 0, has_cond=dvec is not None)
+            (logw,), _ = runner.forward(*([dvec] if dvec is not None else []))
+        # exp, length_scale and ceil stay in torch on [B, Tx] (plumbing): the durations are bit for bit those of the other path
+        dur = torch.ceil(torch.exp(logw) * x_mask * length_scale).squeeze(1).contiguous()
+        B, C, Tx = x_m.shape
+        xl = x_lengths.to(torch.int32).contiguous()
+        cum = torch.empty(B, Tx, dtype=torch.int32, device=dev)
+        y_len = torch.empty(B, dtype=torch.int32, device=dev)
+        logw_ = torch.empty(B, 1, Tx, dtype=torch.float32, device=dev)
+        _lib.check(L.gt_synth_lengths(_lib.ptr(dur), _lib.ptr(xl), _lib.ptr(cum), _lib.ptr(y_len), _lib.ptr(logw_), B, Tx, st),
+                   "gt_synth_lengths")
+        if self._front_pin is None or self._front_pin.numel() < B:            # pinned staging of the readback, kept across calls
+            self._front_pin = torch.empty(max(B, 64), dtype=torch.int32).pin_memory()
+        host = self._front_pin[:B]
+        host.copy_(y_len, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()                         # the call's one readback: all B lengths
+        lens = host.tolist()
+        Ty = max(lens)
+        T2 = Ty // 2
+        # the squeezed mel axis, ragged: utterances back to back, no rows for padded frames
+        rcy = ops.RowsCtx(y_len, T2, lengths_host=[v // 2 for v in lens], round_to=self.rows_cfg.row_round)
+        rcy.stamps = self.rows_cfg.stamps
+        xm = x_m.float().contiguous()
+        xs = None if self.mean_only else x_logs.float().contiguous()
+        rows = torch.empty(rcy.R, 2 * C, dtype=torch.float32, device=dev)
+        z_m = torch.empty(B, C, Ty, dtype=torch.float32, device=dev)
+        z_logs = torch.empty(B, C, Ty, dtype=torch.float32, device=dev)
+        frame2token = torch.empty(B, Ty, dtype=torch.int32, device=dev)
+        attn = torch.empty(B, 1, Tx, Ty, dtype=torch.float32, device=dev)
+        args = _lib.fill_args(_lib.SynthPriorArgs, x_m=xm, x_logs=xs, cum=cum, x_len=xl, y_len=y_len, row0=rcy.row0, Tp=rcy.Tp, R=rcy.R,
+                              rows=rows, z_m=z_m, z_logs=z_logs, frame2token=frame2token, attn=attn, B=B, C=C, Tx=Tx, Ty=Ty,
+                              seed=seed, noise_scale=float(noise_scale))
+        _lib.check(L.gt_synth_prior(ctypes.byref(args), st), "gt_synth_prior")
+        z_mask = ops.length_mask(y_len, Ty).to(x_mask.dtype)
+        pitch = energy = None
+        if self.use_spp or self.use_sep:                              # models.py:1203-1228, at the frame rate (uniform rows)
+            rcf = ops.RowsCtx(y_len, Ty)
+            xf = self._gather_features(rc, xb, rcf, frame2token)      # frames no token owns (-1) are masked rows: not read
+            if self.use_spp:
+                nz = randn_rows(rcf.R, 2, f0_noise_scale)
+                pitch = rcf.from_rows(self.proj_pitch._reverse_rows(rcf, xf, self.proj_pitch.cond_vec(g), nz)[:, None].contiguous()).squeeze(1) * pitch_scale
+            if self.use_sep:
+                nz = randn_rows(rcf.R, 3, energy_noise_scale)
+                energy = rcf.from_rows(self.proj_energy._reverse_rows(rcf, xf, self.proj_energy.cond_vec(g), nz)[:, None].contiguous()).squeeze(1) * energy_scale
+        if T2 == 0:                                                   # no utterance has two frames: nothing to decode
+            yo = torch.zeros(B, C, 0, dtype=x_m.dtype, device=dev)
+        else:
+            yo = self.decoder.reverse_rows(rcy, rows, g=g, pitch=pitch, energy=energy).to(x_m.dtype)
+        # what the last call put in front of the decoder (tests, tools): rows context, sampled latent rows, frame -> token map
+        self._front_last = dict(rc=rcy, rows=rows, frame2token=frame2token, seed=seed)
+        return (yo, z_m, z_logs, None, z_mask), (x_m, x_logs, x_mask), (attn.to(x_mask.dtype), logw, logw_), (pitch, energy)
 
     @staticmethod
     def _gather_features(rcx, xb, rcf, frame2token):

@@ -706,6 +706,48 @@ int gt_rows_gather_tokens(const void* x_rows, int ldx, const int32_t* frame2toke
                           const int32_t* utt_f, const int32_t* row0_f, int Tp_f, const float* rowmask_f, void* out, int R_f, int C,
                           void* stream);
 
+/* ---- Device front end of synthesis (FlowGenerator.infer with set_synthesis_front; csrc/synth_front.hip).
+ * Vector stores only, no atomics, one writer per output element: deterministic.
+ *
+ * The Gaussian generator (csrc/common.h randn_key / randn_pair; all arithmetic mod 2^32, hash_u32 = the dropout hash):
+ *   key(seed, stream, b) = hash_u32(hash_u32(seed) + b * 0x9E3779B1 + stream * 0x85EBCA6B)
+ *   h1 = hash_u32(key + s * 0x9E3779B1 + c * 0x85EBCA6B),  h2 = hash_u32(h1 + 0x632BE5AB)
+ *   u1 = ((h1 >> 9) + 0.5) * 2^-23,  u2 likewise from h2;  r = sqrt(-2 ln u1),  e0 = r cos(2 pi u2),  e1 = r sin(2 pi u2)
+ * stream: 0 prior, 1 duration predictor, 2 pitch predictor, 3 energy predictor.
+ *
+ * gt_synth_lengths: dur [B, Tx] fp32 = ceil(w), integer valued (tokens i >= x_len[b] count as 0, a duration is clamped to
+ *   [0, 2^20]) -> cum [B, Tx] int32 inclusive scan, y_len [B] int32 = max(sum, 1) (models.py:1189), and optionally
+ *   logw [B, Tx] = log(1e-8 + dur) * (i < x_len[b]) (models.py:1199).  Tx <= 512, else GT_E_UNSUPPORTED.  B == 0 returns 0.
+ *
+ * gt_synth_prior: models.py:1196-1201 + commons.squeeze.  Frame t of utterance b belongs to the first token i < x_len[b] with
+ *   cum[b, i] > t (commons.generate_path, zero-duration tokens included), to none when t >= sum(dur) or t >= y_len[b];
+ *   z[b, c, t] = x_m[b, c, i] + exp(x_logs[b, c, i]) * e * noise_scale,  e = e0 (t even) / e1 (t odd) of (seed, stream 0, b, s = t / 2, c)
+ *   rows [R, 2 C] fp32: rows[r, j * C + c] = z[b, c, 2 s + j] for the row r of squeezed frame s < y_len[b] / 2 (an odd trailing
+ *   frame is dropped); EVERY one of the R rows is written, halo / padding / rounding rows as zeros.  row0 (int32 [B + 1]) = the
+ *   ragged layout's row offsets, NULL = uniform rows (R == B * Tp); Tp as in RowsCtx (>= the rows of the largest utterance).
+ *   Optional outputs (NULL-able), over all Ty frames, zero where no token owns the frame: z_m / z_logs [B, C, Ty] (z_logs = 0 when
+ *   x_logs == NULL, the mean_only form), frame2token [B, Ty] int32 (-1 where no token owns the frame), attn [B, Tx, Ty] fp32.
+ *   NULL args / required pointer: GT_E_INVAL;  R == 0 or B == 0: 0;  Tx > 512 or C > 80: GT_E_UNSUPPORTED;  fp32 pointers not
+ *   16-byte aligned: GT_E_ALIGN.
+ *
+ * gt_randn_rows: out [R, ncol] fp32 = scale * (e0 | e1 by the parity of col) of (seed, stream, b = 0, s = row, c = col / 2). */
+typedef struct gt_synth_prior_args {
+  const float* x_m; const float* x_logs;        /* [B, C, Tx] fp32; x_logs NULL = mean_only */
+  const int32_t* cum;                           /* [B, Tx] gt_synth_lengths' scan */
+  const int32_t* x_len; const int32_t* y_len;   /* [B] */
+  const int32_t* row0; int Tp, R;               /* rows layout of the squeezed mel axis */
+  float* rows;                                  /* out: [R, 2 C] */
+  float* z_m; float* z_logs;                    /* optional out: [B, C, Ty] */
+  int32_t* frame2token;                         /* optional out: [B, Ty] */
+  float* attn;                                  /* optional out: [B, Tx, Ty] */
+  int B, C, Tx, Ty;
+  uint32_t seed; float noise_scale;
+} gt_synth_prior_args;
+int gt_synth_lengths(const float* dur, const int32_t* x_len, int32_t* cum, int32_t* y_len, float* logw, int B, int Tx, void* stream);
+int gt_synth_prior(const gt_synth_prior_args* args, void* stream);
+int gt_synth_prior_args_size(void);             /* sizeof(gt_synth_prior_args) */
+int gt_randn_rows(float* out, int R, int ncol, uint32_t seed, uint32_t stream_id, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,13 @@ written by every launch + each launch's weight images once; L2 hits and halo re-
 
     python tools/synth_bench.py [--json out.json] [--seconds 0.5] [--repeats 2] [--shape both|batch|single]
 
+--infer: whole FlowGenerator.infer calls instead (text in, mel out, the call's device-to-host readback included), graph-free, same
+warm-up and repeat rule, fused_reverse on: the device front end (set_synthesis_front) off and on, alternating.  A cfg 2 model whose
+duration predictor is pinned to 5 frames per token (zero projection weight, bias log 4.9), so the mel lengths are 5 x the text
+lengths: the bench batch (B = 32, train.synth_batch's text lengths, T_y <= 750) and one utterance of 160 tokens = 800 frames.
+Per variant: wall time per call, what one call puts on the device (C-ABI entries + aten operators on device tensors).  On a tree
+without set_synthesis_front only the front-off variant is measured (the parent's numbers for the run-to-run spread).
+
 Kernel times come from separate runs, one per shape, under
 `rocprofv3 --kernel-trace --stats -- python tools/synth_bench.py --seconds 0.1 --repeats 1 --shape batch` (or `single`)."""
 import argparse
@@ -25,16 +32,18 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--json", default=None)
 ap.add_argument("--seconds", type=float, default=0.5)
 ap.add_argument("--repeats", type=int, default=2)
+ap.add_argument("--infer", action="store_true", help="time whole infer calls, device front end off / on")
 ap.add_argument("--shape", choices=["both", "batch", "single"], default="both", help="one shape only (a kernel-trace run per shape)")
 opt = ap.parse_args()
 
 dev = torch.device("cuda:0")
 NB, NL, H, C = 12, 4, 192, 160
 torch.manual_seed(0)
-dec = models.FlowSpecDecoder(80, H, 5, 1, NB, NL, p_dropout=0.05).to(dev).eval()
-for b in range(NB):                                                    # a coupling that does something (end is zero-initialised)
-    torch.nn.init.normal_(dec.flows[3 * b + 2].end.weight, std=0.01)
-dec.store_inverse()
+if not opt.infer:
+    dec = models.FlowSpecDecoder(80, H, 5, 1, NB, NL, p_dropout=0.05).to(dev).eval()
+    for b in range(NB):                                                # a coupling that does something (end is zero-initialised)
+        torch.nn.init.normal_(dec.flows[3 * b + 2].end.weight, std=0.01)
+    dec.store_inverse()
 
 
 def numel_bytes(t):
@@ -132,4 +141,86 @@ def main():
             f.write("\n")
 
 
-main()
+def infer_main():
+    import math
+    import time
+    from torch.utils._python_dispatch import TorchDispatchMode
+    gen = models.FlowGenerator(148, 192, 768, 256, 80, use_sdp=False, kernel_size=3, n_heads=2, n_layers_enc=6, p_dropout=0.1,
+                               n_blocks_dec=NB, kernel_size_dec=5, dilation_rate=1, n_block_layers=NL, p_dropout_dec=0.05, n_sqz=2,
+                               window_size=4, mean_only=True, prenet=True).eval()
+    with torch.no_grad():
+        for b in range(NB):
+            torch.nn.init.normal_(gen.decoder.flows[3 * b + 2].end.weight, std=0.01)
+        gen.encoder.proj_w.proj.weight.zero_()                         # 5 frames per token: ceil(4.9)
+        gen.encoder.proj_w.proj.bias.fill_(math.log(4.9))
+    gen = gen.to(dev)
+    has_front = hasattr(gen, "set_synthesis_front")
+    gen.store_inverse(fused_reverse=True)
+    # aten operators that only make a view, an allocation or a host-side answer: no kernel
+    free = {"view", "_unsafe_view", "reshape", "_reshape_alias", "transpose", "t", "permute", "squeeze", "unsqueeze", "expand", "slice",
+            "select", "as_strided", "detach", "alias", "empty", "empty_like", "empty_strided", "new_empty", "new_empty_strided",
+            "unbind", "split", "split_with_sizes", "narrow", "is_pinned", "_local_scalar_dense", "lift_fresh", "_pin_memory", "resize_",
+            "set_", "is_same_size", "record_stream"}
+
+    class Count(TorchDispatchMode):
+        n = 0
+
+        def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+            res = func(*args, **(kwargs or {}))
+            flat = list(args) + list((kwargs or {}).values()) + (list(res) if isinstance(res, (tuple, list)) else [res])
+            if func.overloadpacket.__name__ not in free and any(isinstance(t, torch.Tensor) and t.is_cuda for t in flat):
+                self.n += 1
+            return res
+
+    ids_b, t_x, _, _ = train.synth_batch(32, 150, 800, 0, "cpu")
+    g = torch.Generator().manual_seed(5)
+    cases = [("bench batch: B = 32, T_x <= 150, 5 frames per token", ids_b, t_x),
+             ("one utterance, 160 tokens = 800 frames", torch.randint(1, 148, (1, 160), generator=g), torch.tensor([160]))]
+    variants = [False, True] if has_front else [False]
+    name_of = {False: "front_off", True: "front_on"}
+
+    def call(ids, xl, front, n):
+        if has_front:
+            gen.set_synthesis_front(front)
+        for _ in range(n):
+            res = gen.infer(ids, xl, noise_scale=0.667)
+        return res
+
+    out = dict(device=torch.cuda.get_device_name(0), model="cfg 2: 6 encoder layers, 12 blocks x 4 layers, H = 192, eval, store_inverse(fused_reverse=True)",
+               seconds_per_variant=opt.seconds, device_front_available=has_front, shapes=[])
+    for name, ids, xl in cases:
+        ids, xl = ids.to(dev), xl.to(dev)
+        rec = dict(name=name, B=int(ids.shape[0]), Tx=int(ids.shape[1]), variants={})
+        for front in variants:
+            res = call(ids, xl, front, 3)
+            with _lib.record_calls() as names, Count() as cnt:
+                res = call(ids, xl, front, 1)
+            torch.cuda.synchronize()
+            assert torch.isfinite(res[0][0]).all()
+            rec["T_y"] = int(res[0][0].shape[2])
+            rec["variants"][name_of[front]] = dict(c_abi_entries=len(names), aten_device_ops=cnt.n, launches_per_call=len(names) + cnt.n,
+                                                   ms_per_call=[])
+        for rep in range(opt.repeats):
+            for front in variants:
+                torch.cuda.synchronize(); t0 = time.perf_counter(); call(ids, xl, front, 5); torch.cuda.synchronize()
+                n = max(5, int(opt.seconds / ((time.perf_counter() - t0) / 5)) + 1)
+                torch.cuda.synchronize(); t0 = time.perf_counter(); call(ids, xl, front, n); torch.cuda.synchronize()
+                rec["variants"][name_of[front]]["ms_per_call"].append(round((time.perf_counter() - t0) * 1e3 / n, 4))
+        for v in rec["variants"].values():
+            t = v["ms_per_call"]
+            v["ms_mean"], v["ms_spread"] = round(sum(t) / len(t), 4), round(max(t) - min(t), 4)
+        if has_front:
+            rec["front_on_over_front_off_time"] = round(rec["variants"]["front_on"]["ms_mean"] / rec["variants"]["front_off"]["ms_mean"], 4)
+        print(f'{name}: T_y {rec["T_y"]}; ' + "; ".join(f'{k} {v["ms_mean"]:.3f} ms (+- {v["ms_spread"]:.3f}), {v["launches_per_call"]} launches '
+                                                        f'({v["c_abi_entries"]} C-ABI + {v["aten_device_ops"]} aten)' for k, v in rec["variants"].items()), flush=True)
+        out["shapes"].append(rec)
+    if has_front:
+        gen.set_synthesis_front(False)
+    if opt.json:
+        os.makedirs(os.path.dirname(os.path.abspath(opt.json)), exist_ok=True)
+        with open(opt.json, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
+infer_main() if opt.infer else main()
