@@ -353,32 +353,243 @@ __device__ __forceinline__ void weightnorm_bwd_row(
   }
 }
 
-__global__ __launch_bounds__(64 * WNB_ROWS) void gt_weightnorm_bwd_kernel(
+// The same row with 16-byte accesses (Cin % 4 == 0; part, v, dv 16-byte aligned, so every (slab, tap) row of the partials and every
+// v / dv row starts on a 16-byte boundary).  weightnorm_bwd_row above runs three dependent phases of 4-byte accesses — 15 + 15 + 15
+// wave instructions of 256 B for n = 960, the v row requested only after the partials have landed, the old dv row only inside the
+// store loop.  Here a lane owns 16-byte CHUNKS: chunk c of the partials is 4 consecutive ci of one tap (c = tap * Cin/4 + ci/4), chunk
+// c of v / dv is elements 4c .. 4c+3 of the row.  Per pass of WNF_P chunks per lane (1024 elements: one pass for the decoder's n = 960,
+// three at n = 2304) EVERY global load of the pass is issued before the first use: the partials of one or two slabs (three and more go
+// chunk by chunk, four loads in flight), the v chunks, and — ahead of the first pass — the old dv chunks, inv_norm, g and the bias partials.
+// Results are bit-identical to weightnorm_bwd_row: the slab sum keeps (s0+s1)+(s2+s3) over groups of four slabs, the remainder
+// into s0; <dW, v> keeps lane l adding i = l, l+64, ... ascending — v is staged beside dws in the wave's LDS strip and both are read
+// back in that order; dv is elementwise from the same a, bcoef, dws[i], v[i].
+constexpr int WNF_P = 4;                       // 16-byte chunks per lane and pass
+typedef float wnf4_t __attribute__((ext_vector_type(4)));
+// Global-address-space accesses: the batched kernel reads its pointers from the job table, which would make these flat instructions
+// (counted by the LDS counter as well).  No load below is predicated per lane — a lane past the row's end reads the row's last chunk
+// and drops it — and no loaded value is merged with a constant: either makes the compiler wait for each load where it is issued.
+__device__ __forceinline__ wnf4_t wnf_ld4(const float* p) { return *(const __attribute__((address_space(1))) wnf4_t*)(uintptr_t)p; }
+__device__ __forceinline__ float wnf_ld1(const float* p) { return *(const __attribute__((address_space(1))) float*)(uintptr_t)p; }
+__device__ __forceinline__ void wnf_st4(float* p, wnf4_t x) { *(__attribute__((address_space(1))) wnf4_t*)(uintptr_t)p = x; }
+
+// The roundings of the 4-byte form as the compiler emits it, spelled out so that the two forms cannot drift apart: dv = a dW - bcoef v
+// is two products and a difference (left to itself the compiler fuses two of the four components of a chunk and not the others);
+// the dot product and dg + d inv are fused multiply-adds.
+__device__ __forceinline__ float wnf_dv(float a, float dw, float bcoef, float x)
+{
+#pragma clang fp contract(off)
+  const float l = a * dw, r = bcoef * x;
+  return l - r;
+}
+
+// slab sums of the pass's chunks, NS = S <= 2 slabs: every load of the pass at once.  (s0 + 0) + (0 + 0) is what the 4-byte form computes.
+template <int NS>
+__device__ __forceinline__ void wnf_slabs_few(const float* const (&pp)[WNF_P], size_t sstride, wnf4_t (&t)[WNF_P])
+{
+  // (keeps the compiler from hoisting the load the NS = 1 and NS = 2 branches have in common, and its wait, above the branch)
+  asm volatile("; %0 slab(s) per pass" :: "n"(NS) : "memory");
+  wnf4_t a[WNF_P][NS];
+#pragma unroll
+  for (int p = 0; p < WNF_P; ++p)
+#pragma unroll
+    for (int q = 0; q < NS; ++q) a[p][q] = wnf_ld4(pp[p] + (size_t)q * sstride);
+#pragma unroll
+  for (int p = 0; p < WNF_P; ++p) {
+    wnf4_t s0 = 0.f;
+#pragma unroll
+    for (int q = 0; q < NS; ++q) s0 += a[p][q];
+    t[p] = (s0 + 0.f) + (0.f + 0.f);
+  }
+}
+
+__device__ __forceinline__ void weightnorm_bwd_row16(
+    const float* __restrict__ part, const float* __restrict__ part_bias, int S, const float* __restrict__ v,
+    const float* __restrict__ g, const float* __restrict__ inv_norm, float* __restrict__ dv, float* __restrict__ dg,
+    float* __restrict__ dbias, int Cout, int Cin, int taps, int accumulate, int co, float* dws, float* vs)
+{
+  const int lane = threadIdx.x & 63, n = Cin * taps, nch = n >> 2;
+  const unsigned c4 = (unsigned)Cin >> 2;
+  const size_t sstride = (size_t)taps * Cout * Cin;              // one slab
+  const float* vr = v + (size_t)co * n;
+  float* dr = dv + (size_t)co * n;
+  // the row's scalars and the old dv chunks of the first pass: requested now, used after the partials
+  float pb, odb, inv, gg, odg;
+  if (dbias) {
+    pb = wnf_ld1(part_bias + (size_t)max(min(lane, S - 1), 0) * Cout + co);
+    if (accumulate) odb = wnf_ld1(dbias + co);
+  }
+  if (g) {
+    inv = wnf_ld1(inv_norm + co); gg = wnf_ld1(g + co);
+    if (accumulate) odg = wnf_ld1(dg + co);
+  }
+  wnf4_t od[WNF_P];
+  if (accumulate) {
+#pragma unroll
+    for (int p = 0; p < WNF_P; ++p) od[p] = wnf_ld4(dr + 4 * min(64 * p + lane, nch - 1));
+  }
+  for (int c0 = 0; c0 < nch; c0 += 64 * WNF_P) {
+    const float* pp[WNF_P]; int o[WNF_P]; wnf4_t vv[WNF_P], t[WNF_P];
+#pragma unroll
+    for (int p = 0; p < WNF_P; ++p) {
+      const unsigned c = (unsigned)min(c0 + 64 * p + lane, nch - 1);
+      const unsigned tap = c / c4, ci = (c - tap * c4) * 4;
+      pp[p] = part + ((size_t)tap * Cout + co) * Cin + ci;
+      o[p] = (int)(ci * taps + tap);
+    }
+    if (g) {
+#pragma unroll
+      for (int p = 0; p < WNF_P; ++p) vv[p] = wnf_ld4(vr + 4 * min(c0 + 64 * p + lane, nch - 1));
+    }
+    // one or two slabs is the usual case (slabs exist to fill the chip; a network's worth of jobs does that alone)
+    if (S <= 2) {
+      if (S == 1) wnf_slabs_few<1>(pp, sstride, t);
+      else        wnf_slabs_few<2>(pp, sstride, t);
+#pragma unroll
+      for (int p = 0; p < WNF_P; ++p) {
+        if (c0 + 64 * p + lane >= nch) continue;
+        float* d = dws + o[p];                                    // [tap][ci] -> [ci][tap]
+        d[0] = t[p].x; d[taps] = t[p].y; d[2 * taps] = t[p].z; d[3 * taps] = t[p].w;
+      }
+    } else {
+      // three slabs and more: chunk by chunk, four loads in flight as in the 4-byte form (all chunks at once would hold up to 128
+      // registers of sums and operands and take resident waves from the usual case)
+#pragma unroll 1
+      for (int p = 0; p < WNF_P; ++p) {
+        const int cp = c0 + 64 * p + lane;
+        const unsigned c = (unsigned)min(cp, nch - 1);
+        const unsigned tap = c / c4, ci = (c - tap * c4) * 4;
+        const float* q = part + ((size_t)tap * Cout + co) * Cin + ci;
+        wnf4_t s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        int k = 0;
+        for (; k + 4 <= S; k += 4) {
+          const wnf4_t a0 = wnf_ld4(q + (size_t)k * sstride), a1 = wnf_ld4(q + (size_t)(k + 1) * sstride);
+          const wnf4_t a2 = wnf_ld4(q + (size_t)(k + 2) * sstride), a3 = wnf_ld4(q + (size_t)(k + 3) * sstride);
+          s0 += a0; s1 += a1; s2 += a2; s3 += a3;
+        }
+        for (; k < S; ++k) s0 += wnf_ld4(q + (size_t)k * sstride);
+        const wnf4_t r = (s0 + s1) + (s2 + s3);
+        if (cp < nch) {
+          float* d = dws + ci * taps + tap;
+          d[0] = r.x; d[taps] = r.y; d[2 * taps] = r.z; d[3 * taps] = r.w;
+        }
+      }
+    }
+    if (g) {
+#pragma unroll
+      for (int p = 0; p < WNF_P; ++p) {
+        const int c = c0 + 64 * p + lane;
+        if (c < nch) *reinterpret_cast<wnf4_t*>(vs + 4 * c) = vv[p];
+      }
+    }
+  }
+  if (dbias) {
+    float sb = 0.f;
+    for (int k0 = 0; k0 < S; k0 += 64) {
+      if (k0) pb = wnf_ld1(part_bias + (size_t)min(k0 + lane, S - 1) * Cout + co);
+      const int m = min(64, S - k0);
+      for (int k = 0; k < m; ++k) sb += __shfl(pb, k);
+    }
+    if (lane == 0) dbias[co] = accumulate ? odb + sb : sb;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  float a = 1.f, bcoef = 0.f;
+  if (g) {
+    float dot = 0.f;
+    for (int i = lane; i < n; i += 64) dot = __builtin_fmaf(dws[i], vs[i], dot);
+    const float d = wave_sum(dot);
+    if (lane == 0) dg[co] = accumulate ? __builtin_fmaf(d, inv, odg) : d * inv;
+    a = gg * inv; bcoef = gg * d * inv * inv * inv;
+  }
+  for (int c0 = 0; c0 < nch; c0 += 64 * WNF_P) {
+    if (c0 && accumulate) {
+#pragma unroll
+      for (int p = 0; p < WNF_P; ++p) od[p] = wnf_ld4(dr + 4 * min(c0 + 64 * p + lane, nch - 1));
+    }
+#pragma unroll
+    for (int p = 0; p < WNF_P; ++p) {
+      const int c = c0 + 64 * p + lane;
+      if (c >= nch) continue;
+      wnf4_t val = *reinterpret_cast<const wnf4_t*>(dws + 4 * c);
+      if (g) {
+        const wnf4_t x = *reinterpret_cast<const wnf4_t*>(vs + 4 * c);
+        val.x = wnf_dv(a, val.x, bcoef, x.x); val.y = wnf_dv(a, val.y, bcoef, x.y);
+        val.z = wnf_dv(a, val.z, bcoef, x.z); val.w = wnf_dv(a, val.w, bcoef, x.w);
+      }
+      if (accumulate) { val.x = od[p].x + val.x; val.y = od[p].y + val.y; val.z = od[p].z + val.z; val.w = od[p].w + val.w; }
+      wnf_st4(dr + 4 * c, val);
+    }
+  }
+}
+
+// One row through the 16-byte form where its shape and pointers allow it (a wave-uniform choice), else through weightnorm_bwd_row.
+// `strip` is the wave's LDS: [2][strip_elems] floats (dws | v), strip_elems % 4 == 0.
+__device__ __forceinline__ void weightnorm_bwd_dispatch(
+    const float* __restrict__ part, const float* __restrict__ part_bias, int S, const float* __restrict__ v,
+    const float* __restrict__ g, const float* __restrict__ inv_norm, float* __restrict__ dv, float* __restrict__ dg,
+    float* __restrict__ dbias, int Cout, int Cin, int taps, int accumulate, int co, float* strip, int strip_elems)
+{
+  const bool wide = !(Cin & 3) && !((reinterpret_cast<uintptr_t>(part) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(dv)) & 15);
+  if (wide) {
+    weightnorm_bwd_row16(part, part_bias, S, v, g, inv_norm, dv, dg, dbias, Cout, Cin, taps, accumulate, co, strip, strip + strip_elems);
+  } else {
+    weightnorm_bwd_row(part, part_bias, S, v, g, inv_norm, dv, dg, dbias, Cout, Cin, taps, accumulate, co, strip);
+    // vmcnt(0) lgkmcnt(0): the compiler lays this branch out ahead of the other one and, with flat accesses of this one pending on
+    // paper, puts a full wait between every two groups of loads there
+    __builtin_amdgcn_s_waitcnt(0x0070);
+  }
+}
+
+// Rows (waves) per workgroup: blockDim.x / 64, from wnb_rows() on the host.
+__global__ __launch_bounds__(64 * WNB_ROWS, 3) void gt_weightnorm_bwd_kernel(
     const float* __restrict__ part, const float* __restrict__ part_bias, int S, const float* __restrict__ v,
     const float* __restrict__ g, const float* __restrict__ inv_norm, float* __restrict__ dv, float* __restrict__ dg,
     float* __restrict__ dbias, int Cout, int Cin, int taps, int accumulate)
 {
-  extern __shared__ float dws[];               // [WNB_ROWS][Cin*taps] summed dW of a co, natural (ci, tap) order
-  const int w = threadIdx.x >> 6, co = blockIdx.x * WNB_ROWS + w;
+  extern __shared__ __attribute__((aligned(16))) float dws[];    // [rows][2][strip]: summed dW of a co in natural (ci, tap) order | its v row
+  const int w = threadIdx.x >> 6, co = blockIdx.x * (blockDim.x >> 6) + w;
   if (co >= Cout) return;
-  weightnorm_bwd_row(part, part_bias, S, v, g, inv_norm, dv, dg, dbias, Cout, Cin, taps, accumulate, co, dws + (size_t)w * Cin * taps);
+  const int strip = (Cin * taps + 3) & ~3;
+  weightnorm_bwd_dispatch(part, part_bias, S, v, g, inv_norm, dv, dg, dbias, Cout, Cin, taps, accumulate, co, dws + (size_t)w * 2 * strip, strip);
 }
 
-// Batched form: one wave per output channel of ANY conv; the job is found by bisection on row_start.
-__global__ __launch_bounds__(64 * WNB_ROWS) void gt_weightnorm_bwd_batched_kernel(const gt_wnb_job* __restrict__ jobs, int n_jobs, int total_rows,
+// Batched form: one wave per output channel of ANY conv.  The job of a row is the last one whose row_start is at or before it: every
+// lane tests the row_start of one job (of four, 256 jobs per round of independent loads) and the ballots count the jobs at or before
+// the row — one load latency where a bisection over 120 jobs spent seven dependent ones before the row's first useful load.
+__global__ __launch_bounds__(64 * WNB_ROWS, 3) void gt_weightnorm_bwd_batched_kernel(const gt_wnb_job* __restrict__ jobs, int n_jobs, int total_rows,
                                                                                 int max_row_elems)
 {
-  extern __shared__ float dws[];
-  const int w = threadIdx.x >> 6, row = blockIdx.x * WNB_ROWS + w;
+  extern __shared__ __attribute__((aligned(16))) float dws[];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, row = blockIdx.x * (blockDim.x >> 6) + w;
   if (row >= total_rows) return;
-  int lo = 0, hi = n_jobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].row_start <= row) lo = mid; else hi = mid - 1;
+  int cnt = 0;
+  for (int i0 = 0; i0 < n_jobs; i0 += 256) {
+    int rs[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int i = i0 + 64 * u + lane;
+      rs[u] = jobs[min(i, n_jobs - 1)].row_start;                // unpredicated: the four loads leave together
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) cnt += __popcll(__ballot(i0 + 64 * u + lane < n_jobs && rs[u] <= row));
   }
+  const int lo = __builtin_amdgcn_readfirstlane(cnt > 0 ? cnt - 1 : 0);
   const gt_wnb_job j = jobs[lo];
-  weightnorm_bwd_row(j.part, j.part_bias, j.S, j.v, j.g, j.inv_norm, j.dv, j.dg, j.dbias, j.Cout, j.Cin, j.taps,
-                     j.accumulate, row - j.row_start, dws + (size_t)w * max_row_elems);
+  const int strip = (max_row_elems + 3) & ~3;
+  weightnorm_bwd_dispatch(j.part, j.part_bias, j.S, j.v, j.g, j.inv_norm, j.dv, j.dg, j.dbias, j.Cout, j.Cin, j.taps,
+                          j.accumulate, row - j.row_start, dws + (size_t)w * 2 * strip, strip);
+}
+
+// LDS of a launch: every wave holds [2][strip] floats (dW | v of its row), strip = the longest row rounded up to 16 bytes.  Four rows
+// per workgroup up to n = 1920; three at the packing limit n = 2304 (54 KB); two up to the n = 3840 the 4-byte form always took.
+constexpr size_t WNB_LDS_MAX = 60 * 1024;
+static size_t wnb_lds(int rows, int max_row_elems) { return (size_t)rows * 2 * ((max_row_elems + 3) & ~3) * sizeof(float); }
+static int wnb_rows(int max_row_elems)
+{
+  int rows = WNB_ROWS;
+  while (rows > 1 && wnb_lds(rows, max_row_elems) > WNB_LDS_MAX) --rows;
+  return rows;
 }
 
 // Column sums over rows: out[n] (+)= sum_m Y[m, n] (bias gradients).  bf16 or fp32 input.
@@ -455,10 +666,11 @@ extern "C" int gt_weightnorm_bwd(const void* workspace, int R, const float* v, c
   if (g && (!inv_norm || !dg)) return GT_E_INVAL;
   int S = 0;
   gt_conv_wgrad_workspace_bytes(R, Cin, Cout, taps, &S);
-  const size_t lds = (size_t)WNB_ROWS * Cin * taps * sizeof(float);
-  if (lds > 60 * 1024) return GT_E_UNSUPPORTED;
+  if ((size_t)WNB_ROWS * Cin * taps * sizeof(float) > WNB_LDS_MAX) return GT_E_UNSUPPORTED;
+  const int rows = wnb_rows(Cin * taps);
+  const size_t lds = wnb_lds(rows, Cin * taps);
   const float* part = static_cast<const float*>(workspace);
-  hipLaunchKernelGGL(gt_weightnorm_bwd_kernel, dim3((Cout + WNB_ROWS - 1) / WNB_ROWS), dim3(64 * WNB_ROWS), lds, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(gt_weightnorm_bwd_kernel, dim3((Cout + rows - 1) / rows), dim3(64 * rows), lds, static_cast<hipStream_t>(stream),
                      part, part + (size_t)S * taps * Cout * Cin, S, v, g, inv_norm, dv, dg, dbias, Cout, Cin, taps, accumulate);
   return gt_launch_status(__func__);
 }
@@ -480,9 +692,10 @@ extern "C" int gt_conv_wgrad_batched(const void* jobs_device, const void* tiles_
 extern "C" int gt_weightnorm_bwd_batched(const void* jobs_device, int n_jobs, int total_rows, int max_row_elems, void* stream)
 {
   if (!jobs_device || n_jobs <= 0 || total_rows <= 0 || max_row_elems <= 0) return GT_E_INVAL;
-  const size_t lds = (size_t)WNB_ROWS * max_row_elems * sizeof(float);
-  if (lds > 60 * 1024) return GT_E_UNSUPPORTED;
-  hipLaunchKernelGGL(gt_weightnorm_bwd_batched_kernel, dim3((total_rows + WNB_ROWS - 1) / WNB_ROWS), dim3(64 * WNB_ROWS), lds,
+  if ((size_t)WNB_ROWS * max_row_elems * sizeof(float) > WNB_LDS_MAX) return GT_E_UNSUPPORTED;
+  const int rows = wnb_rows(max_row_elems);
+  const size_t lds = wnb_lds(rows, max_row_elems);
+  hipLaunchKernelGGL(gt_weightnorm_bwd_batched_kernel, dim3((total_rows + rows - 1) / rows), dim3(64 * rows), lds,
                      static_cast<hipStream_t>(stream), static_cast<const gt_wnb_job*>(jobs_device), n_jobs, total_rows, max_row_elems);
   return gt_launch_status(__func__);
 }
