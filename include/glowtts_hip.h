@@ -301,7 +301,13 @@ int gt_param_partials_reduce(const gt_partials_args* args, void* stream);
  * q,k,v,out: bf16 rows [B*Tp, H*D]; Ek,Ev: [2*win+1, D] fp32 shared by heads; P: [B,H,T,T] fp32
  * (softmax before dropout, kept for the backward); workspace: gt_attn_bwd_workspace_bytes(B,T,H) bytes of
  * scratch, 16-byte aligned; dEk/dEv ACCUMULATE.  D = 96, win = 4, T <= 384 run on bf16 MFMA (gt_attn_mfma_shape), the rest
- * on the generic kernels. */
+ * on the generic kernels.
+ *   workspace   device scratch of at least gt_attn_bwd_workspace_bytes(B,T,H) bytes, 16-byte aligned; after gt_attn_bwd it
+ *               holds what the call's second pass read (dS = P (dP - sum_j dP P) / sqrt(D), zero where masked):
+ *               on the MFMA kernels bf16 dS^T [B,H,T(key j),TI(query i)], TI = ceil(T/32)*32, followed by dropout(P)^T in
+ *               the same shape with the rows of queries i >= lens[b] zero, columns i >= T of both zero;
+ *               on the generic kernels fp32 dS [B,H,T(query i),T(key j)].
+ * Query rows i >= lens[b] contribute nothing to dk, dv, dEk and dEv (and get dq = 0) whatever dout holds there. */
 int gt_attn_fwd(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
                 const int32_t* lens, void* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, int D, int win,
                 float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream);
