@@ -137,6 +137,11 @@ PROTOTYPES = {
     "gt_synth_prior": (c_int, [c_void_p, c_void_p]),
     "gt_synth_prior_args_size": (c_int, []),
     "gt_randn_rows": (c_int, [c_void_p, c_int, c_int, c_u32, c_u32, c_float, c_void_p]),
+    "gt_synth_call_size": (c_int, []),
+    "gt_synth_geometry": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
+    "gt_synth_prior_call": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "gt_randn_rows_call": (c_int, [c_void_p, c_int, c_int, c_void_p, c_u32, c_int, c_void_p]),
 }
 
 
@@ -253,6 +258,12 @@ class SynthPriorArgs(ctypes.Structure):
                 ("row0", c_void_p), ("Tp", c_int), ("R", c_int), ("rows", c_void_p), ("z_m", c_void_p), ("z_logs", c_void_p),
                 ("frame2token", c_void_p), ("attn", c_void_p), ("B", c_int), ("C", c_int), ("Tx", c_int), ("Ty", c_int),
                 ("seed", c_u32), ("noise_scale", c_float)]
+
+
+class SynthCall(ctypes.Structure):
+    """struct gt_synth_call (include/glowtts_hip.h): the scalars of one synthesis call, read from device memory; its size is checked
+    against gt_synth_call_size() (tests/test_synthesis_graph_cabi.py)"""
+    _fields_ = [("seed", c_u32), ("noise_scale", c_float), ("noise_scale_w", c_float), ("length_scale", c_float)]
 
 
 def fill_args(cls, **kw):

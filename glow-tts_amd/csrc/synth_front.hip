@@ -57,7 +57,10 @@ __global__ __launch_bounds__(64) void gt_synth_lengths_kernel(const float* __res
 // tiles they fall into, so every row has one writer.  The tokens a tile touches are a contiguous range of the utterance: their
 // means / log-deviations go through LDS frame by frame (a wave reads one channel along Tx, one workgroup-wide phase later a
 // wave writes rows along the channels).
-__global__ __launch_bounds__(256) void gt_synth_prior_kernel(gt_synth_prior_args a)
+// CALL: seed / noise_scale come from the gt_synth_call block in device memory (a captured graph replays with the scalars of
+// every call) instead of the by-value arguments; the only difference between the two instantiations.
+template <bool CALL>
+__global__ __launch_bounds__(256) void gt_synth_prior_kernel(gt_synth_prior_args a, const gt_synth_call* __restrict__ call)
 {
   __shared__ float m_s[SF_C_MAX * SF_LD];
   __shared__ float l_s[SF_C_MAX * SF_LD];
@@ -67,6 +70,8 @@ __global__ __launch_bounds__(256) void gt_synth_prior_kernel(gt_synth_prior_args
   const int C = a.C, Tx = a.Tx, Ty = a.Ty;
   const int n = min(max(a.x_len[b], 0), Tx);
   const int ylen = a.y_len[b];
+  // a tile behind the utterance's rows AND behind the optional outputs' frames has nothing to write (a capacity-sized grid)
+  if (k * SF_ROWS >= gt_row_count(a.row0, b, a.Tp) && k * SF_FRAMES - 2 * HALO >= Ty) return;
   for (int i = tid; i < n; i += 256) cum_s[i] = a.cum[(size_t)b * Tx + i];
   __syncthreads();
   const int t0 = k * SF_FRAMES - 2 * HALO;
@@ -104,8 +109,8 @@ __global__ __launch_bounds__(256) void gt_synth_prior_kernel(gt_synth_prior_args
   __syncthreads();
   const int base = gt_row_base(a.row0, b, a.Tp), nrow = gt_row_count(a.row0, b, a.Tp);
   const int len_sq = ylen / 2;                          // commons.squeeze drops an odd trailing frame
-  const uint32_t key = randn_key(a.seed, 0u, (uint32_t)b);
-  const float ns = a.noise_scale;
+  const uint32_t key = randn_key(CALL ? call->seed : a.seed, 0u, (uint32_t)b);
+  const float ns = CALL ? call->noise_scale : a.noise_scale;
   const int ldr = 2 * C;
   for (int idx = tid; idx < SF_ROWS * C; idx += 256) {
     const int j = idx / C, c = idx - j * C;
@@ -128,9 +133,11 @@ __global__ __launch_bounds__(256) void gt_synth_prior_kernel(gt_synth_prior_args
   }
 }
 
+template <bool CALL>
 __global__ __launch_bounds__(256) void gt_randn_rows_kernel(float* __restrict__ out, int R, int ncol, uint32_t seed, uint32_t stream_id,
-                                                            float scale)
+                                                            float scale, const gt_synth_call* __restrict__ call, int which_scale)
 {
+  if (CALL) { seed = call->seed; scale = which_scale == 0 ? call->noise_scale : call->noise_scale_w; }
   const int np = (ncol + 1) >> 1;
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= R * np) return;
@@ -139,6 +146,74 @@ __global__ __launch_bounds__(256) void gt_randn_rows_kernel(float* __restrict__ 
   randn_pair(randn_key(seed, stream_id, 0u), (uint32_t)row, (uint32_t)p, e0, e1);
   out[(size_t)row * ncol + 2 * p] = e0 * scale;
   if (2 * p + 1 < ncol) out[(size_t)row * ncol + 2 * p + 1] = e1 * scale;
+}
+
+// The ragged rows layout of the squeezed mel axis from the predicted lengths, on the device: what
+// RowsCtx.row_starts + gt_rows_ctx_fill give for lengths [min(y_len, Ty_cap) / 2], with starts[B] = R_cap.  Every workgroup redoes
+// the <= 1024-element scan in LDS (4 lengths per thread, shuffles inside a wave, 4 wave totals through LDS) and fills its own 256
+// rows by binary search: no grid-wide ordering, one writer per element.  Rows that do not fit (status bit 1): the clipped offsets
+// have the closed form row0[b] = min(P[b], R_cap - 2 HALO (B - b)) of the unclipped offsets P — utterances in order, each keeps its
+// two halos and as many frames as still fit in front of the halos of those behind it — so nothing is sequential.
+__global__ __launch_bounds__(256) void gt_synth_geometry_kernel(const int32_t* __restrict__ y_len, int B, int Ty_cap, int R_cap,
+                                                                int32_t* __restrict__ row0, int32_t* __restrict__ len_sq,
+                                                                int32_t* __restrict__ y_len_eff, int64_t* __restrict__ rowbatch,
+                                                                int32_t* __restrict__ rowframe, float* __restrict__ rowmask,
+                                                                int32_t* __restrict__ rowutt, int32_t* __restrict__ status)
+{
+  __shared__ int32_t r0_s[GT_STEP_MAX_B];
+  __shared__ int32_t len_s[GT_STEP_MAX_B];
+  __shared__ int32_t wsum_s[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int yl[4], l[4];
+  int own = 0, over = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = tid * 4 + k;
+    yl[k] = i < B ? max(y_len[i], 0) : 0;
+    over |= yl[k] > Ty_cap;
+    yl[k] = min(yl[k], Ty_cap);
+    l[k] = yl[k] >> 1;
+    own += i < B ? l[k] + 2 * HALO : 0;
+  }
+  int incl = own;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) wsum_s[w] = incl;
+  over = __syncthreads_or(over);
+  int P = incl - own;                                    // unclipped offset of this thread's first utterance
+  for (int j = 0; j < w; ++j) P += wsum_s[j];
+  const int total = wsum_s[0] + wsum_s[1] + wsum_s[2] + wsum_s[3];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = tid * 4 + k;
+    if (i < B) {
+      const int start = min(P, R_cap - 2 * HALO * (B - i));
+      P += l[k] + 2 * HALO;
+      const int le = min(P, R_cap - 2 * HALO * (B - i - 1)) - start - 2 * HALO;      // frames that fit: <= l[k], >= 0
+      r0_s[i] = start;
+      len_s[i] = le;
+      if (blockIdx.x == 0) {
+        row0[i] = start;
+        len_sq[i] = le;
+        y_len_eff[i] = le == l[k] ? yl[k] : 2 * le;      // an odd trailing frame stays (the prior's optional outputs hold it)
+        if (i == B - 1) row0[B] = R_cap;                  // the last utterance owns the spare rows, masked
+      }
+    }
+  }
+  if (blockIdx.x == 0 && tid == 0) *status = (over ? 1 : 0) | (total > R_cap ? 2 : 0);
+  __syncthreads();
+  const int m = blockIdx.x * 256 + tid;
+  if (m >= R_cap) return;
+  int lo = 0, hi = B - 1;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (r0_s[mid] <= m) lo = mid; else hi = mid - 1; }
+  const int t = m - r0_s[lo] - HALO;
+  rowbatch[m] = lo;
+  if (rowutt) rowutt[m] = lo;
+  rowframe[m] = t;
+  rowmask[m] = (t >= 0 && t < len_s[lo]) ? 1.f : 0.f;
 }
 
 extern "C" int gt_synth_lengths(const float* dur, const int32_t* x_len, int32_t* cum, int32_t* y_len, float* logw, int B, int Tx,
@@ -153,8 +228,25 @@ extern "C" int gt_synth_lengths(const float* dur, const int32_t* x_len, int32_t*
 }
 
 extern "C" int gt_synth_prior_args_size(void) { return (int)sizeof(gt_synth_prior_args); }
+extern "C" int gt_synth_call_size(void) { return (int)sizeof(gt_synth_call); }
 
-extern "C" int gt_synth_prior(const gt_synth_prior_args* args, void* stream)
+extern "C" int gt_synth_geometry(const int32_t* y_len, int B, int Ty_cap, int R_cap, int32_t* row0, int32_t* len_sq, int32_t* y_len_eff,
+                                 int64_t* rowbatch, int32_t* rowframe, float* rowmask, int32_t* rowutt, int32_t* status, void* stream)
+{
+  if (B < 0 || R_cap < 0 || Ty_cap < 0 || (Ty_cap & 1)) return GT_E_INVAL;
+  if (B == 0 || R_cap == 0) return 0;
+  if (B > GT_STEP_MAX_B || Ty_cap > (1 << 20)) return GT_E_UNSUPPORTED;   // 1024 utterances of 2^19 + 4 rows stay inside int32
+  if (!y_len || !row0 || !len_sq || !y_len_eff || !rowbatch || !rowframe || !rowmask || !status) return GT_E_INVAL;
+  if ((long long)R_cap < 2LL * HALO * B) return GT_E_INVAL;               // every utterance keeps its two halos
+  if (((uintptr_t)y_len | (uintptr_t)row0 | (uintptr_t)len_sq | (uintptr_t)y_len_eff | (uintptr_t)rowframe | (uintptr_t)rowmask |
+       (uintptr_t)rowutt | (uintptr_t)status) & 3) return GT_E_ALIGN;
+  if ((uintptr_t)rowbatch & 7) return GT_E_ALIGN;
+  hipLaunchKernelGGL(gt_synth_geometry_kernel, dim3((R_cap + 255) / 256), dim3(256), 0, GT_ST(stream), y_len, B, Ty_cap, R_cap, row0,
+                     len_sq, y_len_eff, rowbatch, rowframe, rowmask, rowutt, status);
+  GT_RET();
+}
+
+static int synth_prior_launch(const gt_synth_prior_args* args, const gt_synth_call* call, bool from_call, void* stream)
 {
   if (!args) return GT_E_INVAL;
   const gt_synth_prior_args& a = *args;
@@ -162,25 +254,49 @@ extern "C" int gt_synth_prior(const gt_synth_prior_args* args, void* stream)
   if (a.R == 0 || a.B == 0) return 0;
   if (a.C <= 0 || a.Tx <= 0 || a.Ty <= 0 || a.Tp <= 2 * HALO) return GT_E_INVAL;
   if (a.Tx > SF_TX_MAX || a.C > SF_C_MAX || a.B > 65535) return GT_E_UNSUPPORTED;
-  if (!a.x_m || !a.cum || !a.x_len || !a.y_len || !a.rows) return GT_E_INVAL;
+  if (!a.x_m || !a.cum || !a.x_len || !a.y_len || !a.rows || (from_call && !call)) return GT_E_INVAL;
   if (!a.row0 && (long long)a.B * a.Tp != a.R) return GT_E_INVAL;             // uniform rows: utterance b owns [b Tp, (b + 1) Tp)
   if (!al16(a.x_m) || !al16(a.x_logs) || !al16(a.rows) || !al16(a.z_m) || !al16(a.z_logs) || !al16(a.attn)) return GT_E_ALIGN;
-  if (((uintptr_t)a.cum | (uintptr_t)a.x_len | (uintptr_t)a.y_len | (uintptr_t)a.row0 | (uintptr_t)a.frame2token) & 3) return GT_E_ALIGN;
+  if (((uintptr_t)a.cum | (uintptr_t)a.x_len | (uintptr_t)a.y_len | (uintptr_t)a.row0 | (uintptr_t)a.frame2token | (uintptr_t)call) & 3)
+    return GT_E_ALIGN;
   // row tiles over the largest utterance (Tp bounds it in the ragged layout), and frame tiles over all Ty frames of the optional outputs
   const int gx = max((a.Tp + SF_ROWS - 1) / SF_ROWS, (a.Ty + 2 * HALO + SF_FRAMES - 1) / SF_FRAMES);
-  hipLaunchKernelGGL(gt_synth_prior_kernel, dim3(gx, a.B), dim3(256), 0, GT_ST(stream), a);
+  if (from_call) hipLaunchKernelGGL(gt_synth_prior_kernel<true>, dim3(gx, a.B), dim3(256), 0, GT_ST(stream), a, call);
+  else hipLaunchKernelGGL(gt_synth_prior_kernel<false>, dim3(gx, a.B), dim3(256), 0, GT_ST(stream), a, call);
+  GT_RET();
+}
+
+extern "C" int gt_synth_prior(const gt_synth_prior_args* args, void* stream) { return synth_prior_launch(args, nullptr, false, stream); }
+
+extern "C" int gt_synth_prior_call(const gt_synth_prior_args* args, const gt_synth_call* call, void* stream)
+{
+  return synth_prior_launch(args, call, true, stream);
+}
+
+static int randn_rows_launch(float* out, int R, int ncol, uint32_t seed, uint32_t stream_id, float scale, const gt_synth_call* call,
+                             bool from_call, int which_scale, void* stream)
+{
+  if (R < 0 || ncol <= 0 || (from_call && (which_scale < 0 || which_scale > 1))) return GT_E_INVAL;
+  if (R == 0) return 0;
+  if (!out || (from_call && !call)) return GT_E_INVAL;
+  if ((uintptr_t)call & 3) return GT_E_ALIGN;
+  if ((uintptr_t)out & 3) return GT_E_ALIGN;
+  const long long n = (long long)R * ((ncol + 1) / 2);
+  if (n > 0x7fffffffLL) return GT_E_UNSUPPORTED;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (from_call)
+    hipLaunchKernelGGL(gt_randn_rows_kernel<true>, grid, dim3(256), 0, GT_ST(stream), out, R, ncol, seed, stream_id, scale, call, which_scale);
+  else
+    hipLaunchKernelGGL(gt_randn_rows_kernel<false>, grid, dim3(256), 0, GT_ST(stream), out, R, ncol, seed, stream_id, scale, call, which_scale);
   GT_RET();
 }
 
 extern "C" int gt_randn_rows(float* out, int R, int ncol, uint32_t seed, uint32_t stream_id, float scale, void* stream)
 {
-  if (R < 0 || ncol <= 0) return GT_E_INVAL;
-  if (R == 0) return 0;
-  if (!out) return GT_E_INVAL;
-  if ((uintptr_t)out & 3) return GT_E_ALIGN;
-  const long long n = (long long)R * ((ncol + 1) / 2);
-  if (n > 0x7fffffffLL) return GT_E_UNSUPPORTED;
-  hipLaunchKernelGGL(gt_randn_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, GT_ST(stream), out, R, ncol, seed, stream_id,
-                     scale);
-  GT_RET();
+  return randn_rows_launch(out, R, ncol, seed, stream_id, scale, nullptr, false, 0, stream);
+}
+
+extern "C" int gt_randn_rows_call(float* out, int R, int ncol, const gt_synth_call* call, uint32_t stream_id, int which_scale, void* stream)
+{
+  return randn_rows_launch(out, R, ncol, 0u, stream_id, 0.f, call, true, which_scale, stream);
 }

@@ -106,10 +106,11 @@ class FlowSpecDecoder(nn.Module):
         return z, logdet
 
     @torch.no_grad()
-    def reverse_rows(self, rc, rows, g=None, pitch=None, energy=None):
+    def reverse_rows(self, rc, rows, g=None, pitch=None, energy=None, out=None):
         """forward(reverse=True, prepared=True) from the squeezed latent in the rows layout: rc = ops.RowsCtx of the squeezed mel axis,
         rows [rc.R, 2 * in_channels] fp32 (what commons.squeeze + the rows packing of z would give: zero halo / padding rows)
-        -> the mel [b, in_channels, 2 * rc.T] fp32, zero past every utterance's length.  The caller has prepared the weights."""
+        -> the mel [b, in_channels, 2 * rc.T] fp32, zero past every utterance's length.  The caller has prepared the weights.
+        out: a contiguous fp32 buffer of that shape to write the mel into (a captured graph's static output) instead of a new one."""
         if (pitch is not None or energy is not None) and not hasattr(self.flows[2], "wn_pitch"):
             raise ValueError("pitch / energy conditioning needs FlowSpecDecoder(with_prosody_wn=True)")
         pitch = pitch.unsqueeze(1) if (pitch is not None and pitch.dim() == 2) else pitch
@@ -117,7 +118,7 @@ class FlowSpecDecoder(nn.Module):
         wns = [self.flows[3 * b + 2].wn for b in range(self.n_blocks)]
         conds = _wn_cond_all(wns, g)
         runner = _DecoderRunner(self, None, g is not None, False, 0, energy, pitch)
-        return runner.reverse_rows(rc, rows, conds, self._prosody_affine("wn_energy", energy), self._prosody_affine("wn_pitch", pitch))
+        return runner.reverse_rows(rc, rows, conds, self._prosody_affine("wn_energy", energy), self._prosody_affine("wn_pitch", pitch), out=out)
 
     def _prosody_affine(self, which, contour):
         """cond_layer1 of every block's wn_energy / wn_pitch as (effective weight, bias) pairs [n_blocks, 2, 2*H*n/n_sqz]:
@@ -245,7 +246,7 @@ class _DecoderRunner:
         _lib.check(L.gt_unsqueeze_rows_f32(_lib.ptr(cur), _lib.ptr(x), _lib.ptr(rc.lengths), B, C, T2 * 2, rc.Tp, _lib.ptr(rc.row0), st), "gt_unsqueeze_rows_f32")
         return x
 
-    def reverse_rows(self, rc, rows, conds, eaff=None, paff=None):
+    def reverse_rows(self, rc, rows, conds, eaff=None, paff=None, out=None):
         """reverse() for a caller that already holds the squeezed latent in the rows layout (FlowGenerator.infer with the device front
         end): rc = the RowsCtx of the squeezed mel axis, rows [rc.R, 2C] fp32 with zero halo / padding rows -> x [B, C, 2 * rc.T] fp32.
         On ragged rows the fused pass unsqueezes in its last launch."""
@@ -254,11 +255,14 @@ class _DecoderRunner:
         esig, psig = self._contour_rows(rc, self.energy, B, T2 * 2), self._contour_rows(rc, self.pitch, B, T2 * 2)
         fused = dec.fused_reverse and dec.fused_boundary and all(dec.flows[3 * b].initialized for b in range(dec.n_blocks))
         pros = dict(esig=esig, eaff=eaff, psig=psig, paff=paff)
+        if out is not None:
+            assert out.shape == (B, C, 2 * T2) and out.dtype == torch.float32 and out.is_contiguous()
         if fused and getattr(rc, "rowbatch", None) is not None:
-            x = ops.zeros_big((B, C, 2 * T2), torch.float32, rows.device)
+            x = ops.zeros_big((B, C, 2 * T2), torch.float32, rows.device) if out is None else out.zero_()
             flow_impl.decoder_rev_fused(rc, dec, rows, conds, x_bct=x, **pros)
             return x
-        return self._rows_to_x(rc, rows, B, C, T2, conds, fused, pros)
+        x = self._rows_to_x(rc, rows, B, C, T2, conds, fused, pros)
+        return x if out is None else out.copy_(x)
 
     def backward(self, saved_all, dz, dlogdet):
         L = _lib.lib()

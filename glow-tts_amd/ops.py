@@ -375,6 +375,30 @@ class RowsCtx:
         self.rowutt = torch.empty(self.R, dtype=torch.int32, device=self.device)
         self._fill(starts, lengths_host)
 
+    @classmethod
+    def capacity(cls, B, T, R, device, alloc=None):
+        """The capacity form of the ragged context (synthesis.Synthesizer): R rows and T (squeezed) frames per utterance
+        are fixed when it is built, outside capture; row0 / lengths and the per-row tables are allocated but NOT filled — the captured
+        graph's gt_synth_geometry writes them from the lengths it predicts, on the device, at every replay.  Same attributes as a
+        context built from host lengths; Tp is what such a context has when it is rounded to R (an upper bound that only sizes grids).
+        alloc(n, dtype) -> tensor: where the buffers come from (default torch.zeros)."""
+        assert not torch.cuda.is_current_stream_capturing(), "a capacity RowsCtx is built outside graph capture"
+        assert R >= 2 * HALO * B, "no room for the halos of every utterance"
+        alloc = alloc or (lambda n, dtype: torch.zeros(n, dtype=dtype, device=device))
+        rc = cls.__new__(cls)
+        rc.device, rc.B, rc.T, rc.ragged = torch.device(device), int(B), int(T), True
+        rc.rnd = rc.R = int(R)
+        rc.Tp = rc.T + 2 * HALO + rc.rnd - 1
+        rc.rowmask2d = None
+        rc._geo = alloc(2 * rc.B + 1, torch.int32)
+        rc.row0, rc.lengths = rc._geo[:rc.B + 1], rc._geo[rc.B + 1:]
+        rc._ring, rc._ring_i = [], 0
+        rc.rowbatch = alloc(rc.R, torch.int64)
+        rc.rowframe = alloc(rc.R, torch.int32)
+        rc.rowmask = alloc(rc.R, torch.float32)
+        rc.rowutt = alloc(rc.R, torch.int32)
+        return rc
+
     RING = 8
 
     def _stage(self, starts, lengths_host):

@@ -1,0 +1,386 @@
+"""Synthesis as ONE captured graph (FlowGenerator.compile_synthesis).
+
+FlowGenerator.infer with the device front end is ~116 dependent launches issued from Python; its GPU work is a fraction of the time
+the host needs to issue them.  A Synthesizer captures the whole call — text encoder, duration predictor, durations -> lengths, the
+row geometry of the mel axis (gt_synth_geometry, built on the device from the predicted lengths), the sampled prior
+(gt_synth_prior_call) and the reverse decoder — once, at sizes that are capacities, with the call's scalars (seed, noise_scale,
+length_scale) in a device-side gt_synth_call block.  One call is then one upload, one replay and one readback, nothing of it is baked
+into the graph, and the host does not synchronise in between: several calls can be in flight.
+
+A call whose predicted lengths do not fit the capacities (status != 0) is a handled outcome: the kernels stay inside their buffers,
+and the handle re-runs the call through the eager path (or raises SynthesisOverflow)."""
+import ctypes
+import weakref
+
+import torch
+
+from . import _lib, ops
+
+HALO = ops.HALO
+GUARD = 256                # canary bytes in front of and behind every static buffer
+CANARY = 0xA5
+
+
+class SynthesisOverflow(RuntimeError):
+    """The predicted lengths of a call did not fit the synthesiser's capacities.  status: bit 0 = an utterance longer than max_frames,
+    bit 1 = the rows of the batch do not fit max_rows; lengths: the predicted frame counts (unclipped)."""
+
+    def __init__(self, status, lengths):
+        super().__init__(f"synthesis overflow (status {status}): predicted lengths {lengths} do not fit the compiled capacities")
+        self.status, self.lengths = status, lengths
+
+
+def default_rows(batch, max_frames, row_round):
+    """rows of `batch` utterances of max_frames frames on the squeezed axis, rounded up to row_round"""
+    need = batch * (max_frames // 2 + 2 * HALO)
+    return -(-need // row_round) * row_round
+
+
+class SynthesisHandle:
+    """One call in flight.  lengths() / mel() / aux() wait for the call's event (not for the device).
+
+    Stream order: what mel() / aux() return is safe to use on the stream that is current when they are called.  Views of the static
+    buffers are valid until the next call is issued: that call's replay waits for the work queued so far on the streams the views
+    were handed out on (and on the stream it is issued from) before it overwrites them.  mel(clone=True) is copied on the
+    synthesiser's own stream, so the next replay waits for nothing of the caller's."""
+
+    def __init__(self, synth, slot, inputs, call):
+        self._synth, self._slot, self._inputs, self._call = synth, slot, inputs, call
+        self._saved = None          # (mel, aux, event) copies, taken in stream order when a later call was issued before this one was read
+        self._read = None           # (lengths, status) once the event has passed
+        self._eager = None
+        # mel() has been handed out: the next call may overwrite the static buffers.  aux() alone does not set it — a caller who
+        # looked at the durations first and asks for the mel after the next call still gets this call's (at the price of one copy aside)
+        self._done = False
+
+    def _wait(self):
+        if self._read is None:
+            self._synth._retire(self._slot)              # waits for the call's event, reads y_len | status, sets _read
+            assert self._read is not None, "a slot is marked read only together with its live handle"
+        return self._read
+
+    @property
+    def status(self):
+        return self._wait()[1]
+
+    def lengths(self):
+        """predicted frame counts [B] (host list); what the eager path returns as y_lengths"""
+        return list(self._wait()[0])
+
+    def _fallback(self, fallback):
+        lens, status = self._wait()
+        if not fallback:
+            raise SynthesisOverflow(status, list(lens))
+        s = self._synth
+        dev = s.device
+        if self._eager is None:
+            x, xl, g, l = self._inputs
+            seed, ns, ls = self._call
+            # on the synthesiser's stream, behind the calls in flight (the eager path shares the model's scratch buffers with the graph)
+            # and behind what the caller's stream has queued (it may have produced device-resident inputs).  EVERYTHING the eager call
+            # reads is built on that stream: the encoder gathers by token id without a bounds check, so it must never see the padded
+            # text before its fill
+            s.stream.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(s.stream):
+                for t in (x, xl, g, l):
+                    if t is not None and t.is_cuda:
+                        t.record_stream(s.stream)                                       # the caller's tensors, read on this stream
+                xp = torch.zeros(s.batch, s.max_tokens, dtype=torch.int64, device=dev)   # the text as the graph saw it: padded to max_tokens
+                xp[:, :x.shape[1]] = x.to(dev)
+                self._eager = s.gen.infer(xp, xl.to(dev), g=None if g is None else g.to(dev), l=None if l is None else l.to(dev),
+                                          noise_scale=ns, length_scale=ls, seed=seed)
+        cur = torch.cuda.current_stream(dev)
+        cur.wait_stream(s.stream)
+        for grp in self._eager:                                                        # allocated on s.stream, used on the caller's
+            for t in grp:
+                if t is not None:
+                    t.record_stream(cur)
+        return self._eager
+
+    def _from_saved(self):
+        """the outputs that were moved aside: the caller's stream waits for that copy and is registered as a user of its memory"""
+        mel, aux, ev = self._saved
+        cur = torch.cuda.current_stream(self._synth.device)
+        cur.wait_event(ev)
+        for t in [mel] + list((aux or {}).values()):
+            t.record_stream(cur)
+        return mel, aux
+
+    def mel(self, clone=False, fallback=True):
+        """[B, C, max(lengths)] fp32 — max(lengths) rounded down to even, as infer returns it: the squeeze drops an odd trailing frame —
+        zero past every utterance's length: a view of the synthesiser's static buffer, valid until the next call (clone=True: a copy
+        that outlives it).  After an overflow: the eager path's mel of the same call, re-run when this is called (fallback=False:
+        SynthesisOverflow is raised here, not when the call was issued)."""
+        lens, status = self._wait()
+        if status != 0:
+            return self._fallback(fallback)[0][0]
+        self._done = True
+        s = self._synth
+        T = max(lens) // 2 * 2
+        if self._saved is not None:                      # a later call was issued first: this call's outputs were moved aside
+            return self._from_saved()[0][:, :, :T]
+        cur = torch.cuda.current_stream(s.device)
+        if not clone:
+            s._handed.add(cur)                           # the next replay waits for what this stream has queued by then
+            return s.mel_static[:, :, :T]
+        with torch.cuda.stream(s.stream):                # idle behind this call (its event has passed): ordered before the next replay
+            out = s.mel_static[:, :, :T].clone()
+        cur.wait_stream(s.stream)
+        out.record_stream(cur)
+        return out
+
+    def aux(self, fallback=True):
+        """aux=True: dict(z_m, z_logs [B, C, Ty], attn [B, 1, Tx, Ty], logw, logw_ [B, 1, Tx]) as infer returns them (views, valid until
+        the next call)"""
+        s = self._synth
+        if not s.aux:
+            raise RuntimeError("compile_synthesis(aux=True) keeps z_m / z_logs / attn / logw / logw_")
+        lens, status = self._wait()
+        if status != 0:
+            (y, z_m, z_logs, _, _), _, (attn, logw, logw_), _ = self._fallback(fallback)
+            return dict(z_m=z_m, z_logs=z_logs, attn=attn, logw=logw, logw_=logw_)
+        if self._saved is not None:
+            src = self._from_saved()[1]
+        else:
+            src = s.aux_static
+            s._handed.add(torch.cuda.current_stream(s.device))
+        Ty = max(lens)
+        return dict(z_m=src["z_m"][:, :, :Ty], z_logs=src["z_logs"][:, :, :Ty], attn=src["attn"][:, :, :, :Ty], logw=src["logw"],
+                    logw_=src["logw_"])
+
+
+class Synthesizer:
+    """gen.compile_synthesis(...): see FlowGenerator.compile_synthesis.  Attributes: batch, max_tokens, max_frames, max_rows, aux,
+    overflows (calls whose lengths did not fit; a call is counted when its status is read — by its handle, or when its ring slot is
+    taken again), mel_static / aux_static (the graph's outputs), stream (its own), captured_entries (C-ABI launches inside the graph).
+    Any number of calls may be in flight: the RING-th call after an unread one first reads that one's lengths and status into its
+    handle (which waits for it), so a handle read late still returns its own call's."""
+
+    RING = 8
+
+    def __init__(self, gen, batch, max_tokens, max_frames, max_rows=None, aux=False):
+        if gen.use_sdp or gen.use_spp or gen.use_sep or gen.use_emo_embeds:
+            raise NotImplementedError("compile_synthesis covers the deterministic duration predictor with optional speaker / language "
+                                      "vectors; stochastic predictors and emotion inputs (cfg 5) are not captured")
+        if not (gen.synthesis_front and gen.decoder.fused_reverse and gen.decoder._inv_cache is not None):
+            raise RuntimeError("compile_synthesis needs store_inverse(fused_reverse=True, device_front=True) in effect")
+        if gen.n_sqz != 2:
+            raise NotImplementedError("compile_synthesis needs n_sqz = 2 (the rows layout of the fused reverse pass)")
+        batch, max_tokens, max_frames = int(batch), int(max_tokens), int(max_frames)
+        if batch < 1 or batch > _lib.STEP_MAX_B or max_tokens < 1 or max_tokens > 512 or max_frames < 2 or max_frames % 2:
+            raise ValueError("compile_synthesis: 1 <= batch <= 1024, 1 <= max_tokens <= 512, max_frames even and >= 2")
+        self.gen, self.batch, self.max_tokens, self.max_frames, self.aux = gen, batch, max_tokens, max_frames, bool(aux)
+        self.max_rows = int(max_rows) if max_rows is not None else default_rows(batch, max_frames, gen.rows_cfg.row_round)
+        if self.max_rows < 2 * HALO * batch:
+            raise ValueError("compile_synthesis: max_rows leaves no room for the halos of every utterance")
+        if self.max_rows % 8:
+            # the kernels state no granularity of R; ragged contexts exist, and are tested, with R rounded to 8 and above
+            raise ValueError("compile_synthesis: max_rows must be a multiple of 8")
+        self.device = dev = next(gen.parameters()).device
+        self.overflows = 0
+        self._guards = []
+        B, Tx, Ty, R, C = batch, max_tokens, max_frames, self.max_rows, gen.out_channels
+        # ---- static inputs: ONE buffer = ids | x_lengths | call block | g | l, uploaded with one copy
+        self.g_dim = (512 if gen.use_spk_embeds else gen.gin_channels) if (gen.gin_channels or gen.use_spk_embeds) else 0
+        self.takes_l = bool(gen.use_lang_embeds and gen.lin_channels)
+        lay, off = {}, 0
+        for name, n, dt in (("ids", B * Tx, torch.int64), ("x_len", B, torch.int64), ("call", 4, torch.int32),
+                            ("g", B * self.g_dim, torch.float32), ("l", B if self.takes_l else 0, torch.int64)):
+            lay[name] = (off, n, dt)
+            off += (n * torch.empty(0, dtype=dt).element_size() + 15) // 16 * 16
+        self._layout, self._in_bytes = lay, off
+        self._in = self._static(off, torch.uint8)
+        view = lambda name: self._in[lay[name][0]:lay[name][0] + lay[name][1] * torch.empty(0, dtype=lay[name][2]).element_size()].view(lay[name][2])  # noqa: E731
+        self.ids, self.x_len, self.call = view("ids").view(B, Tx), view("x_len"), view("call")
+        self.g = view("g").view(B, self.g_dim) if self.g_dim else None
+        self.l = view("l") if self.takes_l else None
+        self.length_scale = self.call.view(torch.float32)[3]           # 0-dim: read by the graph's torch plumbing at replay
+        # ---- static outputs
+        self._back = self._static(B + 1, torch.int32)                    # y_len | status: the call's one readback
+        self.y_len, self.status = self._back[:B], self._back[B:]
+        self.y_len_eff = self._static(B, torch.int32)
+        self.cum = self._static(B * Tx, torch.int32).view(B, Tx)
+        self.rows = self._static(R * 2 * C, torch.float32).view(R, 2 * C)
+        self.mel_static = self._static(B * C * Ty, torch.float32).view(B, C, Ty)
+        self.aux_static = None
+        if self.aux:
+            self.aux_static = dict(z_m=self._static(B * C * Ty, torch.float32).view(B, C, Ty),
+                                   z_logs=self._static(B * C * Ty, torch.float32).view(B, C, Ty),
+                                   attn=self._static(B * Tx * Ty, torch.float32).view(B, 1, Tx, Ty),
+                                   logw_=self._static(B * Tx, torch.float32).view(B, 1, Tx))
+        self.rc = ops.RowsCtx.capacity(B, Ty // 2, R, dev, alloc=self._static)
+        self.rc.stamps = None
+        self._ring, self._ring_i = [], 0
+        self._latest = None
+        self._handed = set()                                             # streams that views of the static outputs were handed out on
+        self.stream = torch.cuda.Stream(device=dev)
+        self._capture()
+
+    # ---- buffers ----------------------------------------------------------------------------------------------------------------
+    def _static(self, n, dtype):
+        """n elements between two canary margins (guards_intact checks them), zero-filled"""
+        nbytes = max(n, 1) * torch.empty(0, dtype=dtype).element_size()
+        pad = (nbytes + 15) // 16 * 16
+        flat = torch.full((pad + 2 * GUARD,), CANARY, dtype=torch.uint8, device=self.device)
+        flat[GUARD:GUARD + nbytes] = 0
+        self._guards.append((flat, nbytes))
+        return flat[GUARD:GUARD + nbytes].view(dtype)[:n]
+
+    def guards_intact(self):
+        """True when no byte of the canary margins around the static buffers has changed"""
+        ok = torch.ones((), dtype=torch.bool, device=self.device)
+        for flat, nbytes in self._guards:
+            ok = ok & (flat[:GUARD] == CANARY).all() & (flat[GUARD + nbytes:] == CANARY).all()
+        return bool(ok)
+
+    # ---- the call, as launches ------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def _body(self):
+        from .text_models import _DurationRunner
+        gen, rcy = self.gen, self.rc
+        L = _lib.lib()
+        st = _lib.current_stream(self.device)
+        B, Tx, Ty, C = self.batch, self.max_tokens, self.max_frames, gen.out_channels
+        gen.rows_cfg.host_lengths.clear()
+        g = gen.condition(self.g, None, None) if self.g is not None else None
+        l = gen.emb_l(self.l).unsqueeze(-1) if self.l is not None else None
+        xo, x_m, x_logs, x_mask = gen.encoder(self.ids, self.x_len, l=l, g=g, prepared=True)
+        rc, xb = gen.encoder._last_rows
+        pw = gen.encoder.proj_w
+        dvec = pw.cond_vec(g, l)
+        runner = _DurationRunner(pw, rc, xb, False, 0, has_cond=dvec is not None)
+        (logw,), _ = runner.forward(*([dvec] if dvec is not None else []))
+        # exp, length_scale and ceil stay in torch on [B, Tx], as in infer — length_scale is a device scalar of the call block
+        dur = torch.ceil(torch.exp(logw) * x_mask * self.length_scale).squeeze(1).contiguous()
+        xl = self.x_len.to(torch.int32)
+        a = self.aux_static or {}
+        _lib.check(L.gt_synth_lengths(_lib.ptr(dur), _lib.ptr(xl), _lib.ptr(self.cum), _lib.ptr(self.y_len), _lib.ptr(a.get("logw_")), B, Tx, st),
+                   "gt_synth_lengths")
+        _lib.check(L.gt_synth_geometry(_lib.ptr(self.y_len), B, Ty, rcy.R, _lib.ptr(rcy.row0), _lib.ptr(rcy.lengths), _lib.ptr(self.y_len_eff),
+                                       _lib.ptr(rcy.rowbatch), _lib.ptr(rcy.rowframe), _lib.ptr(rcy.rowmask), _lib.ptr(rcy.rowutt),
+                                       _lib.ptr(self.status), st), "gt_synth_geometry")
+        xm = x_m.float().contiguous()
+        xs = None if gen.mean_only else x_logs.float().contiguous()
+        args = _lib.fill_args(_lib.SynthPriorArgs, x_m=xm, x_logs=xs, cum=self.cum, x_len=xl, y_len=self.y_len_eff, row0=rcy.row0, Tp=rcy.Tp,
+                              R=rcy.R, rows=self.rows, z_m=a.get("z_m"), z_logs=a.get("z_logs"), frame2token=None, attn=a.get("attn"),
+                              B=B, C=C, Tx=Tx, Ty=Ty, seed=0, noise_scale=0.0)
+        _lib.check(L.gt_synth_prior_call(ctypes.byref(args), _lib.ptr(self.call), st), "gt_synth_prior_call")
+        gen.decoder.reverse_rows(rcy, self.rows, g=g, out=self.mel_static)
+        if self.aux:
+            a["logw"] = logw
+        return xm, xs, xl, dur, logw                                     # kept: the graph replays into these
+
+    def _capture(self):
+        dev = self.device
+        cur = torch.cuda.current_stream(dev)
+        # warm-up inputs: a full-length text of token 1, no noise — whatever lengths come out, the kernels stay inside the capacities
+        self.ids.fill_(1)
+        self.x_len.fill_(self.max_tokens)
+        self.call.copy_(self._call_words(0, 0.0, 1.0).to(dev))
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            # eager, on the capture stream: one-time attribute calls, scratch growth, pointer tables built "outside graph capture"
+            with _lib.record_calls() as names:
+                self._body()
+            self.captured_entries = len(names)                           # C-ABI launches inside the graph (the rest is aten plumbing)
+        self.stream.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
+            self._keep = self._body()
+        cur.wait_stream(self.stream)
+        torch.cuda.synchronize(dev)
+
+    # ---- calling ------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _call_words(seed, noise_scale, length_scale):
+        c = _lib.SynthCall(seed=int(seed) & 0xFFFFFFFF, noise_scale=float(noise_scale), noise_scale_w=1.0, length_scale=float(length_scale))
+        return torch.frombuffer(bytearray(bytes(c)), dtype=torch.int32).clone()
+
+    def _slot(self):
+        """the next [pinned staging of the inputs, pinned readback, event, weakref of the call's handle, read] of the ring; a slot's
+        event is recorded behind the readback of the call that used it.  A slot that is taken again is retired first: its call's
+        lengths and status go to its handle (if that is still alive) before the next call's readback replaces them."""
+        if len(self._ring) < self.RING:
+            self._ring.append([torch.zeros(self._in_bytes, dtype=torch.uint8).pin_memory(),
+                               torch.zeros(self.batch + 1, dtype=torch.int32).pin_memory(), torch.cuda.Event(), None, True])
+            slot = self._ring[-1]
+        else:
+            slot = self._ring[self._ring_i % self.RING]
+            self._retire(slot)
+        self._ring_i += 1
+        return slot
+
+    def _retire(self, slot):
+        """wait for the slot's call, read its y_len | status ONCE: counted in `overflows`, handed to the call's handle"""
+        if slot[4]:
+            return
+        slot[2].synchronize()
+        vals = slot[1].tolist()
+        slot[4] = True
+        if vals[-1] != 0:
+            self.overflows += 1
+        h = slot[3]() if slot[3] is not None else None
+        if h is not None:
+            h._read = (vals[:-1], vals[-1])
+            h._slot = None
+        slot[3] = None
+
+    def __call__(self, x, x_lengths, g=None, l=None, seed=None, noise_scale=1., length_scale=1.):
+        """-> SynthesisHandle.  x [batch, <= max_tokens] ids (zero-padded to max_tokens), x_lengths [batch], g / l as infer takes them;
+        host tensors are staged directly (device tensors are read back first).  Nothing is launched when the shapes do not fit."""
+        B, Tx = self.batch, self.max_tokens
+        if x.dim() != 2 or x.shape[0] != B or x_lengths.shape != (B,):
+            raise ValueError(f"this synthesiser is compiled for a batch of {B}: got x {tuple(x.shape)}, x_lengths {tuple(x_lengths.shape)}")
+        if x.shape[1] > Tx:
+            raise ValueError(f"x has {x.shape[1]} tokens, the synthesiser is compiled for max_tokens = {Tx}")
+        if (g is None) != (self.g is None) or (l is None) != (self.l is None):
+            raise ValueError("g / l must be given exactly when the model takes a speaker / language vector")
+        if g is not None:
+            g2 = g.squeeze(-1) if g.dim() == 3 else g
+            if g2.shape != (B, self.g_dim):
+                raise ValueError(f"g must be [{B}, {self.g_dim}], got {tuple(g.shape)}")
+        if l is not None and l.shape != (B,):
+            raise ValueError(f"l must be [{B}], got {tuple(l.shape)}")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())      # torch's default CPU generator, as infer does
+        seed = int(seed) & 0xFFFFFFFF
+        slot = self._slot()
+        host, back, ev = slot[:3]
+        lay = self._layout
+
+        def put(name, shape=None):
+            o, n, dt = lay[name]
+            v = host[o:o + n * torch.empty(0, dtype=dt).element_size()].view(dt)
+            return v if shape is None else v.view(shape)
+
+        ids = put("ids", (B, Tx))
+        ids.zero_()
+        ids[:, :x.shape[1]].copy_(x)
+        put("x_len").copy_(x_lengths)
+        put("call").copy_(self._call_words(seed, noise_scale, length_scale))
+        if g is not None:
+            put("g", (B, self.g_dim)).copy_(g2)
+        if l is not None:
+            put("l").copy_(l)
+        prev = self._latest() if self._latest is not None else None
+        if self._handed:
+            # (no wait when nothing was handed out: clones are made on the synthesiser's own stream, so queued calls and callers that
+            # only clone never serialise with the caller's stream.)  Views of the static outputs are in use: this replay overwrites them only behind what their streams, and the stream this
+            # call comes from, have queued so far
+            for st in self._handed | {torch.cuda.current_stream(self.device)}:
+                self.stream.wait_stream(st)
+            self._handed.clear()
+        with torch.cuda.stream(self.stream):
+            if prev is not None and not prev._done and prev._saved is None and (prev._read is None or prev._read[1] == 0):
+                # the previous call has not been read yet: its outputs move aside, in stream order, before this call overwrites them
+                saved_ev = torch.cuda.Event()
+                prev._saved = (self.mel_static.clone(), {k: v.clone() for k, v in self.aux_static.items()} if self.aux else None, saved_ev)
+                saved_ev.record(self.stream)
+            self._in.copy_(host, non_blocking=True)
+            self.graph.replay()
+            back.copy_(self._back, non_blocking=True)
+            ev.record(self.stream)
+        h = SynthesisHandle(self, slot, (x, x_lengths, g, l), (seed, float(noise_scale), float(length_scale)))
+        slot[3], slot[4] = weakref.ref(h), False
+        self._latest = weakref.ref(h)
+        return h

@@ -516,6 +516,20 @@ class FlowGenerator(nn.Module):
             return self.decoder.fused_reverse
         return self.decoder.fused_reverse, self.set_synthesis_front(device_front)
 
+    def compile_synthesis(self, batch, max_tokens, max_frames, max_rows=None, aux=False):
+        """Synthesis as ONE captured graph (glow-tts_amd/synthesis.py) -> synthesis.Synthesizer.  Needs
+        store_inverse(fused_reverse=True, device_front=True) in effect.  The sizes are capacities, fixed here: a batch of exactly `batch`
+        texts of up to max_tokens tokens, up to max_frames (even) mel frames per utterance and max_rows rows of the squeezed mel axis
+        (default: `batch` utterances of max_frames frames, rounded to rows_cfg.row_round).  Calling the synthesiser —
+        `h = synth(x, x_lengths, g=None, l=None, seed=None, noise_scale=1., length_scale=1.)` — is one upload, one graph replay and one
+        readback, without a host synchronisation: `h.lengths()` / `h.mel()` wait for that call alone, so calls can be queued back to
+        back.  The mel is bit-identical to infer(seed=)'s on the same rows.  A call whose predicted lengths do not fit the capacities is
+        re-run through infer (synth.overflows counts them; `mel(fallback=False)` raises synthesis.SynthesisOverflow instead).
+        aux=True also keeps z_m, z_logs, attn, logw, logw_ (h.aux()).  Covered: the deterministic duration predictor, with the optional
+        speaker vector g and language id l; use_sdp / use_spp / use_sep or emotion inputs raise NotImplementedError."""
+        from .synthesis import Synthesizer
+        return Synthesizer(self, batch, max_tokens, max_frames, max_rows=max_rows, aux=aux)
+
     @torch.no_grad()
     def infer(self, x, x_lengths, y=None, y_lengths=None, g=None, emo=None, emo_cartesian=None, l=None, gst_token=None,
               noise_scale=1., noise_scale_w=1., f0_noise_scale=1., energy_noise_scale=1., length_scale=1., pitch_scale=1.0,

@@ -754,6 +754,38 @@ int gt_synth_prior(const gt_synth_prior_args* args, void* stream);
 int gt_synth_prior_args_size(void);             /* sizeof(gt_synth_prior_args) */
 int gt_randn_rows(float* out, int R, int ncol, uint32_t seed, uint32_t stream_id, float scale, void* stream);
 
+/* ---- Synthesis as one captured graph (FlowGenerator.compile_synthesis, glow-tts_amd/synthesis.py): nothing of a call
+ * is baked into the launch sequence — the row geometry of the mel axis is built on the device from the predicted lengths, the call's
+ * scalars are read from device memory, every size is a capacity.  Vector stores only, no atomics, one writer per element.
+ *
+ * gt_synth_geometry: y_len [B] int32 (gt_synth_lengths' output) + the capacities Ty_cap (frames, even) and R_cap (rows of the
+ *   squeezed axis) -> everything a ragged rows context of the squeezed mel axis holds, in ONE launch: exactly
+ *   RowsCtx.row_starts(lengths [v / 2], T = Ty_cap / 2) with starts[B] = R_cap, followed by gt_rows_ctx_fill:
+ *     len_sq[b] = min(y_len[b], Ty_cap) / 2,   row0[0] = 0,   row0[b + 1] = row0[b] + len_sq[b] + 2 GT_HALO,   row0[B] = R_cap
+ *     rowbatch [R_cap] int64 / rowframe / rowmask / rowutt (optional) as gt_rows_ctx_fill writes them: the rows behind the last
+ *     utterance's frames belong to the last utterance and are masked.  y_len_eff [B] = the frame count gt_synth_prior[_call] must
+ *     be given as y_len (min(y_len[b], Ty_cap); 2 len_sq[b] where the rows were cut).
+ *   status (one int32): bit 0 = some y_len[b] > Ty_cap; bit 1 = the rows of the (frame-clipped) lengths do not fit R_cap.  With
+ *   bit 1 the kernel stays inside its buffers: utterances are laid out in order, each keeps its two halos, and len_sq[b] is cut to
+ *   what fits in front of the halos of the utterances behind it (possibly 0): row0[b] = min(unclipped row0[b], R_cap - 2 GT_HALO
+ *   (B - b)).  row0 stays monotone, row0[b + 1] <= R_cap, len_sq[b] + 2 GT_HALO <= row0[b + 1] - row0[b], all R_cap table entries
+ *   are written.  A non-zero status is a handled outcome: the caller discards the call's output (or takes the clipped one).
+ *   B < 0, R_cap < 0, Ty_cap < 0 or odd: GT_E_INVAL;  B == 0 or R_cap == 0: 0;  B > GT_STEP_MAX_B or Ty_cap > 2^20:
+ *   GT_E_UNSUPPORTED;  a NULL pointer other than rowutt, or R_cap < 2 GT_HALO B (no room for the halos): GT_E_INVAL;  int32 /
+ *   fp32 pointers not 4-byte, rowbatch not 8-byte aligned: GT_E_ALIGN.
+ *
+ * gt_synth_call: the scalars of ONE synthesis call, in DEVICE memory (uploaded per call; a captured graph reads them at replay).
+ * gt_synth_prior_call / gt_randn_rows_call: gt_synth_prior / gt_randn_rows — the same kernel code, bit-identical outputs — with
+ *   seed and the scale taken from *call (args->seed / args->noise_scale are ignored; which_scale: 0 = noise_scale, 1 =
+ *   noise_scale_w, anything else GT_E_INVAL).  length_scale is read by the host-side plumbing between the duration predictor and
+ *   gt_synth_lengths.  call == NULL: GT_E_INVAL (behind the R == 0 / B == 0 returns);  not 4-byte aligned: GT_E_ALIGN. */
+typedef struct gt_synth_call { uint32_t seed; float noise_scale; float noise_scale_w; float length_scale; } gt_synth_call;
+int gt_synth_call_size(void);                   /* sizeof(gt_synth_call) */
+int gt_synth_geometry(const int32_t* y_len, int B, int Ty_cap, int R_cap, int32_t* row0, int32_t* len_sq, int32_t* y_len_eff,
+                      int64_t* rowbatch, int32_t* rowframe, float* rowmask, int32_t* rowutt, int32_t* status, void* stream);
+int gt_synth_prior_call(const gt_synth_prior_args* args, const gt_synth_call* call, void* stream);
+int gt_randn_rows_call(float* out, int R, int ncol, const gt_synth_call* call, uint32_t stream_id, int which_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,14 @@ lengths: the bench batch (B = 32, train.synth_batch's text lengths, T_y <= 750) 
 Per variant: wall time per call, what one call puts on the device (C-ABI entries + aten operators on device tensors).  On a tree
 without set_synthesis_front only the front-off variant is measured (the parent's numbers for the run-to-run spread).
 
+--graph: whole calls again, three variants alternating in one process with the same windows and repeats: eager infer with the device
+front end on (the call's readback included), the captured graph of FlowGenerator.compile_synthesis replayed call by call (each call's
+upload, replay and readback, `mel()` taken before the next call), and N calls queued before the first is read (--queue N; every
+handle is kept and its mel read afterwards, so each call but the last also pays the device copy that moves its outputs aside).  The
+same model and the same two shapes as --infer; the batch is compiled at its own sizes (150 tokens, 750 frames), the single utterance
+at 160 tokens and 800 frames and, to show what unused capacity costs, at 1600 frames.  Every repeat is recorded; output defaults to
+profiles/synth_graph_bench.json.
+
 Kernel times come from separate runs, one per shape, under
 `rocprofv3 --kernel-trace --stats -- python tools/synth_bench.py --seconds 0.1 --repeats 1 --shape batch` (or `single`)."""
 import argparse
@@ -33,13 +41,15 @@ ap.add_argument("--json", default=None)
 ap.add_argument("--seconds", type=float, default=0.5)
 ap.add_argument("--repeats", type=int, default=2)
 ap.add_argument("--infer", action="store_true", help="time whole infer calls, device front end off / on")
+ap.add_argument("--graph", action="store_true", help="time eager infer against the captured synthesis graph (compile_synthesis)")
+ap.add_argument("--queue", type=int, default=16, help="--graph: replays queued before one synchronisation")
 ap.add_argument("--shape", choices=["both", "batch", "single"], default="both", help="one shape only (a kernel-trace run per shape)")
 opt = ap.parse_args()
 
 dev = torch.device("cuda:0")
 NB, NL, H, C = 12, 4, 192, 160
 torch.manual_seed(0)
-if not opt.infer:
+if not opt.infer and not opt.graph:
     dec = models.FlowSpecDecoder(80, H, 5, 1, NB, NL, p_dropout=0.05).to(dev).eval()
     for b in range(NB):                                                # a coupling that does something (end is zero-initialised)
         torch.nn.init.normal_(dec.flows[3 * b + 2].end.weight, std=0.01)
@@ -223,4 +233,95 @@ def infer_main():
             f.write("\n")
 
 
-infer_main() if opt.infer else main()
+def graph_main():
+    import math
+    import time
+    gen = models.FlowGenerator(148, 192, 768, 256, 80, use_sdp=False, kernel_size=3, n_heads=2, n_layers_enc=6, p_dropout=0.1,
+                               n_blocks_dec=NB, kernel_size_dec=5, dilation_rate=1, n_block_layers=NL, p_dropout_dec=0.05, n_sqz=2,
+                               window_size=4, mean_only=True, prenet=True).eval()
+    with torch.no_grad():
+        for b in range(NB):
+            torch.nn.init.normal_(gen.decoder.flows[3 * b + 2].end.weight, std=0.01)
+        gen.encoder.proj_w.proj.weight.zero_()                         # 5 frames per token: ceil(4.9)
+        gen.encoder.proj_w.proj.bias.fill_(math.log(4.9))
+    gen = gen.to(dev)
+    assert gen.store_inverse(fused_reverse=True, device_front=True) == (True, True)
+    ids_b, t_x, _, _ = train.synth_batch(32, 150, 800, 0, "cpu")
+    g = torch.Generator().manual_seed(5)
+    one = torch.randint(1, 148, (1, 160), generator=g)
+    cases = []
+    if opt.shape != "single":
+        cases.append(("bench batch: B = 32, T_x <= 150, 5 frames per token", ids_b, t_x, [(int(ids_b.shape[1]), 5 * int(ids_b.shape[1]))]))
+    if opt.shape != "batch":
+        cases.append(("one utterance, 160 tokens = 800 frames", one, torch.tensor([160]), [(160, 800), (160, 1600)]))
+    out = dict(device=torch.cuda.get_device_name(0), model="cfg 2: 6 encoder layers, 12 blocks x 4 layers, H = 192, eval, "
+               "store_inverse(fused_reverse=True, device_front=True)", seconds_per_variant=opt.seconds, queued_calls=opt.queue, shapes=[])
+    for name, ids, xl, caps in cases:
+        ids_d, xl_d = ids.to(dev), xl.to(dev)
+        B = int(ids.shape[0])
+
+        def eager(n):
+            for _ in range(n):
+                res = gen.infer(ids_d, xl_d, noise_scale=0.667, seed=7)     # synchronises inside: its one readback
+            return res[0][0]
+
+        rec = dict(name=name, B=B, Tx=int(ids.shape[1]), variants={})
+        want = eager(3)
+        with _lib.record_calls() as names:
+            eager(1)
+        torch.cuda.synchronize()
+        rec["T_y"] = int(want.shape[2])
+        runs = {"eager_front_on": eager}
+        rec["variants"]["eager_front_on"] = dict(c_abi_entries_per_call=len(names), ms_per_call=[])
+        for Tx_cap, Ty_cap in caps:
+            synth = gen.compile_synthesis(B, Tx_cap, Ty_cap)
+
+            def replay(n, synth=synth):
+                for _ in range(n):
+                    y = synth(ids, xl, seed=7, noise_scale=0.667).mel()     # waits for this call's readback
+                return y
+
+            def queued(n, synth=synth):
+                hs = [synth(ids, xl, seed=7, noise_scale=0.667) for _ in range(n)]     # every handle is kept and read: each unread call's
+                return [h.mel() for h in hs][-1]                                       # mel is copied aside before the next replay
+
+            got = replay(3)
+            tag = f"{Tx_cap}x{Ty_cap}"
+            rec["variants"]["replay_" + tag] = dict(max_tokens=Tx_cap, max_frames=Ty_cap, max_rows=synth.max_rows, launches_per_call="1 upload + 1 graph replay + 1 readback",
+                                                    c_abi_entries_inside_the_graph=synth.captured_entries,
+                                                    max_abs_difference_to_eager=(got - want).abs().max().item(), overflows=synth.overflows, ms_per_call=[])
+            rec["variants"]["queued_" + tag] = dict(max_tokens=Tx_cap, max_frames=Ty_cap, max_rows=synth.max_rows, calls_per_synchronisation=opt.queue, ms_per_call=[])
+            runs["replay_" + tag] = replay
+            runs["queued_" + tag] = queued
+        for rep in range(opt.repeats):
+            for k, fn in runs.items():
+                unit = opt.queue if k.startswith("queued_") else 1
+                torch.cuda.synchronize(); t0 = time.perf_counter(); fn(5 * unit) if unit == 1 else [fn(unit) for _ in range(2)]; torch.cuda.synchronize()
+                per = (time.perf_counter() - t0) / (5 if unit == 1 else 2 * unit)
+                n = max(5, int(opt.seconds / per) + 1)
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                if unit == 1:
+                    fn(n)
+                else:
+                    n = -(-n // unit) * unit
+                    for _ in range(n // unit):
+                        fn(unit)
+                torch.cuda.synchronize()
+                rec["variants"][k]["ms_per_call"].append(round((time.perf_counter() - t0) * 1e3 / n, 4))
+        for v in rec["variants"].values():
+            t = v["ms_per_call"]
+            v["ms_mean"], v["ms_spread"] = round(sum(t) / len(t), 4), round(max(t) - min(t), 4)
+        base = rec["variants"]["eager_front_on"]["ms_mean"]
+        for k, v in rec["variants"].items():
+            if k != "eager_front_on":
+                v["over_eager_time"] = round(v["ms_mean"] / base, 4)
+        print(f'{name}: T_y {rec["T_y"]}; ' + "; ".join(f'{k} {v["ms_mean"]:.3f} ms (+- {v["ms_spread"]:.3f})' for k, v in rec["variants"].items()), flush=True)
+        out["shapes"].append(rec)
+    path = opt.json or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "synth_graph_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
+graph_main() if opt.graph else infer_main() if opt.infer else main()
