@@ -142,6 +142,15 @@ PROTOTYPES = {
                                   c_void_p, c_void_p]),
     "gt_synth_prior_call": (c_int, [c_void_p, c_void_p, c_void_p]),
     "gt_randn_rows_call": (c_int, [c_void_p, c_int, c_int, c_void_p, c_u32, c_int, c_void_p]),
+    "gt_synth_call_ext_size": (c_int, []),
+    "gt_randn_keyed": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_u32, c_u32, c_float, c_void_p]),
+    "gt_randn_keyed_call": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_u32, c_int, c_void_p]),
+    "gt_synth_frame_geometry": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
+    "gt_synth_contours": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
+    "gt_synth_contours_call": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
 
@@ -264,6 +273,13 @@ class SynthCall(ctypes.Structure):
     """struct gt_synth_call (include/glowtts_hip.h): the scalars of one synthesis call, read from device memory; its size is checked
     against gt_synth_call_size() (tests/test_synthesis_graph_cabi.py)"""
     _fields_ = [("seed", c_u32), ("noise_scale", c_float), ("noise_scale_w", c_float), ("length_scale", c_float)]
+
+
+class SynthCallExt(ctypes.Structure):
+    """struct gt_synth_call_ext (include/glowtts_hip.h): gt_synth_call + the scalars of the pitch / energy predictors; its size is
+    checked against gt_synth_call_ext_size() (tests/test_synth_prosody_cabi.py)"""
+    _fields_ = [("base", SynthCall), ("f0_noise_scale", c_float), ("energy_noise_scale", c_float), ("pitch_scale", c_float),
+                ("energy_scale", c_float)]
 
 
 def fill_args(cls, **kw):

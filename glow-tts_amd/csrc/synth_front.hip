@@ -154,6 +154,10 @@ __global__ __launch_bounds__(256) void gt_randn_rows_kernel(float* __restrict__ 
 // rows by binary search: no grid-wide ordering, one writer per element.  Rows that do not fit (status bit 1): the clipped offsets
 // have the closed form row0[b] = min(P[b], R_cap - 2 HALO (B - b)) of the unclipped offsets P — utterances in order, each keeps its
 // two halos and as many frames as still fit in front of the halos of those behind it — so nothing is sequential.
+// DIV = 2: the squeezed axis (gt_synth_geometry).  DIV = 1: the frame-rate axis of the stochastic pitch / energy predictors
+// (gt_synth_frame_geometry) — the same scan, closed form and tables on whole frames; it runs behind the DIV = 2 launch in
+// stream order, takes that launch's y_len_eff as its lengths, writes no y_len_eff of its own and ORs bit 2 into the status word.
+template <int DIV>
 __global__ __launch_bounds__(256) void gt_synth_geometry_kernel(const int32_t* __restrict__ y_len, int B, int Ty_cap, int R_cap,
                                                                 int32_t* __restrict__ row0, int32_t* __restrict__ len_sq,
                                                                 int32_t* __restrict__ y_len_eff, int64_t* __restrict__ rowbatch,
@@ -172,7 +176,7 @@ __global__ __launch_bounds__(256) void gt_synth_geometry_kernel(const int32_t* _
     yl[k] = i < B ? max(y_len[i], 0) : 0;
     over |= yl[k] > Ty_cap;
     yl[k] = min(yl[k], Ty_cap);
-    l[k] = yl[k] >> 1;
+    l[k] = DIV == 2 ? yl[k] >> 1 : yl[k];
     own += i < B ? l[k] + 2 * HALO : 0;
   }
   int incl = own;
@@ -198,12 +202,15 @@ __global__ __launch_bounds__(256) void gt_synth_geometry_kernel(const int32_t* _
       if (blockIdx.x == 0) {
         row0[i] = start;
         len_sq[i] = le;
-        y_len_eff[i] = le == l[k] ? yl[k] : 2 * le;      // an odd trailing frame stays (the prior's optional outputs hold it)
+        if (DIV == 2) y_len_eff[i] = le == l[k] ? yl[k] : 2 * le;      // an odd trailing frame stays (the prior's optional outputs hold it)
         if (i == B - 1) row0[B] = R_cap;                  // the last utterance owns the spare rows, masked
       }
     }
   }
-  if (blockIdx.x == 0 && tid == 0) *status = (over ? 1 : 0) | (total > R_cap ? 2 : 0);
+  if (blockIdx.x == 0 && tid == 0) {
+    if (DIV == 2) *status = (over ? 1 : 0) | (total > R_cap ? 2 : 0);
+    else if (total > R_cap) *status |= 4;        // one thread, behind the squeezed geometry's store in stream order
+  }
   __syncthreads();
   const int m = blockIdx.x * 256 + tid;
   if (m >= R_cap) return;
@@ -241,8 +248,24 @@ extern "C" int gt_synth_geometry(const int32_t* y_len, int B, int Ty_cap, int R_
   if (((uintptr_t)y_len | (uintptr_t)row0 | (uintptr_t)len_sq | (uintptr_t)y_len_eff | (uintptr_t)rowframe | (uintptr_t)rowmask |
        (uintptr_t)rowutt | (uintptr_t)status) & 3) return GT_E_ALIGN;
   if ((uintptr_t)rowbatch & 7) return GT_E_ALIGN;
-  hipLaunchKernelGGL(gt_synth_geometry_kernel, dim3((R_cap + 255) / 256), dim3(256), 0, GT_ST(stream), y_len, B, Ty_cap, R_cap, row0,
+  hipLaunchKernelGGL(gt_synth_geometry_kernel<2>, dim3((R_cap + 255) / 256), dim3(256), 0, GT_ST(stream), y_len, B, Ty_cap, R_cap, row0,
                      len_sq, y_len_eff, rowbatch, rowframe, rowmask, rowutt, status);
+  GT_RET();
+}
+
+extern "C" int gt_synth_frame_geometry(const int32_t* y_len_eff, int B, int Ty_cap, int Rf_cap, int32_t* row0_f, int32_t* len_f,
+                                       int64_t* rowbatch, int32_t* rowframe, float* rowmask, int32_t* rowutt, int32_t* status, void* stream)
+{
+  if (B < 0 || Rf_cap < 0 || Ty_cap < 0) return GT_E_INVAL;
+  if (B == 0 || Rf_cap == 0) return 0;
+  if (B > GT_STEP_MAX_B || Ty_cap > (1 << 20)) return GT_E_UNSUPPORTED;   // 1024 utterances of 2^20 + 4 rows stay inside int32
+  if (!y_len_eff || !row0_f || !len_f || !rowbatch || !rowframe || !rowmask || !status) return GT_E_INVAL;
+  if ((long long)Rf_cap < 2LL * HALO * B) return GT_E_INVAL;              // every utterance keeps its two halos
+  if (((uintptr_t)y_len_eff | (uintptr_t)row0_f | (uintptr_t)len_f | (uintptr_t)rowframe | (uintptr_t)rowmask | (uintptr_t)rowutt |
+       (uintptr_t)status) & 3) return GT_E_ALIGN;
+  if ((uintptr_t)rowbatch & 7) return GT_E_ALIGN;
+  hipLaunchKernelGGL(gt_synth_geometry_kernel<1>, dim3((Rf_cap + 255) / 256), dim3(256), 0, GT_ST(stream), y_len_eff, B, Ty_cap, Rf_cap,
+                     row0_f, len_f, (int32_t*)nullptr, rowbatch, rowframe, rowmask, rowutt, status);
   GT_RET();
 }
 

@@ -106,11 +106,25 @@ class FlowSpecDecoder(nn.Module):
         return z, logdet
 
     @torch.no_grad()
-    def reverse_rows(self, rc, rows, g=None, pitch=None, energy=None, out=None):
+    def reverse_rows(self, rc, rows, g=None, pitch=None, energy=None, out=None, pitch_rows=None, energy_rows=None):
         """forward(reverse=True, prepared=True) from the squeezed latent in the rows layout: rc = ops.RowsCtx of the squeezed mel axis,
         rows [rc.R, 2 * in_channels] fp32 (what commons.squeeze + the rows packing of z would give: zero halo / padding rows)
         -> the mel [b, in_channels, 2 * rc.T] fp32, zero past every utterance's length.  The caller has prepared the weights.
-        out: a contiguous fp32 buffer of that shape to write the mel into (a captured graph's static output) instead of a new one."""
+        out: a contiguous fp32 buffer of that shape to write the mel into (a captured graph's static output) instead of a new one.
+        pitch_rows / energy_rows [rc.R, 2] fp32: the contours ALREADY squeezed onto rc's rows (gt_synth_contours; what
+        flow_impl.contour_rows makes of pitch / energy), used in place of pitch / energy."""
+        if pitch_rows is not None or energy_rows is not None:
+            if pitch is not None or energy is not None:
+                raise ValueError("reverse_rows: give the contours as pitch / energy or as pitch_rows / energy_rows, not both")
+            if not hasattr(self.flows[2], "wn_pitch"):
+                raise ValueError("pitch / energy conditioning needs FlowSpecDecoder(with_prosody_wn=True)")
+            for r in (pitch_rows, energy_rows):
+                if r is not None and not (r.shape == (rc.R, 2) and r.dtype == torch.float32 and r.is_contiguous()):
+                    raise ValueError("pitch_rows / energy_rows are contiguous fp32 [rc.R, 2]")
+            wns = [self.flows[3 * b + 2].wn for b in range(self.n_blocks)]
+            runner = _DecoderRunner(self, None, g is not None, False, 0)
+            return runner.reverse_rows(rc, rows, _wn_cond_all(wns, g), self._prosody_affine("wn_energy", energy_rows),
+                                       self._prosody_affine("wn_pitch", pitch_rows), out=out, esig=energy_rows, psig=pitch_rows)
         if (pitch is not None or energy is not None) and not hasattr(self.flows[2], "wn_pitch"):
             raise ValueError("pitch / energy conditioning needs FlowSpecDecoder(with_prosody_wn=True)")
         pitch = pitch.unsqueeze(1) if (pitch is not None and pitch.dim() == 2) else pitch
@@ -246,13 +260,15 @@ class _DecoderRunner:
         _lib.check(L.gt_unsqueeze_rows_f32(_lib.ptr(cur), _lib.ptr(x), _lib.ptr(rc.lengths), B, C, T2 * 2, rc.Tp, _lib.ptr(rc.row0), st), "gt_unsqueeze_rows_f32")
         return x
 
-    def reverse_rows(self, rc, rows, conds, eaff=None, paff=None, out=None):
+    def reverse_rows(self, rc, rows, conds, eaff=None, paff=None, out=None, esig=None, psig=None):
         """reverse() for a caller that already holds the squeezed latent in the rows layout (FlowGenerator.infer with the device front
         end): rc = the RowsCtx of the squeezed mel axis, rows [rc.R, 2C] fp32 with zero halo / padding rows -> x [B, C, 2 * rc.T] fp32.
-        On ragged rows the fused pass unsqueezes in its last launch."""
+        On ragged rows the fused pass unsqueezes in its last launch.  esig / psig: contour rows already on rc (instead of the
+        runner's energy / pitch contours)."""
         dec = self.dec
         B, C, T2 = rc.B, dec.in_channels, rc.T
-        esig, psig = self._contour_rows(rc, self.energy, B, T2 * 2), self._contour_rows(rc, self.pitch, B, T2 * 2)
+        if esig is None and psig is None:
+            esig, psig = self._contour_rows(rc, self.energy, B, T2 * 2), self._contour_rows(rc, self.pitch, B, T2 * 2)
         fused = dec.fused_reverse and dec.fused_boundary and all(dec.flows[3 * b].initialized for b in range(dec.n_blocks))
         pros = dict(esig=esig, eaff=eaff, psig=psig, paff=paff)
         if out is not None:

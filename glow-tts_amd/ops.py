@@ -267,6 +267,9 @@ class RowsConfig:
         self.host_lengths = {}      # "x" / "y" -> list of ints for the batch in flight (set by FlowGenerator.forward)
         self.prebuilt = {}          # "x" / "y" -> ragged RowsCtx the next forward must use (train.Trainer, around capture / replay)
         self.stamps = None          # KernelStamps for the decoder's fused WaveNet kernels (bench.py), attached to the "y" context
+        # infer under set_synthesis_front(noise_key="frame"): the frame-rate rows of the pitch / energy predictors are ragged (padded
+        # frames cost nothing); False = uniform rows, for measuring the difference (tools/synth_bench.py --cfg5)
+        self.frame_rows_ragged = True
         # how the step is laid out over streams (defaults from the process environment, read when the model is built; the owner of
         # the model — a Trainer, a test — changes THIS object, not a module global):
         import os

@@ -8,7 +8,12 @@ length_scale) in a device-side gt_synth_call block.  One call is then one upload
 into the graph, and the host does not synchronise in between: several calls can be in flight.
 
 A call whose predicted lengths do not fit the capacities (status != 0) is a handled outcome: the kernels stay inside their buffers,
-and the handle re-runs the call through the eager path (or raises SynthesisOverflow)."""
+and the handle re-runs the call through the eager path (or raises SynthesisOverflow).
+
+compile_synthesis(stochastic=True) captures the FULL model the same way: the emotion front end, the stochastic
+duration predictor in reverse, and the stochastic pitch / energy predictors on a second capacity context — the ragged frame-rate rows,
+built on the device by gt_synth_frame_geometry — with noise keyed by (utterance, token / frame) (gt_randn_keyed_call), the call's eight
+scalars in a gt_synth_call_ext block, and the contours written into the decoder's rows by gt_synth_contours_call.  One stream, no fork."""
 import ctypes
 import weakref
 
@@ -23,11 +28,18 @@ CANARY = 0xA5
 
 class SynthesisOverflow(RuntimeError):
     """The predicted lengths of a call did not fit the synthesiser's capacities.  status: bit 0 = an utterance longer than max_frames,
-    bit 1 = the rows of the batch do not fit max_rows; lengths: the predicted frame counts (unclipped)."""
+    bit 1 = the rows of the batch do not fit max_rows, bit 2 = the frame-rate rows of the pitch / energy predictors do not fit
+    max_frame_rows; lengths: the predicted frame counts (unclipped)."""
 
     def __init__(self, status, lengths):
         super().__init__(f"synthesis overflow (status {status}): predicted lengths {lengths} do not fit the compiled capacities")
         self.status, self.lengths = status, lengths
+
+
+def default_frame_rows(batch, max_frames, row_round):
+    """rows of `batch` utterances of max_frames frames on the un-squeezed axis, rounded up to row_round"""
+    need = batch * (max_frames + 2 * HALO)
+    return -(-need // row_round) * row_round
 
 
 def default_rows(batch, max_frames, row_round):
@@ -46,7 +58,7 @@ class SynthesisHandle:
 
     def __init__(self, synth, slot, inputs, call):
         self._synth, self._slot, self._inputs, self._call = synth, slot, inputs, call
-        self._saved = None          # (mel, aux, event) copies, taken in stream order when a later call was issued before this one was read
+        self._saved = None          # (mel, aux, event, prosody) copies, taken in stream order when a later call was issued before this one was read
         self._read = None           # (lengths, status) once the event has passed
         self._eager = None
         # mel() has been handed out: the next call may overwrite the static buffers.  aux() alone does not set it — a caller who
@@ -74,21 +86,26 @@ class SynthesisHandle:
         s = self._synth
         dev = s.device
         if self._eager is None:
-            x, xl, g, l = self._inputs
-            seed, ns, ls = self._call
+            x, xl, g, l, emo, emoc = self._inputs
+            seed, ns, ls = self._call[:3]
+            # a full-model synthesiser passes every scalar of the call on; the plain one calls infer as it always did
+            more = dict(zip(("noise_scale_w", "f0_noise_scale", "energy_noise_scale", "pitch_scale", "energy_scale"), self._call[3:])) \
+                if s.stochastic else {}
+            if emo is not None:
+                more.update(emo=emo.to(dev), emo_cartesian=emoc.to(dev))
             # on the synthesiser's stream, behind the calls in flight (the eager path shares the model's scratch buffers with the graph)
             # and behind what the caller's stream has queued (it may have produced device-resident inputs).  EVERYTHING the eager call
             # reads is built on that stream: the encoder gathers by token id without a bounds check, so it must never see the padded
             # text before its fill
             s.stream.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(s.stream):
-                for t in (x, xl, g, l):
+                for t in (x, xl, g, l, emo, emoc):
                     if t is not None and t.is_cuda:
                         t.record_stream(s.stream)                                       # the caller's tensors, read on this stream
                 xp = torch.zeros(s.batch, s.max_tokens, dtype=torch.int64, device=dev)   # the text as the graph saw it: padded to max_tokens
                 xp[:, :x.shape[1]] = x.to(dev)
                 self._eager = s.gen.infer(xp, xl.to(dev), g=None if g is None else g.to(dev), l=None if l is None else l.to(dev),
-                                          noise_scale=ns, length_scale=ls, seed=seed)
+                                          noise_scale=ns, length_scale=ls, seed=seed, **more)
         cur = torch.cuda.current_stream(dev)
         cur.wait_stream(s.stream)
         for grp in self._eager:                                                        # allocated on s.stream, used on the caller's
@@ -99,12 +116,12 @@ class SynthesisHandle:
 
     def _from_saved(self):
         """the outputs that were moved aside: the caller's stream waits for that copy and is registered as a user of its memory"""
-        mel, aux, ev = self._saved
+        mel, aux, ev, pros = self._saved
         cur = torch.cuda.current_stream(self._synth.device)
         cur.wait_event(ev)
-        for t in [mel] + list((aux or {}).values()):
+        for t in [mel] + list((aux or {}).values()) + [t for t in (pros or ()) if t is not None]:
             t.record_stream(cur)
-        return mel, aux
+        return mel, aux, pros
 
     def mel(self, clone=False, fallback=True):
         """[B, C, max(lengths)] fp32 — max(lengths) rounded down to even, as infer returns it: the squeeze drops an odd trailing frame —
@@ -128,6 +145,22 @@ class SynthesisHandle:
         cur.wait_stream(s.stream)
         out.record_stream(cur)
         return out
+
+    def prosody(self, fallback=True):
+        """(pitch, energy): [B, max(lengths)] fp32 each, zero past every utterance's length, scaled by pitch_scale / energy_scale — what
+        infer returns as its last group (None for a predictor the model does not have).  Views of static buffers under the same
+        stream-order rules as mel(); they are copied aside together with it."""
+        s = self._synth
+        lens, status = self._wait()
+        if status != 0:
+            return tuple(self._fallback(fallback)[3])
+        if self._saved is not None:
+            src = self._from_saved()[2]
+        else:
+            src = (s.pitch_static, s.energy_static)
+            s._handed.add(torch.cuda.current_stream(s.device))
+        Ty = max(lens)
+        return tuple(None if t is None else t[:, :Ty] for t in src)
 
     def aux(self, fallback=True):
         """aux=True: dict(z_m, z_logs [B, C, Ty], attn [B, 1, Tx, Ty], logw, logw_ [B, 1, Tx]) as infer returns them (views, valid until
@@ -154,14 +187,20 @@ class Synthesizer:
     overflows (calls whose lengths did not fit; a call is counted when its status is read — by its handle, or when its ring slot is
     taken again), mel_static / aux_static (the graph's outputs), stream (its own), captured_entries (C-ABI launches inside the graph).
     Any number of calls may be in flight: the RING-th call after an unread one first reads that one's lengths and status into its
-    handle (which waits for it), so a handle read late still returns its own call's."""
+    handle (which waits for it), so a handle read late still returns its own call's.
+    stochastic=True adds: max_frame_rows, rcf (the capacity context of the frame-rate rows; None for a model without
+    pitch / energy predictors), pitch_static / energy_static [batch, max_frames], and status bit 2."""
 
     RING = 8
 
-    def __init__(self, gen, batch, max_tokens, max_frames, max_rows=None, aux=False):
-        if gen.use_sdp or gen.use_spp or gen.use_sep or gen.use_emo_embeds:
+    def __init__(self, gen, batch, max_tokens, max_frames, max_rows=None, aux=False, stochastic=False, max_frame_rows=None):
+        self.stochastic = bool(stochastic)
+        if not self.stochastic and (gen.use_sdp or gen.use_spp or gen.use_sep or gen.use_emo_embeds):
             raise NotImplementedError("compile_synthesis covers the deterministic duration predictor with optional speaker / language "
-                                      "vectors; stochastic predictors and emotion inputs (cfg 5) are not captured")
+                                      "vectors; stochastic predictors and emotion inputs (cfg 5) are captured with stochastic=True")
+        if self.stochastic and gen.noise_key != "frame":
+            raise RuntimeError('compile_synthesis(stochastic=True) needs set_synthesis_front(noise_key="frame") in effect: a capture at '
+                               "capacity sizes can only reproduce noise that does not depend on the rows layout")
         if not (gen.synthesis_front and gen.decoder.fused_reverse and gen.decoder._inv_cache is not None):
             raise RuntimeError("compile_synthesis needs store_inverse(fused_reverse=True, device_front=True) in effect")
         if gen.n_sqz != 2:
@@ -176,6 +215,15 @@ class Synthesizer:
         if self.max_rows % 8:
             # the kernels state no granularity of R; ragged contexts exist, and are tested, with R rounded to 8 and above
             raise ValueError("compile_synthesis: max_rows must be a multiple of 8")
+        self.has_prosody = bool(self.stochastic and (gen.use_spp or gen.use_sep))
+        self.max_frame_rows = None
+        if self.has_prosody:
+            self.max_frame_rows = int(max_frame_rows) if max_frame_rows is not None else \
+                default_frame_rows(batch, max_frames, gen.rows_cfg.row_round)
+            if self.max_frame_rows < 2 * HALO * batch:
+                raise ValueError("compile_synthesis: max_frame_rows leaves no room for the halos of every utterance")
+            if self.max_frame_rows % 8:
+                raise ValueError("compile_synthesis: max_frame_rows must be a multiple of 8")
         self.device = dev = next(gen.parameters()).device
         self.overflows = 0
         self._guards = []
@@ -183,9 +231,12 @@ class Synthesizer:
         # ---- static inputs: ONE buffer = ids | x_lengths | call block | g | l, uploaded with one copy
         self.g_dim = (512 if gen.use_spk_embeds else gen.gin_channels) if (gen.gin_channels or gen.use_spk_embeds) else 0
         self.takes_l = bool(gen.use_lang_embeds and gen.lin_channels)
+        self.takes_emo = bool(self.stochastic and gen.use_emo_embeds)
+        n_call = (_lib.SynthCallExt if self.stochastic else _lib.SynthCall)
         lay, off = {}, 0
-        for name, n, dt in (("ids", B * Tx, torch.int64), ("x_len", B, torch.int64), ("call", 4, torch.int32),
-                            ("g", B * self.g_dim, torch.float32), ("l", B if self.takes_l else 0, torch.int64)):
+        for name, n, dt in (("ids", B * Tx, torch.int64), ("x_len", B, torch.int64), ("call", ctypes.sizeof(n_call) // 4, torch.int32),
+                            ("g", B * self.g_dim, torch.float32), ("l", B if self.takes_l else 0, torch.int64),
+                            ("emo", B if self.takes_emo else 0, torch.int64), ("emo_cartesian", 3 * B if self.takes_emo else 0, torch.float32)):
             lay[name] = (off, n, dt)
             off += (n * torch.empty(0, dtype=dt).element_size() + 15) // 16 * 16
         self._layout, self._in_bytes = lay, off
@@ -194,6 +245,8 @@ class Synthesizer:
         self.ids, self.x_len, self.call = view("ids").view(B, Tx), view("x_len"), view("call")
         self.g = view("g").view(B, self.g_dim) if self.g_dim else None
         self.l = view("l") if self.takes_l else None
+        self.emo = view("emo") if self.takes_emo else None
+        self.emo_cartesian = view("emo_cartesian").view(B, 3) if self.takes_emo else None
         self.length_scale = self.call.view(torch.float32)[3]           # 0-dim: read by the graph's torch plumbing at replay
         # ---- static outputs
         self._back = self._static(B + 1, torch.int32)                    # y_len | status: the call's one readback
@@ -210,6 +263,15 @@ class Synthesizer:
                                    logw_=self._static(B * Tx, torch.float32).view(B, 1, Tx))
         self.rc = ops.RowsCtx.capacity(B, Ty // 2, R, dev, alloc=self._static)
         self.rc.stamps = None
+        # ---- the pitch / energy predictors: frame-rate rows at capacity, their contours, the frame -> token map between the two
+        self.rcf = self.frame2token = self.pitch_static = self.energy_static = self.psig = self.esig = None
+        if self.has_prosody:
+            self.rcf = ops.RowsCtx.capacity(B, Ty, self.max_frame_rows, dev, alloc=self._static)
+            self.frame2token = self._static(B * Ty, torch.int32).view(B, Ty)
+            if gen.use_spp:
+                self.pitch_static, self.psig = self._static(B * Ty, torch.float32).view(B, Ty), self._static(R * 2, torch.float32).view(R, 2)
+            if gen.use_sep:
+                self.energy_static, self.esig = self._static(B * Ty, torch.float32).view(B, Ty), self._static(R * 2, torch.float32).view(R, 2)
         self._ring, self._ring_i = [], 0
         self._latest = None
         self._handed = set()                                             # streams that views of the static outputs were handed out on
@@ -242,14 +304,24 @@ class Synthesizer:
         st = _lib.current_stream(self.device)
         B, Tx, Ty, C = self.batch, self.max_tokens, self.max_frames, gen.out_channels
         gen.rows_cfg.host_lengths.clear()
-        g = gen.condition(self.g, None, None) if self.g is not None else None
+        g = gen.condition(self.g, self.emo, self.emo_cartesian) if self.g is not None else None
         l = gen.emb_l(self.l).unsqueeze(-1) if self.l is not None else None
         xo, x_m, x_logs, x_mask = gen.encoder(self.ids, self.x_len, l=l, g=g, prepared=True)
         rc, xb = gen.encoder._last_rows
         pw = gen.encoder.proj_w
         dvec = pw.cond_vec(g, l)
-        runner = _DurationRunner(pw, rc, xb, False, 0, has_cond=dvec is not None)
-        (logw,), _ = runner.forward(*([dvec] if dvec is not None else []))
+
+        def keyed_noise(rcn, stream, which):
+            nz = torch.empty(rcn.R, 2, dtype=torch.float32, device=self.device)
+            _lib.check(L.gt_randn_keyed_call(_lib.ptr(nz), _lib.ptr(rcn.row0), rcn.Tp, _lib.ptr(rcn.lengths), rcn.B, rcn.R, 2,
+                                             _lib.ptr(self.call), stream, which, st), "gt_randn_keyed_call")
+            return nz
+
+        if gen.use_sdp:                                                  # only under stochastic=True (the constructor)
+            logw = rc.from_rows(pw._reverse_rows(rc, xb, dvec, keyed_noise(rc, 1, 1))[:, None].contiguous())
+        else:
+            runner = _DurationRunner(pw, rc, xb, False, 0, has_cond=dvec is not None)
+            (logw,), _ = runner.forward(*([dvec] if dvec is not None else []))
         # exp, length_scale and ceil stay in torch on [B, Tx], as in infer — length_scale is a device scalar of the call block
         dur = torch.ceil(torch.exp(logw) * x_mask * self.length_scale).squeeze(1).contiguous()
         xl = self.x_len.to(torch.int32)
@@ -259,13 +331,29 @@ class Synthesizer:
         _lib.check(L.gt_synth_geometry(_lib.ptr(self.y_len), B, Ty, rcy.R, _lib.ptr(rcy.row0), _lib.ptr(rcy.lengths), _lib.ptr(self.y_len_eff),
                                        _lib.ptr(rcy.rowbatch), _lib.ptr(rcy.rowframe), _lib.ptr(rcy.rowmask), _lib.ptr(rcy.rowutt),
                                        _lib.ptr(self.status), st), "gt_synth_geometry")
+        rcf = self.rcf
+        if rcf is not None:                                              # behind gt_synth_geometry: ORs bit 2 into the status word
+            _lib.check(L.gt_synth_frame_geometry(_lib.ptr(self.y_len_eff), B, Ty, rcf.R, _lib.ptr(rcf.row0), _lib.ptr(rcf.lengths),
+                                                 _lib.ptr(rcf.rowbatch), _lib.ptr(rcf.rowframe), _lib.ptr(rcf.rowmask), _lib.ptr(rcf.rowutt),
+                                                 _lib.ptr(self.status), st), "gt_synth_frame_geometry")
         xm = x_m.float().contiguous()
         xs = None if gen.mean_only else x_logs.float().contiguous()
         args = _lib.fill_args(_lib.SynthPriorArgs, x_m=xm, x_logs=xs, cum=self.cum, x_len=xl, y_len=self.y_len_eff, row0=rcy.row0, Tp=rcy.Tp,
-                              R=rcy.R, rows=self.rows, z_m=a.get("z_m"), z_logs=a.get("z_logs"), frame2token=None, attn=a.get("attn"),
+                              R=rcy.R, rows=self.rows, z_m=a.get("z_m"), z_logs=a.get("z_logs"), frame2token=self.frame2token, attn=a.get("attn"),
                               B=B, C=C, Tx=Tx, Ty=Ty, seed=0, noise_scale=0.0)
         _lib.check(L.gt_synth_prior_call(ctypes.byref(args), _lib.ptr(self.call), st), "gt_synth_prior_call")
-        gen.decoder.reverse_rows(rcy, self.rows, g=g, out=self.mel_static)
+        if rcf is not None:                                              # models.py:1203-1228 on the capture stream: no fork
+            xf = gen._gather_features(rc, xb, rcf, self.frame2token)
+            prow = erow = None
+            if gen.use_spp:
+                prow = gen.proj_pitch._reverse_rows(rcf, xf, gen.proj_pitch.cond_vec(g), keyed_noise(rcf, 2, 2))
+            if gen.use_sep:
+                erow = gen.proj_energy._reverse_rows(rcf, xf, gen.proj_energy.cond_vec(g), keyed_noise(rcf, 3, 3))
+            _lib.check(L.gt_synth_contours_call(_lib.ptr(prow), _lib.ptr(erow), _lib.ptr(rcf.row0), rcf.Tp, _lib.ptr(rcf.lengths), rcf.R,
+                                                _lib.ptr(rcy.row0), rcy.Tp, _lib.ptr(rcy.lengths), rcy.R, _lib.ptr(self.psig),
+                                                _lib.ptr(self.esig), _lib.ptr(self.pitch_static), _lib.ptr(self.energy_static), B, Ty,
+                                                _lib.ptr(self.call), st), "gt_synth_contours_call")
+        gen.decoder.reverse_rows(rcy, self.rows, g=g, out=self.mel_static, pitch_rows=self.psig, energy_rows=self.esig)
         if self.aux:
             a["logw"] = logw
         return xm, xs, xl, dur, logw                                     # kept: the graph replays into these
@@ -276,7 +364,10 @@ class Synthesizer:
         # warm-up inputs: a full-length text of token 1, no noise — whatever lengths come out, the kernels stay inside the capacities
         self.ids.fill_(1)
         self.x_len.fill_(self.max_tokens)
-        self.call.copy_(self._call_words(0, 0.0, 1.0).to(dev))
+        self.call.copy_(self._call_words(0, 0.0, 1.0, ext=(0.0, 0.0, 1.0, 1.0) if self.stochastic else None,
+                                         noise_scale_w=0.0 if self.stochastic else 1.0).to(dev))
+        if self.takes_emo:
+            self.g.fill_(1.0)                                            # emb_g normalises the speaker vector: not the zero vector
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             # eager, on the capture stream: one-time attribute calls, scratch growth, pointer tables built "outside graph capture"
@@ -292,8 +383,13 @@ class Synthesizer:
 
     # ---- calling ------------------------------------------------------------------------------------------------------------------
     @staticmethod
-    def _call_words(seed, noise_scale, length_scale):
-        c = _lib.SynthCall(seed=int(seed) & 0xFFFFFFFF, noise_scale=float(noise_scale), noise_scale_w=1.0, length_scale=float(length_scale))
+    def _call_words(seed, noise_scale, length_scale, ext=None, noise_scale_w=1.0):
+        """the call block as int32 words: gt_synth_call, or gt_synth_call_ext when ext = (f0_noise_scale, energy_noise_scale,
+        pitch_scale, energy_scale) is given"""
+        c = _lib.SynthCall(seed=int(seed) & 0xFFFFFFFF, noise_scale=float(noise_scale), noise_scale_w=float(noise_scale_w),
+                           length_scale=float(length_scale))
+        if ext is not None:
+            c = _lib.SynthCallExt(c, *[float(v) for v in ext])
         return torch.frombuffer(bytearray(bytes(c)), dtype=torch.int32).clone()
 
     def _slot(self):
@@ -325,9 +421,12 @@ class Synthesizer:
             h._slot = None
         slot[3] = None
 
-    def __call__(self, x, x_lengths, g=None, l=None, seed=None, noise_scale=1., length_scale=1.):
+    def __call__(self, x, x_lengths, g=None, l=None, seed=None, noise_scale=1., length_scale=1., emo=None, emo_cartesian=None,
+                 noise_scale_w=1., f0_noise_scale=1., energy_noise_scale=1., pitch_scale=1., energy_scale=1.):
         """-> SynthesisHandle.  x [batch, <= max_tokens] ids (zero-padded to max_tokens), x_lengths [batch], g / l as infer takes them;
-        host tensors are staged directly (device tensors are read back first).  Nothing is launched when the shapes do not fit."""
+        host tensors are staged directly (device tensors are read back first).  Nothing is launched when the shapes do not fit.
+        stochastic=True: emo [batch] / emo_cartesian [batch, 3] (exactly when the model has the emotion front end) and the scalars of
+        the stochastic predictors, as infer takes them; everything is validated before anything is launched."""
         B, Tx = self.batch, self.max_tokens
         if x.dim() != 2 or x.shape[0] != B or x_lengths.shape != (B,):
             raise ValueError(f"this synthesiser is compiled for a batch of {B}: got x {tuple(x.shape)}, x_lengths {tuple(x_lengths.shape)}")
@@ -341,6 +440,15 @@ class Synthesizer:
                 raise ValueError(f"g must be [{B}, {self.g_dim}], got {tuple(g.shape)}")
         if l is not None and l.shape != (B,):
             raise ValueError(f"l must be [{B}], got {tuple(l.shape)}")
+        if (emo is None) != (not self.takes_emo) or (emo_cartesian is None) != (not self.takes_emo):
+            raise ValueError("emo / emo_cartesian must be given exactly when the synthesiser was compiled with stochastic=True for a "
+                             "model with the emotion front end")
+        if emo is not None and (emo.shape != (B,) or emo_cartesian.shape != (B, 3)):
+            raise ValueError(f"emo must be [{B}] and emo_cartesian [{B}, 3], got {tuple(emo.shape)} and {tuple(emo_cartesian.shape)}")
+        ext = tuple(float(v) for v in (f0_noise_scale, energy_noise_scale, pitch_scale, energy_scale))
+        noise_scale_w = float(noise_scale_w)
+        if not self.stochastic and (noise_scale_w, *ext) != (1., 1., 1., 1., 1.):
+            raise ValueError("noise_scale_w / f0_noise_scale / energy_noise_scale / pitch_scale / energy_scale need compile_synthesis(stochastic=True)")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())      # torch's default CPU generator, as infer does
         seed = int(seed) & 0xFFFFFFFF
@@ -357,11 +465,14 @@ class Synthesizer:
         ids.zero_()
         ids[:, :x.shape[1]].copy_(x)
         put("x_len").copy_(x_lengths)
-        put("call").copy_(self._call_words(seed, noise_scale, length_scale))
+        put("call").copy_(self._call_words(seed, noise_scale, length_scale, ext=ext if self.stochastic else None, noise_scale_w=noise_scale_w))
         if g is not None:
             put("g", (B, self.g_dim)).copy_(g2)
         if l is not None:
             put("l").copy_(l)
+        if emo is not None:
+            put("emo").copy_(emo)
+            put("emo_cartesian", (B, 3)).copy_(emo_cartesian)
         prev = self._latest() if self._latest is not None else None
         if self._handed:
             # (no wait when nothing was handed out: clones are made on the synthesiser's own stream, so queued calls and callers that
@@ -374,13 +485,15 @@ class Synthesizer:
             if prev is not None and not prev._done and prev._saved is None and (prev._read is None or prev._read[1] == 0):
                 # the previous call has not been read yet: its outputs move aside, in stream order, before this call overwrites them
                 saved_ev = torch.cuda.Event()
-                prev._saved = (self.mel_static.clone(), {k: v.clone() for k, v in self.aux_static.items()} if self.aux else None, saved_ev)
+                prev._saved = (self.mel_static.clone(), {k: v.clone() for k, v in self.aux_static.items()} if self.aux else None, saved_ev,
+                               tuple(None if t is None else t.clone() for t in (self.pitch_static, self.energy_static)))
                 saved_ev.record(self.stream)
             self._in.copy_(host, non_blocking=True)
             self.graph.replay()
             back.copy_(self._back, non_blocking=True)
             ev.record(self.stream)
-        h = SynthesisHandle(self, slot, (x, x_lengths, g, l), (seed, float(noise_scale), float(length_scale)))
+        h = SynthesisHandle(self, slot, (x, x_lengths, g, l, emo, emo_cartesian),
+                            (seed, float(noise_scale), float(length_scale), noise_scale_w, *ext))
         slot[3], slot[4] = weakref.ref(h), False
         self._latest = weakref.ref(h)
         return h

@@ -462,6 +462,7 @@ class FlowGenerator(nn.Module):
             self.proj_energy = StochasticEnergyPredictor(henc, 256, 3, 0.1, 4, gin_channels=gin_channels)
         self._step = 0
         self.synthesis_front = False                                 # set_synthesis_front: infer's device front end (opt-in)
+        self.noise_key = "row"                                       # set_synthesis_front(noise_key=): how the predictors' noise is keyed
         self._front_pin = self._front_last = None
         # rows-layout state of THIS model (ragged packing, row rounding, the batch's host-side lengths): shared with the
         # encoder / decoder runners; train.Trainer configures it — nothing process-global
@@ -494,14 +495,21 @@ class FlowGenerator(nn.Module):
         emosty = self.emosty_layer_norm(F.softplus(torch.cat((emos_proj, style), dim=-1)))
         return torch.cat((g, intens + emosty), dim=-1).unsqueeze(-1)
 
-    def set_synthesis_front(self, on=True):
+    def set_synthesis_front(self, on=True, noise_key="row"):
         """Opt-in device front end of infer (csrc/synth_front.hip): gt_synth_lengths turns the durations into lengths,
         ONE device-to-host copy brings all of them back, gt_synth_prior writes the sampled, squeezed latent straight into the RAGGED rows
         layout the reverse decoder reads (padded frames then cost nothing, and the fused reverse pass unsqueezes in its last launch),
         and every draw of the call — the prior's and the stochastic predictors' — comes from a counter-hash Gaussian generator that the
-        host can restate from `infer(..., seed=)` alone.  Off (the default): infer is torch.randn and the uniform rows layout.  Returns
-        what is in effect."""
+        host can restate from `infer(..., seed=)` alone.  Off (the default): infer is torch.randn and the uniform rows layout.
+        noise_key: "row" — the stochastic predictors' draws are keyed by the row index of the rows layout in use
+        (gt_randn_rows) and the pitch / energy predictors run on uniform frame rows; "frame" — the draws are keyed by (utterance, token)
+        / (utterance, frame) (gt_randn_keyed), independent of the layout, the frame-rate rows are ragged, and the contours go into the
+        decoder's rows in one launch (gt_synth_contours).  "frame" is what compile_synthesis(stochastic=True) reproduces.  Returns
+        whether the front end is in effect."""
+        if noise_key not in ("row", "frame"):
+            raise ValueError('set_synthesis_front: noise_key is "row" or "frame"')
         self.synthesis_front = bool(on)
+        self.noise_key = noise_key
         return self.synthesis_front
 
     def store_inverse(self, fused_reverse=None, device_front=None):
@@ -516,7 +524,7 @@ class FlowGenerator(nn.Module):
             return self.decoder.fused_reverse
         return self.decoder.fused_reverse, self.set_synthesis_front(device_front)
 
-    def compile_synthesis(self, batch, max_tokens, max_frames, max_rows=None, aux=False):
+    def compile_synthesis(self, batch, max_tokens, max_frames, max_rows=None, aux=False, stochastic=False, max_frame_rows=None):
         """Synthesis as ONE captured graph (glow-tts_amd/synthesis.py) -> synthesis.Synthesizer.  Needs
         store_inverse(fused_reverse=True, device_front=True) in effect.  The sizes are capacities, fixed here: a batch of exactly `batch`
         texts of up to max_tokens tokens, up to max_frames (even) mel frames per utterance and max_rows rows of the squeezed mel axis
@@ -526,9 +534,16 @@ class FlowGenerator(nn.Module):
         back.  The mel is bit-identical to infer(seed=)'s on the same rows.  A call whose predicted lengths do not fit the capacities is
         re-run through infer (synth.overflows counts them; `mel(fallback=False)` raises synthesis.SynthesisOverflow instead).
         aux=True also keeps z_m, z_logs, attn, logw, logw_ (h.aux()).  Covered: the deterministic duration predictor, with the optional
-        speaker vector g and language id l; use_sdp / use_spp / use_sep or emotion inputs raise NotImplementedError."""
+        speaker vector g and language id l; use_sdp / use_spp / use_sep or emotion inputs raise NotImplementedError unless
+        stochastic=True: the full model — the stochastic duration predictor in reverse, the stochastic pitch / energy
+        predictors at the frame rate, the emotion front end — in the same one graph, on one stream.  It needs
+        set_synthesis_front(noise_key="frame") in effect (RuntimeError otherwise), and reproduces infer(seed=) under that keying.
+        max_frame_rows: rows of the un-squeezed mel axis the pitch / energy predictors run on (default: `batch` utterances of
+        max_frames frames, rounded to rows_cfg.row_round; a multiple of 8).  The call then also takes emo=, emo_cartesian=,
+        noise_scale_w=, f0_noise_scale=, energy_noise_scale=, pitch_scale=, energy_scale=, and `h.prosody()` returns (pitch, energy)."""
         from .synthesis import Synthesizer
-        return Synthesizer(self, batch, max_tokens, max_frames, max_rows=max_rows, aux=aux)
+        return Synthesizer(self, batch, max_tokens, max_frames, max_rows=max_rows, aux=aux, stochastic=stochastic,
+                           max_frame_rows=max_frame_rows)
 
     @torch.no_grad()
     def infer(self, x, x_lengths, y=None, y_lengths=None, g=None, emo=None, emo_cartesian=None, l=None, gst_token=None,
@@ -618,9 +633,15 @@ class FlowGenerator(nn.Module):
         L = _lib.lib()
         st = _lib.current_stream(dev)
 
-        def randn_rows(R, stream, scale):
-            nz = torch.empty(R, 2, dtype=torch.float32, device=dev)
-            _lib.check(L.gt_randn_rows(_lib.ptr(nz), R, 2, seed, stream, float(scale), st), "gt_randn_rows")
+        keyed = self.noise_key == "frame"
+
+        def randn_rows(rcn, stream, scale):
+            nz = torch.empty(rcn.R, 2, dtype=torch.float32, device=dev)
+            if keyed:                                                        # (utterance, token / frame): independent of the layout
+                _lib.check(L.gt_randn_keyed(_lib.ptr(nz), _lib.ptr(rcn.row0), rcn.Tp, _lib.ptr(rcn.lengths), rcn.B, rcn.R, 2, seed, stream,
+                                            float(scale), st), "gt_randn_keyed")
+            else:
+                _lib.check(L.gt_randn_rows(_lib.ptr(nz), rcn.R, 2, seed, stream, float(scale), st), "gt_randn_rows")
             return nz
 
         g = self.condition(g, emo, emo_cartesian)
@@ -631,7 +652,7 @@ class FlowGenerator(nn.Module):
         pw = self.encoder.proj_w
         dvec = pw.cond_vec(g, l)
         if self.use_sdp:
-            logw = rc.from_rows(pw._reverse_rows(rc, xb, dvec, randn_rows(rc.R, 1, noise_scale_w))[:, None].contiguous())
+            logw = rc.from_rows(pw._reverse_rows(rc, xb, dvec, randn_rows(rc, 1, noise_scale_w))[:, None].contiguous())
         else:
             runner = _DurationRunner(pw, rc, xb, False, 0, has_cond=dvec is not None)
             (logw,), _ = runner.forward(*([dvec] if dvec is not None else []))
@@ -667,22 +688,44 @@ class FlowGenerator(nn.Module):
                               seed=seed, noise_scale=float(noise_scale))
         _lib.check(L.gt_synth_prior(ctypes.byref(args), st), "gt_synth_prior")
         z_mask = ops.length_mask(y_len, Ty).to(x_mask.dtype)
-        pitch = energy = None
-        if self.use_spp or self.use_sep:                              # models.py:1203-1228, at the frame rate (uniform rows)
+        pitch = energy = psig = esig = rcf = None
+        if (self.use_spp or self.use_sep) and keyed:                  # models.py:1203-1228, at the frame rate on RAGGED rows
+            rcf = ops.RowsCtx(y_len, Ty, lengths_host=lens, round_to=self.rows_cfg.row_round) if self.rows_cfg.frame_rows_ragged \
+                else ops.RowsCtx(y_len, Ty)
+            xf = self._gather_features(rc, xb, rcf, frame2token)
+            prow = erow = None
+            if self.use_spp:
+                prow = self.proj_pitch._reverse_rows(rcf, xf, self.proj_pitch.cond_vec(g), randn_rows(rcf, 2, f0_noise_scale))
+                pitch = torch.empty(B, Ty, dtype=torch.float32, device=dev)
+                psig = torch.empty(rcy.R, 2, dtype=torch.float32, device=dev)
+            if self.use_sep:
+                erow = self.proj_energy._reverse_rows(rcf, xf, self.proj_energy.cond_vec(g), randn_rows(rcf, 3, energy_noise_scale))
+                energy = torch.empty(B, Ty, dtype=torch.float32, device=dev)
+                esig = torch.empty(rcy.R, 2, dtype=torch.float32, device=dev)
+            # the contours for the return tuple and, squeezed, on the decoder's rows: one launch
+            _lib.check(L.gt_synth_contours(_lib.ptr(prow), _lib.ptr(erow), _lib.ptr(rcf.row0), rcf.Tp, _lib.ptr(rcf.lengths), rcf.R,
+                                           _lib.ptr(rcy.row0), rcy.Tp, _lib.ptr(rcy.lengths), rcy.R, _lib.ptr(psig), _lib.ptr(esig),
+                                           _lib.ptr(pitch), _lib.ptr(energy), B, Ty, float(pitch_scale), float(energy_scale), st),
+                       "gt_synth_contours")
+        elif self.use_spp or self.use_sep:                            # models.py:1203-1228, at the frame rate (uniform rows)
             rcf = ops.RowsCtx(y_len, Ty)
             xf = self._gather_features(rc, xb, rcf, frame2token)      # frames no token owns (-1) are masked rows: not read
             if self.use_spp:
-                nz = randn_rows(rcf.R, 2, f0_noise_scale)
+                nz = randn_rows(rcf, 2, f0_noise_scale)
                 pitch = rcf.from_rows(self.proj_pitch._reverse_rows(rcf, xf, self.proj_pitch.cond_vec(g), nz)[:, None].contiguous()).squeeze(1) * pitch_scale
             if self.use_sep:
-                nz = randn_rows(rcf.R, 3, energy_noise_scale)
+                nz = randn_rows(rcf, 3, energy_noise_scale)
                 energy = rcf.from_rows(self.proj_energy._reverse_rows(rcf, xf, self.proj_energy.cond_vec(g), nz)[:, None].contiguous()).squeeze(1) * energy_scale
         if T2 == 0:                                                   # no utterance has two frames: nothing to decode
             yo = torch.zeros(B, C, 0, dtype=x_m.dtype, device=dev)
         else:
-            yo = self.decoder.reverse_rows(rcy, rows, g=g, pitch=pitch, energy=energy).to(x_m.dtype)
-        # what the last call put in front of the decoder (tests, tools): rows context, sampled latent rows, frame -> token map
-        self._front_last = dict(rc=rcy, rows=rows, frame2token=frame2token, seed=seed)
+            if keyed:
+                yo = self.decoder.reverse_rows(rcy, rows, g=g, pitch_rows=psig, energy_rows=esig).to(x_m.dtype)
+            else:
+                yo = self.decoder.reverse_rows(rcy, rows, g=g, pitch=pitch, energy=energy).to(x_m.dtype)
+        # what the last call put in front of the decoder (tests, tools): rows context, sampled latent rows, frame -> token map, and
+        # the frame-rate rows context of the pitch / energy predictors (None without them)
+        self._front_last = dict(rc=rcy, rows=rows, frame2token=frame2token, seed=seed, rc_frames=rcf)
         return (yo, z_m, z_logs, None, z_mask), (x_m, x_logs, x_mask), (attn.to(x_mask.dtype), logw, logw_), (pitch, energy)
 
     @staticmethod

@@ -786,6 +786,54 @@ int gt_synth_geometry(const int32_t* y_len, int B, int Ty_cap, int R_cap, int32_
 int gt_synth_prior_call(const gt_synth_prior_args* args, const gt_synth_call* call, void* stream);
 int gt_randn_rows_call(float* out, int R, int ncol, const gt_synth_call* call, uint32_t stream_id, int which_scale, void* stream);
 
+/* ---- Full-model synthesis: stochastic duration / pitch / energy predictors (csrc/synth_prosody.hip, csrc/synth_front.hip; DESIGN
+ * 4.14).  Vector stores only, no atomics, one writer per element.
+ *
+ * gt_randn_keyed: the predictors' noise keyed by (utterance, token or frame) instead of by row index, so a draw does not depend on
+ *   the rows layout.  Row r of out [R, ncol] fp32 belongs to utterance b and frame t = r - row0[b] - GT_HALO of the rows layout given
+ *   as row0 (int32 [B + 1]; NULL = uniform rows, R == B * Tp) and Tp, as gt_synth_prior takes it:
+ *     out[r, col] = scale * (e0 | e1 by the parity of col) of (seed, stream_id, b, s = t, c = col / 2)   for 0 <= t < lengths[b]
+ *   and 0 on every other row (halo, padding, rounding): EVERY one of the R rows is written, the `* rowmask` is folded in.
+ *   R < 0, B < 0, ncol <= 0: GT_E_INVAL;  R == 0: 0;  out / lengths NULL, B == 0, uniform rows with R != B * Tp: GT_E_INVAL;
+ *   pointers not 4-byte aligned: GT_E_ALIGN;  R * ceil(ncol / 2) > 2^31 - 1: GT_E_UNSUPPORTED.
+ * gt_synth_call_ext: gt_synth_call followed by the four scalars of the pitch / energy predictors, in DEVICE memory.  Its first 16
+ *   bytes ARE a gt_synth_call: gt_synth_prior_call / gt_randn_rows_call take the same pointer.
+ * gt_randn_keyed_call: gt_randn_keyed — the same kernel code, bit-identical output — with seed and the scale from *call
+ *   (which_scale: 0 = noise_scale, 1 = noise_scale_w, 2 = f0_noise_scale, 3 = energy_noise_scale; anything else GT_E_INVAL;
+ *   call == NULL: GT_E_INVAL behind the R == 0 return; not 4-byte aligned: GT_E_ALIGN).
+ *
+ * gt_synth_frame_geometry: the ragged rows context of the UN-squeezed mel axis (the frame rate the pitch / energy predictors run at)
+ *   at capacity Rf_cap, from gt_synth_geometry's y_len_eff (<= Ty_cap): exactly RowsCtx.row_starts(y_len_eff, T = Ty_cap) with
+ *   starts[B] = Rf_cap, followed by gt_rows_ctx_fill:  len_f[b] = min(y_len_eff[b], Ty_cap),  row0_f[b + 1] = row0_f[b] + len_f[b] +
+ *   2 GT_HALO,  row0_f[B] = Rf_cap,  rowbatch / rowframe / rowmask / rowutt (optional) [Rf_cap].  Launched BEHIND gt_synth_geometry on
+ *   the same stream: when the frame rows do not fit Rf_cap one thread ORs bit 2 (value 4) into *status, and gt_synth_geometry's
+ *   overflow rule holds on whole frames — every utterance keeps its halos, len_f[b] is cut to what fits in front of the halos of
+ *   the utterances behind it, row0_f[b] = min(unclipped row0_f[b], Rf_cap - 2 GT_HALO (B - b)), row0_f is monotone, all Rf_cap table
+ *   entries are written.  Argument checks as gt_synth_geometry (Ty_cap may be odd); Rf_cap < 2 GT_HALO B: GT_E_INVAL.
+ *
+ * gt_synth_contours: the predictors' outputs on the frame-rate rows (pitch_rows / energy_rows [Rf] fp32, either may be NULL) ->
+ *   pitch / energy [B, Ty] fp32 = rows[row of frame t] * scale for t < len_f[b], 0 behind it (the return tuple's contours), and
+ *   psig / esig [R, 2] fp32 = the squeezed contour rows the reverse decoder's prosody WaveNets read: sig[r, j] = contour[b, 2 s + j]
+ *   for the row r of squeezed frame s < min(len_sq[b], Ty / 2), 0 on every other row; all R rows are written.  One launch for what
+ *   was from_rows -> * scale -> reshape -> gt_squeeze_rows_f32 per contour, bit-identical to it.  Both rows layouts are given as
+ *   (row0, Tp) with row0 == NULL = uniform.  An output whose pointer is NULL is not written; an output whose input is NULL is zero.
+ *   B == 0: 0;  len_f / len_sq NULL, a uniform layout whose B * Tp differs from its row count: GT_E_INVAL;  pointers not 4-byte
+ *   (psig / esig: 8-byte) aligned: GT_E_ALIGN.  gt_synth_contours_call: the same kernel code with pitch_scale / energy_scale from *call. */
+typedef struct gt_synth_call_ext { gt_synth_call base; float f0_noise_scale; float energy_noise_scale; float pitch_scale; float energy_scale; } gt_synth_call_ext;
+int gt_synth_call_ext_size(void);               /* sizeof(gt_synth_call_ext) = 32 */
+int gt_randn_keyed(float* out, const int32_t* row0, int Tp, const int32_t* lengths, int B, int R, int ncol, uint32_t seed,
+                   uint32_t stream_id, float scale, void* stream);
+int gt_randn_keyed_call(float* out, const int32_t* row0, int Tp, const int32_t* lengths, int B, int R, int ncol,
+                        const gt_synth_call_ext* call, uint32_t stream_id, int which_scale, void* stream);
+int gt_synth_frame_geometry(const int32_t* y_len_eff, int B, int Ty_cap, int Rf_cap, int32_t* row0_f, int32_t* len_f, int64_t* rowbatch,
+                            int32_t* rowframe, float* rowmask, int32_t* rowutt, int32_t* status, void* stream);
+int gt_synth_contours(const float* pitch_rows, const float* energy_rows, const int32_t* row0_f, int Tp_f, const int32_t* len_f, int Rf,
+                      const int32_t* row0, int Tp, const int32_t* len_sq, int R, float* psig, float* esig, float* pitch, float* energy,
+                      int B, int Ty, float pitch_scale, float energy_scale, void* stream);
+int gt_synth_contours_call(const float* pitch_rows, const float* energy_rows, const int32_t* row0_f, int Tp_f, const int32_t* len_f,
+                           int Rf, const int32_t* row0, int Tp, const int32_t* len_sq, int R, float* psig, float* esig, float* pitch,
+                           float* energy, int B, int Ty, const gt_synth_call_ext* call, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

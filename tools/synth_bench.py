@@ -25,6 +25,16 @@ same model and the same two shapes as --infer; the batch is compiled at its own 
 at 160 tokens and 800 frames and, to show what unused capacity costs, at 1600 frames.  Every repeat is recorded; output defaults to
 profiles/synth_graph_bench.json.
 
+--cfg5 [--graph]: the FULL model (tests/test_synthesis_fused_gpu.py's CFG5: emotion front end, stochastic duration predictor in
+reverse, stochastic pitch / energy predictors at the frame rate, 10 encoder layers, 12 decoder blocks), whole infer calls on the same
+two shapes with the same windows and repeats, the variants alternating in one process.  The stochastic duration predictor keeps all
+its work but its last flow (the elementwise affine, log_scale = 20) maps every draw to log w = 0, so with length_scale = 4.9 every
+token gets 5 frames.  Variants: eager with noise_key="row" (the path before DESIGN.md 4.14: row-keyed noise, uniform frame rows, four
+launches per contour), eager with noise_key="frame" on uniform frame rows (rows_cfg.frame_rows_ragged = False) and on ragged ones
+(the default), and with --graph the captured graph of compile_synthesis(stochastic=True) replayed call by call.  Three ratios per
+shape: replay over eager-frame, eager-frame over eager-row, ragged over uniform frame rows.  Every repeat is recorded; output defaults
+to profiles/synth_graph_cfg5_bench.json.
+
 Kernel times come from separate runs, one per shape, under
 `rocprofv3 --kernel-trace --stats -- python tools/synth_bench.py --seconds 0.1 --repeats 1 --shape batch` (or `single`)."""
 import argparse
@@ -42,6 +52,7 @@ ap.add_argument("--seconds", type=float, default=0.5)
 ap.add_argument("--repeats", type=int, default=2)
 ap.add_argument("--infer", action="store_true", help="time whole infer calls, device front end off / on")
 ap.add_argument("--graph", action="store_true", help="time eager infer against the captured synthesis graph (compile_synthesis)")
+ap.add_argument("--cfg5", action="store_true", help="the full cfg 5 model: eager row / frame keyed calls (and with --graph the captured graph)")
 ap.add_argument("--queue", type=int, default=16, help="--graph: replays queued before one synchronisation")
 ap.add_argument("--shape", choices=["both", "batch", "single"], default="both", help="one shape only (a kernel-trace run per shape)")
 opt = ap.parse_args()
@@ -49,7 +60,7 @@ opt = ap.parse_args()
 dev = torch.device("cuda:0")
 NB, NL, H, C = 12, 4, 192, 160
 torch.manual_seed(0)
-if not opt.infer and not opt.graph:
+if not opt.infer and not opt.graph and not opt.cfg5:
     dec = models.FlowSpecDecoder(80, H, 5, 1, NB, NL, p_dropout=0.05).to(dev).eval()
     for b in range(NB):                                                # a coupling that does something (end is zero-initialised)
         torch.nn.init.normal_(dec.flows[3 * b + 2].end.weight, std=0.01)
@@ -324,4 +335,111 @@ def graph_main():
         f.write("\n")
 
 
-graph_main() if opt.graph else infer_main() if opt.infer else main()
+def cfg5_main():
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tests"))
+    sys.path.insert(0, os.path.join(root, "tests", "golden"))
+    from test_synthesis_fused_gpu import CFG5
+    gen = models.FlowGenerator(n_vocab=187, out_channels=80, n_lang=10, **CFG5).eval()
+    with torch.no_grad():
+        for b in range(CFG5["n_blocks_dec"]):
+            torch.nn.init.normal_(gen.decoder.flows[3 * b + 2].end.weight, std=0.01)
+        ea = gen.encoder.proj_w.flows[0]                               # log w = (z - translation) * exp(-log_scale) ~ 0: 5 frames per token
+        ea.log_scale.fill_(20.0)
+        ea.translation.zero_()
+    gen = gen.to(dev)
+    assert gen.store_inverse(fused_reverse=True, device_front=True) == (True, True)
+    ids_b, t_x, _, _ = train.synth_batch(32, 150, 800, 0, "cpu")
+    g = torch.Generator().manual_seed(5)
+    one = torch.randint(1, 148, (1, 160), generator=g)
+    cases = []
+    if opt.shape != "single":
+        cases.append(("bench batch: B = 32, T_x <= 150, 5 frames per token", ids_b, t_x))
+    if opt.shape != "batch":
+        cases.append(("one utterance, 160 tokens = 800 frames", one, torch.tensor([160])))
+    scal = dict(noise_scale=0.667, noise_scale_w=0.8, f0_noise_scale=0.8, energy_noise_scale=0.8, length_scale=4.9, pitch_scale=1.1,
+                energy_scale=0.9)
+    out = dict(device=torch.cuda.get_device_name(0), model="cfg 5: emotion front end, SDP (last flow pinned: 5 frames per token), SPP, SEP, "
+               "10 encoder layers, 12 blocks x 4 layers, H = 192, eval, store_inverse(fused_reverse=True, device_front=True)",
+               seconds_per_variant=opt.seconds, call=scal, shapes=[])
+    for name, ids, xl in cases:
+        B, Tx = int(ids.shape[0]), int(ids.shape[1])
+        cond = dict(g=torch.randn(B, 512, generator=g), emo=torch.randint(0, 5, (B,), generator=g),
+                    emo_cartesian=torch.rand(B, 3, generator=g) * torch.tensor([1.5, 3.1, 4.6]) + torch.tensor([0.0, 0.0, -1.55]),
+                    l=torch.randint(0, 3, (B,), generator=g))
+        ids_d, xl_d, cond_d = ids.to(dev), xl.to(dev), {k: v.to(dev) for k, v in cond.items()}
+
+        def eager(n, key, ragged=True):
+            gen.set_synthesis_front(True, noise_key=key)
+            gen.rows_cfg.frame_rows_ragged = ragged
+            for _ in range(n):
+                res = gen.infer(ids_d, xl_d, seed=7, **cond_d, **scal)      # synchronises inside: its one readback
+            gen.rows_cfg.frame_rows_ragged = True
+            return res
+
+        runs = {"eager_row": lambda n: eager(n, "row"), "eager_frame_uniform": lambda n: eager(n, "frame", False),
+                "eager_frame": lambda n: eager(n, "frame")}
+        rec = dict(name=name, B=B, Tx=Tx, variants={})
+        for k, fn in runs.items():
+            res = fn(3)
+            with _lib.record_calls() as names:
+                res = fn(1)
+            torch.cuda.synchronize()
+            assert torch.isfinite(res[0][0]).all() and torch.isfinite(res[3][0]).all()
+            rec["T_y"] = int(res[0][0].shape[2])
+            rec["variants"][k] = dict(c_abi_entries_per_call=len(names), ms_per_call=[])
+            if k == "eager_frame":
+                want, frame_rows = res, gen._front_last["rc_frames"].R
+        rec["frame_rows_ragged"] = frame_rows
+        rec["frame_rows_uniform"] = B * (int(want[3][0].shape[1]) + 2 * ops.HALO)
+        if opt.graph:
+            gen.set_synthesis_front(True, noise_key="frame")
+            rcy = gen._front_last["rc"]
+            # the default capacities (`batch` utterances of max_frames frames each) and, where that differs, the rows this batch needs
+            caps = [("replay", None, None)] + ([("replay_fit", rcy.R, frame_rows)] if B > 1 else [])
+            for tag, max_rows, max_frame_rows in caps:
+                synth = gen.compile_synthesis(B, Tx, 5 * Tx, max_rows=max_rows, stochastic=True, max_frame_rows=max_frame_rows)
+
+                def replay(n, synth=synth):
+                    for _ in range(n):
+                        h = synth(ids, xl, seed=7, **cond, **scal)
+                        y = h.mel()                                         # waits for this call's readback
+                    return h, y
+
+                h, y = replay(3)
+                pitch, energy = h.prosody()
+                rec["variants"][tag] = dict(max_tokens=Tx, max_frames=5 * Tx, max_rows=synth.max_rows, max_frame_rows=synth.max_frame_rows,
+                                            launches_per_call="1 upload + 1 graph replay + 1 readback",
+                                            c_abi_entries_inside_the_graph=synth.captured_entries, status=h.status, overflows=synth.overflows,
+                                            max_abs_difference_to_eager=dict(mel=(y - want[0][0]).abs().max().item(),
+                                                                             pitch=(pitch - want[3][0]).abs().max().item(),
+                                                                             energy=(energy - want[3][1]).abs().max().item()),
+                                            ms_per_call=[])
+                runs[tag] = replay
+        for rep_i in range(opt.repeats):
+            for k, fn in runs.items():
+                torch.cuda.synchronize(); t0 = time.perf_counter(); fn(3); torch.cuda.synchronize()
+                n = max(3, int(opt.seconds / ((time.perf_counter() - t0) / 3)) + 1)
+                torch.cuda.synchronize(); t0 = time.perf_counter(); fn(n); torch.cuda.synchronize()
+                rec["variants"][k]["ms_per_call"].append(round((time.perf_counter() - t0) * 1e3 / n, 4))
+        for v in rec["variants"].values():
+            t = v["ms_per_call"]
+            v["ms_mean"], v["ms_spread"] = round(sum(t) / len(t), 4), round(max(t) - min(t), 4)
+        ms = {k: v["ms_mean"] for k, v in rec["variants"].items()}
+        rec["eager_frame_over_eager_row_time"] = round(ms["eager_frame"] / ms["eager_row"], 4)
+        rec["ragged_over_uniform_frame_rows_time"] = round(ms["eager_frame"] / ms["eager_frame_uniform"], 4)
+        for tag in ("replay", "replay_fit"):
+            if tag in ms:
+                rec[tag + "_over_eager_frame_time"] = round(ms[tag] / ms["eager_frame"], 4)
+        print(f'{name}: T_y {rec["T_y"]}; ' + "; ".join(f'{k} {v["ms_mean"]:.3f} ms (+- {v["ms_spread"]:.3f})' for k, v in rec["variants"].items()), flush=True)
+        out["shapes"].append(rec)
+    gen.set_synthesis_front(True, noise_key="row")
+    path = opt.json or os.path.join(root, "profiles", "synth_graph_cfg5_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
+cfg5_main() if opt.cfg5 else graph_main() if opt.graph else infer_main() if opt.infer else main()
