@@ -16,6 +16,7 @@ built on the device by gt_synth_frame_geometry — with noise keyed by (utteranc
 scalars in a gt_synth_call_ext block, and the contours written into the decoder's rows by gt_synth_contours_call.  One stream, no fork."""
 import ctypes
 import weakref
+from typing import NamedTuple
 
 import torch
 
@@ -46,6 +47,146 @@ def default_rows(batch, max_frames, row_round):
     """rows of `batch` utterances of max_frames frames on the squeezed axis, rounded up to row_round"""
     need = batch * (max_frames // 2 + 2 * HALO)
     return -(-need // row_round) * row_round
+
+
+# ---- the call: ONE pipeline for infer (device front end off / on) and the captured graph --------------------------------------------------
+class CallScalars(NamedTuple):
+    """the scalars of one synthesis call, in the field order of gt_synth_call_ext and under infer's keyword names"""
+    seed: int
+    noise_scale: float = 1.
+    noise_scale_w: float = 1.
+    length_scale: float = 1.
+    f0_noise_scale: float = 1.
+    energy_noise_scale: float = 1.
+    pitch_scale: float = 1.
+    energy_scale: float = 1.
+
+    def words(self, ext):
+        """the call block as int32 words: gt_synth_call, or (ext) gt_synth_call_ext, whose first 16 bytes are the gt_synth_call"""
+        c = _lib.SynthCall(int(self.seed) & 0xFFFFFFFF, *[float(v) for v in self[1:4]])
+        if ext:
+            c = _lib.SynthCallExt(c, *[float(v) for v in self[4:]])
+        return torch.frombuffer(bytearray(bytes(c)), dtype=torch.int32).clone()
+
+
+def _launch(device, name, *args):
+    """the C-ABI entry `name` on the current stream of device"""
+    _lib.check(getattr(_lib.lib(), name)(*args, _lib.current_stream(device)), name)
+
+
+class ByValue:
+    """The scalar source of the eager path: a CallScalars, handed to the kernels by value.  keyed: the predictors' draws are keyed by
+    (utterance, token / frame), independent of the layout (gt_randn_keyed: what FromBlock reproduces), else by the row (gt_randn_rows).
+    noise -> [rc.R, 2] draws of the generator's stream stream_id times scale `which` (1 noise_scale_w, 2 f0_, 3 energy_noise_scale);
+    prior / contours launch gt_synth_prior / gt_synth_contours on the arguments every source shares."""
+
+    def __init__(self, scalars, keyed, device):
+        self.scalars, self.keyed, self.device, self.length_scale = scalars, keyed, device, scalars.length_scale
+
+    def noise(self, rc, stream_id, which):
+        s, p = self.scalars, _lib.ptr
+        nz = torch.empty(rc.R, 2, dtype=torch.float32, device=self.device)
+        scale = float((s.noise_scale, s.noise_scale_w, s.f0_noise_scale, s.energy_noise_scale)[which])
+        if self.keyed:
+            _launch(self.device, "gt_randn_keyed", p(nz), p(rc.row0), rc.Tp, p(rc.lengths), rc.B, rc.R, 2, s.seed, stream_id, scale)
+        else:
+            _launch(self.device, "gt_randn_rows", p(nz), rc.R, 2, s.seed, stream_id, scale)
+        return nz
+
+    def prior(self, args):
+        args.seed, args.noise_scale = self.scalars.seed, float(self.scalars.noise_scale)
+        _launch(self.device, "gt_synth_prior", ctypes.byref(args))
+
+    def contours(self, *args):
+        _launch(self.device, "gt_synth_contours", *args, float(self.scalars.pitch_scale), float(self.scalars.energy_scale))
+
+
+class FromBlock:
+    """The scalar source of a captured graph: the gt_synth_call[_ext] block in device memory, read by the *_call entries at every
+    replay; length_scale is a 0-dim view of it, read by the graph's torch plumbing."""
+    keyed = True
+
+    def __init__(self, call):
+        self.call, self.device, self.length_scale = call, call.device, call.view(torch.float32)[3]
+
+    def noise(self, rc, stream_id, which):
+        p = _lib.ptr
+        nz = torch.empty(rc.R, 2, dtype=torch.float32, device=self.device)
+        _launch(self.device, "gt_randn_keyed_call", p(nz), p(rc.row0), rc.Tp, p(rc.lengths), rc.B, rc.R, 2, p(self.call), stream_id, which)
+        return nz
+
+    def prior(self, args):
+        _launch(self.device, "gt_synth_prior_call", ctypes.byref(args), _lib.ptr(self.call))
+
+    def contours(self, *args):
+        _launch(self.device, "gt_synth_contours_call", *args, _lib.ptr(self.call))
+
+
+def text_stage(gen, ids, x_len, g, l, emo, emo_cartesian, draw):
+    """conditioning -> text encoder -> duration predictor (the stochastic one in reverse on the noise draw(rc) [rc.R, 2], or the
+    deterministic one) -> g, l, x_m, x_logs, x_mask, the text rows (rc, xb), logw [B, 1, Tx]"""
+    from .text_models import _DurationRunner
+    g = gen.condition(g, emo, emo_cartesian)
+    if l is not None:
+        l = gen.emb_l(l).unsqueeze(-1)
+    xo, x_m, x_logs, x_mask = gen.encoder(ids, x_len, l=l, g=g, prepared=True)
+    rc, xb = gen.encoder._last_rows
+    pw = gen.encoder.proj_w
+    dvec = pw.cond_vec(g, l)
+    if gen.use_sdp:
+        logw = rc.from_rows(pw._reverse_rows(rc, xb, dvec, draw(rc))[:, None].contiguous())
+    else:
+        runner = _DurationRunner(pw, rc, xb, False, 0, has_cond=dvec is not None)
+        (logw,), _ = runner.forward(*([dvec] if dvec is not None else []))
+    return g, l, x_m, x_logs, x_mask, rc, xb, logw
+
+
+def lengths_stage(logw, x_mask, length_scale, x_len, cum, y_len, logw_):
+    """durations -> gt_synth_lengths into the caller's cum [B, Tx], y_len [B] and (or None) logw_ [B, 1, Tx] -> dur, x_len as int32.
+    exp, length_scale (a float, or a 0-dim device tensor) and ceil stay in torch on [B, Tx] (plumbing): the durations are bit for bit
+    those of infer without the front end"""
+    p = _lib.ptr
+    dur = torch.ceil(torch.exp(logw) * x_mask * length_scale).squeeze(1).contiguous()
+    xl = x_len.to(torch.int32).contiguous()
+    _launch(dur.device, "gt_synth_lengths", p(dur), p(xl), p(cum), p(y_len), p(logw_), *dur.shape)
+    return dur, xl
+
+
+def prior_stage(gen, x_m, x_logs, cum, xl, y_len, rcy, bufs, source, Ty):
+    """the sampled, squeezed latent into bufs["rows"] on the rows of rcy; z_m, z_logs [B, C, Ty], frame2token [B, Ty] and attn
+    [B, 1, Tx, Ty] where bufs has them (None: not written) -> the fp32 x_m / x_logs the launch read"""
+    B, C, Tx = x_m.shape
+    xm = x_m.float().contiguous()
+    xs = None if gen.mean_only else x_logs.float().contiguous()
+    source.prior(_lib.fill_args(_lib.SynthPriorArgs, x_m=xm, x_logs=xs, cum=cum, x_len=xl, y_len=y_len, row0=rcy.row0, Tp=rcy.Tp, R=rcy.R,
+                                **{k: bufs[k] for k in ("rows", "z_m", "z_logs", "frame2token", "attn")}, B=B, C=C, Tx=Tx, Ty=Ty,
+                                seed=0, noise_scale=0.0))
+    return xm, xs
+
+
+def prosody_stage(gen, g, rc, xb, rcy, rcf, bufs, source, Ty):
+    """models.py:1203-1228 at the frame rate, on the rows of rcf, on the caller's one stream: token rows gathered by
+    bufs["frame2token"] (frames no token owns, -1, are masked rows: not read) -> the stochastic pitch / energy predictors in reverse
+    -> pitch, energy [B, Ty] (None for a predictor the model does not have) and the keywords decoder.reverse_rows takes them by"""
+    xf = gen._gather_features(rc, xb, rcf, bufs["frame2token"])
+    if not source.keyed:                                             # eager only: row-keyed draws, the contours through from_rows
+        pitch = energy = None
+        if gen.use_spp:
+            nz = source.noise(rcf, 2, 2)
+            pitch = rcf.from_rows(gen.proj_pitch._reverse_rows(rcf, xf, gen.proj_pitch.cond_vec(g), nz)[:, None].contiguous()).squeeze(1) * source.scalars.pitch_scale
+        if gen.use_sep:
+            nz = source.noise(rcf, 3, 3)
+            energy = rcf.from_rows(gen.proj_energy._reverse_rows(rcf, xf, gen.proj_energy.cond_vec(g), nz)[:, None].contiguous()).squeeze(1) * source.scalars.energy_scale
+        return pitch, energy, dict(pitch=pitch, energy=energy)
+    prow = erow = None
+    if gen.use_spp:
+        prow = gen.proj_pitch._reverse_rows(rcf, xf, gen.proj_pitch.cond_vec(g), source.noise(rcf, 2, 2))
+    if gen.use_sep:
+        erow = gen.proj_energy._reverse_rows(rcf, xf, gen.proj_energy.cond_vec(g), source.noise(rcf, 3, 3))
+    p = _lib.ptr                                                     # for the return tuple and, squeezed, on the decoder's rows: one launch
+    source.contours(p(prow), p(erow), p(rcf.row0), rcf.Tp, p(rcf.lengths), rcf.R, p(rcy.row0), rcy.Tp, p(rcy.lengths), rcy.R, p(bufs["psig"]),
+                    p(bufs["esig"]), p(bufs["pitch"]), p(bufs["energy"]), rcy.B, Ty)
+    return bufs["pitch"], bufs["energy"], dict(pitch_rows=bufs["psig"], energy_rows=bufs["esig"])
 
 
 class SynthesisHandle:
@@ -87,10 +228,9 @@ class SynthesisHandle:
         dev = s.device
         if self._eager is None:
             x, xl, g, l, emo, emoc = self._inputs
-            seed, ns, ls = self._call[:3]
+            c = self._call
             # a full-model synthesiser passes every scalar of the call on; the plain one calls infer as it always did
-            more = dict(zip(("noise_scale_w", "f0_noise_scale", "energy_noise_scale", "pitch_scale", "energy_scale"), self._call[3:])) \
-                if s.stochastic else {}
+            more = c._asdict() if s.stochastic else dict(seed=c.seed, noise_scale=c.noise_scale, length_scale=c.length_scale)
             if emo is not None:
                 more.update(emo=emo.to(dev), emo_cartesian=emoc.to(dev))
             # on the synthesiser's stream, behind the calls in flight (the eager path shares the model's scratch buffers with the graph)
@@ -104,8 +244,7 @@ class SynthesisHandle:
                         t.record_stream(s.stream)                                       # the caller's tensors, read on this stream
                 xp = torch.zeros(s.batch, s.max_tokens, dtype=torch.int64, device=dev)   # the text as the graph saw it: padded to max_tokens
                 xp[:, :x.shape[1]] = x.to(dev)
-                self._eager = s.gen.infer(xp, xl.to(dev), g=None if g is None else g.to(dev), l=None if l is None else l.to(dev),
-                                          noise_scale=ns, length_scale=ls, seed=seed, **more)
+                self._eager = s.gen.infer(xp, xl.to(dev), g=None if g is None else g.to(dev), l=None if l is None else l.to(dev), **more)
         cur = torch.cuda.current_stream(dev)
         cur.wait_stream(s.stream)
         for grp in self._eager:                                                        # allocated on s.stream, used on the caller's
@@ -247,7 +386,8 @@ class Synthesizer:
         self.l = view("l") if self.takes_l else None
         self.emo = view("emo") if self.takes_emo else None
         self.emo_cartesian = view("emo_cartesian").view(B, 3) if self.takes_emo else None
-        self.length_scale = self.call.view(torch.float32)[3]           # 0-dim: read by the graph's torch plumbing at replay
+        self.source = FromBlock(self.call)
+        self.length_scale = self.source.length_scale                     # 0-dim: read by the graph's torch plumbing at replay
         # ---- static outputs
         self._back = self._static(B + 1, torch.int32)                    # y_len | status: the call's one readback
         self.y_len, self.status = self._back[:B], self._back[B:]
@@ -298,62 +438,24 @@ class Synthesizer:
     # ---- the call, as launches ------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def _body(self):
-        from .text_models import _DurationRunner
-        gen, rcy = self.gen, self.rc
-        L = _lib.lib()
-        st = _lib.current_stream(self.device)
-        B, Tx, Ty, C = self.batch, self.max_tokens, self.max_frames, gen.out_channels
+        gen, rcy, rcf, src = self.gen, self.rc, self.rcf, self.source
+        p, dev, B, Ty = _lib.ptr, self.device, self.batch, self.max_frames
         gen.rows_cfg.host_lengths.clear()
-        g = gen.condition(self.g, self.emo, self.emo_cartesian) if self.g is not None else None
-        l = gen.emb_l(self.l).unsqueeze(-1) if self.l is not None else None
-        xo, x_m, x_logs, x_mask = gen.encoder(self.ids, self.x_len, l=l, g=g, prepared=True)
-        rc, xb = gen.encoder._last_rows
-        pw = gen.encoder.proj_w
-        dvec = pw.cond_vec(g, l)
-
-        def keyed_noise(rcn, stream, which):
-            nz = torch.empty(rcn.R, 2, dtype=torch.float32, device=self.device)
-            _lib.check(L.gt_randn_keyed_call(_lib.ptr(nz), _lib.ptr(rcn.row0), rcn.Tp, _lib.ptr(rcn.lengths), rcn.B, rcn.R, 2,
-                                             _lib.ptr(self.call), stream, which, st), "gt_randn_keyed_call")
-            return nz
-
-        if gen.use_sdp:                                                  # only under stochastic=True (the constructor)
-            logw = rc.from_rows(pw._reverse_rows(rc, xb, dvec, keyed_noise(rc, 1, 1))[:, None].contiguous())
-        else:
-            runner = _DurationRunner(pw, rc, xb, False, 0, has_cond=dvec is not None)
-            (logw,), _ = runner.forward(*([dvec] if dvec is not None else []))
-        # exp, length_scale and ceil stay in torch on [B, Tx], as in infer — length_scale is a device scalar of the call block
-        dur = torch.ceil(torch.exp(logw) * x_mask * self.length_scale).squeeze(1).contiguous()
-        xl = self.x_len.to(torch.int32)
+        # the stochastic duration predictor only under stochastic=True (the constructor)
+        g, l, x_m, x_logs, x_mask, rc, xb, logw = text_stage(gen, self.ids, self.x_len, self.g, self.l, self.emo, self.emo_cartesian,
+                                                             lambda rcx: src.noise(rcx, 1, 1))
         a = self.aux_static or {}
-        _lib.check(L.gt_synth_lengths(_lib.ptr(dur), _lib.ptr(xl), _lib.ptr(self.cum), _lib.ptr(self.y_len), _lib.ptr(a.get("logw_")), B, Tx, st),
-                   "gt_synth_lengths")
-        _lib.check(L.gt_synth_geometry(_lib.ptr(self.y_len), B, Ty, rcy.R, _lib.ptr(rcy.row0), _lib.ptr(rcy.lengths), _lib.ptr(self.y_len_eff),
-                                       _lib.ptr(rcy.rowbatch), _lib.ptr(rcy.rowframe), _lib.ptr(rcy.rowmask), _lib.ptr(rcy.rowutt),
-                                       _lib.ptr(self.status), st), "gt_synth_geometry")
-        rcf = self.rcf
+        dur, xl = lengths_stage(logw, x_mask, src.length_scale, self.x_len, self.cum, self.y_len, a.get("logw_"))
+        _launch(dev, "gt_synth_geometry", p(self.y_len), B, Ty, rcy.R, p(rcy.row0), p(rcy.lengths), p(self.y_len_eff), p(rcy.rowbatch),
+                p(rcy.rowframe), p(rcy.rowmask), p(rcy.rowutt), p(self.status))
         if rcf is not None:                                              # behind gt_synth_geometry: ORs bit 2 into the status word
-            _lib.check(L.gt_synth_frame_geometry(_lib.ptr(self.y_len_eff), B, Ty, rcf.R, _lib.ptr(rcf.row0), _lib.ptr(rcf.lengths),
-                                                 _lib.ptr(rcf.rowbatch), _lib.ptr(rcf.rowframe), _lib.ptr(rcf.rowmask), _lib.ptr(rcf.rowutt),
-                                                 _lib.ptr(self.status), st), "gt_synth_frame_geometry")
-        xm = x_m.float().contiguous()
-        xs = None if gen.mean_only else x_logs.float().contiguous()
-        args = _lib.fill_args(_lib.SynthPriorArgs, x_m=xm, x_logs=xs, cum=self.cum, x_len=xl, y_len=self.y_len_eff, row0=rcy.row0, Tp=rcy.Tp,
-                              R=rcy.R, rows=self.rows, z_m=a.get("z_m"), z_logs=a.get("z_logs"), frame2token=self.frame2token, attn=a.get("attn"),
-                              B=B, C=C, Tx=Tx, Ty=Ty, seed=0, noise_scale=0.0)
-        _lib.check(L.gt_synth_prior_call(ctypes.byref(args), _lib.ptr(self.call), st), "gt_synth_prior_call")
-        if rcf is not None:                                              # models.py:1203-1228 on the capture stream: no fork
-            xf = gen._gather_features(rc, xb, rcf, self.frame2token)
-            prow = erow = None
-            if gen.use_spp:
-                prow = gen.proj_pitch._reverse_rows(rcf, xf, gen.proj_pitch.cond_vec(g), keyed_noise(rcf, 2, 2))
-            if gen.use_sep:
-                erow = gen.proj_energy._reverse_rows(rcf, xf, gen.proj_energy.cond_vec(g), keyed_noise(rcf, 3, 3))
-            _lib.check(L.gt_synth_contours_call(_lib.ptr(prow), _lib.ptr(erow), _lib.ptr(rcf.row0), rcf.Tp, _lib.ptr(rcf.lengths), rcf.R,
-                                                _lib.ptr(rcy.row0), rcy.Tp, _lib.ptr(rcy.lengths), rcy.R, _lib.ptr(self.psig),
-                                                _lib.ptr(self.esig), _lib.ptr(self.pitch_static), _lib.ptr(self.energy_static), B, Ty,
-                                                _lib.ptr(self.call), st), "gt_synth_contours_call")
-        gen.decoder.reverse_rows(rcy, self.rows, g=g, out=self.mel_static, pitch_rows=self.psig, energy_rows=self.esig)
+            _launch(dev, "gt_synth_frame_geometry", p(self.y_len_eff), B, Ty, rcf.R, p(rcf.row0), p(rcf.lengths), p(rcf.rowbatch),
+                    p(rcf.rowframe), p(rcf.rowmask), p(rcf.rowutt), p(self.status))
+        bufs = dict(rows=self.rows, z_m=a.get("z_m"), z_logs=a.get("z_logs"), frame2token=self.frame2token, attn=a.get("attn"),
+                    pitch=self.pitch_static, energy=self.energy_static, psig=self.psig, esig=self.esig)
+        xm, xs = prior_stage(gen, x_m, x_logs, self.cum, xl, self.y_len_eff, rcy, bufs, src, Ty)
+        contours = prosody_stage(gen, g, rc, xb, rcy, rcf, bufs, src, Ty)[2] if rcf is not None else {}
+        gen.decoder.reverse_rows(rcy, self.rows, g=g, out=self.mel_static, **contours)
         if self.aux:
             a["logw"] = logw
         return xm, xs, xl, dur, logw                                     # kept: the graph replays into these
@@ -364,8 +466,8 @@ class Synthesizer:
         # warm-up inputs: a full-length text of token 1, no noise — whatever lengths come out, the kernels stay inside the capacities
         self.ids.fill_(1)
         self.x_len.fill_(self.max_tokens)
-        self.call.copy_(self._call_words(0, 0.0, 1.0, ext=(0.0, 0.0, 1.0, 1.0) if self.stochastic else None,
-                                         noise_scale_w=0.0 if self.stochastic else 1.0).to(dev))
+        warm = CallScalars(0, noise_scale=0.0, noise_scale_w=0.0 if self.stochastic else 1.0, f0_noise_scale=0.0, energy_noise_scale=0.0)
+        self.call.copy_(warm.words(self.stochastic).to(dev))
         if self.takes_emo:
             self.g.fill_(1.0)                                            # emb_g normalises the speaker vector: not the zero vector
         self.stream.wait_stream(cur)
@@ -382,16 +484,6 @@ class Synthesizer:
         torch.cuda.synchronize(dev)
 
     # ---- calling ------------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _call_words(seed, noise_scale, length_scale, ext=None, noise_scale_w=1.0):
-        """the call block as int32 words: gt_synth_call, or gt_synth_call_ext when ext = (f0_noise_scale, energy_noise_scale,
-        pitch_scale, energy_scale) is given"""
-        c = _lib.SynthCall(seed=int(seed) & 0xFFFFFFFF, noise_scale=float(noise_scale), noise_scale_w=float(noise_scale_w),
-                           length_scale=float(length_scale))
-        if ext is not None:
-            c = _lib.SynthCallExt(c, *[float(v) for v in ext])
-        return torch.frombuffer(bytearray(bytes(c)), dtype=torch.int32).clone()
-
     def _slot(self):
         """the next [pinned staging of the inputs, pinned readback, event, weakref of the call's handle, read] of the ring; a slot's
         event is recorded behind the readback of the call that used it.  A slot that is taken again is retired first: its call's
@@ -445,13 +537,13 @@ class Synthesizer:
                              "model with the emotion front end")
         if emo is not None and (emo.shape != (B,) or emo_cartesian.shape != (B, 3)):
             raise ValueError(f"emo must be [{B}] and emo_cartesian [{B}, 3], got {tuple(emo.shape)} and {tuple(emo_cartesian.shape)}")
-        ext = tuple(float(v) for v in (f0_noise_scale, energy_noise_scale, pitch_scale, energy_scale))
-        noise_scale_w = float(noise_scale_w)
-        if not self.stochastic and (noise_scale_w, *ext) != (1., 1., 1., 1., 1.):
+        call = CallScalars(0, *[float(v) for v in (noise_scale, noise_scale_w, length_scale, f0_noise_scale, energy_noise_scale, pitch_scale,
+                                                   energy_scale)])
+        if not self.stochastic and (call.noise_scale_w, *call[4:]) != (1., 1., 1., 1., 1.):
             raise ValueError("noise_scale_w / f0_noise_scale / energy_noise_scale / pitch_scale / energy_scale need compile_synthesis(stochastic=True)")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())      # torch's default CPU generator, as infer does
-        seed = int(seed) & 0xFFFFFFFF
+        call = call._replace(seed=int(seed) & 0xFFFFFFFF)
         slot = self._slot()
         host, back, ev = slot[:3]
         lay = self._layout
@@ -465,7 +557,7 @@ class Synthesizer:
         ids.zero_()
         ids[:, :x.shape[1]].copy_(x)
         put("x_len").copy_(x_lengths)
-        put("call").copy_(self._call_words(seed, noise_scale, length_scale, ext=ext if self.stochastic else None, noise_scale_w=noise_scale_w))
+        put("call").copy_(call.words(self.stochastic))
         if g is not None:
             put("g", (B, self.g_dim)).copy_(g2)
         if l is not None:
@@ -492,8 +584,7 @@ class Synthesizer:
             self.graph.replay()
             back.copy_(self._back, non_blocking=True)
             ev.record(self.stream)
-        h = SynthesisHandle(self, slot, (x, x_lengths, g, l, emo, emo_cartesian),
-                            (seed, float(noise_scale), float(length_scale), noise_scale_w, *ext))
+        h = SynthesisHandle(self, slot, (x, x_lengths, g, l, emo, emo_cartesian), call)
         slot[3], slot[4] = weakref.ref(h), False
         self._latest = weakref.ref(h)
         return h

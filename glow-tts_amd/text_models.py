@@ -556,26 +556,18 @@ class FlowGenerator(nn.Module):
         seed (set_synthesis_front only): the call's noise is a function of this integer alone; None draws one from torch's default
         CPU generator, so torch.manual_seed still governs the call."""
         if self.synthesis_front:
-            return self._infer_front(x, x_lengths, g, emo, emo_cartesian, l, noise_scale, noise_scale_w, f0_noise_scale,
-                                     energy_noise_scale, length_scale, pitch_scale, energy_scale, seed)
+            from .synthesis import CallScalars
+            return self._infer_front(x, x_lengths, g, emo, emo_cartesian, l, CallScalars(
+                seed, noise_scale, noise_scale_w, length_scale, f0_noise_scale, energy_noise_scale, pitch_scale, energy_scale))
         if seed is not None:
             raise ValueError("infer(seed=) needs the device front end: call set_synthesis_front() (or store_inverse(device_front=True)) first")
         if self.decoder._inv_cache is None:
             self.prepare()
+        from .synthesis import text_stage
         self.rows_cfg.host_lengths.clear()
-        g = self.condition(g, emo, emo_cartesian)
-        if l is not None:
-            l = self.emb_l(l).unsqueeze(-1)
-        xo, x_m, x_logs, x_mask = self.encoder(x, x_lengths, l=l, g=g, prepared=True)
-        rc, xb = self.encoder._last_rows
-        pw = self.encoder.proj_w
-        dvec = pw.cond_vec(g, l)
-        if self.use_sdp:
-            nz = torch.randn(rc.R, 2, dtype=torch.float32, device=x.device) * noise_scale_w
-            logw = rc.from_rows(pw._reverse_rows(rc, xb, dvec, nz)[:, None].contiguous())
-        else:
-            runner = _DurationRunner(pw, rc, xb, False, 0, has_cond=dvec is not None)
-            (logw,), _ = runner.forward(*([dvec] if dvec is not None else []))
+        g, l, x_m, x_logs, x_mask, rc, xb, logw = text_stage(
+            self, x, x_lengths, g, l, emo, emo_cartesian,
+            lambda rcx: torch.randn(rcx.R, 2, dtype=torch.float32, device=x.device) * noise_scale_w)
         w = torch.exp(logw) * x_mask * length_scale
         w_ceil = torch.ceil(w)
         y_lengths = torch.clamp_min(torch.sum(w_ceil, [1, 2]), 1).long()
@@ -619,10 +611,12 @@ class FlowGenerator(nn.Module):
         yo, logdet = self.decoder(z, z_mask, g=g, pitch=pitch, energy=energy, reverse=True, prepared=True)
         return (yo, z_m, z_logs, logdet, z_mask), (x_m, x_logs, x_mask), (attn, logw, logw_), (pitch, energy)
 
-    def _infer_front(self, x, x_lengths, g, emo, emo_cartesian, l, noise_scale, noise_scale_w, f0_noise_scale, energy_noise_scale,
-                     length_scale, pitch_scale, energy_scale, seed):
-        """infer with the device front end (set_synthesis_front): same return structure, shapes and dtypes."""
-        import ctypes
+    def _infer_front(self, x, x_lengths, g, emo, emo_cartesian, l, scalars):
+        """infer with the device front end (set_synthesis_front): same return structure, shapes and dtypes.  The stages are those of
+        synthesis.py with the call's scalars (a synthesis.CallScalars) by value; here is what only the eager path does: the seed, the
+        readback of the lengths, the row contexts built on the host from them, fresh outputs sized by them."""
+        from .synthesis import ByValue, lengths_stage, prior_stage, prosody_stage, text_stage
+        seed = scalars.seed
         if seed is None:
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())           # torch's default CPU generator
         seed = int(seed) & 0xFFFFFFFF
@@ -630,41 +624,12 @@ class FlowGenerator(nn.Module):
             self.prepare()
         self.rows_cfg.host_lengths.clear()
         dev = x.device
-        L = _lib.lib()
-        st = _lib.current_stream(dev)
-
-        keyed = self.noise_key == "frame"
-
-        def randn_rows(rcn, stream, scale):
-            nz = torch.empty(rcn.R, 2, dtype=torch.float32, device=dev)
-            if keyed:                                                        # (utterance, token / frame): independent of the layout
-                _lib.check(L.gt_randn_keyed(_lib.ptr(nz), _lib.ptr(rcn.row0), rcn.Tp, _lib.ptr(rcn.lengths), rcn.B, rcn.R, 2, seed, stream,
-                                            float(scale), st), "gt_randn_keyed")
-            else:
-                _lib.check(L.gt_randn_rows(_lib.ptr(nz), rcn.R, 2, seed, stream, float(scale), st), "gt_randn_rows")
-            return nz
-
-        g = self.condition(g, emo, emo_cartesian)
-        if l is not None:
-            l = self.emb_l(l).unsqueeze(-1)
-        xo, x_m, x_logs, x_mask = self.encoder(x, x_lengths, l=l, g=g, prepared=True)
-        rc, xb = self.encoder._last_rows
-        pw = self.encoder.proj_w
-        dvec = pw.cond_vec(g, l)
-        if self.use_sdp:
-            logw = rc.from_rows(pw._reverse_rows(rc, xb, dvec, randn_rows(rc, 1, noise_scale_w))[:, None].contiguous())
-        else:
-            runner = _DurationRunner(pw, rc, xb, False, 0, has_cond=dvec is not None)
-            (logw,), _ = runner.forward(*([dvec] if dvec is not None else []))
-        # exp, length_scale and ceil stay in torch on [B, Tx] (plumbing): the durations are bit for bit those of the other path
-        dur = torch.ceil(torch.exp(logw) * x_mask * length_scale).squeeze(1).contiguous()
+        src = ByValue(scalars._replace(seed=seed), self.noise_key == "frame", dev)
+        g, l, x_m, x_logs, x_mask, rc, xb, logw = text_stage(self, x, x_lengths, g, l, emo, emo_cartesian, lambda rcx: src.noise(rcx, 1, 1))
         B, C, Tx = x_m.shape
-        xl = x_lengths.to(torch.int32).contiguous()
-        cum = torch.empty(B, Tx, dtype=torch.int32, device=dev)
-        y_len = torch.empty(B, dtype=torch.int32, device=dev)
-        logw_ = torch.empty(B, 1, Tx, dtype=torch.float32, device=dev)
-        _lib.check(L.gt_synth_lengths(_lib.ptr(dur), _lib.ptr(xl), _lib.ptr(cum), _lib.ptr(y_len), _lib.ptr(logw_), B, Tx, st),
-                   "gt_synth_lengths")
+        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)      # noqa: E731
+        cum, y_len, logw_ = new(B, Tx, dtype=torch.int32), new(B, dtype=torch.int32), new(B, 1, Tx)
+        dur, xl = lengths_stage(logw, x_mask, src.length_scale, x_lengths, cum, y_len, logw_)
         if self._front_pin is None or self._front_pin.numel() < B:            # pinned staging of the readback, kept across calls
             self._front_pin = torch.empty(max(B, 64), dtype=torch.int32).pin_memory()
         host = self._front_pin[:B]
@@ -676,57 +641,29 @@ class FlowGenerator(nn.Module):
         # the squeezed mel axis, ragged: utterances back to back, no rows for padded frames
         rcy = ops.RowsCtx(y_len, T2, lengths_host=[v // 2 for v in lens], round_to=self.rows_cfg.row_round)
         rcy.stamps = self.rows_cfg.stamps
-        xm = x_m.float().contiguous()
-        xs = None if self.mean_only else x_logs.float().contiguous()
-        rows = torch.empty(rcy.R, 2 * C, dtype=torch.float32, device=dev)
-        z_m = torch.empty(B, C, Ty, dtype=torch.float32, device=dev)
-        z_logs = torch.empty(B, C, Ty, dtype=torch.float32, device=dev)
-        frame2token = torch.empty(B, Ty, dtype=torch.int32, device=dev)
-        attn = torch.empty(B, 1, Tx, Ty, dtype=torch.float32, device=dev)
-        args = _lib.fill_args(_lib.SynthPriorArgs, x_m=xm, x_logs=xs, cum=cum, x_len=xl, y_len=y_len, row0=rcy.row0, Tp=rcy.Tp, R=rcy.R,
-                              rows=rows, z_m=z_m, z_logs=z_logs, frame2token=frame2token, attn=attn, B=B, C=C, Tx=Tx, Ty=Ty,
-                              seed=seed, noise_scale=float(noise_scale))
-        _lib.check(L.gt_synth_prior(ctypes.byref(args), st), "gt_synth_prior")
+        bufs = dict(rows=new(rcy.R, 2 * C), z_m=new(B, C, Ty), z_logs=new(B, C, Ty), frame2token=new(B, Ty, dtype=torch.int32),
+                    attn=new(B, 1, Tx, Ty))
+        prior_stage(self, x_m, x_logs, cum, xl, y_len, rcy, bufs, src, Ty)
         z_mask = ops.length_mask(y_len, Ty).to(x_mask.dtype)
-        pitch = energy = psig = esig = rcf = None
-        if (self.use_spp or self.use_sep) and keyed:                  # models.py:1203-1228, at the frame rate on RAGGED rows
-            rcf = ops.RowsCtx(y_len, Ty, lengths_host=lens, round_to=self.rows_cfg.row_round) if self.rows_cfg.frame_rows_ragged \
-                else ops.RowsCtx(y_len, Ty)
-            xf = self._gather_features(rc, xb, rcf, frame2token)
-            prow = erow = None
-            if self.use_spp:
-                prow = self.proj_pitch._reverse_rows(rcf, xf, self.proj_pitch.cond_vec(g), randn_rows(rcf, 2, f0_noise_scale))
-                pitch = torch.empty(B, Ty, dtype=torch.float32, device=dev)
-                psig = torch.empty(rcy.R, 2, dtype=torch.float32, device=dev)
-            if self.use_sep:
-                erow = self.proj_energy._reverse_rows(rcf, xf, self.proj_energy.cond_vec(g), randn_rows(rcf, 3, energy_noise_scale))
-                energy = torch.empty(B, Ty, dtype=torch.float32, device=dev)
-                esig = torch.empty(rcy.R, 2, dtype=torch.float32, device=dev)
-            # the contours for the return tuple and, squeezed, on the decoder's rows: one launch
-            _lib.check(L.gt_synth_contours(_lib.ptr(prow), _lib.ptr(erow), _lib.ptr(rcf.row0), rcf.Tp, _lib.ptr(rcf.lengths), rcf.R,
-                                           _lib.ptr(rcy.row0), rcy.Tp, _lib.ptr(rcy.lengths), rcy.R, _lib.ptr(psig), _lib.ptr(esig),
-                                           _lib.ptr(pitch), _lib.ptr(energy), B, Ty, float(pitch_scale), float(energy_scale), st),
-                       "gt_synth_contours")
-        elif self.use_spp or self.use_sep:                            # models.py:1203-1228, at the frame rate (uniform rows)
-            rcf = ops.RowsCtx(y_len, Ty)
-            xf = self._gather_features(rc, xb, rcf, frame2token)      # frames no token owns (-1) are masked rows: not read
-            if self.use_spp:
-                nz = randn_rows(rcf, 2, f0_noise_scale)
-                pitch = rcf.from_rows(self.proj_pitch._reverse_rows(rcf, xf, self.proj_pitch.cond_vec(g), nz)[:, None].contiguous()).squeeze(1) * pitch_scale
-            if self.use_sep:
-                nz = randn_rows(rcf, 3, energy_noise_scale)
-                energy = rcf.from_rows(self.proj_energy._reverse_rows(rcf, xf, self.proj_energy.cond_vec(g), nz)[:, None].contiguous()).squeeze(1) * energy_scale
+        pitch = energy = rcf = None
+        contours = {}
+        if self.use_spp or self.use_sep:
+            # the frame rate: ragged rows under the frame keying (padded frames cost nothing), uniform ones under the row keying
+            rcf = ops.RowsCtx(y_len, Ty, lengths_host=lens, round_to=self.rows_cfg.row_round) \
+                if src.keyed and self.rows_cfg.frame_rows_ragged else ops.RowsCtx(y_len, Ty)
+            if src.keyed:
+                bufs.update(pitch=new(B, Ty) if self.use_spp else None, psig=new(rcy.R, 2) if self.use_spp else None,
+                            energy=new(B, Ty) if self.use_sep else None, esig=new(rcy.R, 2) if self.use_sep else None)
+            pitch, energy, contours = prosody_stage(self, g, rc, xb, rcy, rcf, bufs, src, Ty)
         if T2 == 0:                                                   # no utterance has two frames: nothing to decode
             yo = torch.zeros(B, C, 0, dtype=x_m.dtype, device=dev)
         else:
-            if keyed:
-                yo = self.decoder.reverse_rows(rcy, rows, g=g, pitch_rows=psig, energy_rows=esig).to(x_m.dtype)
-            else:
-                yo = self.decoder.reverse_rows(rcy, rows, g=g, pitch=pitch, energy=energy).to(x_m.dtype)
+            yo = self.decoder.reverse_rows(rcy, bufs["rows"], g=g, **contours).to(x_m.dtype)
         # what the last call put in front of the decoder (tests, tools): rows context, sampled latent rows, frame -> token map, and
         # the frame-rate rows context of the pitch / energy predictors (None without them)
-        self._front_last = dict(rc=rcy, rows=rows, frame2token=frame2token, seed=seed, rc_frames=rcf)
-        return (yo, z_m, z_logs, None, z_mask), (x_m, x_logs, x_mask), (attn.to(x_mask.dtype), logw, logw_), (pitch, energy)
+        self._front_last = dict(rc=rcy, rows=bufs["rows"], frame2token=bufs["frame2token"], seed=seed, rc_frames=rcf)
+        return (yo, bufs["z_m"], bufs["z_logs"], None, z_mask), (x_m, x_logs, x_mask), (bufs["attn"].to(x_mask.dtype), logw, logw_), \
+            (pitch, energy)
 
     @staticmethod
     def _gather_features(rcx, xb, rcf, frame2token):

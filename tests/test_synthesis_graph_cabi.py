@@ -88,3 +88,26 @@ def test_call_entries_argument_validation_needs_no_device(built):
     assert L.gt_randn_rows_call(P, 8, 2, P, 1, 2, None) == INVAL                  # which_scale: 0 or 1
     assert L.gt_randn_rows_call(P, 8, 2, P + 1, 1, 0, None) == ALIGN
     assert L.gt_randn_rows_call(P + 2, 8, 2, P, 1, 0, None) == ALIGN
+
+
+def test_call_scalars_are_the_call_block_field_for_field():
+    """synthesis.CallScalars.words: the bytes of gt_synth_call_ext built field by field; the plain block is its first 16 bytes"""
+    from glow_tts_amd import _lib
+    from glow_tts_amd.synthesis import CallScalars
+    names = [f[0] for f in _lib.SynthCall._fields_] + [f[0] for f in _lib.SynthCallExt._fields_[1:]]
+    assert list(CallScalars._fields) == names                                     # the field order of gt_synth_call_ext
+    vals = dict(seed=0xFFFFFFFE, noise_scale=0.667, noise_scale_w=0.8, length_scale=1.3, f0_noise_scale=0.3, energy_noise_scale=0.9,
+                pitch_scale=1.25, energy_scale=0.75)
+    c = CallScalars(**vals)
+    want = _lib.SynthCallExt(_lib.SynthCall(*[vals[k] for k in names[:4]]), *[vals[k] for k in names[4:]])
+    ext, plain = c.words(True), c.words(False)
+    assert ext.dtype == plain.dtype and str(ext.dtype) == "torch.int32"
+    assert ctypes.sizeof(_lib.SynthCallExt) == 32 and ext.numel() * 4 == 32 and plain.numel() * 4 == 16
+    assert ext.numpy().tobytes() == bytes(want)
+    for i, k in enumerate(names):                                                 # ... and word by word, under the struct's own names
+        field = want.base if i < 4 else want
+        raw = (ctypes.c_uint32 if k == "seed" else ctypes.c_float)(getattr(field, k))
+        assert ext.numpy().tobytes()[4 * i:4 * i + 4] == bytes(raw), k
+    assert ext.numpy().tobytes()[:16] == plain.numpy().tobytes() == bytes(want.base)
+    assert CallScalars(seed=-1).words(False)[0].item() == -1                      # the seed is taken modulo 2^32
+    assert CallScalars(seed=3)[1:] == (1.,) * 7                                   # infer's defaults
