@@ -12,147 +12,164 @@ LIB_PATH = os.environ.get("GT_LIB") or os.path.join(_HERE, "libglowtts_hip.so") 
 c_void_p, c_int, c_i64, c_size_t, c_float, c_u32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
                                                     ctypes.c_size_t, ctypes.c_float, ctypes.c_uint32)
 
-# name -> (restype, argtypes); mirrors include/glowtts_hip.h one to one
+
+class Pointer(ctypes.c_void_p):
+    """Pointer parameter of a C-ABI entry: a tensor (anything with data_ptr()) passes its address, a ctypes structure passes by
+    reference, everything else (None, int, c_void_p, a byref result) is what c_void_p takes."""
+
+    @classmethod
+    def from_param(cls, v):
+        if hasattr(v, "data_ptr"):
+            v = v.data_ptr()
+        elif isinstance(v, ctypes.Structure):
+            return ctypes.byref(v)
+        return ctypes.c_void_p.from_param(v)
+
+
+STATUS = "status"      # restype marker: the entry returns 0 or a GT_E_* code (bound as c_int; `call` raises GtError on non-zero)
+c_void_p = Pointer     # for the table only: the structures below keep the real c_void_p, so reading a field gives an int
+
+# name -> (restype, argtypes); mirrors include/glowtts_hip.h one to one (tests/test_cabi.py compares it with the declarations)
 PROTOTYPES = {
     "gt_version": (ctypes.c_char_p, []),
-    "gt_mas_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                           c_int, c_int, c_int, c_i64, c_i64, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "gt_mas_f32": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                            c_int, c_int, c_int, c_i64, c_i64, c_void_p, c_size_t, c_void_p, c_void_p]),
     "gt_mas_lds_bytes": (c_size_t, [c_int, c_int]),
     "gt_mas_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "gt_mas_lengths_from_mask_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                             c_i64, c_i64, c_void_p]),
-    "gt_conv_gemm_bf16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                                  c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                                  c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                  c_int, c_int, c_float, c_u32, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gt_mas_lengths_from_mask_f32": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                              c_i64, c_i64, c_void_p]),
+    "gt_conv_gemm_bf16": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                   c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                   c_int, c_int, c_float, c_u32, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "gt_conv_wgrad_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_void_p]),
     "gt_conv_wgrad_ci_tile": (c_int, [c_int]),
-    "gt_conv_wgrad_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "gt_weightnorm_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_int, c_int, c_int, c_int, c_void_p]),
-    "gt_conv_wgrad_batched": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "gt_weightnorm_bwd_batched": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
-    "gt_adamw_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
-    "gt_colsum": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
-    "gt_squeeze_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "gt_unsqueeze_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "gt_flow_scalars": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    "gt_flow_scalars_multi": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
-    "gt_actnorm_ddi": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "gt_actnorm_invconv_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "gt_actnorm_invconv_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "gt_actnorm_invconv_rev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gt_coupling_rev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "gt_coupling_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
-    "gt_coupling_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
-    "gt_gate_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                            c_int, c_int, c_float, c_u32, c_void_p, c_void_p]),
-    "gt_relu_drop_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
-    "gt_rows_add_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "gt_rows_f32_to_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
-    "gt_layernorm_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                 c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_u32, c_float, c_u32, c_int, c_void_p, c_void_p]),
-    "gt_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                 c_float, c_float, c_u32, c_float, c_u32, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                 c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "gt_conv_wgrad_bf16": (STATUS, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "gt_weightnorm_bwd": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int, c_int, c_int, c_int, c_void_p]),
+    "gt_conv_wgrad_batched": (STATUS, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gt_weightnorm_bwd_batched": (STATUS, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gt_adamw_flat": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "gt_colsum": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "gt_squeeze_rows_f32": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gt_unsqueeze_rows_f32": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gt_flow_scalars": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "gt_flow_scalars_multi": (STATUS, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "gt_actnorm_ddi": (STATUS, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gt_actnorm_invconv_fwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gt_actnorm_invconv_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gt_actnorm_invconv_rev": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gt_coupling_rev": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gt_coupling_fwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "gt_coupling_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "gt_gate_bwd": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                             c_int, c_int, c_float, c_u32, c_void_p, c_void_p]),
+    "gt_relu_drop_bwd": (STATUS, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    "gt_rows_add_bf16": (STATUS, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gt_rows_f32_to_bf16": (STATUS, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "gt_layernorm_fwd": (STATUS, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_u32, c_float, c_u32, c_int, c_void_p, c_void_p]),
+    "gt_layernorm_bwd": (STATUS, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                  c_float, c_float, c_u32, c_float, c_u32, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gt_layernorm_bwd_partial_rows": (c_int, [c_int]),
-    "gt_layernorm_bwd_partials": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                          c_float, c_float, c_u32, c_float, c_u32, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                          c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "gt_param_partials_reduce": (c_int, [c_void_p, c_void_p]),
+    "gt_layernorm_bwd_partials": (STATUS, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                           c_float, c_float, c_u32, c_float, c_u32, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "gt_param_partials_reduce": (STATUS, [c_void_p, c_void_p]),
     "gt_dds_bwd_partial_rows": (c_int, [c_int]),
-    "gt_attn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                            c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_u32, c_void_p, c_void_p]),
+    "gt_attn_fwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                             c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_u32, c_void_p, c_void_p]),
     "gt_attn_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gt_attn_mfma_shape": (c_int, [c_int, c_int, c_int]),
-    "gt_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                            c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                            c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_u32, c_void_p, c_void_p]),
-    "gt_embedding_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
-    "gt_embedding_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
-    "gt_rows_add_cond": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                 c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "gt_rows_ctx_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gt_step_inputs": (c_int, [c_void_p, c_void_p]),
-    "gt_step_zero": (c_int, [c_void_p, c_void_p]),
-    "gt_rows_utt_sum": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "gt_logp_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "gt_prior_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "gt_rows_from_bct": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "gt_bct_from_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "gt_mle_finish": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "gt_duration_loss_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "gt_duration_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "gt_prior_expand_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "gt_mle_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "gt_mle_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
-    "gt_mark": (c_int, [c_void_p, c_void_p]),
-    "gt_length_mask": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
-    "gt_wn_layer_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
-                                c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                c_int, c_int, c_int, c_float, c_u32, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "gt_wn_layer_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_u32,
-                                c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "gt_wn_stack_fwd": (c_int, [c_void_p, c_void_p]),
+    "gt_attn_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                             c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                             c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_u32, c_void_p, c_void_p]),
+    "gt_embedding_fwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    "gt_embedding_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    "gt_rows_add_cond": (STATUS, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                  c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gt_rows_ctx_fill": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gt_step_inputs": (STATUS, [c_void_p, c_void_p]),
+    "gt_step_zero": (STATUS, [c_void_p, c_void_p]),
+    "gt_rows_utt_sum": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gt_logp_f32": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "gt_prior_expand": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "gt_rows_from_bct": (STATUS, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gt_bct_from_rows": (STATUS, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gt_mle_finish": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gt_duration_loss_fwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gt_duration_loss_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gt_prior_expand_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "gt_mle_sums": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gt_mle_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
+    "gt_mark": (STATUS, [c_void_p, c_void_p]),
+    "gt_length_mask": (STATUS, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "gt_wn_layer_fwd": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                 c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                 c_int, c_int, c_int, c_float, c_u32, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "gt_wn_layer_bwd": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                 c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_u32,
+                                 c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "gt_wn_stack_fwd": (STATUS, [c_void_p, c_void_p]),
     "gt_wn_stack_rows_per_workgroup": (c_int, [c_int]),
     "gt_wn_stack_row_blocks": (c_int, [c_int, c_int, c_int]),
-    "gt_cond_affine_grads": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "gt_wn_stack_bwd": (c_int, [c_void_p, c_void_p]),
-    "gt_wn_boundary_fwd": (c_int, [c_void_p, c_void_p]),
-    "gt_wn_boundary_bwd": (c_int, [c_void_p, c_void_p]),
+    "gt_cond_affine_grads": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gt_wn_stack_bwd": (STATUS, [c_void_p, c_void_p]),
+    "gt_wn_boundary_fwd": (STATUS, [c_void_p, c_void_p]),
+    "gt_wn_boundary_bwd": (STATUS, [c_void_p, c_void_p]),
     "gt_boundary_param_partials": (c_int, []),
-    "gt_wn_boundary_rev": (c_int, [c_void_p, c_void_p]),
+    "gt_wn_boundary_rev": (STATUS, [c_void_p, c_void_p]),
     "gt_boundary_rev_args_size": (c_int, []),
-    "gt_boundary_param_reduce": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "gt_rows_split3": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
-    "gt_dds_sep_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "gt_dds_out_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_u32, c_void_p, c_void_p]),
-    "gt_dds_out_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_u32, c_void_p, c_void_p]),
-    "gt_dds_sep_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                               c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
-    "gt_dds_dw_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "gt_convflow_pre_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gt_convflow_pre_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
-    "gt_convflow_spline_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
-    "gt_convflow_spline_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
+    "gt_boundary_param_reduce": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gt_rows_split3": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "gt_dds_sep_fwd": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "gt_dds_out_fwd": (STATUS, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_u32, c_void_p, c_void_p]),
+    "gt_dds_out_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_u32, c_void_p, c_void_p]),
+    "gt_dds_sep_bwd": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    "gt_dds_dw_bwd": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gt_convflow_pre_fwd": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gt_convflow_pre_bwd": (STATUS, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "gt_convflow_spline_fwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
+    "gt_convflow_spline_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
     "gt_convflow_spline_partial_rows": (c_int, [c_int]),
     "gt_convflow_spline_partial_width": (c_int, []),
-    "gt_convflow_spline_inv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gt_ea_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p]),
-    "gt_ea_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p]),
-    "gt_sdp_mid_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "gt_sdp_mid_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "gt_nll_gauss_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "gt_nll_gauss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "gt_rows_gather_tokens": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gt_pack_conv_weights_multi": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
-    "gt_pack_conv_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                     c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "gt_synth_lengths": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gt_synth_prior": (c_int, [c_void_p, c_void_p]),
+    "gt_convflow_spline_inv": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gt_ea_fwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p]),
+    "gt_ea_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p]),
+    "gt_sdp_mid_fwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "gt_sdp_mid_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "gt_nll_gauss_fwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "gt_nll_gauss_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "gt_rows_gather_tokens": (STATUS, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gt_pack_conv_weights_multi": (STATUS, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gt_pack_conv_weights": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gt_synth_lengths": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gt_synth_prior": (STATUS, [c_void_p, c_void_p]),
     "gt_synth_prior_args_size": (c_int, []),
-    "gt_randn_rows": (c_int, [c_void_p, c_int, c_int, c_u32, c_u32, c_float, c_void_p]),
+    "gt_randn_rows": (STATUS, [c_void_p, c_int, c_int, c_u32, c_u32, c_float, c_void_p]),
     "gt_synth_call_size": (c_int, []),
-    "gt_synth_geometry": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_void_p]),
-    "gt_synth_prior_call": (c_int, [c_void_p, c_void_p, c_void_p]),
-    "gt_randn_rows_call": (c_int, [c_void_p, c_int, c_int, c_void_p, c_u32, c_int, c_void_p]),
+    "gt_synth_geometry": (STATUS, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "gt_synth_prior_call": (STATUS, [c_void_p, c_void_p, c_void_p]),
+    "gt_randn_rows_call": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_u32, c_int, c_void_p]),
     "gt_synth_call_ext_size": (c_int, []),
-    "gt_randn_keyed": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_u32, c_u32, c_float, c_void_p]),
-    "gt_randn_keyed_call": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_u32, c_int, c_void_p]),
-    "gt_synth_frame_geometry": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_void_p]),
-    "gt_synth_contours": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                  c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
-    "gt_synth_contours_call": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gt_randn_keyed": (STATUS, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_u32, c_u32, c_float, c_void_p]),
+    "gt_randn_keyed_call": (STATUS, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_u32, c_int, c_void_p]),
+    "gt_synth_frame_geometry": (STATUS, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
+    "gt_synth_contours": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
+    "gt_synth_contours_call": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
-
+c_void_p = ctypes.c_void_p
 
 
 class PackDesc(ctypes.Structure):
@@ -282,6 +299,14 @@ class SynthCallExt(ctypes.Structure):
                 ("energy_scale", c_float)]
 
 
+# mirror -> its C struct in include/glowtts_hip.h (tests/test_cabi.py compares every size and field offset with a C compiler's)
+C_STRUCTS = {PackDesc: "gt_pack_desc", StepCopy: "gt_step_copy", StepCtx: "gt_step_ctx", StepInputsArgs: "gt_step_inputs_args",
+             PartialsJob: "gt_partials_job", PartialsArgs: "gt_partials_args", StepZeroArgs: "gt_step_zero_args",
+             WnStackFwdArgs: "gt_wn_stack_fwd_args", WnStackBwdArgs: "gt_wn_stack_bwd_args", BoundaryFwdArgs: "gt_boundary_fwd_args",
+             BoundaryBwdArgs: "gt_boundary_bwd_args", BoundaryRevArgs: "gt_boundary_rev_args", SynthPriorArgs: "gt_synth_prior_args",
+             SynthCall: "gt_synth_call", SynthCallExt: "gt_synth_call_ext"}
+
+
 def fill_args(cls, **kw):
     """ctypes struct from keyword arguments: tensors become device pointers, None stays NULL, ints stay ints."""
     a = cls()
@@ -307,7 +332,8 @@ class HipLibraryMissing(RuntimeError):
 
 
 def lib():
-    """Load (once) and return the HIP library; raise loudly if it is not built."""
+    """Load (once) and return the HIP library; raise loudly if it is not built.  The raw surface (with `check`, `ptr`,
+    `current_stream`), for callers that inspect a status themselves: bench.py, the tests and tools/.  Product code uses `call`."""
     global _LIB
     if _LIB is None:
         if not os.path.exists(LIB_PATH):
@@ -324,7 +350,7 @@ def lib():
                 fn = getattr(L, name)
             except AttributeError as e:
                 raise HipLibraryMissing(f"{LIB_PATH} does not export {name}; rebuild it") from e
-            fn.restype = res
+            fn.restype = c_int if res is STATUS else res
             fn.argtypes = args
         if os.environ.get("GT_TRACE_CALLS"):
             L = _Traced(L, os.environ["GT_TRACE_CALLS"])
@@ -389,17 +415,49 @@ class record_calls:
         return False
 
 
+class GtError(RuntimeError):
+    """a C-ABI entry returned a GT_E_* status"""
+
+    def __init__(self, entry, code):
+        super().__init__(f"{entry} failed: {GT_ERRORS.get(code, code)}")
+        self.entry, self.code = entry, code
+
+
+class _Call:
+    """`call.gt_x(a, b, ..., stream)`: the entry through lib() on every call (so record_calls and GT_TRACE_CALLS see it), tensors and
+    structures passed as they are (Pointer); a status entry raises GtError on a non-zero return, a value entry returns its value."""
+
+    def __getattr__(self, name):
+        if name not in PROTOTYPES:
+            raise AttributeError(f"{name} is not a C-ABI entry")
+        status = PROTOTYPES[name][0] is STATUS
+
+        def entry(*args):
+            rc = getattr(lib(), name)(*args)
+            if not status:
+                return rc
+            if rc != 0:
+                raise GtError(name, rc)
+        setattr(self, name, entry)
+        return entry
+
+
+call = _Call()
+
+
 def check(rc, what):
+    """raw surface: raise on a non-zero status of an entry called through lib()"""
     if rc != 0:
-        raise RuntimeError(f"{what} failed: {GT_ERRORS.get(rc, rc)}")
+        raise GtError(what, rc)
 
 
 def ptr(t):
-    """Device pointer of a torch tensor (or None)."""
+    """raw surface: device pointer of a torch tensor (or None)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def current_stream(device=None):
+    """the device's current stream as the C-ABI's stream argument"""
     import torch
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 

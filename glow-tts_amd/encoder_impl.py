@@ -12,7 +12,7 @@ copies meet.
 """
 import torch
 
-from . import _lib
+from ._lib import call
 from .flow_impl import _st, conv_param_grads
 from .ops import conv_rows, grad_accumulator, seed_word, zeros_small
 from .ops import zeros_big as ops_zeros_big
@@ -21,25 +21,21 @@ LN_EPS = 1e-4
 
 
 def _ln_fwd(rc, ln, a, y, p_in, seed_in, p_out, seed_out, relu, want_f32, C):
-    L = _lib.lib()
     R = rc.R
     dev = rc.device
     out_f32 = torch.empty(R, C, dtype=torch.float32, device=dev) if want_f32 else None
     out_bf = torch.empty(R, C, dtype=torch.bfloat16, device=dev)
     mean = torch.empty(R, dtype=torch.float32, device=dev)
     rstd = torch.empty(R, dtype=torch.float32, device=dev)
-    _lib.check(L.gt_layernorm_fwd(_lib.ptr(a), _lib.ptr(y), 0 if y is None else y.stride(0), _lib.ptr(ln.gamma), _lib.ptr(ln.beta),
-                                  _lib.ptr(rc.rowmask), _lib.ptr(out_f32), _lib.ptr(out_bf), C, _lib.ptr(mean), _lib.ptr(rstd),
-                                  R, C, LN_EPS, float(p_in), int(seed_in), float(p_out), int(seed_out), int(relu),
-                                  _lib.ptr(seed_word(dev)) if (p_in > 0 or p_out > 0) else None, _st(dev)),
-               "gt_layernorm_fwd")
+    call.gt_layernorm_fwd(a, y, 0 if y is None else y.stride(0), ln.gamma, ln.beta, rc.rowmask, out_f32, out_bf, C, mean, rstd, R, C, LN_EPS,
+                          float(p_in), int(seed_in), float(p_out), int(seed_out), int(relu), seed_word(dev) if (p_in > 0 or p_out > 0) else None,
+                          _st(dev))
     return out_f32, out_bf, (a, y, mean, rstd, p_in, seed_in, p_out, seed_out, relu, C)
 
 
 def _ln_bwd(rc, ln, saved, dout_f32, dout_bf, want_da, want_dy, grads, relu_in=False):
     """relu_in: the bf16 input y is a ReLU's output (conv -> relu -> norm, models.py:591-598): dy is zeroed where y is zero, i.e.
     the ReLU's backward rides along instead of a launch of its own."""
-    L = _lib.lib()
     a, y, mean, rstd, p_in, seed_in, p_out, seed_out, relu, C = saved
     R = rc.R
     dev = rc.device
@@ -52,23 +48,18 @@ def _ln_bwd(rc, ln, saved, dout_f32, dout_bf, want_da, want_dy, grads, relu_in=F
     if q is not None:
         # inside a module's backward (an open WgradQueue): per-workgroup partial sums now, ONE reduce launch for all the LayerNorms of
         # the module when the queue is flushed — instead of 2 C same-address atomics per workgroup in every launch
-        part = torch.empty(L.gt_layernorm_bwd_partial_rows(R), 2 * C, dtype=torch.float32, device=dev)
-        _lib.check(L.gt_layernorm_bwd_partials(_lib.ptr(a), _lib.ptr(y), 0 if y is None else y.stride(0), _lib.ptr(ln.gamma), _lib.ptr(ln.beta),
-                                               _lib.ptr(rc.rowmask), _lib.ptr(mean), _lib.ptr(rstd), R, C, LN_EPS,
-                                               float(p_in), int(seed_in), float(p_out), int(seed_out), int(bool(relu)) | (2 if relu_in else 0),
-                                               _lib.ptr(seed_word(dev)) if (p_in > 0 or p_out > 0) else None,
-                                               _lib.ptr(dout_f32), _lib.ptr(dout_bf), 0 if dout_bf is None else dout_bf.stride(0),
-                                               _lib.ptr(da), _lib.ptr(dy), C, _lib.ptr(part), _st(dev)), "gt_layernorm_bwd_partials")
+        part = torch.empty(call.gt_layernorm_bwd_partial_rows(R), 2 * C, dtype=torch.float32, device=dev)
+        call.gt_layernorm_bwd_partials(a, y, 0 if y is None else y.stride(0), ln.gamma, ln.beta, rc.rowmask, mean, rstd, R, C, LN_EPS, float(p_in),
+                                       int(seed_in), float(p_out), int(seed_out), int(bool(relu)) | (2 if relu_in else 0),
+                                       seed_word(dev) if (p_in > 0 or p_out > 0) else None, dout_f32, dout_bf,
+                                       0 if dout_bf is None else dout_bf.stride(0), da, dy, C, part, _st(dev))
         q.add_ln(part, dg, db)
         grads[ln.gamma] = dg
         grads[ln.beta] = db
         return da, dy
-    _lib.check(L.gt_layernorm_bwd(_lib.ptr(a), _lib.ptr(y), 0 if y is None else y.stride(0), _lib.ptr(ln.gamma), _lib.ptr(ln.beta),
-                                  _lib.ptr(rc.rowmask), _lib.ptr(mean), _lib.ptr(rstd), R, C, LN_EPS,
-                                  float(p_in), int(seed_in), float(p_out), int(seed_out), int(bool(relu)) | (2 if relu_in else 0),
-                                  _lib.ptr(seed_word(dev)) if (p_in > 0 or p_out > 0) else None,
-                                  _lib.ptr(dout_f32), _lib.ptr(dout_bf), 0 if dout_bf is None else dout_bf.stride(0),
-                                  _lib.ptr(da), _lib.ptr(dy), C, _lib.ptr(dg), _lib.ptr(db), _st(dev)), "gt_layernorm_bwd")
+    call.gt_layernorm_bwd(a, y, 0 if y is None else y.stride(0), ln.gamma, ln.beta, rc.rowmask, mean, rstd, R, C, LN_EPS, float(p_in), int(seed_in),
+                          float(p_out), int(seed_out), int(bool(relu)) | (2 if relu_in else 0), seed_word(dev) if (p_in > 0 or p_out > 0) else None,
+                          dout_f32, dout_bf, 0 if dout_bf is None else dout_bf.stride(0), da, dy, C, dg, db, _st(dev))
     grads[ln.gamma] = dg
     grads[ln.beta] = db
     return da, dy
@@ -76,7 +67,6 @@ def _ln_bwd(rc, ln, saved, dout_f32, dout_bf, want_da, want_dy, grads, relu_in=F
 
 # ----------------------------------------------------------------------------- attention
 def mha_fwd(rc, att, xb, p, seed):
-    L = _lib.lib()
     dev = xb.device
     R = rc.R
     H, D, C = att.n_heads, att.k_channels, att.channels
@@ -88,17 +78,14 @@ def mha_fwd(rc, att, xb, p, seed):
     P = torch.empty(rc.B, H, rc.T, rc.T, dtype=torch.float32, device=dev)
     Ek = att.emb_rel_k.detach().reshape(-1, D).contiguous()
     Ev = att.emb_rel_v.detach().reshape(-1, D).contiguous()
-    _lib.check(L.gt_attn_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), 3 * C, _lib.ptr(Ek), _lib.ptr(Ev), _lib.ptr(rc.lengths),
-                             _lib.ptr(o), C, _lib.ptr(P), rc.B, rc.T, rc.Tp, _lib.ptr(rc.row0), H, D, att.window_size, float(p), int(seed),
-                             _lib.ptr(seed_word(dev)) if p > 0 else None, _st(dev)),
-               "gt_attn_fwd")
+    call.gt_attn_fwd(q, k, v, 3 * C, Ek, Ev, rc.lengths, o, C, P, rc.B, rc.T, rc.Tp, rc.row0, H, D, att.window_size, float(p), int(seed),
+                     seed_word(dev) if p > 0 else None, _st(dev))
     y = conv_rows(o, att.conv_o.pc, rc, bias=att.conv_o.bias)
     return y, (xb, q, k, v, o, P, Ek, Ev, p, seed)
 
 
 def mha_bwd(rc, att, saved, dy, grads):
     """dy: bf16 rows gradient of the attention block output.  Returns dxb (bf16)."""
-    L = _lib.lib()
     xb, q, k, v, o, P, Ek, Ev, p, seed = saved
     dev = xb.device
     R = rc.R
@@ -110,15 +97,12 @@ def mha_bwd(rc, att, saved, dy, grads):
     dqkv = ops_zeros_big((R, 3 * C), torch.bfloat16, dev)
     dq, dk, dv = dqkv[:, :C], dqkv[:, C:2 * C], dqkv[:, 2 * C:]
     from .flow_impl import _scratch
-    ws_bytes = L.gt_attn_bwd_workspace_bytes(rc.B, rc.T, H)
+    ws_bytes = call.gt_attn_bwd_workspace_bytes(rc.B, rc.T, H)
     ws = _scratch("attn_bwd", ws_bytes, dev)
     dEk = grad_accumulator(att.emb_rel_k, Ek.shape)
     dEv = grad_accumulator(att.emb_rel_v, Ev.shape)
-    _lib.check(L.gt_attn_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), 3 * C, _lib.ptr(Ek), _lib.ptr(Ev), _lib.ptr(rc.lengths),
-                             _lib.ptr(do), C, _lib.ptr(P), _lib.ptr(ws), ws_bytes, _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), 3 * C,
-                             _lib.ptr(dEk), _lib.ptr(dEv), rc.B, rc.T, rc.Tp, _lib.ptr(rc.row0), H, D, att.window_size, float(p), int(seed),
-                             _lib.ptr(seed_word(dev)) if p > 0 else None, _st(dev)),
-               "gt_attn_bwd")
+    call.gt_attn_bwd(q, k, v, 3 * C, Ek, Ev, rc.lengths, do, C, P, ws, ws_bytes, dq, dk, dv, 3 * C, dEk, dEv, rc.B, rc.T, rc.Tp, rc.row0, H, D,
+                     att.window_size, float(p), int(seed), seed_word(dev) if p > 0 else None, _st(dev))
     grads[att.emb_rel_k] = dEk.view_as(att.emb_rel_k)
     grads[att.emb_rel_v] = dEv.view_as(att.emb_rel_v)
     grads.update(conv_param_grads(att.conv_q, xb, dq, R))
@@ -143,7 +127,6 @@ def layer_fwd(rc, enc, i, x, xb, train, seed):
 def layer_bwd(rc, enc, i, saved, dx, dxb, grads):
     """(dx fp32, dxb bf16): gradients wrt the layer's fp32 output and its bf16 copy (either may be
     None).  Returns the same pair for the layer input."""
-    L = _lib.lib()
     s_att, s_ln1, xb1, f1, s_ln2, p = saved
     att, ffn = enc.attn_layers[i], enc.ffn_layers[i]
     R = rc.R
@@ -161,7 +144,6 @@ def layer_bwd(rc, enc, i, saved, dx, dxb, grads):
 
 # ----------------------------------------------------------------------------- prenet (ConvReluNorm)
 def crn_fwd(rc, crn, x0, xb0, train, seed):
-    L = _lib.lib()
     p = crn.p_dropout if train else 0.0
     C = crn.hidden_channels
     h = xb0
@@ -173,24 +155,21 @@ def crn_fwd(rc, crn, x0, xb0, train, seed):
         h = hn
     x1 = conv_rows(h, crn.proj.pc, rc, bias=crn.proj.bias, addend=x0, mask=True, out_f32=True)
     xb1 = torch.empty(rc.R, crn.out_channels, dtype=torch.bfloat16, device=rc.device)
-    _lib.check(L.gt_rows_f32_to_bf16(_lib.ptr(x1), x1.stride(0), _lib.ptr(xb1), xb1.stride(0), None, rc.R, crn.out_channels,
-                                     _st(rc.device)), "gt_rows_f32_to_bf16")
+    call.gt_rows_f32_to_bf16(x1, x1.stride(0), xb1, xb1.stride(0), None, rc.R, crn.out_channels, _st(rc.device))
     return x1, xb1, (saved, h)
 
 
 def _sum_grads_to_bf16(rc, dx, dxb, C, masked=True):
     """bf16( (dx + dxb) * mask ) — where the fp32 stream and its bf16 copy meet again."""
-    L = _lib.lib()
     dev = rc.device
     if dx is None:
         tot = dxb.float()
     else:
         tot = dx.clone() if dxb is not None else dx
         if dxb is not None:
-            _lib.check(L.gt_rows_add_bf16(_lib.ptr(tot), tot.stride(0), _lib.ptr(dxb), dxb.stride(0), rc.R, C, _st(dev)), "gt_rows_add_bf16")
+            call.gt_rows_add_bf16(tot, tot.stride(0), dxb, dxb.stride(0), rc.R, C, _st(dev))
     out = torch.empty(rc.R, C, dtype=torch.bfloat16, device=dev)
-    _lib.check(L.gt_rows_f32_to_bf16(_lib.ptr(tot), tot.stride(0), _lib.ptr(out), C, _lib.ptr(rc.rowmask) if masked else None,
-                                     rc.R, C, _st(dev)), "gt_rows_f32_to_bf16")
+    call.gt_rows_f32_to_bf16(tot, tot.stride(0), out, C, rc.rowmask if masked else None, rc.R, C, _st(dev))
     return tot, out
 
 
@@ -200,7 +179,6 @@ def crn_bwd(rc, crn, saved_all, dx1, dxb1, grads):
     R = rc.R
     C = crn.out_channels
     tot, dpre = _sum_grads_to_bf16(rc, dx1, dxb1, C)             # x1 = (x0 + proj(h)) * mask
-    L = _lib.lib()
     dx0 = torch.empty(R, C, dtype=torch.float32, device=rc.device)
     dx0.copy_(dpre)                                               # masked sum, residual path
     grads.update(conv_param_grads(crn.proj, hlast, dpre, R))
@@ -228,14 +206,12 @@ def dp_fwd(rc, dp, xb, train, seed):
 def dp_bwd(rc, dp, saved, dout, grads, want_dx=False):
     """dout: [R, 8] fp32 (only column 0 non-zero).  x is detached in the reference: no input grad, except for the
     speaker vector added to it (want_dx: returns the bf16 input gradient its cond conv needs)."""
-    L = _lib.lib()
     xb, c1, s1, h1, c2, s2, h2 = saved
     R = rc.R
     dev = rc.device
     F = dp.filter_channels
     db = torch.empty(R, 8, dtype=torch.bfloat16, device=dev)
-    _lib.check(L.gt_rows_f32_to_bf16(_lib.ptr(dout), dout.stride(0), _lib.ptr(db), 8, _lib.ptr(rc.rowmask), R, 8, _st(dev)),
-               "gt_rows_f32_to_bf16")
+    call.gt_rows_f32_to_bf16(dout, dout.stride(0), db, 8, rc.rowmask, R, 8, _st(dev))
     g = conv_param_grads(dp.proj_pad, h2, db, R)
     grads[dp.proj.weight] = g[dp.proj_pad.weight][:1].contiguous()
     grads[dp.proj.bias] = g[dp.proj_pad.bias][:1].contiguous()

@@ -9,6 +9,7 @@ backward mirrors what autograd derives for the reference modules:
 import torch
 
 from . import _lib
+from ._lib import call
 from .ops import KERNEL_TIMER, RowsCtx, conv_rows, grad_accumulator, seed_word, zeros_small  # noqa: F401
 
 _SCRATCH = {}
@@ -48,28 +49,24 @@ def conv_param_grads(conv, x, dy, R, want_bias=True, parts=None):
         return q.add(conv, R, pl, want_bias)
     if parts is not None:                     # immediate mode: gather the pieces into one [R, Cout] buffer
         dy = torch.cat([d[:, :c] for d, _, c in sorted(parts, key=lambda t: t[1])], dim=1)
-    L = _lib.lib()
     pc = conv.pc
     dev = x.device
     import ctypes
     S = ctypes.c_int(0)
-    nbytes = L.gt_conv_wgrad_workspace_bytes(R, pc.Cin, pc.Cout, pc.taps, ctypes.byref(S))
+    nbytes = call.gt_conv_wgrad_workspace_bytes(R, pc.Cin, pc.Cout, pc.taps, ctypes.byref(S))
     ws = _scratch("wgrad", nbytes, dev)
-    _lib.check(L.gt_conv_wgrad_bf16(_lib.ptr(x), x.stride(0), _lib.ptr(dy), dy.stride(0), R, pc.Cin, pc.Cout, pc.taps,
-                                    _lib.ptr(ws), nbytes, _st(dev)), "gt_conv_wgrad_bf16")
+    call.gt_conv_wgrad_bf16(x, x.stride(0), dy, dy.stride(0), R, pc.Cin, pc.Cout, pc.taps, ws, nbytes, _st(dev))
     out = {}
     v = conv.weight_v if conv.weight_norm else conv.weight
     dv = torch.empty_like(v)
     db = torch.empty_like(conv.bias) if (want_bias and conv.bias is not None) else None
     if conv.weight_norm:
         dg = torch.empty_like(conv.weight_g)
-        _lib.check(L.gt_weightnorm_bwd(_lib.ptr(ws), R, _lib.ptr(v), _lib.ptr(conv.weight_g), _lib.ptr(pc.inv_norm),
-                                       _lib.ptr(dv), _lib.ptr(dg), _lib.ptr(db), pc.Cout, pc.Cin, pc.taps, 0, _st(dev)), "gt_weightnorm_bwd")
+        call.gt_weightnorm_bwd(ws, R, v, conv.weight_g, pc.inv_norm, dv, dg, db, pc.Cout, pc.Cin, pc.taps, 0, _st(dev))
         out[conv.weight_v] = dv
         out[conv.weight_g] = dg
     else:
-        _lib.check(L.gt_weightnorm_bwd(_lib.ptr(ws), R, _lib.ptr(v), None, None, _lib.ptr(dv), None, _lib.ptr(db),
-                                       pc.Cout, pc.Cin, pc.taps, 0, _st(dev)), "gt_weightnorm_bwd")
+        call.gt_weightnorm_bwd(ws, R, v, None, None, dv, None, db, pc.Cout, pc.Cin, pc.taps, 0, _st(dev))
         out[conv.weight] = dv
     if db is not None:
         out[conv.bias] = db
@@ -79,28 +76,24 @@ def conv_param_grads(conv, x, dy, R, want_bias=True, parts=None):
 # ----------------------------------------------------------------------------- ActNorm + InvConvNear
 def actnorm_ddi(rc, x, an):
     """ActNorm.initialize (modules.py:607-619) from the rows this layer is about to see; writes an.logs / an.bias."""
-    L = _lib.lib()
     R, C = x.shape
     ws = torch.empty(2 * C, dtype=torch.float64, device=x.device)
     with torch.no_grad():
-        _lib.check(L.gt_actnorm_ddi(_lib.ptr(x), _lib.ptr(rc.lengths), rc.B, R, C, _lib.ptr(ws), _lib.ptr(an.logs.data),
-                                    _lib.ptr(an.bias.data), _st(x.device)), "gt_actnorm_ddi")
+        call.gt_actnorm_ddi(x, rc.lengths, rc.B, R, C, ws, an.logs.data, an.bias.data, _st(x.device))
     an.initialized = True
 
 
 def flow_scalars(logs, W):
     """scal[18] = {sum logs, logdet W, W^-T} (gt_flow_scalars) for one ActNorm / InvConvNear pair."""
-    L = _lib.lib()
     lg = logs.detach().reshape(-1).contiguous()
     Wc = W.detach().contiguous()
     scal = torch.empty(18, dtype=torch.float32, device=lg.device)
-    _lib.check(L.gt_flow_scalars(_lib.ptr(lg), lg.numel(), _lib.ptr(Wc), _lib.ptr(scal), _st(lg.device)), "gt_flow_scalars")
+    call.gt_flow_scalars(lg, lg.numel(), Wc, scal, _st(lg.device))
     return scal
 
 
 def actnorm_invconv_fwd(rc, x, logs, bias, W, logdet, want_x0=True):
     """x: [R,C] fp32 rows.  Returns y [R,C] fp32, x0 bf16 [R,C/2] (coupling start input), saved."""
-    L = _lib.lib()
     dev = x.device
     R, C = x.shape
     y = torch.empty_like(x)
@@ -109,15 +102,12 @@ def actnorm_invconv_fwd(rc, x, logs, bias, W, logdet, want_x0=True):
     lg = logs.detach().reshape(-1).contiguous()
     bs = bias.detach().reshape(-1).contiguous()
     Wc = W.detach().contiguous()
-    _lib.check(L.gt_flow_scalars(_lib.ptr(lg), C, _lib.ptr(Wc), _lib.ptr(scal), _st(dev)), "gt_flow_scalars")
-    _lib.check(L.gt_actnorm_invconv_fwd(_lib.ptr(x), _lib.ptr(y), _lib.ptr(x0), C // 2, _lib.ptr(lg), _lib.ptr(bs), _lib.ptr(Wc),
-                                        _lib.ptr(scal), _lib.ptr(rc.rowmask), _lib.ptr(rc.lengths), _lib.ptr(logdet),
-                                        rc.B, R, C, _st(dev)), "gt_actnorm_invconv_fwd")
+    call.gt_flow_scalars(lg, C, Wc, scal, _st(dev))
+    call.gt_actnorm_invconv_fwd(x, y, x0, C // 2, lg, bs, Wc, scal, rc.rowmask, rc.lengths, logdet, rc.B, R, C, _st(dev))
     return y, x0, (x, lg, bs, Wc, scal)
 
 
 def actnorm_invconv_bwd(rc, saved, dy, dlogdet, logs, bias, W):
-    L = _lib.lib()
     x, lg, bs, Wc, scal = saved
     dev = x.device
     R, C = x.shape
@@ -125,10 +115,7 @@ def actnorm_invconv_bwd(rc, saved, dy, dlogdet, logs, bias, W):
     dlogs = grad_accumulator(logs, (C,))
     dbias = grad_accumulator(bias, (C,))
     dW = grad_accumulator(W, (16,))
-    _lib.check(L.gt_actnorm_invconv_bwd(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(dx), _lib.ptr(lg), _lib.ptr(bs), _lib.ptr(Wc),
-                                        _lib.ptr(scal), _lib.ptr(rc.rowmask), _lib.ptr(rc.lengths), _lib.ptr(dlogdet),
-                                        _lib.ptr(dlogs), _lib.ptr(dbias), _lib.ptr(dW), rc.B, R, C, _st(dev)),
-               "gt_actnorm_invconv_bwd")
+    call.gt_actnorm_invconv_bwd(x, dy, dx, lg, bs, Wc, scal, rc.rowmask, rc.lengths, dlogdet, dlogs, dbias, dW, rc.B, R, C, _st(dev))
     return dx, {logs: dlogs.view_as(logs), bias: dbias.view_as(bias), W: dW.view_as(W)}
 
 
@@ -173,7 +160,6 @@ def wn_fwd(rc, wn, h0, cond, train, seed, cond_per_row=False, layers_only=False,
     save=False (synthesis, no dropout): the whole-WaveNet kernel stores the gated activations only — no tanh / sigmoid halves, no x_i
     (the saved tuple then holds empty lists for them); the per-layer kernels always write them, and so does the whole-WaveNet kernel
     under affine conditioning (its acts-only form is built for cond / no conditioning only: csrc/wn_stack.hip, SAVE)."""
-    L = _lib.lib()
     R, H = h0.shape
     dev = h0.device
     n = wn.n_layers
@@ -188,7 +174,6 @@ def wn_fwd(rc, wn, h0, cond, train, seed, cond_per_row=False, layers_only=False,
     stamps = getattr(rc, "stamps", None)              # bench.py: live in-graph timing of the dominant kernel (ops.KernelStamps)
     if fused and getattr(wn, "stack_fwd", True) and n <= 4 and _stack_pays(R, n, dev):
         # all layers in ONE launch (csrc/wn_stack.hip: the 2-row halo between layers is recomputed, not exchanged)
-        import ctypes
         save = save or p > 0 or affine is not None
         ts = [torch.empty(R, H, dtype=torch.bfloat16, device=dev) for _ in range(n)] if save else []
         ss = [torch.empty(R, H, dtype=torch.bfloat16, device=dev) for _ in range(n)] if save else []
@@ -206,9 +191,8 @@ def wn_fwd(rc, wn, h0, cond, train, seed, cond_per_row=False, layers_only=False,
             stamps=stamps.buf if stamps else None, stamp_slot=stamps.take(f"stack{n}") if stamps else 0, stamp_base=stamps.base if stamps else None,
             **(dict(aff_w=aff_w, aff_b=aff_b, aff_sig=aff_sig) if affine is not None else {}))
         _ev = KERNEL_TIMER.start("wn_stack_fwd")
-        rcode = L.gt_wn_stack_fwd(ctypes.byref(args), _st(dev))
+        call.gt_wn_stack_fwd(args, _st(dev))
         KERNEL_TIMER.stop(_ev)
-        _lib.check(rcode, "gt_wn_stack_fwd")
         saved = (xs, ts, ss, acts_all, p, seed)
         if layers_only:
             return None, saved
@@ -226,18 +210,12 @@ def wn_fwd(rc, wn, h0, cond, train, seed, cond_per_row=False, layers_only=False,
             s = torch.empty(R, H, dtype=torch.bfloat16, device=dev)
             xn = None if last else torch.empty(R, H, dtype=torch.bfloat16, device=dev)
             _ev = KERNEL_TIMER.start("wn_layer_fwd")
-            rcode = L.gt_wn_layer_fwd(_lib.ptr(x), x.stride(0), _lib.ptr(il.pc.fwd), _lib.ptr(il.bias),
-                                      _lib.ptr(ci), 0 if ci is None else ci.stride(0),
-                                      _lib.ptr(rc.row0) if (ci is not None and not cond_per_row) else None,
-                                      0 if (cond_per_row or ci is None) else rc.B, rc.Tp, _lib.ptr(rc.rowmask),
-                                      _lib.ptr(acts), acts.stride(0), _lib.ptr(t), _lib.ptr(s), H,
-                                      None if last else _lib.ptr(rs.pc_res.fwd),
-                                      None if last else rs.bias.data_ptr(), _lib.ptr(xn), H,
-                                      R, H, wn.kernel_size, float(p), int(seed + i), _lib.ptr(seed_word(dev)) if p > 0 else None,
-                                      _lib.ptr(stamps.buf) if stamps else None, stamps.take("layer_last" if last else "layer") if stamps else 0,
-                                      _lib.ptr(stamps.base) if stamps else None, _st(dev))
+            call.gt_wn_layer_fwd(x, x.stride(0), il.pc.fwd, il.bias, ci, 0 if ci is None else ci.stride(0),
+                                 rc.row0 if (ci is not None and not cond_per_row) else None, 0 if (cond_per_row or ci is None) else rc.B, rc.Tp,
+                                 rc.rowmask, acts, acts.stride(0), t, s, H, None if last else rs.pc_res.fwd, None if last else rs.bias.data_ptr(), xn,
+                                 H, R, H, wn.kernel_size, float(p), int(seed + i), seed_word(dev) if p > 0 else None, stamps.buf if stamps else None,
+                                 stamps.take("layer_last" if last else "layer") if stamps else 0, stamps.base if stamps else None, _st(dev))
             KERNEL_TIMER.stop(_ev)
-            _lib.check(rcode, "gt_wn_layer_fwd")
             ts.append(t); ss.append(s)
             if not last:
                 x = xn
@@ -291,7 +269,6 @@ def _wn_bwd_fused(rc, wn, saved, dskip, want_dcond, cond_per_row, dacts_skip=Non
     """One kernel per layer boundary (gt_wn_layer_bwd): the k=5 data gradient of layer i+1's in_layer gives dX_{i+1} (the
     gradient at x_{i+1}); on that tile the residual 1x1's data gradient + the skip-path gradient + the gate backward of
     layer i follow, and d pre_i leaves for the next launch and for the weight gradients."""
-    L = _lib.lib()
     xs, ts, ss, acts_all, p, seed = saved
     R, H = dskip.shape
     dev = dskip.device
@@ -306,7 +283,6 @@ def _wn_bwd_fused(rc, wn, saved, dskip, want_dcond, cond_per_row, dacts_skip=Non
         dacts_skip = conv_rows(dskip, wn.pc_skipcat, rc, dgrad=True)
     if use_stack:
         # the whole data-gradient chain in ONE launch (csrc/wn_stack.hip), then the weight-gradient jobs on what it wrote
-        import ctypes
         bf = dict(dtype=torch.bfloat16, device=dev)
         dpre = [torch.empty(R, 2 * H, **bf) for _ in range(n)]
         dpre_c = [torch.empty(R, 2 * H, **bf) if need_c else None for _ in range(n)]
@@ -318,9 +294,8 @@ def _wn_bwd_fused(rc, wn, saved, dskip, want_dcond, cond_per_row, dacts_skip=Non
             rowmask=rc.rowmask, dpre=dpre + pad, dpre_c=dpre_c + pad, dx=dxs + pad, R=R, H=H, taps=wn.kernel_size, n_layers=n,
             drop_p=float(p), drop_seed=int(seed), seed_dev=seed_word(dev) if p > 0 else None)
         _ev = KERNEL_TIMER.start("wn_stack_bwd")
-        rcode = L.gt_wn_stack_bwd(ctypes.byref(args), _st(dev))
+        call.gt_wn_stack_bwd(args, _st(dev))
         KERNEL_TIMER.stop(_ev)
-        _lib.check(rcode, "gt_wn_stack_bwd")
         for i in reversed(range(n)):
             acts = acts_all[:, i * H:(i + 1) * H]
             if i == n - 1:
@@ -332,18 +307,15 @@ def _wn_bwd_fused(rc, wn, saved, dskip, want_dcond, cond_per_row, dacts_skip=Non
                 _dcond_store(rc, dcond, i, H, dpre_c[i] if need_c else dpre[i], cond_per_row)
         if affine_grads is not None:
             src = (dpre_c if need_c else dpre) + [None] * (4 - n)
-            _lib.check(L.gt_cond_affine_grads(_lib.ptr(src[0]), _lib.ptr(src[1]), _lib.ptr(src[2]), _lib.ptr(src[3]), 2 * H,
-                                              _lib.ptr(affine_grads[0]), _lib.ptr(affine_grads[1]), _lib.ptr(affine_grads[2]), R, H, n, _st(dev)),
-                       "gt_cond_affine_grads")
+            call.gt_cond_affine_grads(src[0], src[1], src[2], src[3], 2 * H, affine_grads[0], affine_grads[1], affine_grads[2], R, H, n, _st(dev))
         return dxs[0], grads, dcond
     # top layer: no residual output, d acts = skip path only
     i = n - 1
     dpre = torch.empty(R, 2 * H, dtype=torch.bfloat16, device=dev)
     dpre_c = torch.empty(R, 2 * H, dtype=torch.bfloat16, device=dev) if need_c else None
     via = dacts_skip[:, i * H:(i + 1) * H]
-    _lib.check(L.gt_gate_bwd(_lib.ptr(via), via.stride(0), _lib.ptr(ts[i]), _lib.ptr(ss[i]), ts[i].stride(0), _lib.ptr(dpre), 2 * H,
-                             _lib.ptr(dpre_c), R, H, float(p), int(seed + i), _lib.ptr(seed_word(dev)) if p > 0 else None, _st(dev)),
-               "gt_gate_bwd")
+    call.gt_gate_bwd(via, via.stride(0), ts[i], ss[i], ts[i].stride(0), dpre, 2 * H, dpre_c, R, H, float(p), int(seed + i),
+                     seed_word(dev) if p > 0 else None, _st(dev))
     grads.update(conv_param_grads(wn.res_skip_layers[i], acts_all[:, i * H:(i + 1) * H], dskip, R))
     grads.update(conv_param_grads(wn.in_layers[i], xs[i], dpre, R))
     if want_dcond:
@@ -356,11 +328,9 @@ def _wn_bwd_fused(rc, wn, saved, dskip, want_dcond, cond_per_row, dacts_skip=Non
         dpre_i = torch.empty(R, 2 * H, dtype=torch.bfloat16, device=dev)
         dpre_ci = torch.empty(R, 2 * H, dtype=torch.bfloat16, device=dev) if need_c else None
         via = dacts_skip[:, i * H:(i + 1) * H]
-        _lib.check(L.gt_wn_layer_bwd(_lib.ptr(dpre), 2 * H, _lib.ptr(nxt.pc.dgrad), _lib.ptr(dX), H, _lib.ptr(rc.rowmask),
-                                     _lib.ptr(dXn), H, _lib.ptr(rs.pc_res.dgrad), _lib.ptr(via), via.stride(0),
-                                     _lib.ptr(ts[i]), _lib.ptr(ss[i]), H, _lib.ptr(dpre_i), _lib.ptr(dpre_ci), 2 * H, R, H, wn.kernel_size,
-                                     float(p), int(seed + i), _lib.ptr(seed_word(dev)) if p > 0 else None, None, 0, None, _st(dev)),
-                   "gt_wn_layer_bwd")
+        call.gt_wn_layer_bwd(dpre, 2 * H, nxt.pc.dgrad, dX, H, rc.rowmask, dXn, H, rs.pc_res.dgrad, via, via.stride(0), ts[i], ss[i], H, dpre_i,
+                             dpre_ci, 2 * H, R, H, wn.kernel_size, float(p), int(seed + i), seed_word(dev) if p > 0 else None, None, 0, None,
+                             _st(dev))
         acts = acts_all[:, i * H:(i + 1) * H]
         grads.update(conv_param_grads(rs, acts, None, R, parts=[(dXn, 0, H), (dskip, H, H)]))
         grads.update(conv_param_grads(wn.in_layers[i], xs[i], dpre_i, R))
@@ -369,15 +339,13 @@ def _wn_bwd_fused(rc, wn, saved, dskip, want_dcond, cond_per_row, dacts_skip=Non
         dX, dpre = dXn, dpre_i
     # d x_0 = dgrad(in_layer_0) + (residual path), through the mask of x_0's producer: the same kernel without its second stage
     dh0 = torch.empty(R, H, dtype=torch.bfloat16, device=dev)
-    _lib.check(L.gt_wn_layer_bwd(_lib.ptr(dpre), 2 * H, _lib.ptr(wn.in_layers[0].pc.dgrad), _lib.ptr(dX), H, _lib.ptr(rc.rowmask),
-                                 _lib.ptr(dh0), H, None, None, 0, None, None, 0, None, None, 0, R, H, wn.kernel_size, 0.0, 0, None, None, 0, None,
-                                 _st(dev)), "gt_wn_layer_bwd")
+    call.gt_wn_layer_bwd(dpre, 2 * H, wn.in_layers[0].pc.dgrad, dX, H, rc.rowmask, dh0, H, None, None, 0, None, None, 0, None, None, 0, R, H,
+                         wn.kernel_size, 0.0, 0, None, None, 0, None, _st(dev))
     return dh0, grads, dcond
 
 
 def _wn_bwd_unfused(rc, wn, saved, dskip, want_dcond=False, cond_per_row=False):
     """round 1's launch sequence (two GEMM kernels per layer), kept as the reference the fused path is tested against"""
-    L = _lib.lib()
     xs, ts, ss, acts_all, p, seed = saved
     R, H = dskip.shape
     dev = dskip.device
@@ -407,9 +375,8 @@ def _wn_bwd_unfused(rc, wn, saved, dskip, want_dcond=False, cond_per_row=False):
             grads.update(conv_param_grads(rs, acts, dskip, R))
         if not fused:
             dpre = torch.empty(R, 2 * H, dtype=torch.bfloat16, device=dev)
-            _lib.check(L.gt_gate_bwd(_lib.ptr(dacts), dacts.stride(0), _lib.ptr(ts[i]), _lib.ptr(ss[i]), ts[i].stride(0),
-                                     _lib.ptr(dpre), 2 * H, _lib.ptr(dpre_c), R, H, float(p), int(seed + i),
-                                     _lib.ptr(seed_word(dev)) if p > 0 else None, _st(dev)), "gt_gate_bwd")
+            call.gt_gate_bwd(dacts, dacts.stride(0), ts[i], ss[i], ts[i].stride(0), dpre, 2 * H, dpre_c, R, H, float(p), int(seed + i),
+                             seed_word(dev) if p > 0 else None, _st(dev))
         grads.update(conv_param_grads(wn.in_layers[i], xs[i], dpre, R))
         if want_dcond:
             _dcond_store(rc, dcond, i, H, dpre_c if dpre_c is not None else dpre, cond_per_row)
@@ -424,12 +391,10 @@ def contour_rows(rc, c, B, T):
     for one channel, on the squeezed rows context rc (T = un-squeezed frames covered, even)."""
     if c is None:
         return None
-    L = _lib.lib()
     cc = c.detach().float().reshape(B, 1, -1)[:, :, :T].contiguous()
     assert cc.shape[2] == T, "pitch / energy must cover the mel frames"
     rows = torch.empty(rc.R, 2, dtype=torch.float32, device=cc.device)
-    _lib.check(L.gt_squeeze_rows_f32(_lib.ptr(cc), _lib.ptr(rows), _lib.ptr(rc.lengths), B, 1, T, rc.Tp, _lib.ptr(rc.row0),
-                                     _st(cc.device)), "gt_squeeze_rows_f32")
+    call.gt_squeeze_rows_f32(cc, rows, rc.lengths, B, 1, T, rc.Tp, rc.row0, _st(cc.device))
     return rows
 
 
@@ -458,7 +423,6 @@ def prosody_chain(cb, econd, pcond):
 def coupling_fwd(rc, cb, x, x0_bf16, cond, logdet, train, seed, econd=None, pcond=None):
     """attentions.CouplingBlock.forward on rows.  x [R,C] fp32, x0_bf16 = bf16(x[:, :C/2]).
     econd / pcond: [R, 2*H*n] fp32 per-frame conditioning of wn_energy / wn_pitch (cond_layer1 output, squeezed)."""
-    L = _lib.lib()
     dev = x.device
     R, C = x.shape
     h0 = conv_rows(x0_bf16, cb.start.pc, rc, bias=cb.start.bias, mask=True)
@@ -471,14 +435,12 @@ def coupling_fwd(rc, cb, x, x0_bf16, cond, logdet, train, seed, econd=None, pcon
         wn_saved = (wn_saved, pros_saved)
     out = conv_rows(wn_out, cb.end.pc, rc, bias=cb.end.bias, out_f32=True)      # [R,C] = [m | logs]
     z = torch.empty_like(x)
-    _lib.check(L.gt_coupling_fwd(_lib.ptr(out), _lib.ptr(x), _lib.ptr(z), _lib.ptr(rc.rowmask), _lib.ptr(logdet),
-                                 rc.B, R, C, rc.Tp, _lib.ptr(rc.row0), int(cb.sigmoid_scale), _st(dev)), "gt_coupling_fwd")
+    call.gt_coupling_fwd(out, x, z, rc.rowmask, logdet, rc.B, R, C, rc.Tp, rc.row0, int(cb.sigmoid_scale), _st(dev))
     return z, (x, x0_bf16, h0, wn_out, wn_saved, out)
 
 
 def coupling_bwd(rc, cb, saved, dz, dlogdet, want_dcond=False, econd=False, pcond=False):
     """econd / pcond: whether wn_energy / wn_pitch ran in the forward; returns (dx, grads, dcond, [d econd, d pcond])."""
-    L = _lib.lib()
     x, x0_bf16, h0, wn_out, wn_saved, out = saved
     chain = prosody_chain(cb, econd or None, pcond or None)
     pros_saved = []
@@ -488,9 +450,7 @@ def coupling_bwd(rc, cb, saved, dz, dlogdet, want_dcond=False, econd=False, pcon
     R, C = x.shape
     dx = torch.empty_like(x)
     dout = torch.empty(R, C, dtype=torch.bfloat16, device=dev)
-    _lib.check(L.gt_coupling_bwd(_lib.ptr(out), _lib.ptr(x), _lib.ptr(dz), _lib.ptr(dlogdet), _lib.ptr(rc.rowmask),
-                                 _lib.ptr(dx), _lib.ptr(dout), rc.B, R, C, rc.Tp, _lib.ptr(rc.row0), int(cb.sigmoid_scale), _st(dev)),
-               "gt_coupling_bwd")
+    call.gt_coupling_bwd(out, x, dz, dlogdet, rc.rowmask, dx, dout, rc.B, R, C, rc.Tp, rc.row0, int(cb.sigmoid_scale), _st(dev))
     grads = conv_param_grads(cb.end, wn_out, dout, R)
     dskip = conv_rows(dout, cb.end.pc, rc, dgrad=True, mask=True)                # d(wn out) * mask = d skip
     dpros = {}
@@ -558,8 +518,7 @@ def flow_scalars_all(dec):
         lp, wp = _ptr_table(dec)
         C = dec.flows[0].channels
         scal = torch.empty(nb, 18, dtype=torch.float32, device=lp.device)
-        _lib.check(_lib.lib().gt_flow_scalars_multi(_lib.ptr(lp), _lib.ptr(wp), C, _lib.ptr(scal), nb, _st(lp.device)),
-                   "gt_flow_scalars_multi")
+        call.gt_flow_scalars_multi(lp, wp, C, scal, nb, _st(lp.device))
         return scal, Ws
     Ws = [w.contiguous() for w in Ws]
     return torch.stack([flow_scalars(l, w) for l, w in zip(lgs, Ws)]), Ws
@@ -591,7 +550,6 @@ def decoder_fwd_fused(rc, dec, rows, conds, logdet, train, seed, y_bct=None, z_b
     conds[b]: [B, 2*H*n] or None.  Returns (z rows, per-block saved state).
     y_bct / z_bct ([B, C/2, T] fp32, T even, z_bct pre-zeroed): the decoder's input / output at the public boundary — the first
     launch then squeezes (rows = None) and the last one unsqueezes (the returned z rows are None)."""
-    L = _lib.lib()
     dev = rc.rowmask.device
     R, C = rc.R, 2 * dec.in_channels
     H, nb, n = dec.hidden_channels, dec.n_blocks, dec.n_layers
@@ -633,13 +591,11 @@ def decoder_fwd_fused(rc, dec, rows, conds, logdet, train, seed, y_bct=None, z_b
                 kw["pf_ptr"], kw["pf_bytes"] = _prefetch_list(cb.wn, "fwd")
             blocks.append(st)
         args = _lib.fill_args(_lib.BoundaryFwdArgs, **kw)
-        import ctypes
         if BOUNDARY_TRACE is not None:
             BOUNDARY_TRACE.append(("gt_wn_boundary_fwd", args, kw))
         _ev = KERNEL_TIMER.start("wn_boundary_fwd")
-        rcode = L.gt_wn_boundary_fwd(ctypes.byref(args), _st(dev))
+        call.gt_wn_boundary_fwd(args, _st(dev))
         KERNEL_TIMER.stop(_ev)
-        _lib.check(rcode, "gt_wn_boundary_fwd")
         if b < nb:
             # the block's WaveNets: wn (speaker vector) [-> wn_energy -> wn_pitch (affine per-frame conditioning)]; between two of them
             # only the skip GEMM + mask (one launch); the last one's gated activations go straight into the next boundary launch
@@ -660,8 +616,6 @@ def decoder_bwd_fused(rc, dec, blocks, drows, dlogdet, has_cond, dz_bct=None, dx
     of the decoder's output rows; returns (d input rows [R, C], {param: grad}, [dcond per block]).
     dz_bct / dx_bct ([B, C/2, T] fp32, T even, dx_bct pre-zeroed): the gradients at the public boundary — the first launch then
     squeezes dz (drows = None), the last one unsqueezes the input gradient (returned rows are None)."""
-    import ctypes
-    L = _lib.lib()
     dev = rc.rowmask.device
     R, C = rc.R, 2 * dec.in_channels
     H, nb, n = dec.hidden_channels, dec.n_blocks, dec.n_layers
@@ -670,7 +624,7 @@ def decoder_bwd_fused(rc, dec, blocks, drows, dlogdet, has_cond, dz_bct=None, dx
     grads, dconds = {}, [None] * nb
     # ActNorm / InvConvNear parameter gradients: one row of partial sums per workgroup and launch, added up by ONE launch after the
     # pass (gt_boundary_param_reduce) — as atomics, 152 workgroups on the same 336 addresses cost ~10 us of every 33 us launch
-    n_wg, PG = (R + 63) // 64, L.gt_boundary_param_partials()
+    n_wg, PG = (R + 63) // 64, call.gt_boundary_param_partials()
     pg = torch.empty(nb, n_wg * PG, **f32)
     pg_dst = []
     dx_prev = None                                         # [d z0 | d y1] of the block whose WaveNet backward runs next
@@ -716,13 +670,12 @@ def decoder_bwd_fused(rc, dec, blocks, drows, dlogdet, has_cond, dz_bct=None, dx
         if BOUNDARY_TRACE is not None:
             BOUNDARY_TRACE.append(("gt_wn_boundary_bwd", args, kw))
         _ev = KERNEL_TIMER.start("wn_boundary_bwd")
-        rcode = L.gt_wn_boundary_bwd(ctypes.byref(args), _st(dev))
+        call.gt_wn_boundary_bwd(args, _st(dev))
         KERNEL_TIMER.stop(_ev)
-        _lib.check(rcode, "gt_wn_boundary_bwd")
         if b == 0:
             pg_dst.sort(key=lambda t: t[0])
             tab = _grad_ptr_table(dec, [t for _, *ts in pg_dst for t in ts])
-            _lib.check(L.gt_boundary_param_reduce(_lib.ptr(pg), n_wg, nb, _lib.ptr(tab), _st(dev)), "gt_boundary_param_reduce")
+            call.gt_boundary_param_reduce(pg, n_wg, nb, tab, _st(dev))
             return dx_out, grads, dconds
         # block b-1: end conv's parameter gradients, the WaveNet's backward, then the start conv's
         cbp, svp = dec.flows[3 * (b - 1) + 2], blocks[b - 1]
@@ -751,7 +704,6 @@ def decoder_bwd_fused(rc, dec, blocks, drows, dlogdet, has_cond, dz_bct=None, dx
 def actnorm_invconv_rev(rc, y, logs, bias, W, want_x0=True, scal=None):
     """InvConvNear^-1 then ActNorm^-1 on rows (modules.py:647-652, 592-594).  y: [R,C] fp32 -> x, bf16(x[:, :C/2]).
     scal: the pair's cached flow scalars (FlowSpecDecoder.store_inverse); computed here when None."""
-    L = _lib.lib()
     dev = y.device
     R, C = y.shape
     x = torch.empty_like(y)
@@ -760,15 +712,13 @@ def actnorm_invconv_rev(rc, y, logs, bias, W, want_x0=True, scal=None):
     bs = bias.detach().reshape(-1).contiguous()
     if scal is None:
         scal = flow_scalars(logs, W)
-    _lib.check(L.gt_actnorm_invconv_rev(_lib.ptr(y), _lib.ptr(x), _lib.ptr(x0), C // 2, _lib.ptr(lg), _lib.ptr(bs), _lib.ptr(scal),
-                                        _lib.ptr(rc.rowmask), R, C, _st(dev)), "gt_actnorm_invconv_rev")
+    call.gt_actnorm_invconv_rev(y, x, x0, C // 2, lg, bs, scal, rc.rowmask, R, C, _st(dev))
     return x, x0
 
 
 def coupling_rev(rc, cb, z, z0_bf16, cond, econd=None, pcond=None):
     """attentions.CouplingBlock.forward with reverse=True on rows: the same start / WN / end GEMMs as the forward
     (evaluation mode), then x1 = (z1 - m) * exp(-logs) * mask."""
-    L = _lib.lib()
     dev = z.device
     R, C = z.shape
     h0 = conv_rows(z0_bf16, cb.start.pc, rc, bias=cb.start.bias, mask=True)
@@ -777,8 +727,7 @@ def coupling_rev(rc, cb, z, z0_bf16, cond, econd=None, pcond=None):
         wn_out, _ = wn_fwd(rc, wnp, wn_out, c, False, 0, cond_per_row=True)
     out = conv_rows(wn_out, cb.end.pc, rc, bias=cb.end.bias, out_f32=True)
     x = torch.empty_like(z)
-    _lib.check(L.gt_coupling_rev(_lib.ptr(out), _lib.ptr(z), _lib.ptr(x), _lib.ptr(rc.rowmask), R, C, int(cb.sigmoid_scale),
-                                 _st(dev)), "gt_coupling_rev")
+    call.gt_coupling_rev(out, z, x, rc.rowmask, R, C, int(cb.sigmoid_scale), _st(dev))
     return x
 
 
@@ -792,8 +741,6 @@ def decoder_rev_fused(rc, dec, rows, conds, z_bct=None, x_bct=None, esig=None, e
     the boundary kernel sits behind the last one, a skip GEMM (conv_rows) between two of them; the affine-conditioned ones run the
     saving form of the WaveNet kernel (wn_fwd).  The flow scalars are
     FlowSpecDecoder.store_inverse's cache when there is one."""
-    import ctypes
-    L = _lib.lib()
     dev = rc.rowmask.device
     R, C = rc.R, 2 * dec.in_channels
     H, nb, n = dec.hidden_channels, dec.n_blocks, dec.n_layers
@@ -831,9 +778,8 @@ def decoder_rev_fused(rc, dec, rows, conds, z_bct=None, x_bct=None, esig=None, e
         if BOUNDARY_TRACE is not None:
             BOUNDARY_TRACE.append(("gt_wn_boundary_rev", args, kw))
         _ev = KERNEL_TIMER.start("wn_boundary_rev")
-        rcode = L.gt_wn_boundary_rev(ctypes.byref(args), _st(dev))
+        call.gt_wn_boundary_rev(args, _st(dev))
         KERNEL_TIMER.stop(_ev)
-        _lib.check(rcode, "gt_wn_boundary_rev")
         state = x
         if k < nb:
             chain = block_chain(dec.flows[3 * bh + 2], conds[bh], esig, None if eaff is None else eaff[bh], psig, None if paff is None else paff[bh])

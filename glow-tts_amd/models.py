@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 from . import _lib, flow_impl, wgrad
+from ._lib import call
 from .attentions import CouplingBlock, _wn_cond_all
 from .modules import ActNorm, InvConvNear, _RowsFn, _mask_lengths, prepare_all
 from . import ops
@@ -170,7 +171,6 @@ class _DecoderRunner:
         return conds, eaff, paff
 
     def forward(self, x, *rest):
-        L = _lib.lib()
         dec = self.dec
         nb = dec.n_blocks
         conds, eaff, paff = self._split_inputs(rest)
@@ -196,7 +196,7 @@ class _DecoderRunner:
             _, blocks = flow_impl.decoder_fwd_fused(rc, dec, None, conds, logdet, self.train, self.seed, y_bct=xin, z_bct=z, **pros)
             return (z.to(x.dtype), logdet), (rc, ("fused", blocks), (B, C, T), esig, psig)
         rows = torch.empty(rc.R, 2 * C, dtype=torch.float32, device=dev)
-        _lib.check(L.gt_squeeze_rows_f32(_lib.ptr(xin), _lib.ptr(rows), _lib.ptr(rc.lengths), B, C, T, rc.Tp, _lib.ptr(rc.row0), st), "gt_squeeze_rows_f32")
+        call.gt_squeeze_rows_f32(xin, rows, rc.lengths, B, C, T, rc.Tp, rc.row0, st)
         cur = rows
         if fused:
             cur, blocks = flow_impl.decoder_fwd_fused(rc, dec, rows, conds, logdet, self.train, self.seed, **pros)
@@ -212,12 +212,11 @@ class _DecoderRunner:
                                              pcond=self._cond_rows(psig, None if paff is None else paff[b]))
             saved.append((s1, s2))
         z = torch.empty(B, C, T2 * 2, dtype=torch.float32, device=dev)
-        _lib.check(L.gt_unsqueeze_rows_f32(_lib.ptr(cur), _lib.ptr(z), _lib.ptr(rc.lengths), B, C, T2 * 2, rc.Tp, _lib.ptr(rc.row0), st), "gt_unsqueeze_rows_f32")
+        call.gt_unsqueeze_rows_f32(cur, z, rc.lengths, B, C, T2 * 2, rc.Tp, rc.row0, st)
         return (z.to(x.dtype), logdet), (rc, saved, (B, C, T), esig, psig)
 
     def reverse(self, z, conds, eaff=None, paff=None):
         """z [B, C, T] -> x: flows in reverse order (coupling^-1, InvConvNear^-1, ActNorm^-1 per block)."""
-        L = _lib.lib()
         dec = self.dec
         B, C, T = z.shape
         dev = z.device
@@ -235,12 +234,11 @@ class _DecoderRunner:
             flow_impl.decoder_rev_fused(rc, dec, None, conds, z_bct=zin, x_bct=x, **pros)
             return x.to(z.dtype)
         cur = torch.empty(rc.R, 2 * C, dtype=torch.float32, device=dev)
-        _lib.check(L.gt_squeeze_rows_f32(_lib.ptr(zin), _lib.ptr(cur), _lib.ptr(rc.lengths), B, C, T, rc.Tp, _lib.ptr(rc.row0), st), "gt_squeeze_rows_f32")
+        call.gt_squeeze_rows_f32(zin, cur, rc.lengths, B, C, T, rc.Tp, rc.row0, st)
         return self._rows_to_x(rc, cur, B, C, T2, conds, fused, pros).to(z.dtype)
 
     def _rows_to_x(self, rc, cur, B, C, T2, conds, fused, pros):
         """squeezed latent rows [R, 2C] fp32 -> x [B, C, 2*T2] fp32: the fused pass or the launch sequence, then unsqueeze"""
-        L = _lib.lib()
         dec = self.dec
         dev = cur.device
         st = _lib.current_stream(dev)
@@ -249,7 +247,7 @@ class _DecoderRunner:
             cur = flow_impl.decoder_rev_fused(rc, dec, cur, conds, **pros)
         else:
             x0 = torch.empty(rc.R, C, dtype=torch.bfloat16, device=dev)
-            _lib.check(L.gt_rows_f32_to_bf16(_lib.ptr(cur), 2 * C, _lib.ptr(x0), C, None, rc.R, C, st), "gt_rows_f32_to_bf16")
+            call.gt_rows_f32_to_bf16(cur, 2 * C, x0, C, None, rc.R, C, st)
             for b in reversed(range(dec.n_blocks)):
                 an, ic, cb = dec.flows[3 * b], dec.flows[3 * b + 1], dec.flows[3 * b + 2]
                 cur = flow_impl.coupling_rev(rc, cb, cur, x0, conds[b], econd=self._cond_rows(esig, None if eaff is None else eaff[b]),
@@ -257,7 +255,7 @@ class _DecoderRunner:
                 cur, x0 = flow_impl.actnorm_invconv_rev(rc, cur, an.logs, an.bias, ic.weight, want_x0=b > 0,
                                                         scal=None if dec._inv_cache is None else dec._inv_cache[b])
         x = torch.empty(B, C, T2 * 2, dtype=torch.float32, device=dev)
-        _lib.check(L.gt_unsqueeze_rows_f32(_lib.ptr(cur), _lib.ptr(x), _lib.ptr(rc.lengths), B, C, T2 * 2, rc.Tp, _lib.ptr(rc.row0), st), "gt_unsqueeze_rows_f32")
+        call.gt_unsqueeze_rows_f32(cur, x, rc.lengths, B, C, T2 * 2, rc.Tp, rc.row0, st)
         return x
 
     def reverse_rows(self, rc, rows, conds, eaff=None, paff=None, out=None, esig=None, psig=None):
@@ -281,7 +279,6 @@ class _DecoderRunner:
         return x if out is None else out.copy_(x)
 
     def backward(self, saved_all, dz, dlogdet):
-        L = _lib.lib()
         rc, saved, (B, C, T), esig, psig = saved_all
         dec = self.dec
         nb = dec.n_blocks
@@ -310,7 +307,7 @@ class _DecoderRunner:
             drows.zero_()
         else:
             dzc = dz.float().contiguous()
-            _lib.check(L.gt_squeeze_rows_f32(_lib.ptr(dzc), _lib.ptr(drows), _lib.ptr(rc.lengths), B, C, T2 * 2, rc.Tp, _lib.ptr(rc.row0), st), "gt_squeeze_rows_f32")
+            call.gt_squeeze_rows_f32(dzc, drows, rc.lengths, B, C, T2 * 2, rc.Tp, rc.row0, st)
         dconds = [None] * nb
         cur = drows
         # data-gradient chain now; ALL weight gradients of the decoder go out as one batch when the block ends
@@ -336,10 +333,10 @@ class _DecoderRunner:
                 grads.update(g1)
         dx = torch.zeros(B, C, T, dtype=torch.float32, device=dev) if T != T2 * 2 else torch.empty(B, C, T, dtype=torch.float32, device=dev)
         if T == T2 * 2:
-            _lib.check(L.gt_unsqueeze_rows_f32(_lib.ptr(cur), _lib.ptr(dx), _lib.ptr(rc.lengths), B, C, T, rc.Tp, _lib.ptr(rc.row0), st), "gt_unsqueeze_rows_f32")
+            call.gt_unsqueeze_rows_f32(cur, dx, rc.lengths, B, C, T, rc.Tp, rc.row0, st)
         else:
             tmp = torch.empty(B, C, T2 * 2, dtype=torch.float32, device=dev)
-            _lib.check(L.gt_unsqueeze_rows_f32(_lib.ptr(cur), _lib.ptr(tmp), _lib.ptr(rc.lengths), B, C, T2 * 2, rc.Tp, _lib.ptr(rc.row0), st), "gt_unsqueeze_rows_f32")
+            call.gt_unsqueeze_rows_f32(cur, tmp, rc.lengths, B, C, T2 * 2, rc.Tp, rc.row0, st)
             dx[:, :, :T2 * 2] = tmp
         out = [dx]
         if self.has_cond:

@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from . import _lib, flow_impl
+from ._lib import call
 from .ops import PackSlice, PackedConv, RowsCtx
 
 
@@ -121,14 +122,11 @@ class WNConvP(ConvP):
 
 def _pack_one(pc, v, g):
     """Single-conv packing (tests / tools; training packs everything in one launch through _PackPlan)."""
-    L = _lib.lib()
     v = v.detach().contiguous().float()
     gg = None if g is None else g.detach().reshape(-1).contiguous().float()
     km = getattr(pc, "km", 1)
-    _lib.check(L.gt_pack_conv_weights(_lib.ptr(v), _lib.ptr(gg), _lib.ptr(pc.fwd), _lib.ptr(pc.dgrad), _lib.ptr(pc.inv_norm),
-                                      pc.Cout, pc.Cin, pc.taps, max(pc.Np_f, pc.Cout), max(pc.Kp_f, km * pc.Cin),
-                                      max(pc.Np_d, pc.Cin), max(pc.Kp_d, km * pc.Cout), pc.flags,
-                                      _lib.current_stream(v.device)), "gt_pack_conv_weights")
+    call.gt_pack_conv_weights(v, gg, pc.fwd, pc.dgrad, pc.inv_norm, pc.Cout, pc.Cin, pc.taps, max(pc.Np_f, pc.Cout), max(pc.Kp_f, km * pc.Cin),
+                              max(pc.Np_d, pc.Cin), max(pc.Kp_d, km * pc.Cout), pc.flags, _lib.current_stream(v.device))
 
 
 def _pack_key(entry):
@@ -143,7 +141,6 @@ class _PackPlan:
     The descriptor table lives on the device and is rebuilt only when a parameter's storage moves."""
 
     def __init__(self, module):
-        import ctypes
         entries = []                                     # (v, g, PackedConv)
         for m in module.modules():
             if isinstance(m, ConvP):
@@ -192,8 +189,7 @@ class _PackPlan:
             return
         dev = self.keep[0][0].device
         for table, n, rows, group8 in self.tables:
-            _lib.check(_lib.lib().gt_pack_conv_weights_multi(_lib.ptr(table), n, rows, group8, _lib.current_stream(dev)),
-                       "gt_pack_conv_weights_multi")
+            call.gt_pack_conv_weights_multi(table, n, rows, group8, _lib.current_stream(dev))
 
 
 _RETIRED_PLANS = []

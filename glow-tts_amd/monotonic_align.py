@@ -7,6 +7,7 @@ called through the C-ABI.  No device->host round trip, no copies of the lattice.
 import torch
 
 from . import _lib
+from ._lib import call
 
 _DT = {torch.float32: _lib.GT_DT_F32, torch.int32: _lib.GT_DT_I32, torch.float16: _lib.GT_DT_F16,
        torch.bfloat16: _lib.GT_DT_BF16, torch.uint8: _lib.GT_DT_U8}
@@ -33,7 +34,6 @@ def maximum_path_lengths(value, t_x, t_y, mask=None, out_dtype=None, want_durati
     Returns MASResult; ``path`` has dtype ``out_dtype`` (default value.dtype).
     """
     _lib.require_cuda(value, t_x, t_y, mask)
-    L = _lib.lib()
     if value.dim() != 3:
         raise ValueError("value must be [b, t_x, t_y]")
     out_dtype = out_dtype or value.dtype
@@ -59,16 +59,16 @@ def maximum_path_lengths(value, t_x, t_y, mask=None, out_dtype=None, want_durati
     status = torch.zeros((1,), dtype=torch.int32, device=v.device) if validate else None
     ws = None
     if B and T_x and T_y:
-        ws_bytes = L.gt_mas_workspace_bytes(B, T_x, T_y)
+        ws_bytes = call.gt_mas_workspace_bytes(B, T_x, T_y)
         ws = torch.empty((ws_bytes // 4,), dtype=torch.int32, device=v.device)
-        rc = L.gt_mas_f32(_lib.ptr(v), _lib.ptr(m), _lib.ptr(t_x), _lib.ptr(t_y), _lib.ptr(path),
-                          _DT[out_dtype], _lib.ptr(dur), _lib.ptr(f2t), B, T_x, T_y,
-                          v.stride(0), v.stride(1), _lib.ptr(ws), ws_bytes, _lib.ptr(status),
-                          _lib.current_stream(v.device))
-        if rc == -2:
+        try:
+            call.gt_mas_f32(v, m, t_x, t_y, path, _DT[out_dtype], dur, f2t, B, T_x, T_y,
+                            v.stride(0), v.stride(1), ws, ws_bytes, status, _lib.current_stream(v.device))
+        except _lib.GtError as e:
+            if e.code != -2:
+                raise
             raise RuntimeError(f"gt_mas_f32: lattice [{T_x},{T_y}] exceeds the kernel's limits "
-                               f"(T_x<=512, LDS {L.gt_mas_lds_bytes(T_x, T_y)} B > 160 KiB)")
-        _lib.check(rc, "gt_mas_f32")
+                               f"(T_x<=512, LDS {call.gt_mas_lds_bytes(T_x, T_y)} B > 160 KiB)") from None
     if validate:
         st = int(status.item())
         if st & 1:
@@ -100,7 +100,6 @@ def result_from_path(path, t_x, t_y):
 def lengths_from_mask(mask):
     """t_x, t_y as reference monotonic_align/__init__.py:18-19 derives them, on the device."""
     _lib.require_cuda(mask)
-    L = _lib.lib()
     m = mask.detach().to(torch.float32)
     if m.stride(2) != 1:
         m = m.contiguous()
@@ -108,9 +107,7 @@ def lengths_from_mask(mask):
     t_x = torch.zeros((B,), dtype=torch.int32, device=m.device)
     t_y = torch.zeros((B,), dtype=torch.int32, device=m.device)
     if B and T_x and T_y:
-        _lib.check(L.gt_mas_lengths_from_mask_f32(_lib.ptr(m), _lib.ptr(t_x), _lib.ptr(t_y), B, T_x, T_y,
-                                                  m.stride(0), m.stride(1), _lib.current_stream(m.device)),
-                   "gt_mas_lengths_from_mask_f32")
+        call.gt_mas_lengths_from_mask_f32(m, t_x, t_y, B, T_x, T_y, m.stride(0), m.stride(1), _lib.current_stream(m.device))
     return t_x, t_y
 
 

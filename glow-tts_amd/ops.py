@@ -6,6 +6,7 @@ row mask); all arithmetic of the hot path happens in libglowtts_hip.so.
 import torch
 
 from . import _lib
+from ._lib import call
 
 HALO = 2  # GT_HALO in include/glowtts_hip.h
 
@@ -116,10 +117,9 @@ class Marks:
         self.names = []
 
     def mark(self, name):
-        from . import _lib
         k = len(self.names)
         self.names.append(name)
-        _lib.check(_lib.lib().gt_mark(self.buf.data_ptr() + 8 * k, _lib.current_stream(self.buf.device)), "gt_mark")
+        call.gt_mark(self.buf.data_ptr() + 8 * k, _lib.current_stream(self.buf.device))
 
     def report(self):
         t = self.buf[:len(self.names)].cpu().tolist()
@@ -170,7 +170,6 @@ def step_head(device, extra=None, bump=True):
         if extra is not None:
             extra.zero_()
         return
-    import ctypes
     key = str(device)
     regions = []
     a = _ARENA.get(key)
@@ -198,7 +197,7 @@ def step_head(device, extra=None, bump=True):
     args.n = len(regions)
     if bump:
         args.seed_word, args.seed_inc = seed_word(device).data_ptr(), 0x632BE5AB
-    _lib.check(_lib.lib().gt_step_zero(ctypes.byref(args), _lib.current_stream(device)), "gt_step_zero")
+    call.gt_step_zero(args, _lib.current_stream(device))
 
 
 def arena_end(device):
@@ -290,7 +289,6 @@ DEFAULT_ROWS = RowsConfig()
 def rows_add_cond(rc, x, xb, cond, want_f32=True, want_bf16=True):
     """(x or xb)[m,:] + cond[utterance(m),:] on the valid rows (gt_rows_add_cond): the speaker vector that
     attentions.py:66-67 / models.py:587-589 broadcast over time.  Returns (fp32 rows or None, bf16 rows or None)."""
-    L = _lib.lib()
     src = x if x is not None else xb
     R, C = src.shape
     dev = src.device
@@ -298,9 +296,8 @@ def rows_add_cond(rc, x, xb, cond, want_f32=True, want_bf16=True):
     assert cond.shape == (rc.B, C), (cond.shape, rc.B, C)
     out = torch.empty(R, C, dtype=torch.float32, device=dev) if want_f32 else None
     outb = torch.empty(R, C, dtype=torch.bfloat16, device=dev) if want_bf16 else None
-    _lib.check(L.gt_rows_add_cond(_lib.ptr(x), 0 if x is None else x.stride(0), _lib.ptr(xb), 0 if xb is None else xb.stride(0),
-                                  _lib.ptr(cond), _lib.ptr(rc.rowmask), _lib.ptr(out), C, _lib.ptr(outb), C,
-                                  rc.B, R, C, rc.Tp, _lib.ptr(rc.row0), _lib.current_stream(dev)), "gt_rows_add_cond")
+    call.gt_rows_add_cond(x, 0 if x is None else x.stride(0), xb, 0 if xb is None else xb.stride(0), cond, rc.rowmask, out, C, outb, C, rc.B, R, C,
+                          rc.Tp, rc.row0, _lib.current_stream(dev))
     return out, outb
 
 
@@ -436,9 +433,8 @@ class RowsCtx:
         host, ev = self._stage(starts, lengths_host)
         self._geo.copy_(host, non_blocking=True)
         ev.record(torch.cuda.current_stream(self.device))
-        _lib.check(_lib.lib().gt_rows_ctx_fill(_lib.ptr(self.row0), _lib.ptr(self.lengths), _lib.ptr(self.rowbatch),
-                                               _lib.ptr(self.rowframe), _lib.ptr(self.rowmask), _lib.ptr(self.rowutt), self.B, self.R,
-                                               _lib.current_stream(self.device)), "gt_rows_ctx_fill")
+        call.gt_rows_ctx_fill(self.row0, self.lengths, self.rowbatch, self.rowframe, self.rowmask, self.rowutt, self.B, self.R,
+                              _lib.current_stream(self.device))
 
     def row_utt(self):
         """int32 [R]: utterance of every row (rows past the last utterance's frames belong to the last one)."""
@@ -447,13 +443,10 @@ class RowsCtx:
     def utt_sum(self, rows, out, accumulate=False, masked=True):
         """out[b, :] (+)= sum of the (valid) rows of utterance b; rows bf16 or fp32 [R, C] (a column slice is fine),
         out fp32 [B, C] (a column slice is fine) — gt_rows_utt_sum."""
-        L = _lib.lib()
         C = rows.shape[1]
         assert rows.stride(1) == 1 and out.stride(1) == 1 and out.shape == (self.B, C) and out.dtype == torch.float32
-        _lib.check(L.gt_rows_utt_sum(_lib.ptr(rows), rows.stride(0), int(rows.dtype == torch.float32),
-                                     _lib.ptr(self.rowmask) if masked else None, _lib.ptr(out), out.stride(0), int(accumulate),
-                                     self.B, self.R, C, self.Tp, _lib.ptr(self.row0), _lib.current_stream(rows.device)),
-                   "gt_rows_utt_sum")
+        call.gt_rows_utt_sum(rows, rows.stride(0), int(rows.dtype == torch.float32), self.rowmask if masked else None, out, out.stride(0),
+                             int(accumulate), self.B, self.R, C, self.Tp, self.row0, _lib.current_stream(rows.device))
         return out
 
     @staticmethod
@@ -488,9 +481,8 @@ class RowsCtx:
         if x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and dtype in (torch.float32, torch.bfloat16):
             xc = x.contiguous()
             out = torch.empty(self.R, C, device=x.device, dtype=dtype)
-            _lib.check(_lib.lib().gt_rows_from_bct(_lib.ptr(xc), int(xc.dtype == torch.float32), _lib.ptr(out), int(dtype == torch.float32),
-                                                   _lib.ptr(self.row0) if self.ragged else None, B, C, T, self.Tp, self.R,
-                                                   _lib.current_stream(x.device)), "gt_rows_from_bct")
+            call.gt_rows_from_bct(xc, int(xc.dtype == torch.float32), out, int(dtype == torch.float32), self.row0 if self.ragged else None, B, C, T,
+                                  self.Tp, self.R, _lib.current_stream(x.device))
             return out
         if not self.ragged:
             out = torch.zeros(self.B, self.Tp, C, device=x.device, dtype=dtype)
@@ -509,9 +501,8 @@ class RowsCtx:
         if xr.is_cuda and xr.dtype in (torch.float32, torch.bfloat16) and dtype in (torch.float32, torch.bfloat16) and self.ragged:
             rows = xr.contiguous()
             out = torch.empty(self.B, C, self.T, device=xr.device, dtype=dtype)
-            _lib.check(_lib.lib().gt_bct_from_rows(_lib.ptr(rows), int(rows.dtype == torch.float32), _lib.ptr(out), int(dtype == torch.float32),
-                                                   _lib.ptr(self.lengths), _lib.ptr(self.row0), self.B, C, self.T, self.Tp, self.R,
-                                                   _lib.current_stream(xr.device)), "gt_bct_from_rows")
+            call.gt_bct_from_rows(rows, int(rows.dtype == torch.float32), out, int(dtype == torch.float32), self.lengths, self.row0, self.B, C,
+                                  self.T, self.Tp, self.R, _lib.current_stream(xr.device))
             return out
         if not self.ragged:
             x = xr.reshape(self.B, self.Tp, C)[:, HALO:HALO + self.T].transpose(1, 2)
@@ -529,8 +520,7 @@ def length_mask(lengths, T, dtype=torch.float32):
         return (torch.arange(T, device=lengths.device)[None, :] < lengths[:, None]).unsqueeze(1).to(dtype)
     out = torch.empty(B, 1, T, dtype=torch.float32, device=lengths.device)
     ln = lengths if lengths.dtype in (torch.int32, torch.int64) else lengths.long()
-    _lib.check(_lib.lib().gt_length_mask(_lib.ptr(ln.contiguous()), int(ln.dtype == torch.int64), _lib.ptr(out), B, T,
-                                         _lib.current_stream(lengths.device)), "gt_length_mask")
+    call.gt_length_mask(ln.contiguous(), int(ln.dtype == torch.int64), out, B, T, _lib.current_stream(lengths.device))
     return out
 
 
@@ -624,14 +614,11 @@ class PackedConv:
 
     def pack(self, v, g=None):
         """v: [Cout, Cin, taps] fp32 (weight_v or plain weight), g: [Cout,1,1] or None."""
-        L = _lib.lib()
         v = v.detach().contiguous().float()
         assert tuple(v.shape) == (self.Cout, self.Cin, self.taps), (v.shape, self.Cout, self.Cin, self.taps)
         gg = None if g is None else g.detach().reshape(-1).contiguous().float()
-        _lib.check(L.gt_pack_conv_weights(_lib.ptr(v), _lib.ptr(gg), _lib.ptr(self.fwd), _lib.ptr(self.dgrad),
-                                          _lib.ptr(self.inv_norm), self.Cout, self.Cin, self.taps,
-                                          self.Np_f, self.Kp_f, self.Np_d, self.Kp_d, self.flags,
-                                          _lib.current_stream(v.device)), "gt_pack_conv_weights")
+        call.gt_pack_conv_weights(v, gg, self.fwd, self.dgrad, self.inv_norm, self.Cout, self.Cin, self.taps, self.Np_f, self.Kp_f, self.Np_d,
+                                  self.Kp_d, self.flags, _lib.current_stream(v.device))
         return self
 
 
@@ -641,7 +628,6 @@ def conv_rows(x, pc, ctx, *, dgrad=False, bias=None, cond=None, mask=False, out=
     """Y = epilogue(conv(x)) in the rows layout via gt_conv_gemm_bf16.  x: [R, >=Cin] bf16.
     `out`/`addend` may be column-slices of wider row buffers (row stride taken from .stride(0)).
     tile: _lib.GT_TILE_* (0 = the library's choice; tests force every variant)."""
-    L = _lib.lib()
     assert x.dtype == torch.bfloat16 and x.stride(1) == 1
     R = x.shape[0] if R is None else R
     km = getattr(pc, "km", 1)                       # bf16x3 split images: x is [hi | hi | lo], three times as wide
@@ -659,16 +645,10 @@ def conv_rows(x, pc, ctx, *, dgrad=False, bias=None, cond=None, mask=False, out=
             gate_t = torch.empty(R, n_out, device=x.device, dtype=torch.bfloat16)
             gate_s = torch.empty(R, n_out, device=x.device, dtype=torch.bfloat16)
     _ev = KERNEL_TIMER.start(tag)
-    rc = L.gt_conv_gemm_bf16(_lib.ptr(x), x.stride(0), _lib.ptr(W), _lib.ptr(bias),
-                             _lib.ptr(cond), 0 if cond is None else cond.stride(0),
-                             _lib.ptr(ctx.rowmask) if mask else None,
-                             _lib.ptr(out), out.stride(0), int(out_f32),
-                             _lib.ptr(addend), 0 if addend is None else addend.stride(0),
-                             _lib.ptr(gate_t), _lib.ptr(gate_s), 0 if gate_t is None else gate_t.stride(0),
-                             R, N, Cin, pc.taps, ctx.Tp, Np, Kp, int(relu), int(gate), float(drop_p), int(seed),
-                             _lib.ptr(seed_word(x.device)) if (drop_p > 0 and gate != 3) else None,
-                             _lib.ptr(ctx.row0) if (cond is not None and not cond_per_row) else None,
-                             0 if cond_per_row else ctx.B, int(tile), _lib.current_stream(x.device))
+    call.gt_conv_gemm_bf16(x, x.stride(0), W, bias, cond, 0 if cond is None else cond.stride(0), ctx.rowmask if mask else None, out, out.stride(0),
+                           int(out_f32), addend, 0 if addend is None else addend.stride(0), gate_t, gate_s, 0 if gate_t is None else gate_t.stride(0),
+                           R, N, Cin, pc.taps, ctx.Tp, Np, Kp, int(relu), int(gate), float(drop_p), int(seed),
+                           seed_word(x.device) if (drop_p > 0 and gate != 3) else None, ctx.row0 if (cond is not None and not cond_per_row) else None,
+                           0 if cond_per_row else ctx.B, int(tile), _lib.current_stream(x.device))
     KERNEL_TIMER.stop(_ev)
-    _lib.check(rc, "gt_conv_gemm_bf16")
     return (out, gate_t, gate_s) if gate == 1 else out

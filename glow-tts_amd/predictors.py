@@ -19,6 +19,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops, wgrad
+from ._lib import call
 from .flow_impl import conv_param_grads
 from .modules import ConvP, LayerNorm, _RowsFn, _mask_lengths, prepare_all
 from .ops import RowsCtx, conv_rows, grad_accumulator
@@ -34,7 +35,7 @@ def _bias_grad_f32(conv, dy, grads):
     """bias gradient of a 1x1 conv from the fp32 output-gradient rows (column sums, gt_colsum): the bf16 copy that feeds
     the weight-gradient GEMM would cost the bias ~2^-8 per summand for nothing"""
     db = grad_accumulator(conv.bias)
-    _lib.check(_lib.lib().gt_colsum(_lib.ptr(dy), dy.stride(0), 1, _lib.ptr(db), dy.shape[0], dy.shape[1], _st(dy.device)), "gt_colsum")
+    call.gt_colsum(dy, dy.stride(0), 1, db, dy.shape[0], dy.shape[1], _st(dy.device))
     grads[conv.bias] = db
 
 
@@ -45,8 +46,7 @@ def _split3_rows(x, rc=None):
     x_hi w_hi + x_hi w_lo + x_lo w_hi on the bf16 MFMA GEMM — three passes of a tiny GEMM instead of an fp32 kernel."""
     R, C = x.shape
     out = torch.empty(R, 3 * C, dtype=torch.bfloat16, device=x.device)
-    _lib.check(_lib.lib().gt_rows_split3(_lib.ptr(x), x.stride(0), int(x.dtype == torch.float32), _lib.ptr(out), 3 * C, None, R, C, _st(x.device)),
-               "gt_rows_split3")
+    call.gt_rows_split3(x, x.stride(0), int(x.dtype == torch.float32), out, 3 * C, None, R, C, _st(x.device))
     return out
 
 
@@ -77,7 +77,6 @@ class DilatedDepthSeparableConv(nn.Module):
 
 def dds_fwd(rc, dds, x, train, seed, want_bf16=False):
     """x: fp32 rows [R, C] (masked; the `+ g` of modules.py:724-725 already applied).  -> (out fp32, out bf16 | None, saved)"""
-    L = _lib.lib()
     dev = x.device
     R, C = x.shape
     utt = rc.row_utt()
@@ -87,15 +86,13 @@ def dds_fwd(rc, dds, x, train, seed, want_bf16=False):
     for i in range(dds.num_layers):
         sep, n1, c1, n2 = dds.convs_sep[i], dds.norms_1[i], dds.convs_1x1[i], dds.norms_2[i]
         a1 = torch.empty(R, 3 * C, dtype=torch.bfloat16, device=dev)              # bf16x3: [hi | hi | lo]
-        _lib.check(L.gt_dds_sep_fwd(_lib.ptr(x), x.stride(0), _lib.ptr(sep.weight), _lib.ptr(sep.bias), _lib.ptr(n1.gamma), _lib.ptr(n1.beta),
-                                    _lib.ptr(utt), _lib.ptr(rc.rowmask), _lib.ptr(a1), 3 * C, R, C, dds.kernel_size ** i, LN_EPS, _st(dev)),
-                   "gt_dds_sep_fwd")
+        call.gt_dds_sep_fwd(x, x.stride(0), sep.weight, sep.bias, n1.gamma, n1.beta, utt, rc.rowmask, a1, 3 * C, R, C, dds.kernel_size ** i, LN_EPS,
+                            _st(dev))
         h2 = conv_rows(a1, c1.pc, rc, bias=c1.bias, out_f32=True)
         out = torch.empty(R, C, dtype=torch.float32, device=dev)
         last = i == dds.num_layers - 1
-        _lib.check(L.gt_dds_out_fwd(_lib.ptr(h2), _lib.ptr(x), x.stride(0), _lib.ptr(n2.gamma), _lib.ptr(n2.beta), _lib.ptr(rc.rowmask),
-                                    _lib.ptr(out), None, R, C, LN_EPS, float(p), int(seed + i),
-                                    _lib.ptr(ops.seed_word(dev)) if p > 0 else None, _st(dev)), "gt_dds_out_fwd")
+        call.gt_dds_out_fwd(h2, x, x.stride(0), n2.gamma, n2.beta, rc.rowmask, out, None, R, C, LN_EPS, float(p), int(seed + i),
+                            ops.seed_word(dev) if p > 0 else None, _st(dev))
         saved.append((x, a1, h2))
         x = out
     if want_bf16:
@@ -105,7 +102,6 @@ def dds_fwd(rc, dds, x, train, seed, want_bf16=False):
 
 def dds_bwd(rc, dds, saved_all, dy, grads):
     """dy: fp32 rows, gradient at dds_fwd's output -> gradient at its input; parameter gradients into `grads`."""
-    L = _lib.lib()
     saved, p, seed = saved_all
     dev = dy.device
     R, C = dy.shape
@@ -114,7 +110,7 @@ def dds_bwd(rc, dds, saved_all, dy, grads):
     # and ONE launch adds them up when the queue is flushed; each of them used to end in 384 - 768 same-address atomics per workgroup
     # (556 workgroups at cfg 5's 17.8 k frame rows: 32 - 65 us per launch, ~180 of them per step)
     q = wgrad.active()
-    n_part = L.gt_dds_bwd_partial_rows(R) if q is not None else 0
+    n_part = call.gt_dds_bwd_partial_rows(R) if q is not None else 0
 
     def part(width):
         return torch.empty(n_part, width, dtype=torch.float32, device=dev) if q is not None else None
@@ -125,9 +121,8 @@ def dds_bwd(rc, dds, saved_all, dy, grads):
         dg2, db2 = grad_accumulator(n2.gamma), grad_accumulator(n2.beta)
         dh2 = torch.empty(R, 3 * C, dtype=torch.bfloat16, device=dev)             # bf16x3
         pt = part(2 * C)
-        _lib.check(L.gt_dds_out_bwd(_lib.ptr(h2), _lib.ptr(dy), _lib.ptr(n2.gamma), _lib.ptr(n2.beta), _lib.ptr(rc.rowmask), _lib.ptr(dh2),
-                                    _lib.ptr(dg2), _lib.ptr(db2), _lib.ptr(pt), R, C, LN_EPS, float(p), int(seed + i),
-                                    _lib.ptr(ops.seed_word(dev)) if p > 0 else None, _st(dev)), "gt_dds_out_bwd")
+        call.gt_dds_out_bwd(h2, dy, n2.gamma, n2.beta, rc.rowmask, dh2, dg2, db2, pt, R, C, LN_EPS, float(p), int(seed + i),
+                            ops.seed_word(dev) if p > 0 else None, _st(dev))
         if pt is not None:
             q.add_ln(pt, dg2, db2)
         grads[n2.gamma], grads[n2.beta] = dg2, db2
@@ -135,17 +130,14 @@ def dds_bwd(rc, dds, saved_all, dy, grads):
         da1 = conv_rows(dh2, c1.pc, rc, dgrad=True, out_f32=True)
         dg1, db1 = grad_accumulator(n1.gamma), grad_accumulator(n1.beta)
         dh1 = torch.empty(R, C, dtype=torch.float32, device=dev)
-        _lib.check(L.gt_dds_sep_bwd(_lib.ptr(x), x.stride(0), _lib.ptr(sep.weight), _lib.ptr(sep.bias), _lib.ptr(n1.gamma), _lib.ptr(n1.beta),
-                                    _lib.ptr(utt), _lib.ptr(rc.rowmask), _lib.ptr(da1), _lib.ptr(dh1), _lib.ptr(dg1), _lib.ptr(db1),
-                                    _lib.ptr(pt1 := part(2 * C)), R, C, dds.kernel_size ** i, LN_EPS, _st(dev)), "gt_dds_sep_bwd")
+        call.gt_dds_sep_bwd(x, x.stride(0), sep.weight, sep.bias, n1.gamma, n1.beta, utt, rc.rowmask, da1, dh1, dg1, db1, pt1 := part(2 * C), R, C,
+                            dds.kernel_size ** i, LN_EPS, _st(dev))
         if pt1 is not None:
             q.add_ln(pt1, dg1, db1)
         grads[n1.gamma], grads[n1.beta] = dg1, db1
         dw, db = grad_accumulator(sep.weight), grad_accumulator(sep.bias)
         dx = torch.empty(R, C, dtype=torch.float32, device=dev)
-        _lib.check(L.gt_dds_dw_bwd(_lib.ptr(x), x.stride(0), _lib.ptr(dh1), _lib.ptr(dy), _lib.ptr(sep.weight), _lib.ptr(utt),
-                                   _lib.ptr(rc.rowmask), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(pt2 := part(4 * C)), R, C,
-                                   dds.kernel_size ** i, _st(dev)), "gt_dds_dw_bwd")
+        call.gt_dds_dw_bwd(x, x.stride(0), dh1, dy, sep.weight, utt, rc.rowmask, dx, dw, db, pt2 := part(4 * C), R, C, dds.kernel_size ** i, _st(dev))
         if pt2 is not None:
             q.add_ln(pt2, dw, db)
         grads[sep.weight], grads[sep.bias] = dw, db
@@ -196,41 +188,34 @@ class ConvFlow(nn.Module):
 
 def _ea_fwd(rc, ea, z, acc, sign=-1.0, reverse=False):
     out = torch.empty_like(z)
-    _lib.check(_lib.lib().gt_ea_fwd(_lib.ptr(z), _lib.ptr(ea.log_scale), _lib.ptr(ea.translation), _lib.ptr(rc.rowmask), _lib.ptr(rc.row_utt()),
-                                    _lib.ptr(out), _lib.ptr(acc), float(sign), int(reverse), z.shape[0], _st(z.device)), "gt_ea_fwd")
+    call.gt_ea_fwd(z, ea.log_scale, ea.translation, rc.rowmask, rc.row_utt(), out, acc, float(sign), int(reverse), z.shape[0], _st(z.device))
     return out
 
 
 def _ea_bwd(rc, ea, z_in, dz, gacc, grads, sign=-1.0):
     dx = torch.empty_like(dz)
     dls, dtr = grad_accumulator(ea.log_scale), grad_accumulator(ea.translation)
-    _lib.check(_lib.lib().gt_ea_bwd(_lib.ptr(z_in), _lib.ptr(ea.log_scale), _lib.ptr(dz), _lib.ptr(gacc), _lib.ptr(rc.rowmask), _lib.ptr(rc.row_utt()),
-                                    _lib.ptr(dx), _lib.ptr(dls), _lib.ptr(dtr), float(sign), z_in.shape[0], _st(dz.device)), "gt_ea_bwd")
+    call.gt_ea_bwd(z_in, ea.log_scale, dz, gacc, rc.rowmask, rc.row_utt(), dx, dls, dtr, float(sign), z_in.shape[0], _st(dz.device))
     grads[ea.log_scale], grads[ea.translation] = dls, dtr
     return dx
 
 
 def _cf_fwd(rc, cf, z, g1, g2, acc, sign=-1.0):
     """ConvFlow forward + the channel flip that follows it (models.py:314-318).  z [R,2] fp32 rows."""
-    L = _lib.lib()
     dev = z.device
     R = z.shape[0]
     C = cf.hidden_channels
     x0 = torch.empty(R, C, dtype=torch.float32, device=dev)
-    _lib.check(L.gt_convflow_pre_fwd(_lib.ptr(z), 2, _lib.ptr(cf.pre.weight), _lib.ptr(cf.pre.bias), _lib.ptr(g1), _lib.ptr(g2),
-                                     _lib.ptr(rc.rowmask), _lib.ptr(x0), R, C, _st(dev)), "gt_convflow_pre_fwd")
+    call.gt_convflow_pre_fwd(z, 2, cf.pre.weight, cf.pre.bias, g1, g2, rc.rowmask, x0, R, C, _st(dev))
     h, _, sv = dds_fwd(rc, cf.convs, x0, False, 0)
     zo = torch.empty_like(z)
     par = torch.empty(R, 32, dtype=torch.float32, device=dev)
-    _lib.check(L.gt_convflow_spline_fwd(_lib.ptr(h), _lib.ptr(cf.proj.weight), _lib.ptr(cf.proj.bias), _lib.ptr(z), _lib.ptr(rc.rowmask),
-                                        _lib.ptr(rc.row_utt()), _lib.ptr(zo), _lib.ptr(par), _lib.ptr(acc), float(sign), 1, R, C, _st(dev)),
-               "gt_convflow_spline_fwd")
+    call.gt_convflow_spline_fwd(h, cf.proj.weight, cf.proj.bias, z, rc.rowmask, rc.row_utt(), zo, par, acc, float(sign), 1, R, C, _st(dev))
     return zo, (z, sv, h, par)
 
 
 def _cf_bwd(rc, cf, saved, dzo, gacc, dg, grads, sign=-1.0):
     """-> dz_in; dg [R,C] (+)= gradient at the conditioning rows (None: not wanted)"""
-    L = _lib.lib()
     z, sv, h, par = saved
     dev = z.device
     R = z.shape[0]
@@ -239,34 +224,28 @@ def _cf_bwd(rc, cf, saved, dzo, gacc, dg, grads, sign=-1.0):
     dz = torch.empty_like(z)
     dWp, dbp = grad_accumulator(cf.proj.weight), grad_accumulator(cf.proj.bias)
     q = wgrad.active()                               # inside a module's backward: partial rows + the queue's one reduce launch
-    pt = torch.empty(L.gt_convflow_spline_partial_rows(R), L.gt_convflow_spline_partial_width(), dtype=torch.float32, device=dev) \
-        if (q is not None and dWp.numel() + dbp.numel() == L.gt_convflow_spline_partial_width()) else None
-    _lib.check(L.gt_convflow_spline_bwd(_lib.ptr(h), _lib.ptr(cf.proj.weight), _lib.ptr(par), _lib.ptr(z), _lib.ptr(dzo), _lib.ptr(gacc),
-                                        _lib.ptr(rc.rowmask), _lib.ptr(rc.row_utt()), _lib.ptr(dh), _lib.ptr(dWp), _lib.ptr(dbp), _lib.ptr(pt),
-                                        _lib.ptr(dz), float(sign), 1, R, C, _st(dev)), "gt_convflow_spline_bwd")
+    pt = torch.empty(call.gt_convflow_spline_partial_rows(R), call.gt_convflow_spline_partial_width(), dtype=torch.float32, device=dev) \
+        if (q is not None and dWp.numel() + dbp.numel() == call.gt_convflow_spline_partial_width()) else None
+    call.gt_convflow_spline_bwd(h, cf.proj.weight, par, z, dzo, gacc, rc.rowmask, rc.row_utt(), dh, dWp, dbp, pt, dz, float(sign), 1, R, C, _st(dev))
     if pt is not None:
         q.add_ln(pt, dWp, dbp)
     grads[cf.proj.weight], grads[cf.proj.bias] = dWp, dbp
     dx0 = dds_bwd(rc, cf.convs, sv, dh, grads)
     dwp, dbpre = grad_accumulator(cf.pre.weight), grad_accumulator(cf.pre.bias)
-    _lib.check(L.gt_convflow_pre_bwd(_lib.ptr(dx0), _lib.ptr(z), 2, _lib.ptr(cf.pre.weight), _lib.ptr(rc.rowmask), _lib.ptr(dwp), _lib.ptr(dbpre),
-                                     _lib.ptr(dz), 2, _lib.ptr(dg), R, C, _st(dev)), "gt_convflow_pre_bwd")
+    call.gt_convflow_pre_bwd(dx0, z, 2, cf.pre.weight, rc.rowmask, dwp, dbpre, dz, 2, dg, R, C, _st(dev))
     grads[cf.pre.weight], grads[cf.pre.bias] = dwp, dbpre
     return dz
 
 
 def _cf_rev(rc, cf, z, g1):
     """ConvFlow.forward(reverse=True) (modules.py:805-819): z [R,2] -> [z0, RQS^-1(z1)] (no flip here)."""
-    L = _lib.lib()
     dev = z.device
     R, C = z.shape[0], cf.hidden_channels
     x0 = torch.empty(R, C, dtype=torch.float32, device=dev)
-    _lib.check(L.gt_convflow_pre_fwd(_lib.ptr(z), 2, _lib.ptr(cf.pre.weight), _lib.ptr(cf.pre.bias), _lib.ptr(g1), None,
-                                     _lib.ptr(rc.rowmask), _lib.ptr(x0), R, C, _st(dev)), "gt_convflow_pre_fwd")
+    call.gt_convflow_pre_fwd(z, 2, cf.pre.weight, cf.pre.bias, g1, None, rc.rowmask, x0, R, C, _st(dev))
     h, _, _ = dds_fwd(rc, cf.convs, x0, False, 0)
     zo = torch.empty_like(z)
-    _lib.check(L.gt_convflow_spline_inv(_lib.ptr(h), _lib.ptr(cf.proj.weight), _lib.ptr(cf.proj.bias), _lib.ptr(z), _lib.ptr(rc.rowmask),
-                                        _lib.ptr(zo), R, C, _st(dev)), "gt_convflow_spline_inv")
+    call.gt_convflow_spline_inv(h, cf.proj.weight, cf.proj.bias, z, rc.rowmask, zo, R, C, _st(dev))
     return zo
 
 
@@ -293,14 +272,12 @@ def flows_bwd(rc, flows, saved, dz, gacc, dg, grads):
 
 
 def _nll_gauss(rc, z, acc):
-    _lib.check(_lib.lib().gt_nll_gauss_fwd(_lib.ptr(z), _lib.ptr(rc.rowmask), _lib.ptr(rc.row_utt()), _lib.ptr(acc), z.shape[0], _st(z.device)),
-               "gt_nll_gauss_fwd")
+    call.gt_nll_gauss_fwd(z, rc.rowmask, rc.row_utt(), acc, z.shape[0], _st(z.device))
 
 
 def _nll_gauss_bwd(rc, z, gacc):
     dz = torch.empty_like(z)
-    _lib.check(_lib.lib().gt_nll_gauss_bwd(_lib.ptr(z), _lib.ptr(gacc), _lib.ptr(rc.rowmask), _lib.ptr(rc.row_utt()), _lib.ptr(dz), z.shape[0],
-                                           _st(z.device)), "gt_nll_gauss_bwd")
+    call.gt_nll_gauss_bwd(z, gacc, rc.rowmask, rc.row_utt(), dz, z.shape[0], _st(z.device))
     return dz
 
 
@@ -412,27 +389,23 @@ class StochasticDurationPredictor(_PredictorBase):
 
     def _nll_fwd(self, rc, xb, w, noise, vec, train, seed):
         """xb bf16 rows [R,C], w fp32 rows [R] (durations), noise fp32 rows [R,2] -> nll [B] (models.py:280-322)"""
-        L = _lib.lib()
         dev = xb.device
         R, C = xb.shape[0], self.filter_channels
         xc, s_c = self._cond_fwd(rc, xb, vec, train, seed)
         hw0 = torch.empty(R, C, dtype=torch.float32, device=dev)
-        _lib.check(L.gt_convflow_pre_fwd(_lib.ptr(w), 1, _lib.ptr(self.post_pre.weight), _lib.ptr(self.post_pre.bias), None, None,
-                                         _lib.ptr(rc.rowmask), _lib.ptr(hw0), R, C, _st(dev)), "gt_convflow_pre_fwd")
+        call.gt_convflow_pre_fwd(w, 1, self.post_pre.weight, self.post_pre.bias, None, None, rc.rowmask, hw0, R, C, _st(dev))
         hw1, hw1b, s_h = dds_fwd(rc, self.post_convs, hw0, train, seed + 8, want_bf16=True)
         h = conv_rows(hw1b, self.post_proj.pc, rc, bias=self.post_proj.bias, mask=True, out_f32=True)
         acc = torch.zeros(rc.B, dtype=torch.float32, device=dev)
         e_q = (noise * rc.rowmask[:, None]).contiguous()
         z_q, s_q = flows_fwd(rc, self.post_flows, e_q, xc, h, acc)
         z = torch.empty_like(z_q)
-        _lib.check(L.gt_sdp_mid_fwd(_lib.ptr(z_q), _lib.ptr(w), _lib.ptr(e_q), _lib.ptr(rc.rowmask), _lib.ptr(rc.row_utt()), _lib.ptr(z),
-                                    _lib.ptr(acc), R, _st(dev)), "gt_sdp_mid_fwd")
+        call.gt_sdp_mid_fwd(z_q, w, e_q, rc.rowmask, rc.row_utt(), z, acc, R, _st(dev))
         z_f, s_f = flows_fwd(rc, self.flows, z, xc, None, acc)
         _nll_gauss(rc, z_f, acc)
         return acc, (s_c, s_h, hw1b, s_q, z_q, w, s_f, z_f)
 
     def _nll_bwd(self, rc, saved, gacc, grads, want_dvec):
-        L = _lib.lib()
         s_c, s_h, hw1b, s_q, z_q, w, s_f, z_f = saved
         dev = z_f.device
         R, C = z_f.shape[0], self.filter_channels
@@ -440,8 +413,7 @@ class StochasticDurationPredictor(_PredictorBase):
         dz = _nll_gauss_bwd(rc, z_f, gacc)
         dz = flows_bwd(rc, self.flows, s_f, dz, gacc, dxc, grads)
         dzq = torch.empty_like(dz)
-        _lib.check(L.gt_sdp_mid_bwd(_lib.ptr(z_q), _lib.ptr(w), _lib.ptr(dz), _lib.ptr(gacc), _lib.ptr(rc.rowmask), _lib.ptr(rc.row_utt()),
-                                    _lib.ptr(dzq), R, _st(dev)), "gt_sdp_mid_bwd")
+        call.gt_sdp_mid_bwd(z_q, w, dz, gacc, rc.rowmask, rc.row_utt(), dzq, R, _st(dev))
         dsum = torch.zeros(R, C, dtype=torch.float32, device=dev)                 # gradient at (xc + h), the posterior's condition
         flows_bwd(rc, self.post_flows, s_q, dzq, gacc, dsum, grads)
         dxc += dsum
@@ -452,8 +424,7 @@ class StochasticDurationPredictor(_PredictorBase):
         dhw1 = conv_rows(dhb, self.post_proj.pc, rc, dgrad=True, out_f32=True, mask=True)
         dhw0 = dds_bwd(rc, self.post_convs, s_h, dhw1, grads)
         dwp, dbp = grad_accumulator(self.post_pre.weight), grad_accumulator(self.post_pre.bias)
-        _lib.check(L.gt_convflow_pre_bwd(_lib.ptr(dhw0), _lib.ptr(w), 1, _lib.ptr(self.post_pre.weight), _lib.ptr(rc.rowmask), _lib.ptr(dwp),
-                                         _lib.ptr(dbp), None, 0, None, R, C, _st(dev)), "gt_convflow_pre_bwd")
+        call.gt_convflow_pre_bwd(dhw0, w, 1, self.post_pre.weight, rc.rowmask, dwp, dbp, None, 0, None, R, C, _st(dev))
         grads[self.post_pre.weight], grads[self.post_pre.bias] = dwp, dbp
         return self._cond_bwd(rc, s_c, dxc, grads, want_dvec)
 

@@ -71,7 +71,7 @@ class CallScalars(NamedTuple):
 
 def _launch(device, name, *args):
     """the C-ABI entry `name` on the current stream of device"""
-    _lib.check(getattr(_lib.lib(), name)(*args, _lib.current_stream(device)), name)
+    getattr(_lib.call, name)(*args, _lib.current_stream(device))
 
 
 class ByValue:
@@ -84,18 +84,18 @@ class ByValue:
         self.scalars, self.keyed, self.device, self.length_scale = scalars, keyed, device, scalars.length_scale
 
     def noise(self, rc, stream_id, which):
-        s, p = self.scalars, _lib.ptr
+        s = self.scalars
         nz = torch.empty(rc.R, 2, dtype=torch.float32, device=self.device)
         scale = float((s.noise_scale, s.noise_scale_w, s.f0_noise_scale, s.energy_noise_scale)[which])
         if self.keyed:
-            _launch(self.device, "gt_randn_keyed", p(nz), p(rc.row0), rc.Tp, p(rc.lengths), rc.B, rc.R, 2, s.seed, stream_id, scale)
+            _launch(self.device, "gt_randn_keyed", nz, rc.row0, rc.Tp, rc.lengths, rc.B, rc.R, 2, s.seed, stream_id, scale)
         else:
-            _launch(self.device, "gt_randn_rows", p(nz), rc.R, 2, s.seed, stream_id, scale)
+            _launch(self.device, "gt_randn_rows", nz, rc.R, 2, s.seed, stream_id, scale)
         return nz
 
     def prior(self, args):
         args.seed, args.noise_scale = self.scalars.seed, float(self.scalars.noise_scale)
-        _launch(self.device, "gt_synth_prior", ctypes.byref(args))
+        _launch(self.device, "gt_synth_prior", args)
 
     def contours(self, *args):
         _launch(self.device, "gt_synth_contours", *args, float(self.scalars.pitch_scale), float(self.scalars.energy_scale))
@@ -110,16 +110,15 @@ class FromBlock:
         self.call, self.device, self.length_scale = call, call.device, call.view(torch.float32)[3]
 
     def noise(self, rc, stream_id, which):
-        p = _lib.ptr
         nz = torch.empty(rc.R, 2, dtype=torch.float32, device=self.device)
-        _launch(self.device, "gt_randn_keyed_call", p(nz), p(rc.row0), rc.Tp, p(rc.lengths), rc.B, rc.R, 2, p(self.call), stream_id, which)
+        _launch(self.device, "gt_randn_keyed_call", nz, rc.row0, rc.Tp, rc.lengths, rc.B, rc.R, 2, self.call, stream_id, which)
         return nz
 
     def prior(self, args):
-        _launch(self.device, "gt_synth_prior_call", ctypes.byref(args), _lib.ptr(self.call))
+        _launch(self.device, "gt_synth_prior_call", args, self.call)
 
     def contours(self, *args):
-        _launch(self.device, "gt_synth_contours_call", *args, _lib.ptr(self.call))
+        _launch(self.device, "gt_synth_contours_call", *args, self.call)
 
 
 def text_stage(gen, ids, x_len, g, l, emo, emo_cartesian, draw):
@@ -145,10 +144,9 @@ def lengths_stage(logw, x_mask, length_scale, x_len, cum, y_len, logw_):
     """durations -> gt_synth_lengths into the caller's cum [B, Tx], y_len [B] and (or None) logw_ [B, 1, Tx] -> dur, x_len as int32.
     exp, length_scale (a float, or a 0-dim device tensor) and ceil stay in torch on [B, Tx] (plumbing): the durations are bit for bit
     those of infer without the front end"""
-    p = _lib.ptr
     dur = torch.ceil(torch.exp(logw) * x_mask * length_scale).squeeze(1).contiguous()
     xl = x_len.to(torch.int32).contiguous()
-    _launch(dur.device, "gt_synth_lengths", p(dur), p(xl), p(cum), p(y_len), p(logw_), *dur.shape)
+    _launch(dur.device, "gt_synth_lengths", dur, xl, cum, y_len, logw_, *dur.shape)
     return dur, xl
 
 
@@ -183,9 +181,9 @@ def prosody_stage(gen, g, rc, xb, rcy, rcf, bufs, source, Ty):
         prow = gen.proj_pitch._reverse_rows(rcf, xf, gen.proj_pitch.cond_vec(g), source.noise(rcf, 2, 2))
     if gen.use_sep:
         erow = gen.proj_energy._reverse_rows(rcf, xf, gen.proj_energy.cond_vec(g), source.noise(rcf, 3, 3))
-    p = _lib.ptr                                                     # for the return tuple and, squeezed, on the decoder's rows: one launch
-    source.contours(p(prow), p(erow), p(rcf.row0), rcf.Tp, p(rcf.lengths), rcf.R, p(rcy.row0), rcy.Tp, p(rcy.lengths), rcy.R, p(bufs["psig"]),
-                    p(bufs["esig"]), p(bufs["pitch"]), p(bufs["energy"]), rcy.B, Ty)
+    # for the return tuple and, squeezed, on the decoder's rows: one launch
+    source.contours(prow, erow, rcf.row0, rcf.Tp, rcf.lengths, rcf.R, rcy.row0, rcy.Tp, rcy.lengths, rcy.R, bufs["psig"], bufs["esig"],
+                    bufs["pitch"], bufs["energy"], rcy.B, Ty)
     return bufs["pitch"], bufs["energy"], dict(pitch_rows=bufs["psig"], energy_rows=bufs["esig"])
 
 
@@ -439,18 +437,18 @@ class Synthesizer:
     @torch.no_grad()
     def _body(self):
         gen, rcy, rcf, src = self.gen, self.rc, self.rcf, self.source
-        p, dev, B, Ty = _lib.ptr, self.device, self.batch, self.max_frames
+        dev, B, Ty = self.device, self.batch, self.max_frames
         gen.rows_cfg.host_lengths.clear()
         # the stochastic duration predictor only under stochastic=True (the constructor)
         g, l, x_m, x_logs, x_mask, rc, xb, logw = text_stage(gen, self.ids, self.x_len, self.g, self.l, self.emo, self.emo_cartesian,
                                                              lambda rcx: src.noise(rcx, 1, 1))
         a = self.aux_static or {}
         dur, xl = lengths_stage(logw, x_mask, src.length_scale, self.x_len, self.cum, self.y_len, a.get("logw_"))
-        _launch(dev, "gt_synth_geometry", p(self.y_len), B, Ty, rcy.R, p(rcy.row0), p(rcy.lengths), p(self.y_len_eff), p(rcy.rowbatch),
-                p(rcy.rowframe), p(rcy.rowmask), p(rcy.rowutt), p(self.status))
+        _launch(dev, "gt_synth_geometry", self.y_len, B, Ty, rcy.R, rcy.row0, rcy.lengths, self.y_len_eff, rcy.rowbatch, rcy.rowframe,
+                rcy.rowmask, rcy.rowutt, self.status)
         if rcf is not None:                                              # behind gt_synth_geometry: ORs bit 2 into the status word
-            _launch(dev, "gt_synth_frame_geometry", p(self.y_len_eff), B, Ty, rcf.R, p(rcf.row0), p(rcf.lengths), p(rcf.rowbatch),
-                    p(rcf.rowframe), p(rcf.rowmask), p(rcf.rowutt), p(self.status))
+            _launch(dev, "gt_synth_frame_geometry", self.y_len_eff, B, Ty, rcf.R, rcf.row0, rcf.lengths, rcf.rowbatch, rcf.rowframe,
+                    rcf.rowmask, rcf.rowutt, self.status)
         bufs = dict(rows=self.rows, z_m=a.get("z_m"), z_logs=a.get("z_logs"), frame2token=self.frame2token, attn=a.get("attn"),
                     pitch=self.pitch_static, energy=self.energy_static, psig=self.psig, esig=self.esig)
         xm, xs = prior_stage(gen, x_m, x_logs, self.cum, xl, self.y_len_eff, rcy, bufs, src, Ty)

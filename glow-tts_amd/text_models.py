@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from . import _lib, encoder_impl, ops
+from ._lib import call
 from . import monotonic_align
 from .attentions import Encoder
 from .modules import ConvP, ConvReluNorm, LayerNorm, _RowsFn, prepare_all
@@ -140,7 +141,6 @@ class _TextEncoderRunner:
         self.last = None
 
     def forward(self, *rest):
-        L = _lib.lib()
         te = self.te
         vec = rest[0] if self.has_cond else None
         lvec = rest[int(self.has_cond)] if self.has_lang else None
@@ -152,14 +152,12 @@ class _TextEncoderRunner:
         x = torch.empty(rc.R, C, dtype=torch.float32, device=dev)
         xb = torch.empty(rc.R, C, dtype=torch.bfloat16, device=dev)
         emb = te.emb.weight.detach()
-        _lib.check(L.gt_embedding_fwd(_lib.ptr(self.ids), _lib.ptr(emb), _lib.ptr(rc.lengths), _lib.ptr(x), _lib.ptr(xb),
-                                      B, T, rc.Tp, _lib.ptr(rc.row0), rc.R, Ce, C, math.sqrt(C), _lib.current_stream(dev)), "gt_embedding_fwd")
+        call.gt_embedding_fwd(self.ids, emb, rc.lengths, x, xb, B, T, rc.Tp, rc.row0, rc.R, Ce, C, math.sqrt(C), _lib.current_stream(dev))
         if lvec is not None:                             # x = cat(emb * sqrt(H), l expanded over time) (models.py:698-699)
             lc = lvec.detach().float().contiguous()
             zero = ops.zeros_small((rc.R, te.lin_channels), torch.float32, dev)
-            _lib.check(L.gt_rows_add_cond(_lib.ptr(zero), te.lin_channels, None, 0, _lib.ptr(lc), _lib.ptr(rc.rowmask),
-                                          x.data_ptr() + 4 * Ce, C, xb.data_ptr() + 2 * Ce, C, B, rc.R, te.lin_channels, rc.Tp,
-                                          _lib.ptr(rc.row0), _lib.current_stream(dev)), "gt_rows_add_cond")
+            call.gt_rows_add_cond(zero, te.lin_channels, None, 0, lc, rc.rowmask, x.data_ptr() + 4 * Ce, C, xb.data_ptr() + 2 * Ce, C, B, rc.R,
+                                  te.lin_channels, rc.Tp, rc.row0, _lib.current_stream(dev))
         s_pre = None
         if te.prenet:
             x, xb, s_pre = encoder_impl.crn_fwd(rc, te.pre, x, xb, self.train, self.seed)
@@ -179,7 +177,6 @@ class _TextEncoderRunner:
         return (xo, x_m, x_logs), (rc, s_pre, s_layers, xb)
 
     def backward(self, saved_all, dxo, dx_m, dx_logs):
-        L = _lib.lib()
         from .flow_impl import conv_param_grads
         from .ops import conv_rows
         rc, s_pre, s_layers, xb_final = saved_all
@@ -217,8 +214,7 @@ class _TextEncoderRunner:
         demb = ops.grad_accumulator(te.emb.weight)
         B, T = self.ids.shape
         Ce = C - te.lin_channels
-        _lib.check(L.gt_embedding_bwd(_lib.ptr(self.ids), _lib.ptr(tot), _lib.ptr(rc.lengths), _lib.ptr(demb), B, T, rc.Tp, _lib.ptr(rc.row0), rc.R, Ce, C,
-                                      math.sqrt(C), _lib.current_stream(dev)), "gt_embedding_bwd")
+        call.gt_embedding_bwd(self.ids, tot, rc.lengths, demb, B, T, rc.Tp, rc.row0, rc.R, Ce, C, math.sqrt(C), _lib.current_stream(dev))
         grads[te.emb.weight] = demb
         dl = []
         if self.has_lang:                                # the language vector was broadcast over time: its gradient is the row sum
@@ -261,7 +257,6 @@ class _LogpMasFn:
 
     @staticmethod
     def run(x_m, x_logs, z, x_lengths, y_lengths, mean_only):
-        L = _lib.lib()
         B, C, Tx = x_m.shape
         Ty = z.shape[2]
         dev = z.device
@@ -269,8 +264,7 @@ class _LogpMasFn:
         xm = x_m.detach().float().contiguous()
         xs = None if mean_only else x_logs.detach().float().contiguous()
         zz = z.detach().float().contiguous()
-        _lib.check(L.gt_logp_f32(_lib.ptr(xm), _lib.ptr(xs), _lib.ptr(zz), _lib.ptr(logp), B, C, Tx, Ty,
-                                 _lib.current_stream(dev)), "gt_logp_f32")
+        call.gt_logp_f32(xm, xs, zz, logp, B, C, Tx, Ty, _lib.current_stream(dev))
         r = monotonic_align.maximum_path_lengths(logp, x_lengths.to(torch.int32), y_lengths.to(torch.int32),
                                                  want_durations=True, want_frame2token=True, keep_workspace=True)
         return logp, r
@@ -281,23 +275,20 @@ class _PriorExpandFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_m, f2t, starts):
-        L = _lib.lib()
         B, C, Tx = x_m.shape
         Ty = f2t.shape[1]
         xm = x_m.detach().float().contiguous()
         z_m = torch.empty(B, C, Ty, dtype=torch.float32, device=x_m.device)
-        _lib.check(L.gt_prior_expand(_lib.ptr(xm), _lib.ptr(f2t), _lib.ptr(z_m), B, C, Tx, Ty, _lib.current_stream(x_m.device)), "gt_prior_expand")
+        call.gt_prior_expand(xm, f2t, z_m, B, C, Tx, Ty, _lib.current_stream(x_m.device))
         ctx.f2t, ctx.shape = f2t, (B, C, Tx, Ty)
         return z_m
 
     @staticmethod
     def backward(ctx, dz_m):
-        L = _lib.lib()
         B, C, Tx, Ty = ctx.shape
         d = dz_m.float().contiguous()
         dx_m = torch.empty(B, C, Tx, dtype=torch.float32, device=d.device)
-        _lib.check(L.gt_prior_expand_bwd(_lib.ptr(d), _lib.ptr(ctx.f2t), _lib.ptr(dx_m), B, C, Tx, Ty, _lib.current_stream(d.device)),
-                   "gt_prior_expand_bwd")
+        call.gt_prior_expand_bwd(d, ctx.f2t, dx_m, B, C, Tx, Ty, _lib.current_stream(d.device))
         return dx_m, None, None
 
 
@@ -306,24 +297,21 @@ class _MleLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, m, logs, logdet, mask):
-        L = _lib.lib()
         dev = z.device
         zc, mc = z.detach().float().contiguous(), m.detach().float().contiguous()
         lc = None if logs is None else logs.detach().float().contiguous()
         acc = torch.empty(2 * 2048, dtype=torch.float32, device=dev)       # GT_MLE_PARTS partial pairs, all written by the kernel
-        _lib.check(L.gt_mle_sums(_lib.ptr(zc), _lib.ptr(mc), _lib.ptr(lc), _lib.ptr(acc), zc.numel(), _lib.current_stream(dev)), "gt_mle_sums")
+        call.gt_mle_sums(zc, mc, lc, acc, zc.numel(), _lib.current_stream(dev))
         # the scalar tail in one launch: loss = (acc[0] + 0.5 acc[1] - sum logdet) / denom + 0.5 log 2pi, denom = C * sum(mask)
         ld = logdet.detach().float().contiguous()
         mk = mask.detach().float().contiguous()
         out = torch.empty(2, dtype=torch.float32, device=dev)
-        _lib.check(L.gt_mle_finish(_lib.ptr(acc), _lib.ptr(ld), _lib.ptr(mk), mk.numel(), ld.numel(), z.shape[1], _lib.ptr(out),
-                                   _lib.current_stream(dev)), "gt_mle_finish")
+        call.gt_mle_finish(acc, ld, mk, mk.numel(), ld.numel(), z.shape[1], out, _lib.current_stream(dev))
         ctx.saved = (zc, mc, lc, out, logdet.shape)
         return out[0]
 
     @staticmethod
     def backward(ctx, g):
-        L = _lib.lib()
         zc, mc, lc, out, ld_shape = ctx.saved
         dev = zc.device
         gs = g.float().reshape(1).contiguous()                   # divided by the denominator (out[1]) inside the kernel
@@ -334,8 +322,7 @@ class _MleLossFn(torch.autograd.Function):
         for d in ld_shape:
             nb *= int(d)
         dlogdet = torch.empty(ld_shape, dtype=torch.float32, device=dev)
-        _lib.check(L.gt_mle_bwd(_lib.ptr(zc), _lib.ptr(mc), _lib.ptr(lc), _lib.ptr(gs), _lib.ptr(dz), _lib.ptr(dm), _lib.ptr(dl),
-                                zc.numel(), out[1:].data_ptr(), _lib.ptr(dlogdet), nb, _lib.current_stream(dev)), "gt_mle_bwd")
+        call.gt_mle_bwd(zc, mc, lc, gs, dz, dm, dl, zc.numel(), out[1:].data_ptr(), dlogdet, nb, _lib.current_stream(dev))
         return dz, dm, dl, dlogdet, None
 
 
@@ -345,26 +332,22 @@ class _DurationLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logw, w, x_lengths):
-        L = _lib.lib()
         B, _, Tx = logw.shape
         lw = logw.detach().float().contiguous()
         wc = w.detach().float().contiguous()
         xl = x_lengths.to(torch.int32).contiguous()
         out = torch.empty(B, dtype=torch.float32, device=lw.device)
-        _lib.check(L.gt_duration_loss_fwd(_lib.ptr(lw), _lib.ptr(wc), _lib.ptr(xl), B, Tx, _lib.ptr(out), _lib.current_stream(lw.device)),
-                   "gt_duration_loss_fwd")
+        call.gt_duration_loss_fwd(lw, wc, xl, B, Tx, out, _lib.current_stream(lw.device))
         ctx.saved = (lw, wc, xl, logw.shape)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        L = _lib.lib()
         lw, wc, xl, shape = ctx.saved
         B, _, Tx = shape
         gc = g.float().contiguous()
         d = torch.empty(shape, dtype=torch.float32, device=lw.device)
-        _lib.check(L.gt_duration_loss_bwd(_lib.ptr(lw), _lib.ptr(wc), _lib.ptr(xl), _lib.ptr(gc), B, Tx, _lib.ptr(d), _lib.current_stream(lw.device)),
-                   "gt_duration_loss_bwd")
+        call.gt_duration_loss_bwd(lw, wc, xl, gc, B, Tx, d, _lib.current_stream(lw.device))
         return d, None, None
 
 
@@ -581,20 +564,17 @@ class FlowGenerator(nn.Module):
         attn = (attn * x_mask.transpose(1, 2) * z_mask).unsqueeze(1)
         frame2token = torch.searchsorted(cum.contiguous(), j[None, :].expand(cum.shape[0], Ty).contiguous(), right=True)
         frame2token = frame2token.clamp_(max=dur.shape[1] - 1).to(torch.int32).contiguous()
-        L = _lib.lib()
         B, C, Tx = x_m.shape
         xm = x_m.float().contiguous()
         z_m = torch.empty(B, C, Ty, dtype=torch.float32, device=x.device)
-        _lib.check(L.gt_prior_expand(_lib.ptr(xm), _lib.ptr(frame2token), _lib.ptr(z_m), B, C, Tx, Ty, _lib.current_stream(x.device)),
-                   "gt_prior_expand")
+        call.gt_prior_expand(xm, frame2token, z_m, B, C, Tx, Ty, _lib.current_stream(x.device))
         z_m = z_m * z_mask
         if self.mean_only:
             z_logs = torch.zeros_like(z_m)
         else:
             xs = x_logs.float().contiguous()
             z_logs = torch.empty_like(z_m)
-            _lib.check(L.gt_prior_expand(_lib.ptr(xs), _lib.ptr(frame2token), _lib.ptr(z_logs), B, C, Tx, Ty, _lib.current_stream(x.device)),
-                       "gt_prior_expand")
+            call.gt_prior_expand(xs, frame2token, z_logs, B, C, Tx, Ty, _lib.current_stream(x.device))
             z_logs = z_logs * z_mask
         logw_ = torch.log(1e-8 + torch.sum(attn.squeeze(1), -1)).unsqueeze(1) * x_mask
         z = (z_m + torch.exp(z_logs) * torch.randn_like(z_m) * noise_scale) * z_mask
@@ -670,10 +650,8 @@ class FlowGenerator(nn.Module):
         """x_feature = x @ attn (models.py:1094) for a hard path: frame rows <- token rows (gt_rows_gather_tokens), bf16"""
         C = xb.shape[1]
         out = torch.empty(rcf.R, C, dtype=torch.bfloat16, device=xb.device)
-        _lib.check(_lib.lib().gt_rows_gather_tokens(_lib.ptr(xb), xb.stride(0), _lib.ptr(frame2token), frame2token.shape[1],
-                                                    _lib.ptr(rcx.row0), rcx.Tp, _lib.ptr(rcf.row_utt()), _lib.ptr(rcf.row0), rcf.Tp,
-                                                    _lib.ptr(rcf.rowmask), _lib.ptr(out), rcf.R, C, _lib.current_stream(xb.device)),
-                   "gt_rows_gather_tokens")
+        call.gt_rows_gather_tokens(xb, xb.stride(0), frame2token, frame2token.shape[1], rcx.row0, rcx.Tp, rcf.row_utt(), rcf.row0, rcf.Tp,
+                                   rcf.rowmask, out, rcf.R, C, _lib.current_stream(xb.device))
         return out
 
     def _predict_logw(self, g, l=None):

@@ -16,6 +16,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, models
+from ._lib import call
 
 BASE_MODEL = dict(hidden_channels=192, filter_channels=768, filter_channels_dp=256, kernel_size=3, p_dropout=0.1,
                   n_blocks_dec=12, n_layers_enc=6, n_heads=2, p_dropout_dec=0.05, dilation_rate=1, kernel_size_dec=5,
@@ -279,9 +280,8 @@ class FlatAdamW:
 
     def _launch(self, s, e):
         dev = self.flat_p.device
-        _lib.check(_lib.lib().gt_adamw_flat(self.flat_p.data_ptr() + 4 * s, self.gb.flat.data_ptr() + 4 * s, self.m.data_ptr() + 4 * s,
-                                            self.v.data_ptr() + 4 * s, e - s, _lib.ptr(self.hyper), _lib.ptr(self.gnorm_sq),
-                                            _lib.current_stream(dev)), "gt_adamw_flat")
+        call.gt_adamw_flat(self.flat_p.data_ptr() + 4 * s, self.gb.flat.data_ptr() + 4 * s, self.m.data_ptr() + 4 * s, self.v.data_ptr() + 4 * s,
+                           e - s, self.hyper, self.gnorm_sq, _lib.current_stream(dev))
 
     def step_early(self, lo, hi):
         """Update floats [lo, hi) NOW, on the current stream, before the rest of the backward has finished: the caller knows that
@@ -358,9 +358,8 @@ def _upload_step_inputs(pairs, ctx_lens):
         staged.append((host, ev))
     args.n_ctx = len(staged)
     if n or staged:
-        import ctypes
         dev = pairs[0][0].device if pairs else ctx_lens[0][0].device
-        _lib.check(_lib.lib().gt_step_inputs(ctypes.byref(args), _lib.current_stream(dev)), "gt_step_inputs")
+        call.gt_step_inputs(args, _lib.current_stream(dev))
         for host, ev in staged:
             ev.record(torch.cuda.current_stream(dev))
 

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import call
 
 JOB = np.dtype([("X", "u8"), ("dY", "u8"), ("part", "u8"), ("part_bias", "u8"), ("ldx", "i4"), ("ldy", "i4"), ("R", "i4"),
                 ("Cin", "i4"), ("Cout", "i4"), ("co_begin", "i4"), ("co_count", "i4"), ("slab_rows", "i4")])
@@ -22,6 +23,7 @@ WNB = np.dtype([("part", "u8"), ("part_bias", "u8"), ("v", "u8"), ("g", "u8"), (
                 ("dbias", "u8"), ("S", "i4"), ("Cout", "i4"), ("Cin", "i4"), ("taps", "i4"), ("row_start", "i4"),
                 ("accumulate", "i4"), ("pad0_", "i4"), ("pad1_", "i4")])
 assert JOB.itemsize == 64 and TILE.itemsize == 16 and WNB.itemsize == 96
+C_STRUCTS = {"gt_wgrad_job": JOB, "gt_wgrad_tile": TILE, "gt_wnb_job": WNB}      # include/glowtts_hip.h; layouts checked in tests/test_cabi.py
 
 # Row slabs per job.  A launch's workgroups (tiles x slabs) run two per CU — SLOTS at a time —, each walks its slab's rows at about
 # ROW_US per row whatever the tap count (operand latency, not MFMA, sets it; measured 0.033 us with both slots of a CU busy), and every
@@ -133,7 +135,7 @@ def single_slabs(R, Cin, Cout, taps):
     """Row slabs of the single-conv weight gradient (gt_conv_wgrad_bf16, flow_impl.conv_param_grads outside a queue) for R rows."""
     import ctypes
     S = ctypes.c_int(0)
-    _lib.lib().gt_conv_wgrad_workspace_bytes(R, Cin, Cout, taps, ctypes.byref(S))
+    call.gt_conv_wgrad_workspace_bytes(R, Cin, Cout, taps, ctypes.byref(S))
     return S.value
 
 
@@ -249,13 +251,12 @@ class WgradQueue:
     def _flush_ln(self):
         if not self.ln_jobs:
             return
-        import ctypes
         args = _lib.PartialsArgs()
         for i, (part, da, db) in enumerate(self.ln_jobs):
             j = args.job[i]
             j.partials, j.dst_a, j.dst_b, j.n_rows, j.Ca, j.Cb = part.data_ptr(), da.data_ptr(), db.data_ptr(), part.shape[0], da.numel(), db.numel()
         args.n_jobs = len(self.ln_jobs)
-        _lib.check(_lib.lib().gt_param_partials_reduce(ctypes.byref(args), _lib.current_stream(self.dev)), "gt_param_partials_reduce")
+        call.gt_param_partials_reduce(args, _lib.current_stream(self.dev))
         self.ln_jobs = []
 
     def _plan(self):
@@ -341,7 +342,6 @@ class WgradQueue:
             _KEEP.append(obj)
 
     def _flush(self):
-        L = _lib.lib()
         dev = self.dev
         jobs, tiles, wnbs, rows, max_n, nbytes = self._plan()
         ws = _scratch(dev, nbytes)
@@ -419,10 +419,9 @@ class WgradQueue:
             cache["pkey"], cache["jobs"], cache["wnb"] = pkey, upload(ja), upload(wa)
         counts = cache["counts"]
         st = _lib.current_stream(dev)
-        assert all(L.gt_conv_wgrad_ci_tile(t) == w for t, w in CI_TILE.items()), "wgrad.CI_TILE does not match the library's tile widths"
-        _lib.check(L.gt_conv_wgrad_batched(_lib.ptr(cache["jobs"]), _lib.ptr(cache["tiles"]), counts[0], counts[1], counts[2], st),
-                   "gt_conv_wgrad_batched")
-        _lib.check(L.gt_weightnorm_bwd_batched(_lib.ptr(cache["wnb"]), len(wnbs), rows, max_n, st), "gt_weightnorm_bwd_batched")
+        assert all(call.gt_conv_wgrad_ci_tile(t) == w for t, w in CI_TILE.items()), "wgrad.CI_TILE does not match the library's tile widths"
+        call.gt_conv_wgrad_batched(cache["jobs"], cache["tiles"], counts[0], counts[1], counts[2], st)
+        call.gt_weightnorm_bwd_batched(cache["wnb"], len(wnbs), rows, max_n, st)
         if capturing:
             self._keep(cache)
         self.items = []
