@@ -36,6 +36,9 @@ PROTOTYPES = {
                             c_int, c_int, c_int, c_i64, c_i64, c_void_p, c_size_t, c_void_p, c_void_p]),
     "gt_mas_lds_bytes": (c_size_t, [c_int, c_int]),
     "gt_mas_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gt_mas_long_f32": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                 c_int, c_int, c_int, c_i64, c_i64, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "gt_mas_long_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gt_mas_lengths_from_mask_f32": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                               c_i64, c_i64, c_void_p]),
     "gt_conv_gemm_bf16": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
@@ -462,8 +465,13 @@ def current_stream(device=None):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+class CpuTensorError(RuntimeError, TypeError):
+    """a CPU tensor where a device tensor is required: the wrong kind of argument (TypeError), raised as the RuntimeError callers of
+    the first releases catch"""
+
+
 def require_cuda(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
-            raise RuntimeError("glow_tts_amd ops run on the MI355X only (got a CPU tensor); "
+            raise CpuTensorError("glow_tts_amd ops run on the MI355X only (got a CPU tensor); "
                                "there is no CPU fallback — use oracle/ for CPU checking in tests")

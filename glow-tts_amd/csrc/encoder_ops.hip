@@ -689,6 +689,31 @@ __global__ __launch_bounds__(256) void gt_prior_expand_bwd_kernel(const float* _
   }
   for (int i = lane; i < Tx; i += 64) dxm[(size_t)bc * Tx + i] = a[i];
 }
+// The same walk for Tx > 512, where acc[4][512] ends: one wave per workgroup and (b, c) row, the row's Tx accumulators in dynamic LDS.
+__global__ __launch_bounds__(64) void gt_prior_expand_bwd_long_kernel(const float* __restrict__ dzm, const int32_t* __restrict__ f2t,
+                                                                      float* __restrict__ dxm, int B, int C, int Tx, int Ty)
+{
+  extern __shared__ float acc_long[];
+  const int lane = threadIdx.x;
+  const int bc = blockIdx.x;
+  const int b = bc / C;
+  float* a = acc_long;
+  for (int i = lane; i < Tx; i += 64) a[i] = 0.f;
+  for (int j0 = 0; j0 < Ty; j0 += 64) {
+    const int j = j0 + lane;
+    int t = -1; float v = 0.f;
+    if (j < Ty) { t = f2t[(size_t)b * Ty + j]; v = dzm[(size_t)bc * Ty + j]; }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float vv = __shfl_up(v, off);
+      const int tt = __shfl_up(t, off);
+      if (lane >= off && tt == t) v += vv;
+    }
+    const int tn = __shfl_down(t, 1);
+    if (t >= 0 && t < Tx && (lane == 63 || tn != t)) a[t] += v;
+  }
+  for (int i = lane; i < Tx; i += 64) dxm[(size_t)bc * Tx + i] = a[i];
+}
 // mle loss partial sums (commons.py:28-33): acc[0] += sum(logs*?) ... computed over [B,C,T] tensors:
 //   acc[0] += sum logs,  acc[1] += sum exp(-2 logs) (z-m)^2   (logs may be NULL = 0)
 __global__ __launch_bounds__(256) void gt_mle_sums_kernel(const float* __restrict__ z, const float* __restrict__ m,
@@ -1084,7 +1109,12 @@ extern "C" int gt_prior_expand(const float* x_m, const int32_t* frame2token, flo
 extern "C" int gt_prior_expand_bwd(const float* dz_m, const int32_t* frame2token, float* dx_m, int B, int C, int Tx, int Ty, void* stream)
 {
   if (!dz_m || !frame2token || !dx_m || B <= 0 || C <= 0 || Tx <= 0 || Ty <= 0) return GT_E_INVAL;
-  if (Tx > 512) return GT_E_UNSUPPORTED;                      // the MAS kernel's own limit
+  if (Tx > 16384) return GT_E_UNSUPPORTED;                    // 64 KiB of LDS per row; gt_mas_long_f32 stops at 4096 tokens
+  if (Tx > 512) {                                             // past acc[4][512]: a wave per workgroup, Tx floats of dynamic LDS
+    hipLaunchKernelGGL(gt_prior_expand_bwd_long_kernel, dim3((unsigned)((size_t)B * C)), dim3(64), (size_t)Tx * 4, GT_ST(stream),
+                       dz_m, frame2token, dx_m, B, C, Tx, Ty);
+    GT_RET();
+  }
   hipLaunchKernelGGL(gt_prior_expand_bwd_kernel, dim3(((size_t)B * C + 3) / 4), dim3(256), 0, GT_ST(stream), dz_m, frame2token, dx_m, B, C, Tx, Ty);
   GT_RET();
 }

@@ -2,12 +2,17 @@
 
 Mirrors reference monotonic_align/__init__.py:6-21 (``maximum_path(value, mask)``), whose
 Cython core (core.pyx:9-45) is replaced by the HIP kernel ``gt_mas_f32`` (csrc/mas.hip)
-called through the C-ABI.  No device->host round trip, no copies of the lattice.
+called through the C-ABI.  No device->host round trip, no copies of the lattice.  Lattices past
+that kernel's limits (more than 512 tokens, or direction bits past its LDS) go to
+``gt_mas_long_f32`` (csrc/mas_long.hip): same outputs, direction bits in the workspace.
 """
 import torch
 
 from . import _lib
 from ._lib import call
+
+MAS_MAX_TX, MAS_LDS_CAP = 512, 160 * 1024                                     # gt_mas_f32 (csrc/mas.hip)
+MAS_LONG_MAX_TX, MAS_LONG_MAX_TY, MAS_LONG_MAX_B = 4096, 32768, 65535           # gt_mas_long_f32 (include/glowtts_hip.h)
 
 _DT = {torch.float32: _lib.GT_DT_F32, torch.int32: _lib.GT_DT_I32, torch.float16: _lib.GT_DT_F16,
        torch.bfloat16: _lib.GT_DT_BF16, torch.uint8: _lib.GT_DT_U8}
@@ -23,7 +28,7 @@ class MASResult:
 
 
 def maximum_path_lengths(value, t_x, t_y, mask=None, out_dtype=None, want_durations=False,
-                         want_frame2token=False, validate=False, keep_workspace=False):
+                         want_frame2token=False, validate=False, keep_workspace=False, allow_long=False):
     """MAS from explicit lengths (the native form: no mask traffic).
 
     value: [b, t_x_max, t_y_max] float tensor on the GPU (fp32 is used as is; other float
@@ -31,6 +36,8 @@ def maximum_path_lengths(value, t_x, t_y, mask=None, out_dtype=None, want_durati
     t_x, t_y: [b] int32 device tensors.
     mask:  optional [b, t_x_max, t_y_max]; when given the kernel evaluates value*mask
            (__init__.py:11) on the fly.
+    allow_long: a lattice gt_mas_f32 refuses (t_x_max > 512, or gt_mas_lds_bytes > 160 KiB) goes to gt_mas_long_f32
+           instead of raising; every lattice gt_mas_f32 accepts is still computed by it.
     Returns MASResult; ``path`` has dtype ``out_dtype`` (default value.dtype).
     """
     _lib.require_cuda(value, t_x, t_y, mask)
@@ -59,16 +66,24 @@ def maximum_path_lengths(value, t_x, t_y, mask=None, out_dtype=None, want_durati
     status = torch.zeros((1,), dtype=torch.int32, device=v.device) if validate else None
     ws = None
     if B and T_x and T_y:
-        ws_bytes = call.gt_mas_workspace_bytes(B, T_x, T_y)
-        ws = torch.empty((ws_bytes // 4,), dtype=torch.int32, device=v.device)
-        try:
-            call.gt_mas_f32(v, m, t_x, t_y, path, _DT[out_dtype], dur, f2t, B, T_x, T_y,
-                            v.stride(0), v.stride(1), ws, ws_bytes, status, _lib.current_stream(v.device))
-        except _lib.GtError as e:
-            if e.code != -2:
-                raise
-            raise RuntimeError(f"gt_mas_f32: lattice [{T_x},{T_y}] exceeds the kernel's limits "
-                               f"(T_x<=512, LDS {call.gt_mas_lds_bytes(T_x, T_y)} B > 160 KiB)") from None
+        args = (v, m, t_x, t_y, path, _DT[out_dtype], dur, f2t, B, T_x, T_y, v.stride(0), v.stride(1))
+        if allow_long and not fits_lds_kernel(T_x, T_y):
+            if T_x > MAS_LONG_MAX_TX or T_y > MAS_LONG_MAX_TY or B > MAS_LONG_MAX_B:
+                raise RuntimeError(f"gt_mas_long_f32: lattice [{B},{T_x},{T_y}] exceeds the kernel's limits (T_x<={MAS_LONG_MAX_TX}, "
+                                   f"T_y<={MAS_LONG_MAX_TY}, B<={MAS_LONG_MAX_B})")
+            ws_bytes = call.gt_mas_long_workspace_bytes(B, T_x, T_y)
+            ws = torch.empty((ws_bytes // 4,), dtype=torch.int32, device=v.device)
+            call.gt_mas_long_f32(*args, ws, ws_bytes, status, _lib.current_stream(v.device))
+        else:
+            ws_bytes = call.gt_mas_workspace_bytes(B, T_x, T_y)
+            ws = torch.empty((ws_bytes // 4,), dtype=torch.int32, device=v.device)
+            try:
+                call.gt_mas_f32(*args, ws, ws_bytes, status, _lib.current_stream(v.device))
+            except _lib.GtError as e:
+                if e.code != -2:
+                    raise
+                raise RuntimeError(f"gt_mas_f32: lattice [{T_x},{T_y}] exceeds the kernel's limits "
+                                   f"(T_x<=512, LDS {call.gt_mas_lds_bytes(T_x, T_y)} B > 160 KiB)") from None
     if validate:
         st = int(status.item())
         if st & 1:
@@ -78,6 +93,11 @@ def maximum_path_lengths(value, t_x, t_y, mask=None, out_dtype=None, want_durati
             raise ValueError("maximum_path: a length is negative or exceeds the lattice")
     starts = ws[:B * (T_x + 1)].view(B, T_x + 1) if (keep_workspace and ws is not None) else None
     return MASResult(path, dur, f2t, status, starts)
+
+
+def fits_lds_kernel(T_x, T_y):
+    """gt_mas_f32's own rule (csrc/mas.hip), evaluated on the host: does it accept a [T_x, T_y] lattice?"""
+    return T_x <= MAS_MAX_TX and call.gt_mas_lds_bytes(T_x, T_y) <= MAS_LDS_CAP
 
 
 def result_from_path(path, t_x, t_y):
@@ -116,7 +136,8 @@ def maximum_path(value, mask, validate=False):
 
     value: [b, t_x, t_y], mask: [b, t_x, t_y]  ->  path [b, t_x, t_y] on value's device, in
     value's dtype, entries {0,1}.  Inputs are not modified.  Lengths come from the mask's first
-    column / row and the DP runs on value*mask, exactly like the reference.
+    column / row and the DP runs on value*mask, exactly like the reference.  Any lattice up to
+    4096 x 32768 (gt_mas_long_f32 past gt_mas_f32's limits); beyond that a RuntimeError names the limits.
     """
     t_x, t_y = lengths_from_mask(mask)
-    return maximum_path_lengths(value, t_x, t_y, mask=mask, validate=validate).path
+    return maximum_path_lengths(value, t_x, t_y, mask=mask, validate=validate, allow_long=True).path

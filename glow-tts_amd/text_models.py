@@ -266,7 +266,7 @@ class _LogpMasFn:
         zz = z.detach().float().contiguous()
         call.gt_logp_f32(xm, xs, zz, logp, B, C, Tx, Ty, _lib.current_stream(dev))
         r = monotonic_align.maximum_path_lengths(logp, x_lengths.to(torch.int32), y_lengths.to(torch.int32),
-                                                 want_durations=True, want_frame2token=True, keep_workspace=True)
+                                                 want_durations=True, want_frame2token=True, keep_workspace=True, allow_long=True)
         return logp, r
 
 

@@ -67,7 +67,7 @@ const char* gt_version(void);
  *   status      optional device int32, OR-ed with GT_MAS_ST_* bits.  Utterances with
  *               invalid lengths get an all-zero path.
  *
- * Limits: T_x <= 512, and gt_mas_lds_bytes(T_x,T_y) <= 160 KiB, else GT_E_UNSUPPORTED.
+ * Limits: T_x <= 512, and gt_mas_lds_bytes(T_x,T_y) <= 160 KiB, else GT_E_UNSUPPORTED (gt_mas_long_f32 takes those).
  * Bit-exact with the reference for every t_x <= t_y (IEEE fp32, same tie-breaks).
  */
 int gt_mas_f32(const float* logp, const float* mask,
@@ -83,6 +83,34 @@ size_t gt_mas_workspace_bytes(int B, int T_x, int T_y);
 
 /* LDS bytes one workgroup of gt_mas_f32 needs for a [T_x, T_y] lattice (host helper). */
 size_t gt_mas_lds_bytes(int T_x, int T_y);
+
+/* Monotonic Alignment Search for the lattices gt_mas_f32 refuses (T_x > 512, or gt_mas_lds_bytes > 160 KiB).  Arguments,
+ * outputs, status bits and error codes are gt_mas_f32's, word for word: the logp*mask form, any stride_b / stride_x, path in the
+ * five GT_DT_* types with every element written by the same chip-wide kernel, durations, frame2token (-1 past t_y), an all-zero
+ * path for invalid or empty utterances; asynchronous on `stream`, no allocation, no host synchronisation.  Bit-exact with the
+ * reference for every t_x <= t_y, and with gt_mas_f32 wherever both accept the lattice (gt_mas_f32 is the faster one there:
+ * callers dispatch to it first).
+ *
+ * The rows are walked in bands of 512 by one workgroup per utterance; the direction bits (T_x*T_y/8 bytes) and the band
+ * boundaries live in the workspace, nothing in LDS grows with T_x*T_y.
+ *   workspace   at least gt_mas_long_workspace_bytes(B,T_x,T_y) bytes, 4-byte aligned.  Its head is the same int32
+ *               [B, T_x+1] row start columns gt_mas_f32 leaves; the rest is scratch.
+ * Limits (checked on the host, GT_E_UNSUPPORTED): T_x <= GT_MAS_LONG_MAX_TX (row starts in LDS), T_y <= GT_MAS_LONG_MAX_TY,
+ * B <= GT_MAS_LONG_MAX_B (grid of the path kernel). */
+#define GT_MAS_LONG_MAX_TX 4096
+#define GT_MAS_LONG_MAX_TY 32768
+#define GT_MAS_LONG_MAX_B  65535
+int gt_mas_long_f32(const float* logp, const float* mask,
+                    const int32_t* t_x, const int32_t* t_y,
+                    void* path, int path_dtype,
+                    float* durations, int32_t* frame2token,
+                    int B, int T_x, int T_y, int64_t stride_b, int64_t stride_x,
+                    void* workspace, size_t workspace_bytes,
+                    int32_t* status, void* stream);
+
+/* Scratch bytes gt_mas_long_f32 needs for a batch (host helper): row starts + two band-boundary rows per utterance +
+ * B * ceil(T_x/64)*64 * ceil(T_y/32) direction words.  0 for an empty batch. */
+size_t gt_mas_long_workspace_bytes(int B, int T_x, int T_y);
 
 /* Lengths from a [B,T_x,T_y] fp32 mask the way monotonic_align/__init__.py:18-19 does:
  * t_x[b] = sum_x mask[b,x,0], t_y[b] = sum_y mask[b,0,y] (truncated to int32). */
@@ -379,7 +407,8 @@ int gt_rows_utt_sum(const void* y, int ldy, int is_f32, const float* rowmask, fl
 int gt_logp_f32(const float* x_m, const float* x_logs, const float* z, float* logp, int B, int C, int Tx, int Ty, void* stream);
 
 /* Prior expansion models.py:1118-1119 as a gather by frame2token (from gt_mas_f32; -1 = padded frame) and its backward as
- * the segment sums over the frames of every token (deterministic: fixed summation order; Tx <= 512). */
+ * the segment sums over the frames of every token (deterministic: fixed summation order; Tx <= 16384, past 512 tokens with one
+ * wave per workgroup and Tx floats of dynamic LDS; GT_E_UNSUPPORTED beyond). */
 int gt_prior_expand(const float* x_m, const int32_t* frame2token, float* z_m, int B, int C, int Tx, int Ty, void* stream);
 int gt_prior_expand_bwd(const float* dz_m, const int32_t* frame2token, float* dx_m, int B, int C, int Tx, int Ty, void* stream);
 
