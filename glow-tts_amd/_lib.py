@@ -88,6 +88,7 @@ PROTOTYPES = {
                              c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_u32, c_void_p, c_void_p]),
     "gt_attn_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gt_attn_mfma_shape": (c_int, [c_int, c_int, c_int]),
+    "gt_attn_long_shape": (c_int, [c_int, c_int, c_int]),
     "gt_attn_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                              c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                              c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_u32, c_void_p, c_void_p]),

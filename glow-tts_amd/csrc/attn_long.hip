@@ -1,0 +1,642 @@
+// Relative-position attention for long texts (505 < T <= GT_ATTN_LONG_MAX_T; D = 96, window 4) on bf16 MFMA for gfx950.
+//
+// Same contract, lane mapping and arithmetic as the <12> kernels of attn_mfma.hip (read that file first): one score tile
+// live at a time, two walks over the key tiles.  What changes: the tile count is a runtime loop and NO full-length operand
+// sits in LDS or in registers.
+//   * operands read as plain rows (K in the forward, V in the backward pass 1, the dS^T / P'^T columns in pass 2) come
+//     straight from L2 into registers, one tile ahead;
+//   * operands read through transposing LDS reads (V in the forward, K in pass 1, Q and dO in pass 2) are staged per
+//     32-row tile in a two-slot LDS ring shared by the workgroup: every thread loads its share of tile t+1 into registers
+//     before tile t is consumed, drops it into the other slot afterwards, and ONE barrier per tile closes the step (slot
+//     (t+1)&1 was last read in step t-1, which every wave has left).  Waves that own no query (key) rows still stage.
+// LDS per workgroup: forward 30 720 B, pass 1 72 448 B, pass 2 24 576 B — whatever T is.
+#include <stdlib.h>
+#include "attn_frag.h"
+#include "internal.h"
+
+namespace {
+using namespace gt_attn_frag;
+
+constexpr int TILE_U4 = 32 * (D / 8);          // uint4s of one staged [32][VP] tile (384)
+
+// one [32][VP] tile of rows 32t .. 32t+31 (rows >= T zero): thread tid holds uint4 x = tid + 256u, u < 2
+#define GT_TILE_LOAD(regs, src, lds_, t)                                                       \
+  _Pragma("unroll") for (int u_ = 0; u_ < 2; ++u_) {                                           \
+    const int x_ = tid + 256 * u_;                                                             \
+    const int row_ = x_ / (D / 8), c8_ = x_ - row_ * (D / 8);                                  \
+    uint4 val_ = make_uint4(0, 0, 0, 0);                                                       \
+    if (x_ < TILE_U4 && 32 * (t) + row_ < T)                                                   \
+      val_ = *reinterpret_cast<const uint4*>((src) + RW(32 * (t) + row_) * (lds_) + h * D + c8_ * 8); \
+    (regs)[u_] = val_;                                                                         \
+  }
+#define GT_TILE_STORE(slot, regs)                                                              \
+  _Pragma("unroll") for (int u_ = 0; u_ < 2; ++u_) {                                           \
+    const int x_ = tid + 256 * u_;                                                             \
+    const int row_ = x_ / (D / 8), c8_ = x_ - row_ * (D / 8);                                  \
+    if (x_ < TILE_U4) *reinterpret_cast<uint4*>((slot) + row_ * VP + c8_ * 8) = (regs)[u_];    \
+  }
+
+// =========================================================================================
+// Forward: one workgroup per (utterance, head, 128 queries), a wave owns 32 queries.
+__global__ __launch_bounds__(256, 2) void gt_attn_long_fwd_kernel(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,
+    const float* __restrict__ Ek, const float* __restrict__ Ev, const int32_t* __restrict__ lens,
+    bf16_t* __restrict__ out, int ldo, float* __restrict__ Pout,
+    int T, int Tp, const int32_t* row0, int H, uint32_t drop_thresh, uint32_t drop_seed, float drop_scale, const uint32_t* __restrict__ seed_dev)
+{
+  if (seed_dev) drop_seed ^= *seed_dev;
+  __shared__ __attribute__((aligned(16))) bf16_t Vr[2 * 32 * VP];   // V ring: two [32][VP] tiles
+  __shared__ __attribute__((aligned(16))) bf16_t Eks[32 * KP];      // rows >= 9 are zero
+  __shared__ __attribute__((aligned(16))) bf16_t EvT[D * 16];       // EvT[d][r], r >= 9 zero
+  __shared__ __attribute__((aligned(16))) float  QE[4 * 32 * NW];
+  __shared__ __attribute__((aligned(16))) bf16_t PB[4 * 32 * 16];
+
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+  const int len = lens[b];
+  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
+  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;          // see gt_attn_fwd_mfma_kernel
+  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
+
+  for (int i = tid; i < 32 * D; i += 256) { const int rr = i / D, c = i - rr * D; Eks[rr * KP + c] = rr < NW ? f2bf(Ek[rr * D + c]) : (bf16_t)0; }
+  for (int i = tid; i < D * 16; i += 256) { const int d = i >> 4, rr = i & 15; EvT[i] = rr < NW ? f2bf(Ev[rr * D + d]) : (bf16_t)0; }
+  for (int i = tid; i < 4 * 32 * 16; i += 256) PB[i] = 0;
+  const int nt = (T + 31) >> 5;                                  // key tiles that hold keys (uniform)
+  uint4 vr[2];
+  GT_TILE_LOAD(vr, v, ld, 0)
+  GT_TILE_STORE(Vr, vr)
+  __syncthreads();
+
+  const int i0 = blockIdx.x * 128 + 32 * w;
+  const bool active = i0 < T;                                    // wave-uniform
+  const int i = i0 + r;
+  const int ic = i < T ? i : T - 1;
+  float* qe = QE + w * 32 * NW;
+  bf16_t* pb = PB + w * 32 * 16;
+  const float inv_sqrt = rsqrtf((float)D);
+
+  bf16x8_t qf[6];
+#pragma unroll
+  for (int ks = 0; ks < 6; ++ks)
+    qf[ks] = *reinterpret_cast<const bf16x8_t*>(q + RW(ic) * ld + h * D + ks * 16 + 8 * hh);
+  if (active) {
+    f32x16_t acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks) {
+      const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(Eks + r * KP + ks * 16 + 8 * hh);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, qf[ks], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) qe[r * NW + e + 4 * hh] = acc[e];
+    if (hh == 0) qe[r * NW + 8] = acc[4];
+  }
+  __builtin_amdgcn_wave_barrier();
+
+  // K fragments of key tile t: lane (key r of the tile, k-half hh); rows >= T are zero
+  auto load_k = [&](int t, bf16x8_t* kf) {
+    const int j = 32 * t + r;
+    if (j < T) {
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) kf[ks] = *reinterpret_cast<const bf16x8_t*>(k + RW(j) * ld + h * D + ks * 16 + 8 * hh);
+    } else {
+      const uint4 z = make_uint4(0, 0, 0, 0);
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) kf[ks] = __builtin_bit_cast(bf16x8_t, z);
+    }
+  };
+  // masked, scaled scores of one tile (element e <-> key 32t + (e&3) + 8(e>>2) + 4hh)
+  auto scores = [&](int t, const bf16x8_t* kf, f32x16_t& st) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) st[e] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], st, 0, 0, 0);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int j = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
+      float sc = st[e];
+      const int rel = j - i + WIN;
+      if ((unsigned)rel <= 2u * WIN) sc += qe[r * NW + rel];
+      sc *= inv_sqrt;
+      if (j >= T) sc = -3.0e38f;                                 // not a key at all
+      else if (j >= len || i >= len) sc = -1e4f;                 // masked_fill(mask == 0, -1e4), attentions.py:260
+      st[e] = sc;
+    }
+  };
+
+  // ---- pass 1 (no LDS operand, no barrier): online max / denominator over this lane's keys, then the lane halves merge
+  float mx = -3.0e38f, den = 0.f;
+  bf16x8_t kf[6], kn[6];
+  if (active) {
+    load_k(0, kf);
+#pragma unroll 1
+    for (int t = 0; t < nt; ++t) {
+      if (t + 1 < nt) load_k(t + 1, kn);
+      f32x16_t st;
+      scores(t, kf, st);
+      float tm = st[0];
+#pragma unroll
+      for (int e = 1; e < 16; ++e) tm = fmaxf(tm, st[e]);
+      const float mn = fmaxf(mx, tm);
+      float add = 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) add += __expf(st[e] - mn);
+      den = den * __expf(mx - mn) + add;
+      mx = mn;
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) kf[ks] = kn[ks];
+    }
+    const float mo = __shfl_xor(mx, 32), dn = __shfl_xor(den, 32);
+    const float mm = fmaxf(mx, mo);
+    den = den * __expf(mx - mm) + dn * __expf(mo - mm);
+    mx = mm;
+  }
+  const float rden = active ? 1.0f / den : 0.f;
+
+  // ---- pass 2: P = softmax, dropout, O^T = V^T P^T (+ Ev^T band(P)^T); V tile t in ring slot t & 1
+  float* prow = Pout + (((size_t)b * H + h) * T + ic) * T;
+  const uint32_t drow = (uint32_t)((b * H + h) * T + i);
+  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
+  const bool vec = (T & 3) == 0;
+  f32x16_t o[3];
+#pragma unroll
+  for (int dt = 0; dt < 3; ++dt) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
+  }
+  if (active) load_k(0, kf);
+#pragma unroll 1
+  for (int t = 0; t < nt; ++t) {
+    if (t + 1 < nt) {
+      GT_TILE_LOAD(vr, v, ld, t + 1)
+      if (active) load_k(t + 1, kn);
+    }
+    if (active) {
+      const bf16_t* Vs = Vr + (t & 1) * 32 * VP;
+      f32x16_t st;
+      scores(t, kf, st);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int j0 = 32 * t + 8 * g + 4 * hh;
+        float p4[4];
+#pragma unroll
+        for (int e2 = 0; e2 < 4; ++e2) p4[e2] = __expf(st[4 * g + e2] - mx) * rden;
+        if (i < T) {
+          if (vec && j0 + 3 < T) *reinterpret_cast<float4*>(prow + j0) = make_float4(p4[0], p4[1], p4[2], p4[3]);
+          else {
+#pragma unroll
+            for (int e2 = 0; e2 < 4; ++e2) if (j0 + e2 < T) prow[j0 + e2] = p4[e2];
+          }
+        }
+#pragma unroll
+        for (int e2 = 0; e2 < 4; ++e2) {
+          const int j = j0 + e2;
+          float pd = p4[e2];
+          if (drop_thresh) pd = drop_keep(drop_seed, drow, j, drop_thresh) ? pd * drop_scale : 0.f;
+          st[4 * g + e2] = pd;
+          const int rel = j - i + WIN;
+          if ((unsigned)rel <= 2u * WIN && j < T) pb[r * 16 + rel] = f2bf(pd);
+        }
+      }
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        float f8[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f8[e] = st[8 * s2 + e];
+        const bf16x8_t pf = pack8(f8);
+#pragma unroll
+        for (int dt = 0; dt < 3; ++dt) {
+          const bf16_t* va = Vs + (16 * s2 + 4 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          const bf16x8_t af = tr_frag8(va, va + 8 * VP);
+          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, pf, o[dt], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) kf[ks] = kn[ks];
+    }
+    if (t + 1 < nt) { GT_TILE_STORE(Vr + ((t + 1) & 1) * 32 * VP, vr) }
+    __syncthreads();
+  }
+  if (!active) return;
+  {
+    const bf16x8_t bfp = *reinterpret_cast<const bf16x8_t*>(pb + r * 16 + 8 * hh);      // band(P)^T: k = rel
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt) {
+      const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(EvT + (32 * dt + r) * 16 + 8 * hh);
+      o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfp, o[dt], 0, 0, 0);
+    }
+  }
+  if (i < T && i <= nv1) {
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d = 32 * dt + 8 * g + 4 * hh;
+        *reinterpret_cast<uint2*>(out + (rbase + i) * ldo + h * D + d) =
+            make_uint2(pack2bf(o[dt][4 * g], o[dt][4 * g + 1]), pack2bf(o[dt][4 * g + 2], o[dt][4 * g + 3]));
+      }
+  }
+}
+
+// =========================================================================================
+// Backward pass 1 (dS, P', dQ, dEk, dEv): the one-tile recompute form of gt_attn_bwd_q_mfma_kernel<12, 4, true>, 4 waves x
+// 32 queries.  Pass A (Dsum) reads V rows and P only; pass B stages K per tile for the transposing reads of dQ^T.  The
+// Q / dO tiles of the dEk / dEv contraction share one per-wave [32][VP] area, loaded one after the other at the end.
+constexpr int LWBN = 32 * 16 + 2 * 16 * BTP + 32 * VP;         // per wave: dSB[32][16] | dSBT[16][BTP] | PdBT[16][BTP] | QD[32][VP]
+constexpr size_t LDS_BWD_Q = (size_t)2 * 32 * VP * 2 + 32 * KP * 2 + D * 16 * 2 + 2 * NW * D * 4 + 4 * 32 * NW * 4 + (size_t)4 * LWBN * 2;
+
+__global__ __launch_bounds__(256, 2) void gt_attn_long_bwd_q_kernel(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,
+    const float* __restrict__ Ek, const float* __restrict__ Ev, const int32_t* __restrict__ lens,
+    const bf16_t* __restrict__ dout, int lddo, const float* __restrict__ P,
+    bf16_t* __restrict__ dST, bf16_t* __restrict__ PdT, int TI,
+    bf16_t* __restrict__ dq, int lddq, float* __restrict__ dEk, float* __restrict__ dEv,
+    int T, int Tp, const int32_t* row0, int H, uint32_t drop_thresh, uint32_t drop_seed, float drop_scale, const uint32_t* __restrict__ seed_dev)
+{
+  if (seed_dev) drop_seed ^= *seed_dev;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  bf16_t* Kr  = reinterpret_cast<bf16_t*>(smem);                 // K ring: two [32][VP] tiles
+  bf16_t* Evs = Kr + 2 * 32 * VP;                                // [32][KP]    rows >= 9 zero
+  bf16_t* EkT = Evs + 32 * KP;                                   // [96][16]
+  float*  Acc = reinterpret_cast<float*>(EkT + D * 16);          // [2][NW][D]  block-local dEk | dEv
+  float*  DOE = Acc + 2 * NW * D;                                // [4][32][NW]
+  bf16_t* WB  = reinterpret_cast<bf16_t*>(DOE + 4 * 32 * NW);    // [4][LWBN]
+
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+  const int len = lens[b];
+  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
+  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;          // see gt_attn_bwd_q_mfma_kernel
+  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
+
+  for (int i = tid; i < 32 * D; i += 256) { const int rr = i / D, c = i - rr * D; Evs[rr * KP + c] = rr < NW ? f2bf(Ev[rr * D + c]) : (bf16_t)0; }
+  for (int i = tid; i < D * 16; i += 256) { const int d = i >> 4, rr = i & 15; EkT[i] = rr < NW ? f2bf(Ek[rr * D + d]) : (bf16_t)0; }
+  for (int i = tid; i < 2 * NW * D; i += 256) Acc[i] = 0.f;
+  for (int i = tid; i < 4 * (32 * 16 + 2 * 16 * BTP); i += 256) {             // band tables start at zero
+    const int ww = i / (32 * 16 + 2 * 16 * BTP), o = i - ww * (32 * 16 + 2 * 16 * BTP);
+    WB[ww * LWBN + o] = 0;
+  }
+  const int nt = (T + 31) >> 5;                                  // key tiles that hold keys (uniform)
+  uint4 kr[2];
+  GT_TILE_LOAD(kr, k, ld, 0)
+  GT_TILE_STORE(Kr, kr)
+  __syncthreads();
+
+  const int i0 = (blockIdx.x * 4 + w) * 32;
+  const bool active = i0 < T;                                    // wave-uniform
+  const int i = i0 + r;
+  const int ic = i < T ? i : T - 1;
+  float* doe = DOE + w * 32 * NW;
+  bf16_t* dSB = WB + w * LWBN;
+  bf16_t* dSBT = dSB + 32 * 16;
+  bf16_t* PdBT = dSBT + 16 * BTP;
+  bf16_t* QD = PdBT + 16 * BTP;
+  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
+
+  bf16x8_t dof[6];
+#pragma unroll
+  for (int ks = 0; ks < 6; ++ks)
+    dof[ks] = *reinterpret_cast<const bf16x8_t*>(dout + RW(ic) * lddo + h * D + ks * 16 + 8 * hh);
+  if (active) {
+    f32x16_t acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks) {
+      const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(Evs + r * KP + ks * 16 + 8 * hh);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, dof[ks], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) doe[r * NW + e + 4 * hh] = acc[e];
+    if (hh == 0) doe[r * NW + 8] = acc[4];
+  }
+  __builtin_amdgcn_wave_barrier();
+
+  const float inv_sqrt = rsqrtf((float)D);
+  const float* prow = P + (((size_t)b * H + h) * T + ic) * T;
+  const uint32_t drow = (uint32_t)((b * H + h) * T + i);
+  const bool vec = (T & 3) == 0;
+  bf16_t* dst_base = dST + ((size_t)b * H + h) * T * TI;
+  bf16_t* pdt_base = PdT + ((size_t)b * H + h) * T * TI;
+
+  // V fragments of key tile t: lane (key r of the tile, k-half hh); rows >= T are zero
+  auto load_v = [&](int t, bf16x8_t* vf) {
+    const int j = 32 * t + r;
+    if (j < T) {
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) vf[ks] = *reinterpret_cast<const bf16x8_t*>(v + RW(j) * ld + h * D + ks * 16 + 8 * hh);
+    } else {
+      const uint4 z = make_uint4(0, 0, 0, 0);
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) vf[ks] = __builtin_bit_cast(bf16x8_t, z);
+    }
+  };
+  auto dp_tile = [&](const bf16x8_t* vf, f32x16_t& st) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) st[e] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[ks], dof[ks], st, 0, 0, 0);
+  };
+  auto load_p4 = [&](int j0, float* p4) {
+    p4[0] = p4[1] = p4[2] = p4[3] = 0.f;
+    if (vec && j0 + 3 < T) { const float4 pv = *reinterpret_cast<const float4*>(prow + j0); p4[0] = pv.x; p4[1] = pv.y; p4[2] = pv.z; p4[3] = pv.w; }
+    else {
+#pragma unroll
+      for (int e2 = 0; e2 < 4; ++e2) if (j0 + e2 < T) p4[e2] = prow[j0 + e2];
+    }
+  };
+  auto dp_elem = [&](float dp, int j) {
+    const int rel = j - i + WIN;
+    if ((unsigned)rel <= 2u * WIN) dp += doe[r * NW + rel];
+    if (drop_thresh) dp = drop_keep(drop_seed, drow, j, drop_thresh) ? dp * drop_scale : 0.f;
+    return j >= T ? 0.f : dp;
+  };
+
+  // ---- pass A (no LDS operand, no barrier): Dsum = sum_j dP P
+  float dsum = 0.f;
+  bf16x8_t vf[6], vn[6];
+  if (active) {
+    load_v(0, vf);
+#pragma unroll 1
+    for (int t = 0; t < nt; ++t) {
+      if (t + 1 < nt) load_v(t + 1, vn);
+      f32x16_t st;
+      dp_tile(vf, st);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int j0 = 32 * t + 8 * g + 4 * hh;
+        float p4[4];
+        load_p4(j0, p4);
+#pragma unroll
+        for (int e2 = 0; e2 < 4; ++e2) dsum += dp_elem(st[4 * g + e2], j0 + e2) * p4[e2];
+      }
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) vf[ks] = vn[ks];
+    }
+    dsum += __shfl_xor(dsum, 32);
+  }
+
+  // ---- pass B: recompute dPd^T per tile, dS^T, store dS^T / P'^T, dQ^T += K^T dS^T; K tile t in ring slot t & 1
+  f32x16_t o[3];
+#pragma unroll
+  for (int dt = 0; dt < 3; ++dt) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
+  }
+  if (active) load_v(0, vf);
+#pragma unroll 1
+  for (int t = 0; t < nt; ++t) {
+    if (t + 1 < nt) {
+      GT_TILE_LOAD(kr, k, ld, t + 1)
+      if (active) load_v(t + 1, vn);
+    }
+    if (active) {
+      const bf16_t* Ks = Kr + (t & 1) * 32 * VP;
+      f32x16_t st;
+      dp_tile(vf, st);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int j0 = 32 * t + 8 * g + 4 * hh;
+        float p4[4];
+        load_p4(j0, p4);
+#pragma unroll
+        for (int e2 = 0; e2 < 4; ++e2) {
+          const int j = j0 + e2;
+          float ds = p4[e2] * (dp_elem(st[4 * g + e2], j) - dsum) * inv_sqrt;
+          float pd = p4[e2];
+          if (drop_thresh) pd = drop_keep(drop_seed, drow, j, drop_thresh) ? pd * drop_scale : 0.f;
+          if (j >= T || j >= len || i >= len || i >= T) ds = 0.f;          // masked_fill blocks the gradient
+          if (i >= len || i >= T) pd = 0.f;                                // padded queries carry no upstream gradient
+          st[4 * g + e2] = ds;
+          if (j < T) {
+            dst_base[(size_t)j * TI + i] = f2bf(ds);
+            pdt_base[(size_t)j * TI + i] = f2bf(pd);
+            const int rel = j - i + WIN;
+            if ((unsigned)rel <= 2u * WIN) { const bf16_t db = f2bf(ds); dSB[r * 16 + rel] = db; dSBT[rel * BTP + r] = db; PdBT[rel * BTP + r] = f2bf(pd); }
+          }
+        }
+      }
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        float f8[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f8[e] = st[8 * s2 + e];
+        const bf16x8_t pf = pack8(f8);
+#pragma unroll
+        for (int dt = 0; dt < 3; ++dt) {
+          const bf16_t* ka = Ks + (16 * s2 + 4 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          const bf16x8_t af = tr_frag8(ka, ka + 8 * VP);
+          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, pf, o[dt], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) vf[ks] = vn[ks];
+    }
+    if (t + 1 < nt) { GT_TILE_STORE(Kr + ((t + 1) & 1) * 32 * VP, kr) }
+    __syncthreads();
+  }
+
+  if (active) {
+    {
+      const bf16x8_t bfp = *reinterpret_cast<const bf16x8_t*>(dSB + r * 16 + 8 * hh);
+#pragma unroll
+      for (int dt = 0; dt < 3; ++dt) {
+        const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(EkT + (32 * dt + r) * 16 + 8 * hh);
+        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfp, o[dt], 0, 0, 0);
+      }
+    }
+    if (i < T && i <= nv1) {
+#pragma unroll
+      for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int d = 32 * dt + 8 * g + 4 * hh;
+          *reinterpret_cast<uint2*>(dq + (rbase + i) * lddq + h * D + d) =
+              make_uint2(pack2bf(o[dt][4 * g], o[dt][4 * g + 1]), pack2bf(o[dt][4 * g + 2], o[dt][4 * g + 3]));
+        }
+    }
+    // dEk[r'][d] += sum_i dSBT[r'][i] Q[i][d];  dEv[r'][d] += sum_i PdBT[r'][i] dO[i][d]   (K = 32 queries, one MFMA chain)
+#pragma unroll 1
+    for (int which = 0; which < 2; ++which) {
+      const bf16_t* At = which ? PdBT : dSBT;
+      const bf16_t* src = which ? dout : q;
+      const int lds_ = which ? lddo : ld;
+      __builtin_amdgcn_wave_barrier();                             // the previous contraction has read QD
+      for (int c = lane; c < 32 * (D / 8); c += 64) {              // this wave's Q (dO) rows, rows >= T zero
+        const int rr = c / (D / 8), c8 = c - rr * (D / 8);
+        uint4 x = make_uint4(0, 0, 0, 0);
+        if (i0 + rr < T) x = *reinterpret_cast<const uint4*>(src + RW(i0 + rr) * lds_ + h * D + c8 * 8);
+        *reinterpret_cast<uint4*>(QD + rr * VP + c8 * 8) = x;
+      }
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int dt = 0; dt < 3; ++dt) {
+        f32x16_t acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(At + (r & 15) * BTP + 16 * ks + 8 * hh);
+          if (r >= 16) { const uint4 z = make_uint4(0, 0, 0, 0); af = __builtin_bit_cast(bf16x8_t, z); }
+          const bf16_t* ba = QD + (16 * ks + 8 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          const bf16x8_t bf_ = tr_frag8(ba, ba + 4 * VP);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf_, acc, 0, 0, 0);
+        }
+        float* dstA = Acc + which * NW * D;
+        const int d = 32 * dt + r;                                   // D layout: column = d (lane&31), row r' = (e&3)+8(e>>2)+4hh
+#pragma unroll
+        for (int e = 0; e < 4; ++e) atomicAdd(dstA + (e + 4 * hh) * D + d, acc[e]);
+        if (hh == 0) atomicAdd(dstA + 8 * D + d, acc[4]);
+      }
+    }
+  }
+  __syncthreads();
+  for (int x = tid; x < NW * D; x += 256) {
+    if (Acc[x] != 0.f) atomicAdd(dEk + x, Acc[x]);
+    if (Acc[NW * D + x] != 0.f) atomicAdd(dEv + x, Acc[NW * D + x]);
+  }
+}
+
+// =========================================================================================
+// Backward pass 2 (dK, dV): one workgroup per (utterance, head, 128 keys), a wave owns 32 keys and walks the 32-query
+// tiles.  Q and dO rows of a tile go through the LDS ring (transposing reads); the dS^T / P'^T columns of the wave's keys
+// come straight from the pass-1 workspace, one tile ahead.  dK = dS^T Q and dV = P'^T dO accumulate in registers.
+__global__ __launch_bounds__(256, 2) void gt_attn_long_bwd_kv_kernel(
+    const bf16_t* __restrict__ q, int ld, const bf16_t* __restrict__ dout, int lddo,
+    const bf16_t* __restrict__ dST, const bf16_t* __restrict__ PdT, int TI,
+    bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int lddk, int T, int Tp, const int32_t* row0, int H)
+{
+  __shared__ __attribute__((aligned(16))) bf16_t Qr[2 * 32 * VP];   // Q ring: two [32][VP] tiles
+  __shared__ __attribute__((aligned(16))) bf16_t Or[2 * 32 * VP];   // dO ring
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
+  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;          // see gt_attn_bwd_kv_mfma_kernel
+  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
+
+  const int nqt = TI >> 5;                                       // query tiles (uniform); TI = ceil(T/32)*32
+  uint4 qr[2], dr[2];
+  GT_TILE_LOAD(qr, q, ld, 0)
+  GT_TILE_LOAD(dr, dout, lddo, 0)
+  GT_TILE_STORE(Qr, qr)
+  GT_TILE_STORE(Or, dr)
+  __syncthreads();
+
+  const int j0 = blockIdx.x * 128 + 32 * w;
+  const bool active = j0 < T;                                    // wave-uniform
+  const int j = j0 + r, jc = j < T ? j : T - 1;
+  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
+  const bf16_t* dsr = dST + (((size_t)b * H + h) * T + jc) * TI;
+  const bf16_t* pdr = PdT + (((size_t)b * H + h) * T + jc) * TI;
+  f32x16_t ak[3], av[3];
+#pragma unroll
+  for (int dt = 0; dt < 3; ++dt) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) { ak[dt][e] = 0.f; av[dt][e] = 0.f; }
+  }
+  // columns i = 32t + 16ks + 8hh .. +7 of this lane's key row: dS[i, j], P'[i, j]
+  auto load_cols = [&](int t, bf16x8_t* bds, bf16x8_t* bpd) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      bds[ks] = *reinterpret_cast<const bf16x8_t*>(dsr + 32 * t + 16 * ks + 8 * hh);
+      bpd[ks] = *reinterpret_cast<const bf16x8_t*>(pdr + 32 * t + 16 * ks + 8 * hh);
+    }
+  };
+  bf16x8_t bds[2], bpd[2], nds[2], npd[2];
+  if (active) load_cols(0, bds, bpd);
+#pragma unroll 1
+  for (int t = 0; t < nqt; ++t) {
+    if (t + 1 < nqt) {
+      GT_TILE_LOAD(qr, q, ld, t + 1)
+      GT_TILE_LOAD(dr, dout, lddo, t + 1)
+      if (active) load_cols(t + 1, nds, npd);
+    }
+    if (active) {
+      const bf16_t* Qs = Qr + (t & 1) * 32 * VP;
+      const bf16_t* dOs = Or + (t & 1) * 32 * VP;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+        for (int dt = 0; dt < 3; ++dt) {
+          const bf16_t* qa = Qs + (16 * ks + 8 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          const bf16_t* da = dOs + (16 * ks + 8 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          ak[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag8(qa, qa + 4 * VP), bds[ks], ak[dt], 0, 0, 0);
+          av[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag8(da, da + 4 * VP), bpd[ks], av[dt], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) { bds[ks] = nds[ks]; bpd[ks] = npd[ks]; }
+    }
+    if (t + 1 < nqt) {
+      GT_TILE_STORE(Qr + ((t + 1) & 1) * 32 * VP, qr)
+      GT_TILE_STORE(Or + ((t + 1) & 1) * 32 * VP, dr)
+    }
+    __syncthreads();
+  }
+  if (active && j < T && j <= nv1) {
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d = 32 * dt + 8 * g + 4 * hh;
+        *reinterpret_cast<uint2*>(dk + RW(j) * lddk + h * D + d) =
+            make_uint2(pack2bf(ak[dt][4 * g], ak[dt][4 * g + 1]), pack2bf(ak[dt][4 * g + 2], ak[dt][4 * g + 3]));
+        *reinterpret_cast<uint2*>(dv + RW(j) * lddk + h * D + d) =
+            make_uint2(pack2bf(av[dt][4 * g], av[dt][4 * g + 1]), pack2bf(av[dt][4 * g + 2], av[dt][4 * g + 3]));
+      }
+  }
+}
+
+#undef GT_TILE_LOAD
+#undef GT_TILE_STORE
+
+}  // namespace
+
+// The shapes the key-tiled kernels take, in both directions: past the last T at which the generic backward's LDS holds an
+// utterance-head (505), up to the token limit of gt_mas_long_f32.
+extern "C" int gt_attn_long_shape(int T, int Dh, int win) { return Dh == D && win == WIN && T > 505 && T <= GT_ATTN_LONG_MAX_T; }
+
+// returns 1 if the shape is not handled here (caller falls back to the generic kernel)
+int gt_attn_fwd_long_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                          const int32_t* lens, void* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win,
+                          uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
+{
+  if (!gt_attn_long_shape(T, Dh, win) || (ld & 7) || (ldo & 3)) return 1;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return 1;
+  hipLaunchKernelGGL(gt_attn_long_fwd_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
+                     static_cast<bf16_t*>(out), ldo, P, T, Tp, row0, H, th, sd, sc, seed_dev);
+  return gt_launch_status(__func__);
+}
+
+int gt_attn_bwd_long_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                          const int32_t* lens, const void* dout, int lddo, const float* P, void* ws, size_t ws_bytes,
+                          void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
+                          int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
+{
+  if (!gt_attn_long_shape(T, Dh, win) || (ld & 7) || (lddo & 7) || (lddq & 3)) return 1;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)ws) & 15) return 1;
+  if (ws_bytes < gt_attn_bwd_mfma_ws_bytes(B, T, H)) return 1;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int TI = ((T + 31) / 32) * 32;
+  bf16_t* dST = static_cast<bf16_t*>(ws);                        // the MFMA family's workspace format (launch_bwd of attn_mfma.hip)
+  bf16_t* PdT = dST + (size_t)B * H * T * TI;
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_long_bwd_q_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BWD_Q) != hipSuccess)
+      return GT_E_LAUNCH;
+    attr = true;
+  }
+  hipLaunchKernelGGL(gt_attn_long_bwd_q_kernel, dim3((T + 127) / 128, H, B), dim3(256), LDS_BWD_Q, st,
+                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
+                     static_cast<const bf16_t*>(dout), lddo, P, dST, PdT, TI, static_cast<bf16_t*>(dq), lddq, dEk, dEv,
+                     T, Tp, row0, H, th, sd, sc, seed_dev);
+  hipLaunchKernelGGL(gt_attn_long_bwd_kv_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, st,
+                     static_cast<const bf16_t*>(q), ld, static_cast<const bf16_t*>(dout), lddo, dST, PdT, TI,
+                     static_cast<bf16_t*>(dk), static_cast<bf16_t*>(dv), lddq, T, Tp, row0, H);
+  return gt_launch_status(__func__);
+}

@@ -13,30 +13,11 @@
 //                          ds_read_b64_tr_b16 (pitch 192 B) in the permuted k order that map requires.
 //   O^T += Ev^T band(P)^T  the relative-value term as one K=16 MFMA per 32 channels.
 #include <stdlib.h>
-#include "common.h"
-#include "../../include/glowtts_hip.h"
+#include "attn_frag.h"
 #include "internal.h"
 
 namespace {
-
-constexpr int HALO = GT_HALO;
-constexpr int D = 96, WIN = 4, NW = 9;
-constexpr int KP = 104;            // K / Ek pitch in halfs (208 B): conflict-free ds_read_b128 over 16 rows
-constexpr int VP = 96;             // V pitch in halfs (192 B): conflict-free transposing reads
-
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4_t;
-typedef __attribute__((__vector_size__(8 * sizeof(short)))) short s16x8_t;
-
-__device__ __forceinline__ bf16x8_t tr_frag8(const bf16_t* p0, const bf16_t* p1) {
-  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(uintptr_t)p0);
-  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(uintptr_t)p1);
-  s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-__device__ __forceinline__ bf16x8_t pack8(const float* f) {
-  const uint4 u = make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
-  return __builtin_bit_cast(bf16x8_t, u);
-}
+using namespace gt_attn_frag;
 
 template <int NT>   // key tiles of 32 (T <= 32*NT)
 __global__ __launch_bounds__(256, 1) void gt_attn_fwd_mfma_kernel(
@@ -470,8 +451,6 @@ int launch_fwd_long(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, c
 //   dS^T and dropout(P)^T leave as bf16 [B,H,T,TI] (query index contiguous) for pass 2.
 // Pass 2 (per 32-key block): dK^T = Q^T dS, dV^T = dO^T dropout(P) with Q^T / dO^T through
 // transposing reads of LDS-staged Q / dO and the B operands straight from the pass-1 buffers.
-constexpr int BTP = 40;            // pitch (halfs) of the transposed band tables [16][32 + pad]
-
 template <int NT, int WV, bool ONE_TILE>
 __global__ __launch_bounds__(64 * WV, 1) void gt_attn_bwd_q_mfma_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,

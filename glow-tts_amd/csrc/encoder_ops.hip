@@ -952,12 +952,14 @@ extern "C" int gt_attn_fwd(const void* q, const void* k, const void* v, int ld, 
                            float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream)
 {
   if (!q || !k || !v || !Ek || !Ev || !lens || !out || !P || B <= 0 || T <= 0 || H <= 0) return GT_E_INVAL;
-  if (D > AT_MAXD || (D & 1) || win < 0 || drop_p >= 1.f) return GT_E_UNSUPPORTED;
+  if (D > AT_MAXD || (D & 1) || win < 0 || drop_p >= 1.f || T > GT_ATTN_LONG_MAX_T) return GT_E_UNSUPPORTED;
   uint32_t th; float sc;
   gt_drop_params(drop_p, &th, &sc);
   {
-    const int rc = gt_attn_fwd_mfma_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, P, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
+    int rc = gt_attn_fwd_mfma_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, P, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
     if (rc != 1) return rc;                        // handled (or failed loudly) on the MFMA path
+    rc = gt_attn_fwd_long_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, P, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
+    if (rc != 1) return rc;                        // ... or on the key-tiled one (505 < T)
   }
   const size_t lds = attn_lds(T, D, win, (size_t)4 * D + (size_t)AT_QT * T);
   if (lds > 160 * 1024) return GT_E_UNSUPPORTED;
@@ -983,14 +985,17 @@ extern "C" int gt_attn_bwd(const void* q, const void* k, const void* v, int ld, 
                            int B, int T, int Tp, const int32_t* row0, int H, int D, int win, float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream)
 {
   if (!q || !k || !v || !Ek || !Ev || !lens || !dout || !P || !workspace || !dq || !dk || !dv || !dEk || !dEv) return GT_E_INVAL;
-  if (D > AT_MAXD || (D & 1) || win < 0 || drop_p >= 1.f) return GT_E_UNSUPPORTED;
+  if (D > AT_MAXD || (D & 1) || win < 0 || drop_p >= 1.f || T > GT_ATTN_LONG_MAX_T) return GT_E_UNSUPPORTED;
   if (workspace_bytes < gt_attn_bwd_workspace_bytes(B, T, H)) return GT_E_INVAL;
   float* dS_ws = static_cast<float*>(workspace);
   uint32_t th; float sc;
   gt_drop_params(drop_p, &th, &sc);
   {
-    const int rc = gt_attn_bwd_mfma_impl(q, k, v, ld, Ek, Ev, lens, dout, lddo, P, workspace, workspace_bytes, dq, dk, dv, lddq,
-                                         dEk, dEv, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
+    int rc = gt_attn_bwd_mfma_impl(q, k, v, ld, Ek, Ev, lens, dout, lddo, P, workspace, workspace_bytes, dq, dk, dv, lddq,
+                                   dEk, dEv, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
+    if (rc != 1) return rc;
+    rc = gt_attn_bwd_long_impl(q, k, v, ld, Ek, Ev, lens, dout, lddo, P, workspace, workspace_bytes, dq, dk, dv, lddq,
+                               dEk, dEv, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
     if (rc != 1) return rc;
   }
   const size_t lds1 = attn_lds(T, D, win, (size_t)2 * (2 * win + 1) * D + (size_t)AT_QT * 2 * D + (size_t)AT_QT * T);

@@ -28,6 +28,17 @@ int gt_attn_bwd_mfma_impl(const void* q, const void* k, const void* v, int ld, c
                           int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win, uint32_t drop_thresh, uint32_t drop_seed, float drop_scale,
                           const uint32_t* seed_dev, void* stream);
 
+// Key-tiled MFMA attention for 505 < T <= GT_ATTN_LONG_MAX_T (attn_long.hip, gt_attn_long_shape); same arguments, same workspace
+// format and the same "returns 1 when the shape or the layout is not handled" as the two entries above.
+int gt_attn_fwd_long_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                          const int32_t* lens, void* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win,
+                          uint32_t drop_thresh, uint32_t drop_seed, float drop_scale, const uint32_t* seed_dev, void* stream);
+int gt_attn_bwd_long_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                          const int32_t* lens, const void* dout, int lddo, const float* P, void* ws, size_t ws_bytes,
+                          void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
+                          int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win, uint32_t drop_thresh, uint32_t drop_seed, float drop_scale,
+                          const uint32_t* seed_dev, void* stream);
+
 // The chip-wide kernel that writes the dense 0/1 path [B, T_x, T_y] (element type path_dtype, GT_DT_*) from the int32
 // [B, T_x + 1] row start columns both MAS kernels leave in their workspace (mas.hip).  0 or GT_E_LAUNCH.
 int gt_mas_expand_launch(const int32_t* starts, void* path, int path_dtype, int B, int T_x, int T_y, void* stream);

@@ -66,7 +66,12 @@ def _ln_bwd(rc, ln, saved, dout_f32, dout_bf, want_da, want_dy, grads, relu_in=F
 
 
 # ----------------------------------------------------------------------------- attention
+ATTN_MAX_T = 4096           # GT_ATTN_LONG_MAX_T of include/glowtts_hip.h: the longest text gt_attn_fwd / gt_attn_bwd take
+
+
 def mha_fwd(rc, att, xb, p, seed):
+    if rc.T > ATTN_MAX_T:       # before any allocation or launch: P and the backward's workspace are 4 B H T^2 bytes each per layer
+        raise ValueError(f"attention takes at most {ATTN_MAX_T} tokens per utterance (GT_ATTN_LONG_MAX_T), got T = {rc.T}")
     dev = xb.device
     R = rc.R
     H, D, C = att.n_heads, att.k_channels, att.channels

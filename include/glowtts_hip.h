@@ -328,11 +328,14 @@ int gt_param_partials_reduce(const gt_partials_args* args, void* stream);
  *   out_i = sum_j dropout(softmax)[i,j] v_j + sum_{|j-i|<=win} dropout(softmax)[i,j] Ev[j-i+win].
  * q,k,v,out: bf16 rows [B*Tp, H*D]; Ek,Ev: [2*win+1, D] fp32 shared by heads; P: [B,H,T,T] fp32
  * (softmax before dropout, kept for the backward); workspace: gt_attn_bwd_workspace_bytes(B,T,H) bytes of
- * scratch, 16-byte aligned; dEk/dEv ACCUMULATE.  D = 96, win = 4, T <= 384 run on bf16 MFMA (gt_attn_mfma_shape), the rest
- * on the generic kernels.
+ * scratch, 16-byte aligned; dEk/dEv ACCUMULATE.  D = 96, win = 4: T <= 384 runs on bf16 MFMA (gt_attn_mfma_shape) and
+ * 505 < T <= GT_ATTN_LONG_MAX_T on key-tiled bf16 MFMA kernels whose LDS and registers do not grow with T (gt_attn_long_shape);
+ * the rest runs on the generic kernels, which hold an utterance-head in LDS: at D = 96, win = 4 the forward to T = 597, the
+ * backward to T = 505 — GT_E_UNSUPPORTED past what fits, and for every T > GT_ATTN_LONG_MAX_T before anything is launched.
+ * P and the workspace are each 4 B H T^2 bytes (4.3 GB at B = 32, H = 2, T = 4096).
  *   workspace   device scratch of at least gt_attn_bwd_workspace_bytes(B,T,H) bytes, 16-byte aligned; after gt_attn_bwd it
  *               holds what the call's second pass read (dS = P (dP - sum_j dP P) / sqrt(D), zero where masked):
- *               on the MFMA kernels bf16 dS^T [B,H,T(key j),TI(query i)], TI = ceil(T/32)*32, followed by dropout(P)^T in
+ *               on the MFMA kernels (both families) bf16 dS^T [B,H,T(key j),TI(query i)], TI = ceil(T/32)*32, followed by dropout(P)^T in
  *               the same shape with the rows of queries i >= lens[b] zero, columns i >= T of both zero;
  *               on the generic kernels fp32 dS [B,H,T(query i),T(key j)].
  * Query rows i >= lens[b] contribute nothing to dk, dv, dEk and dEv (and get dq = 0) whatever dout holds there. */
@@ -340,9 +343,13 @@ int gt_attn_fwd(const void* q, const void* k, const void* v, int ld, const float
                 const int32_t* lens, void* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, int D, int win,
                 float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream);
 size_t gt_attn_bwd_workspace_bytes(int B, int T, int H);
-/* 1 if gt_attn_fwd / gt_attn_bwd run a (T, D, win) shape on the MFMA kernels, 0 if on the generic ones (the dispatchers' own test;
+/* 1 if gt_attn_fwd / gt_attn_bwd run a (T, D, win) shape on the T <= 384 MFMA kernels, 0 if not (the dispatchers' own test;
  * operands laid out as the rows layout leaves them) */
 int gt_attn_mfma_shape(int T, int D, int win);
+/* 1 if they run it on the key-tiled MFMA kernels: D == 96, win == 4, 505 < T <= GT_ATTN_LONG_MAX_T (the token limit of
+ * gt_mas_long_f32).  Both directions switch at the same T, so a backward differentiates what its forward computed. */
+#define GT_ATTN_LONG_MAX_T 4096
+int gt_attn_long_shape(int T, int D, int win);
 int gt_attn_bwd(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
                 const int32_t* lens, const void* dout, int lddo, const float* P, void* workspace, size_t workspace_bytes,
                 void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
