@@ -13,11 +13,26 @@
 //                          ds_read_b64_tr_b16 (pitch 192 B) in the permuted k order that map requires.
 //   O^T += Ev^T band(P)^T  the relative-value term as one K=16 MFMA per 32 channels.
 #include <stdlib.h>
+#include <type_traits>
 #include "attn_frag.h"
 #include "internal.h"
 
+#ifndef ATTN_PHASES
+#define ATTN_PHASES 0                         // dev: shader-clock stamps of the 8 waves of the T <= 160 backward (tools/attn_bwd_phases.py), 0 in every build that ships
+#endif
+
 namespace {
 using namespace gt_attn_frag;
+
+#if ATTN_PHASES
+// [8 waves][128 workgroups][16]
+__device__ unsigned long long g_attn_ph[8 * 128 * 16];
+#define APH(i) do { const unsigned wg_ = blockIdx.y * gridDim.x + blockIdx.x;                                                       \
+                    if ((threadIdx.x & 63) == 0 && wg_ < 128)                                                                       \
+                      g_attn_ph[((threadIdx.x >> 6) * 128 + wg_) * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define APH(i) do { } while (0)
+#endif
 
 template <int NT>   // key tiles of 32 (T <= 32*NT)
 __global__ __launch_bounds__(256, 1) void gt_attn_fwd_mfma_kernel(
@@ -451,7 +466,7 @@ int launch_fwd_long(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, c
 //   dS^T and dropout(P)^T leave as bf16 [B,H,T,TI] (query index contiguous) for pass 2.
 // Pass 2 (per 32-key block): dK^T = Q^T dS, dV^T = dO^T dropout(P) with Q^T / dO^T through
 // transposing reads of LDS-staged Q / dO and the B operands straight from the pass-1 buffers.
-template <int NT, int WV, bool ONE_TILE>
+template <int NT, int WV>
 __global__ __launch_bounds__(64 * WV, 1) void gt_attn_bwd_q_mfma_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,
     const float* __restrict__ Ek, const float* __restrict__ Ev, const int32_t* __restrict__ lens,
@@ -555,9 +570,9 @@ __global__ __launch_bounds__(64 * WV, 1) void gt_attn_bwd_q_mfma_kernel(
 #pragma unroll
       for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
     }
-    if constexpr (ONE_TILE) {
-      // 161 <= T <= 256: holding all NT score tiles of a wave (NT*16 accumulators) next to P and the dropout masks does
-      // not fit the register file.  One tile at a time instead: pass A walks the key tiles for Dsum only, pass B
+    {
+      // 161 <= T <= 384 (T <= 160: gt_attn_bwd_fused_kernel below): holding all NT score tiles of a wave (NT*16 accumulators)
+      // next to P and the dropout masks does not fit the register file.  One tile at a time instead: pass A walks the key tiles for Dsum only, pass B
       // RECOMPUTES each tile's dPd^T (6 MFMAs, operands already in LDS / registers), turns it into dS^T, stores it and
       // feeds dQ^T straight away — live state is one tile + the dQ^T accumulators, whatever NT is.
       auto dp_tile = [&](int t, f32x16_t& st) {
@@ -649,93 +664,6 @@ __global__ __launch_bounds__(64 * WV, 1) void gt_attn_bwd_q_mfma_kernel(
         }
       }
       __builtin_amdgcn_wave_barrier();
-    } else {
-      f32x16_t s[NT];
-  #pragma unroll
-      for (int t = 0; t < NT; ++t) {
-  #pragma unroll
-        for (int e = 0; e < 16; ++e) s[t][e] = 0.f;
-  #pragma unroll
-        for (int ks = 0; ks < 6; ++ks) {
-          const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(Vs + (32 * t + r) * KP + ks * 16 + 8 * hh);
-          s[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, dof[ks], s[t], 0, 0, 0);
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-
-      // pass A: dP in place, Dsum
-      float dsum = 0.f;
-  #pragma unroll
-      for (int t = 0; t < NT; ++t)
-  #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int j0 = 32 * t + 8 * g + 4 * hh;
-          float p4[4] = {0.f, 0.f, 0.f, 0.f};
-          if (vec && j0 + 3 < T) { const float4 pv = *reinterpret_cast<const float4*>(prow + j0); p4[0] = pv.x; p4[1] = pv.y; p4[2] = pv.z; p4[3] = pv.w; }
-          else {
-  #pragma unroll
-            for (int e2 = 0; e2 < 4; ++e2) if (j0 + e2 < T) p4[e2] = prow[j0 + e2];
-          }
-  #pragma unroll
-          for (int e2 = 0; e2 < 4; ++e2) {
-            const int j = j0 + e2;
-            float dp = s[t][4 * g + e2];
-            const int rel = j - i + WIN;
-            if ((unsigned)rel <= 2u * WIN) dp += doe[r * NW + rel];
-            if (drop_thresh) dp = drop_keep(drop_seed, drow, j, drop_thresh) ? dp * drop_scale : 0.f;
-            if (j >= T) dp = 0.f;
-            s[t][4 * g + e2] = dp;
-            dsum += dp * p4[e2];
-          }
-        }
-      dsum += __shfl_xor(dsum, 32);
-      // pass B: dS in place; write dS^T, dropout(P)^T and the band tables
-  #pragma unroll
-      for (int t = 0; t < NT; ++t)
-  #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int j0 = 32 * t + 8 * g + 4 * hh;
-          float p4[4] = {0.f, 0.f, 0.f, 0.f};
-          if (vec && j0 + 3 < T) { const float4 pv = *reinterpret_cast<const float4*>(prow + j0); p4[0] = pv.x; p4[1] = pv.y; p4[2] = pv.z; p4[3] = pv.w; }
-          else {
-  #pragma unroll
-            for (int e2 = 0; e2 < 4; ++e2) if (j0 + e2 < T) p4[e2] = prow[j0 + e2];
-          }
-  #pragma unroll
-          for (int e2 = 0; e2 < 4; ++e2) {
-            const int j = j0 + e2;
-            float ds = p4[e2] * (s[t][4 * g + e2] - dsum) * inv_sqrt;
-            float pd = p4[e2];
-            if (drop_thresh) pd = drop_keep(drop_seed, drow, j, drop_thresh) ? pd * drop_scale : 0.f;
-            if (j >= T || j >= len || i >= len || i >= T) ds = 0.f;          // masked_fill blocks the gradient
-            if (i >= len || i >= T) pd = 0.f;                                // padded queries carry no upstream gradient
-            s[t][4 * g + e2] = ds;
-            if (j < T) {
-              dst_base[(size_t)j * TI + i] = f2bf(ds);
-              pdt_base[(size_t)j * TI + i] = f2bf(pd);
-              const int rel = j - i + WIN;
-              if ((unsigned)rel <= 2u * WIN) { const bf16_t db = f2bf(ds); dSB[r * 16 + rel] = db; dSBT[rel * BTP + r] = db; PdBT[rel * BTP + r] = f2bf(pd); }
-            }
-          }
-        }
-      __builtin_amdgcn_wave_barrier();
-
-      // dQ^T = K^T dS^T + Ek^T band(dS)^T
-  #pragma unroll
-      for (int t = 0; t < NT; ++t)
-  #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          float f8[8];
-  #pragma unroll
-          for (int e = 0; e < 8; ++e) f8[e] = s[t][8 * s2 + e];
-          const bf16x8_t pf = pack8(f8);
-  #pragma unroll
-          for (int dt = 0; dt < 3; ++dt) {
-            const bf16_t* ka = Ks + (32 * t + 16 * s2 + 4 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
-            const bf16x8_t af = tr_frag8(ka, ka + 8 * VP);
-            o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, pf, o[dt], 0, 0, 0);
-          }
-        }
     }
     {
       const bf16x8_t bfp = *reinterpret_cast<const bf16x8_t*>(dSB + r * 16 + 8 * hh);
@@ -855,7 +783,402 @@ __global__ __launch_bounds__(256, 1) void gt_attn_bwd_kv_mfma_kernel(
   }
 }
 
-template <int NT, int WV, bool ONE_TILE = (NT > 5)>
+// =========================================================================================
+// Backward for T <= 160: the two passes above in ONE workgroup of 8 waves per (utterance, head), grid (H, B).
+//   phase 1  waves 0..4 take one 32-query tile each (one score tile live at a time, as the kernel above): the dropout bit of an
+//            element is hashed ONCE (16 bits per key tile kept between the Dsum pass and the dS pass), the band code runs only
+//            for the key tiles w-1, w, w+1 that can meet the band of query tile w.  dS^T goes to LDS [j][i]; P'^T leaves per
+//            32 x 32 tile through a per-wave LDS stage as 16-byte row segments.  P is read in both passes (8-byte loads for even
+//            T): all 80 values of a lane held between the passes need 256 + 29 registers at two waves per SIMD (spills).
+//   barrier  (with its workgroup-scope fences: phase 2 reads P'^T rows other waves stored)
+//   phase 2  Q over K's area, dO over V's; waves 0..4 take one 32-key tile each (dK^T = Q^T dS, dV^T = dO^T P' with dS^T from LDS
+//            and P'^T from the L2-hot workspace, the whole row in flight under the staging); waves 5..7 take the dEk / dEv
+//            contraction of query tiles {0, 3}, {1, 4}, {2} (one LDS accumulation per wave, one global atomic per address); all waves then
+//            store the dS^T rows (16-byte segments, LDS -> workspace) — last, because a store in front of a load holds that load's
+//            wait (one counter for both).
+// LDS (bytes): K|Q [160][VP] 30720, V|dO [160][KP] 33280, dS^T [160][DSP] 53760, EkT 3072, Ev [9][KP] 1872 and DOE [5][32][9] 5760
+// (the dE accumulators alias these two in phase 2), band tables 5 x 3584, P'^T stage 5 x 2560: 159184.
+constexpr int FNT = 5, FTP = FNT * 32, FTH = 512;
+constexpr int DSP = 168;           // dS^T pitch in halfs (336 B): conflict-free ds_read_b128 over 16 rows, 16-byte row segments
+constexpr int PWP = 40;            // pitch of the per-wave P'^T stage [32 keys][32 queries + pad]
+constexpr int FBAND = 32 * 16 + 2 * 16 * BTP;
+constexpr size_t FUSED_LDS = (size_t)FTP * VP * 2 + FTP * KP * 2 + FTP * DSP * 2 + D * 16 * 2 + NW * KP * 2 + FNT * 32 * NW * 4 +
+                             FNT * FBAND * 2 + FNT * 32 * PWP * 2;
+static_assert(2 * NW * D * 4 <= NW * KP * 2 + FNT * 32 * NW * 4, "the dE accumulators alias Ev | DOE");
+static_assert(FUSED_LDS <= 160 * 1024, "LDS budget");
+
+template <int N> using ic_t = std::integral_constant<int, N>;
+
+__global__ __launch_bounds__(FTH, 1) void gt_attn_bwd_fused_kernel(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,
+    const float* __restrict__ Ek, const float* __restrict__ Ev, const int32_t* __restrict__ lens,
+    const bf16_t* __restrict__ dout, int lddo, const float* __restrict__ P,
+    bf16_t* dST, bf16_t* PdT, int TI,
+    bf16_t* __restrict__ dq, bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int lddq, float* __restrict__ dEk, float* __restrict__ dEv,
+    int T, int Tp, const int32_t* row0, int H, uint32_t drop_thresh, uint32_t drop_seed, float drop_scale, const uint32_t* __restrict__ seed_dev)
+{
+  APH(0);
+  if (seed_dev) drop_seed ^= *seed_dev;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  bf16_t* Ks  = reinterpret_cast<bf16_t*>(smem);                 // [FTP][VP]   A of dQ^T (transposing reads); phase 2: Q
+  bf16_t* Vs  = Ks + FTP * VP;                                   // [FTP][KP]   A of dPd^T (ds_read_b128);     phase 2: dO [FTP][VP]
+  bf16_t* dSs = Vs + FTP * KP;                                   // [FTP][DSP]  dS^T[j][i]
+  bf16_t* EkT = dSs + FTP * DSP;                                 // [96][16]
+  bf16_t* Evs = EkT + D * 16;                                    // [NW][KP]
+  float*  DOE = reinterpret_cast<float*>(Evs + NW * KP);         // [FNT][32][NW]
+  bf16_t* WB  = reinterpret_cast<bf16_t*>(DOE + FNT * 32 * NW);  // per query tile: dSB[32][16] | dSBT[16][BTP] | PdBT[16][BTP]
+  bf16_t* PW  = WB + FNT * FBAND;                                // per query tile: P'^T stage [32][PWP]
+  float*  Acc = reinterpret_cast<float*>(Evs);                   // [2][NW][D]  dEk | dEv of this (b, h): phase 2 only
+
+  const int b = blockIdx.y, h = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, hh = lane >> 5;
+  const int len = lens[b];
+  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
+  // rows this utterance owns behind rbase (frames + trailing halo): in the ragged layout frame indices past them belong
+  // to the NEXT utterance — reads are clamped onto the (zero) trailing halo row, stores are dropped
+  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;
+  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
+  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
+  bf16_t* dst_base = dST + ((size_t)b * H + h) * T * TI;
+  bf16_t* pdt_base = PdT + ((size_t)b * H + h) * T * TI;
+  const bool tile = w < FNT && 32 * w < T;                       // wave-uniform: this wave owns query tile w, later key tile w
+
+  for (int x = tid; x < FTP * (D / 8); x += FTH) {
+    const int j = x / (D / 8), c8 = x - j * (D / 8);
+    uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
+    if (j < T) {
+      kk = *reinterpret_cast<const uint4*>(k + RW(j) * ld + h * D + c8 * 8);
+      vv = *reinterpret_cast<const uint4*>(v + RW(j) * ld + h * D + c8 * 8);
+    }
+    *reinterpret_cast<uint4*>(Ks + j * VP + c8 * 8) = kk;
+    *reinterpret_cast<uint4*>(Vs + j * KP + c8 * 8) = vv;
+  }
+  for (int x = tid; x < NW * D; x += FTH) { const int rr = x / D, c = x - rr * D; Evs[rr * KP + c] = f2bf(Ev[x]); }
+  for (int x = tid; x < D * 16; x += FTH) { const int d = x >> 4, rr = x & 15; EkT[x] = rr < NW ? f2bf(Ek[rr * D + d]) : (bf16_t)0; }
+  for (int x = tid; x < FNT * FBAND; x += FTH) WB[x] = 0;         // band tables start at zero
+  __syncthreads();
+  APH(1);
+
+  if (tile) {
+    const int i = 32 * w + r;                                    // this lane's query
+    const int ic = i < T ? i : T - 1;
+    float* doe = DOE + w * 32 * NW;
+    bf16_t* dSB = WB + w * FBAND;
+    bf16_t* dSBT = dSB + 32 * 16;
+    bf16_t* PdBT = dSBT + 16 * BTP;
+    bf16_t* pw = PW + w * 32 * PWP;
+    const float* prow = P + (((size_t)b * H + h) * T + ic) * T;
+
+    const int palign = (T & 3) == 0 ? 4 : (T & 1) == 0 ? 2 : 1;  // alignment (floats) of prow + a multiple of 4
+    auto load_p = [&](int t, float* pt) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int j0 = 32 * t + 8 * g + 4 * hh;
+        float* p4 = pt + 4 * g;
+        p4[0] = p4[1] = p4[2] = p4[3] = 0.f;
+        if (palign == 4 && j0 + 3 < T) { const float4 pv = *reinterpret_cast<const float4*>(prow + j0); p4[0] = pv.x; p4[1] = pv.y; p4[2] = pv.z; p4[3] = pv.w; }
+        else if (palign == 2 && j0 + 3 < T) {
+          const float2 pa = *reinterpret_cast<const float2*>(prow + j0), pc = *reinterpret_cast<const float2*>(prow + j0 + 2);
+          p4[0] = pa.x; p4[1] = pa.y; p4[2] = pc.x; p4[3] = pc.y;
+        } else {
+#pragma unroll
+          for (int e2 = 0; e2 < 4; ++e2) if (j0 + e2 < T) p4[e2] = prow[j0 + e2];
+        }
+      }
+    };
+
+    bf16x8_t dof[6];
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks)
+      dof[ks] = *reinterpret_cast<const bf16x8_t*>(dout + RW(ic) * lddo + h * D + ks * 16 + 8 * hh);
+    {
+      f32x16_t acc;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) {
+        const uint4 z = make_uint4(0, 0, 0, 0);
+        bf16x8_t af = __builtin_bit_cast(bf16x8_t, z);           // rows >= 9 of Ev are zero and not kept
+        if (r < NW) af = *reinterpret_cast<const bf16x8_t*>(Evs + r * KP + ks * 16 + 8 * hh);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, dof[ks], acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) doe[r * NW + e + 4 * hh] = acc[e];
+      if (hh == 0) doe[r * NW + 8] = acc[4];
+    }
+    const float inv_sqrt = rsqrtf((float)D);
+    const uint32_t drow = (uint32_t)((b * H + h) * T + i);
+    const bool qdead = i >= len || i >= T;
+    const int jlive = len < T ? len : T;
+    f32x16_t o[3];
+    auto dp_tile = [&](int t, f32x16_t& st) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) st[e] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) {
+        const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(Vs + (32 * t + r) * KP + ks * 16 + 8 * hh);
+        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, dof[ks], st, 0, 0, 0);
+      }
+    };
+    __builtin_amdgcn_wave_barrier();                             // doe written by both lane halves
+    APH(2);
+
+    // pass A: Dsum; the dropout bits of the wave's elements, 16 per key tile
+    uint32_t km[FNT];
+    float dsum = 0.f;
+    auto pass_a = [&](auto tc, auto bandc) {
+      constexpr int t = decltype(tc)::value;
+      constexpr bool BAND = decltype(bandc)::value;
+      f32x16_t st;
+      dp_tile(t, st);
+      float pt[16];
+      load_p(t, pt);
+      uint32_t m = 0;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int j = 32 * t + 8 * (e >> 2) + 4 * hh + (e & 3);
+        float dp = st[e];
+        if (BAND) { const int rel = j - i + WIN; if ((unsigned)rel <= 2u * WIN) dp += doe[r * NW + rel]; }
+        if (drop_thresh) {
+          const bool keep = drop_keep(drop_seed, drow, j, drop_thresh);
+          m |= (uint32_t)keep << e;
+          dp = keep ? dp * drop_scale : 0.f;
+        }
+        dsum += dp * pt[e];                                      // j >= T: P is 0 and dp finite (V rows of zeros, DOE), the term is 0
+      }
+      km[t] = m;
+    };
+    // pass B: the tile's dPd^T again (6 MFMAs), dS^T into LDS, P'^T through the stage, the band tables, then dQ^T
+    auto pass_b = [&](auto tc, auto bandc) {
+      constexpr int t = decltype(tc)::value;
+      constexpr bool BAND = decltype(bandc)::value;
+      f32x16_t st;
+      dp_tile(t, st);
+      float pt[16];
+      load_p(t, pt);
+      const uint32_t m = km[t];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int jl = 8 * (e >> 2) + 4 * hh + (e & 3), j = 32 * t + jl;
+        const bool keep = (m >> e) & 1u;
+        float dp = st[e];
+        if (BAND) { const int rel = j - i + WIN; if ((unsigned)rel <= 2u * WIN) dp += doe[r * NW + rel]; }
+        if (drop_thresh) dp = keep ? dp * drop_scale : 0.f;
+        float ds = pt[e] * (dp - dsum) * inv_sqrt;
+        float pd = pt[e];
+        if (drop_thresh) pd = keep ? pd * drop_scale : 0.f;
+        if (j >= jlive || qdead) ds = 0.f;                                   // masked_fill blocks the gradient (keys >= T or >= len)
+        if (qdead) pd = 0.f;                                                 // padded queries carry no upstream gradient
+        st[e] = ds;
+        const bf16_t db = f2bf(ds), pb = f2bf(pd);
+        dSs[j * DSP + i] = db;
+        pw[jl * PWP + r] = pb;
+        if (BAND) {
+          const int rel = j - i + WIN;
+          if ((unsigned)rel <= 2u * WIN && j < T) { dSB[r * 16 + rel] = db; dSBT[rel * BTP + r] = db; PdBT[rel * BTP + r] = pb; }
+        }
+      }
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        float f8[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f8[e] = st[8 * s2 + e];
+        const bf16x8_t pf = pack8(f8);
+#pragma unroll
+        for (int dt = 0; dt < 3; ++dt) {
+          const bf16_t* ka = Ks + (32 * t + 16 * s2 + 4 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          const bf16x8_t af = tr_frag8(ka, ka + 8 * VP);
+          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, pf, o[dt], 0, 0, 0);
+        }
+      }
+      // the tile's P'^T rows (keys) leave as 16-byte segments of 8 queries: lane -> (row, segment), two rows per lane
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        const int row = (lane >> 2) + 16 * s2, seg = lane & 3;
+        const bf16x8_t x = *reinterpret_cast<const bf16x8_t*>(pw + row * PWP + 8 * seg);
+        if (32 * t + row < T) *reinterpret_cast<bf16x8_t*>(pdt_base + (size_t)(32 * t + row) * TI + 32 * w + 8 * seg) = x;
+      }
+      __builtin_amdgcn_wave_barrier();
+    };
+    // key tiles below T, unrolled with the tile index a constant (as runtime loops over t, next tile's P prefetched, the kernel
+    // measured 51.4 instead of 47.4 us at T = 150); the band of query tile w meets the key tiles w-1, w, w+1 only
+    auto tiles = [&](auto&& f) {
+      auto one = [&](auto tc) {
+        constexpr int t = decltype(tc)::value;
+        if (32 * t < T) {                                        // wave-uniform
+          if (t + 1 >= w && t <= w + 1) f(tc, std::true_type{}); else f(tc, std::false_type{});
+        }
+      };
+      one(ic_t<0>{}); one(ic_t<1>{}); one(ic_t<2>{}); one(ic_t<3>{}); one(ic_t<4>{});
+    };
+#pragma unroll
+    for (int t = 0; t < FNT; ++t) km[t] = 0;
+    tiles(pass_a);
+    dsum += __shfl_xor(dsum, 32);
+    APH(3);
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
+    }
+    tiles(pass_b);
+    APH(4);
+    {
+      const bf16x8_t bfp = *reinterpret_cast<const bf16x8_t*>(dSB + r * 16 + 8 * hh);
+#pragma unroll
+      for (int dt = 0; dt < 3; ++dt) {
+        const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(EkT + (32 * dt + r) * 16 + 8 * hh);
+        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfp, o[dt], 0, 0, 0);
+      }
+    }
+    if (i < T && i <= nv1) {
+#pragma unroll
+      for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int d = 32 * dt + 8 * g + 4 * hh;
+          *reinterpret_cast<uint2*>(dq + (rbase + i) * lddq + h * D + d) =
+              make_uint2(pack2bf(o[dt][4 * g], o[dt][4 * g + 1]), pack2bf(o[dt][4 * g + 2], o[dt][4 * g + 3]));
+        }
+    }
+  }
+  APH(5);
+  __syncthreads();                                               // with its workgroup-scope fences: the P'^T rows stored above are read back below by other waves of this workgroup
+  APH(6);
+
+  // ---- phase 2: K, V, Ev and DOE are dead; Q and dO take the operand areas
+  const int nks = TI / 16;
+  bf16x8_t bpd[2 * FNT];                                          // key 32 w + r's whole P'^T row: in flight under the staging below
+  if (tile) {
+    const int j = 32 * w + r, jc = j < T ? j : T - 1;
+    const bf16_t* pdr = pdt_base + (size_t)jc * TI;
+#pragma unroll
+    for (int ks = 0; ks < 2 * FNT; ++ks) {
+      const uint4 z = make_uint4(0, 0, 0, 0);
+      bpd[ks] = __builtin_bit_cast(bf16x8_t, z);
+      if (ks < nks) bpd[ks] = *reinterpret_cast<const bf16x8_t*>(pdr + 16 * ks + 8 * hh);
+    }
+  }
+  bf16_t* Qs = Ks;
+  bf16_t* dOs = Vs;                                              // [FTP][VP]
+  for (int x = tid; x < FTP * (D / 8); x += FTH) {
+    const int j = x / (D / 8), c8 = x - j * (D / 8);
+    uint4 qq = make_uint4(0, 0, 0, 0), dd = qq;
+    if (j < T) {
+      qq = *reinterpret_cast<const uint4*>(q + RW(j) * ld + h * D + c8 * 8);
+      dd = *reinterpret_cast<const uint4*>(dout + RW(j) * lddo + h * D + c8 * 8);
+    }
+    *reinterpret_cast<uint4*>(Qs + j * VP + c8 * 8) = qq;
+    *reinterpret_cast<uint4*>(dOs + j * VP + c8 * 8) = dd;
+  }
+  for (int x = tid; x < 2 * NW * D; x += FTH) Acc[x] = 0.f;
+  __syncthreads();
+  APH(7);
+
+  if (tile) {                                                    // key tile w: dK^T = Q^T dS, dV^T = dO^T P'
+    const int j = 32 * w + r;
+    const bf16_t* dsr = dSs + j * DSP;
+    f32x16_t ak[3], av[3];
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) { ak[dt][e] = 0.f; av[dt][e] = 0.f; }
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2 * FNT; ++ks) {
+      if (ks < nks) {
+        const bf16x8_t bds = *reinterpret_cast<const bf16x8_t*>(dsr + 16 * ks + 8 * hh);   // dS[i = 16ks+8hh.., j]
+#pragma unroll
+        for (int dt = 0; dt < 3; ++dt) {
+          const bf16_t* qa = Qs + (16 * ks + 8 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          const bf16_t* da = dOs + (16 * ks + 8 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          ak[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag8(qa, qa + 4 * VP), bds, ak[dt], 0, 0, 0);
+          av[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag8(da, da + 4 * VP), bpd[ks], av[dt], 0, 0, 0);
+        }
+      }
+    }
+    if (j < T && j <= nv1) {
+#pragma unroll
+      for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int d = 32 * dt + 8 * g + 4 * hh;
+          *reinterpret_cast<uint2*>(dk + RW(j) * lddq + h * D + d) =
+              make_uint2(pack2bf(ak[dt][4 * g], ak[dt][4 * g + 1]), pack2bf(ak[dt][4 * g + 2], ak[dt][4 * g + 3]));
+          *reinterpret_cast<uint2*>(dv + RW(j) * lddq + h * D + d) =
+              make_uint2(pack2bf(av[dt][4 * g], av[dt][4 * g + 1]), pack2bf(av[dt][4 * g + 2], av[dt][4 * g + 3]));
+        }
+    }
+  }
+  APH(9);
+  // dEk[r'][d] += sum_i dSBT[r'][i] Q[i][d];  dEv[r'][d] += sum_i PdBT[r'][i] dO[i][d]: the three waves without a key tile, query
+  // tiles {0, 3}, {1, 4}, {2} chained in the MFMA accumulators (K = the queries of the wave's tiles), one LDS accumulation per wave
+  if (w >= FNT && 32 * (w - FNT) < T) {
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {
+#pragma unroll
+      for (int dt = 0; dt < 3; ++dt) {
+        f32x16_t acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll 1
+        for (int x = w - FNT; x < FNT && 32 * x < T; x += 8 - FNT) {
+          const bf16_t* At = WB + x * FBAND + 32 * 16 + (which ? 16 * BTP : 0);
+          const bf16_t* Bt = (which ? dOs : Qs) + 32 * x * VP;
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) {
+            bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(At + (r & 15) * BTP + 16 * ks + 8 * hh);
+            if (r >= 16) { const uint4 z = make_uint4(0, 0, 0, 0); af = __builtin_bit_cast(bf16x8_t, z); }
+            const bf16_t* ba = Bt + (16 * ks + 8 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+            const bf16x8_t bf_ = tr_frag8(ba, ba + 4 * VP);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf_, acc, 0, 0, 0);
+          }
+        }
+        float* dstA = Acc + which * NW * D;
+        const int d = 32 * dt + r;                                   // D layout: column = d (lane&31), row r' = (e&3)+8(e>>2)+4hh
+#pragma unroll
+        for (int e = 0; e < 4; ++e) atomicAdd(dstA + (e + 4 * hh) * D + d, acc[e]);
+        if (hh == 0) atomicAdd(dstA + 8 * D + d, acc[4]);
+      }
+    }
+  }
+  APH(10);
+  {                                                              // dS^T rows j < T, all TI columns, as 16-byte segments
+    const int nseg = TI >> 3;
+    for (int x = tid; x < T * nseg; x += FTH) {
+      const int j = x / nseg, s = x - j * nseg;
+      *reinterpret_cast<bf16x8_t*>(dst_base + (size_t)j * TI + 8 * s) = *reinterpret_cast<const bf16x8_t*>(dSs + j * DSP + 8 * s);
+    }
+  }
+  __syncthreads();
+  for (int y = tid; y < NW * D; y += FTH) {
+    if (Acc[y] != 0.f) atomicAdd(dEk + y, Acc[y]);
+    if (Acc[NW * D + y] != 0.f) atomicAdd(dEv + y, Acc[NW * D + y]);
+  }
+  APH(11);
+}
+
+int launch_bwd_fused(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const float* Ek, const float* Ev, const int32_t* lens,
+                     const bf16_t* dout, int lddo, const float* P, bf16_t* ws, bf16_t* dq, bf16_t* dk, bf16_t* dv, int lddq,
+                     float* dEk, float* dEv, int B, int T, int Tp, const int32_t* row0, int H, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, hipStream_t st)
+{
+  const int TI = ((T + 31) / 32) * 32;
+  bf16_t* dST = ws;
+  bf16_t* PdT = ws + (size_t)B * H * T * TI;
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_bwd_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH;
+    attr = true;
+  }
+  if (T > FTP) return 1;
+  hipLaunchKernelGGL(gt_attn_bwd_fused_kernel, dim3(H, B), dim3(FTH), FUSED_LDS, st,
+                     q, k, v, ld, Ek, Ev, lens, dout, lddo, P, dST, PdT, TI, dq, dk, dv, lddq, dEk, dEv, T, Tp, row0, H, th, sd, sc, seed_dev);
+  return gt_launch_status(__func__);
+}
+
+template <int NT, int WV>
 int launch_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const float* Ek, const float* Ev, const int32_t* lens,
                const bf16_t* dout, int lddo, const float* P, bf16_t* ws, bf16_t* dq, bf16_t* dk, bf16_t* dv, int lddq,
                float* dEk, float* dEv, int B, int T, int Tp, const int32_t* row0, int H, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, hipStream_t st)
@@ -870,12 +1193,12 @@ int launch_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const 
   const size_t lds2 = (size_t)2 * TPAD * VP * 2;
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_bwd_q_mfma_kernel<NT, WV, ONE_TILE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_bwd_q_mfma_kernel<NT, WV>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_bwd_kv_mfma_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH;
     attr = true;
   }
   if (lds1 > 160 * 1024 || lds2 > 160 * 1024) return 1;
-  hipLaunchKernelGGL((gt_attn_bwd_q_mfma_kernel<NT, WV, ONE_TILE>), dim3((T + 32 * WV - 1) / (32 * WV), H, B), dim3(64 * WV), lds1, st,
+  hipLaunchKernelGGL((gt_attn_bwd_q_mfma_kernel<NT, WV>), dim3((T + 32 * WV - 1) / (32 * WV), H, B), dim3(64 * WV), lds1, st,
                      q, k, v, ld, Ek, Ev, lens, dout, lddo, P, dST, PdT, TI, dq, lddq, dEk, dEv, T, Tp, row0, H, th, sd, sc, seed_dev);
   hipLaunchKernelGGL(gt_attn_bwd_kv_mfma_kernel<NT>, dim3((T + 127) / 128, H, B), dim3(256), lds2, st,
                      q, ld, dout, lddo, dST, PdT, TI, dk, dv, lddq, T, Tp, row0, H);
@@ -883,6 +1206,13 @@ int launch_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const 
 }
 
 }  // namespace
+
+#if ATTN_PHASES
+extern "C" int gt_dev_attn_phases(void* dst, size_t bytes)
+{
+  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_attn_ph), bytes < sizeof(g_attn_ph) ? bytes : sizeof(g_attn_ph)) == hipSuccess ? 0 : -1;
+}
+#endif
 
 size_t gt_attn_bwd_mfma_ws_bytes(int B, int T, int H)
 {
@@ -907,9 +1237,8 @@ int gt_attn_bwd_mfma_impl(const void* q, const void* k, const void* v, int ld, c
   const bf16_t* dd = static_cast<const bf16_t*>(dout);
   bf16_t* w16 = static_cast<bf16_t*>(ws);
   bf16_t* dqq = static_cast<bf16_t*>(dq); bf16_t* dkk = static_cast<bf16_t*>(dk); bf16_t* dvv = static_cast<bf16_t*>(dv);
-  // (T <= 160 through the one-tile-at-a-time form of the longer sequences — <5, 4, true>: 138 registers instead of 362 — measured 66.6 vs
-  //  71.0 us back to back and 13 us of a 4.4 ms step: within the noise, not taken; 5 waves per workgroup, one workgroup per head: 460 us)
-  if (T <= 160) return launch_bwd<5, 4>(qq, kk, vv, ld, Ek, Ev, lens, dd, lddo, P, w16, dqq, dkk, dvv, lddq, dEk, dEv, B, T, Tp, row0, H, th, sd, sc, seed_dev, st);
+  // T <= 160: the whole backward of one (utterance, head) in one workgroup (gt_attn_bwd_fused_kernel)
+  if (T <= 160) return launch_bwd_fused(qq, kk, vv, ld, Ek, Ev, lens, dd, lddo, P, w16, dqq, dkk, dvv, lddq, dEk, dEv, B, T, Tp, row0, H, th, sd, sc, seed_dev, st);
   // 161 <= T <= 256: 8 key tiles, 2 waves per workgroup (153 KB of LDS), one score tile live at a time (recompute form:
   // the first version kept all 8 tiles in registers, needed scratch and faulted — see DESIGN.md §4.5)
   if (T <= 256) return launch_bwd<8, 2>(qq, kk, vv, ld, Ek, Ev, lens, dd, lddo, P, w16, dqq, dkk, dvv, lddq, dEk, dEv, B, T, Tp, row0, H, th, sd, sc, seed_dev, st);
