@@ -156,12 +156,15 @@ PROTOTYPES = {
                                       c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "gt_synth_lengths": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "gt_synth_prior": (STATUS, [c_void_p, c_void_p]),
+    "gt_synth_lengths_long": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gt_synth_prior_long": (STATUS, [c_void_p, c_void_p]),
     "gt_synth_prior_args_size": (c_int, []),
     "gt_randn_rows": (STATUS, [c_void_p, c_int, c_int, c_u32, c_u32, c_float, c_void_p]),
     "gt_synth_call_size": (c_int, []),
     "gt_synth_geometry": (STATUS, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),
     "gt_synth_prior_call": (STATUS, [c_void_p, c_void_p, c_void_p]),
+    "gt_synth_prior_long_call": (STATUS, [c_void_p, c_void_p, c_void_p]),
     "gt_randn_rows_call": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_u32, c_int, c_void_p]),
     "gt_synth_call_ext_size": (c_int, []),
     "gt_randn_keyed": (STATUS, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_u32, c_u32, c_float, c_void_p]),
@@ -197,6 +200,7 @@ class StepCtx(ctypes.Structure):
 
 
 STEP_MAX_COPIES, STEP_MAX_CTX, STEP_MAX_B = 10, 3, 1024
+SYNTH_MAX_TX, SYNTH_LONG_MAX_TX = 512, 4096      # tokens gt_synth_lengths / gt_synth_prior[_call] take, and their *_long forms (GT_SYNTH_LONG_MAX_TX)
 
 
 class StepInputsArgs(ctypes.Structure):

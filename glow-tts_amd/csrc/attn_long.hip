@@ -38,6 +38,9 @@ constexpr int TILE_U4 = 32 * (D / 8);          // uint4s of one staged [32][VP] 
 
 // =========================================================================================
 // Forward: one workgroup per (utterance, head, 128 queries), a wave owns 32 queries.
+// STORE_P = false (gt_attn_fwd with P == NULL: a forward nobody differentiates, synthesis): pass 2 leaves out its P stores and
+// nothing else, so `out` is the same bit for bit.
+template <bool STORE_P>
 __global__ __launch_bounds__(256, 2) void gt_attn_long_fwd_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,
     const float* __restrict__ Ek, const float* __restrict__ Ev, const int32_t* __restrict__ lens,
@@ -156,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void gt_attn_long_fwd_kernel(
   const float rden = active ? 1.0f / den : 0.f;
 
   // ---- pass 2: P = softmax, dropout, O^T = V^T P^T (+ Ev^T band(P)^T); V tile t in ring slot t & 1
-  float* prow = Pout + (((size_t)b * H + h) * T + ic) * T;
+  float* prow = STORE_P ? Pout + (((size_t)b * H + h) * T + ic) * T : nullptr;
   const uint32_t drow = (uint32_t)((b * H + h) * T + i);
   const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
   const bool vec = (T & 3) == 0;
@@ -183,7 +186,7 @@ __global__ __launch_bounds__(256, 2) void gt_attn_long_fwd_kernel(
         float p4[4];
 #pragma unroll
         for (int e2 = 0; e2 < 4; ++e2) p4[e2] = __expf(st[4 * g + e2] - mx) * rden;
-        if (i < T) {
+        if (STORE_P && i < T) {
           if (vec && j0 + 3 < T) *reinterpret_cast<float4*>(prow + j0) = make_float4(p4[0], p4[1], p4[2], p4[3]);
           else {
 #pragma unroll
@@ -607,7 +610,8 @@ int gt_attn_fwd_long_impl(const void* q, const void* k, const void* v, int ld, c
 {
   if (!gt_attn_long_shape(T, Dh, win) || (ld & 7) || (ldo & 3)) return 1;
   if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return 1;
-  hipLaunchKernelGGL(gt_attn_long_fwd_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(P ? gt_attn_long_fwd_kernel<true> : gt_attn_long_fwd_kernel<false>, dim3((T + 127) / 128, H, B), dim3(256), 0,
+                     static_cast<hipStream_t>(stream),
                      static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
                      static_cast<bf16_t*>(out), ldo, P, T, Tp, row0, H, th, sd, sc, seed_dev);
   return gt_launch_status(__func__);

@@ -951,10 +951,15 @@ extern "C" int gt_attn_fwd(const void* q, const void* k, const void* v, int ld, 
                            const int32_t* lens, void* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, int D, int win,
                            float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream)
 {
-  if (!q || !k || !v || !Ek || !Ev || !lens || !out || !P || B <= 0 || T <= 0 || H <= 0) return GT_E_INVAL;
+  if (!q || !k || !v || !Ek || !Ev || !lens || !out || B <= 0 || T <= 0 || H <= 0) return GT_E_INVAL;
   if (D > AT_MAXD || (D & 1) || win < 0 || drop_p >= 1.f || T > GT_ATTN_LONG_MAX_T) return GT_E_UNSUPPORTED;
   uint32_t th; float sc;
   gt_drop_params(drop_p, &th, &sc);
+  if (!P) {                                        // a forward that stores no P: the key-tiled kernel, and nothing else
+    if (!gt_attn_long_shape(T, D, win)) return GT_E_INVAL;
+    const int rc = gt_attn_fwd_long_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, P, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
+    return rc == 1 ? GT_E_ALIGN : rc;              // 1: strides / operand alignment it does not take
+  }
   {
     int rc = gt_attn_fwd_mfma_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, P, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
     if (rc != 1) return rc;                        // handled (or failed loudly) on the MFMA path

@@ -16,6 +16,9 @@
 #define SF_FRAMES 64         // ... = frames of it
 #define SF_LD (SF_FRAMES + 1)   // LDS pitch of a channel's frames: the row phase reads one channel per lane, 65 words apart
 #define SF_DUR_MAX 1048576.f // a token's duration is clamped here: 512 tokens stay inside int32
+#define SF_LONG_TX_MAX GT_SYNTH_LONG_MAX_TX   // tokens per utterance of the *_long entries (gt_attn_fwd's and gt_mas_long_f32's limit)
+#define SF_LONG_DUR_MAX 262144.f              // ... and their clamp: 4096 tokens of 2^18 frames sum to 2^30
+#define SF_LONG_TOK (SF_LONG_TX_MAX / 256)    // tokens per thread of gt_synth_lengths_long_kernel
 
 // One wave per utterance: lane l owns tokens [8 l, 8 l + 8); inclusive scan over the wave with shuffles.
 __global__ __launch_bounds__(64) void gt_synth_lengths_kernel(const float* __restrict__ dur, const int32_t* __restrict__ x_len,
@@ -52,19 +55,62 @@ __global__ __launch_bounds__(64) void gt_synth_lengths_kernel(const float* __res
   if (lane == 63) y_len[b] = max(incl, 1);
 }
 
+// 513 .. 4096 tokens (gt_synth_lengths_long; it takes every 1 <= Tx <= 4096): one workgroup per utterance, thread t owns tokens
+// [16 t, 16 t + 16); the scan of a wave as above, the totals of the four waves through LDS (as gt_synth_geometry_kernel does).
+// Integer sums: the same cum / y_len in whatever order they are added.
+__global__ __launch_bounds__(256) void gt_synth_lengths_long_kernel(const float* __restrict__ dur, const int32_t* __restrict__ x_len,
+                                                                    int32_t* __restrict__ cum, int32_t* __restrict__ y_len,
+                                                                    float* __restrict__ logw, int Tx)
+{
+  __shared__ int32_t wsum_s[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int n = min(max(x_len[b], 0), Tx);
+  const size_t base = (size_t)b * Tx;
+  int d[SF_LONG_TOK];
+  int own = 0;
+#pragma unroll
+  for (int k = 0; k < SF_LONG_TOK; ++k) {
+    const int i = tid * SF_LONG_TOK + k;
+    d[k] = (i < n) ? (int)fminf(fmaxf(dur[base + i], 0.f), SF_LONG_DUR_MAX) : 0;     // fmaxf drops a NaN
+    own += d[k];
+  }
+  int incl = own;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) wsum_s[w] = incl;
+  __syncthreads();
+  int run = incl - own;
+  for (int j = 0; j < w; ++j) run += wsum_s[j];
+#pragma unroll
+  for (int k = 0; k < SF_LONG_TOK; ++k) {
+    const int i = tid * SF_LONG_TOK + k;
+    run += d[k];
+    if (i < Tx) {
+      cum[base + i] = run;
+      if (logw) logw[base + i] = logf(1e-8f + (float)d[k]) * (i < n ? 1.f : 0.f);
+    }
+  }
+  if (tid == 255) y_len[b] = max(run, 1);
+}
+
 // A workgroup owns utterance blockIdx.y and row offsets [32 k, 32 k + 32) of it = squeezed frames s in [32 k - 2, 32 k + 30) =
 // frames t in [64 k - 4, 64 k + 60): the halo rows in front belong to tile 0, the halo / padding / rounding rows behind to the
 // tiles they fall into, so every row has one writer.  The tokens a tile touches are a contiguous range of the utterance: their
 // means / log-deviations go through LDS frame by frame (a wave reads one channel along Tx, one workgroup-wide phase later a
 // wave writes rows along the channels).
 // CALL: seed / noise_scale come from the gt_synth_call block in device memory (a captured graph replays with the scalars of
-// every call) instead of the by-value arguments; the only difference between the two instantiations.
-template <bool CALL>
+// every call) instead of the by-value arguments; the only difference between those two instantiations.
+// LONG (Tx <= SF_LONG_TX_MAX, the *_long entries): the utterance's scan is the one Tx-sized thing here; the 64 binary searches of a
+// tile read it where gt_synth_lengths_long left it (16 KiB at most, L2-hot) instead of every tile copying the whole row into LDS.
+template <bool CALL, bool LONG>
 __global__ __launch_bounds__(256) void gt_synth_prior_kernel(gt_synth_prior_args a, const gt_synth_call* __restrict__ call)
 {
   __shared__ float m_s[SF_C_MAX * SF_LD];
   __shared__ float l_s[SF_C_MAX * SF_LD];
-  __shared__ int32_t cum_s[SF_TX_MAX];
+  __shared__ int32_t cum_s[LONG ? 1 : SF_TX_MAX];
   __shared__ int32_t tok_s[SF_FRAMES];
   const int b = blockIdx.y, k = blockIdx.x, tid = threadIdx.x;
   const int C = a.C, Tx = a.Tx, Ty = a.Ty;
@@ -72,15 +118,19 @@ __global__ __launch_bounds__(256) void gt_synth_prior_kernel(gt_synth_prior_args
   const int ylen = a.y_len[b];
   // a tile behind the utterance's rows AND behind the optional outputs' frames has nothing to write (a capacity-sized grid)
   if (k * SF_ROWS >= gt_row_count(a.row0, b, a.Tp) && k * SF_FRAMES - 2 * HALO >= Ty) return;
-  for (int i = tid; i < n; i += 256) cum_s[i] = a.cum[(size_t)b * Tx + i];
-  __syncthreads();
+  const int32_t* __restrict__ cum_b = a.cum + (size_t)b * Tx;
+  if (!LONG) {
+    for (int i = tid; i < n; i += 256) cum_s[i] = cum_b[i];
+    __syncthreads();
+  }
+  const int32_t* cum_r = LONG ? cum_b : cum_s;          // entries [0, n) are read
   const int t0 = k * SF_FRAMES - 2 * HALO;
   if (tid < SF_FRAMES) {
     const int t = t0 + tid;
     int tok = -1;                                       // commons.generate_path: the first token whose cumulative duration passes t
-    if (t >= 0 && t < ylen && n > 0 && t < cum_s[n - 1]) {
+    if (t >= 0 && t < ylen && n > 0 && t < cum_r[n - 1]) {
       int lo = 0, hi = n - 1;
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (cum_s[mid] > t) hi = mid; else lo = mid + 1; }
+      while (lo < hi) { const int mid = (lo + hi) >> 1; if (cum_r[mid] > t) hi = mid; else lo = mid + 1; }
       tok = lo;
     }
     tok_s[tid] = tok;
@@ -234,6 +284,17 @@ extern "C" int gt_synth_lengths(const float* dur, const int32_t* x_len, int32_t*
   GT_RET();
 }
 
+extern "C" int gt_synth_lengths_long(const float* dur, const int32_t* x_len, int32_t* cum, int32_t* y_len, float* logw, int B, int Tx,
+                                     void* stream)
+{
+  if (B < 0 || Tx <= 0) return GT_E_INVAL;
+  if (B == 0) return 0;
+  if (!dur || !x_len || !cum || !y_len) return GT_E_INVAL;
+  if (Tx > SF_LONG_TX_MAX) return GT_E_UNSUPPORTED;
+  hipLaunchKernelGGL(gt_synth_lengths_long_kernel, dim3(B), dim3(256), 0, GT_ST(stream), dur, x_len, cum, y_len, logw, Tx);
+  GT_RET();
+}
+
 extern "C" int gt_synth_prior_args_size(void) { return (int)sizeof(gt_synth_prior_args); }
 extern "C" int gt_synth_call_size(void) { return (int)sizeof(gt_synth_call); }
 
@@ -269,14 +330,14 @@ extern "C" int gt_synth_frame_geometry(const int32_t* y_len_eff, int B, int Ty_c
   GT_RET();
 }
 
-static int synth_prior_launch(const gt_synth_prior_args* args, const gt_synth_call* call, bool from_call, void* stream)
+static int synth_prior_launch(const gt_synth_prior_args* args, const gt_synth_call* call, bool from_call, bool long_form, void* stream)
 {
   if (!args) return GT_E_INVAL;
   const gt_synth_prior_args& a = *args;
   if (a.R < 0 || a.B < 0) return GT_E_INVAL;
   if (a.R == 0 || a.B == 0) return 0;
   if (a.C <= 0 || a.Tx <= 0 || a.Ty <= 0 || a.Tp <= 2 * HALO) return GT_E_INVAL;
-  if (a.Tx > SF_TX_MAX || a.C > SF_C_MAX || a.B > 65535) return GT_E_UNSUPPORTED;
+  if (a.Tx > (long_form ? SF_LONG_TX_MAX : SF_TX_MAX) || a.C > SF_C_MAX || a.B > 65535) return GT_E_UNSUPPORTED;
   if (!a.x_m || !a.cum || !a.x_len || !a.y_len || !a.rows || (from_call && !call)) return GT_E_INVAL;
   if (!a.row0 && (long long)a.B * a.Tp != a.R) return GT_E_INVAL;             // uniform rows: utterance b owns [b Tp, (b + 1) Tp)
   if (!al16(a.x_m) || !al16(a.x_logs) || !al16(a.rows) || !al16(a.z_m) || !al16(a.z_logs) || !al16(a.attn)) return GT_E_ALIGN;
@@ -284,16 +345,27 @@ static int synth_prior_launch(const gt_synth_prior_args* args, const gt_synth_ca
     return GT_E_ALIGN;
   // row tiles over the largest utterance (Tp bounds it in the ragged layout), and frame tiles over all Ty frames of the optional outputs
   const int gx = max((a.Tp + SF_ROWS - 1) / SF_ROWS, (a.Ty + 2 * HALO + SF_FRAMES - 1) / SF_FRAMES);
-  if (from_call) hipLaunchKernelGGL(gt_synth_prior_kernel<true>, dim3(gx, a.B), dim3(256), 0, GT_ST(stream), a, call);
-  else hipLaunchKernelGGL(gt_synth_prior_kernel<false>, dim3(gx, a.B), dim3(256), 0, GT_ST(stream), a, call);
+  auto kernel = long_form ? (from_call ? gt_synth_prior_kernel<true, true> : gt_synth_prior_kernel<false, true>)
+                          : (from_call ? gt_synth_prior_kernel<true, false> : gt_synth_prior_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(gx, a.B), dim3(256), 0, GT_ST(stream), a, call);
   GT_RET();
 }
 
-extern "C" int gt_synth_prior(const gt_synth_prior_args* args, void* stream) { return synth_prior_launch(args, nullptr, false, stream); }
+extern "C" int gt_synth_prior(const gt_synth_prior_args* args, void* stream) { return synth_prior_launch(args, nullptr, false, false, stream); }
 
 extern "C" int gt_synth_prior_call(const gt_synth_prior_args* args, const gt_synth_call* call, void* stream)
 {
-  return synth_prior_launch(args, call, true, stream);
+  return synth_prior_launch(args, call, true, false, stream);
+}
+
+extern "C" int gt_synth_prior_long(const gt_synth_prior_args* args, void* stream)
+{
+  return synth_prior_launch(args, nullptr, false, true, stream);
+}
+
+extern "C" int gt_synth_prior_long_call(const gt_synth_prior_args* args, const gt_synth_call* call, void* stream)
+{
+  return synth_prior_launch(args, call, true, true, stream);
 }
 
 static int randn_rows_launch(float* out, int R, int ncol, uint32_t seed, uint32_t stream_id, float scale, const gt_synth_call* call,

@@ -69,7 +69,18 @@ def _ln_bwd(rc, ln, saved, dout_f32, dout_bf, want_da, want_dy, grads, relu_in=F
 ATTN_MAX_T = 4096           # GT_ATTN_LONG_MAX_T of include/glowtts_hip.h: the longest text gt_attn_fwd / gt_attn_bwd take
 
 
-def mha_fwd(rc, att, xb, p, seed):
+def attn_long_shape(T, D, win):
+    """gt_attn_long_shape of csrc/attn_long.hip on the host (a test compares the two): the shapes of the key-tiled kernels, the only
+    ones at which gt_attn_fwd takes P == NULL.  Were the two ever to differ, a NULL P at a shape the library does not take is
+    GT_E_INVAL, not a wrong result."""
+    return D == 96 and win == 4 and 505 < T <= ATTN_MAX_T
+
+
+def mha_fwd(rc, att, xb, p, seed, keep_p=True):
+    """keep_p=False: a forward nobody differentiates (synthesis).  At the shapes of the key-tiled kernels (gt_attn_long_shape) no
+    [B, H, T, T] tensor is then allocated, gt_attn_fwd stores no P and the saved tuple carries None in its place; `out` is the same bit
+    for bit.  At every other shape the flag changes nothing.  It cannot be inferred from grad mode: the training forward runs inside
+    _RowsFn.apply, where grad mode is off."""
     if rc.T > ATTN_MAX_T:       # before any allocation or launch: P and the backward's workspace are 4 B H T^2 bytes each per layer
         raise ValueError(f"attention takes at most {ATTN_MAX_T} tokens per utterance (GT_ATTN_LONG_MAX_T), got T = {rc.T}")
     dev = xb.device
@@ -80,7 +91,9 @@ def mha_fwd(rc, att, xb, p, seed):
     # the attention kernel writes frame rows only: halo rows must be finite zeros (they meet zero
     # gradients in the wgrad GEMM, and 0 * NaN garbage would poison it)
     o = ops_zeros_big((R, C), torch.bfloat16, dev)
-    P = torch.empty(rc.B, H, rc.T, rc.T, dtype=torch.float32, device=dev)
+    P = None
+    if keep_p or not attn_long_shape(rc.T, D, att.window_size):
+        P = torch.empty(rc.B, H, rc.T, rc.T, dtype=torch.float32, device=dev)
     Ek = att.emb_rel_k.detach().reshape(-1, D).contiguous()
     Ev = att.emb_rel_v.detach().reshape(-1, D).contiguous()
     call.gt_attn_fwd(q, k, v, 3 * C, Ek, Ev, rc.lengths, o, C, P, rc.B, rc.T, rc.Tp, rc.row0, H, D, att.window_size, float(p), int(seed),
@@ -92,6 +105,8 @@ def mha_fwd(rc, att, xb, p, seed):
 def mha_bwd(rc, att, saved, dy, grads):
     """dy: bf16 rows gradient of the attention block output.  Returns dxb (bf16)."""
     xb, q, k, v, o, P, Ek, Ev, p, seed = saved
+    if P is None:
+        raise RuntimeError("attention backward after a forward that stored no P (mha_fwd(keep_p=False))")
     dev = xb.device
     R = rc.R
     H, D, C = att.n_heads, att.k_channels, att.channels
@@ -117,11 +132,11 @@ def mha_bwd(rc, att, saved, dy, grads):
 
 
 # ----------------------------------------------------------------------------- one encoder layer
-def layer_fwd(rc, enc, i, x, xb, train, seed):
+def layer_fwd(rc, enc, i, x, xb, train, seed, keep_p=True):
     p = enc.p_dropout if train else 0.0
     att, ffn = enc.attn_layers[i], enc.ffn_layers[i]
     C = enc.hidden_channels
-    y, s_att = mha_fwd(rc, att, xb, p, seed)
+    y, s_att = mha_fwd(rc, att, xb, p, seed, keep_p=keep_p)
     x1, xb1, s_ln1 = _ln_fwd(rc, enc.norm_layers_1[i], x, y, p, seed + 1, 0.0, 0, 0, True, C)
     f1 = conv_rows(xb1, ffn.conv_1.pc, rc, bias=ffn.conv_1.bias, relu=True, mask=True, drop_p=p, seed=seed + 2)
     f2 = conv_rows(f1, ffn.conv_2.pc, rc, bias=ffn.conv_2.bias, mask=True)

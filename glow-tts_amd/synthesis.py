@@ -74,11 +74,21 @@ def _launch(device, name, *args):
     getattr(_lib.call, name)(*args, _lib.current_stream(device))
 
 
+def _by_tokens(name, Tx):
+    """the front-end entry `name` for texts of Tx tokens: itself to 512 tokens (a short call launches what it always launched), its
+    *_long form (csrc/synth_front.hip; to GT_SYNTH_LONG_MAX_TX = 4096 tokens) past them"""
+    if Tx <= _lib.SYNTH_MAX_TX:
+        return name
+    return {"gt_synth_lengths": "gt_synth_lengths_long", "gt_synth_prior": "gt_synth_prior_long",
+            "gt_synth_prior_call": "gt_synth_prior_long_call"}[name]
+
+
 class ByValue:
     """The scalar source of the eager path: a CallScalars, handed to the kernels by value.  keyed: the predictors' draws are keyed by
     (utterance, token / frame), independent of the layout (gt_randn_keyed: what FromBlock reproduces), else by the row (gt_randn_rows).
     noise -> [rc.R, 2] draws of the generator's stream stream_id times scale `which` (1 noise_scale_w, 2 f0_, 3 energy_noise_scale);
-    prior / contours launch gt_synth_prior / gt_synth_contours on the arguments every source shares."""
+    prior / contours launch gt_synth_prior (past 512 tokens gt_synth_prior_long) / gt_synth_contours on the arguments every source
+    shares."""
 
     def __init__(self, scalars, keyed, device):
         self.scalars, self.keyed, self.device, self.length_scale = scalars, keyed, device, scalars.length_scale
@@ -95,7 +105,7 @@ class ByValue:
 
     def prior(self, args):
         args.seed, args.noise_scale = self.scalars.seed, float(self.scalars.noise_scale)
-        _launch(self.device, "gt_synth_prior", args)
+        _launch(self.device, _by_tokens("gt_synth_prior", args.Tx), args)
 
     def contours(self, *args):
         _launch(self.device, "gt_synth_contours", *args, float(self.scalars.pitch_scale), float(self.scalars.energy_scale))
@@ -115,7 +125,7 @@ class FromBlock:
         return nz
 
     def prior(self, args):
-        _launch(self.device, "gt_synth_prior_call", args, self.call)
+        _launch(self.device, _by_tokens("gt_synth_prior_call", args.Tx), args, self.call)
 
     def contours(self, *args):
         _launch(self.device, "gt_synth_contours_call", *args, self.call)
@@ -123,12 +133,13 @@ class FromBlock:
 
 def text_stage(gen, ids, x_len, g, l, emo, emo_cartesian, draw):
     """conditioning -> text encoder -> duration predictor (the stochastic one in reverse on the noise draw(rc) [rc.R, 2], or the
-    deterministic one) -> g, l, x_m, x_logs, x_mask, the text rows (rc, xb), logw [B, 1, Tx]"""
+    deterministic one) -> g, l, x_m, x_logs, x_mask, the text rows (rc, xb), logw [B, 1, Tx].  The one place synthesis calls the
+    encoder from: no backward follows, so past 505 tokens its attention stores no P (keep_p=False)"""
     from .text_models import _DurationRunner
     g = gen.condition(g, emo, emo_cartesian)
     if l is not None:
         l = gen.emb_l(l).unsqueeze(-1)
-    xo, x_m, x_logs, x_mask = gen.encoder(ids, x_len, l=l, g=g, prepared=True)
+    xo, x_m, x_logs, x_mask = gen.encoder(ids, x_len, l=l, g=g, prepared=True, keep_p=False)
     rc, xb = gen.encoder._last_rows
     pw = gen.encoder.proj_w
     dvec = pw.cond_vec(g, l)
@@ -141,12 +152,12 @@ def text_stage(gen, ids, x_len, g, l, emo, emo_cartesian, draw):
 
 
 def lengths_stage(logw, x_mask, length_scale, x_len, cum, y_len, logw_):
-    """durations -> gt_synth_lengths into the caller's cum [B, Tx], y_len [B] and (or None) logw_ [B, 1, Tx] -> dur, x_len as int32.
+    """durations -> gt_synth_lengths (past 512 tokens gt_synth_lengths_long) into the caller's cum [B, Tx], y_len [B] and (or None) logw_ [B, 1, Tx] -> dur, x_len as int32.
     exp, length_scale (a float, or a 0-dim device tensor) and ceil stay in torch on [B, Tx] (plumbing): the durations are bit for bit
     those of infer without the front end"""
     dur = torch.ceil(torch.exp(logw) * x_mask * length_scale).squeeze(1).contiguous()
     xl = x_len.to(torch.int32).contiguous()
-    _launch(dur.device, "gt_synth_lengths", dur, xl, cum, y_len, logw_, *dur.shape)
+    _launch(dur.device, _by_tokens("gt_synth_lengths", dur.shape[1]), dur, xl, cum, y_len, logw_, *dur.shape)
     return dur, xl
 
 
@@ -343,8 +354,11 @@ class Synthesizer:
         if gen.n_sqz != 2:
             raise NotImplementedError("compile_synthesis needs n_sqz = 2 (the rows layout of the fused reverse pass)")
         batch, max_tokens, max_frames = int(batch), int(max_tokens), int(max_frames)
-        if batch < 1 or batch > _lib.STEP_MAX_B or max_tokens < 1 or max_tokens > 512 or max_frames < 2 or max_frames % 2:
-            raise ValueError("compile_synthesis: 1 <= batch <= 1024, 1 <= max_tokens <= 512, max_frames even and >= 2")
+        if batch < 1 or batch > _lib.STEP_MAX_B or max_tokens < 1 or max_tokens > _lib.SYNTH_LONG_MAX_TX or max_frames < 2 or max_frames % 2:
+            raise ValueError(f"compile_synthesis: 1 <= batch <= 1024, 1 <= max_tokens <= {_lib.SYNTH_LONG_MAX_TX}, max_frames even and >= 2")
+        if aux and batch * max_tokens * max_frames > 2 ** 31 - 1:                 # before any allocation: 4 bytes each
+            raise ValueError(f"compile_synthesis(aux=True): the static attn buffer has batch * max_tokens * max_frames = "
+                             f"{batch} * {max_tokens} * {max_frames} = {batch * max_tokens * max_frames} elements, more than 2^31 - 1")
         self.gen, self.batch, self.max_tokens, self.max_frames, self.aux = gen, batch, max_tokens, max_frames, bool(aux)
         self.max_rows = int(max_rows) if max_rows is not None else default_rows(batch, max_frames, gen.rows_cfg.row_round)
         if self.max_rows < 2 * HALO * batch:

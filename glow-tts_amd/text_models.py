@@ -113,9 +113,10 @@ class TextEncoder(nn.Module):
             self.proj_s = ConvP(hidden_channels, out_channels, 1)
         self._step = 0
 
-    def forward(self, x, x_lengths, l=None, g=None, emo=None, prepared=False):
+    def forward(self, x, x_lengths, l=None, g=None, emo=None, prepared=False, keep_p=True):
         """ids [b, t] int64, lengths [b] -> (x [b,H,t], x_m [b,80,t], x_logs [b,80,t], x_mask [b,1,t])
-        exactly as reference models.py:692-716."""
+        exactly as reference models.py:692-716.  keep_p=False (synthesis: no backward follows): the attention of texts past 505
+        tokens stores no P (encoder_impl.mha_fwd); the outputs are the same bit for bit."""
         assert emo is None, "emotion conditioning is commented out in the reference encoder (models.py:695-696)"
         assert (l is None) == (self.lin_channels == 0), "l [b, lin_channels, 1] is required exactly when lin_channels != 0"
         if not prepared:
@@ -126,7 +127,7 @@ class TextEncoder(nn.Module):
         vec = self.encoder.cond_vec(g)                # speaker vector, added before encoder layer index 2
         lvec = None if l is None else l.squeeze(-1)     # [b, lin]: a differentiable input of the node (emb_l upstream)
         runner = _TextEncoderRunner(self, x, x_lengths, self.training, seed=(self._step * 104729) & 0x7fffffff,
-                                    has_cond=vec is not None, has_lang=lvec is not None)
+                                    has_cond=vec is not None, has_lang=lvec is not None, keep_p=keep_p)
         outs = _RowsFn.apply(runner, 3, *([vec] if vec is not None else []), *([lvec] if lvec is not None else []), *runner.params)
         xo, x_m, x_logs = outs[0], outs[1], outs[2]
         self._last_rows = runner.last            # (rc, xb_final) for the duration predictor
@@ -134,9 +135,9 @@ class TextEncoder(nn.Module):
 
 
 class _TextEncoderRunner:
-    def __init__(self, te, ids, lengths, train, seed, has_cond=False, has_lang=False):
+    def __init__(self, te, ids, lengths, train, seed, has_cond=False, has_lang=False, keep_p=True):
         self.te, self.ids, self.lengths, self.train, self.seed = te, ids.contiguous(), lengths, train, seed
-        self.has_cond, self.has_lang = has_cond, has_lang
+        self.has_cond, self.has_lang, self.keep_p = has_cond, has_lang, keep_p
         self.params = [p for n, p in te.named_parameters() if not n.startswith("proj_w.") and not n.startswith("encoder.cond_g.")]
         self.last = None
 
@@ -165,7 +166,7 @@ class _TextEncoderRunner:
         for i in range(te.encoder.n_layers):
             if i == te.encoder.COND_LAYER and vec is not None:
                 x, xb = ops.rows_add_cond(rc, x, None, vec)
-            x, xb, s = encoder_impl.layer_fwd(rc, te.encoder, i, x, xb, self.train, self.seed + 16 + 8 * i)
+            x, xb, s = encoder_impl.layer_fwd(rc, te.encoder, i, x, xb, self.train, self.seed + 16 + 8 * i, keep_p=self.keep_p)
             s_layers.append(s)
         from .ops import conv_rows
         xm_r = conv_rows(xb, te.proj_m.pc, rc, bias=te.proj_m.bias, mask=True, out_f32=True)
@@ -484,6 +485,7 @@ class FlowGenerator(nn.Module):
         layout the reverse decoder reads (padded frames then cost nothing, and the fused reverse pass unsqueezes in its last launch),
         and every draw of the call — the prior's and the stochastic predictors' — comes from a counter-hash Gaussian generator that the
         host can restate from `infer(..., seed=)` alone.  Off (the default): infer is torch.randn and the uniform rows layout.
+        Texts of up to 4096 tokens (GT_SYNTH_LONG_MAX_TX): past 512 tokens the *_long entries of the same kernels take over.
         noise_key: "row" — the stochastic predictors' draws are keyed by the row index of the rows layout in use
         (gt_randn_rows) and the pitch / energy predictors run on uniform frame rows; "frame" — the draws are keyed by (utterance, token)
         / (utterance, frame) (gt_randn_keyed), independent of the layout, the frame-rate rows are ragged, and the contours go into the
@@ -510,13 +512,17 @@ class FlowGenerator(nn.Module):
     def compile_synthesis(self, batch, max_tokens, max_frames, max_rows=None, aux=False, stochastic=False, max_frame_rows=None):
         """Synthesis as ONE captured graph (glow-tts_amd/synthesis.py) -> synthesis.Synthesizer.  Needs
         store_inverse(fused_reverse=True, device_front=True) in effect.  The sizes are capacities, fixed here: a batch of exactly `batch`
-        texts of up to max_tokens tokens, up to max_frames (even) mel frames per utterance and max_rows rows of the squeezed mel axis
-        (default: `batch` utterances of max_frames frames, rounded to rows_cfg.row_round).  Calling the synthesiser —
+        texts of up to max_tokens tokens (1 <= max_tokens <= 4096), up to max_frames (even) mel frames per utterance and max_rows rows
+        of the squeezed mel axis (default: `batch` utterances of max_frames frames, rounded to rows_cfg.row_round).  The encoder runs at
+        max_tokens whatever a call's text length is: a capacity of 385 .. 505 tokens runs the generic (VALU) attention kernels, several
+        times slower than the MFMA ones on either side, so for long texts compile at max_tokens >= 506 (or <= 384 for short ones).
+        Calling the synthesiser —
         `h = synth(x, x_lengths, g=None, l=None, seed=None, noise_scale=1., length_scale=1.)` — is one upload, one graph replay and one
         readback, without a host synchronisation: `h.lengths()` / `h.mel()` wait for that call alone, so calls can be queued back to
         back.  The mel is bit-identical to infer(seed=)'s on the same rows.  A call whose predicted lengths do not fit the capacities is
         re-run through infer (synth.overflows counts them; `mel(fallback=False)` raises synthesis.SynthesisOverflow instead).
-        aux=True also keeps z_m, z_logs, attn, logw, logw_ (h.aux()).  Covered: the deterministic duration predictor, with the optional
+        aux=True also keeps z_m, z_logs, attn, logw, logw_ (h.aux()); its static attn buffer is 4 * batch * max_tokens * max_frames
+        bytes (ValueError past 2^31 - 1 elements).  Covered: the deterministic duration predictor, with the optional
         speaker vector g and language id l; use_sdp / use_spp / use_sep or emotion inputs raise NotImplementedError unless
         stochastic=True: the full model — the stochastic duration predictor in reverse, the stochastic pitch / energy
         predictors at the frame rate, the emotion front end — in the same one graph, on one stream.  It needs
@@ -537,7 +543,7 @@ class FlowGenerator(nn.Module):
         decoder(reverse=True) -> mel.  Returns ((y, z_m, z_logs, None, z_mask), (x_m, x_logs, x_mask), (attn, logw, logw_),
         (pitch, energy)).  The output length is data dependent, so this reads the predicted lengths back from the device once.
         seed (set_synthesis_front only): the call's noise is a function of this integer alone; None draws one from torch's default
-        CPU generator, so torch.manual_seed still governs the call."""
+        CPU generator, so torch.manual_seed still governs the call.  Texts of up to 4096 tokens, with the front end off or on."""
         if self.synthesis_front:
             from .synthesis import CallScalars
             return self._infer_front(x, x_lengths, g, emo, emo_cartesian, l, CallScalars(

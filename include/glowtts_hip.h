@@ -333,6 +333,10 @@ int gt_param_partials_reduce(const gt_partials_args* args, void* stream);
  * the rest runs on the generic kernels, which hold an utterance-head in LDS: at D = 96, win = 4 the forward to T = 597, the
  * backward to T = 505 — GT_E_UNSUPPORTED past what fits, and for every T > GT_ATTN_LONG_MAX_T before anything is launched.
  * P and the workspace are each 4 B H T^2 bytes (4.3 GB at B = 32, H = 2, T = 4096).
+ * gt_attn_fwd with P == NULL — a forward nobody differentiates (synthesis) — is taken when, and only when, gt_attn_long_shape(T, D,
+ * win) holds: the key-tiled kernel then stores no P and writes the same `out`, bit for bit (strides / operand alignment that kernel
+ * does not take: GT_E_ALIGN).  At every other shape a NULL P is GT_E_INVAL (T > GT_ATTN_LONG_MAX_T: GT_E_UNSUPPORTED comes first).
+ * gt_attn_bwd always needs the P its forward stored.
  *   workspace   device scratch of at least gt_attn_bwd_workspace_bytes(B,T,H) bytes, 16-byte aligned; after gt_attn_bwd it
  *               holds what the call's second pass read (dS = P (dP - sum_j dP P) / sqrt(D), zero where masked):
  *               on the MFMA kernels (both families) bf16 dS^T [B,H,T(key j),TI(query i)], TI = ceil(T/32)*32, followed by dropout(P)^T in
@@ -772,7 +776,15 @@ int gt_rows_gather_tokens(const void* x_rows, int ldx, const int32_t* frame2toke
  *   NULL args / required pointer: GT_E_INVAL;  R == 0 or B == 0: 0;  Tx > 512 or C > 80: GT_E_UNSUPPORTED;  fp32 pointers not
  *   16-byte aligned: GT_E_ALIGN.
  *
- * gt_randn_rows: out [R, ncol] fp32 = scale * (e0 | e1 by the parity of col) of (seed, stream, b = 0, s = row, c = col / 2). */
+ * gt_randn_rows: out [R, ncol] fp32 = scale * (e0 | e1 by the parity of col) of (seed, stream, b = 0, s = row, c = col / 2).
+ *
+ * Texts of 513 .. GT_SYNTH_LONG_MAX_TX tokens: gt_synth_lengths_long / gt_synth_prior_long (and gt_synth_prior_long_call below) keep
+ *   the contracts of gt_synth_lengths / gt_synth_prior / gt_synth_prior_call — outputs, masks, one writer per element, refusal codes —
+ *   for every 1 <= Tx <= GT_SYNTH_LONG_MAX_TX (= GT_ATTN_LONG_MAX_T); Tx > GT_SYNTH_LONG_MAX_TX: GT_E_UNSUPPORTED before any launch.
+ *   On Tx <= 512 they write what the short entries write, bit for bit, the noise included, with ONE difference: gt_synth_lengths_long
+ *   clamps a token's duration to [0, 2^18] (4096 tokens then sum to at most 2^30, inside int32) where gt_synth_lengths clamps to
+ *   [0, 2^20].  The short entries keep refusing Tx > 512. */
+#define GT_SYNTH_LONG_MAX_TX 4096
 typedef struct gt_synth_prior_args {
   const float* x_m; const float* x_logs;        /* [B, C, Tx] fp32; x_logs NULL = mean_only */
   const int32_t* cum;                           /* [B, Tx] gt_synth_lengths' scan */
@@ -787,6 +799,8 @@ typedef struct gt_synth_prior_args {
 } gt_synth_prior_args;
 int gt_synth_lengths(const float* dur, const int32_t* x_len, int32_t* cum, int32_t* y_len, float* logw, int B, int Tx, void* stream);
 int gt_synth_prior(const gt_synth_prior_args* args, void* stream);
+int gt_synth_lengths_long(const float* dur, const int32_t* x_len, int32_t* cum, int32_t* y_len, float* logw, int B, int Tx, void* stream);
+int gt_synth_prior_long(const gt_synth_prior_args* args, void* stream);
 int gt_synth_prior_args_size(void);             /* sizeof(gt_synth_prior_args) */
 int gt_randn_rows(float* out, int R, int ncol, uint32_t seed, uint32_t stream_id, float scale, void* stream);
 
@@ -820,6 +834,7 @@ int gt_synth_call_size(void);                   /* sizeof(gt_synth_call) */
 int gt_synth_geometry(const int32_t* y_len, int B, int Ty_cap, int R_cap, int32_t* row0, int32_t* len_sq, int32_t* y_len_eff,
                       int64_t* rowbatch, int32_t* rowframe, float* rowmask, int32_t* rowutt, int32_t* status, void* stream);
 int gt_synth_prior_call(const gt_synth_prior_args* args, const gt_synth_call* call, void* stream);
+int gt_synth_prior_long_call(const gt_synth_prior_args* args, const gt_synth_call* call, void* stream);
 int gt_randn_rows_call(float* out, int R, int ncol, const gt_synth_call* call, uint32_t stream_id, int which_scale, void* stream);
 
 /* ---- Full-model synthesis: stochastic duration / pitch / energy predictors (csrc/synth_prosody.hip, csrc/synth_front.hip; DESIGN

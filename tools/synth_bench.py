@@ -35,6 +35,9 @@ launches per contour), eager with noise_key="frame" on uniform frame rows (rows_
 shape: replay over eager-frame, eager-frame over eager-row, ragged over uniform frame rows.  Every repeat is recorded; output defaults
 to profiles/synth_graph_cfg5_bench.json.
 
+--tokens BxT[,BxT...] (--infer, --graph): texts of a given length instead of the two shapes above, e.g. `--tokens 1x1024,8x600` (long
+texts); --front off|on|both picks the variants of --infer.
+
 Kernel times come from separate runs, one per shape, under
 `rocprofv3 --kernel-trace --stats -- python tools/synth_bench.py --seconds 0.1 --repeats 1 --shape batch` (or `single`)."""
 import argparse
@@ -54,6 +57,9 @@ ap.add_argument("--infer", action="store_true", help="time whole infer calls, de
 ap.add_argument("--graph", action="store_true", help="time eager infer against the captured synthesis graph (compile_synthesis)")
 ap.add_argument("--cfg5", action="store_true", help="the full cfg 5 model: eager row / frame keyed calls (and with --graph the captured graph)")
 ap.add_argument("--queue", type=int, default=16, help="--graph: replays queued before one synchronisation")
+ap.add_argument("--tokens", default=None, help="--infer / --graph: the shapes as BxT[,BxT...], B texts of T tokens each (5 T frames), "
+                "e.g. 1x1024,8x600, instead of the two default shapes")
+ap.add_argument("--front", choices=["both", "off", "on"], default="both", help="--infer: the variants to time")
 ap.add_argument("--shape", choices=["both", "batch", "single"], default="both", help="one shape only (a kernel-trace run per shape)")
 opt = ap.parse_args()
 
@@ -162,6 +168,16 @@ def main():
             f.write("\n")
 
 
+def token_cases():
+    """--tokens BxT[,BxT...] -> [(name, ids [B, T], x_lengths [B])]"""
+    g = torch.Generator().manual_seed(5)
+    out = []
+    for spec in opt.tokens.split(","):
+        B, T = (int(v) for v in spec.lower().split("x"))
+        out.append((f"{B} x {T} tokens = {5 * T} frames each", torch.randint(1, 148, (B, T), generator=g), torch.full((B,), T)))
+    return out
+
+
 def infer_main():
     import math
     import time
@@ -197,7 +213,9 @@ def infer_main():
     g = torch.Generator().manual_seed(5)
     cases = [("bench batch: B = 32, T_x <= 150, 5 frames per token", ids_b, t_x),
              ("one utterance, 160 tokens = 800 frames", torch.randint(1, 148, (1, 160), generator=g), torch.tensor([160]))]
-    variants = [False, True] if has_front else [False]
+    if opt.tokens:
+        cases = token_cases()
+    variants = [v for v in ([False, True] if has_front else [False]) if opt.front in ("both", "on" if v else "off")]
     name_of = {False: "front_off", True: "front_on"}
 
     def call(ids, xl, front, n):
@@ -230,7 +248,7 @@ def infer_main():
         for v in rec["variants"].values():
             t = v["ms_per_call"]
             v["ms_mean"], v["ms_spread"] = round(sum(t) / len(t), 4), round(max(t) - min(t), 4)
-        if has_front:
+        if len(variants) == 2:
             rec["front_on_over_front_off_time"] = round(rec["variants"]["front_on"]["ms_mean"] / rec["variants"]["front_off"]["ms_mean"], 4)
         print(f'{name}: T_y {rec["T_y"]}; ' + "; ".join(f'{k} {v["ms_mean"]:.3f} ms (+- {v["ms_spread"]:.3f}), {v["launches_per_call"]} launches '
                                                         f'({v["c_abi_entries"]} C-ABI + {v["aten_device_ops"]} aten)' for k, v in rec["variants"].items()), flush=True)
@@ -265,6 +283,8 @@ def graph_main():
         cases.append(("bench batch: B = 32, T_x <= 150, 5 frames per token", ids_b, t_x, [(int(ids_b.shape[1]), 5 * int(ids_b.shape[1]))]))
     if opt.shape != "batch":
         cases.append(("one utterance, 160 tokens = 800 frames", one, torch.tensor([160]), [(160, 800), (160, 1600)]))
+    if opt.tokens:
+        cases = [(name, ids, xl, [(int(ids.shape[1]), 5 * int(ids.shape[1]))]) for name, ids, xl in token_cases()]
     out = dict(device=torch.cuda.get_device_name(0), model="cfg 2: 6 encoder layers, 12 blocks x 4 layers, H = 192, eval, "
                "store_inverse(fused_reverse=True, device_front=True)", seconds_per_variant=opt.seconds, queued_calls=opt.queue, shapes=[])
     for name, ids, xl, caps in cases:
