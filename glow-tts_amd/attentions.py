@@ -174,6 +174,7 @@ class MultiHeadAttention(nn.Module):
         self.channels, self.out_channels, self.n_heads, self.window_size = channels, out_channels, n_heads, window_size
         self.heads_share, self.block_length, self.proximal_bias, self.p_dropout = heads_share, block_length, proximal_bias, p_dropout
         self.attn = None
+        self.keep_p = True      # False: past 505 tokens (encoder_impl.attn_long_shape) the forward keeps row statistics, not P: attn stays None
         self.k_channels = channels // n_heads
         self.conv_q = ConvP(channels, channels, 1)
         self.conv_k = ConvP(channels, channels, 1)
@@ -226,8 +227,10 @@ class _MHARunner:
         B, C, T = x.shape
         rc = RowsCtx(_mask_lengths(self.x_mask), T)
         xb = rc.to_rows(x.detach() * self.x_mask, torch.bfloat16)
-        y, saved = encoder_impl.mha_fwd(rc, self.att, xb, self.att.p_dropout if self.train else 0.0, self.seed)
-        return (rc.from_rows(y, torch.float32), saved[5]), (rc, saved)
+        y, saved = encoder_impl.mha_fwd(rc, self.att, xb, self.att.p_dropout if self.train else 0.0, self.seed,
+                                        keep_p=True if getattr(self.att, "keep_p", True) else "stats")
+        P = saved[5]
+        return (rc.from_rows(y, torch.float32), None if isinstance(P, encoder_impl.AttnStats) else P), (rc, saved)
 
     def backward(self, saved_all, dy, _dp):
         rc, saved = saved_all
@@ -305,7 +308,8 @@ class _EncoderRunner:
         for i in range(self.enc.n_layers):
             if i == self.enc.COND_LAYER and vec is not None:
                 xr, xb = ops.rows_add_cond(rc, xr, None, vec)
-            xr, xb, s = encoder_impl.layer_fwd(rc, self.enc, i, xr, xb, self.train, self.seed + 8 * i)
+            xr, xb, s = encoder_impl.layer_fwd(rc, self.enc, i, xr, xb, self.train, self.seed + 8 * i,
+                                               keep_p=True if getattr(getattr(self.enc, "rows_cfg", None), "attn_keep_p", True) else "stats")
             saved.append(s)
         return (rc.from_rows(xr),), (rc, saved)
 

@@ -70,7 +70,7 @@ def build(force=False, verbose=False):
     if not srcs:
         raise RuntimeError("no HIP sources under " + CSRC)
     hdrs = glob.glob(os.path.join(ROOT, "include", "*.h")) + glob.glob(os.path.join(CSRC, "*.h")) + \
-        glob.glob(os.path.join(CSRC, "*.hpp"))
+        glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.inc"))
     os.makedirs(OBJ, exist_ok=True)
     objs, procs = [], []
     for s in srcs:

@@ -40,6 +40,9 @@ constexpr int TILE_U4 = 32 * (D / 8);          // uint4s of one staged [32][VP] 
 // Forward: one workgroup per (utterance, head, 128 queries), a wave owns 32 queries.
 // STORE_P = false (gt_attn_fwd with P == NULL: a forward nobody differentiates, synthesis): pass 2 leaves out its P stores and
 // nothing else, so `out` is the same bit for bit.
+// STATS (gt_attn_long_fwd_stats_kernel, gt_attn_fwd_stats: the training forward whose backward recomputes P): no P either; after
+// pass 1 every query row i < T, padded ones included, stores the pair it holds, (mx, rden) = (maximum of the masked, scaled scores,
+// 1 / denominator), to Pout = stats[B, H, T, 2].  With them P[i, j] = __expf(s - mx) * rden is pass 2's expression on the same values.
 template <bool STORE_P>
 __global__ __launch_bounds__(256, 2) void gt_attn_long_fwd_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,
@@ -47,200 +50,18 @@ __global__ __launch_bounds__(256, 2) void gt_attn_long_fwd_kernel(
     bf16_t* __restrict__ out, int ldo, float* __restrict__ Pout,
     int T, int Tp, const int32_t* row0, int H, uint32_t drop_thresh, uint32_t drop_seed, float drop_scale, const uint32_t* __restrict__ seed_dev)
 {
-  if (seed_dev) drop_seed ^= *seed_dev;
-  __shared__ __attribute__((aligned(16))) bf16_t Vr[2 * 32 * VP];   // V ring: two [32][VP] tiles
-  __shared__ __attribute__((aligned(16))) bf16_t Eks[32 * KP];      // rows >= 9 are zero
-  __shared__ __attribute__((aligned(16))) bf16_t EvT[D * 16];       // EvT[d][r], r >= 9 zero
-  __shared__ __attribute__((aligned(16))) float  QE[4 * 32 * NW];
-  __shared__ __attribute__((aligned(16))) bf16_t PB[4 * 32 * 16];
+  constexpr bool STATS = false;
+#include "attn_long_fwd_body.inc"
+}
 
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int r = lane & 31, hh = lane >> 5;
-  const int len = lens[b];
-  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
-  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;          // see gt_attn_fwd_mfma_kernel
-  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
-
-  for (int i = tid; i < 32 * D; i += 256) { const int rr = i / D, c = i - rr * D; Eks[rr * KP + c] = rr < NW ? f2bf(Ek[rr * D + c]) : (bf16_t)0; }
-  for (int i = tid; i < D * 16; i += 256) { const int d = i >> 4, rr = i & 15; EvT[i] = rr < NW ? f2bf(Ev[rr * D + d]) : (bf16_t)0; }
-  for (int i = tid; i < 4 * 32 * 16; i += 256) PB[i] = 0;
-  const int nt = (T + 31) >> 5;                                  // key tiles that hold keys (uniform)
-  uint4 vr[2];
-  GT_TILE_LOAD(vr, v, ld, 0)
-  GT_TILE_STORE(Vr, vr)
-  __syncthreads();
-
-  const int i0 = blockIdx.x * 128 + 32 * w;
-  const bool active = i0 < T;                                    // wave-uniform
-  const int i = i0 + r;
-  const int ic = i < T ? i : T - 1;
-  float* qe = QE + w * 32 * NW;
-  bf16_t* pb = PB + w * 32 * 16;
-  const float inv_sqrt = rsqrtf((float)D);
-
-  bf16x8_t qf[6];
-#pragma unroll
-  for (int ks = 0; ks < 6; ++ks)
-    qf[ks] = *reinterpret_cast<const bf16x8_t*>(q + RW(ic) * ld + h * D + ks * 16 + 8 * hh);
-  if (active) {
-    f32x16_t acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 6; ++ks) {
-      const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(Eks + r * KP + ks * 16 + 8 * hh);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, qf[ks], acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) qe[r * NW + e + 4 * hh] = acc[e];
-    if (hh == 0) qe[r * NW + 8] = acc[4];
-  }
-  __builtin_amdgcn_wave_barrier();
-
-  // K fragments of key tile t: lane (key r of the tile, k-half hh); rows >= T are zero
-  auto load_k = [&](int t, bf16x8_t* kf) {
-    const int j = 32 * t + r;
-    if (j < T) {
-#pragma unroll
-      for (int ks = 0; ks < 6; ++ks) kf[ks] = *reinterpret_cast<const bf16x8_t*>(k + RW(j) * ld + h * D + ks * 16 + 8 * hh);
-    } else {
-      const uint4 z = make_uint4(0, 0, 0, 0);
-#pragma unroll
-      for (int ks = 0; ks < 6; ++ks) kf[ks] = __builtin_bit_cast(bf16x8_t, z);
-    }
-  };
-  // masked, scaled scores of one tile (element e <-> key 32t + (e&3) + 8(e>>2) + 4hh)
-  auto scores = [&](int t, const bf16x8_t* kf, f32x16_t& st) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) st[e] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 6; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], st, 0, 0, 0);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int j = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-      float sc = st[e];
-      const int rel = j - i + WIN;
-      if ((unsigned)rel <= 2u * WIN) sc += qe[r * NW + rel];
-      sc *= inv_sqrt;
-      if (j >= T) sc = -3.0e38f;                                 // not a key at all
-      else if (j >= len || i >= len) sc = -1e4f;                 // masked_fill(mask == 0, -1e4), attentions.py:260
-      st[e] = sc;
-    }
-  };
-
-  // ---- pass 1 (no LDS operand, no barrier): online max / denominator over this lane's keys, then the lane halves merge
-  float mx = -3.0e38f, den = 0.f;
-  bf16x8_t kf[6], kn[6];
-  if (active) {
-    load_k(0, kf);
-#pragma unroll 1
-    for (int t = 0; t < nt; ++t) {
-      if (t + 1 < nt) load_k(t + 1, kn);
-      f32x16_t st;
-      scores(t, kf, st);
-      float tm = st[0];
-#pragma unroll
-      for (int e = 1; e < 16; ++e) tm = fmaxf(tm, st[e]);
-      const float mn = fmaxf(mx, tm);
-      float add = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) add += __expf(st[e] - mn);
-      den = den * __expf(mx - mn) + add;
-      mx = mn;
-#pragma unroll
-      for (int ks = 0; ks < 6; ++ks) kf[ks] = kn[ks];
-    }
-    const float mo = __shfl_xor(mx, 32), dn = __shfl_xor(den, 32);
-    const float mm = fmaxf(mx, mo);
-    den = den * __expf(mx - mm) + dn * __expf(mo - mm);
-    mx = mm;
-  }
-  const float rden = active ? 1.0f / den : 0.f;
-
-  // ---- pass 2: P = softmax, dropout, O^T = V^T P^T (+ Ev^T band(P)^T); V tile t in ring slot t & 1
-  float* prow = STORE_P ? Pout + (((size_t)b * H + h) * T + ic) * T : nullptr;
-  const uint32_t drow = (uint32_t)((b * H + h) * T + i);
-  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
-  const bool vec = (T & 3) == 0;
-  f32x16_t o[3];
-#pragma unroll
-  for (int dt = 0; dt < 3; ++dt) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
-  }
-  if (active) load_k(0, kf);
-#pragma unroll 1
-  for (int t = 0; t < nt; ++t) {
-    if (t + 1 < nt) {
-      GT_TILE_LOAD(vr, v, ld, t + 1)
-      if (active) load_k(t + 1, kn);
-    }
-    if (active) {
-      const bf16_t* Vs = Vr + (t & 1) * 32 * VP;
-      f32x16_t st;
-      scores(t, kf, st);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int j0 = 32 * t + 8 * g + 4 * hh;
-        float p4[4];
-#pragma unroll
-        for (int e2 = 0; e2 < 4; ++e2) p4[e2] = __expf(st[4 * g + e2] - mx) * rden;
-        if (STORE_P && i < T) {
-          if (vec && j0 + 3 < T) *reinterpret_cast<float4*>(prow + j0) = make_float4(p4[0], p4[1], p4[2], p4[3]);
-          else {
-#pragma unroll
-            for (int e2 = 0; e2 < 4; ++e2) if (j0 + e2 < T) prow[j0 + e2] = p4[e2];
-          }
-        }
-#pragma unroll
-        for (int e2 = 0; e2 < 4; ++e2) {
-          const int j = j0 + e2;
-          float pd = p4[e2];
-          if (drop_thresh) pd = drop_keep(drop_seed, drow, j, drop_thresh) ? pd * drop_scale : 0.f;
-          st[4 * g + e2] = pd;
-          const int rel = j - i + WIN;
-          if ((unsigned)rel <= 2u * WIN && j < T) pb[r * 16 + rel] = f2bf(pd);
-        }
-      }
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        float f8[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f8[e] = st[8 * s2 + e];
-        const bf16x8_t pf = pack8(f8);
-#pragma unroll
-        for (int dt = 0; dt < 3; ++dt) {
-          const bf16_t* va = Vs + (16 * s2 + 4 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
-          const bf16x8_t af = tr_frag8(va, va + 8 * VP);
-          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, pf, o[dt], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int ks = 0; ks < 6; ++ks) kf[ks] = kn[ks];
-    }
-    if (t + 1 < nt) { GT_TILE_STORE(Vr + ((t + 1) & 1) * 32 * VP, vr) }
-    __syncthreads();
-  }
-  if (!active) return;
-  {
-    const bf16x8_t bfp = *reinterpret_cast<const bf16x8_t*>(pb + r * 16 + 8 * hh);      // band(P)^T: k = rel
-#pragma unroll
-    for (int dt = 0; dt < 3; ++dt) {
-      const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(EvT + (32 * dt + r) * 16 + 8 * hh);
-      o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfp, o[dt], 0, 0, 0);
-    }
-  }
-  if (i < T && i <= nv1) {
-#pragma unroll
-    for (int dt = 0; dt < 3; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = 32 * dt + 8 * g + 4 * hh;
-        *reinterpret_cast<uint2*>(out + (rbase + i) * ldo + h * D + d) =
-            make_uint2(pack2bf(o[dt][4 * g], o[dt][4 * g + 1]), pack2bf(o[dt][4 * g + 2], o[dt][4 * g + 3]));
-      }
-  }
+__global__ __launch_bounds__(256, 2) void gt_attn_long_fwd_stats_kernel(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,
+    const float* __restrict__ Ek, const float* __restrict__ Ev, const int32_t* __restrict__ lens,
+    bf16_t* __restrict__ out, int ldo, float* __restrict__ Pout,
+    int T, int Tp, const int32_t* row0, int H, uint32_t drop_thresh, uint32_t drop_seed, float drop_scale, const uint32_t* __restrict__ seed_dev)
+{
+  constexpr bool STORE_P = false, STATS = true;
+#include "attn_long_fwd_body.inc"
 }
 
 // =========================================================================================
@@ -594,6 +415,483 @@ __global__ __launch_bounds__(256, 2) void gt_attn_long_bwd_kv_kernel(
   }
 }
 
+// =========================================================================================
+// P-free backward (gt_attn_bwd_stats): nothing of size T^2 is read or written.  Both kernels recompute P tile by tile from q, k, Ek
+// and the forward's row statistics (mx, rden): P[i, j] = __expf(s[i, j] - mx_i) * rden_i, the forward's own expression.
+// Between them goes one record of WSQ floats per query row i < T of every (b, h):
+//   [0] Dsum_i   [1 .. 9] q_i . Ek[r]   [10 .. 18] dO_i . Ev[r]   [19] zero
+// (the qe / doe band tables of the query side, so both kernels add the same bits on the band).
+constexpr int WSQ = 20;
+
+// Query side: gt_attn_long_bwd_q_kernel with load_p4 replaced by the forward's `scores` (K fragment as A, Q fragment as B, band,
+// scale, mask) and the forward's P expression, so P, Dsum, the bf16 dS operand and the dQ chain are the saved-P kernel's bit for
+// bit.  The K fragments of the score MFMAs are 16-byte row reads of the K ring that pass B stages anyway; pass A stages the same
+// ring (one barrier per tile there too) instead of holding a second set of K fragments and their prefetch copy in registers: that
+// keeps the kernel at two workgroups per CU.  Tile t of pass A sits in slot t & 1; its last step stages tile 0 again, so tile t
+// of pass B sits in slot (nt + t) & 1.  The bf16 Ek rows of the qe table are read out of EkT (the same f2bf values as the
+// forward's Eks image), so no second Ek image is staged.
+constexpr size_t LDS_BWD_QS = LDS_BWD_Q + (size_t)4 * 32 * NW * 4;
+
+__global__ __launch_bounds__(256, 2) void gt_attn_long_bwd_q_stats_kernel(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,
+    const float* __restrict__ Ek, const float* __restrict__ Ev, const int32_t* __restrict__ lens,
+    const bf16_t* __restrict__ dout, int lddo, const float* __restrict__ stats, float* __restrict__ wsq,
+    bf16_t* __restrict__ dq, int lddq, float* __restrict__ dEk, float* __restrict__ dEv,
+    int T, int Tp, const int32_t* row0, int H, uint32_t drop_thresh, uint32_t drop_seed, float drop_scale, const uint32_t* __restrict__ seed_dev)
+{
+  if (seed_dev) drop_seed ^= *seed_dev;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  bf16_t* Kr  = reinterpret_cast<bf16_t*>(smem);                 // K ring: two [32][VP] tiles
+  bf16_t* Evs = Kr + 2 * 32 * VP;                                // [32][KP]    rows >= 9 zero
+  bf16_t* EkT = Evs + 32 * KP;                                   // [96][16]
+  float*  Acc = reinterpret_cast<float*>(EkT + D * 16);          // [2][NW][D]  block-local dEk | dEv
+  float*  DOE = Acc + 2 * NW * D;                                // [4][32][NW]
+  float*  QE  = DOE + 4 * 32 * NW;                               // [4][32][NW]
+  bf16_t* WB  = reinterpret_cast<bf16_t*>(QE + 4 * 32 * NW);     // [4][LWBN]
+
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+  const int len = lens[b];
+  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
+  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;          // see gt_attn_bwd_q_mfma_kernel
+  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
+
+  for (int i = tid; i < 32 * D; i += 256) { const int rr = i / D, c = i - rr * D; Evs[rr * KP + c] = rr < NW ? f2bf(Ev[rr * D + c]) : (bf16_t)0; }
+  for (int i = tid; i < D * 16; i += 256) { const int d = i >> 4, rr = i & 15; EkT[i] = rr < NW ? f2bf(Ek[rr * D + d]) : (bf16_t)0; }
+  for (int i = tid; i < 2 * NW * D; i += 256) Acc[i] = 0.f;
+  for (int i = tid; i < 4 * (32 * 16 + 2 * 16 * BTP); i += 256) {             // band tables start at zero
+    const int ww = i / (32 * 16 + 2 * 16 * BTP), o = i - ww * (32 * 16 + 2 * 16 * BTP);
+    WB[ww * LWBN + o] = 0;
+  }
+  const int nt = (T + 31) >> 5;                                  // key tiles that hold keys (uniform)
+  uint4 kr[2];
+  GT_TILE_LOAD(kr, k, ld, 0)
+  GT_TILE_STORE(Kr, kr)
+  __syncthreads();
+
+  const int i0 = (blockIdx.x * 4 + w) * 32;
+  const bool active = i0 < T;                                    // wave-uniform
+  const int i = i0 + r;
+  const int ic = i < T ? i : T - 1;
+  float* doe = DOE + w * 32 * NW;
+  float* qe = QE + w * 32 * NW;
+  bf16_t* dSB = WB + w * LWBN;
+  bf16_t* dSBT = dSB + 32 * 16;
+  bf16_t* PdBT = dSBT + 16 * BTP;
+  bf16_t* QD = PdBT + 16 * BTP;
+  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
+  const size_t bhT = ((size_t)b * H + h) * T;
+
+  bf16x8_t dof[6];
+#pragma unroll
+  for (int ks = 0; ks < 6; ++ks)
+    dof[ks] = *reinterpret_cast<const bf16x8_t*>(dout + RW(ic) * lddo + h * D + ks * 16 + 8 * hh);
+  // This wave's Q rows sit in its QD strip (free until the dEk / dEv contractions at the end) and the Q fragment of an MFMA is a
+  // 16-byte row read there: 24 registers fewer than holding them.  Rows >= T are zero; the forward read row T - 1 there, and in
+  // both nothing computed for such a query is stored.
+  for (int c = lane; c < 32 * (D / 8); c += 64) {
+    const int rr = c / (D / 8), c8 = c - rr * (D / 8);
+    uint4 x = make_uint4(0, 0, 0, 0);
+    if (i0 + rr < T) x = *reinterpret_cast<const uint4*>(q + RW(i0 + rr) * ld + h * D + c8 * 8);
+    *reinterpret_cast<uint4*>(QD + rr * VP + c8 * 8) = x;
+  }
+  __builtin_amdgcn_wave_barrier();
+  auto qf = [&](int ks) { return *reinterpret_cast<const bf16x8_t*>(QD + r * VP + ks * 16 + 8 * hh); };
+  if (active) {
+    f32x16_t acc, acq;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) { acc[e] = 0.f; acq[e] = 0.f; }
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks) {
+      const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(Evs + r * KP + ks * 16 + 8 * hh);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, dof[ks], acc, 0, 0, 0);
+      s16x8_t ek = {0, 0, 0, 0, 0, 0, 0, 0};                      // row r of bf16 Ek (rows >= 9 zero), out of its transposed image
+      if (r < NW) {
+#pragma unroll
+        for (int x = 0; x < 8; ++x) ek[x] = (short)EkT[(ks * 16 + 8 * hh + x) * 16 + r];
+      }
+      acq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, ek), qf(ks), acq, 0, 0, 0);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { doe[r * NW + e + 4 * hh] = acc[e]; qe[r * NW + e + 4 * hh] = acq[e]; }
+    if (hh == 0) { doe[r * NW + 8] = acc[4]; qe[r * NW + 8] = acq[4]; }
+  }
+  __builtin_amdgcn_wave_barrier();
+
+  const float inv_sqrt = rsqrtf((float)D);
+  const float mx = stats[(bhT + ic) * 2], rden = stats[(bhT + ic) * 2 + 1];
+  const uint32_t drow = (uint32_t)((b * H + h) * T + i);
+
+  // V fragments of key tile t: lane (key r of the tile, k-half hh); rows >= T are zero
+  auto load_v = [&](int t, bf16x8_t* vf) {
+    const int j = 32 * t + r;
+    if (j < T) {
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) vf[ks] = *reinterpret_cast<const bf16x8_t*>(v + RW(j) * ld + h * D + ks * 16 + 8 * hh);
+    } else {
+      const uint4 z = make_uint4(0, 0, 0, 0);
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) vf[ks] = __builtin_bit_cast(bf16x8_t, z);
+    }
+  };
+  auto dp_tile = [&](const bf16x8_t* vf, f32x16_t& st) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) st[e] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[ks], dof[ks], st, 0, 0, 0);
+  };
+  // P of one tile from the staged K tile Ks (rows >= T zero, as load_k of the forward leaves them): the forward's scores lambda,
+  // then its P expression (element e <-> key 32t + (e&3) + 8(e>>2) + 4hh)
+  auto p_tile = [&](int t, const bf16_t* Ks, f32x16_t& sp) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) sp[e] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks) {
+      const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(Ks + r * VP + ks * 16 + 8 * hh);
+      sp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf(ks), sp, 0, 0, 0);
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int j = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
+      float sc = sp[e];
+      const int rel = j - i + WIN;
+      if ((unsigned)rel <= 2u * WIN) sc += qe[r * NW + rel];
+      sc *= inv_sqrt;
+      if (j >= T) sc = -3.0e38f;                                 // not a key at all
+      else if (j >= len || i >= len) sc = -1e4f;
+      sp[e] = __expf(sc - mx) * rden;
+    }
+  };
+  auto dp_elem = [&](float dp, int j) {
+    const int rel = j - i + WIN;
+    if ((unsigned)rel <= 2u * WIN) dp += doe[r * NW + rel];
+    if (drop_thresh) dp = drop_keep(drop_seed, drow, j, drop_thresh) ? dp * drop_scale : 0.f;
+    return j >= T ? 0.f : dp;
+  };
+
+  // ---- pass A: Dsum = sum_j dP P; K tile t in ring slot t & 1, the last step stages tile 0 for pass B
+  float dsum = 0.f;
+  bf16x8_t vf[6], vn[6];
+  if (active) load_v(0, vf);
+#pragma unroll 1
+  for (int t = 0; t < nt; ++t) {
+    const int tn = t + 1 < nt ? t + 1 : 0;
+    GT_TILE_LOAD(kr, k, ld, tn)
+    if (active) {
+      load_v(tn, vn);
+      f32x16_t st, sp;
+      p_tile(t, Kr + (t & 1) * 32 * VP, sp);
+      dp_tile(vf, st);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int j0 = 32 * t + 8 * g + 4 * hh;
+#pragma unroll
+        for (int e2 = 0; e2 < 4; ++e2) dsum += dp_elem(st[4 * g + e2], j0 + e2) * sp[4 * g + e2];
+      }
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) vf[ks] = vn[ks];
+    }
+    GT_TILE_STORE(Kr + ((t + 1) & 1) * 32 * VP, kr)
+    __syncthreads();
+  }
+  if (active) {
+    dsum += __shfl_xor(dsum, 32);
+    if (i < T) {                                                 // what the key side needs of this query row
+      float* rec = wsq + (bhT + i) * WSQ;
+      const float* tab = hh ? doe : qe;
+      if (hh == 0) rec[0] = dsum; else rec[WSQ - 1] = 0.f;
+#pragma unroll
+      for (int x = 0; x < NW; ++x) rec[1 + NW * hh + x] = tab[r * NW + x];
+    }
+  }
+
+  // ---- pass B: recompute P and dPd^T per tile, dS^T, dQ^T += K^T dS^T; K tile t in ring slot (nt + t) & 1
+  f32x16_t o[3];
+#pragma unroll
+  for (int dt = 0; dt < 3; ++dt) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
+  }
+#pragma unroll 1
+  for (int t = 0; t < nt; ++t) {
+    if (t + 1 < nt) {
+      GT_TILE_LOAD(kr, k, ld, t + 1)
+      if (active) load_v(t + 1, vn);
+    }
+    if (active) {
+      const bf16_t* Ks = Kr + ((nt + t) & 1) * 32 * VP;
+      f32x16_t st, sp;
+      p_tile(t, Ks, sp);
+      dp_tile(vf, st);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int j0 = 32 * t + 8 * g + 4 * hh;
+#pragma unroll
+        for (int e2 = 0; e2 < 4; ++e2) {
+          const int j = j0 + e2;
+          const float p = sp[4 * g + e2];
+          float ds = p * (dp_elem(st[4 * g + e2], j) - dsum) * inv_sqrt;
+          float pd = p;
+          if (drop_thresh) pd = drop_keep(drop_seed, drow, j, drop_thresh) ? pd * drop_scale : 0.f;
+          if (j >= T || j >= len || i >= len || i >= T) ds = 0.f;          // masked_fill blocks the gradient
+          if (i >= len || i >= T) pd = 0.f;                                // padded queries carry no upstream gradient
+          st[4 * g + e2] = ds;
+          if (j < T) {
+            const int rel = j - i + WIN;
+            if ((unsigned)rel <= 2u * WIN) { const bf16_t db = f2bf(ds); dSB[r * 16 + rel] = db; dSBT[rel * BTP + r] = db; PdBT[rel * BTP + r] = f2bf(pd); }
+          }
+        }
+      }
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        float f8[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f8[e] = st[8 * s2 + e];
+        const bf16x8_t pf = pack8(f8);
+#pragma unroll
+        for (int dt = 0; dt < 3; ++dt) {
+          const bf16_t* ka = Ks + (16 * s2 + 4 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          const bf16x8_t af = tr_frag8(ka, ka + 8 * VP);
+          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, pf, o[dt], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) vf[ks] = vn[ks];
+    }
+    if (t + 1 < nt) { GT_TILE_STORE(Kr + ((nt + t + 1) & 1) * 32 * VP, kr) }
+    __syncthreads();
+  }
+
+  if (active) {
+    {
+      const bf16x8_t bfp = *reinterpret_cast<const bf16x8_t*>(dSB + r * 16 + 8 * hh);
+#pragma unroll
+      for (int dt = 0; dt < 3; ++dt) {
+        const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(EkT + (32 * dt + r) * 16 + 8 * hh);
+        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfp, o[dt], 0, 0, 0);
+      }
+    }
+    if (i < T && i <= nv1) {
+#pragma unroll
+      for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int d = 32 * dt + 8 * g + 4 * hh;
+          *reinterpret_cast<uint2*>(dq + (rbase + i) * lddq + h * D + d) =
+              make_uint2(pack2bf(o[dt][4 * g], o[dt][4 * g + 1]), pack2bf(o[dt][4 * g + 2], o[dt][4 * g + 3]));
+        }
+    }
+    // dEk[r'][d] += sum_i dSBT[r'][i] Q[i][d];  dEv[r'][d] += sum_i PdBT[r'][i] dO[i][d]   (K = 32 queries, one MFMA chain)
+#pragma unroll 1
+    for (int which = 0; which < 2; ++which) {
+      const bf16_t* At = which ? PdBT : dSBT;
+      const bf16_t* src = which ? dout : q;
+      const int lds_ = which ? lddo : ld;
+      __builtin_amdgcn_wave_barrier();                             // the previous contraction has read QD
+      for (int c = lane; c < 32 * (D / 8); c += 64) {              // this wave's Q (dO) rows, rows >= T zero
+        const int rr = c / (D / 8), c8 = c - rr * (D / 8);
+        uint4 x = make_uint4(0, 0, 0, 0);
+        if (i0 + rr < T) x = *reinterpret_cast<const uint4*>(src + RW(i0 + rr) * lds_ + h * D + c8 * 8);
+        *reinterpret_cast<uint4*>(QD + rr * VP + c8 * 8) = x;
+      }
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int dt = 0; dt < 3; ++dt) {
+        f32x16_t acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(At + (r & 15) * BTP + 16 * ks + 8 * hh);
+          if (r >= 16) { const uint4 z = make_uint4(0, 0, 0, 0); af = __builtin_bit_cast(bf16x8_t, z); }
+          const bf16_t* ba = QD + (16 * ks + 8 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          const bf16x8_t bf_ = tr_frag8(ba, ba + 4 * VP);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf_, acc, 0, 0, 0);
+        }
+        float* dstA = Acc + which * NW * D;
+        const int d = 32 * dt + r;                                   // D layout: column = d (lane&31), row r' = (e&3)+8(e>>2)+4hh
+#pragma unroll
+        for (int e = 0; e < 4; ++e) atomicAdd(dstA + (e + 4 * hh) * D + d, acc[e]);
+        if (hh == 0) atomicAdd(dstA + 8 * D + d, acc[4]);
+      }
+    }
+  }
+  __syncthreads();
+  for (int x = tid; x < NW * D; x += 256) {
+    if (Acc[x] != 0.f) atomicAdd(dEk + x, Acc[x]);
+    if (Acc[NW * D + x] != 0.f) atomicAdd(dEv + x, Acc[NW * D + x]);
+  }
+}
+
+// Key side: one workgroup per (utterance, head, 128 keys), a wave owns 32 keys, keeps their K and V fragments in registers (lane =
+// key r, k-half hh, as load_k / load_v form them) and walks the 32-query tiles below lens[b] (tiles wholly past it add nothing).
+// Per tile:  S = Q K^T and dP' = dO V^T with the tile's Q / dO rows (16-byte row reads of the ring) as the A operand and the
+// wave's K / V fragments as B, so a lane holds key j = j0 + r and accumulator element e holds query
+//     i = 32t + (e&3) + 8(e>>2) + 4hh;
+// the band terms come from the query side's records (only the tiles next to the wave's keys touch the band), then P, the keep
+// bit, dS and P' as on the query side, per-query mx / rden / Dsum out of an LDS ring staged one tile ahead.
+// The accumulators are then the B operand of dK^T = Q^T dS and dV^T = dO^T P' up to a permutation of the k index: MFMA s2 takes
+// pack8(st + 8 s2), i.e. k index 8hh + kk <-> query 32t + 16 s2 + 4hh + (kk&3) + 8(kk>>2), and the A fragment
+// tr_frag8(a + (16 s2 + 4hh + qd) VP ..., ... + 8 VP) reads the ring's rows in that same order (the forward's P'V product and the
+// query side's dQ product, with queries where they have keys).
+// One workgroup per CU: the K / V fragments (48 registers), the two accumulator sets (96) and the two score tiles (32) do not fit
+// the 256 registers a lane has at two.
+__global__ __launch_bounds__(256, 1) void gt_attn_long_bwd_kv_stats_kernel(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,
+    const int32_t* __restrict__ lens, const bf16_t* __restrict__ dout, int lddo,
+    const float* __restrict__ stats, const float* __restrict__ wsq,
+    bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int lddk, int T, int Tp, const int32_t* row0, int H,
+    uint32_t drop_thresh, uint32_t drop_seed, float drop_scale, const uint32_t* __restrict__ seed_dev)
+{
+  if (seed_dev) drop_seed ^= *seed_dev;
+  __shared__ __attribute__((aligned(16))) bf16_t Qr[2 * 32 * VP];   // Q ring: two [32][VP] tiles
+  __shared__ __attribute__((aligned(16))) bf16_t Or[2 * 32 * VP];   // dO ring
+  __shared__ __attribute__((aligned(16))) float  Sr[2 * 3 * 32];    // per-query ring: mx[32] | rden[32] | Dsum[32]
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+  const int len = lens[b];
+  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
+  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;          // see gt_attn_bwd_kv_mfma_kernel
+  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
+  const size_t bhT = ((size_t)b * H + h) * T;
+
+  const int nq = len < T ? len : T;
+  const int nqt = (nq + 31) >> 5;                                // query tiles that hold an unpadded query (uniform)
+  // the per-query triple of tile t: thread tid < 96 holds entry tid of mx[32] | rden[32] | Dsum[32]; queries >= T zero
+  auto load_row = [&](int t) {
+    const int i = 32 * t + (tid & 31);
+    if (tid >= 96 || i >= T) return 0.f;
+    return tid < 64 ? stats[(bhT + i) * 2 + (tid >> 5)] : wsq[(bhT + i) * WSQ];
+  };
+  uint4 qr[2], dr[2];
+  float sr = load_row(0);
+  GT_TILE_LOAD(qr, q, ld, 0)
+  GT_TILE_LOAD(dr, dout, lddo, 0)
+  GT_TILE_STORE(Qr, qr)
+  GT_TILE_STORE(Or, dr)
+  if (tid < 96) Sr[tid] = sr;
+  __syncthreads();
+
+  const int j0 = blockIdx.x * 128 + 32 * w;
+  const bool active = j0 < T;                                    // wave-uniform
+  const int j = j0 + r;
+  const int tj = j0 >> 5;                                        // the query tile of this wave's keys: tiles tj - 1 .. tj + 1 touch the band
+  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
+  const float inv_sqrt = rsqrtf((float)D);
+  bf16x8_t kf[6], vf[6];
+  if (active && j < T) {
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks) {
+      kf[ks] = *reinterpret_cast<const bf16x8_t*>(k + RW(j) * ld + h * D + ks * 16 + 8 * hh);
+      vf[ks] = *reinterpret_cast<const bf16x8_t*>(v + RW(j) * ld + h * D + ks * 16 + 8 * hh);
+    }
+  } else {
+    const uint4 z = make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks) { kf[ks] = __builtin_bit_cast(bf16x8_t, z); vf[ks] = __builtin_bit_cast(bf16x8_t, z); }
+  }
+  f32x16_t ak[3], av[3];
+#pragma unroll
+  for (int dt = 0; dt < 3; ++dt) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) { ak[dt][e] = 0.f; av[dt][e] = 0.f; }
+  }
+#pragma unroll 1
+  for (int t = 0; t < nqt; ++t) {
+    if (t + 1 < nqt) {
+      GT_TILE_LOAD(qr, q, ld, t + 1)
+      GT_TILE_LOAD(dr, dout, lddo, t + 1)
+      sr = load_row(t + 1);
+    }
+    if (active) {
+      const bf16_t* Qs = Qr + (t & 1) * 32 * VP;
+      const bf16_t* dOs = Or + (t & 1) * 32 * VP;
+      const float* Ss = Sr + (t & 1) * 96;
+      f32x16_t ss, sd;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) { ss[e] = 0.f; sd[e] = 0.f; }
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) {
+        const bf16x8_t qa = *reinterpret_cast<const bf16x8_t*>(Qs + r * VP + ks * 16 + 8 * hh);
+        const bf16x8_t da = *reinterpret_cast<const bf16x8_t*>(dOs + r * VP + ks * 16 + 8 * hh);
+        ss = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], ss, 0, 0, 0);
+        sd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[ks], sd, 0, 0, 0);
+      }
+      const bool band = t + 1 >= tj && t <= tj + 1;              // wave-uniform
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float4 mx4 = *reinterpret_cast<const float4*>(Ss + 8 * g + 4 * hh);
+        const float4 rd4 = *reinterpret_cast<const float4*>(Ss + 32 + 8 * g + 4 * hh);
+        const float4 ds4 = *reinterpret_cast<const float4*>(Ss + 64 + 8 * g + 4 * hh);
+        const float mxs[4] = {mx4.x, mx4.y, mx4.z, mx4.w}, rds[4] = {rd4.x, rd4.y, rd4.z, rd4.w}, dss[4] = {ds4.x, ds4.y, ds4.z, ds4.w};
+#pragma unroll
+        for (int e2 = 0; e2 < 4; ++e2) {
+          const int i = 32 * t + 8 * g + 4 * hh + e2;
+          float sc = ss[4 * g + e2], dp = sd[4 * g + e2];
+          if (band) {
+            const int rel = j - i + WIN;
+            if ((unsigned)rel <= 2u * WIN && i < T) {
+              const float* rec = wsq + (bhT + i) * WSQ;
+              sc += rec[1 + rel];
+              dp += rec[1 + NW + rel];
+            }
+          }
+          sc *= inv_sqrt;
+          if (j >= T) sc = -3.0e38f;                             // not a key at all
+          else if (j >= len || i >= len) sc = -1e4f;
+          const float p = __expf(sc - mxs[e2]) * rds[e2];
+          float pd = p;
+          if (drop_thresh) {
+            const bool keep = drop_keep(drop_seed, (uint32_t)((b * H + h) * T + i), j, drop_thresh);
+            dp = keep ? dp * drop_scale : 0.f;
+            pd = keep ? pd * drop_scale : 0.f;
+          }
+          if (j >= T) dp = 0.f;
+          float ds = p * (dp - dss[e2]) * inv_sqrt;
+          if (j >= T || j >= len || i >= len || i >= T) ds = 0.f;            // masked_fill blocks the gradient
+          if (j >= T || i >= len || i >= T) pd = 0.f;                        // padded queries carry no upstream gradient
+          ss[4 * g + e2] = ds;
+          sd[4 * g + e2] = pd;
+        }
+      }
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        float f8[8], g8[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { f8[e] = ss[8 * s2 + e]; g8[e] = sd[8 * s2 + e]; }
+        const bf16x8_t bds = pack8(f8), bpd = pack8(g8);         // bf16, as the saved-P path's workspace held them
+#pragma unroll
+        for (int dt = 0; dt < 3; ++dt) {
+          const bf16_t* qa = Qs + (16 * s2 + 4 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          const bf16_t* da = dOs + (16 * s2 + 4 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
+          ak[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag8(qa, qa + 8 * VP), bds, ak[dt], 0, 0, 0);
+          av[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag8(da, da + 8 * VP), bpd, av[dt], 0, 0, 0);
+        }
+      }
+    }
+    if (t + 1 < nqt) {
+      GT_TILE_STORE(Qr + ((t + 1) & 1) * 32 * VP, qr)
+      GT_TILE_STORE(Or + ((t + 1) & 1) * 32 * VP, dr)
+      if (tid < 96) Sr[((t + 1) & 1) * 96 + tid] = sr;
+    }
+    __syncthreads();
+  }
+  if (active && j < T && j <= nv1) {
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d = 32 * dt + 8 * g + 4 * hh;
+        *reinterpret_cast<uint2*>(dk + RW(j) * lddk + h * D + d) =
+            make_uint2(pack2bf(ak[dt][4 * g], ak[dt][4 * g + 1]), pack2bf(ak[dt][4 * g + 2], ak[dt][4 * g + 3]));
+        *reinterpret_cast<uint2*>(dv + RW(j) * lddk + h * D + d) =
+            make_uint2(pack2bf(av[dt][4 * g], av[dt][4 * g + 1]), pack2bf(av[dt][4 * g + 2], av[dt][4 * g + 3]));
+      }
+  }
+}
+
 #undef GT_TILE_LOAD
 #undef GT_TILE_STORE
 
@@ -642,5 +940,47 @@ int gt_attn_bwd_long_impl(const void* q, const void* k, const void* v, int ld, c
   hipLaunchKernelGGL(gt_attn_long_bwd_kv_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, st,
                      static_cast<const bf16_t*>(q), ld, static_cast<const bf16_t*>(dout), lddo, dST, PdT, TI,
                      static_cast<bf16_t*>(dk), static_cast<bf16_t*>(dv), lddq, T, Tp, row0, H);
+  return gt_launch_status(__func__);
+}
+
+// The P-free pair (gt_attn_fwd_stats / gt_attn_bwd_stats): the caller has checked the shape; 1 = strides / operand alignment
+// the kernels do not take.
+size_t gt_attn_long_stats_ws_bytes(int B, int T, int H) { return (size_t)B * H * T * WSQ * sizeof(float); }
+
+int gt_attn_fwd_long_stats_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                                const int32_t* lens, void* out, int ldo, float* stats, int B, int T, int Tp, const int32_t* row0, int H,
+                                uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
+{
+  if ((ld & 7) || (ldo & 3)) return 1;
+  if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || ((uintptr_t)stats & 7)) return 1;
+  hipLaunchKernelGGL(gt_attn_long_fwd_stats_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
+                     static_cast<bf16_t*>(out), ldo, stats, T, Tp, row0, H, th, sd, sc, seed_dev);
+  return gt_launch_status(__func__);
+}
+
+int gt_attn_bwd_long_stats_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                                const int32_t* lens, const void* dout, int lddo, const float* stats, void* ws,
+                                void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
+                                int B, int T, int Tp, const int32_t* row0, int H, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
+{
+  if ((ld & 7) || (lddo & 7) || (lddq & 3)) return 1;
+  if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)ws) & 15) || ((uintptr_t)stats & 7)) return 1;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_long_bwd_q_stats_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BWD_QS) != hipSuccess)
+      return GT_E_LAUNCH;
+    attr = true;
+  }
+  float* wsq = static_cast<float*>(ws);
+  hipLaunchKernelGGL(gt_attn_long_bwd_q_stats_kernel, dim3((T + 127) / 128, H, B), dim3(256), LDS_BWD_QS, st,
+                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
+                     static_cast<const bf16_t*>(dout), lddo, stats, wsq, static_cast<bf16_t*>(dq), lddq, dEk, dEv,
+                     T, Tp, row0, H, th, sd, sc, seed_dev);
+  hipLaunchKernelGGL(gt_attn_long_bwd_kv_stats_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, st,
+                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, lens,
+                     static_cast<const bf16_t*>(dout), lddo, stats, wsq,
+                     static_cast<bf16_t*>(dk), static_cast<bf16_t*>(dv), lddq, T, Tp, row0, H, th, sd, sc, seed_dev);
   return gt_launch_status(__func__);
 }

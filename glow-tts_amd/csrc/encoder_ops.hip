@@ -1024,6 +1024,49 @@ extern "C" int gt_attn_bwd(const void* q, const void* k, const void* v, int ld, 
   GT_RET();
 }
 
+// The P-free pair: the key-tiled family only, no fallback.  Checks in the header's order: NULL pointers, the token limit and the
+// shape, the workspace size, alignment.
+extern "C" size_t gt_attn_stats_bytes(int B, int T, int H)
+{
+  if (B <= 0 || T <= 0 || H <= 0) return 0;
+  return (size_t)B * H * T * 2 * sizeof(float);
+}
+
+extern "C" size_t gt_attn_bwd_stats_workspace_bytes(int B, int T, int H)
+{
+  if (B <= 0 || T <= 0 || H <= 0) return 0;
+  return gt_attn_long_stats_ws_bytes(B, T, H);
+}
+
+extern "C" int gt_attn_fwd_stats(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                                 const int32_t* lens, void* out, int ldo, float* stats, int B, int T, int Tp, const int32_t* row0, int H, int D,
+                                 int win, float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream)
+{
+  if (!q || !k || !v || !Ek || !Ev || !lens || !out || !stats || B <= 0 || T <= 0 || H <= 0) return GT_E_INVAL;
+  if (T > GT_ATTN_LONG_MAX_T || !gt_attn_long_shape(T, D, win) || drop_p >= 1.f) return GT_E_UNSUPPORTED;
+  uint32_t th; float sc;
+  gt_drop_params(drop_p, &th, &sc);
+  const int rc = gt_attn_fwd_long_stats_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, stats, B, T, Tp, row0, H, th, drop_seed, sc, seed_dev, stream);
+  return rc == 1 ? GT_E_ALIGN : rc;
+}
+
+extern "C" int gt_attn_bwd_stats(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                                 const int32_t* lens, const void* dout, int lddo, const float* stats, void* workspace, size_t workspace_bytes,
+                                 void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
+                                 int B, int T, int Tp, const int32_t* row0, int H, int D, int win, float drop_p, uint32_t drop_seed,
+                                 const uint32_t* seed_dev, void* stream)
+{
+  if (!q || !k || !v || !Ek || !Ev || !lens || !dout || !stats || !workspace || !dq || !dk || !dv || !dEk || !dEv || B <= 0 || T <= 0 || H <= 0)
+    return GT_E_INVAL;
+  if (T > GT_ATTN_LONG_MAX_T || !gt_attn_long_shape(T, D, win) || drop_p >= 1.f) return GT_E_UNSUPPORTED;
+  if (workspace_bytes < gt_attn_bwd_stats_workspace_bytes(B, T, H)) return GT_E_INVAL;
+  uint32_t th; float sc;
+  gt_drop_params(drop_p, &th, &sc);
+  const int rc = gt_attn_bwd_long_stats_impl(q, k, v, ld, Ek, Ev, lens, dout, lddo, stats, workspace, dq, dk, dv, lddq, dEk, dEv,
+                                             B, T, Tp, row0, H, th, drop_seed, sc, seed_dev, stream);
+  return rc == 1 ? GT_E_ALIGN : rc;
+}
+
 extern "C" int gt_embedding_fwd(const int64_t* ids, const float* emb, const int32_t* lens, float* out_f32, void* out_bf16,
                                 int B, int T, int Tp, const int32_t* row0, int R, int C, int ld, float scale, void* stream)
 {

@@ -39,6 +39,18 @@ int gt_attn_bwd_long_impl(const void* q, const void* k, const void* v, int ld, c
                           int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win, uint32_t drop_thresh, uint32_t drop_seed, float drop_scale,
                           const uint32_t* seed_dev, void* stream);
 
+// The P-free pair of the key-tiled family (gt_attn_fwd_stats / gt_attn_bwd_stats): the caller has checked gt_attn_long_shape and the
+// workspace size (gt_attn_long_stats_ws_bytes); 1 = strides / operand alignment the kernels do not take.
+size_t gt_attn_long_stats_ws_bytes(int B, int T, int H);
+int gt_attn_fwd_long_stats_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                                const int32_t* lens, void* out, int ldo, float* stats, int B, int T, int Tp, const int32_t* row0, int H,
+                                uint32_t drop_thresh, uint32_t drop_seed, float drop_scale, const uint32_t* seed_dev, void* stream);
+int gt_attn_bwd_long_stats_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                                const int32_t* lens, const void* dout, int lddo, const float* stats, void* ws,
+                                void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
+                                int B, int T, int Tp, const int32_t* row0, int H, uint32_t drop_thresh, uint32_t drop_seed, float drop_scale,
+                                const uint32_t* seed_dev, void* stream);
+
 // The chip-wide kernel that writes the dense 0/1 path [B, T_x, T_y] (element type path_dtype, GT_DT_*) from the int32
 // [B, T_x + 1] row start columns both MAS kernels leave in their workspace (mas.hip).  0 or GT_E_LAUNCH.
 int gt_mas_expand_launch(const int32_t* starts, void* path, int path_dtype, int B, int T_x, int T_y, void* stream);

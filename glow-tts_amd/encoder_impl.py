@@ -76,11 +76,21 @@ def attn_long_shape(T, D, win):
     return D == 96 and win == 4 and 505 < T <= ATTN_MAX_T
 
 
+class AttnStats:
+    """What mha_fwd(keep_p="stats") saves where P was: t = stats [B, H, T, 2] fp32 of gt_attn_fwd_stats."""
+
+    def __init__(self, t):
+        self.t = t
+
+
 def mha_fwd(rc, att, xb, p, seed, keep_p=True):
     """keep_p=False: a forward nobody differentiates (synthesis).  At the shapes of the key-tiled kernels (gt_attn_long_shape) no
     [B, H, T, T] tensor is then allocated, gt_attn_fwd stores no P and the saved tuple carries None in its place; `out` is the same bit
     for bit.  At every other shape the flag changes nothing.  It cannot be inferred from grad mode: the training forward runs inside
-    _RowsFn.apply, where grad mode is off."""
+    _RowsFn.apply, where grad mode is off.
+    keep_p="stats": a training forward without a saved P.  At the key-tiled shapes gt_attn_fwd_stats stores two floats per query row
+    ([B, H, T, 2]: row maximum and reciprocal denominator) where P would be, `out` is the same bit for bit, and mha_bwd recomputes P
+    tile by tile (gt_attn_bwd_stats); at every other shape it is keep_p=True."""
     if rc.T > ATTN_MAX_T:       # before any allocation or launch: P and the backward's workspace are 4 B H T^2 bytes each per layer
         raise ValueError(f"attention takes at most {ATTN_MAX_T} tokens per utterance (GT_ATTN_LONG_MAX_T), got T = {rc.T}")
     dev = xb.device
@@ -92,12 +102,17 @@ def mha_fwd(rc, att, xb, p, seed, keep_p=True):
     # gradients in the wgrad GEMM, and 0 * NaN garbage would poison it)
     o = ops_zeros_big((R, C), torch.bfloat16, dev)
     P = None
-    if keep_p or not attn_long_shape(rc.T, D, att.window_size):
+    long_shape = attn_long_shape(rc.T, D, att.window_size)
+    stats = isinstance(keep_p, str) and keep_p == "stats" and long_shape
+    if stats:
+        P = AttnStats(torch.empty(rc.B, H, rc.T, 2, dtype=torch.float32, device=dev))
+    elif keep_p or not long_shape:
         P = torch.empty(rc.B, H, rc.T, rc.T, dtype=torch.float32, device=dev)
     Ek = att.emb_rel_k.detach().reshape(-1, D).contiguous()
     Ev = att.emb_rel_v.detach().reshape(-1, D).contiguous()
-    call.gt_attn_fwd(q, k, v, 3 * C, Ek, Ev, rc.lengths, o, C, P, rc.B, rc.T, rc.Tp, rc.row0, H, D, att.window_size, float(p), int(seed),
-                     seed_word(dev) if p > 0 else None, _st(dev))
+    (call.gt_attn_fwd_stats if stats else call.gt_attn_fwd)(
+        q, k, v, 3 * C, Ek, Ev, rc.lengths, o, C, P.t if stats else P, rc.B, rc.T, rc.Tp, rc.row0, H, D, att.window_size, float(p), int(seed),
+        seed_word(dev) if p > 0 else None, _st(dev))
     y = conv_rows(o, att.conv_o.pc, rc, bias=att.conv_o.bias)
     return y, (xb, q, k, v, o, P, Ek, Ev, p, seed)
 
@@ -117,12 +132,14 @@ def mha_bwd(rc, att, saved, dy, grads):
     dqkv = ops_zeros_big((R, 3 * C), torch.bfloat16, dev)
     dq, dk, dv = dqkv[:, :C], dqkv[:, C:2 * C], dqkv[:, 2 * C:]
     from .flow_impl import _scratch
-    ws_bytes = call.gt_attn_bwd_workspace_bytes(rc.B, rc.T, H)
-    ws = _scratch("attn_bwd", ws_bytes, dev)
+    stats = isinstance(P, AttnStats)
+    ws_bytes = (call.gt_attn_bwd_stats_workspace_bytes if stats else call.gt_attn_bwd_workspace_bytes)(rc.B, rc.T, H)
+    ws = _scratch("attn_bwd_stats" if stats else "attn_bwd", ws_bytes, dev)
     dEk = grad_accumulator(att.emb_rel_k, Ek.shape)
     dEv = grad_accumulator(att.emb_rel_v, Ev.shape)
-    call.gt_attn_bwd(q, k, v, 3 * C, Ek, Ev, rc.lengths, do, C, P, ws, ws_bytes, dq, dk, dv, 3 * C, dEk, dEv, rc.B, rc.T, rc.Tp, rc.row0, H, D,
-                     att.window_size, float(p), int(seed), seed_word(dev) if p > 0 else None, _st(dev))
+    (call.gt_attn_bwd_stats if stats else call.gt_attn_bwd)(
+        q, k, v, 3 * C, Ek, Ev, rc.lengths, do, C, P.t if stats else P, ws, ws_bytes, dq, dk, dv, 3 * C, dEk, dEv, rc.B, rc.T, rc.Tp, rc.row0,
+        H, D, att.window_size, float(p), int(seed), seed_word(dev) if p > 0 else None, _st(dev))
     grads[att.emb_rel_k] = dEk.view_as(att.emb_rel_k)
     grads[att.emb_rel_v] = dEv.view_as(att.emb_rel_v)
     grads.update(conv_param_grads(att.conv_q, xb, dq, R))

@@ -266,7 +266,7 @@ class _RowsFn(torch.autograd.Function):
         outs, saved = runner.forward(*tensors)
         ctx.set_materialize_grads(False)          # runners take None for an unused output's gradient (no zero fills)
         ctx.runner, ctx.saved, ctx.n_in = runner, saved, len(tensors)
-        ctx.mark_non_differentiable(*[o for o in outs[n_out:]])
+        ctx.mark_non_differentiable(*[o for o in outs[n_out:] if o is not None])    # None: an output the runner did not keep
         return tuple(outs)
 
     @staticmethod

@@ -269,6 +269,10 @@ class RowsConfig:
         # infer under set_synthesis_front(noise_key="frame"): the frame-rate rows of the pitch / energy predictors are ragged (padded
         # frames cost nothing); False = uniform rows, for measuring the difference (tools/synth_bench.py --cfg5)
         self.frame_rows_ragged = True
+        # the training forward of the text encoder keeps each layer's softmax P [B, H, T, T] for the backward.  False: at the key-tiled
+        # attention shapes (505 < T <= 4096) it keeps two floats per query row instead and the backward recomputes P
+        # (encoder_impl.mha_fwd(keep_p="stats")); at every other shape nothing changes.  train.Trainer(attn_keep_p=)
+        self.attn_keep_p = True
         # how the step is laid out over streams (defaults from the process environment, read when the model is built; the owner of
         # the model — a Trainer, a test — changes THIS object, not a module global):
         import os

@@ -444,12 +444,15 @@ class Trainer:
 
     def __init__(self, model, lr=2e-4, betas=(0.9, 0.98), eps=1e-9, world=1, graph=False, total_steps=None,
                  split_graph=None, ragged=None, max_graphs=8, pad_tx=16, pad_ty=32, kernel_stamps=False, grad_wire="fp32",
-                 force_collectives=False, capture_after=2, ty_boundaries=None, row_round=None, early_decoder_adam=True, pack_in_tail=True, split_roots=True):
+                 force_collectives=False, capture_after=2, ty_boundaries=None, row_round=None, early_decoder_adam=True, pack_in_tail=True, split_roots=True,
+                 attn_keep_p=None):
         """total_steps: length of the OneCycleLR schedule the reference runs (train_ms_emo_lang_pitch.py:161);
         None keeps lr / betas constant.  split_graph=True selects the phased form (the decoder's gradient slice on the wire while the
         encoder's backward runs: three graphs); the default at any world size is ONE backward — the encoder's backward beside the
         decoder's, which is worth 1.16 ms of a 4.84 ms step (bench.py --split-graph 1 at N = 1: 6.0 ms) — and then the whole flat
-        buffer on the wire (114 MB fp32: ~0.3-0.7 ms exposed on an 8-GPU xGMI node) between the two graphs."""
+        buffer on the wire (114 MB fp32: ~0.3-0.7 ms exposed on an 8-GPU xGMI node) between the two graphs.
+        attn_keep_p: None leaves model.rows_cfg.attn_keep_p as it is (True: every encoder layer keeps its softmax P for the backward);
+        False trains texts past 505 tokens without it (ops.RowsConfig.attn_keep_p), eagerly and under the captured step alike."""
         from collections import OrderedDict
         self.model = model
         self.world = world
@@ -512,6 +515,8 @@ class Trainer:
         self.cfg.ragged = (os.environ.get("GT_RAGGED", "1") != "0") if ragged is None else bool(ragged)
         # ragged row count granularity (one graph per rounded size)
         self.cfg.row_round = int(row_round) if row_round else (512 if self.graph_mode else 128)
+        if attn_keep_p is not None:
+            self.cfg.attn_keep_p = bool(attn_keep_p)
         self.ty_boundaries = list(ty_boundaries) if ty_boundaries else None
         # bench.py: device-side begin / end stamps of every fused WaveNet-layer forward launch, valid inside replayed graphs
         self.stamps = None

@@ -332,7 +332,8 @@ int gt_param_partials_reduce(const gt_partials_args* args, void* stream);
  * 505 < T <= GT_ATTN_LONG_MAX_T on key-tiled bf16 MFMA kernels whose LDS and registers do not grow with T (gt_attn_long_shape);
  * the rest runs on the generic kernels, which hold an utterance-head in LDS: at D = 96, win = 4 the forward to T = 597, the
  * backward to T = 505 — GT_E_UNSUPPORTED past what fits, and for every T > GT_ATTN_LONG_MAX_T before anything is launched.
- * P and the workspace are each 4 B H T^2 bytes (4.3 GB at B = 32, H = 2, T = 4096).
+ * P and the workspace are each 4 B H T^2 bytes (4.3 GB at B = 32, H = 2, T = 4096); gt_attn_fwd_stats / gt_attn_bwd_stats below
+ * train the key-tiled shapes with O(B H T) bytes instead.
  * gt_attn_fwd with P == NULL — a forward nobody differentiates (synthesis) — is taken when, and only when, gt_attn_long_shape(T, D,
  * win) holds: the key-tiled kernel then stores no P and writes the same `out`, bit for bit (strides / operand alignment that kernel
  * does not take: GT_E_ALIGN).  At every other shape a NULL P is GT_E_INVAL (T > GT_ATTN_LONG_MAX_T: GT_E_UNSUPPORTED comes first).
@@ -359,6 +360,34 @@ int gt_attn_bwd(const void* q, const void* k, const void* v, int ld, const float
                 void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
                 int B, int T, int Tp, const int32_t* row0, int H, int D, int win, float drop_p, uint32_t drop_seed,
                 const uint32_t* seed_dev, void* stream);
+
+/* The same attention at the key-tiled shapes without anything of size T^2 (opt-in; gt_attn_fwd / gt_attn_bwd are unchanged).
+ * gt_attn_fwd_stats writes the `out` of gt_attn_fwd bit for bit, stores no P, and leaves two floats per query row:
+ *   stats       [B, H, T, 2] fp32, 8-byte aligned, gt_attn_stats_bytes(B,T,H) = 8 B H T bytes: for query i of (b, h)
+ *               stats[..., 0] = mx, the maximum over the keys of the masked, scaled scores, and stats[..., 1] = rden = 1 / sum_j
+ *               exp(s[i,j] - mx), so that P[i,j] = exp(s[i,j] - mx) * rden is the forward's own P.  Every i < T is written, padded
+ *               queries (i >= lens[b]) included.
+ * gt_attn_bwd_stats recomputes P tile by tile from q, k, Ek and stats in both of its kernels; dq equals gt_attn_bwd's bit for bit on
+ * the same operands, dk / dv / dEk / dEv round as gt_attn_bwd's do (bf16 dS and P' feed their MFMAs) and differ from them in fp32
+ * summation order only.  dEk/dEv ACCUMULATE; query rows i >= lens[b] contribute nothing and get dq = 0; one writer per row as above.
+ *   workspace   device scratch of at least gt_attn_bwd_stats_workspace_bytes(B,T,H) = 80 B H T bytes, 16-byte aligned; after the
+ *               call it holds one record of 20 floats per query row, [B, H, T, 20]: [0] Dsum_i = sum_j dP P, [1..9] q_i . Ek[r],
+ *               [10..18] dO_i . Ev[r] (Ek / Ev rounded to bf16, r = j - i + win), [19] zero.
+ * Asynchronous, no allocation, no global state.  Refused before any launch, in this order: a NULL pointer (stats and workspace
+ * included) or a non-positive B, T, H: GT_E_INVAL; T > GT_ATTN_LONG_MAX_T or any shape at which gt_attn_long_shape(T, D, win) is 0 (there
+ * is no other kernel behind these entries), or drop_p >= 1: GT_E_UNSUPPORTED; workspace_bytes too small: GT_E_INVAL; strides or
+ * operand alignment the kernels do not take (ld, lddo multiples of 8, ldo, lddq of 4; q, k, v, dout, workspace 16-byte aligned,
+ * stats 8-byte): GT_E_ALIGN. */
+size_t gt_attn_stats_bytes(int B, int T, int H);
+size_t gt_attn_bwd_stats_workspace_bytes(int B, int T, int H);
+int gt_attn_fwd_stats(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                      const int32_t* lens, void* out, int ldo, float* stats, int B, int T, int Tp, const int32_t* row0, int H, int D, int win,
+                      float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream);
+int gt_attn_bwd_stats(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
+                      const int32_t* lens, const void* dout, int lddo, const float* stats, void* workspace, size_t workspace_bytes,
+                      void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
+                      int B, int T, int Tp, const int32_t* row0, int H, int D, int win, float drop_p, uint32_t drop_seed,
+                      const uint32_t* seed_dev, void* stream);
 
 /* Embedding * scale into rows (models.py:693): fp32 and/or bf16 output, zero halo / padded rows.  emb [n_vocab, C];
  * the rows have stride ld >= C (ld > C: the language embedding of models.py:698-699 fills channels [C, ld) — written by
