@@ -14,6 +14,7 @@ sequences on the rows layout; the noise the reference draws with torch.randn ins
 which is how the parity tests pin the stochastic paths.
 """
 import math
+import os
 
 import torch
 from torch import nn
@@ -25,6 +26,9 @@ from .modules import ConvP, LayerNorm, _RowsFn, _mask_lengths, prepare_all
 from .ops import RowsCtx, conv_rows, grad_accumulator
 
 LN_EPS = 1e-5                     # modules.LayerNorm2 (modules.py:57)
+# process-level default of DilatedDepthSeparableConv.fused (read once at import): one kernel per DDSConv layer and direction
+# (csrc/dds_layer.hip) instead of three forward / four backward launches; off = the per-op launch sequence
+DDS_FUSED = os.environ.get("GT_DDS_FUSED", "0") != "0"
 
 
 def _st(dev):
@@ -55,6 +59,7 @@ class DilatedDepthSeparableConv(nn.Module):
         super().__init__()
         assert kernel_size == 3 and channels == 192, "kernels implement kernel_size 3 at 192 channels (every reference use)"
         self.channels, self.kernel_size, self.num_layers, self.dropout_p = channels, kernel_size, num_layers, dropout_p
+        self.fused = DDS_FUSED
         self.convs_sep = nn.ModuleList()
         self.convs_1x1 = nn.ModuleList()
         self.norms_1 = nn.ModuleList()
@@ -66,6 +71,13 @@ class DilatedDepthSeparableConv(nn.Module):
             self.convs_1x1.append(ConvP(channels, channels, 1, split3=True))
             self.norms_1.append(LayerNorm(channels, eps=LN_EPS))
             self.norms_2.append(LayerNorm(channels, eps=LN_EPS))
+
+    def set_fused(self, on=True):
+        """One kernel per layer and direction (gt_dds_layer_fwd / gt_dds_layer_bwd + gt_dds_dw_bwd) in dds_fwd / dds_bwd; off (the
+        default, GT_DDS_FUSED) = the per-op launches.  The saved tensors are the same, so a forward of one path pairs with the
+        backward of the other.  Returns the switch."""
+        self.fused = bool(on)
+        return self.fused
 
     def forward(self, x, x_mask, g=None):
         """modules.py:718-735 as a stand-alone module: x [b, C, t], x_mask [b, 1, t], g [b, C, t] or None."""
@@ -86,6 +98,17 @@ def dds_fwd(rc, dds, x, train, seed, want_bf16=False):
     for i in range(dds.num_layers):
         sep, n1, c1, n2 = dds.convs_sep[i], dds.norms_1[i], dds.convs_1x1[i], dds.norms_2[i]
         a1 = torch.empty(R, 3 * C, dtype=torch.bfloat16, device=dev)              # bf16x3: [hi | hi | lo]
+        if dds.fused:
+            h2 = torch.empty(R, C, dtype=torch.float32, device=dev)
+            out = torch.empty(R, C, dtype=torch.float32, device=dev)
+            if want_bf16 and i == dds.num_layers - 1:
+                outb = torch.empty(R, 3 * C, dtype=torch.bfloat16, device=dev)
+            call.gt_dds_layer_fwd(x, x.stride(0), sep.weight, sep.bias, n1.gamma, n1.beta, c1.pc.fwd, c1.pc.Kp_f, c1.bias, n2.gamma, n2.beta,
+                                  utt, rc.rowmask, a1, 3 * C, h2, out, outb, 3 * C, R, C, dds.kernel_size ** i, LN_EPS, float(p), int(seed + i),
+                                  ops.seed_word(dev) if p > 0 else None, _st(dev))
+            saved.append((x, a1, h2))
+            x = out
+            continue
         call.gt_dds_sep_fwd(x, x.stride(0), sep.weight, sep.bias, n1.gamma, n1.beta, utt, rc.rowmask, a1, 3 * C, R, C, dds.kernel_size ** i, LN_EPS,
                             _st(dev))
         h2 = conv_rows(a1, c1.pc, rc, bias=c1.bias, out_f32=True)
@@ -95,7 +118,7 @@ def dds_fwd(rc, dds, x, train, seed, want_bf16=False):
                             ops.seed_word(dev) if p > 0 else None, _st(dev))
         saved.append((x, a1, h2))
         x = out
-    if want_bf16:
+    if want_bf16 and outb is None:
         outb = _split3_rows(x)
     return x, outb, (saved, p, seed)
 
@@ -119,6 +142,30 @@ def dds_bwd(rc, dds, saved_all, dy, grads):
         sep, n1, c1, n2 = dds.convs_sep[i], dds.norms_1[i], dds.convs_1x1[i], dds.norms_2[i]
         x, a1, h2 = saved[i]
         dg2, db2 = grad_accumulator(n2.gamma), grad_accumulator(n2.beta)
+        if dds.fused:
+            dg1, db1 = grad_accumulator(n1.gamma), grad_accumulator(n1.beta)
+            dh2 = torch.empty(R, C, dtype=torch.bfloat16, device=dev)             # the hi part: the weight gradient's operand
+            dh1 = torch.empty(R, C, dtype=torch.float32, device=dev)
+            n_lp = call.gt_dds_layer_partial_rows(R)
+            ptl = torch.empty(n_lp, 2 * C, dtype=torch.float32, device=dev) if q is not None else None
+            call.gt_dds_layer_bwd(x, x.stride(0), sep.weight, sep.bias, n1.gamma, n1.beta, c1.pc.dgrad, c1.pc.Kp_d, n2.gamma, n2.beta, utt,
+                                  rc.rowmask, h2, dy, dh2, C, dh1, dg2, db2, dg1, db1, ptl, R, C, dds.kernel_size ** i, LN_EPS, float(p),
+                                  int(seed + i), ops.seed_word(dev) if p > 0 else None, _st(dev))
+            if ptl is not None:                                                   # rows [0, n) = LN2's partials, [n, 2n) = LN1's
+                q.add_ln(ptl[:n_lp // 2], dg2, db2)
+                q.add_ln(ptl[n_lp // 2:], dg1, db1)
+            grads[n2.gamma], grads[n2.beta] = dg2, db2
+            grads[n1.gamma], grads[n1.beta] = dg1, db1
+            grads.update(conv_param_grads(c1, a1[:, :C], dh2, R))
+            dw, db = grad_accumulator(sep.weight), grad_accumulator(sep.bias)
+            dx = torch.empty(R, C, dtype=torch.float32, device=dev)
+            call.gt_dds_dw_bwd(x, x.stride(0), dh1, dy, sep.weight, utt, rc.rowmask, dx, dw, db, pt2 := part(4 * C), R, C, dds.kernel_size ** i,
+                               _st(dev))
+            if pt2 is not None:
+                q.add_ln(pt2, dw, db)
+            grads[sep.weight], grads[sep.bias] = dw, db
+            dy = dx
+            continue
         dh2 = torch.empty(R, 3 * C, dtype=torch.bfloat16, device=dev)             # bf16x3
         pt = part(2 * C)
         call.gt_dds_out_bwd(h2, dy, n2.gamma, n2.beta, rc.rowmask, dh2, dg2, db2, pt, R, C, LN_EPS, float(p), int(seed + i),

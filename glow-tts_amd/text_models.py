@@ -498,6 +498,17 @@ class FlowGenerator(nn.Module):
         self.noise_key = noise_key
         return self.synthesis_front
 
+    def set_fused_predictors(self, on=True):
+        """Opt-in: every DilatedDepthSeparableConv of the model (the stochastic predictors' condition encoders and ConvFlows, training
+        and sampling direction) runs ONE kernel per layer and direction (DilatedDepthSeparableConv.set_fused, csrc/dds_layer.hip,
+        DESIGN.md 4.6.1) instead of three forward / four backward launches.  Off is the default (process-level GT_DDS_FUSED).  Returns
+        the number of modules switched."""
+        from .predictors import DilatedDepthSeparableConv
+        mods = [m for m in self.modules() if isinstance(m, DilatedDepthSeparableConv)]
+        for m in mods:
+            m.set_fused(on)
+        return len(mods)
+
     def store_inverse(self, fused_reverse=None, device_front=None):
         """models.py:1255-1256: freeze the model for synthesis (weights packed once, flow scalars cached).  fused_reverse = True / False:
         the decoder's reverse passes (infer, the second half of voice_conversion) run one kernel between consecutive WaveNets

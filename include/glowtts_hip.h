@@ -734,6 +734,39 @@ int gt_dds_sep_bwd(const float* x, int ldx, const float* w, const float* b, cons
 int gt_dds_dw_bwd(const float* x, int ldx, const float* dh1, const float* dy, const float* w, const int32_t* utt,
                   const float* rowmask, float* dx, float* dw, float* db, float* partials, int R, int C, int dilation, void* stream);
 
+/* The same layer as ONE launch per direction (csrc/dds_layer.hip): a workgroup owns gt_dds_layer_tile_rows() (64)
+ * consecutive rows, keeps a1 / d h2 in LDS as a bf16 hi / lo pair and runs the split 1x1 product on the MFMA units itself.  Same
+ * arithmetic as the five kernels above (fp32 row work, bf16x3 product with fp32 accumulation, the same dropout hash of
+ * (seed ^ *seed_dev, row, channel)); only the summation order of the 1x1 product differs.  Each direction pairs with the other path's.
+ *   gt_dds_layer_fwd:  x -> a1 (bf16x3 rows [R, lda >= 3C] = [hi | hi | lo], saved), h2 (fp32 [R, C], saved, = gt_conv_gemm_bf16's
+ *                      output incl. bias), out = (x + dropout(gelu(LayerNorm2(h2)))) * mask (fp32 [R, C]) and, unless NULL,
+ *                      out_split3 = gt_rows_split3(out) (bf16x3 rows [R, ldo3 >= 3C]).  Masked rows: a1 = out = 0, h2 = b1x1.
+ *                      w1x1_split: the forward image of gt_pack_conv_weights flag 8 (row-major [>= C][Kp], Kp >= 3C).
+ *   gt_dds_layer_bwd:  dy -> d h2 (its bf16 hi part, rows [R, lddh >= C]: the operand of the deferred weight / bias gradient),
+ *                      d h1 (fp32 [R, C]: gt_dds_dw_bwd's input), d gamma2 / d beta2 / d gamma1 / d beta1.  h1 is recomputed from x.
+ *                      w1x1_dgrad_split: the data-gradient image of flag 8 ([>= C][Kp], Kp >= 3C).
+ *                      Parameter gradients: one atomic per address and workgroup, or with `partials` (then the four gradient
+ *                      pointers may be NULL) plain stores into partials [gt_dds_layer_partial_rows(R)][2C]: with
+ *                      n = gt_dds_layer_partial_rows(R) / 2 workgroups, row w < n is workgroup w's [d gamma2 | d beta2] and row
+ *                      n + w its [d gamma1 | d beta1] — two buffers of the form gt_param_partials_reduce takes, back to back.
+ *   gt_dds_dw_bwd follows gt_dds_layer_bwd unchanged (dx[m] needs d h1[m +- d] across tiles).
+ * Refusals, before any launch and in this order: a NULL required pointer GT_E_INVAL; C != 192, dilation not a power of 3
+ * (1, 3, 9, ...; <= 0 included) or R <= 0 GT_E_UNSUPPORTED; drop_p outside [0, 1) GT_E_INVAL; ldx < C, lda < 3C, ldo3 < 3C with
+ * out_split3, lddh < C, Kp < 3C, Kp % 8 != 0 or an image that is not 16-byte aligned GT_E_ALIGN.
+ * gt_dds_layer_partial_rows(R) = 2 ceil(R / 64), 0 for R <= 0. */
+int gt_dds_layer_tile_rows(void);
+int gt_dds_layer_partial_rows(int R);
+int gt_dds_layer_fwd(const float* x, int ldx, const float* w_sep, const float* b_sep, const float* gamma1, const float* beta1,
+                     const void* w1x1_split, int Kp, const float* b1x1, const float* gamma2, const float* beta2,
+                     const int32_t* utt, const float* rowmask, void* a1_bf16, int lda, float* h2, float* out,
+                     void* out_split3, int ldo3, int R, int C, int dilation, float eps, float drop_p, uint32_t seed,
+                     const uint32_t* seed_dev, void* stream);
+int gt_dds_layer_bwd(const float* x, int ldx, const float* w_sep, const float* b_sep, const float* gamma1, const float* beta1,
+                     const void* w1x1_dgrad_split, int Kp, const float* gamma2, const float* beta2,
+                     const int32_t* utt, const float* rowmask, const float* h2, const float* dy, void* dh2_bf16, int lddh,
+                     float* dh1, float* dgamma2, float* dbeta2, float* dgamma1, float* dbeta1, float* partials,
+                     int R, int C, int dilation, float eps, float drop_p, uint32_t seed, const uint32_t* seed_dev, void* stream);
+
 /* ConvFlow (modules.py:792-819), in_channels = 2, on z rows [R, 2]:
  *   gt_convflow_pre_fwd:    x0 = (w_pre * z[:,0] + b_pre + g1 (+ g2)) * mask          (pre + DDSConv's `x = x + g`)
  *   gt_convflow_pre_bwd:    dx0 -> d w_pre, d b_pre, dz[:,0] += sum_c dx0 w_pre, dg += dx0      (dz / dg may be NULL)
