@@ -402,13 +402,16 @@ def dds_conv(P, pre, x, x_mask, g=None, kernel_size=3, num_layers=3, drop=None):
     return x * x_mask
 
 
-def rq_spline_fwd(inputs, uw, uh, ud, tail_bound=5.0, min_bin=1e-3, min_der=1e-3):
+def rq_spline_fwd(inputs, uw, uh, ud, tail_bound=5.0, min_bin=1e-3, min_der=1e-3, end_ud=None, bin_idx=None):
     """transforms.piecewise_rational_quadratic_transform(inverse=False, tails="linear") (transforms.py:12-202): inputs [...],
     uw / uh [..., K], ud [..., K-1] -> (outputs, logabsdet).  Restated without boolean-mask scatter: the spline is
-    evaluated everywhere on clamped inputs and the linear tails are selected afterwards (same values inside and outside)."""
+    evaluated everywhere on clamped inputs and the linear tails are selected afterwards (same values inside and outside).
+    end_ud: the raw derivative parameter of the two end knots; None is the reference's constant, which pins their derivative to 1
+    (anything else is a planted defect of oracle/spline64.py).  bin_idx [...]: evaluate with that bin's piece instead of the searched
+    one (oracle/spline64.py: at a knot the neighbouring piece is as good an answer)."""
     K = uw.shape[-1]
     inside = (inputs >= -tail_bound) & (inputs <= tail_bound)
-    const = math.log(math.exp(1 - min_der) - 1)
+    const = math.log(math.exp(1 - min_der) - 1) if end_ud is None else end_ud
     ud = F.pad(ud, (1, 1), value=const)
     left = bottom = -tail_bound
     right = top = tail_bound
@@ -424,6 +427,8 @@ def rq_spline_fwd(inputs, uw, uh, ud, tail_bound=5.0, min_bin=1e-3, min_der=1e-3
     heights = cumh[..., 1:] - cumh[..., :-1]
     loc = cumw.detach().clone(); loc[..., -1] += 1e-6                          # transforms.searchsorted (:46-48)
     idx = (torch.sum(x[..., None] >= loc, -1) - 1).clamp(0, K - 1)[..., None]
+    if bin_idx is not None:
+        idx = bin_idx.clamp(0, K - 1)[..., None]
     in_cw, in_w = cumw.gather(-1, idx)[..., 0], widths.gather(-1, idx)[..., 0]
     in_ch, in_h = cumh.gather(-1, idx)[..., 0], heights.gather(-1, idx)[..., 0]
     delta = (heights / widths).gather(-1, idx)[..., 0]

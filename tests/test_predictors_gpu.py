@@ -5,7 +5,13 @@ pinned to the reference's own modules by tests/golden/float_golden/: dds_*, sp_*
 
 Tolerances: the 192x192 1x1 convs run in bf16 with fp32 accumulation, everything else (depthwise convs, LayerNorms, GELU,
 the 29-row proj, the spline, the likelihood sums) in fp32: activations 2e-2 of max-abs, nll 1e-2 relative, parameter
-gradients 8e-2 of max-abs (bf16 operands of the weight-gradient GEMMs)."""
+gradients 8e-2 of max-abs (bf16 operands of the weight-gradient GEMMs).
+
+What these inputs do NOT reach: tests/golden/fill.py gives a ConvFlow's proj.weight entries of about 0.7 / sqrt(192), so the raw widths
+and heights that reach the spline here are about +-0.05 after the 1 / sqrt(C) scale: the ten bins stay within a few percent of uniform
+and the knots sit near -5, -4, ..., 5.  Wide parameters (narrow bins, steep slopes, the softplus switch), the bin search at the edges,
+flip = 0, the accumulate-into destinations and the launch shapes of the spline and likelihood row kernels are covered at kernel level,
+against float64, by tests/test_predictor_rows_fp64_gpu.py (oracle/spline64.py)."""
 import os
 import sys
 
