@@ -228,7 +228,7 @@ class _MHARunner:
         rc = RowsCtx(_mask_lengths(self.x_mask), T)
         xb = rc.to_rows(x.detach() * self.x_mask, torch.bfloat16)
         y, saved = encoder_impl.mha_fwd(rc, self.att, xb, self.att.p_dropout if self.train else 0.0, self.seed,
-                                        keep_p=True if getattr(self.att, "keep_p", True) else "stats")
+                                        keep_p=encoder_impl.save_mode(self.att))
         P = saved[5]
         return (rc.from_rows(y, torch.float32), None if isinstance(P, encoder_impl.AttnStats) else P), (rc, saved)
 
@@ -309,7 +309,7 @@ class _EncoderRunner:
             if i == self.enc.COND_LAYER and vec is not None:
                 xr, xb = ops.rows_add_cond(rc, xr, None, vec)
             xr, xb, s = encoder_impl.layer_fwd(rc, self.enc, i, xr, xb, self.train, self.seed + 8 * i,
-                                               keep_p=True if getattr(getattr(self.enc, "rows_cfg", None), "attn_keep_p", True) else "stats")
+                                               keep_p=encoder_impl.save_mode(self.enc))
             saved.append(s)
         return (rc.from_rows(xr),), (rc, saved)
 

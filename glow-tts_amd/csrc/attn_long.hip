@@ -898,89 +898,45 @@ __global__ __launch_bounds__(256, 1) void gt_attn_long_bwd_kv_stats_kernel(
 }  // namespace
 
 // The shapes the key-tiled kernels take, in both directions: past the last T at which the generic backward's LDS holds an
-// utterance-head (505), up to the token limit of gt_mas_long_f32.
-extern "C" int gt_attn_long_shape(int T, int Dh, int win) { return Dh == D && win == WIN && T > 505 && T <= GT_ATTN_LONG_MAX_T; }
+// utterance-head, up to the token limit of gt_mas_long_f32 (gt_attn_route).
+extern "C" int gt_attn_long_shape(int T, int Dh, int win) { return gt_attn_route(T, Dh, win) == GT_ATTN_LONG_P; }
 
-// returns 1 if the shape is not handled here (caller falls back to the generic kernel)
-int gt_attn_fwd_long_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
-                          const int32_t* lens, void* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win,
-                          uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
+// The three forwards differ in what pass 2 leaves behind: P (LONG_P), nothing (LONG_NOP), the row statistics (LONG_STATS).
+int gt_attn_fwd_long_impl(const gt_attn_call& c, gt_attn_path path)
 {
-  if (!gt_attn_long_shape(T, Dh, win) || (ld & 7) || (ldo & 3)) return 1;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return 1;
-  hipLaunchKernelGGL(P ? gt_attn_long_fwd_kernel<true> : gt_attn_long_fwd_kernel<false>, dim3((T + 127) / 128, H, B), dim3(256), 0,
-                     static_cast<hipStream_t>(stream),
-                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
-                     static_cast<bf16_t*>(out), ldo, P, T, Tp, row0, H, th, sd, sc, seed_dev);
-  return gt_launch_status(__func__);
-}
-
-int gt_attn_bwd_long_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
-                          const int32_t* lens, const void* dout, int lddo, const float* P, void* ws, size_t ws_bytes,
-                          void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
-                          int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
-{
-  if (!gt_attn_long_shape(T, Dh, win) || (ld & 7) || (lddo & 7) || (lddq & 3)) return 1;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)ws) & 15) return 1;
-  if (ws_bytes < gt_attn_bwd_mfma_ws_bytes(B, T, H)) return 1;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int TI = ((T + 31) / 32) * 32;
-  bf16_t* dST = static_cast<bf16_t*>(ws);                        // the MFMA family's workspace format (launch_bwd of attn_mfma.hip)
-  bf16_t* PdT = dST + (size_t)B * H * T * TI;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_long_bwd_q_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BWD_Q) != hipSuccess)
-      return GT_E_LAUNCH;
-    attr = true;
+  const dim3 grid((c.T + 127) / 128, c.H, c.B);
+  if (path == GT_ATTN_LONG_STATS) {
+    hipLaunchKernelGGL(gt_attn_long_fwd_stats_kernel, grid, dim3(256), 0, c.stream,
+                       c.q, c.k, c.v, c.ld, c.Ek, c.Ev, c.lens, c.out, c.ldo, c.stats, c.T, c.Tp, c.row0, c.H, c.th, c.sd, c.sc, c.seed_dev);
+    return gt_launch_status("gt_attn_fwd_long_stats_impl");
   }
-  hipLaunchKernelGGL(gt_attn_long_bwd_q_kernel, dim3((T + 127) / 128, H, B), dim3(256), LDS_BWD_Q, st,
-                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
-                     static_cast<const bf16_t*>(dout), lddo, P, dST, PdT, TI, static_cast<bf16_t*>(dq), lddq, dEk, dEv,
-                     T, Tp, row0, H, th, sd, sc, seed_dev);
-  hipLaunchKernelGGL(gt_attn_long_bwd_kv_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, st,
-                     static_cast<const bf16_t*>(q), ld, static_cast<const bf16_t*>(dout), lddo, dST, PdT, TI,
-                     static_cast<bf16_t*>(dk), static_cast<bf16_t*>(dv), lddq, T, Tp, row0, H);
+  hipLaunchKernelGGL(path == GT_ATTN_LONG_P ? gt_attn_long_fwd_kernel<true> : gt_attn_long_fwd_kernel<false>, grid, dim3(256), 0, c.stream,
+                     c.q, c.k, c.v, c.ld, c.Ek, c.Ev, c.lens, c.out, c.ldo, c.P, c.T, c.Tp, c.row0, c.H, c.th, c.sd, c.sc, c.seed_dev);
   return gt_launch_status(__func__);
 }
 
-// The P-free pair (gt_attn_fwd_stats / gt_attn_bwd_stats): the caller has checked the shape; 1 = strides / operand alignment
-// the kernels do not take.
 size_t gt_attn_long_stats_ws_bytes(int B, int T, int H) { return (size_t)B * H * T * WSQ * sizeof(float); }
 
-int gt_attn_fwd_long_stats_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
-                                const int32_t* lens, void* out, int ldo, float* stats, int B, int T, int Tp, const int32_t* row0, int H,
-                                uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
+int gt_attn_bwd_long_impl(const gt_attn_call& c, gt_attn_path path)
 {
-  if ((ld & 7) || (ldo & 3)) return 1;
-  if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || ((uintptr_t)stats & 7)) return 1;
-  hipLaunchKernelGGL(gt_attn_long_fwd_stats_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
-                     static_cast<bf16_t*>(out), ldo, stats, T, Tp, row0, H, th, sd, sc, seed_dev);
-  return gt_launch_status(__func__);
-}
-
-int gt_attn_bwd_long_stats_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
-                                const int32_t* lens, const void* dout, int lddo, const float* stats, void* ws,
-                                void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
-                                int B, int T, int Tp, const int32_t* row0, int H, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
-{
-  if ((ld & 7) || (lddo & 7) || (lddq & 3)) return 1;
-  if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)ws) & 15) || ((uintptr_t)stats & 7)) return 1;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_long_bwd_q_stats_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BWD_QS) != hipSuccess)
-      return GT_E_LAUNCH;
-    attr = true;
+  const dim3 grid((c.T + 127) / 128, c.H, c.B);
+  if (path == GT_ATTN_LONG_STATS) {
+    if (const int rc = gt_allow_lds<&gt_attn_long_bwd_q_stats_kernel>((int)LDS_BWD_QS)) return rc;
+    float* wsq = static_cast<float*>(c.ws);
+    hipLaunchKernelGGL(gt_attn_long_bwd_q_stats_kernel, grid, dim3(256), LDS_BWD_QS, c.stream,
+                       c.q, c.k, c.v, c.ld, c.Ek, c.Ev, c.lens, c.dout, c.lddo, c.stats, wsq, c.dq, c.lddq, c.dEk, c.dEv,
+                       c.T, c.Tp, c.row0, c.H, c.th, c.sd, c.sc, c.seed_dev);
+    hipLaunchKernelGGL(gt_attn_long_bwd_kv_stats_kernel, grid, dim3(256), 0, c.stream,
+                       c.q, c.k, c.v, c.ld, c.lens, c.dout, c.lddo, c.stats, wsq, c.dk, c.dv, c.lddq, c.T, c.Tp, c.row0, c.H,
+                       c.th, c.sd, c.sc, c.seed_dev);
+    return gt_launch_status("gt_attn_bwd_long_stats_impl");
   }
-  float* wsq = static_cast<float*>(ws);
-  hipLaunchKernelGGL(gt_attn_long_bwd_q_stats_kernel, dim3((T + 127) / 128, H, B), dim3(256), LDS_BWD_QS, st,
-                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
-                     static_cast<const bf16_t*>(dout), lddo, stats, wsq, static_cast<bf16_t*>(dq), lddq, dEk, dEv,
-                     T, Tp, row0, H, th, sd, sc, seed_dev);
-  hipLaunchKernelGGL(gt_attn_long_bwd_kv_stats_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, st,
-                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, lens,
-                     static_cast<const bf16_t*>(dout), lddo, stats, wsq,
-                     static_cast<bf16_t*>(dk), static_cast<bf16_t*>(dv), lddq, T, Tp, row0, H, th, sd, sc, seed_dev);
+  const gt_attn_bwd_ws w(c);                                     // the MFMA family's workspace format
+  if (const int rc = gt_allow_lds<&gt_attn_long_bwd_q_kernel>((int)LDS_BWD_Q)) return rc;
+  hipLaunchKernelGGL(gt_attn_long_bwd_q_kernel, grid, dim3(256), LDS_BWD_Q, c.stream,
+                     c.q, c.k, c.v, c.ld, c.Ek, c.Ev, c.lens, c.dout, c.lddo, c.P, w.dST, w.PdT, w.TI, c.dq, c.lddq, c.dEk, c.dEv,
+                     c.T, c.Tp, c.row0, c.H, c.th, c.sd, c.sc, c.seed_dev);
+  hipLaunchKernelGGL(gt_attn_long_bwd_kv_kernel, grid, dim3(256), 0, c.stream,
+                     c.q, c.ld, c.dout, c.lddo, w.dST, w.PdT, w.TI, c.dk, c.dv, c.lddq, c.T, c.Tp, c.row0, c.H);
   return gt_launch_status(__func__);
 }

@@ -218,19 +218,13 @@ __global__ __launch_bounds__(256, 1) void gt_attn_fwd_mfma_kernel(
 }
 
 template <int NT>
-int launch_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const float* Ek, const float* Ev, const int32_t* lens,
-               bf16_t* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, hipStream_t st)
+int launch_fwd(const gt_attn_call& c)
 {
   constexpr int TPAD = NT * 32;
   const size_t lds = (size_t)TPAD * KP * 2 + (size_t)TPAD * VP * 2 + 32 * KP * 2 + D * 16 * 2 + 4 * 32 * NW * 4 + 4 * 32 * 16 * 2;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_fwd_mfma_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return GT_E_LAUNCH;
-    attr = true;
-  }
-  hipLaunchKernelGGL(gt_attn_fwd_mfma_kernel<NT>, dim3((T + 127) / 128, H, B), dim3(256), lds, st,
-                     q, k, v, ld, Ek, Ev, lens, out, ldo, P, T, Tp, row0, H, th, sd, sc, seed_dev);
+  if (const int rc = gt_allow_lds<&gt_attn_fwd_mfma_kernel<NT>>(160 * 1024)) return rc;
+  hipLaunchKernelGGL(gt_attn_fwd_mfma_kernel<NT>, dim3((c.T + 127) / 128, c.H, c.B), dim3(256), lds, c.stream,
+                     c.q, c.k, c.v, c.ld, c.Ek, c.Ev, c.lens, c.out, c.ldo, c.P, c.T, c.Tp, c.row0, c.H, c.th, c.sd, c.sc, c.seed_dev);
   return gt_launch_status(__func__);
 }
 
@@ -441,19 +435,13 @@ __global__ __launch_bounds__(256, 1) void gt_attn_fwd_mfma_long_kernel(
 }
 
 template <int NT>
-int launch_fwd_long(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const float* Ek, const float* Ev, const int32_t* lens,
-                    bf16_t* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, hipStream_t st)
+int launch_fwd_long(const gt_attn_call& c)
 {
   constexpr int TPAD = NT * 32;
   const size_t lds = (size_t)TPAD * VP * 2 + 32 * KP * 2 + D * 16 * 2 + 4 * 32 * NW * 4 + 4 * 32 * 16 * 2;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_fwd_mfma_long_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return GT_E_LAUNCH;
-    attr = true;
-  }
-  hipLaunchKernelGGL(gt_attn_fwd_mfma_long_kernel<NT>, dim3((T + 127) / 128, H, B), dim3(256), lds, st,
-                     q, k, v, ld, Ek, Ev, lens, out, ldo, P, T, Tp, row0, H, th, sd, sc, seed_dev);
+  if (const int rc = gt_allow_lds<&gt_attn_fwd_mfma_long_kernel<NT>>(160 * 1024)) return rc;
+  hipLaunchKernelGGL(gt_attn_fwd_mfma_long_kernel<NT>, dim3((c.T + 127) / 128, c.H, c.B), dim3(256), lds, c.stream,
+                     c.q, c.k, c.v, c.ld, c.Ek, c.Ev, c.lens, c.out, c.ldo, c.P, c.T, c.Tp, c.row0, c.H, c.th, c.sd, c.sc, c.seed_dev);
   return gt_launch_status(__func__);
 }
 
@@ -1160,48 +1148,33 @@ __global__ __launch_bounds__(FTH, 1) void gt_attn_bwd_fused_kernel(
   APH(11);
 }
 
-int launch_bwd_fused(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const float* Ek, const float* Ev, const int32_t* lens,
-                     const bf16_t* dout, int lddo, const float* P, bf16_t* ws, bf16_t* dq, bf16_t* dk, bf16_t* dv, int lddq,
-                     float* dEk, float* dEv, int B, int T, int Tp, const int32_t* row0, int H, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, hipStream_t st)
+int launch_bwd_fused(const gt_attn_call& c)        // T <= FTP
 {
-  const int TI = ((T + 31) / 32) * 32;
-  bf16_t* dST = ws;
-  bf16_t* PdT = ws + (size_t)B * H * T * TI;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_bwd_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH;
-    attr = true;
-  }
-  if (T > FTP) return 1;
-  hipLaunchKernelGGL(gt_attn_bwd_fused_kernel, dim3(H, B), dim3(FTH), FUSED_LDS, st,
-                     q, k, v, ld, Ek, Ev, lens, dout, lddo, P, dST, PdT, TI, dq, dk, dv, lddq, dEk, dEv, T, Tp, row0, H, th, sd, sc, seed_dev);
+  const gt_attn_bwd_ws w(c);
+  if (const int rc = gt_allow_lds<&gt_attn_bwd_fused_kernel>(160 * 1024)) return rc;
+  hipLaunchKernelGGL(gt_attn_bwd_fused_kernel, dim3(c.H, c.B), dim3(FTH), FUSED_LDS, c.stream,
+                     c.q, c.k, c.v, c.ld, c.Ek, c.Ev, c.lens, c.dout, c.lddo, c.P, w.dST, w.PdT, w.TI, c.dq, c.dk, c.dv, c.lddq, c.dEk, c.dEv,
+                     c.T, c.Tp, c.row0, c.H, c.th, c.sd, c.sc, c.seed_dev);
   return gt_launch_status(__func__);
 }
 
 template <int NT, int WV>
-int launch_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, const float* Ek, const float* Ev, const int32_t* lens,
-               const bf16_t* dout, int lddo, const float* P, bf16_t* ws, bf16_t* dq, bf16_t* dk, bf16_t* dv, int lddq,
-               float* dEk, float* dEv, int B, int T, int Tp, const int32_t* row0, int H, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, hipStream_t st)
+int launch_bwd(const gt_attn_call& c)
 {
   constexpr int TPAD = NT * 32;
   constexpr int WBN = 32 * 16 + 2 * 16 * BTP + 2 * 32 * VP;
-  const int TI = ((T + 31) / 32) * 32;
-  bf16_t* dST = ws;
-  bf16_t* PdT = ws + (size_t)B * H * T * TI;
-  const size_t lds1 = (NT > 8 ? 0 : (size_t)TPAD * KP * 2) + (size_t)TPAD * VP * 2 + 32 * KP * 2 + D * 16 * 2 + 2 * NW * D * 4 +
-                      (size_t)WV * 32 * NW * 4 + (size_t)WV * WBN * 2;
-  const size_t lds2 = (size_t)2 * TPAD * VP * 2;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_bwd_q_mfma_kernel<NT, WV>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_bwd_kv_mfma_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH;
-    attr = true;
-  }
-  if (lds1 > 160 * 1024 || lds2 > 160 * 1024) return 1;
-  hipLaunchKernelGGL((gt_attn_bwd_q_mfma_kernel<NT, WV>), dim3((T + 32 * WV - 1) / (32 * WV), H, B), dim3(64 * WV), lds1, st,
-                     q, k, v, ld, Ek, Ev, lens, dout, lddo, P, dST, PdT, TI, dq, lddq, dEk, dEv, T, Tp, row0, H, th, sd, sc, seed_dev);
-  hipLaunchKernelGGL(gt_attn_bwd_kv_mfma_kernel<NT>, dim3((T + 127) / 128, H, B), dim3(256), lds2, st,
-                     q, ld, dout, lddo, dST, PdT, TI, dk, dv, lddq, T, Tp, row0, H);
+  constexpr size_t lds1 = (NT > 8 ? 0 : (size_t)TPAD * KP * 2) + (size_t)TPAD * VP * 2 + 32 * KP * 2 + D * 16 * 2 + 2 * NW * D * 4 +
+                          (size_t)WV * 32 * NW * 4 + (size_t)WV * WBN * 2;
+  constexpr size_t lds2 = (size_t)2 * TPAD * VP * 2;
+  static_assert(lds1 <= 160 * 1024 && lds2 <= 160 * 1024, "LDS budget");
+  const gt_attn_bwd_ws w(c);
+  if (const int rc = gt_allow_lds<&gt_attn_bwd_q_mfma_kernel<NT, WV>>(160 * 1024)) return rc;
+  if (const int rc = gt_allow_lds<&gt_attn_bwd_kv_mfma_kernel<NT>>(160 * 1024)) return rc;
+  hipLaunchKernelGGL((gt_attn_bwd_q_mfma_kernel<NT, WV>), dim3((c.T + 32 * WV - 1) / (32 * WV), c.H, c.B), dim3(64 * WV), lds1, c.stream,
+                     c.q, c.k, c.v, c.ld, c.Ek, c.Ev, c.lens, c.dout, c.lddo, c.P, w.dST, w.PdT, w.TI, c.dq, c.lddq, c.dEk, c.dEv,
+                     c.T, c.Tp, c.row0, c.H, c.th, c.sd, c.sc, c.seed_dev);
+  hipLaunchKernelGGL(gt_attn_bwd_kv_mfma_kernel<NT>, dim3((c.T + 127) / 128, c.H, c.B), dim3(256), lds2, c.stream,
+                     c.q, c.ld, c.dout, c.lddo, w.dST, w.PdT, w.TI, c.dk, c.dv, c.lddq, c.T, c.Tp, c.row0, c.H);
   return gt_launch_status(__func__);
 }
 
@@ -1220,43 +1193,41 @@ size_t gt_attn_bwd_mfma_ws_bytes(int B, int T, int H)
   return (size_t)2 * B * H * T * TI * 2;
 }
 
-// The shapes the MFMA kernels take, in both directions (the generic kernels of encoder_ops.hip take the rest): the one predicate both
-// dispatchers below use, exported so that a caller can tell which kernels a launch runs.
-extern "C" int gt_attn_mfma_shape(int T, int Dh, int win) { return Dh == D && win == WIN && T <= 384; }
-
-int gt_attn_bwd_mfma_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
-                          const int32_t* lens, const void* dout, int lddo, const float* P, void* ws, size_t ws_bytes,
-                          void* dq, void* dk, void* dv, int lddq, float* dEk, float* dEv,
-                          int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win, uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
+// Which kernels a shape runs on: the one place where T is compared with the thresholds between the paths (internal.h names them).
+// 160, 256, 384: what 5, 8, 12 key tiles of 32 hold; 505: the last T at which the generic backward's LDS holds an utterance-head.
+gt_attn_path gt_attn_route(int T, int Dh, int win)
 {
-  if (!gt_attn_mfma_shape(T, Dh, win) || (ld & 7) || (lddo & 7) || (lddq & 3)) return 1;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)ws) & 15) return 1;
-  if (ws_bytes < gt_attn_bwd_mfma_ws_bytes(B, T, H)) return 1;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bf16_t* qq = static_cast<const bf16_t*>(q); const bf16_t* kk = static_cast<const bf16_t*>(k); const bf16_t* vv = static_cast<const bf16_t*>(v);
-  const bf16_t* dd = static_cast<const bf16_t*>(dout);
-  bf16_t* w16 = static_cast<bf16_t*>(ws);
-  bf16_t* dqq = static_cast<bf16_t*>(dq); bf16_t* dkk = static_cast<bf16_t*>(dk); bf16_t* dvv = static_cast<bf16_t*>(dv);
-  // T <= 160: the whole backward of one (utterance, head) in one workgroup (gt_attn_bwd_fused_kernel)
-  if (T <= 160) return launch_bwd_fused(qq, kk, vv, ld, Ek, Ev, lens, dd, lddo, P, w16, dqq, dkk, dvv, lddq, dEk, dEv, B, T, Tp, row0, H, th, sd, sc, seed_dev, st);
-  // 161 <= T <= 256: 8 key tiles, 2 waves per workgroup (153 KB of LDS), one score tile live at a time (recompute form:
-  // the first version kept all 8 tiles in registers, needed scratch and faulted — see DESIGN.md §4.5)
-  if (T <= 256) return launch_bwd<8, 2>(qq, kk, vv, ld, Ek, Ev, lens, dd, lddo, P, w16, dqq, dkk, dvv, lddq, dEk, dEv, B, T, Tp, row0, H, th, sd, sc, seed_dev, st);
-  // 257 <= T <= 384 (cfg3): 12 key tiles; K^T (transposing reads) stays in LDS, the V rows come from L2
-  return launch_bwd<12, 4>(qq, kk, vv, ld, Ek, Ev, lens, dd, lddo, P, w16, dqq, dkk, dvv, lddq, dEk, dEv, B, T, Tp, row0, H, th, sd, sc, seed_dev, st);
+  static_assert(FTP == 160, "FUSED160 is what the one-workgroup backward holds: launch_bwd_fused checks no T of its own");
+  if (T > GT_ATTN_LONG_MAX_T) return GT_ATTN_NONE;
+  if (Dh != D || win != WIN) return GT_ATTN_GENERIC;
+  if (T <= 160) return GT_ATTN_FUSED160;
+  if (T <= 256) return GT_ATTN_MFMA256;
+  if (T <= 384) return GT_ATTN_MFMA384;
+  return T <= 505 ? GT_ATTN_GENERIC : GT_ATTN_LONG_P;
 }
 
-// returns 1 if the shape is not handled here (caller falls back to the generic kernel)
-int gt_attn_fwd_mfma_impl(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
-                          const int32_t* lens, void* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, int Dh, int win,
-                          uint32_t th, uint32_t sd, float sc, const uint32_t* seed_dev, void* stream)
+// The shapes the MFMA kernels take, in both directions (the generic kernels of encoder_ops.hip take the rest), exported so that a
+// caller can tell which kernels a launch runs.
+extern "C" int gt_attn_mfma_shape(int T, int Dh, int win)
 {
-  if (!gt_attn_mfma_shape(T, Dh, win) || (ld & 7) || (ldo & 3)) return 1;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return 1;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bf16_t* qq = static_cast<const bf16_t*>(q); const bf16_t* kk = static_cast<const bf16_t*>(k); const bf16_t* vv = static_cast<const bf16_t*>(v);
-  bf16_t* oo = static_cast<bf16_t*>(out);
-  if (T <= 160) return launch_fwd<5>(qq, kk, vv, ld, Ek, Ev, lens, oo, ldo, P, B, T, Tp, row0, H, th, sd, sc, seed_dev, st);
-  if (T <= 256) return launch_fwd<8>(qq, kk, vv, ld, Ek, Ev, lens, oo, ldo, P, B, T, Tp, row0, H, th, sd, sc, seed_dev, st);
-  return launch_fwd_long<12>(qq, kk, vv, ld, Ek, Ev, lens, oo, ldo, P, B, T, Tp, row0, H, th, sd, sc, seed_dev, st);
+  const gt_attn_path p = gt_attn_route(T, Dh, win);
+  return p == GT_ATTN_FUSED160 || p == GT_ATTN_MFMA256 || p == GT_ATTN_MFMA384;
+}
+
+int gt_attn_bwd_mfma_impl(const gt_attn_call& c, gt_attn_path path)
+{
+  // T <= 160: the whole backward of one (utterance, head) in one workgroup (gt_attn_bwd_fused_kernel)
+  if (path == GT_ATTN_FUSED160) return launch_bwd_fused(c);
+  // 161 <= T <= 256: 8 key tiles, 2 waves per workgroup (153 KB of LDS), one score tile live at a time (recompute form:
+  // the first version kept all 8 tiles in registers, needed scratch and faulted — see DESIGN.md §4.5)
+  if (path == GT_ATTN_MFMA256) return launch_bwd<8, 2>(c);
+  // 257 <= T <= 384 (cfg3): 12 key tiles; K^T (transposing reads) stays in LDS, the V rows come from L2
+  return launch_bwd<12, 4>(c);
+}
+
+int gt_attn_fwd_mfma_impl(const gt_attn_call& c, gt_attn_path path)
+{
+  if (path == GT_ATTN_FUSED160) return launch_fwd<5>(c);
+  if (path == GT_ATTN_MFMA256) return launch_fwd<8>(c);
+  return launch_fwd_long<12>(c);
 }

@@ -14,6 +14,7 @@
 // maps dW to (dv, dg) or to a plain dw in the parameter's own [Cout, Cin, taps] layout.
 #include <stdlib.h>
 #include "common.h"
+#include "internal.h"
 #include "mfma_frag.h"
 #include "../../include/glowtts_hip.h"
 
@@ -286,13 +287,8 @@ __global__ __launch_bounds__(256, 2) void gt_conv_wgrad_batched_kernel(
 
 template <int TAPS> static int wgrad_lds_attr()
 {
-  static int done = 0;                          // > 64 KiB of dynamic LDS needs the attribute once per kernel (outside graph capture:
-  if (!done) {                                  //  run one eager step first)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_conv_wgrad_kernel<TAPS>), hipFuncAttributeMaxDynamicSharedMemorySize, WgGeoT<TAPS>::LDS) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_conv_wgrad_batched_kernel<TAPS>), hipFuncAttributeMaxDynamicSharedMemorySize, WgGeoT<TAPS>::LDS) != hipSuccess)
-      return GT_E_LAUNCH;
-    done = 1;
-  }
+  // > 64 KiB of dynamic LDS needs the attribute once per kernel (outside graph capture: run one eager step first)
+  if (gt_allow_lds<&gt_conv_wgrad_kernel<TAPS>>(WgGeoT<TAPS>::LDS) || gt_allow_lds<&gt_conv_wgrad_batched_kernel<TAPS>>(WgGeoT<TAPS>::LDS)) return GT_E_LAUNCH;
   return 0;
 }
 

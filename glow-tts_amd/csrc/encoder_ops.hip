@@ -947,35 +947,52 @@ static size_t attn_lds(int T, int D, int win, size_t extra_floats)
   return halfs * 2 + (size_t)2 * (2 * win + 1) * D * 4 + extra_floats * 4;
 }
 
+// What the four attention entries share of a gt_attn_call; each adds its own direction's fields.  After the entry's checks: p < 1.
+static gt_attn_call attn_call(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev, const int32_t* lens,
+                              int B, int T, int Tp, const int32_t* row0, int H, int D, int win, float drop_p, uint32_t drop_seed,
+                              const uint32_t* seed_dev, void* stream)
+{
+  gt_attn_call c = {};
+  c.q = gt_bf16(q); c.k = gt_bf16(k); c.v = gt_bf16(v); c.ld = ld; c.Ek = Ek; c.Ev = Ev; c.lens = lens;
+  c.B = B; c.T = T; c.Tp = Tp; c.row0 = row0; c.H = H; c.D = D; c.win = win;
+  gt_drop_params(drop_p, &c.th, &c.sc);
+  c.sd = drop_seed; c.seed_dev = seed_dev; c.stream = GT_ST(stream);
+  return c;
+}
+
 extern "C" int gt_attn_fwd(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
                            const int32_t* lens, void* out, int ldo, float* P, int B, int T, int Tp, const int32_t* row0, int H, int D, int win,
                            float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream)
 {
   if (!q || !k || !v || !Ek || !Ev || !lens || !out || B <= 0 || T <= 0 || H <= 0) return GT_E_INVAL;
-  if (D > AT_MAXD || (D & 1) || win < 0 || drop_p >= 1.f || T > GT_ATTN_LONG_MAX_T) return GT_E_UNSUPPORTED;
-  uint32_t th; float sc;
-  gt_drop_params(drop_p, &th, &sc);
+  const gt_attn_path path = gt_attn_route(T, D, win);
+  if (D > AT_MAXD || (D & 1) || win < 0 || drop_p >= 1.f || path == GT_ATTN_NONE) return GT_E_UNSUPPORTED;
+  gt_attn_call c = attn_call(q, k, v, ld, Ek, Ev, lens, B, T, Tp, row0, H, D, win, drop_p, drop_seed, seed_dev, stream);
+  c.out = gt_bf16(out); c.ldo = ldo; c.P = P;
+  const bool mfma_layout = gt_attn_mfma_layout(c);
   if (!P) {                                        // a forward that stores no P: the key-tiled kernel, and nothing else
-    if (!gt_attn_long_shape(T, D, win)) return GT_E_INVAL;
-    const int rc = gt_attn_fwd_long_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, P, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
-    return rc == 1 ? GT_E_ALIGN : rc;              // 1: strides / operand alignment it does not take
+    if (path != GT_ATTN_LONG_P) return GT_E_INVAL;
+    return mfma_layout ? gt_attn_fwd_long_impl(c, GT_ATTN_LONG_NOP) : GT_E_ALIGN;
   }
-  {
-    int rc = gt_attn_fwd_mfma_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, P, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
-    if (rc != 1) return rc;                        // handled (or failed loudly) on the MFMA path
-    rc = gt_attn_fwd_long_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, P, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
-    if (rc != 1) return rc;                        // ... or on the key-tiled one (505 < T)
+  switch (path) {
+    case GT_ATTN_FUSED160: case GT_ATTN_MFMA256: case GT_ATTN_MFMA384:
+      if (mfma_layout) return gt_attn_fwd_mfma_impl(c, path);
+      break;                                       // a layout the MFMA kernels do not take (row pitch, operand alignment): the generic kernel runs
+    case GT_ATTN_LONG_P:
+      if (mfma_layout) return gt_attn_fwd_long_impl(c, path);
+      break;                                       // likewise; the generic LDS holds a forward to T = 597 (the backward to 505): GT_E_UNSUPPORTED past it
+    default: break;
   }
   const size_t lds = attn_lds(T, D, win, (size_t)4 * D + (size_t)AT_QT * T);
   if (lds > 160 * 1024) return GT_E_UNSUPPORTED;
-  static bool attr = false;
-  if (!attr) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH; attr = true; }
-  hipLaunchKernelGGL(gt_attn_fwd_kernel, dim3((T + AT_QT - 1) / AT_QT, H, B), dim3(256), lds, GT_ST(stream),
-                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
-                     static_cast<bf16_t*>(out), ldo, P, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev);
+  if (const int rc = gt_allow_lds<&gt_attn_fwd_kernel>(160 * 1024)) return rc;
+  hipLaunchKernelGGL(gt_attn_fwd_kernel, dim3((T + AT_QT - 1) / AT_QT, H, B), dim3(256), lds, c.stream,
+                     c.q, c.k, c.v, c.ld, c.Ek, c.Ev, c.lens, c.out, c.ldo, c.P, c.T, c.Tp, c.row0, c.H, c.D, c.win, c.th, c.sd, c.sc, c.seed_dev);
   GT_RET();
 }
 
+// Room for either workspace format: the generic kernels' fp32 dS [B, H, T, T] or the MFMA families' bf16 pair (which of the two a
+// call writes depends on D, win and the layout, which this function is not told).
 extern "C" size_t gt_attn_bwd_workspace_bytes(int B, int T, int H)
 {
   if (B <= 0 || T <= 0 || H <= 0) return 0;
@@ -990,37 +1007,36 @@ extern "C" int gt_attn_bwd(const void* q, const void* k, const void* v, int ld, 
                            int B, int T, int Tp, const int32_t* row0, int H, int D, int win, float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream)
 {
   if (!q || !k || !v || !Ek || !Ev || !lens || !dout || !P || !workspace || !dq || !dk || !dv || !dEk || !dEv) return GT_E_INVAL;
-  if (D > AT_MAXD || (D & 1) || win < 0 || drop_p >= 1.f || T > GT_ATTN_LONG_MAX_T) return GT_E_UNSUPPORTED;
+  const gt_attn_path path = gt_attn_route(T, D, win);
+  if (D > AT_MAXD || (D & 1) || win < 0 || drop_p >= 1.f || path == GT_ATTN_NONE) return GT_E_UNSUPPORTED;
   if (workspace_bytes < gt_attn_bwd_workspace_bytes(B, T, H)) return GT_E_INVAL;
-  float* dS_ws = static_cast<float*>(workspace);
-  uint32_t th; float sc;
-  gt_drop_params(drop_p, &th, &sc);
-  {
-    int rc = gt_attn_bwd_mfma_impl(q, k, v, ld, Ek, Ev, lens, dout, lddo, P, workspace, workspace_bytes, dq, dk, dv, lddq,
-                                   dEk, dEv, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
-    if (rc != 1) return rc;
-    rc = gt_attn_bwd_long_impl(q, k, v, ld, Ek, Ev, lens, dout, lddo, P, workspace, workspace_bytes, dq, dk, dv, lddq,
-                               dEk, dEv, B, T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev, stream);
-    if (rc != 1) return rc;
+  gt_attn_call c = attn_call(q, k, v, ld, Ek, Ev, lens, B, T, Tp, row0, H, D, win, drop_p, drop_seed, seed_dev, stream);
+  c.dout = gt_bf16(dout); c.lddo = lddo; c.P = const_cast<float*>(P);      // only read from here on
+  c.ws = workspace; c.ws_bytes = workspace_bytes;
+  c.dq = gt_bf16(dq); c.dk = gt_bf16(dk); c.dv = gt_bf16(dv); c.lddq = lddq; c.dEk = dEk; c.dEv = dEv;
+  const bool mfma_layout = gt_attn_mfma_layout(c) && workspace_bytes >= gt_attn_bwd_mfma_ws_bytes(B, T, H);
+  switch (path) {                                  // the forward's two hand-ons (gt_attn_fwd); a LONG_P call handed on is refused below
+    case GT_ATTN_FUSED160: case GT_ATTN_MFMA256: case GT_ATTN_MFMA384:
+      if (mfma_layout) return gt_attn_bwd_mfma_impl(c, path);
+      break;
+    case GT_ATTN_LONG_P:
+      if (mfma_layout) return gt_attn_bwd_long_impl(c, path);
+      break;
+    default: break;
   }
   const size_t lds1 = attn_lds(T, D, win, (size_t)2 * (2 * win + 1) * D + (size_t)AT_QT * 2 * D + (size_t)AT_QT * T);
   size_t halfs2 = (size_t)T * (D + 2); halfs2 += halfs2 & 1;
   const size_t lds2 = halfs2 * 2 + (size_t)AT_QT * 2 * T * 4;
   if (lds1 > 160 * 1024 || lds2 > 160 * 1024) return GT_E_UNSUPPORTED;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_bwd_q_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_attn_bwd_kv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GT_E_LAUNCH;
-    attr = true;
-  }
+  if (const int rc = gt_allow_lds<&gt_attn_bwd_q_kernel>(160 * 1024)) return rc;
+  if (const int rc = gt_allow_lds<&gt_attn_bwd_kv_kernel>(160 * 1024)) return rc;
+  float* dS_ws = static_cast<float*>(workspace);
   const dim3 grid((T + AT_QT - 1) / AT_QT, H, B);
-  hipLaunchKernelGGL(gt_attn_bwd_q_kernel, grid, dim3(256), lds1, GT_ST(stream),
-                     static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ld, Ek, Ev, lens,
-                     static_cast<const bf16_t*>(dout), lddo, P, dS_ws, static_cast<bf16_t*>(dq), lddq, dEk, dEv,
-                     T, Tp, row0, H, D, win, th, drop_seed, sc, seed_dev);
-  hipLaunchKernelGGL(gt_attn_bwd_kv_kernel, grid, dim3(256), lds2, GT_ST(stream),
-                     static_cast<const bf16_t*>(q), ld, static_cast<const bf16_t*>(dout), lddo, P, dS_ws, lens,
-                     static_cast<bf16_t*>(dk), static_cast<bf16_t*>(dv), lddq, T, Tp, row0, H, D, th, drop_seed, sc, seed_dev);
+  hipLaunchKernelGGL(gt_attn_bwd_q_kernel, grid, dim3(256), lds1, c.stream,
+                     c.q, c.k, c.v, c.ld, c.Ek, c.Ev, c.lens, c.dout, c.lddo, c.P, dS_ws, c.dq, c.lddq, c.dEk, c.dEv,
+                     c.T, c.Tp, c.row0, c.H, c.D, c.win, c.th, c.sd, c.sc, c.seed_dev);
+  hipLaunchKernelGGL(gt_attn_bwd_kv_kernel, grid, dim3(256), lds2, c.stream,
+                     c.q, c.ld, c.dout, c.lddo, c.P, dS_ws, c.lens, c.dk, c.dv, c.lddq, c.T, c.Tp, c.row0, c.H, c.D, c.th, c.sd, c.sc, c.seed_dev);
   GT_RET();
 }
 
@@ -1043,11 +1059,10 @@ extern "C" int gt_attn_fwd_stats(const void* q, const void* k, const void* v, in
                                  int win, float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream)
 {
   if (!q || !k || !v || !Ek || !Ev || !lens || !out || !stats || B <= 0 || T <= 0 || H <= 0) return GT_E_INVAL;
-  if (T > GT_ATTN_LONG_MAX_T || !gt_attn_long_shape(T, D, win) || drop_p >= 1.f) return GT_E_UNSUPPORTED;
-  uint32_t th; float sc;
-  gt_drop_params(drop_p, &th, &sc);
-  const int rc = gt_attn_fwd_long_stats_impl(q, k, v, ld, Ek, Ev, lens, out, ldo, stats, B, T, Tp, row0, H, th, drop_seed, sc, seed_dev, stream);
-  return rc == 1 ? GT_E_ALIGN : rc;
+  if (gt_attn_route(T, D, win) != GT_ATTN_LONG_P || drop_p >= 1.f) return GT_E_UNSUPPORTED;
+  gt_attn_call c = attn_call(q, k, v, ld, Ek, Ev, lens, B, T, Tp, row0, H, D, win, drop_p, drop_seed, seed_dev, stream);
+  c.out = gt_bf16(out); c.ldo = ldo; c.stats = stats;
+  return gt_attn_mfma_layout(c) ? gt_attn_fwd_long_impl(c, GT_ATTN_LONG_STATS) : GT_E_ALIGN;
 }
 
 extern "C" int gt_attn_bwd_stats(const void* q, const void* k, const void* v, int ld, const float* Ek, const float* Ev,
@@ -1058,13 +1073,13 @@ extern "C" int gt_attn_bwd_stats(const void* q, const void* k, const void* v, in
 {
   if (!q || !k || !v || !Ek || !Ev || !lens || !dout || !stats || !workspace || !dq || !dk || !dv || !dEk || !dEv || B <= 0 || T <= 0 || H <= 0)
     return GT_E_INVAL;
-  if (T > GT_ATTN_LONG_MAX_T || !gt_attn_long_shape(T, D, win) || drop_p >= 1.f) return GT_E_UNSUPPORTED;
+  if (gt_attn_route(T, D, win) != GT_ATTN_LONG_P || drop_p >= 1.f) return GT_E_UNSUPPORTED;
   if (workspace_bytes < gt_attn_bwd_stats_workspace_bytes(B, T, H)) return GT_E_INVAL;
-  uint32_t th; float sc;
-  gt_drop_params(drop_p, &th, &sc);
-  const int rc = gt_attn_bwd_long_stats_impl(q, k, v, ld, Ek, Ev, lens, dout, lddo, stats, workspace, dq, dk, dv, lddq, dEk, dEv,
-                                             B, T, Tp, row0, H, th, drop_seed, sc, seed_dev, stream);
-  return rc == 1 ? GT_E_ALIGN : rc;
+  gt_attn_call c = attn_call(q, k, v, ld, Ek, Ev, lens, B, T, Tp, row0, H, D, win, drop_p, drop_seed, seed_dev, stream);
+  c.dout = gt_bf16(dout); c.lddo = lddo; c.stats = const_cast<float*>(stats);   // only read from here on
+  c.ws = workspace; c.ws_bytes = workspace_bytes;
+  c.dq = gt_bf16(dq); c.dk = gt_bf16(dk); c.dv = gt_bf16(dv); c.lddq = lddq; c.dEk = dEk; c.dEv = dEv;
+  return gt_attn_mfma_layout(c) ? gt_attn_bwd_long_impl(c, GT_ATTN_LONG_STATS) : GT_E_ALIGN;
 }
 
 extern "C" int gt_embedding_fwd(const int64_t* ids, const float* emb, const int32_t* lens, float* out_f32, void* out_bf16,

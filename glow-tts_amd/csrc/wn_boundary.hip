@@ -1004,12 +1004,6 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_rev_kernel(gt_boundary_rev
   }
 }
 
-template <typename K>
-int opt_in_lds(K kernel, int bytes)
-{
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? 0 : -1;
-}
-
 }  // namespace
 
 #if WNB_PHASES
@@ -1042,12 +1036,9 @@ extern "C" int gt_wn_boundary_fwd(const gt_boundary_fwd_args* args, void* stream
     if (a.ks_start < HALF / 16) return GT_E_INVAL;
     if (!al16(a.y_next) || !al16(a.y0_bf16) || !al16(a.w_start) || !al16(a.b_start) || !al16(a.h_next)) return GT_E_ALIGN;
   }
-  static bool attr = false;                    // > 64 KB of LDS: opt in once per process
-  if (!attr) {
-    if (opt_in_lds(&gt_wn_boundary_fwd_kernel<true, true>, FWD_LDS) || opt_in_lds(&gt_wn_boundary_fwd_kernel<true, false>, FWD_LDS) ||
-        opt_in_lds(&gt_wn_boundary_fwd_kernel<false, true>, FWD_LDS)) return GT_E_LAUNCH;
-    attr = true;
-  }
+  // > 64 KB of LDS: opt in once per process
+  if (gt_allow_lds<&gt_wn_boundary_fwd_kernel<true, true>>(FWD_LDS) || gt_allow_lds<&gt_wn_boundary_fwd_kernel<true, false>>(FWD_LDS) ||
+      gt_allow_lds<&gt_wn_boundary_fwd_kernel<false, true>>(FWD_LDS)) return GT_E_LAUNCH;
   for (int i = 0; i < 16; ++i) if (a.pf_ptr[i] && (!al16(a.pf_ptr[i]) || (a.pf_bytes[i] & 15))) return GT_E_ALIGN;
   const dim3 grid((a.R + BM - 1) / BM + (a.pf_ptr[0] ? PF_WGS : 0)), block(256);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1085,12 +1076,9 @@ extern "C" int gt_wn_boundary_rev(const gt_boundary_rev_args* args, void* stream
     if (!al16(a.w_start) || !al16(a.b_start) || !al16(a.h_next)) return GT_E_ALIGN;
   }
   for (int i = 0; i < 16; ++i) if (a.pf_ptr[i] && (!al16(a.pf_ptr[i]) || (a.pf_bytes[i] & 15))) return GT_E_ALIGN;
-  static bool attr = false;                    // > 64 KB of LDS: opt in once per process
-  if (!attr) {
-    if (opt_in_lds(&gt_wn_boundary_rev_kernel<true, true>, REV_LDS) || opt_in_lds(&gt_wn_boundary_rev_kernel<true, false>, REV_LDS) ||
-        opt_in_lds(&gt_wn_boundary_rev_kernel<false, true>, REV_LDS)) return GT_E_LAUNCH;
-    attr = true;
-  }
+  // > 64 KB of LDS: opt in once per process
+  if (gt_allow_lds<&gt_wn_boundary_rev_kernel<true, true>>(REV_LDS) || gt_allow_lds<&gt_wn_boundary_rev_kernel<true, false>>(REV_LDS) ||
+      gt_allow_lds<&gt_wn_boundary_rev_kernel<false, true>>(REV_LDS)) return GT_E_LAUNCH;
   const dim3 grid((a.R + BM - 1) / BM + (a.pf_ptr[0] ? PF_WGS : 0)), block(256);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (tail && head) hipLaunchKernelGGL((gt_wn_boundary_rev_kernel<true, true>), grid, block, REV_LDS, st, a);
@@ -1133,12 +1121,8 @@ extern "C" int gt_wn_boundary_bwd(const gt_boundary_bwd_args* args, void* stream
     if (!al16(a.logs_raw) || !al16(a.y) || !al16(a.dout) || !al16(a.w_end_d) || !al16(a.dwn_out) || !al16(a.w_skip_d) || !al16(a.via_skip))
       return GT_E_ALIGN;
   }
-  static bool attr = false;
-  if (!attr) {
-    if (opt_in_lds(&gt_wn_boundary_bwd_kernel<true, true>, BWD_LDS) || opt_in_lds(&gt_wn_boundary_bwd_kernel<true, false>, BWD_LDS) ||
-        opt_in_lds(&gt_wn_boundary_bwd_kernel<false, true>, BWD_LDS)) return GT_E_LAUNCH;
-    attr = true;
-  }
+  if (gt_allow_lds<&gt_wn_boundary_bwd_kernel<true, true>>(BWD_LDS) || gt_allow_lds<&gt_wn_boundary_bwd_kernel<true, false>>(BWD_LDS) ||
+      gt_allow_lds<&gt_wn_boundary_bwd_kernel<false, true>>(BWD_LDS)) return GT_E_LAUNCH;
   for (int i = 0; i < 16; ++i) if (a.pf_ptr[i] && (!al16(a.pf_ptr[i]) || (a.pf_bytes[i] & 15))) return GT_E_ALIGN;
   const dim3 grid((a.R + BM - 1) / BM + (a.pf_ptr[0] ? PF_WGS : 0)), block(256);
   hipStream_t st = static_cast<hipStream_t>(stream);

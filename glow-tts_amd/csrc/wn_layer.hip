@@ -481,13 +481,8 @@ extern "C" int gt_wn_layer_bwd(const void* dpre_next, int lddn, const void* w_in
   a.dpre = static_cast<bf16_t*>(dpre); a.dpre_c = static_cast<bf16_t*>(dpre_c); a.lddp = lddp; a.R = R; a.stamps = stamps; a.stamp_slot = stamp_slot; a.stamp_base = stamp_base;
   const int rc = fill_drop(a, drop_p, drop_seed, seed_dev);
   if (rc) return rc;
-  static bool attr = false;                    // > 64 KB of LDS: opt in once (per process; the attribute is per device function)
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_wn_layer_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, BWD_LDS) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_wn_layer_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, BWD_LDS) != hipSuccess)
-      return GT_E_LAUNCH;
-    attr = true;
-  }
+  // > 64 KB of LDS: opt in once (per process; the attribute is per device function)
+  if (gt_allow_lds<&gt_wn_layer_bwd_kernel<true>>(BWD_LDS) || gt_allow_lds<&gt_wn_layer_bwd_kernel<false>>(BWD_LDS)) return GT_E_LAUNCH;
   const dim3 grid((R + BM - 1) / BM), block(256);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (w_res_dgrad_frag) hipLaunchKernelGGL(gt_wn_layer_bwd_kernel<true>, grid, block, BWD_LDS, st, a);

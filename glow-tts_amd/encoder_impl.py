@@ -76,21 +76,39 @@ def attn_long_shape(T, D, win):
     return D == 96 and win == 4 and 505 < T <= ATTN_MAX_T
 
 
+# What an attention forward saves for its backward: the three values keep_p takes.
+SAVE_P, SAVE_NONE, SAVE_STATS = True, False, "stats"
+
+
+def save_mode(owner, keep_p=SAVE_P):
+    """The one resolver of keep_p.  owner: a MultiHeadAttention (its keep_p switch) or a module that carries rows_cfg
+    (ops.RowsConfig.attn_keep_p); keep_p: what the caller asked for.  A caller's SAVE_NONE (synthesis) or SAVE_STATS stands; its
+    SAVE_P becomes SAVE_STATS where the owner's switch is off."""
+    if not keep_p:
+        return SAVE_NONE
+    if keep_p == SAVE_STATS:
+        return SAVE_STATS
+    switch = getattr(owner, "keep_p", None)
+    if switch is None:
+        switch = getattr(getattr(owner, "rows_cfg", None), "attn_keep_p", True)
+    return SAVE_P if switch else SAVE_STATS
+
+
 class AttnStats:
-    """What mha_fwd(keep_p="stats") saves where P was: t = stats [B, H, T, 2] fp32 of gt_attn_fwd_stats."""
+    """What mha_fwd(keep_p=SAVE_STATS) saves where P was: t = stats [B, H, T, 2] fp32 of gt_attn_fwd_stats."""
 
     def __init__(self, t):
         self.t = t
 
 
-def mha_fwd(rc, att, xb, p, seed, keep_p=True):
-    """keep_p=False: a forward nobody differentiates (synthesis).  At the shapes of the key-tiled kernels (gt_attn_long_shape) no
+def mha_fwd(rc, att, xb, p, seed, keep_p=SAVE_P):
+    """keep_p=SAVE_NONE: a forward nobody differentiates (synthesis).  At the shapes of the key-tiled kernels (gt_attn_long_shape) no
     [B, H, T, T] tensor is then allocated, gt_attn_fwd stores no P and the saved tuple carries None in its place; `out` is the same bit
     for bit.  At every other shape the flag changes nothing.  It cannot be inferred from grad mode: the training forward runs inside
     _RowsFn.apply, where grad mode is off.
-    keep_p="stats": a training forward without a saved P.  At the key-tiled shapes gt_attn_fwd_stats stores two floats per query row
+    keep_p=SAVE_STATS: a training forward without a saved P.  At the key-tiled shapes gt_attn_fwd_stats stores two floats per query row
     ([B, H, T, 2]: row maximum and reciprocal denominator) where P would be, `out` is the same bit for bit, and mha_bwd recomputes P
-    tile by tile (gt_attn_bwd_stats); at every other shape it is keep_p=True."""
+    tile by tile (gt_attn_bwd_stats); at every other shape it is keep_p=SAVE_P."""
     if rc.T > ATTN_MAX_T:       # before any allocation or launch: P and the backward's workspace are 4 B H T^2 bytes each per layer
         raise ValueError(f"attention takes at most {ATTN_MAX_T} tokens per utterance (GT_ATTN_LONG_MAX_T), got T = {rc.T}")
     dev = xb.device
@@ -103,10 +121,10 @@ def mha_fwd(rc, att, xb, p, seed, keep_p=True):
     o = ops_zeros_big((R, C), torch.bfloat16, dev)
     P = None
     long_shape = attn_long_shape(rc.T, D, att.window_size)
-    stats = isinstance(keep_p, str) and keep_p == "stats" and long_shape
+    stats = keep_p == SAVE_STATS and long_shape
     if stats:
         P = AttnStats(torch.empty(rc.B, H, rc.T, 2, dtype=torch.float32, device=dev))
-    elif keep_p or not long_shape:
+    elif keep_p or not long_shape:              # SAVE_P; SAVE_NONE and SAVE_STATS only where a key-tiled kernel runs
         P = torch.empty(rc.B, H, rc.T, rc.T, dtype=torch.float32, device=dev)
     Ek = att.emb_rel_k.detach().reshape(-1, D).contiguous()
     Ev = att.emb_rel_v.detach().reshape(-1, D).contiguous()
@@ -121,7 +139,7 @@ def mha_bwd(rc, att, saved, dy, grads):
     """dy: bf16 rows gradient of the attention block output.  Returns dxb (bf16)."""
     xb, q, k, v, o, P, Ek, Ev, p, seed = saved
     if P is None:
-        raise RuntimeError("attention backward after a forward that stored no P (mha_fwd(keep_p=False))")
+        raise RuntimeError("attention backward after a forward that stored no P (mha_fwd(keep_p=SAVE_NONE))")
     dev = xb.device
     R = rc.R
     H, D, C = att.n_heads, att.k_channels, att.channels
@@ -149,7 +167,7 @@ def mha_bwd(rc, att, saved, dy, grads):
 
 
 # ----------------------------------------------------------------------------- one encoder layer
-def layer_fwd(rc, enc, i, x, xb, train, seed, keep_p=True):
+def layer_fwd(rc, enc, i, x, xb, train, seed, keep_p=SAVE_P):
     p = enc.p_dropout if train else 0.0
     att, ffn = enc.attn_layers[i], enc.ffn_layers[i]
     C = enc.hidden_channels

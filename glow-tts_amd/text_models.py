@@ -128,7 +128,7 @@ class TextEncoder(nn.Module):
         lvec = None if l is None else l.squeeze(-1)     # [b, lin]: a differentiable input of the node (emb_l upstream)
         runner = _TextEncoderRunner(self, x, x_lengths, self.training, seed=(self._step * 104729) & 0x7fffffff,
                                     has_cond=vec is not None, has_lang=lvec is not None,
-                                    keep_p="stats" if keep_p and not getattr(getattr(self, "rows_cfg", None), "attn_keep_p", True) else keep_p)
+                                    keep_p=encoder_impl.save_mode(self, keep_p))
         outs = _RowsFn.apply(runner, 3, *([vec] if vec is not None else []), *([lvec] if lvec is not None else []), *runner.params)
         xo, x_m, x_logs = outs[0], outs[1], outs[2]
         self._last_rows = runner.last            # (rc, xb_final) for the duration predictor

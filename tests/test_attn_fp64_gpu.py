@@ -11,7 +11,11 @@ T per code path and per edge (csrc/attn_mfma.hip's dispatchers; the smallest val
   generic (csrc/encoder_ops.hip)                385;  T = 40 with D = 64 (generic by head size)
 Lengths [T - 7, 1, T] ([min(33, T), 1, T] for T <= 40): a tile-crossing utterance, a length-1 one, the last one full length.  q, k, v
 are windows of one [R, 3 C] buffer, dq, dk, dv of one gradient buffer, the outputs lie between guard rows, and every row no store may
-touch (guards, halos, rows past an utterance's own) holds a canary."""
+touch (guards, halos, rows past an utterance's own) holds a canary.
+
+One more case hands an MFMA shape (T = 33, D = 96) to the generic kernels by layout: the q, k, v buffer's row pitch is 3 C + 2 elements
+(ld & 7 != 0, rows still 4-byte aligned), which the MFMA kernels do not take.  Both directions then run the generic kernels: the
+workspace holds the fp32 dS and the case is checked under the generic rule."""
 import types
 
 import pytest
@@ -34,9 +38,12 @@ def dev():
     return torch.device("cuda:0")
 
 
+GENERIC = "generic gt_attn_fwd_kernel / gt_attn_bwd_q_kernel + gt_attn_bwd_kv_kernel"
+
+
 def _variant(T, D):
     if D != 96 or T > 384:
-        return 0, "generic gt_attn_fwd_kernel / gt_attn_bwd_q_kernel + gt_attn_bwd_kv_kernel"
+        return 0, GENERIC
     if T <= 160:
         return 1, "launch_fwd<5> / launch_bwd<5,4> (all tiles)"
     if T <= 256:
@@ -46,6 +53,16 @@ def _variant(T, D):
 
 @pytest.mark.parametrize("T,D,ragged,p,word,dirty", CASES)
 def test_attention_vs_float64(built, T, D, ragged, p, word, dirty):
+    _run_case(T, D, ragged, p, word, dirty)
+
+
+def test_attention_unaligned_pitch_vs_float64(built):
+    """An MFMA shape whose row pitch the MFMA kernels refuse: the generic kernels run it, forward and backward."""
+    _run_case(33, 96, True, 0.1, False, False, pad=2)
+
+
+def _run_case(T, D, ragged, p, word, dirty, pad=0):
+    """pad: extra elements in the row pitch of the q, k, v buffer; pad & 7 != 0 takes an MFMA shape to the generic kernels"""
     from glow_tts_amd import _lib, ops
     L = _lib.lib()
     C = H * D
@@ -53,6 +70,9 @@ def test_attention_vs_float64(built, T, D, ragged, p, word, dirty):
     mfma, variant = _variant(T, D)
     assert L.gt_attn_mfma_shape(T, D, WIN) == mfma
     tag = f"attn T={T} D={D} {'ragged' if ragged else 'uniform'} p={p}"
+    if pad:
+        assert mfma == 1 and (3 * C + pad) & 7 and not (3 * C + pad) & 1      # an MFMA shape, a pitch it refuses, rows 4-byte aligned
+        mfma, variant, tag = 0, GENERIC + f" by layout (row pitch 3 C + {pad})", tag + f" pitch 3C+{pad}"
     print(f"{tag}: {variant}" + (", seed word on the device" if word else "") + (", non-zero dout on padded rows" if dirty else ""))
     lens_t = torch.tensor(lens, dtype=torch.int32, device=dev())
     rc = ops.RowsCtx(lens_t, T, lengths_host=lens, round_to=128) if ragged else ops.RowsCtx(lens_t, T)
@@ -75,13 +95,13 @@ def test_attention_vs_float64(built, T, D, ragged, p, word, dirty):
             do[rbase[b] + lens[b]:rbase[b] + T] = torch.randn(T - lens[b], C, generator=g)
     do = do.to(torch.bfloat16)
 
-    def guarded(t, fill):
-        buf = torch.full((R_ + 2 * GUARD, t.shape[1]), fill, dtype=t.dtype, device=dev())
-        buf[GUARD:GUARD + R_] = t.to(dev())
-        return buf, buf[GUARD:GUARD + R_]
+    def guarded(t, fill, pad=0):
+        buf = torch.full((R_ + 2 * GUARD, t.shape[1] + pad), fill, dtype=t.dtype, device=dev())
+        buf[GUARD:GUARD + R_, :t.shape[1]] = t.to(dev())
+        return buf, buf[GUARD:GUARD + R_, :t.shape[1]]
 
     nan = float("nan")
-    qb, qv = guarded(qkv, nan)
+    qb, qv = guarded(qkv, nan, pad)
     dob, dov = guarded(do, nan)
     ob, ov = guarded(torch.full((R_, C), CANARY, dtype=torch.bfloat16), CANARY)
     gb, gv = guarded(torch.full((R_, 3 * C), CANARY, dtype=torch.bfloat16), CANARY)
@@ -93,9 +113,9 @@ def test_attention_vs_float64(built, T, D, ragged, p, word, dirty):
     wd = torch.tensor([WORD], dtype=torch.int32, device=dev()) if word else None
     st, r0 = _lib.current_stream(dev()), _lib.ptr(rc.row0)
     q, k, v = qv[:, :C], qv[:, C:2 * C], qv[:, 2 * C:]
-    _lib.check(L.gt_attn_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), 3 * C, _lib.ptr(Ekd), _lib.ptr(Evd), _lib.ptr(rc.lengths), _lib.ptr(ov), C,
+    _lib.check(L.gt_attn_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), 3 * C + pad, _lib.ptr(Ekd), _lib.ptr(Evd), _lib.ptr(rc.lengths), _lib.ptr(ov), C,
                              _lib.ptr(P), B, T, rc.Tp, r0, H, D, WIN, p, SEED, _lib.ptr(wd), st), "gt_attn_fwd")
-    _lib.check(L.gt_attn_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), 3 * C, _lib.ptr(Ekd), _lib.ptr(Evd), _lib.ptr(rc.lengths), _lib.ptr(dov), C,
+    _lib.check(L.gt_attn_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), 3 * C + pad, _lib.ptr(Ekd), _lib.ptr(Evd), _lib.ptr(rc.lengths), _lib.ptr(dov), C,
                              _lib.ptr(P), _lib.ptr(ws), wsb, _lib.ptr(gv[:, :C]), _lib.ptr(gv[:, C:2 * C]), _lib.ptr(gv[:, 2 * C:]), 3 * C,
                              _lib.ptr(dEk), _lib.ptr(dEv), B, T, rc.Tp, r0, H, D, WIN, p, SEED, _lib.ptr(wd), st), "gt_attn_bwd")
     torch.cuda.synchronize()
