@@ -190,6 +190,11 @@ PROTOTYPES = {
                                    c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
     "gt_synth_contours_call": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gt_mel_pack_bytes": (c_size_t, []),
+    "gt_mel_tile_frames": (c_int, []),
+    "gt_mel_pack": (STATUS, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gt_mel_spectrogram": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 c_void_p = ctypes.c_void_p
 

@@ -121,3 +121,51 @@ class TextMelCollate:
         if full:
             return text_padded, input_lengths, mel_padded, output_lengths, spk, emos, cart, f0, energy, lid
         return text_padded, input_lengths, mel_padded, output_lengths
+
+
+class TextAudioCollate:
+    """TextMelCollate for items that carry the waveform instead of the mel: (text ids [t], wave int16 [L]) or the 8-field items
+    (text, wave, spk_embed, emo, emo_cartesian, f0 [1, F], energy [1, F] or None, lid).  Same sorting (by text length, descending),
+    same field order: (text_padded, input_lengths, wav_padded int16 [B, L_max], wav_lengths in SAMPLES) plus, for 8-field items,
+    (spk_embeds, emos, emo_cartesians, f0_padded, energy_padded, lid).  The mel and the energy contour come from the device
+    (audio.TacotronSTFT.mel_spectrogram(wav_padded, wav_lengths)); f0 stays an item field, padded to the 1 + L_max // hop frames
+    that call returns, and energy_padded is None when the items carry none.  L_max is rounded up to 4 samples (the kernel's pitch)."""
+
+    def __init__(self, pin_memory=False, hop_length=256):
+        self.pin, self.hop = pin_memory, hop_length
+
+    _new = TextMelCollate._new
+
+    def __call__(self, batch):
+        input_lengths, order = torch.sort(torch.LongTensor([len(x[0]) for x in batch]), dim=0, descending=True)
+        n = len(batch)
+        text_padded = self._new(n, int(input_lengths[0]), dtype=torch.long)
+        for i, k in enumerate(order.tolist()):
+            text_padded[i, :batch[k][0].size(0)] = batch[k][0]
+        for x in batch:
+            if x[1].dtype != torch.int16 or x[1].dim() != 1:
+                raise ValueError(f"waveforms are int16 [L], got {tuple(x[1].shape)} {x[1].dtype}")
+        l_max = max(x[1].numel() for x in batch)
+        max_t = 1 + l_max // self.hop
+        wav_padded = self._new(n, (l_max + 3) // 4 * 4, dtype=torch.int16)
+        wav_lengths = torch.zeros(n, dtype=torch.long)
+        full = len(batch[0]) >= 8
+        if full:
+            spk = self._new(n, batch[0][2].numel(), dtype=torch.float32)
+            emos, lid = torch.zeros(n, dtype=torch.long), torch.zeros(n, dtype=torch.long)
+            cart = self._new(n, 3, dtype=torch.float32)
+            f0 = self._new(n, 1, max_t, dtype=torch.float32)
+            energy = self._new(n, 1, max_t, dtype=torch.float32) if batch[0][6] is not None else None
+        for i, k in enumerate(order.tolist()):
+            item = batch[k]
+            wav_padded[i, :item[1].numel()] = item[1]
+            wav_lengths[i] = item[1].numel()
+            if full:
+                spk[i] = item[2]; emos[i] = item[3]; cart[i] = item[4]
+                f0[i, :, :item[5].size(1)] = item[5]
+                if energy is not None:
+                    energy[i, :, :item[6].size(1)] = item[6]
+                lid[i] = item[7]
+        if full:
+            return text_padded, input_lengths, wav_padded, wav_lengths, spk, emos, cart, f0, energy, lid
+        return text_padded, input_lengths, wav_padded, wav_lengths

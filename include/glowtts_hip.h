@@ -947,6 +947,35 @@ int gt_synth_contours_call(const float* pitch_rows, const float* energy_rows, co
                            int Rf, const int32_t* row0, int Tp, const int32_t* len_sq, int R, float* psig, float* esig, float* pitch,
                            float* energy, int B, int Ty, const gt_synth_call_ext* call, void* stream);
 
+/* ---- device mel front end (csrc/mel_front.hip): waveforms -> log-mel, energy, magnitudes in one kernel ----------
+ * The reference's TacotronSTFT.mel_spectrogram (commons.py:298-317, stft.py:78-101 CUDA branch) applied to every utterance of a
+ * padded batch on its own, in exact fp32 (v_mfma_f32_32x32x2_f32).  Utterance b has F_b = 1 + wav_len[b] / 256 frames; frame f covers
+ * samples 256 f - 512 .. 256 f + 511, indices outside [0, wav_len[b]) reflected about the utterance's own ends (edge not repeated);
+ *   mag = sqrt(re^2 + im^2) [513 bins],  energy = ||mag||_2,  mel = logf(max(mel_basis mag, clip)),
+ * and every output position f >= F_b is written as 0: all of mel [B, n_mel, F_max], energy [B, F_max] and mag [B, 513, F_max] (mag
+ * may be NULL: not stored, the other two bit-identical) is defined.  No atomics; the summation order of an element depends on its
+ * frame index alone, not on B, F_max or the row: a batch row is bit-identical to the utterance computed alone.
+ *   wav      [B rows, pitch ld_wav elements] fp32 in [-1, 1], or int16 when is_i16 != 0 (scaled by 1/32768 in the kernel).
+ *   wav_len  device int32 [B]; clamped to ld_wav.  wav_len <= 512 (no reflect padding exists) gives an unspecified result, but the
+ *            reflected index is clamped: nothing outside the utterance's wav_len samples is read.  wav_len <= 0: all zeros.
+ *   packed   gt_mel_pack_bytes() bytes written ONCE by gt_mel_pack from the reference's own buffers: basis = STFT.forward_basis
+ *            (fp32 [2 * 513, 1024]: 513 real rows, then 513 imaginary rows, windowed) and mel_basis (fp32 [n_mel, 513]); the same
+ *            n_mel goes to both calls.  The image folds every frame about its centre (K = 512), so the window must be symmetric
+ *            about sample 512 with w[0] = 0 — the periodic Hann window of every reference config.
+ * Supported: n_fft = win = 1024, hop = 256, n_mel <= GT_MEL_MAX_N_MEL; anything else GT_E_UNSUPPORTED before a launch.  NULL wav /
+ * wav_len / packed / mel / energy, B outside [1, GT_MEL_MAX_B], F_max outside [1, GT_MEL_MAX_FRAMES], ld_wav <= 0, n_mel <= 0:
+ * GT_E_INVAL.  Pointers not 16-byte (wav_len: 4-byte) aligned, ld_wav no multiple of 4: GT_E_ALIGN.
+ * gt_mel_tile_frames: frames per workgroup (a tile past an utterance's end costs a zero fill). */
+#define GT_MEL_MAX_N_MEL 128
+#define GT_MEL_MAX_B 65535
+#define GT_MEL_MAX_FRAMES 1048576
+size_t gt_mel_pack_bytes(void);
+int gt_mel_tile_frames(void);
+int gt_mel_pack(const float* basis, const float* mel_basis, int n_fft, int n_mel, void* packed, void* stream);
+int gt_mel_spectrogram(const void* wav, int is_i16, int ld_wav, const int32_t* wav_len, int B, int F_max,
+                       const void* packed, int n_fft, int hop, int win, int n_mel, float clip,
+                       float* mel, float* energy, float* mag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
