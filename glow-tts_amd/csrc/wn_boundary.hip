@@ -173,8 +173,20 @@ __device__ __forceinline__ void coop_store_rows(bf16_t* __restrict__ dst, int ld
 // on a forward launch, + 9 us on a backward one, all of it gone once the images are back in the cache (tools/wn_layer_bench.py,
 // WN_BENCH_COLD).  A boundary launch runs 152 workgroups on 256 CUs: PF_WGS extra workgroups (blockIdx >= the row tiles) read
 // those images once, on CUs that were idle, and retire within a few microseconds.
+//
+// The loads have no consumer, so something must keep the compiler from deleting them.  KEEP = true feeds their XOR to an empty
+// asm volatile: no store, nothing the caller owns is touched, whatever bytes the buffers hold (tests/test_wn_boundary_fp64_gpu.py,
+// test_prefetch_buffers_are_inert).  It used to be a store of the XOR to a caller's pointer — the forward's logdet — under a
+// comparison with one magic word, on the claim that bf16 weight bits never form that word: they can, and logdet[0] then lost every
+// earlier block's log-det.
+// Only the FORWARD kernels pass KEEP = true.  The backward and reverse kernels passed a NULL sink, the compiler deleted their loads,
+// and their prefetch workgroups are EMPTY in the current build and in its parent (the branch is a bare s_endpgm;
+// profiles/wn_boundary_prefetch_isa.txt; earlier builds were not disassembled): with such code only the forward's of the two
+// savings quoted above can come from these workgroups.  KEEP = false keeps that device code
+// byte-identical; turning it on is a performance change that needs its own measurement.
 constexpr int PF_WGS = 64;
-__device__ __forceinline__ void prefetch_images(const void* const (&ptr)[16], const uint32_t (&bytes)[16], int wg, uint32_t* sink)
+template <bool KEEP>
+__device__ __forceinline__ void prefetch_images(const void* const (&ptr)[16], const uint32_t (&bytes)[16], int wg)
 {
   uint32_t acc = 0;
   const int gid = wg * 256 + threadIdx.x, nthr = PF_WGS * 256;
@@ -191,7 +203,7 @@ __device__ __forceinline__ void prefetch_images(const void* const (&ptr)[16], co
       acc ^= v0.x ^ v1.y ^ v2.z ^ v3.w;
     }
   }
-  if (acc == 0x9E3779B9u && sink) *sink = acc;                          // (keeps the loads alive; bf16 weight bits never form this word on every lane)
+  if (KEEP) asm volatile("" :: "v"(acc));                               // consumes the loads; emits nothing
 }
 
 // ------------------------------------------------------------------------------------------------ forward
@@ -208,7 +220,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int n_tiles = (a.R + BM - 1) / BM;
-  if ((int)blockIdx.x >= n_tiles) { prefetch_images(a.pf_ptr, a.pf_bytes, blockIdx.x - n_tiles, reinterpret_cast<uint32_t*>(a.logdet)); return; }
+  if ((int)blockIdx.x >= n_tiles) { prefetch_images<true>(a.pf_ptr, a.pf_bytes, blockIdx.x - n_tiles); return; }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
   const int m0 = blockIdx.x * BM, R = a.R;
@@ -496,7 +508,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int n_tiles = (a.R + BM - 1) / BM;
-  if ((int)blockIdx.x >= n_tiles) { prefetch_images(a.pf_ptr, a.pf_bytes, blockIdx.x - n_tiles, nullptr); return; }
+  if ((int)blockIdx.x >= n_tiles) { prefetch_images<false>(a.pf_ptr, a.pf_bytes, blockIdx.x - n_tiles); return; }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
   const int m0 = blockIdx.x * BM, R = a.R;
@@ -806,7 +818,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_rev_kernel(gt_boundary_rev
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int n_tiles = (a.R + BM - 1) / BM;
-  if ((int)blockIdx.x >= n_tiles) { prefetch_images(a.pf_ptr, a.pf_bytes, blockIdx.x - n_tiles, nullptr); return; }
+  if ((int)blockIdx.x >= n_tiles) { prefetch_images<false>(a.pf_ptr, a.pf_bytes, blockIdx.x - n_tiles); return; }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
   const int m0 = blockIdx.x * BM, R = a.R;

@@ -660,6 +660,9 @@ def decoder_bwd_fused(rc, dec, blocks, drows, dlogdet, has_cond, dz_bct=None, dx
             if _fused_ok(svp.chain[-1][0]):
                 # (the saved tanh / sigmoid halves the same launch reads — 30 MB written in the forward pass — were tried as `extra`: no
                 # change in the step; the backward launch's cold cost is not where its 64 spare workgroups can reach in 28 us)
+                # NOTE: in the current build the backward and reverse kernels' prefetch workgroups load nothing (the compiler deletes
+                # their loads: csrc/wn_boundary.hip prefetch_images<false>), so this list — and the one
+                # decoder_rev_fused passes — only adds 64 empty workgroups, and the experiment above says nothing either way
                 kw["pf_ptr"], kw["pf_bytes"] = _prefetch_list(svp.chain[-1][0], "dgrad")
             new_tail = (dout, dwn, via)
         if dx_out is None:

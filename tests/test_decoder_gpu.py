@@ -85,6 +85,8 @@ def test_wgrad_ring_long_rows_and_ragged_ends(built):
 
 
 def test_actnorm_invconv_fwd_bwd(built):
+    """The wrapper functions against the fp32 oracle and autograd at one shape; the kernels themselves are held to float64 on their
+    own operands, with planted defects, by tests/test_wn_boundary_fp64_gpu.py::test_five_launch_kernels_against_float64."""
     from glow_tts_amd import ops, flow_impl
     B, T, C = 2, 40, 160
     g = torch.Generator().manual_seed(5)
