@@ -220,6 +220,7 @@ class StepCtx(ctypes.Structure):
 
 
 STEP_MAX_COPIES, STEP_MAX_CTX, STEP_MAX_B = 10, 3, 1024
+MLE_PARTS = 2048                                 # GT_MLE_PARTS: partial pairs gt_mle_sums writes (tests/test_loss64.py compares it with the header)
 SYNTH_MAX_TX, SYNTH_LONG_MAX_TX = 512, 4096      # tokens gt_synth_lengths / gt_synth_prior[_call] take, and their *_long forms (GT_SYNTH_LONG_MAX_TX)
 
 

@@ -1188,8 +1188,8 @@ extern "C" int gt_prior_expand_bwd(const float* dz_m, const int32_t* frame2token
 }
 extern "C" int gt_mle_sums(const float* z, const float* m, const float* logs, float* acc2, size_t n, void* stream)
 {
-  if (!z || !m || !acc2) return GT_E_INVAL;
-  if (n == 0) return GT_OK;
+  if (!acc2 || (n && (!z || !m))) return GT_E_INVAL;
+  // n == 0 launches too: the kernel then reads nothing and stores GT_MLE_PARTS zero pairs, which is what gt_mle_finish sums
   if (((uintptr_t)z | (uintptr_t)m | (uintptr_t)logs) & 15) return GT_E_ALIGN;
   if ((uintptr_t)acc2 & 7) return GT_E_ALIGN;
   hipLaunchKernelGGL(gt_mle_sums_kernel, dim3(GT_MLE_PARTS), dim3(256), 0, GT_ST(stream), z, m, logs, acc2, n);

@@ -302,7 +302,7 @@ class _MleLossFn(torch.autograd.Function):
         dev = z.device
         zc, mc = z.detach().float().contiguous(), m.detach().float().contiguous()
         lc = None if logs is None else logs.detach().float().contiguous()
-        acc = torch.empty(2 * 2048, dtype=torch.float32, device=dev)       # GT_MLE_PARTS partial pairs, all written by the kernel
+        acc = torch.empty(2 * _lib.MLE_PARTS, dtype=torch.float32, device=dev)     # GT_MLE_PARTS partial pairs, all written by the kernel
         call.gt_mle_sums(zc, mc, lc, acc, zc.numel(), _lib.current_stream(dev))
         # the scalar tail in one launch: loss = (acc[0] + 0.5 acc[1] - sum logdet) / denom + 0.5 log 2pi, denom = C * sum(mask)
         ld = logdet.detach().float().contiguous()

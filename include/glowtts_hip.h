@@ -453,7 +453,8 @@ int gt_prior_expand(const float* x_m, const int32_t* frame2token, float* z_m, in
 int gt_prior_expand_bwd(const float* dz_m, const int32_t* frame2token, float* dx_m, int B, int C, int Tx, int Ty, void* stream);
 
 /* mle_loss pieces (commons.py:28-33): gt_mle_sums leaves GT_MLE_PARTS partial pairs (sum(logs), sum(exp(-2 logs)(z-m)^2)) in acc2 — one per
- * workgroup, plain stores, summed by gt_mle_finish;
+ * workgroup, plain stores, summed by gt_mle_finish; n == 0 is not refused: the launch leaves GT_MLE_PARTS zero pairs (z, m may then
+ * be NULL), so gt_mle_finish gives -sum(logdet) / denom + 0.5 log(2 pi);
  * backward: dz = g e^{-2 logs}(z-m), dm = -dz, dlogs = g (1 - e^{-2 logs}(z-m)^2), g = *gscale (/ *gdenom when gdenom != NULL:
  * the loss's denominator stays on the device); dlogdet (optional, [B]) receives -g. */
 #define GT_MLE_PARTS 2048      /* acc2 holds this many (sum logs, sum exp(-2 logs)(z-m)^2) partial pairs: 2 * GT_MLE_PARTS floats, all written */
