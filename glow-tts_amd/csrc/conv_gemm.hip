@@ -8,7 +8,9 @@
 // Data layout ("rows"): activations are [R, C] channels-last, R = B * Tp rows where every
 // utterance owns Tp = T + 2*HALO consecutive rows and its first/last HALO rows (and every row
 // past its length) are zero.  A k-tap convolution is then k shifted row-block GEMMs with no
-// boundary logic:  Y[m, n] = sum_tap sum_ci X[m + tap - k/2, ci] * W[tap][n][ci].
+// boundary logic:  Y[m, n] = sum_tap sum_ci X[m + tap - k/2, ci] * W[tap][n][ci].  At the two ends of the buffer the row index is
+// CLAMPED into [0, R-1] (ldx1 / load_stage), which equals reading zeros because rows 0..k/2-1 and R-k/2..R-1 are zero halo rows:
+// a precondition of every k > 1 call (include/glowtts_hip.h; pinned by tests/test_conv_gemm_fp64_gpu.py).
 //
 // Mapping: MFMA A = weight tile (rows = output channels n), MFMA B = activation tile
 // (columns = rows m), so a lane's 16 accumulators are 4 groups of 4 CONSECUTIVE channels of ONE
@@ -479,6 +481,11 @@ extern "C" int gt_conv_gemm_bf16(const void* X, int ldx, const void* Wp, const f
   if ((N & 3) || (Cin & 7) || (ldx & 7) || (ldy & 3) || (Kp % BK) || Kp < Cin) return GT_E_ALIGN;
   if (((uintptr_t)X | (uintptr_t)Wp | (uintptr_t)Y) & 15) return GT_E_ALIGN;
   if (addend && (ldadd & 3)) return GT_E_ALIGN;
+  // the epilogues read bias, cond and a fp32 addend as float4 at channels n % 4 == 0, a bf16 addend as 8-byte halves
+  if (((uintptr_t)bias | (uintptr_t)cond) & 15) return GT_E_ALIGN;
+  if (cond && (ldc & 3)) return GT_E_ALIGN;
+  if ((uintptr_t)addend & (out_f32 ? 15 : 7)) return GT_E_ALIGN;
+  if ((uintptr_t)rowmask & 3) return GT_E_ALIGN;
   if (cond && (Tp <= 0 || (row0 && B <= 0))) return GT_E_INVAL;
   if (tile < GT_TILE_AUTO || tile > GT_TILE_64x64_TAPS) return GT_E_INVAL;
   if (Np % 64 || Np < N) return GT_E_INVAL;
@@ -508,6 +515,7 @@ extern "C" int gt_conv_gemm_bf16(const void* X, int ldx, const void* Wp, const f
   }
   if (gate == 1) {                            // gate: N = Np = 2 * half, [32 tanh | 32 sigmoid] per 64 packed rows, 128-column tiles
     if (!gate_t || !gate_s || (N & 127) || Np != N || out_f32) return GT_E_INVAL;
+    if (addend || rowmask || relu) return GT_E_INVAL;                  // the gate epilogue has none of them: refused, not ignored
     if ((ldts & 7) || (ldy & 7) || (((uintptr_t)gate_t | (uintptr_t)gate_s) & 15)) return GT_E_ALIGN;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -140,6 +140,7 @@ int gt_mas_lengths_from_mask_f32(const float* mask, int32_t* t_x, int32_t* t_y,
  *   gate == 1 (WaveNet gate, commons.py:61-68; N = 2*half, packed with the gate interleave):
  *     pre = drop(acc + bias) + cond;  T = tanh(pre[:half]), S = sigmoid(pre[half:]),
  *     Y[m, :half] = T*S (bf16), T and S are saved to gate_t / gate_s ([R, ldts] bf16; ldts%8, ldy%8 == 0).
+ *     This epilogue has no relu, addend or rowmask: any of them returns GT_E_INVAL.
  *   gate == 2 (backward of that gate fused behind a data-gradient GEMM): d = acc + addend is d(T*S);
  *     gate_t / gate_s are the SAVED T / S (read-only); Y is [R, 2N] bf16: Y[m, n] = d*S*(1-T^2), Y[m, N+n] =
  *     d*T*S*(1-S), both times the forward's dropout mask (drop_p / drop_seed as given to the forward call).
@@ -152,7 +153,12 @@ int gt_mas_lengths_from_mask_f32(const float* mask, int32_t* t_x, int32_t* t_y,
  * host seed at kernel start: a captured HIP graph then draws fresh masks on every replay by bumping that word.
  * tile: 0 = the library's choice from (R, Np, gate); tests force a variant with GT_TILE_64x64 … GT_TILE_256x64
  * (rows x packed channels per workgroup; a variant the shape does not allow returns GT_E_INVAL).
- * Alignment: all pointers 16 B; N%4, Cin%8, ldx%8, ldy%4, Kp%64 == 0. */
+ * End rows: the kernels CLAMP the row index m + tap - k/2 into [0, R-1] instead of reading zeros outside [0, R).  The two agree
+ *   because the first and last k/2 rows of X are zero — halo rows of the first and last utterance in the rows layout (k/2 <= GT_HALO).
+ *   That is a precondition of every call with k > 1; with other rows there, only Y's first and last k/2 rows differ from the
+ *   zero-padded sum (tests/test_conv_gemm_fp64_gpu.py pins the clamp).
+ * Alignment (GT_E_ALIGN otherwise): X, Wp, Y, bias, cond, gate_t, gate_s and a fp32 addend 16 B, a bf16 addend 8 B, rowmask 4 B;
+ *   N%4, Cin%8, ldx%8, ldy%4, ldadd%4, ldc%4, Kp%64 == 0. */
 #define GT_TILE_AUTO 0
 #define GT_TILE_64x64 1
 #define GT_TILE_64x128 2

@@ -6,6 +6,7 @@ import os
 import sys
 import types
 
+import numpy as np
 import pytest
 import torch
 
@@ -89,3 +90,62 @@ def test_decoder_images_equal_the_packers_contract(built):
         n_img += 1
     assert {0, 6, 22} <= seen, seen                            # plain, fragment order, fragment order + [16 | 16] gate interleave
     print(f"{n_img} convs: decoded images equal the packer's contract (flags {sorted(seen)})")
+
+
+# ----------------------------------------------------------------------------- the text encoder's shapes, every packing kernel
+# (Cout, Cin, taps, weight-normed, PackedConv keywords): the FFN's two convs (768 x 192 x 3; 192 x 768 x 3 = 2304 elements per row,
+# exactly the documented limit of the 8-row kernel), the prenet, qkv, the duration predictor and its 8-wide proj_pad, a gate conv
+# with the [32 | 32] interleave gate == 1 reads (flag 1), and a bf16x3 conv (flag 8: one row per workgroup only)
+ENC_CONVS = [(768, 192, 3, False, {}), (192, 768, 3, False, {}), (192, 192, 5, True, {}), (576, 192, 1, False, {}), (256, 192, 3, False, {}),
+             (8, 256, 1, False, {}), (192, 80, 1, True, {}), (384, 192, 5, True, dict(gate=True)), (192, 192, 1, False, dict(split3=True))]
+
+
+def _split_check(tag, v, pc):
+    """flag 8: both images are plain images of [w_hi | w_lo | w_hi] along the reduction axis, zero elsewhere"""
+    Cout, Cin, _ = v.shape
+    vf = v.detach().cpu().float().numpy()[:, :, 0]
+    hi = rows64.bf16_round(vf)
+    lo = rows64.bf16_round((vf - hi.astype(np.float32)).astype(np.float32))
+    want_f = torch.from_numpy(np.concatenate([hi, lo, hi], 1))[None]              # [1][Cout][3 Cin]
+    want_d = torch.from_numpy(np.concatenate([hi.T, lo.T, hi.T], 1))[None]        # [1][Cin][3 Cout]
+    fwd = rows64.decode_fwd(pc.fwd, Cout, 3 * Cin, 1, pc.Np_f, pc.Kp_f, 0)
+    dgr = rows64.decode_fwd(pc.dgrad, Cin, 3 * Cout, 1, pc.Np_d, pc.Kp_d, 0)
+    assert torch.equal(fwd, want_f), (tag, int((fwd != want_f).sum()))
+    assert torch.equal(dgr, want_d), (tag, int((dgr != want_d).sum()))
+    for img, Np, Kp, want in ((pc.fwd, pc.Np_f, pc.Kp_f, want_f), (pc.dgrad, pc.Np_d, pc.Kp_d, want_d)):
+        assert int((rows64.decode_image(img, 1, Np, Kp, False) != 0).sum()) == int((want != 0).sum()), tag
+
+
+@pytest.mark.parametrize("group8", [0, 1, 2])
+def test_encoder_shapes_through_every_multi_conv_packer(built, group8):
+    """gt_pack_conv_weights_multi with group8 = 0 (one row per workgroup: every conv, the split one included), 1 (8 rows, rows of up to
+    2304 elements) and 2 (8 rows, up to 1024): each image equals rows64.packed_weights with the kernel's own inv_norm, padding zero."""
+    from glow_tts_amd import _lib, ops
+    g = torch.Generator().manual_seed(group8)
+    convs = [c for c in ENC_CONVS if group8 == 0 or (not c[4].get("split3") and c[1] * c[2] <= (2304 if group8 == 1 else 1024))]
+    assert group8 == 2 or any(c[1] * c[2] == 2304 for c in convs)
+    entries = []
+    for Cout, Cin, taps, wn, kw in convs:
+        v = (torch.randn(Cout, Cin, taps, generator=g) / (Cin * taps) ** 0.5).to(dev())
+        gg = (torch.rand(Cout, generator=g) + 0.5).to(dev()) if wn else None
+        entries.append((v, gg, ops.PackedConv(Cout, Cin, taps, device=dev(), **kw)))
+    arr = (_lib.PackDesc * len(entries))()
+    row = 0
+    for d, (v, gg, pc) in zip(arr, entries):
+        d.v, d.g = v.data_ptr(), (gg.data_ptr() if gg is not None else None)
+        d.pack_fwd, d.pack_dgrad, d.inv_norm = pc.fwd.data_ptr(), pc.dgrad.data_ptr(), pc.inv_norm.data_ptr()
+        d.Cout, d.Cin, d.taps = pc.Cout, pc.Cin, pc.taps
+        d.Np_fwd, d.Kp_fwd, d.Np_dgrad, d.Kp_dgrad, d.gate, d.row_start = pc.Np_f, pc.Kp_f, pc.Np_d, pc.Kp_d, pc.flags, row
+        row += pc.Cout
+    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev())
+    _lib.call.gt_pack_conv_weights_multi(table, len(entries), row, group8, _lib.current_stream(dev()))
+    torch.cuda.synchronize()
+    seen = set()
+    for v, gg, pc in entries:
+        tag = f"group8={group8} {tuple(v.shape)} flags {pc.flags}"
+        seen.add(pc.flags)
+        if pc.flags & 8:
+            _split_check(tag, v, pc)
+        else:
+            _check_images(tag, (v, gg, pc), pc.inv_norm, True)
+    assert seen == ({0, 1, 8} if group8 == 0 else {0, 1}), seen
