@@ -30,20 +30,46 @@ struct LnArgs {
   const uint32_t* seed_dev;                    // optional device word XOR-ed into both seeds (graph replay)
 };
 
+// Every load of a row goes out before the first use: which of a / y (and, backward, dout_f32 / dout_bf16) exist is a template
+// parameter, channels past C read channel C - 1 (an address only: the value is never used), rows past the end read row R - 1,
+// and the optional rowmask / seed word come through a pointer chosen beforehand (gamma stands in where they are absent).  A
+// wave then waits ONCE for its row instead of once per operand.  The arithmetic is the former kernels'.
+// ln_landed: the compiler otherwise sinks a load into the first block that uses it, behind that block's branch: an empty statement that
+// names the loaded register after ALL the loads were issued keeps them together in front of it.
+template <typename T> __device__ __forceinline__ void ln_landed(T& x) { asm volatile("" : "+v"(x)); }
+
+template <bool HAS_A, bool HAS_Y>
 __global__ __launch_bounds__(256) void gt_layernorm_fwd_kernel(LnArgs p)
 {
-  if (p.seed_dev) { const uint32_t x = *p.seed_dev; p.din_seed ^= x; p.dout_seed ^= x; }
   const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (m >= p.R) return;
+  const uint32_t sx = *(p.seed_dev ? p.seed_dev : reinterpret_cast<const uint32_t*>(p.gamma));
+  float rmv = *(p.rowmask ? p.rowmask + m : p.gamma);
+  float av[4], gv[4], bv[4]; uint32_t yv[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int cl = min(lane + 64 * k, p.C - 1);
+    if (HAS_A) av[k] = p.a[(size_t)m * p.C + cl];
+    if (HAS_Y) yv[k] = p.y[(size_t)m * p.ldy + cl];
+    gv[k] = p.gamma[cl]; bv[k] = p.beta[cl];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (HAS_A) ln_landed(av[k]);
+    if (HAS_Y) ln_landed(yv[k]);
+    ln_landed(gv[k]); ln_landed(bv[k]);
+  }
+  ln_landed(rmv);
+  if (p.seed_dev) { p.din_seed ^= sx; p.dout_seed ^= sx; }
   float s[4]; float sum = 0.f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int c = lane + 64 * k;
     float v = 0.f;
     if (c < p.C) {
-      if (p.a) v = p.a[(size_t)m * p.C + c];
-      if (p.y) {
-        float yy = bf2f(p.y[(size_t)m * p.ldy + c]);
+      if (HAS_A) v = av[k];
+      if (HAS_Y) {
+        float yy = bf2f((bf16_t)yv[k]);
         if (p.din_thresh) yy = drop_keep(p.din_seed, m, c, p.din_thresh) ? yy * p.din_scale : 0.f;
         v += yy;
       }
@@ -57,12 +83,12 @@ __global__ __launch_bounds__(256) void gt_layernorm_fwd_kernel(LnArgs p)
   for (int k = 0; k < 4; ++k) { const int c = lane + 64 * k; if (c < p.C) { const float d = s[k] - mean; var += d * d; } }
   const float rstd = rsqrtf(wave_sum(var) / (float)p.C + p.eps);
   if (lane == 0) { p.mean[m] = mean; p.rstd[m] = rstd; }
-  const float rm = p.rowmask ? p.rowmask[m] : 1.0f;
+  const float rm = p.rowmask ? rmv : 1.0f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int c = lane + 64 * k;
     if (c < p.C) {
-      float o = (s[k] - mean) * rstd * p.gamma[c] + p.beta[c];
+      float o = (s[k] - mean) * rstd * gv[k] + bv[k];
       if (p.relu) o = fmaxf(o, 0.f);
       if (p.dout_thresh) o = drop_keep(p.dout_seed, m, c, p.dout_thresh) ? o * p.dout_scale : 0.f;
       o *= rm;
@@ -78,24 +104,61 @@ struct LnBwdArgs {
   float* da; bf16_t* dy; int lddy;             // gradients wrt a (fp32) and y (bf16, dropout replayed)
   float* dgamma; float* dbeta;                 // accumulated (atomics)
   float* partials;                             // or: row blockIdx.x of [gridDim.x][2 C] receives this workgroup's sums (no atomics)
-  int rows_per_block;
 };
 
-// 16 waves, one row per wave at a time; gamma/beta partials are folded in LDS so that each channel gets ONE
-// atomic per workgroup (same-address float atomics serialise at L2, ~50 ns each: 32 rows per workgroup keeps both
-// the atomic chain and the per-wave row loop short).
-template <int LNB_WAVES>
+// LNB_WAVES waves x LNB_ROWS rows per wave (a workgroup takes LNB_WAVES * LNB_ROWS rows; wave w takes rows w, w + LNB_WAVES, ... in
+// that order); gamma/beta partials are folded in LDS so that each channel gets ONE atomic per workgroup (same-address float
+// atomics serialise at L2, ~50 ns each: 32 rows per workgroup keeps both the atomic chain and the per-wave row loop short).
+// The loads of ALL the wave's rows are in flight before the first row's arithmetic.
+template <int LNB_WAVES, int LNB_ROWS, bool HAS_A, bool HAS_Y, bool HAS_DF, bool HAS_DB>
 __global__ __launch_bounds__(64 * LNB_WAVES) void gt_layernorm_bwd_kernel(LnBwdArgs q)
 {
-  if (q.f.seed_dev) { const uint32_t x = *q.f.seed_dev; q.f.din_seed ^= x; q.f.dout_seed ^= x; }
   const LnArgs& p = q.f;
   __shared__ float sg[LNB_WAVES][256], sb[LNB_WAVES][256];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  constexpr int RPB = LNB_WAVES * LNB_ROWS;
+  const int m0 = blockIdx.x * RPB, m1 = min(p.R, m0 + RPB);
+  const uint32_t sx = *(p.seed_dev ? p.seed_dev : reinterpret_cast<const uint32_t*>(p.gamma));
+  float gv[4], bv[4];
+  float meanv[LNB_ROWS], rstdv[LNB_ROWS], rmv[LNB_ROWS], av[LNB_ROWS][4], dfv[LNB_ROWS][4];
+  uint32_t yv[LNB_ROWS][4], dbv[LNB_ROWS][4];
+#pragma unroll
+  for (int r = 0; r < LNB_ROWS; ++r) {
+    const int ml = min(m0 + w + r * LNB_WAVES, p.R - 1);
+    meanv[r] = p.mean[ml]; rstdv[r] = p.rstd[ml];
+    rmv[r] = *(p.rowmask ? p.rowmask + ml : p.gamma);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int cl = min(lane + 64 * k, p.C - 1);
+      if (HAS_A) av[r][k] = p.a[(size_t)ml * p.C + cl];
+      if (HAS_Y) yv[r][k] = p.y[(size_t)ml * p.ldy + cl];
+      if (HAS_DF) dfv[r][k] = q.dout_f32[(size_t)ml * p.C + cl];
+      if (HAS_DB) dbv[r][k] = q.dout_bf16[(size_t)ml * q.lddo + cl];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { const int cl = min(lane + 64 * k, p.C - 1); gv[k] = p.gamma[cl]; bv[k] = p.beta[cl]; }
+#pragma unroll
+  for (int r = 0; r < LNB_ROWS; ++r) {
+    ln_landed(meanv[r]); ln_landed(rstdv[r]); ln_landed(rmv[r]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (HAS_A) ln_landed(av[r][k]);
+      if (HAS_Y) ln_landed(yv[r][k]);
+      if (HAS_DF) ln_landed(dfv[r][k]);
+      if (HAS_DB) ln_landed(dbv[r][k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { ln_landed(gv[k]); ln_landed(bv[k]); }
+  const uint32_t din_seed = p.seed_dev ? p.din_seed ^ sx : p.din_seed, dout_seed = p.seed_dev ? p.dout_seed ^ sx : p.dout_seed;
   float accg[4] = {0, 0, 0, 0}, accb[4] = {0, 0, 0, 0};
-  const int m0 = blockIdx.x * q.rows_per_block, m1 = min(p.R, m0 + q.rows_per_block);
-  for (int m = m0 + w; m < m1; m += LNB_WAVES) {
-    const float mean = p.mean[m], rstd = p.rstd[m];
-    const float rm = p.rowmask ? p.rowmask[m] : 1.0f;
+#pragma unroll
+  for (int r = 0; r < LNB_ROWS; ++r) {
+    const int m = m0 + w + r * LNB_WAVES;
+    if (m >= m1) break;
+    const float mean = meanv[r], rstd = rstdv[r];
+    const float rm = p.rowmask ? rmv[r] : 1.0f;
     float xh[4], dn[4]; bool keep_in[4];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -103,23 +166,23 @@ __global__ __launch_bounds__(64 * LNB_WAVES) void gt_layernorm_bwd_kernel(LnBwdA
       const int c = lane + 64 * k;
       xh[k] = 0.f; dn[k] = 0.f; keep_in[k] = true;
       if (c < p.C) {
-        float v = p.a ? p.a[(size_t)m * p.C + c] : 0.f;
-        if (p.y) {
-          const bf16_t yraw = p.y[(size_t)m * p.ldy + c];
+        float v = HAS_A ? av[r][k] : 0.f;
+        if (HAS_Y) {
+          const bf16_t yraw = (bf16_t)yv[r][k];
           float yy = bf2f(yraw);
-          if (p.din_thresh) { keep_in[k] = drop_keep(p.din_seed, m, c, p.din_thresh); yy = keep_in[k] ? yy * p.din_scale : 0.f; }
+          if (p.din_thresh) { keep_in[k] = drop_keep(din_seed, m, c, p.din_thresh); yy = keep_in[k] ? yy * p.din_scale : 0.f; }
           if ((p.relu & 2) && !(yraw & 0x7fff)) keep_in[k] = false;      // y is a ReLU's output: no gradient through its zeros
           v += yy;
         }
         xh[k] = (v - mean) * rstd;
         float d = 0.f;
-        if (q.dout_f32) d += q.dout_f32[(size_t)m * p.C + c];
-        if (q.dout_bf16) d += bf2f(q.dout_bf16[(size_t)m * q.lddo + c]);
+        if (HAS_DF) d += dfv[r][k];
+        if (HAS_DB) d += bf2f((bf16_t)dbv[r][k]);
         d *= rm;
-        if (p.dout_thresh) d = drop_keep(p.dout_seed, m, c, p.dout_thresh) ? d * p.dout_scale : 0.f;
-        if ((p.relu & 1) && (xh[k] * p.gamma[c] + p.beta[c]) <= 0.f) d = 0.f;
+        if (p.dout_thresh) d = drop_keep(dout_seed, m, c, p.dout_thresh) ? d * p.dout_scale : 0.f;
+        if ((p.relu & 1) && (xh[k] * gv[k] + bv[k]) <= 0.f) d = 0.f;
         accg[k] += d * xh[k]; accb[k] += d;
-        dn[k] = d * p.gamma[c];
+        dn[k] = d * gv[k];
         s1 += dn[k]; s2 += dn[k] * xh[k];
       }
     }
@@ -876,8 +939,27 @@ extern "C" int gt_layernorm_fwd(const float* a, const void* y, int ldy, const fl
   LnArgs p;
   const int rc = fill_ln(p, a, y, ldy, gamma, beta, rowmask, out_f32, out_bf16, ldo, mean, rstd, R, C, eps, p_in, seed_in, p_out, seed_out, relu, seed_dev);
   if (rc) return rc;
-  hipLaunchKernelGGL(gt_layernorm_fwd_kernel, dim3((R + 3) / 4), dim3(256), 0, GT_ST(stream), p);
+  const dim3 grid((R + 3) / 4), block(256);
+  if (a && y) hipLaunchKernelGGL((gt_layernorm_fwd_kernel<true, true>), grid, block, 0, GT_ST(stream), p);
+  else if (a) hipLaunchKernelGGL((gt_layernorm_fwd_kernel<true, false>), grid, block, 0, GT_ST(stream), p);
+  else hipLaunchKernelGGL((gt_layernorm_fwd_kernel<false, true>), grid, block, 0, GT_ST(stream), p);
   GT_RET();
+}
+
+// One backward instantiation per (geometry, which of a / y / dout_f32 / dout_bf16 exist); fill_ln and the entries have made sure
+// that one of each pair does.
+template <int LNB_WAVES, int LNB_ROWS>
+static void launch_ln_bwd(const LnBwdArgs& q, void* stream)
+{
+  const dim3 grid((q.f.R + LNB_WAVES * LNB_ROWS - 1) / (LNB_WAVES * LNB_ROWS)), block(64 * LNB_WAVES);
+  const int have = (q.f.a ? 1 : 0) | (q.f.y ? 2 : 0) | (q.dout_f32 ? 4 : 0) | (q.dout_bf16 ? 8 : 0);
+  switch (have) {
+#define LN_BWD_CASE(F) \
+    case F: hipLaunchKernelGGL((gt_layernorm_bwd_kernel<LNB_WAVES, LNB_ROWS, ((F) & 1) != 0, ((F) & 2) != 0, ((F) & 4) != 0, ((F) & 8) != 0>), \
+                               grid, block, 0, GT_ST(stream), q); break;
+    LN_BWD_CASE(5) LN_BWD_CASE(6) LN_BWD_CASE(7) LN_BWD_CASE(9) LN_BWD_CASE(10) LN_BWD_CASE(11) LN_BWD_CASE(13) LN_BWD_CASE(14) LN_BWD_CASE(15)
+#undef LN_BWD_CASE
+  }
 }
 
 extern "C" int gt_layernorm_bwd(const float* a, const void* y, int ldy, const float* gamma, const float* beta, const float* rowmask,
@@ -895,19 +977,18 @@ extern "C" int gt_layernorm_bwd(const float* a, const void* y, int ldy, const fl
   q.da = da; q.dy = static_cast<bf16_t*>(dy); q.lddy = lddy; q.dgamma = dgamma; q.dbeta = dbeta; q.partials = nullptr;
   // geometry: 16 waves x 32 rows per workgroup (the gamma / beta partials are folded in LDS before the atomics) while
   // that still gives >= 64 workgroups; short inputs fall back to 4 waves x 16 rows so the chip is not left idle
-  if (R >= 64 * 32) {
-    q.rows_per_block = 32;
-    hipLaunchKernelGGL(gt_layernorm_bwd_kernel<16>, dim3((R + 31) / 32), dim3(1024), 0, GT_ST(stream), q);
-  } else {
-    q.rows_per_block = 16;
-    hipLaunchKernelGGL(gt_layernorm_bwd_kernel<4>, dim3((R + 15) / 16), dim3(256), 0, GT_ST(stream), q);
-  }
+  if (R >= 64 * 32) launch_ln_bwd<16, 2>(q, stream);
+  else launch_ln_bwd<4, 4>(q, stream);
   GT_RET();
 }
 
-// The partials form: ONE row per wave (every load of the launch in flight at once: the saved rows are cold by the time the backward
-// reads them), 16 rows per workgroup, the workgroup's dgamma | dbeta sums to row blockIdx.x of `partials` — no atomics, whose
-// same-address chains grow with the number of workgroups.
+// The partials form: 16 rows per workgroup, the workgroup's dgamma | dbeta sums to row blockIdx.x of `partials` — no atomics, whose
+// same-address chains grow with the number of workgroups.  4 waves x 4 rows (the 48 row loads of a wave in flight together, 8 KB of
+// fold LDS), not 16 waves x 1 row: alone on the machine the 16-wave form is the faster one (5.9 against 8.2 us at 3472 x 192, cold
+// operands), but a 1024-thread workgroup with 32 KB cannot share a CU with the decoder's whole-WaveNet workgroups, and inside the
+// step the 256-thread form is the one that shortens it (profiles/enc_latency_kernels.txt).
+constexpr int LNP_WAVES = 4, LNP_ROWS = 4;
+static_assert(LNP_WAVES * LNP_ROWS == 16, "gt_layernorm_bwd_partial_rows");
 extern "C" int gt_layernorm_bwd_partial_rows(int R) { return R > 0 ? (R + 15) / 16 : 0; }
 
 extern "C" int gt_layernorm_bwd_partials(const float* a, const void* y, int ldy, const float* gamma, const float* beta, const float* rowmask,
@@ -923,8 +1004,7 @@ extern "C" int gt_layernorm_bwd_partials(const float* a, const void* y, int ldy,
   if ((!dout_f32 && !dout_bf16) || !partials) return GT_E_INVAL;
   q.dout_f32 = dout_f32; q.dout_bf16 = static_cast<const bf16_t*>(dout_bf16); q.lddo = lddo;
   q.da = da; q.dy = static_cast<bf16_t*>(dy); q.lddy = lddy; q.dgamma = nullptr; q.dbeta = nullptr; q.partials = partials;
-  q.rows_per_block = 16;
-  hipLaunchKernelGGL(gt_layernorm_bwd_kernel<16>, dim3((R + 15) / 16), dim3(1024), 0, GT_ST(stream), q);
+  launch_ln_bwd<LNP_WAVES, LNP_ROWS>(q, stream);
   GT_RET();
 }
 
