@@ -195,6 +195,9 @@ PROTOTYPES = {
     "gt_mel_pack": (STATUS, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "gt_mel_spectrogram": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gt_yin_tile_frames": (c_int, []),
+    "gt_yin_f0": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
+                           c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 c_void_p = ctypes.c_void_p
 

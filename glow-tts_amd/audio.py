@@ -7,6 +7,9 @@ run by ONE HIP kernel (csrc/mel_front.hip: gt_mel_pack once, gt_mel_spectrogram 
                     `.stft_fn`; `mel_spectrogram(y)` is the reference's call, `mel_spectrogram(y, lengths)` the batched form whose
                     outputs are what `Trainer.step(y=, t_y=, energy=)` and `data.TextMelCollate` use.
   mel_filterbank    NumPy restatement of librosa.filters.mel's defaults (Slaney scale, triangular filters, norm="slaney").
+  YIN               the pitch contour of the reference's get_f0 (yin.compute_yin) for padded batches by ONE kernel (csrc/yin_front.hip:
+                    gt_yin_f0); `f0(y, lengths)` lines up with `TacotronSTFT.mel_spectrogram(y, lengths)`.
+  compute_yin       the reference's signature for one device waveform.
 
 Waveforms are fp32 in [-1, 1] or int16 (scaled by 1/32768 in the kernel = the reference's audio / max_wav_value).  There is no CPU
 path: a CPU tensor raises."""
@@ -154,3 +157,90 @@ class TacotronSTFT(nn.Module):
         lengths = lengths.to(y.device, non_blocking=True)
         mel, energy, _ = self.transform(y, lengths.to(torch.int32), F_max)
         return mel, 1 + lengths // hop, energy.unsqueeze(1)
+
+
+def _device_rows(y):
+    """waveform rows as the kernels take them (16-byte aligned rows of a 4-element pitch): y itself, or a zero-padded copy"""
+    if not y.is_cuda:
+        raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
+    if y.dim() != 2 or y.dtype not in (torch.float32, torch.int16):
+        raise ValueError(f"waveforms are [B, T] fp32 or int16, got {tuple(y.shape)} {y.dtype}")
+    B, T = y.shape
+    if y.stride(1) != 1 or y.stride(0) % 4 or y.data_ptr() % 16:
+        padded = y.new_zeros(B, (T + 3) // 4 * 4)
+        padded[:, :T] = y
+        y = padded
+    return y
+
+
+class YIN(nn.Module):
+    """The pitch contour of the reference's get_f0 (yin.compute_yin: frame 1024, hop 256, 50-600 Hz, threshold 0.1, two zero frames
+    on each side) for padded batches, by ONE HIP kernel (csrc/yin_front.hip: gt_yin_f0).  No parameters, no buffers.
+    A frame of digital silence is f0 = 0, harm = 1, argmin_f0 = 0 (the reference divides 0 / 0 there)."""
+
+    def __init__(self, sampling_rate=22050, frame_length=1024, hop_length=256, f0_min=50, f0_max=600, harm_thresh=0.1, pad_frames=None):
+        super().__init__()
+        self.sampling_rate, self.frame_length, self.hop_length = sampling_rate, frame_length, hop_length
+        self.f0_min, self.f0_max, self.harm_thresh = f0_min, f0_max, harm_thresh
+        self.tau_min, self.tau_max = int(sampling_rate / f0_max), int(sampling_rate / f0_min)
+        self.pad_frames = int((frame_length / hop_length) / 2) if pad_frames is None else pad_frames
+
+    def transform(self, y, wav_len, F_max, aux=False, lead=None):
+        """the kernel call: y [B, T] fp32 / int16 on the device, wav_len device int32 [B], F_max positions per output row ->
+        (f0 [B, F_max], harm or None, argmin_f0 or None); frame i of an utterance lands at position lead + i (lead: pad_frames),
+        every other position is 0.  No host synchronisation, capturable in a graph."""
+        y = _device_rows(y)
+        if wav_len.device != y.device or wav_len.dtype != torch.int32 or wav_len.numel() != y.shape[0]:
+            raise ValueError("wav_len must be int32 [B] on the waveforms' device")
+        B = y.shape[0]
+        f0 = torch.empty(B, F_max, dtype=torch.float32, device=y.device)
+        harm = torch.empty_like(f0) if aux else None
+        amin = torch.empty_like(f0) if aux else None
+        call.gt_yin_f0(y, int(y.dtype == torch.int16), y.stride(0), wav_len.contiguous(), B, F_max, self.frame_length, self.hop_length,
+                       self.tau_min, self.tau_max, float(self.sampling_rate), float(self.harm_thresh),
+                       self.pad_frames if lead is None else lead, f0, harm, amin, _lib.current_stream(y.device))
+        return f0, harm, amin
+
+    def f0(self, y, lengths=None, lengths_host=None, aux=False):
+        """y [B, T] (lengths: sample counts of the padded rows, default T) -> f0 [B, 1, F_max] with F_max = 1 + max(lengths) // hop,
+        chosen as TacotronSTFT.mel_spectrogram(y, lengths) chooses it (from the lengths where the host knows them, else from T with
+        no synchronisation): the contour lines up with that call's mel and energy, zero behind every utterance's frames.
+        aux=True: (f0, harm [B, 1, F_max], argmin_f0 [B, 1, F_max])."""
+        if not y.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
+        B, T = y.shape
+        if lengths is None:
+            wav_len = torch.full((B,), T, dtype=torch.int32, device=y.device)
+            F_max = 1 + T // self.hop_length
+        else:
+            if lengths_host is None and not lengths.is_cuda:
+                lengths_host = lengths.tolist()
+            if lengths_host is not None:
+                lengths_host = [int(v) for v in lengths_host]
+                if len(lengths_host) != B or max(lengths_host) > T:
+                    raise ValueError(f"lengths {lengths_host} do not fit waveforms {tuple(y.shape)}")
+                F_max = 1 + max(lengths_host) // self.hop_length
+            else:
+                F_max = 1 + T // self.hop_length
+            wav_len = lengths.to(y.device, non_blocking=True).to(torch.int32)
+        f0, harm, amin = self.transform(y, wav_len, F_max, aux=aux)
+        if aux:
+            return f0.unsqueeze(1), harm.unsqueeze(1), amin.unsqueeze(1)
+        return f0.unsqueeze(1)
+
+    forward = f0
+
+
+def compute_yin(sig, sr, w_len=512, w_step=256, f0_min=100, f0_max=500, harmo_thresh=0.1):
+    """The reference's yin.compute_yin (same signature and defaults) for ONE device waveform sig [L] (fp32 or int16):
+    -> (pitches, harmonic_rates, argmins, times), tensors of len(range(0, L - w_len, w_step)) entries, unpadded.  The kernel takes
+    w_len = 1024, w_step = 256 and tau_max = int(sr / f0_min) <= 512; any other geometry (the defaults included) raises."""
+    if sig.dim() != 1:
+        raise ValueError(f"compute_yin takes one waveform [L], got {tuple(sig.shape)}")
+    L = sig.shape[0]
+    n = len(range(0, L - w_len, w_step))
+    mod = YIN(sr, w_len, w_step, f0_min, f0_max, harmo_thresh, pad_frames=0)
+    wav_len = torch.full((1,), L, dtype=torch.int32, device=sig.device)
+    f0, harm, amin = mod.transform(sig.unsqueeze(0), wav_len, max(n, 1), aux=True)
+    times = torch.arange(n, dtype=torch.float32, device=sig.device) * (w_step / float(sr))
+    return f0[0, :n], harm[0, :n], amin[0, :n], times

@@ -128,8 +128,9 @@ class TextAudioCollate:
     (text, wave, spk_embed, emo, emo_cartesian, f0 [1, F], energy [1, F] or None, lid).  Same sorting (by text length, descending),
     same field order: (text_padded, input_lengths, wav_padded int16 [B, L_max], wav_lengths in SAMPLES) plus, for 8-field items,
     (spk_embeds, emos, emo_cartesians, f0_padded, energy_padded, lid).  The mel and the energy contour come from the device
-    (audio.TacotronSTFT.mel_spectrogram(wav_padded, wav_lengths)); f0 stays an item field, padded to the 1 + L_max // hop frames
-    that call returns, and energy_padded is None when the items carry none.  L_max is rounded up to 4 samples (the kernel's pitch)."""
+    (audio.TacotronSTFT.mel_spectrogram(wav_padded, wav_lengths)), and so does the pitch contour (audio.YIN.f0(wav_padded,
+    wav_lengths)) when the items carry none: f0_padded and energy_padded are None where the first item's field is None, else the
+    item fields padded to the 1 + L_max // hop frames those calls return.  L_max is rounded up to 4 samples (the kernels' pitch)."""
 
     def __init__(self, pin_memory=False, hop_length=256):
         self.pin, self.hop = pin_memory, hop_length
@@ -154,7 +155,7 @@ class TextAudioCollate:
             spk = self._new(n, batch[0][2].numel(), dtype=torch.float32)
             emos, lid = torch.zeros(n, dtype=torch.long), torch.zeros(n, dtype=torch.long)
             cart = self._new(n, 3, dtype=torch.float32)
-            f0 = self._new(n, 1, max_t, dtype=torch.float32)
+            f0 = self._new(n, 1, max_t, dtype=torch.float32) if batch[0][5] is not None else None
             energy = self._new(n, 1, max_t, dtype=torch.float32) if batch[0][6] is not None else None
         for i, k in enumerate(order.tolist()):
             item = batch[k]
@@ -162,7 +163,8 @@ class TextAudioCollate:
             wav_lengths[i] = item[1].numel()
             if full:
                 spk[i] = item[2]; emos[i] = item[3]; cart[i] = item[4]
-                f0[i, :, :item[5].size(1)] = item[5]
+                if f0 is not None:
+                    f0[i, :, :item[5].size(1)] = item[5]
                 if energy is not None:
                     energy[i, :, :item[6].size(1)] = item[6]
                 lid[i] = item[7]

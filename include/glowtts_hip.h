@@ -983,6 +983,34 @@ int gt_mel_spectrogram(const void* wav, int is_i16, int ld_wav, const int32_t* w
                        const void* packed, int n_fft, int hop, int win, int n_mel, float clip,
                        float* mel, float* energy, float* mag, void* stream);
 
+/* ---- device pitch front end (csrc/yin_front.hip): waveforms -> the YIN f0 contour in one kernel -----------------
+ * The reference's yin.compute_yin (yin.py:70-119) as get_f0 calls it, applied to every utterance of a padded batch on its own, in
+ * fp32 with direct differences.  Utterance b with L = wav_len[b] samples (clamped to ld_wav) has n_b = ceil((L - w_len) / hop)
+ * analysis frames for L > w_len, else 0; frame i is samples hop i .. hop i + w_len - 1 (not centred, not reflected), and nothing at
+ * or beyond index L is read.  Per frame
+ *   d[t] = sum_{j = 0}^{w_len - 1 - t} (x[j] - x[j + t])^2  (t < tau_max),   c[0] = 1,  c[t] = d[t] t / sum_{1..t} d,
+ *   p    = the first t in [tau_min, tau_max) with c[t] < thresh, then forward while t + 1 < tau_max and c[t + 1] < c[t]; 0 if none,
+ * and at position lead + i of the [B, F_max] outputs
+ *   f0 = sr / p (0 when p = 0),   harm = c[p] (min c when p = 0),   argmin_f0 = sr / argmin c if argmin c > tau_min, else 0.
+ * Every other position (the first `lead`, everything from lead + n_b on) is written as 0; lead = 2 is get_f0's padding.  harm and
+ * argmin_f0 may be NULL: not stored, f0 bit-identical.
+ * ONE departure from the reference: a lag whose running sum of d is 0 (digital silence) gets c = 1 where the reference divides
+ * 0 / 0 into NaN, so a silent frame is f0 = 0, argmin_f0 = 0, harm = 1.
+ * Asynchronous, no allocation, no atomics, capturable in a graph; the summation order of an output depends on its (hop, lag) alone,
+ * not on B, F_max or the tile: a batch row is bit-identical to the utterance computed alone.
+ *   wav      [B rows, pitch ld_wav elements] fp32 in [-1, 1], or int16 when is_i16 != 0 (scaled by 1/32768 in the kernel).
+ *   wav_len  device int32 [B].
+ * Refusals, before any launch and in this order: NULL wav / wav_len / f0, B outside [1, GT_MEL_MAX_B], F_max outside
+ * [1, GT_MEL_MAX_FRAMES], ld_wav <= 0, lead < 0, w_len <= 0, hop <= 0, tau_min < 1, tau_max <= tau_min, sr not > 0: GT_E_INVAL;
+ * w_len != 1024, hop != 256 or tau_max > GT_YIN_MAX_TAU: GT_E_UNSUPPORTED; wav, f0, harm, argmin_f0 not 16-byte (wav_len: 4-byte)
+ * aligned, ld_wav no multiple of 4: GT_E_ALIGN.
+ * gt_yin_tile_frames: frames per workgroup (a tile past an utterance's end costs a zero fill). */
+#define GT_YIN_MAX_TAU 512
+int gt_yin_tile_frames(void);
+int gt_yin_f0(const void* wav, int is_i16, int ld_wav, const int32_t* wav_len, int B, int F_max,
+              int w_len, int hop, int tau_min, int tau_max, float sr, float thresh, int lead,
+              float* f0, float* harm, float* argmin_f0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
