@@ -8,26 +8,13 @@ backward mirrors what autograd derives for the reference modules:
 """
 import torch
 
-from . import _lib
+from . import _lib, devstate
 from ._lib import call
 from .ops import KERNEL_TIMER, RowsCtx, conv_rows, grad_accumulator, seed_word, zeros_small  # noqa: F401
 
-_SCRATCH = {}
-_SCRATCH_KEEP = []
-
-
 def _scratch(name, nbytes, device):
-    """Grow-only device scratch (wgrad partial slabs etc.), one per purpose and device.  A captured graph replays into the buffer it
-    was captured with: the capture holds a reference to it (wgrad.capture_keep), so an outgrown buffer lives as long as those graphs."""
-    from . import wgrad
-    key = (name, str(device))
-    buf = _SCRATCH.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
-        _SCRATCH[key] = buf
-    if buf.is_cuda and torch.cuda.is_current_stream_capturing() and not wgrad.capture_keep(buf):
-        _SCRATCH_KEEP.append(buf)              # a capture nobody owns: for the life of the process
-    return buf
+    """Grow-only device scratch (wgrad partial slabs etc.), one per purpose and device (devstate.DeviceState.scratch)."""
+    return devstate.get(device).scratch(name, nbytes)
 
 
 def _st(dev):
@@ -130,17 +117,11 @@ def _fused_ok(wn):
     return True
 
 
-_CUS = {}                    # device -> compute units (a property of the hardware, read once)
-
-
 def _stack_pays(R, n, dev):
     """One launch per WaveNet (csrc/wn_stack.hip) owns 64 - 4 (n - 1) rows per workgroup where the per-layer kernels own 64: more
     workgroups for the same rows.  That is free while they fit the CUs at once (cfg 2: 188 instead of 152 of 256) and loses when it
     costs an extra round of workgroups (cfg 3's longest batches: 268 instead of 218)."""
-    key = str(dev)
-    if key not in _CUS:
-        _CUS[key] = torch.cuda.get_device_properties(dev).multi_processor_count
-    cus = _CUS[key]
+    cus = devstate.get(dev).cus                # compute units: a property of the hardware, read once
     own = 64 - 4 * (n - 1)
     rounds = lambda rows: -(-(-(-R // rows)) // cus)
     return rounds(own) <= rounds(64)

@@ -5,7 +5,7 @@ row mask); all arithmetic of the hot path happens in libglowtts_hip.so.
 """
 import torch
 
-from . import _lib
+from . import _lib, devstate
 from ._lib import call
 
 HALO = 2  # GT_HALO in include/glowtts_hip.h
@@ -94,18 +94,11 @@ class KernelStamps:
         b = self.buf[: 2 * n * self.per_step].cpu().view(n, self.per_step, 2)
         return (b[:, :, 1] - b[:, :, 0])
 
-_SEED = {}
-
 
 def seed_word(device):
     """Device-resident uint32 mixed into every dropout seed (seed_dev of the C-ABI).  Bumping it (even
     from inside a captured HIP graph) gives fresh dropout masks without changing any kernel argument."""
-    key = str(device)
-    t = _SEED.get(key)
-    if t is None:
-        t = torch.zeros(1, dtype=torch.int32, device=device)
-        _SEED[key] = t
-    return t
+    return devstate.get(device).seed
 
 
 class Marks:
@@ -139,25 +132,18 @@ def bump_seed(device):
     seed_word(device).add_(0x632BE5AB)           # odd constant: full-period walk over 2^32
 
 
-# ---- per-step arena of small zero-initialised accumulators --------------------------------------------
-# The backward needs ~150 tiny zeroed buffers per step (atomicAdd targets: LayerNorm gamma/beta, ActNorm
-# logs/bias, InvConv dW, relative-position embeddings ...): one fill of the arena at step start instead
-# of one fill launch each.  Opt-in (train.Trainer): outside a step `zeros_small` is plain torch.zeros.
-_ARENA = {}
-ARENA_BYTES = 1 << 20
-
-
+# ---- the step's two pre-zeroed arenas (devstate.ZeroArena) ---------------------------------------------
+# small: the ~150 tiny zeroed buffers the backward needs per step (atomicAdd targets: LayerNorm gamma/beta, ActNorm logs/bias, InvConv dW,
+# relative-position embeddings ...); big: the per-layer buffers that kernels only partly write (attention outputs and their gradients:
+# halo rows must read as zero, 18 at cfg 2).  ONE fill per step instead of one each; opt-in (train.Trainer): torch.zeros outside a step.
 def arena_begin(device):
     """Zero the arena and hand out slices of it until the next arena_begin (call once per training step,
     after the previous step's optimizer has consumed its gradients)."""
-    key = str(device)
-    a = _ARENA.get(key)
-    if a is None:
-        a = {"buf": torch.zeros(ARENA_BYTES, dtype=torch.uint8, device=device), "off": 0, "on": True}
-        _ARENA[key] = a
-    else:
-        a["buf"].zero_()
-    a["off"], a["on"] = 0, True
+    devstate.get(device).small.begin()
+
+
+def big_begin(device):
+    devstate.get(device).big.begin()
 
 
 def step_head(device, extra=None, bump=True):
@@ -170,21 +156,12 @@ def step_head(device, extra=None, bump=True):
         if extra is not None:
             extra.zero_()
         return
-    key = str(device)
+    st = devstate.get(device)
     regions = []
-    a = _ARENA.get(key)
-    if a is None:
-        arena_begin(device)                            # first use: allocates (zeroed)
-    else:
-        regions.append((a["buf"].data_ptr(), ARENA_BYTES))
-        a["off"], a["on"] = 0, True
-    b = _BIG.get(key)
-    if b is None:
-        big_begin(device)
-    else:
-        n = min(BIG_BYTES, (b["used"] + 4095) & ~4095) if b["used"] else BIG_BYTES
-        regions.append((b["buf"].data_ptr(), n))       # only what the previous step dirtied
-        b["off"], b["on"] = 0, True
+    for ar in (st.small, st.big):
+        n = ar.open()                                  # 0 on first use: allocates (zeroed); big: only what earlier steps dirtied
+        if n:
+            regions.append((ar.buf.data_ptr(), n))
     if extra is not None and extra.numel():
         nb = extra.numel() * extra.element_size()
         if nb % 16 or extra.data_ptr() % 16 or not extra.is_contiguous():
@@ -196,63 +173,22 @@ def step_head(device, extra=None, bump=True):
         args.ptr[i], args.bytes[i] = p, n
     args.n = len(regions)
     if bump:
-        args.seed_word, args.seed_inc = seed_word(device).data_ptr(), 0x632BE5AB
+        args.seed_word, args.seed_inc = st.seed.data_ptr(), 0x632BE5AB
     call.gt_step_zero(args, _lib.current_stream(device))
 
 
 def arena_end(device):
-    a = _ARENA.get(str(device))
-    if a is not None:
-        a["on"] = False
-    b = _BIG.get(str(device))
-    if b is not None:
-        b["on"] = False
-
-
-# A second, larger pre-zeroed region for the per-layer buffers that kernels only partly write (attention outputs and their
-# gradients: halo rows must read as zero): ONE fill per training step instead of one per buffer (18 launches at cfg 2).
-_BIG = {}
-BIG_BYTES = 96 << 20
-
-
-def big_begin(device):
-    key = str(device)
-    b = _BIG.get(key)
-    if b is None:
-        b = {"buf": torch.zeros(BIG_BYTES, dtype=torch.uint8, device=device), "off": 0, "on": True, "used": 0}
-        _BIG[key] = b
-    else:
-        n = min(BIG_BYTES, (b["used"] + 4095) & ~4095) if b["used"] else BIG_BYTES
-        b["buf"][:n].zero_()                          # only what the previous step dirtied
-    b["off"], b["on"] = 0, True
+    st = devstate.get(device)
+    st.small.close(); st.big.close()
 
 
 def zeros_big(shape, dtype, device):
     """Zeroed tensor: a slice of the step's pre-zeroed region inside a Trainer step, torch.zeros otherwise."""
-    n = 1
-    for d in shape:
-        n *= int(d)
-    b = _BIG.get(str(device))
-    nbytes = (n * torch.empty(0, dtype=dtype).element_size() + 255) & ~255
-    if b is None or not b["on"] or b["off"] + nbytes > BIG_BYTES:
-        return torch.zeros(shape, dtype=dtype, device=device)
-    off = b["off"]
-    b["off"] = off + nbytes
-    b["used"] = max(b["used"], b["off"])
-    return b["buf"][off:off + nbytes].view(dtype)[:n].view(shape)
+    return devstate.get(device).big.zeros(shape, dtype)
 
 
 def zeros_small(shape, dtype, device):
-    n = 1
-    for d in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)):
-        n *= int(d)
-    a = _ARENA.get(str(device))
-    nbytes = (n * torch.empty(0, dtype=dtype).element_size() + 255) & ~255
-    if a is None or not a["on"] or nbytes > 65536 or a["off"] + nbytes > ARENA_BYTES:
-        return torch.zeros(shape, dtype=dtype, device=device)
-    off = a["off"]
-    a["off"] = off + nbytes
-    return a["buf"][off:off + nbytes].view(dtype)[:n].view(shape)
+    return devstate.get(device).small.zeros(shape, dtype)
 
 
 class RowsConfig:

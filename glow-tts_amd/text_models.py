@@ -14,7 +14,7 @@ import os
 import torch
 from torch import nn
 
-from . import _lib, encoder_impl, ops
+from . import _lib, devstate, encoder_impl, ops
 from ._lib import call
 from . import monotonic_align
 from .attentions import Encoder
@@ -360,24 +360,12 @@ def mle_loss(z, m, logs, logdet, mask):
 
 # (whether the encoder / the predictors run as parallel branches is per-model state: ops.RowsConfig.encoder_stream / .predictor_branch /
 # .energy_on_main of model.rows_cfg)
-_ENC_STREAMS = {}            # device -> the branch's stream (one per device and process: streams are a device resource, not model state)
-
-
-_FRONT_STREAMS = {}
-
-
 def _front_stream(dev):
-    key = str(dev)
-    if key not in _FRONT_STREAMS:
-        _FRONT_STREAMS[key] = torch.cuda.Stream(device=dev)
-    return _FRONT_STREAMS[key]
+    return devstate.get(dev).stream("front")
 
 
 def _encoder_stream(dev):
-    key = str(dev)
-    if key not in _ENC_STREAMS:
-        _ENC_STREAMS[key] = torch.cuda.Stream(device=dev)
-    return _ENC_STREAMS[key]
+    return devstate.get(dev).stream("encoder")   # the branch's stream: one per device and process (a device resource, not model state)
 
 
 class FlowGenerator(nn.Module):

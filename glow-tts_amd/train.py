@@ -293,6 +293,9 @@ class FlatAdamW:
         self._launch(lo, hi)
         self._early = (lo, hi)
 
+    def cancel_early(self):
+        self._early = None   # the step that called step_early() was abandoned (a capture that failed): the next one starts from scratch
+
     def step(self):
         if self._early is None:
             self._begin()
@@ -733,14 +736,18 @@ class Trainer:
         finally:
             self.cfg.prebuilt.clear()
 
+    def _capture_stream(self):
+        """ONE capture stream per trainer: the parameters' AccumulateGrad nodes stay bound to the stream of the first warm-up"""
+        if getattr(self, "_cap_stream", None) is None:
+            self._cap_stream = torch.cuda.Stream()
+        return self._cap_stream
+
     def _capture_with(self, static, lh, ctxs):
         ids = static[0]
         cond = static[4]
         static = static[:4]
         cur = torch.cuda.current_stream()
-        if getattr(self, "_cap_stream", None) is None:   # ONE capture stream per trainer: the parameters' AccumulateGrad
-            self._cap_stream = torch.cuda.Stream()       # nodes stay bound to the stream of the first warm-up
-        side = self._cap_stream
+        side = self._capture_stream()
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             # warm-up (one-time attribute calls, scratch growth, pinned staging pools) WITHOUT side effects: no
@@ -762,37 +769,49 @@ class Trainer:
         # capture on the stream the warm-up ran on: autograd's AccumulateGrad nodes remember the stream they were
         # created on, and work they launched on another stream would stay outside the captured graph
         from . import wgrad
-        tables = wgrad.table_arena_begin(ids.device) # the captured weight-gradient kernels' job tables: outside the graph's pool
-        g1 = torch.cuda.CUDAGraph()
-        if not self.split and not self.buckets.collect:
-            with torch.cuda.graph(g1, stream=side, capture_error_mode=CAPTURE_MODE):
-                out = self._step_impl(*static, lengths_host=lh, cond=cond, collectives=False)
-            graphs = (g1,)
-        elif not self.split:                         # one backward, then the whole buffer on the wire, then the optimizer
-            with torch.cuda.graph(g1, stream=side, capture_error_mode=CAPTURE_MODE):
-                out = self._fwd_bwd(*static, lengths_host=lh, cond=cond)
-            g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g2, stream=side, pool=g1.pool(), capture_error_mode=CAPTURE_MODE):
-                self._optim(ids.device)
-            graphs = (g1, g2)
-        else:
-            with torch.cuda.graph(g1, stream=side, capture_error_mode=CAPTURE_MODE):
-                out = self._phase1(*static, lengths_host=lh, cond=cond)
-            g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g2, stream=side, pool=g1.pool(), capture_error_mode=CAPTURE_MODE):
-                self._phase2()
-            g3 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g3, stream=side, pool=g1.pool(), capture_error_mode=CAPTURE_MODE):
-                self._optim(ids.device)
-            graphs = (g1, g2, g3)
-        self.n_captures += 1
-        wgrad.sync_uploads(ids.device)               # fill the tables the captured kernels read (once, not per replay)
-        wgrad.table_arena_end(ids.device)
+        with wgrad.capture_scope(ids.device) as tables:      # the weight-gradient kernels' job tables: outside the graph's pool
+            g1 = torch.cuda.CUDAGraph()
+            if not self.split and not self.buckets.collect:
+                with torch.cuda.graph(g1, stream=side, capture_error_mode=CAPTURE_MODE):
+                    out = self._step_impl(*static, lengths_host=lh, cond=cond, collectives=False)
+                graphs = (g1,)
+            elif not self.split:                         # one backward, then the whole buffer on the wire, then the optimizer
+                with torch.cuda.graph(g1, stream=side, capture_error_mode=CAPTURE_MODE):
+                    out = self._fwd_bwd(*static, lengths_host=lh, cond=cond)
+                g2 = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g2, stream=side, pool=g1.pool(), capture_error_mode=CAPTURE_MODE):
+                    self._optim(ids.device)
+                graphs = (g1, g2)
+            else:
+                with torch.cuda.graph(g1, stream=side, capture_error_mode=CAPTURE_MODE):
+                    out = self._phase1(*static, lengths_host=lh, cond=cond)
+                g2 = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g2, stream=side, pool=g1.pool(), capture_error_mode=CAPTURE_MODE):
+                    self._phase2()
+                g3 = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g3, stream=side, pool=g1.pool(), capture_error_mode=CAPTURE_MODE):
+                    self._optim(ids.device)
+                graphs = (g1, g2, g3)
+            self.n_captures += 1
         ctxs = dict(ctxs or {}, _keep=tables)        # wgrad.CaptureKeep: lives (and is released) with this key's graphs
         # how the captured step packs the decoder's weights: its head packs everything (False) or relies on the previous step's
         # end having packed the decoder's (True); its own end packs them for the next step or not
         ctxs["_head_rest"], ctxs["_tail_packed"] = self._head_rest, self._tail_packed
         return graphs, static + [cond], out, ctxs
+
+    def _abandon_capture(self, device, err):
+        """A capture failed: graph mode goes off and the host state the aborted pass may have left half-way is put back, so that the
+        eager step that follows starts like any other.  (wgrad.capture_scope has closed itself and _capture_with restored what the
+        warm-ups did; Adam's step word and the kernel stamps' slot counter live on the device: an aborted pass never moved them.)"""
+        import warnings
+        from . import devstate
+        warnings.warn(f"HIP graph capture of the training step failed ({err!r}); continuing with eager launches")
+        self.graph_mode = False
+        self.opt.cancel_early()                      # the pass stopped between the decoder's flush and the optimizer
+        self._dec_fresh_version, self._tail_packed, self._head_rest = None, False, False      # the next head packs every weight
+        self.model.__dict__.pop("_prepared_by_trainer", None); self.model.__dict__.pop("_prepare_side", None)
+        self.cfg.prebuilt.clear()
+        devstate.get(device).drop_streams()          # they may be left in capture state by the aborted capture: start over with fresh ones
 
     def _rows_key(self, Tx, Ty, lh):
         """the rounded ragged row counts (text, squeezed mel, frame rows) of a batch padded to (Tx, Ty): the head of its graph key"""
@@ -844,13 +863,7 @@ class Trainer:
             try:
                 cap = self._capture(ids, t_x, y, t_y, lh, cond)
             except Exception as e:                   # e.g. an allocation the capture refuses: keep training, eagerly
-                import warnings
-                warnings.warn(f"HIP graph capture of the training step failed ({e!r}); continuing with eager launches")
-                self.graph_mode = False
-                # auxiliary streams that had joined the aborted capture may be left in capture state: start over with fresh ones
-                from . import text_models, wgrad
-                text_models._ENC_STREAMS.clear(); wgrad._SIDE.clear(); wgrad._PENDING.clear()
-                self.cfg.prebuilt.clear()
+                self._abandon_capture(ids.device, e)
                 return None, (ids, y, cond)
             self._captured[key] = cap
             while len(self._captured) > self.max_graphs:
@@ -901,9 +914,7 @@ class Trainer:
             # a segmentation fault (cfg 5, round 3; the round-2 "four capture streams" crash was the same class: a stream the
             # capture had to wait for without it ever having joined the capture).
             cur = torch.cuda.current_stream()
-            if getattr(self, "_cap_stream", None) is None:
-                self._cap_stream = torch.cuda.Stream()
-            side = self._cap_stream
+            side = self._capture_stream()
             side.wait_stream(cur)
             with torch.cuda.stream(side):
                 out = self._step_impl(ids, t_x, y, t_y, lh, cond=cond)

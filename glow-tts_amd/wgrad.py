@@ -8,12 +8,14 @@ rows alive, runs only the data-gradient chain, and at the end `WgradQueue.flush(
 gradients with one launch per tap count (`gt_conv_wgrad_batched`) and ALL weight-norm Jacobians / bias
 gradients with one more (`gt_weightnorm_bwd_batched`).
 """
+import contextlib
 import os
+import types
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, devstate
 from ._lib import call
 
 JOB = np.dtype([("X", "u8"), ("dY", "u8"), ("part", "u8"), ("part_bias", "u8"), ("ldx", "i4"), ("ldy", "i4"), ("R", "i4"),
@@ -44,11 +46,9 @@ FORCE_SLABS = int(os.environ.get("GT_WGRAD_SLABS", "0"))           # dev knob: t
 # backward: mostly small kernels that leave CUs idle); join() makes the current stream wait for them and must run
 # before anything reads the gradients (train.GradBuckets.gather does).
 ASYNC = os.environ.get("GT_WGRAD_ASYNC", "0") != "0"   # measured: a third concurrent stream costs more than it hides
-_SIDE = {}
-_PENDING = set()
 _ACTIVE = []            # stack of open queues
 _KEEP = []              # tables referenced by captured graphs whose queue had no owning module (site)
-_SCRATCH = {}
+_SCOPE = None           # the trainer-owned capture in progress (capture_scope): its table arena, pending table uploads and CaptureKeep
 
 
 _POOL = []              # pinned staging buffers set aside (outside capture) for use inside a graph capture
@@ -58,11 +58,6 @@ _POOL_N, _POOL_BYTES = 64, 1 << 18
 def _fill_pool():
     while len(_POOL) < _POOL_N:
         _POOL.append(torch.empty(_POOL_BYTES, dtype=torch.uint8).pin_memory())
-
-
-_PENDING_UPLOADS = []        # (device table, pinned host copy) of the flushes recorded by the graph capture in progress
-_TABLE_ARENA = {}            # device -> {"buf", "off"}: where a capture's tables live (see _flush)
-_CAPTURE_KEEP = None         # while a trainer captures a step: what that capture's graphs read (pinned staging buffers, tables, scratch)
 
 
 class CaptureKeep(list):
@@ -78,42 +73,38 @@ class CaptureKeep(list):
         self.clear()
 
 
-def table_arena_begin(dev, nbytes=8 << 20):
-    """Before a graph capture (outside it): a buffer for the capture's weight-gradient tables.  Returns the CaptureKeep of this
-    capture (the arena is its first element): the caller keeps it exactly as long as the graph and calls .release() on eviction."""
-    global _CAPTURE_KEEP
-    buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    _TABLE_ARENA[str(dev)] = {"buf": buf, "off": 0}
-    _PENDING_UPLOADS.clear()                          # nothing left over from a capture that failed half-way
-    _CAPTURE_KEEP = CaptureKeep([buf])
-    return _CAPTURE_KEEP
-
-
-def table_arena_end(dev):
-    global _CAPTURE_KEEP
-    _TABLE_ARENA.pop(str(dev), None)
-    _CAPTURE_KEEP = None
+@contextlib.contextmanager
+def capture_scope(dev, nbytes=8 << 20):
+    """`with capture_scope(dev) as keep:` around a trainer's graph captures; entered and left OUTSIDE capture.  Inside, the
+    captured weight-gradient kernels' job tables live in a buffer allocated here (outside the graph's memory pool) and capture_keep()
+    ties objects to `keep`, the capture's CaptureKeep: the caller keeps it exactly as long as the graphs and calls .release() on
+    eviction.  Leaving fills the tables (once: nothing else ever writes them); leaving on an exception drops them and releases `keep`."""
+    global _SCOPE
+    arena = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    sc = _SCOPE = types.SimpleNamespace(dev=dev, arena=arena, off=0, uploads=[], keep=CaptureKeep([arena]))
+    try:
+        yield sc.keep
+        assert not (arena.is_cuda and torch.cuda.is_current_stream_capturing())
+        for dst, host in sc.uploads:
+            dst.copy_(host, non_blocking=True)
+        if sc.uploads and arena.is_cuda:
+            torch.cuda.current_stream(dev).synchronize()
+    except BaseException:
+        sc.keep.release()                    # the pinned staging buffers go back to the pool
+        raise
+    finally:
+        sc.uploads.clear()
+        _SCOPE = None
 
 
 def capture_keep(obj):
     """Tie obj's lifetime to the graph capture in progress (a scratch buffer the captured kernels write into, say); False if no
     trainer-owned capture is open."""
-    if _CAPTURE_KEEP is not None:
-        if not any(o is obj for o in _CAPTURE_KEEP):
-            _CAPTURE_KEEP.append(obj)
+    if _SCOPE is not None:
+        if not any(o is obj for o in _SCOPE.keep):
+            _SCOPE.keep.append(obj)
         return True
     return False
-
-
-
-def sync_uploads(dev):
-    """Right after a graph capture (outside it): fill the tables its weight-gradient kernels read; nothing else ever writes them."""
-    if _PENDING_UPLOADS:
-        assert not torch.cuda.is_current_stream_capturing()
-        for dst, host in _PENDING_UPLOADS:
-            dst.copy_(host, non_blocking=True)
-        _PENDING_UPLOADS.clear()
-        torch.cuda.current_stream(dev).synchronize()
 
 
 def choose_slabs(base_tiles, R, part_bytes):
@@ -140,18 +131,15 @@ def single_slabs(R, Cin, Cout, taps):
 
 
 def _side_stream(dev):
-    key = str(dev)
-    if key not in _SIDE:
-        _SIDE[key] = torch.cuda.Stream(device=dev)
-    return _SIDE[key]
+    return devstate.get(dev).stream("wgrad_side")
 
 
 def join(dev):
     """Current stream waits for every asynchronously flushed queue of this device."""
-    key = str(dev)
-    if key in _PENDING:
-        torch.cuda.current_stream(dev).wait_stream(_SIDE[key])
-        _PENDING.discard(key)
+    st = devstate.get(dev)
+    if st.pending:
+        torch.cuda.current_stream(dev).wait_stream(st.stream("wgrad_side"))
+        st.pending = False
 
 
 def active():
@@ -161,19 +149,7 @@ def active():
 def _scratch(dev, nbytes):
     """Partial-sum workspace of a flush, one per (device, stream the flush runs on): flushes on different streams (the
     decoder's and the text encoder's backward run concurrently, ops.RowsConfig.encoder_stream) must not share it."""
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
-    buf = _SCRATCH.get(key)
-    if buf is None or buf.numel() < nbytes:
-        # A captured step has the address of the buffer it was captured with baked into its kernel arguments, and a later capture
-        # (another row bucket, more slabs) may need a bigger one: the outgrown buffer must stay allocated for as long as any graph
-        # can replay into it — freed, its pages go back to the allocator and the next replay of the older graph writes its partial
-        # sums over whoever owns them then.  Every capture therefore holds a reference to the buffer it used (capture_keep below):
-        # an outgrown buffer lives exactly as long as the graphs that replay into it, and no longer.
-        buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        _SCRATCH[key] = buf
-    if dev.type == "cuda" and torch.cuda.is_current_stream_capturing() and not capture_keep(buf):
-        _KEEP.append(buf)                             # a capture nobody owns (no trainer): keep it for the life of the process
-    return buf
+    return devstate.get(dev).scratch("wgrad_flush", nbytes, per_stream=True)
 
 
 def _grad_out(param):
@@ -321,7 +297,7 @@ class WgradQueue:
                         t.record_stream(side)
             with torch.cuda.stream(side):
                 self._flush()
-            _PENDING.add(str(dev))
+            devstate.get(dev).pending = True
         else:
             self._flush()
 
@@ -363,13 +339,13 @@ class WgradQueue:
                 # The tables of a captured step never change (the graph's buffers are static).  With a table arena open (the
                 # trainer allocates it BEFORE the capture, outside the graph's memory pool — a pool block would be reused by other
                 # tensors of the step and clobbered at every replay) they are copied ONCE, right after the capture
-                # (sync_uploads), instead of by a memcpy node that every replay runs (12 of them per step at cfg 2).
-                ar = _TABLE_ARENA.get(str(dev))
+                # (when capture_scope is left), instead of by a memcpy node that every replay runs (12 of them per step at cfg 2).
+                sc = _SCOPE
                 nb = (raw.size + 255) & ~255
-                if ar is not None and ar["off"] + nb <= ar["buf"].numel():
-                    dst = ar["buf"][ar["off"]:ar["off"] + raw.size]
-                    ar["off"] += nb
-                    _PENDING_UPLOADS.append((dst, host))
+                if sc is not None and sc.dev == dev and sc.off + nb <= sc.arena.numel():
+                    dst = sc.arena[sc.off:sc.off + raw.size]
+                    sc.off += nb
+                    sc.uploads.append((dst, host))
                     return dst
                 return host.to(dev, non_blocking=True)
             host = torch.from_numpy(raw).pin_memory()

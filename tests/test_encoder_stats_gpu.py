@@ -77,7 +77,7 @@ def test_encoder_memory_without_saved_p(built):
     earlier test left there would decide what this one measures: each measured step starts without them and allocates its own.
     Measured on an MI355X with both workspaces left in place instead (P alone): 15 202 304 B against the bound's 16 810 000 — the
     peak moves from a point where both P are live to the first layer's FFN (1.6 MB of activations more, one P fewer)."""
-    from glow_tts_amd import attentions, flow_impl, ops
+    from glow_tts_amd import attentions, devstate, ops
     n_layers, B, T, Hh = 2, 1, 1025, 2
     enc = fill_module(attentions.Encoder(192, 768, Hh, n_layers, kernel_size=3, p_dropout=0.1, window_size=4), "enc.").eval().to(dev())
     enc.rows_cfg = ops.RowsConfig()
@@ -89,7 +89,7 @@ def test_encoder_memory_without_saved_p(built):
         enc.zero_grad(set_to_none=True)
         xd = x.clone().requires_grad_(True)
         for name in ("attn_bwd", "attn_bwd_stats"):
-            flow_impl._SCRATCH.pop((name, str(xd.device)), None)
+            devstate.get(xd.device).scratch_bufs.pop(name, None)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         out = enc(xd, xm)

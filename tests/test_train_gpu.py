@@ -266,9 +266,11 @@ def test_prosody_conditioned_graph_step_matches_eager(built):
 
 def test_failed_capture_falls_back_to_eager_steps(built, monkeypatch):
     """If the step cannot be captured (e.g. a collective that refuses capture), the trainer warns and keeps training with
-    eager launches — same updates as a trainer that never tried."""
+    eager launches — same updates as a trainer that never tried.  The real _capture runs (warm-ups, snapshot / restore, the open
+    wgrad.capture_scope) and fails at graph CONSTRUCTION, before any capture begins, with the host state a capture leaves when it
+    aborts between the decoder's flush and the optimizer; Trainer._abandon_capture must unwind all of it."""
     import warnings
-    from glow_tts_amd import train
+    from glow_tts_amd import devstate, ops, train, wgrad
     cfg = dict(train.BASE_MODEL, n_blocks_dec=1, n_layers_enc=1, p_dropout=0.0, p_dropout_dec=0.0)
     torch.manual_seed(0)
     m1 = train.build_model(cfg, device=dev())
@@ -280,9 +282,13 @@ def test_failed_capture_falls_back_to_eager_steps(built, monkeypatch):
     lh = (batch[1].tolist(), batch[3].tolist())
     t1, t2 = train.Trainer(m1, graph=False), train.Trainer(m2, graph=True)
 
-    def boom(self, *a, **k):
+    front0, seed0 = devstate.get(dev()).stream("front"), ops.seed_word(dev())
+
+    def boom(*a, **k):
+        t2.opt._early = (t2.dec_cov_off, t2.buckets.total)
+        t2._tail_packed = True
         raise RuntimeError("capture refused")
-    monkeypatch.setattr(train.Trainer, "_capture", boom)
+    monkeypatch.setattr(torch.cuda, "CUDAGraph", boom)
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
         for _ in range(2):
@@ -290,6 +296,11 @@ def test_failed_capture_falls_back_to_eager_steps(built, monkeypatch):
             l2, _ = t2.step(*batch, lengths_host=lh)
     torch.cuda.synchronize()
     assert not t2.graph_mode and any("capture of the training step failed" in str(x.message) for x in w)
+    assert t2.adam_steps == t2.n_steps == 2
+    assert t2.opt._early is None
+    assert not wgrad.capture_keep(torch.empty(1))                    # no capture scope is left open
+    assert devstate.get(dev()).stream("front") is not front0         # every auxiliary stream was dropped, the front end's included
+    assert ops.seed_word(dev()) is seed0                             # ... and nothing a captured graph has the address of
     assert abs(l1.item() - l2.item()) <= 1e-3 * max(1.0, abs(l1.item()))
     worst = max((a - b).abs().max().item() for a, b in zip(m1.parameters(), m2.parameters()))
     assert worst < 5e-3, worst
@@ -382,14 +393,11 @@ def test_wgrad_workspace_outgrown_by_a_later_capture_lives_as_long_as_its_graphs
         a = wgrad._scratch(dev(), 1 << 20)
         pa, wa = a.data_ptr(), weakref.ref(a)
         assert wgrad._scratch(dev(), 1 << 19).data_ptr() == pa           # big enough: reused
-        keep = wgrad.table_arena_begin(dev())                            # "a capture is open": whoever asks for scratch now registers it
-        try:
+        with wgrad.capture_scope(dev()) as keep:                         # "a capture is open": whoever asks for scratch now registers it
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=s):
                 assert wgrad._scratch(dev(), 1 << 19).data_ptr() == pa
                 _ = torch.ones(4, device=dev()) * 2.0                    # (a graph with a node in it)
-        finally:
-            wgrad.table_arena_end(dev())
         assert any(t.data_ptr() == pa for t in keep if isinstance(t, torch.Tensor))
         b = wgrad._scratch(dev(), 8 << 20)                               # a later bucket outgrows it
         assert b.numel() >= (8 << 20) and b.data_ptr() != pa
@@ -547,17 +555,17 @@ def test_early_decoder_update_matches_the_single_optimizer_pass(built):
 def test_step_head_one_launch_clears_the_regions_and_bumps_the_seed(built):
     """ops.step_head (gt_step_zero): the step's accumulator arena, its pre-zeroed buffer region and one more region cleared, the dropout
     seed word advanced by bump_seed's constant — one launch; what lies behind a region is untouched."""
-    from glow_tts_amd import ops
+    from glow_tts_amd import devstate, ops
     d = dev()
     ops.arena_begin(d); ops.big_begin(d)                             # allocate
-    a, b = ops._ARENA[str(d)], ops._BIG[str(d)]
-    a["buf"].fill_(3); b["buf"][:8192].fill_(5); b["used"] = 5000
+    a, b = devstate.get(d).small, devstate.get(d).big
+    a.buf.fill_(3); b.buf[:8192].fill_(5); b.used = 5000
     extra = torch.full((1000 + 4,), 2.0, device=d)[:1000]            # 4000 bytes: a multiple of 16, with a guard behind it
     guard = extra.storage_offset()
     seed0 = int(ops.seed_word(d).item())
     ops.step_head(d, extra=extra)
     torch.cuda.synchronize()
-    assert int(a["buf"].count_nonzero()) == 0 and int(b["buf"][:8192].count_nonzero()) == 0 and int(extra.count_nonzero()) == 0
+    assert int(a.buf.count_nonzero()) == 0 and int(b.buf[:8192].count_nonzero()) == 0 and int(extra.count_nonzero()) == 0
     assert (int(ops.seed_word(d).item()) - seed0) & 0xffffffff == 0x632BE5AB
     odd = torch.full((1001,), 2.0, device=d)                         # 4004 bytes: not a multiple of 16 -> the plain fill
     ops.step_head(d, extra=odd, bump=False)
