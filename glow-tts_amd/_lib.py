@@ -198,6 +198,14 @@ PROTOTYPES = {
     "gt_yin_tile_frames": (c_int, []),
     "gt_yin_f0": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
                            c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gt_gl_pack_bytes": (c_size_t, []),
+    "gt_gl_tile_frames": (c_int, []),
+    "gt_gl_tile_hops": (c_int, []),
+    "gt_gl_spec_bytes": (c_size_t, [c_int, c_int]),
+    "gt_gl_pack": (STATUS, [c_void_p, c_int, c_void_p, c_void_p]),
+    "gt_gl_polar": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gt_gl_project": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gt_istft": (STATUS, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
 }
 c_void_p = ctypes.c_void_p
 

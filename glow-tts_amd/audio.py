@@ -10,6 +10,12 @@ run by ONE HIP kernel (csrc/mel_front.hip: gt_mel_pack once, gt_mel_spectrogram 
   YIN               the pitch contour of the reference's get_f0 (yin.compute_yin) for padded batches by ONE kernel (csrc/yin_front.hip:
                     gt_yin_f0); `f0(y, lengths)` lines up with `TacotronSTFT.mel_spectrogram(y, lengths)`.
   compute_yin       the reference's signature for one device waveform.
+  InverseSTFT       carries `inverse_basis` [2 * 513, 1, 1024] (the reference's pinv(4 fourier_basis).T times the window, float64,
+                    rounded once); `inverse(magnitude, phase[, frames])` is the reference's STFT.inverse by two kernels
+                    (csrc/griffin_lim.hip: gt_gl_polar, gt_istft).  A class of its own: STFT keeps its buffers.
+  GriffinLim        the reference's griffin_lim loop on an STFT / TacotronSTFT: gt_gl_project (analysis, Y = M X / |X|) and gt_istft
+                    per iteration, 2 + 2 n launches, no host synchronisation; `from_mel` starts from a log-mel.
+  griffin_lim       the reference's signature.
 
 Waveforms are fp32 in [-1, 1] or int16 (scaled by 1/32768 in the kernel = the reference's audio / max_wav_value).  There is no CPU
 path: a CPU tensor raises."""
@@ -244,3 +250,220 @@ def compute_yin(sig, sr, w_len=512, w_step=256, f0_min=100, f0_max=500, harmo_th
     f0, harm, amin = mod.transform(sig.unsqueeze(0), wav_len, max(n, 1), aux=True)
     times = torch.arange(n, dtype=torch.float32, device=sig.device) * (w_step / float(sr))
     return f0[0, :n], harm[0, :n], amin[0, :n], times
+
+
+# ---- waveform back end: the reference's STFT.inverse and griffin_lim on csrc/griffin_lim.hip ---------------------
+def inverse_basis64(filter_length=1024, hop_length=256, win_length=1024):
+    """float64 [2 * cutoff, n]: the reference's pinv(scale * fourier_basis).T times the centre-padded periodic Hann window, scale =
+    filter_length / hop_length.  The pseudo-inverse of the real/imaginary DFT rows is the irfft weighting in closed form — row k is
+    (cos, -sin)(2 pi k n / n_fft) * c_k / (n_fft * scale), c_k = 1 for bins 0 and n_fft / 2, else 2 (np.linalg.pinv agrees to
+    3e-16, tests/test_griffin_lim_host.py) — written so that columns n and n_fft - n are exact mirrors and the sine rows of bins 0
+    and n_fft / 2 exact zeros, which the float64 pinv only approximates."""
+    n, cutoff, half = filter_length, filter_length // 2 + 1, filter_length // 2
+    k = np.arange(cutoff, dtype=np.int64)[:, None]
+    m = (k * np.arange(half + 1, dtype=np.int64)[None, :]) % n
+    ang = 2.0 * np.pi * m.astype(np.float64) / n
+    c_k = np.where((k == 0) | (k == half), 1.0, 2.0) / (n * (filter_length / hop_length))
+    cos_h = np.cos(ang) * c_k
+    sin_h = np.where((2 * m) % n == 0, 0.0, -np.sin(ang)) * c_k
+    win = np.zeros(n)
+    lpad = (n - win_length) // 2
+    win[lpad:lpad + win_length] = hann_periodic(win_length)
+    cos_h, sin_h = cos_h * win[None, :half + 1], sin_h * win[None, :half + 1]
+    full = np.empty((2 * cutoff, n))
+    full[:cutoff, :half + 1], full[cutoff:, :half + 1] = cos_h, sin_h
+    full[:cutoff, half + 1:], full[cutoff:, half + 1:] = cos_h[:, half - 1:0:-1], -sin_h[:, half - 1:0:-1]
+    return full
+
+
+def spec_unpack(spec, B, F_max):
+    """dev / tests: the kernels' spectrum workspace (include/glowtts_hip.h, gt_gl_*) -> (re, im) [B, 513, F_max]; Im of bin 512 is 0"""
+    tile = call.gt_gl_tile_frames()
+    Fp = (F_max + tile - 1) // tile * tile
+    rows = spec.view(B, Fp * 1025)
+    k = torch.arange(512, device=spec.device)[:, None]
+    f = torch.arange(F_max, device=spec.device)[None, :]
+    idx = ((((f >> 5) * 64 + (k >> 3)) * 64 + (k & 1) * 32 + (f & 31)) * 8 + ((k & 7) >> 1)).reshape(-1)
+    re = torch.cat([rows[:, idx].view(B, 512, F_max), rows[:, Fp * 1024:Fp * 1024 + F_max].unsqueeze(1)], 1)
+    im = torch.cat([rows[:, idx + 4].view(B, 512, F_max), torch.zeros_like(re[:, :1])], 1)
+    return re, im
+
+
+def _check_geometry(fs):
+    if (fs.filter_length, fs.hop_length, fs.win_length) != (1024, 256, 1024):
+        raise ValueError("the waveform back end takes filter_length = win_length = 1024, hop_length = 256 (every reference config)")
+
+
+def _spectrogram_arg(t, name):
+    if not t.is_cuda:
+        raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
+    if t.dim() != 3 or t.shape[1] != 513 or t.dtype != torch.float32:
+        raise ValueError(f"{name} is fp32 [B, 513, F], got {tuple(t.shape)} {t.dtype}")
+    return t.contiguous()
+
+
+def _frames_arg(frames, frames_host, B, F, device):
+    """-> device int32 [B] frame counts; F_b < 4 (no reflect padding: 256 (F_b - 1) <= 512) raises where the host knows the counts"""
+    if frames is None:
+        if F < 4:
+            raise ValueError(f"{F} frames: reflect padding needs at least 4")
+        return torch.full((B,), F, dtype=torch.int32, device=device)
+    if frames_host is None and not frames.is_cuda:
+        frames_host = frames.tolist()
+    if frames_host is not None:
+        frames_host = [int(v) for v in frames_host]
+        if len(frames_host) != B or max(frames_host) > F:
+            raise ValueError(f"frame counts {frames_host} do not fit a [{B}, 513, {F}] spectrogram")
+        if min(frames_host) < 4:
+            raise ValueError(f"an utterance of {min(frames_host)} frames: reflect padding needs at least 4")
+    elif F < 2:
+        raise ValueError(f"{F} frames: no sample")
+    if frames.numel() != B:
+        raise ValueError("frames must be [B]")
+    return frames.to(device, non_blocking=True).to(torch.int32).contiguous()
+
+
+class InverseSTFT(nn.Module):
+    """The reference's STFT.inverse (stft.py:121-148, CUDA branch) by gt_gl_polar + gt_istft.  Carries `inverse_basis`
+    [2 * 513, 1, 1024] = inverse_basis64() rounded to fp32 once; a class of its own, so that STFT / TacotronSTFT keep their buffers."""
+
+    def __init__(self, filter_length=1024, hop_length=256, win_length=1024):
+        super().__init__()
+        self.filter_length, self.hop_length, self.win_length = filter_length, hop_length, win_length
+        basis = inverse_basis64(filter_length, hop_length, win_length).astype(np.float32)
+        self.register_buffer("inverse_basis", torch.from_numpy(basis)[:, None, :].contiguous())
+        self._packed, self._packed_key = None, None
+
+    def _image(self):
+        ib = self.inverse_basis
+        key = (ib.data_ptr(), ib._version)
+        if self._packed_key != key:
+            _check_geometry(self)
+            if ib.dtype != torch.float32 or not ib.is_contiguous() or ib.numel() != 1026 * 1024:
+                raise ValueError("inverse_basis must be a contiguous fp32 [1026, 1, 1024] buffer")
+            packed = torch.empty(call.gt_gl_pack_bytes() // 4, dtype=torch.float32, device=ib.device)
+            call.gt_gl_pack(ib, self.filter_length, packed, _lib.current_stream(ib.device))
+            self._packed, self._packed_key = packed, key
+        return self._packed
+
+    def workspace(self, B, F_max, device):
+        return torch.empty(call.gt_gl_spec_bytes(B, F_max) // 4, dtype=torch.float32, device=device)
+
+    def polar(self, magnitude, phase, n_frames, spec):
+        """kernel call: spec = (mag cos(phase), mag sin(phase)) in the kernels' order"""
+        B, _, F = magnitude.shape
+        call.gt_gl_polar(magnitude, phase, n_frames, B, F, self.filter_length, self.hop_length, self.win_length, spec,
+                         _lib.current_stream(magnitude.device))
+
+    def synthesize(self, spec, n_frames, B, F_max, out=None):
+        """kernel call: the spectrum workspace -> wav [B, 256 (F_max - 1)], row b zero behind its 256 (F_b - 1) samples"""
+        if out is None:
+            out = torch.empty(B, self.hop_length * (F_max - 1), dtype=torch.float32, device=spec.device)
+        call.gt_istft(spec, n_frames, B, F_max, self._image(), self.filter_length, self.hop_length, self.win_length, out, out.stride(0),
+                      _lib.current_stream(spec.device))
+        return out
+
+    def inverse(self, magnitude, phase, frames=None):
+        """inverse(magnitude, phase): the reference's call, [B, 513, F] each -> wav [B, 256 (F - 1)].
+        inverse(magnitude, phase, frames): the ragged form, utterance b inverted from its first frames[b] frames alone."""
+        magnitude, phase = _spectrogram_arg(magnitude, "magnitude"), _spectrogram_arg(phase, "phase")
+        if phase.shape != magnitude.shape or phase.device != magnitude.device:
+            raise ValueError("magnitude and phase differ in shape or device")
+        B, _, F = magnitude.shape
+        if F < 2:
+            raise ValueError(f"{F} frames: no sample")
+        n_frames = torch.full((B,), F, dtype=torch.int32, device=magnitude.device) if frames is None else \
+            frames.to(magnitude.device, non_blocking=True).to(torch.int32).contiguous()
+        spec = self.workspace(B, F, magnitude.device)
+        self.polar(magnitude, phase, n_frames, spec)
+        return self.synthesize(spec, n_frames, B, F)
+
+    forward = inverse
+
+
+class GriffinLim(nn.Module):
+    """The reference's griffin_lim (audio_processing.py:59-75) on the device: gt_gl_polar, gt_istft, then per iteration gt_gl_project
+    (analysis, Y = M X / |X|) and gt_istft — 2 + 2 n_iters launches, no host synchronisation.  `stft` is an audio.STFT or a
+    TacotronSTFT (the analysis reads its forward basis image); the inverse basis lives in `.istft`, an InverseSTFT."""
+
+    def __init__(self, stft):
+        super().__init__()
+        self.stft = stft
+        self.stft_fn = stft.stft_fn if isinstance(stft, TacotronSTFT) else stft
+        _check_geometry(self.stft_fn)
+        self.istft = InverseSTFT(self.stft_fn.filter_length, self.stft_fn.hop_length, self.stft_fn.win_length)
+        self._fwd_packed, self._fwd_key = None, None
+        self._mel_pinv, self._mel_pinv_key = None, None
+
+    def _forward_image(self):
+        if isinstance(self.stft, TacotronSTFT):
+            return self.stft._image()
+        fb = self.stft_fn.forward_basis
+        key = (fb.data_ptr(), fb._version)
+        if self._fwd_key != key:                                              # a plain STFT has no mel basis: the image's mel part is zeros
+            if fb.dtype != torch.float32 or not fb.is_contiguous():
+                raise ValueError("forward_basis must be a contiguous fp32 buffer")
+            packed = torch.empty(call.gt_mel_pack_bytes() // 4, dtype=torch.float32, device=fb.device)
+            call.gt_mel_pack(fb, torch.zeros(1, 513, dtype=torch.float32, device=fb.device), 1024, 1, packed, _lib.current_stream(fb.device))
+            self._fwd_packed, self._fwd_key = packed, key
+        return self._fwd_packed
+
+    def project(self, wav, magnitudes, n_frames, spec):
+        """kernel call, the analysis half: spec = magnitudes * X / |X|, X the STFT of wav's rows (each reflected about its own ends)"""
+        B, _, F = magnitudes.shape
+        call.gt_gl_project(wav, wav.stride(0), magnitudes, n_frames, B, F, self._forward_image(), 1024, 256, 1024, spec,
+                           _lib.current_stream(wav.device))
+
+    def forward(self, magnitudes, frames=None, frames_host=None, n_iters=30, angles=None, seed=0):
+        """magnitudes [B, 513, F] -> wav [B, 256 (F - 1)]; with `frames` (counts per utterance; `frames_host` spares the host a look
+        at a device tensor) the ragged form -> (wav, wav_lengths = 256 (frames - 1)), zero behind each utterance.  `angles`
+        [B, 513, F] are the initial phases; absent, they are uniform in [-pi, pi) from a device torch.Generator seeded with `seed`
+        (one PyTorch op — a caller who captures the loop in a graph passes `angles`)."""
+        magnitudes = _spectrogram_arg(magnitudes, "magnitudes")
+        B, _, F = magnitudes.shape
+        dev = magnitudes.device
+        n_frames = _frames_arg(frames, frames_host, B, F, dev)
+        if angles is None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+            angles = torch.empty_like(magnitudes).uniform_(-np.pi, np.pi, generator=gen)
+        else:
+            angles = _spectrogram_arg(angles, "angles")
+            if angles.shape != magnitudes.shape or angles.device != dev:
+                raise ValueError("angles and magnitudes differ in shape or device")
+        inv = self.istft
+        spec = inv.workspace(B, F, dev)
+        inv.polar(magnitudes, angles, n_frames, spec)
+        wav = inv.synthesize(spec, n_frames, B, F)
+        for _ in range(n_iters):
+            self.project(wav, magnitudes, n_frames, spec)
+            inv.synthesize(spec, n_frames, B, F, out=wav)
+        if frames is None:
+            return wav
+        return wav, (n_frames.clamp(min=1) - 1) * self.stft_fn.hop_length
+
+    def mel_pinv(self):
+        """fp32 [513, n_mel]: the float64 pseudo-inverse of the TacotronSTFT's mel_basis, computed on the host once per version of it"""
+        if not isinstance(self.stft, TacotronSTFT):
+            raise ValueError("from_mel needs a TacotronSTFT (a mel basis)")
+        mb = self.stft.mel_basis
+        key = (mb.data_ptr(), mb._version)
+        if self._mel_pinv_key != key:
+            pinv = np.linalg.pinv(mb.detach().cpu().numpy().astype(np.float64))
+            self._mel_pinv, self._mel_pinv_key = torch.from_numpy(pinv.astype(np.float32)).to(mb.device), key
+        return self._mel_pinv
+
+    def from_mel(self, mel, mel_lengths=None, mel_lengths_host=None, n_iters=30, angles=None, seed=0):
+        """log-mel [B, n_mel, F] (TacotronSTFT.mel_spectrogram's output) -> wav, or (wav, wav_lengths) with mel_lengths.  The
+        reference has no mel inversion: magnitudes = clamp(pinv(mel_basis) exp(mel), min=0) is PyTorch plumbing on [513 x n_mel]
+        (the least-squares spectrum; the bank's null space is lost), then the loop above."""
+        if not mel.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
+        magnitudes = torch.clamp(torch.matmul(self.mel_pinv(), torch.exp(mel.float())), min=0.0)
+        return self.forward(magnitudes, mel_lengths, mel_lengths_host, n_iters, angles, seed)
+
+
+def griffin_lim(magnitudes, stft_fn, n_iters=30, **kw):
+    """the reference's signature; stft_fn is an audio.STFT / TacotronSTFT (a GriffinLim is built for the call) or a GriffinLim"""
+    gl = stft_fn if isinstance(stft_fn, GriffinLim) else GriffinLim(stft_fn).to(magnitudes.device)
+    return gl(magnitudes, n_iters=n_iters, **kw)

@@ -1011,6 +1011,48 @@ int gt_yin_f0(const void* wav, int is_i16, int ld_wav, const int32_t* wav_len, i
               int w_len, int hop, int tau_min, int tau_max, float sr, float thresh, int lead,
               float* f0, float* harm, float* argmin_f0, void* stream);
 
+/* ---- device waveform back end (csrc/griffin_lim.hip): inverse STFT and the two halves of Griffin-Lim ------------
+ * The reference's STFT.inverse (stft.py:121-148 CUDA branch) and griffin_lim (audio_processing.py:59-75) applied to every utterance
+ * of a ragged batch on its own, in exact fp32 (v_mfma_f32_32x32x2_f32), n_fft = win = 1024, hop = 256, periodic Hann window.
+ * Utterance b has F_b = n_frames[b] frames (clamped to F_max; F_b < 2: no sample, every output of the row is 0) and
+ * L_b = 256 (F_b - 1) samples.  One Griffin-Lim run is gt_gl_polar, gt_istft, then n_iters x (gt_gl_project, gt_istft).
+ *   spec     the complex spectrum Y of the batch, gt_gl_spec_bytes(B, F_max) bytes, in the fragment order gt_istft reads: per
+ *            utterance [Fp / 32 frame groups][64 bin groups][64 lanes][re 4 | im 4] fp32 with lane = 32 (bin & 1) + (frame & 31),
+ *            word = (bin & 7) >> 1, bin group = bin >> 3 for bins 0..511, then Re of bin 512 [Fp]; Fp = F_max rounded up to
+ *            gt_gl_tile_frames().  Im of bins 0 and 512 is not kept (its inverse basis row is zero).  Both writers define all of
+ *            it: zeros from frame F_b on.
+ *   gt_gl_pack     once, from the reference's STFT.inverse_basis (fp32 [2 * 513, 1024]: pinv(4 fourier_basis).T times the window;
+ *            it must be even (cos rows) / odd (sin rows) about sample 512 with column 0 zero, and row 0 the window / 4096 — the
+ *            squared-window envelope is taken from it): gt_gl_pack_bytes() bytes.
+ *   gt_gl_polar    spec = (mag cos(phase), mag sin(phase)), mag and phase fp32 [B, 513, F_max]: STFT.inverse's first line.
+ *   gt_gl_project  the analysis half: frames of wav row b ([B rows, pitch ld_wav] fp32, L_b samples) reflected about the utterance's
+ *            own ends as gt_mel_spectrogram takes them (F_b additionally clamped to 1 + ld_wav / 256; a reflected index is clamped
+ *            into [0, L_b): nothing else is read), X = the folded DFT with the basis image of gt_mel_pack (mel_packed), and
+ *            spec = mag X / |X| — the unit phasor instead of the reference's atan2 / cos / sin, the ONE departure from its
+ *            arithmetic (the same mathematics); |X|^2 == 0 in fp32 gives (mag, 0), as atan2(0, 0) = 0 does.
+ *   gt_istft       the synthesis half: per frame x = inverse_basis^T Y, overlap-added (4 frames per sample, ascending frame order),
+ *            divided by the squared-window envelope (the sum of w^2 over the frames that really cover the sample, fp32, same order)
+ *            where it exceeds FLT_MIN, times 1024 / 256, the 512 samples at both ends trimmed: wav row b ([B rows, pitch ld_wav])
+ *            gets L_b samples and zeros behind them up to column 256 (F_max - 1); columns from there on are not written.
+ * Asynchronous, no allocation, no atomics, capturable in a graph; the summation order of an element depends on its index within
+ * its utterance alone, not on B, F_max or the tile: a batch row is bit-identical to the utterance computed alone.
+ * Refusals, before any launch and in this order: a NULL pointer, B outside [1, GT_MEL_MAX_B], F_max outside
+ * [1, GT_MEL_MAX_FRAMES], ld_wav <= 0, gt_istft's ld_wav < 256 (F_max - 1): GT_E_INVAL; n_fft != 1024, hop != 256 or
+ * win != 1024: GT_E_UNSUPPORTED; a pointer not 16-byte (n_frames: 4-byte) aligned, ld_wav no multiple of 4: GT_E_ALIGN.
+ * gt_gl_spec_bytes is 0 for a (B, F_max) the calls refuse.  gt_gl_tile_frames: frames per workgroup of gt_gl_project and gt_istft;
+ * gt_gl_tile_hops: the output hops a gt_istft workgroup completes (its frames less a 3-frame halo). */
+size_t gt_gl_pack_bytes(void);
+int gt_gl_tile_frames(void);
+int gt_gl_tile_hops(void);
+size_t gt_gl_spec_bytes(int B, int F_max);
+int gt_gl_pack(const float* inverse_basis, int n_fft, void* packed, void* stream);
+int gt_gl_polar(const float* mag, const float* phase, const int32_t* n_frames, int B, int F_max, int n_fft, int hop, int win,
+                float* spec, void* stream);
+int gt_gl_project(const float* wav, int ld_wav, const float* mag, const int32_t* n_frames, int B, int F_max, const void* mel_packed,
+                  int n_fft, int hop, int win, float* spec, void* stream);
+int gt_istft(const float* spec, const int32_t* n_frames, int B, int F_max, const void* gl_packed, int n_fft, int hop, int win,
+             float* wav, int ld_wav, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
