@@ -206,6 +206,7 @@ PROTOTYPES = {
     "gt_gl_polar": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gt_gl_project": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gt_istft": (STATUS, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "gt_gl_from_mel": (STATUS, [c_void_p, c_i64, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_u32, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 c_void_p = ctypes.c_void_p
 

@@ -14,7 +14,10 @@ run by ONE HIP kernel (csrc/mel_front.hip: gt_mel_pack once, gt_mel_spectrogram 
                     rounded once); `inverse(magnitude, phase[, frames])` is the reference's STFT.inverse by two kernels
                     (csrc/griffin_lim.hip: gt_gl_polar, gt_istft).  A class of its own: STFT keeps its buffers.
   GriffinLim        the reference's griffin_lim loop on an STFT / TacotronSTFT: gt_gl_project (analysis, Y = M X / |X|) and gt_istft
-                    per iteration, 2 + 2 n launches, no host synchronisation; `from_mel` starts from a log-mel.
+                    per iteration, 2 + 2 n launches, no host synchronisation; `from_mel` starts from a log-mel —
+                    with phases="counter" through ONE kernel (csrc/gl_mel.hip: gt_gl_from_mel) that writes the
+                    magnitudes and the initial spectrum, phases keyed by (seed, utterance, frame, bin); `mel_workspace` /
+                    `run_from_mel` are its capacity-sized form for graph callers (synthesis.Synthesizer).
   griffin_lim       the reference's signature.
 
 Waveforms are fp32 in [-1, 1] or int16 (scaled by 1/32768 in the kernel = the reference's audio / max_wav_value).  There is no CPU
@@ -453,14 +456,69 @@ class GriffinLim(nn.Module):
             self._mel_pinv, self._mel_pinv_key = torch.from_numpy(pinv.astype(np.float32)).to(mb.device), key
         return self._mel_pinv
 
-    def from_mel(self, mel, mel_lengths=None, mel_lengths_host=None, n_iters=30, angles=None, seed=0):
+    def from_mel(self, mel, mel_lengths=None, mel_lengths_host=None, n_iters=30, angles=None, seed=0, phases="torch"):
         """log-mel [B, n_mel, F] (TacotronSTFT.mel_spectrogram's output) -> wav, or (wav, wav_lengths) with mel_lengths.  The
-        reference has no mel inversion: magnitudes = clamp(pinv(mel_basis) exp(mel), min=0) is PyTorch plumbing on [513 x n_mel]
-        (the least-squares spectrum; the bank's null space is lost), then the loop above."""
+        reference has no mel inversion: magnitudes = clamp(pinv(mel_basis) exp(mel), min=0) (the least-squares spectrum; the bank's
+        null space is lost), then the loop above.
+        phases="torch" (default): the inversion is PyTorch plumbing on [513 x n_mel] and the initial phases are `angles`, or a device
+        torch.Generator's draw from `seed` (it depends on the batch shape and cannot be captured with a per-call seed).
+        phases="counter" (DESIGN.md 4.21): ONE gt_gl_from_mel launch writes the magnitudes and the initial spectrum, its phases from the
+        counter generator keyed by (seed, utterance, frame, bin) — 1 + 1 + 2 n_iters launches, no ATen op on the data, no phase tensor,
+        an utterance's samples independent of the batch it is in.  `angles` with it is a ValueError."""
+        if phases not in ("torch", "counter"):
+            raise ValueError(f'phases is "torch" or "counter", got {phases!r}')
         if not mel.is_cuda:
             raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
+        if phases == "counter":
+            if angles is not None:
+                raise ValueError('phases="counter" draws the initial phases in the kernel: angles= cannot be given with it')
+            pinv = self.mel_pinv()
+            if mel.dim() != 3 or mel.shape[1] != pinv.shape[1]:
+                raise ValueError(f"mel is [B, {pinv.shape[1]}, F], got {tuple(mel.shape)}")
+            if mel.dtype != torch.float32 or mel.stride(2) != 1:
+                mel = mel.float().contiguous()
+            B, _, F = mel.shape
+            n_frames = _frames_arg(mel_lengths, mel_lengths_host, B, F, mel.device)
+            wav = self.run_from_mel(mel, n_frames, self.mel_workspace(B, F, mel.device), n_iters, seed=seed)
+            if mel_lengths is None:
+                return wav
+            return wav, (n_frames.clamp(min=1) - 1) * self.stft_fn.hop_length
         magnitudes = torch.clamp(torch.matmul(self.mel_pinv(), torch.exp(mel.float())), min=0.0)
         return self.forward(magnitudes, mel_lengths, mel_lengths_host, n_iters, angles, seed)
+
+    def mel_workspace(self, B, F_max, device):
+        """the buffers of one run_from_mel at capacity (B utterances of up to F_max >= 2 frames): dict(mag [B, 513, F_max], spec (the
+        spectrum workspace), wav [B, 256 (F_max - 1)]) — 4 * B * (513 F_max + 1025 Fp + 256 (F_max - 1)) bytes, Fp = F_max rounded up
+        to 64"""
+        if F_max < 2:
+            raise ValueError(f"{F_max} frames: no sample")
+        return dict(mag=torch.empty(B, 513, F_max, dtype=torch.float32, device=device), spec=self.istft.workspace(B, F_max, device),
+                    wav=torch.empty(B, self.stft_fn.hop_length * (F_max - 1), dtype=torch.float32, device=device))
+
+    def run_from_mel(self, mel, n_frames, bufs, n_iters=30, seed=0, seed_dev=None):
+        """kernel calls, the capacity-sized form for graph callers: fp32 log-mel [B, n_mel, >= F_max] (any batch / channel pitch, frames
+        contiguous), device int32 [B] frame counts and mel_workspace's buffers (F_max is theirs) -> bufs["wav"], row b zero behind its
+        256 (F_b - 1) samples.  gt_gl_from_mel, gt_istft, then n_iters x (gt_gl_project, gt_istft): nothing is allocated once the
+        packed images and mel_pinv() exist (any earlier call), n_frames is never looked at on the host — an utterance of fewer than
+        4 frames gets what the kernels define (clamped reflection; F_b < 2: no sample) — and every grid is sized by F_max, whatever the
+        utterances' lengths are.  The seed of the phases is `seed`, or (seed_dev: a device uint32 / int32 word) read on the device."""
+        mag, spec, wav = bufs["mag"], bufs["spec"], bufs["wav"]
+        B, _, F_max = mag.shape
+        pinv = self.mel_pinv()
+        if not mel.is_cuda or mel.dtype != torch.float32 or mel.dim() != 3 or mel.stride(2) != 1:
+            raise ValueError("run_from_mel takes a device fp32 log-mel [B, n_mel, F] with contiguous frames")
+        if mel.shape[0] != B or mel.shape[1] != pinv.shape[1] or mel.shape[2] < F_max:
+            raise ValueError(f"mel {tuple(mel.shape)} does not fit buffers for [{B}, {pinv.shape[1]}, {F_max}]")
+        if n_frames.dtype != torch.int32 or n_frames.numel() != B or not n_frames.is_cuda or not n_frames.is_contiguous():
+            raise ValueError("n_frames must be a contiguous int32 [B] on the device")
+        inv = self.istft
+        call.gt_gl_from_mel(mel, mel.stride(0) if B > 1 else max(mel.stride(0), F_max), mel.stride(1), n_frames, B, F_max, pinv.shape[1],
+                            pinv, int(seed) & 0xFFFFFFFF, seed_dev, mag, spec, _lib.current_stream(mel.device))
+        inv.synthesize(spec, n_frames, B, F_max, out=wav)
+        for _ in range(n_iters):
+            self.project(wav, mag, n_frames, spec)
+            inv.synthesize(spec, n_frames, B, F_max, out=wav)
+        return wav
 
 
 def griffin_lim(magnitudes, stft_fn, n_iters=30, **kw):

@@ -208,9 +208,9 @@ class SynthesisHandle:
 
     def __init__(self, synth, slot, inputs, call):
         self._synth, self._slot, self._inputs, self._call = synth, slot, inputs, call
-        self._saved = None          # (mel, aux, event, prosody) copies, taken in stream order when a later call was issued before this one was read
+        self._saved = None          # (mel, aux, event, prosody, wav) copies, taken in stream order when a later call was issued before this one was read
         self._read = None           # (lengths, status) once the event has passed
-        self._eager = None
+        self._eager = self._eager_wav = None
         # mel() has been handed out: the next call may overwrite the static buffers.  aux() alone does not set it — a caller who
         # looked at the durations first and asks for the mel after the next call still gets this call's (at the price of one copy aside)
         self._done = False
@@ -264,12 +264,12 @@ class SynthesisHandle:
 
     def _from_saved(self):
         """the outputs that were moved aside: the caller's stream waits for that copy and is registered as a user of its memory"""
-        mel, aux, ev, pros = self._saved
+        mel, aux, ev, pros, wav = self._saved
         cur = torch.cuda.current_stream(self._synth.device)
         cur.wait_event(ev)
-        for t in [mel] + list((aux or {}).values()) + [t for t in (pros or ()) if t is not None]:
+        for t in [mel] + list((aux or {}).values()) + [t for t in (pros or ()) if t is not None] + ([] if wav is None else [wav]):
             t.record_stream(cur)
-        return mel, aux, pros
+        return mel, aux, pros, wav
 
     def mel(self, clone=False, fallback=True):
         """[B, C, max(lengths)] fp32 — max(lengths) rounded down to even, as infer returns it: the squeeze drops an odd trailing frame —
@@ -293,6 +293,51 @@ class SynthesisHandle:
         cur.wait_stream(s.stream)
         out.record_stream(cur)
         return out
+
+    def wav(self, clone=False, fallback=True):
+        """compile_synthesis(vocoder=): (wav [B, 256 (T - 1)] fp32, wav_lengths) with T = max(lengths) rounded down to even (the mel's
+        frames) and wav_lengths[b] = 256 max(2 (lengths[b] // 2) - 1, 0) (a host list) — the call's samples, zero behind every
+        utterance's, bit-identical to GriffinLim.from_mel(mel, 2 (lengths // 2), n_iters=vocoder_iters, seed=the call's seed,
+        phases="counter").  A view of the synthesiser's static buffer under mel()'s stream-order rules (clone=True: a copy that outlives
+        the next call); it is moved aside together with the mel when a later call is issued first.  After an overflow: that eager
+        result on the eager path's mel (fallback=False: SynthesisOverflow).  An utterance of fewer than 4 frames is not refused (the
+        host has not seen the lengths when the loop runs): it gets what the Griffin-Lim kernels define — a reflected index clamped
+        into the utterance, and no sample below 2 frames.
+        Like mel(), wav() marks the call as read: the next call then overwrites the static buffers without moving them aside, so take
+        everything a handle is asked for (mel, wav, prosody, aux) before the next call is issued — or issue the next call first, which
+        moves all of them aside.  A wav() asked of a handle whose outputs a later call has already overwritten raises RuntimeError
+        instead of returning that call's samples."""
+        s = self._synth
+        if s.vocoder is None:
+            raise RuntimeError("compile_synthesis(vocoder=audio.GriffinLim(...)) keeps the samples")
+        lens, status = self._wait()
+        hop = s.vocoder.stft_fn.hop_length
+        wav_lengths = [hop * max(2 * (v // 2) - 1, 0) for v in lens]
+        if status != 0:
+            mel = self._fallback(fallback)[0][0]
+            if self._eager_wav is None:
+                if mel.shape[2] < 2:
+                    self._eager_wav = mel.new_zeros(mel.shape[0], 0)
+                else:
+                    frames = torch.tensor([2 * (v // 2) for v in lens], dtype=torch.int32).to(s.device)
+                    self._eager_wav = s.vocoder.from_mel(mel, frames, n_iters=s.vocoder_iters, seed=self._call.seed, phases="counter")[0]
+            return self._eager_wav, wav_lengths
+        n = hop * max(max(lens) // 2 * 2 - 1, 0)
+        if self._saved is not None:
+            return self._from_saved()[3][:, :n], wav_lengths
+        if self._done and s._latest is not None and s._latest() is not self:
+            raise RuntimeError("this call's outputs were handed out and a later call has overwritten the static buffers: take wav() "
+                               "before the next call is issued, or issue it before anything of this handle is read")
+        self._done = True
+        cur = torch.cuda.current_stream(s.device)
+        if not clone:
+            s._handed.add(cur)
+            return s.wav_static[:, :n], wav_lengths
+        with torch.cuda.stream(s.stream):
+            out = s.wav_static[:, :n].clone()
+        cur.wait_stream(s.stream)
+        out.record_stream(cur)
+        return out, wav_lengths
 
     def prosody(self, fallback=True):
         """(pitch, energy): [B, max(lengths)] fp32 each, zero past every utterance's length, scaled by pitch_scale / energy_scale — what
@@ -337,12 +382,30 @@ class Synthesizer:
     Any number of calls may be in flight: the RING-th call after an unread one first reads that one's lengths and status into its
     handle (which waits for it), so a handle read late still returns its own call's.
     stochastic=True adds: max_frame_rows, rcf (the capacity context of the frame-rate rows; None for a model without
-    pitch / energy predictors), pitch_static / energy_static [batch, max_frames], and status bit 2."""
+    pitch / energy predictors), pitch_static / energy_static [batch, max_frames], and status bit 2.
+    vocoder=audio.GriffinLim adds the waveform back end behind the decoder, inside the same graph: n_frames (int32
+    [batch] = 2 * the squeezed lengths), wav_static [batch, 256 (max_frames - 1)] and voc_bufs (mag [batch, 513, max_frames], the
+    spectrum workspace, wav_static) — 4 batch (513 max_frames + 1025 Fp + 256 (max_frames - 1)) bytes with Fp = max_frames rounded up
+    to 64: 52 + 109 + 26 MB at batch 32 and 800 frames.  vocoder_iters is fixed at capture; every launch of the loop is sized by
+    max_frames, so a call of short utterances pays the loop of the capacity (tiles behind an utterance's end only write zeros)."""
 
     RING = 8
 
-    def __init__(self, gen, batch, max_tokens, max_frames, max_rows=None, aux=False, stochastic=False, max_frame_rows=None):
+    def __init__(self, gen, batch, max_tokens, max_frames, max_rows=None, aux=False, stochastic=False, max_frame_rows=None,
+                 vocoder=None, vocoder_iters=30):
         self.stochastic = bool(stochastic)
+        if vocoder is not None:                                          # refused before any allocation
+            from . import audio
+            if not isinstance(vocoder, audio.GriffinLim) or not isinstance(vocoder.stft, audio.TacotronSTFT):
+                raise TypeError("compile_synthesis(vocoder=) takes an audio.GriffinLim built over an audio.TacotronSTFT")
+            if vocoder.stft.mel_basis.device != next(gen.parameters()).device or vocoder.istft.inverse_basis.device != next(gen.parameters()).device:
+                raise ValueError("compile_synthesis(vocoder=): the vocoder's buffers are not on the model's device")
+            if vocoder.stft.mel_basis.shape[0] != gen.out_channels:
+                raise ValueError(f"compile_synthesis(vocoder=): the vocoder inverts {vocoder.stft.mel_basis.shape[0]} mel channels, the "
+                                 f"model writes {gen.out_channels}")
+            if int(vocoder_iters) != vocoder_iters or vocoder_iters < 0:
+                raise ValueError("compile_synthesis: vocoder_iters is a non-negative integer")
+        self.vocoder, self.vocoder_iters = vocoder, int(vocoder_iters)
         if not self.stochastic and (gen.use_sdp or gen.use_spp or gen.use_sep or gen.use_emo_embeds):
             raise NotImplementedError("compile_synthesis covers the deterministic duration predictor with optional speaker / language "
                                       "vectors; stochastic predictors and emotion inputs (cfg 5) are captured with stochastic=True")
@@ -424,6 +487,16 @@ class Synthesizer:
                 self.pitch_static, self.psig = self._static(B * Ty, torch.float32).view(B, Ty), self._static(R * 2, torch.float32).view(R, 2)
             if gen.use_sep:
                 self.energy_static, self.esig = self._static(B * Ty, torch.float32).view(B, Ty), self._static(R * 2, torch.float32).view(R, 2)
+        # ---- the waveform back end: magnitudes, the spectrum workspace, the samples, the frame counts the mel has
+        self.wav_static = self.voc_bufs = self.n_frames = self._voc_images = None
+        if vocoder is not None:
+            self.n_frames = self._static(B, torch.int32)
+            self.wav_static = self._static(B * 256 * (Ty - 1), torch.float32).view(B, 256 * (Ty - 1))
+            self.voc_bufs = dict(mag=self._static(B * 513 * Ty, torch.float32).view(B, 513, Ty),
+                                 spec=self._static(_lib.call.gt_gl_spec_bytes(B, Ty) // 4, torch.float32), wav=self.wav_static)
+            # packed once, outside the launches that are counted; kept here, because the graph holds their addresses and the vocoder
+            # drops them when it repacks (a changed mel_basis, .to())
+            self._voc_images = (vocoder.istft._image(), vocoder.stft._image(), vocoder.mel_pinv())
         self._ring, self._ring_i = [], 0
         self._latest = None
         self._handed = set()                                             # streams that views of the static outputs were handed out on
@@ -468,6 +541,10 @@ class Synthesizer:
         xm, xs = prior_stage(gen, x_m, x_logs, self.cum, xl, self.y_len_eff, rcy, bufs, src, Ty)
         contours = prosody_stage(gen, g, rc, xb, rcy, rcf, bufs, src, Ty)[2] if rcf is not None else {}
         gen.decoder.reverse_rows(rcy, self.rows, g=g, out=self.mel_static, **contours)
+        if self.vocoder is not None:
+            # the frames the mel really has (the squeeze drops an odd trailing frame); the phases' seed is the call block's first word
+            torch.mul(rcy.lengths, 2, out=self.n_frames)
+            self.vocoder.run_from_mel(self.mel_static, self.n_frames, self.voc_bufs, self.vocoder_iters, seed_dev=self.call[:1])
         if self.aux:
             a["logw"] = logw
         return xm, xs, xl, dur, logw                                     # kept: the graph replays into these
@@ -590,7 +667,8 @@ class Synthesizer:
                 # the previous call has not been read yet: its outputs move aside, in stream order, before this call overwrites them
                 saved_ev = torch.cuda.Event()
                 prev._saved = (self.mel_static.clone(), {k: v.clone() for k, v in self.aux_static.items()} if self.aux else None, saved_ev,
-                               tuple(None if t is None else t.clone() for t in (self.pitch_static, self.energy_static)))
+                               tuple(None if t is None else t.clone() for t in (self.pitch_static, self.energy_static)),
+                               None if self.wav_static is None else self.wav_static.clone())
                 saved_ev.record(self.stream)
             self._in.copy_(host, non_blocking=True)
             self.graph.replay()

@@ -509,7 +509,8 @@ class FlowGenerator(nn.Module):
             return self.decoder.fused_reverse
         return self.decoder.fused_reverse, self.set_synthesis_front(device_front)
 
-    def compile_synthesis(self, batch, max_tokens, max_frames, max_rows=None, aux=False, stochastic=False, max_frame_rows=None):
+    def compile_synthesis(self, batch, max_tokens, max_frames, max_rows=None, aux=False, stochastic=False, max_frame_rows=None,
+                          vocoder=None, vocoder_iters=30):
         """Synthesis as ONE captured graph (glow-tts_amd/synthesis.py) -> synthesis.Synthesizer.  Needs
         store_inverse(fused_reverse=True, device_front=True) in effect.  The sizes are capacities, fixed here: a batch of exactly `batch`
         texts of up to max_tokens tokens (1 <= max_tokens <= 4096), up to max_frames (even) mel frames per utterance and max_rows rows
@@ -529,10 +530,16 @@ class FlowGenerator(nn.Module):
         set_synthesis_front(noise_key="frame") in effect (RuntimeError otherwise), and reproduces infer(seed=) under that keying.
         max_frame_rows: rows of the un-squeezed mel axis the pitch / energy predictors run on (default: `batch` utterances of
         max_frames frames, rounded to rows_cfg.row_round; a multiple of 8).  The call then also takes emo=, emo_cartesian=,
-        noise_scale_w=, f0_noise_scale=, energy_noise_scale=, pitch_scale=, energy_scale=, and `h.prosody()` returns (pitch, energy)."""
+        noise_scale_w=, f0_noise_scale=, energy_noise_scale=, pitch_scale=, energy_scale=, and `h.prosody()` returns (pitch, energy).
+        vocoder=audio.GriffinLim(audio.TacotronSTFT(n_mel_channels=out_channels)) on the model's device (anything else
+        is refused before any allocation): text to WAVEFORM in the same one graph — gt_gl_from_mel (mel inversion, initial phases keyed
+        by the call's seed, read from the call block) and vocoder_iters (fixed here) Griffin-Lim iterations behind the decoder;
+        `h.wav()` -> (wav [batch, 256 (T - 1)], wav_lengths), bit-identical to vocoder.from_mel(mel, 2 (lengths // 2),
+        n_iters=vocoder_iters, seed=seed, phases="counter").  Static memory: 4 batch (513 max_frames + 1025 Fp + 256 (max_frames - 1))
+        bytes, Fp = max_frames rounded up to 64 — about 52 + 109 + 26 MB at batch 32 and 800 frames."""
         from .synthesis import Synthesizer
         return Synthesizer(self, batch, max_tokens, max_frames, max_rows=max_rows, aux=aux, stochastic=stochastic,
-                           max_frame_rows=max_frame_rows)
+                           max_frame_rows=max_frame_rows, vocoder=vocoder, vocoder_iters=vocoder_iters)
 
     @torch.no_grad()
     def infer(self, x, x_lengths, y=None, y_lengths=None, g=None, emo=None, emo_cartesian=None, l=None, gst_token=None,

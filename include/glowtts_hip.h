@@ -1053,6 +1053,25 @@ int gt_gl_project(const float* wav, int ld_wav, const float* mag, const int32_t*
 int gt_istft(const float* spec, const int32_t* n_frames, int B, int F_max, const void* gl_packed, int n_fft, int hop, int win,
              float* wav, int ld_wav, void* stream);
 
+/* ---- mel inversion in front of the loop (csrc/gl_mel.hip) ----------------------------------------------------------
+ * gt_gl_from_mel: ragged log-mel -> linear magnitudes and the loop's initial spectrum in ONE launch; gt_istft follows it directly.
+ *   mel      fp32 log-mel, element (b, k, f) at mel[b * stride_b + k * stride_c + f] (frames contiguous; strides in elements, each
+ *            >= F_max).  Utterance b has F_b = min(max(n_frames[b], 0), F_max) frames; nothing at a frame >= F_b is read.
+ *   mag      out [B, 513, F_max]: mag[b][j][f] = max(sum_k mel_pinv[j][k] expf(mel[b][k][f]), 0) for f < F_b, exactly 0 behind —
+ *            ONE fp32 fmaf chain over k ascending per element (accurate expf): its bits depend on the utterance's data, j and f alone.
+ *   spec     out, gt_gl_spec_bytes(B, F_max) bytes in the order described above, ALL of it defined (zeros from frame F_b on):
+ *            mag (cos phi, sin phi) with phi = pi t, t = 2 u - 1, u = ((h >> 9) + 0.5) 2^-23,
+ *            h = hash(key(seed, 4, b) + f * 0x9E3779B1 + j * 0x85EBCA6B) — the counter generator of the synthesis front end
+ *            (gt_randn_keyed) on stream id 4; (sin, cos) = sincospif(t).  The phase is a function of (seed, b, f, j) alone.  Im of
+ *            bin 0 is stored as gt_gl_polar stores it; Im of bin 512 is not kept.
+ *   seed     by value, or (seed_dev != NULL) *seed_dev read on the device: a captured graph replays with the call's seed.
+ * Asynchronous, no allocation, no atomics, capturable in a graph.
+ * Refusals, before any launch and in this order: a NULL pointer other than seed_dev, B outside [1, GT_MEL_MAX_B], F_max outside
+ * [1, GT_MEL_MAX_FRAMES], n_mel outside [1, GT_MEL_MAX_N_MEL], a stride below F_max (non-positive included): GT_E_INVAL; mag, spec or
+ * mel_pinv not 16-byte, mel, n_frames or seed_dev not 4-byte aligned: GT_E_ALIGN. */
+int gt_gl_from_mel(const float* mel, int64_t stride_b, int64_t stride_c, const int32_t* n_frames, int B, int F_max, int n_mel,
+                   const float* mel_pinv, uint32_t seed, const uint32_t* seed_dev, float* mag, float* spec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

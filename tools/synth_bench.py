@@ -35,6 +35,16 @@ launches per contour), eager with noise_key="frame" on uniform frame rows (rows_
 shape: replay over eager-frame, eager-frame over eager-row, ragged over uniform frame rows.  Every repeat is recorded; output defaults
 to profiles/synth_graph_cfg5_bench.json.
 
+--graph --wav: whole calls to SAMPLES, 30 Griffin-Lim iterations, the same model and the same two shapes, three
+ways alternating in one process, three windows of >= 0.5 s each, a host clock ending in a synchronise: (a) what a caller had before
+compile_synthesis(vocoder=) — the graph replayed to the mel, the lengths read back, GriffinLim.from_mel with torch phases; (a') the
+same with phases="counter" (one gt_gl_from_mel launch instead of the ATen ops and the phase tensor); (b) the ONE graph of
+compile_synthesis(vocoder=GriffinLim, vocoder_iters=30) and h.wav(); and, to split (a') into its parts, the text-to-mel replay alone
+and from_mel(phases="counter") alone on the batch's own mel.  The bench batch is RAGGED (train.synth_batch's text lengths, 5 frames per
+token, the longest at the capacity): the JSON records every utterance's frames, their total and the seconds of audio.  For the single
+utterance (b) is also compiled at 1600 frames, to show what unused capacity costs a loop whose every launch is sized by it.  Every window is recorded; output defaults to
+profiles/synth_wav_bench.json.
+
 --tokens BxT[,BxT...] (--infer, --graph): texts of a given length instead of the two shapes above, e.g. `--tokens 1x1024,8x600` (long
 texts); --front off|on|both picks the variants of --infer.
 
@@ -56,6 +66,7 @@ ap.add_argument("--repeats", type=int, default=2)
 ap.add_argument("--infer", action="store_true", help="time whole infer calls, device front end off / on")
 ap.add_argument("--graph", action="store_true", help="time eager infer against the captured synthesis graph (compile_synthesis)")
 ap.add_argument("--cfg5", action="store_true", help="the full cfg 5 model: eager row / frame keyed calls (and with --graph the captured graph)")
+ap.add_argument("--wav", action="store_true", help="--graph: time whole calls to samples, mel graph + from_mel against the one graph with a vocoder")
 ap.add_argument("--queue", type=int, default=16, help="--graph: replays queued before one synchronisation")
 ap.add_argument("--tokens", default=None, help="--infer / --graph: the shapes as BxT[,BxT...], B texts of T tokens each (5 T frames), "
                 "e.g. 1x1024,8x600, instead of the two default shapes")
@@ -355,6 +366,117 @@ def graph_main():
         f.write("\n")
 
 
+def wav_main():
+    import math
+    import time
+    from glow_tts_amd import audio
+    iters, windows = 30, max(3, opt.repeats)
+    gen = models.FlowGenerator(148, 192, 768, 256, 80, use_sdp=False, kernel_size=3, n_heads=2, n_layers_enc=6, p_dropout=0.1,
+                               n_blocks_dec=NB, kernel_size_dec=5, dilation_rate=1, n_block_layers=NL, p_dropout_dec=0.05, n_sqz=2,
+                               window_size=4, mean_only=True, prenet=True).eval()
+    with torch.no_grad():
+        for b in range(NB):
+            torch.nn.init.normal_(gen.decoder.flows[3 * b + 2].end.weight, std=0.01)
+        gen.encoder.proj_w.proj.weight.zero_()                         # 5 frames per token: ceil(4.9)
+        gen.encoder.proj_w.proj.bias.fill_(math.log(4.9))
+    gen = gen.to(dev)
+    assert gen.store_inverse(fused_reverse=True, device_front=True) == (True, True)
+    voc = audio.GriffinLim(audio.TacotronSTFT(n_mel_channels=80)).to(dev)
+    ids_b, t_x, _, _ = train.synth_batch(32, 150, 800, 0, "cpu")
+    g = torch.Generator().manual_seed(5)
+    one = torch.randint(1, 148, (1, 160), generator=g)
+    cases = []
+    if opt.shape != "single":
+        cases.append(("bench batch: B = 32, T_x <= 150, 5 frames per token", ids_b, t_x, int(ids_b.shape[1]), 5 * int(ids_b.shape[1]), ()))
+    if opt.shape != "batch":
+        cases.append(("one utterance, 160 tokens = 800 frames", one, torch.tensor([160]), 160, 800, (1600,)))
+    out = dict(device=torch.cuda.get_device_name(0), model="cfg 2: 6 encoder layers, 12 blocks x 4 layers, H = 192, eval, "
+               "store_inverse(fused_reverse=True, device_front=True); GriffinLim over TacotronSTFT(80 mel channels)", griffin_lim_iterations=iters,
+               seconds_per_window=opt.seconds, windows=windows, clock="time.perf_counter between two torch.cuda.synchronize()", shapes=[])
+    for name, ids, xl, Tx_cap, Ty_cap, spare_caps in cases:
+        B = int(ids.shape[0])
+        plain = gen.compile_synthesis(B, Tx_cap, Ty_cap)
+        whole = gen.compile_synthesis(B, Tx_cap, Ty_cap, vocoder=voc, vocoder_iters=iters)
+
+        def two_steps(n, phases):
+            for _ in range(n):
+                h = plain(ids, xl, seed=7, noise_scale=0.667)
+                frames = [2 * (v // 2) for v in h.lengths()]                       # the readback
+                wav, _ = voc.from_mel(h.mel(), torch.tensor(frames, dtype=torch.int32, device=dev), mel_lengths_host=frames, n_iters=iters, seed=7,
+                                      phases=phases)
+            return wav
+
+        def one_graph(n):
+            for _ in range(n):
+                wav, _ = whole(ids, xl, seed=7, noise_scale=0.667).wav()           # waits for this call's readback
+            return wav
+
+        h0 = plain(ids, xl, seed=7, noise_scale=0.667)
+        frames0 = [2 * (v // 2) for v in h0.lengths()]                             # the batch is ragged: what the loop really works on
+        mel0 = h0.mel(clone=True)
+        frames0_dev = torch.tensor(frames0, dtype=torch.int32, device=dev)
+
+        def mel_alone(n):
+            for _ in range(n):
+                y = plain(ids, xl, seed=7, noise_scale=0.667).mel()
+            return y
+
+        def loop_alone(n):                                                         # the eager counter path on a mel that is already there
+            for _ in range(n):
+                wav, _ = voc.from_mel(mel0, frames0_dev, mel_lengths_host=frames0, n_iters=iters, seed=7, phases="counter")
+            return wav
+
+        runs = {"mel_graph_then_from_mel_torch": lambda n: two_steps(n, "torch"), "mel_graph_then_from_mel_counter": lambda n: two_steps(n, "counter"),
+                "one_graph_wav": one_graph, "mel_graph_alone": mel_alone, "from_mel_counter_alone": loop_alone}
+        spare = {}
+        for cap in spare_caps:                                                     # the same call in a graph of unused capacity: every launch of the loop is sized by it
+            spare[cap] = gen.compile_synthesis(B, Tx_cap, cap, vocoder=voc, vocoder_iters=iters)
+            runs[f"one_graph_wav_max_frames_{cap}"] = lambda n, w=spare[cap]: [w(ids, xl, seed=7, noise_scale=0.667).wav()[0] for _ in range(n)][-1]
+        rec = dict(name=name, B=B, Tx=int(ids.shape[1]), max_tokens=Tx_cap, max_frames=Ty_cap, frames_per_utterance=frames0,
+                   frames_total=sum(frames0), frames_mean_over_max_frames=round(sum(frames0) / (B * Ty_cap), 4),
+                   audio_seconds_at_22050_hz=round(sum(256 * (F - 1) for F in frames0) / 22050.0, 2), variants={})
+        res = {k: fn(2) for k, fn in runs.items()}
+        torch.cuda.synchronize()
+        rec["wav_samples_per_row"] = int(res["one_graph_wav"].shape[1])
+        rec["one_graph_equals_from_mel_counter"] = bool(torch.equal(res["one_graph_wav"], res["mel_graph_then_from_mel_counter"]))
+        with _lib.record_calls() as names:
+            two_steps(1, "torch")
+        rec["variants"]["mel_graph_then_from_mel_torch"] = dict(c_abi_entries_outside_the_graph=len([n for n in names if not n.endswith("_bytes")]), ms_per_call=[])
+        with _lib.record_calls() as names:
+            two_steps(1, "counter")
+        rec["variants"]["mel_graph_then_from_mel_counter"] = dict(c_abi_entries_outside_the_graph=len([n for n in names if not n.endswith("_bytes")]), ms_per_call=[])
+        rec["variants"]["one_graph_wav"] = dict(c_abi_entries_inside_the_graph=whole.captured_entries, c_abi_entries_outside_the_graph=0,
+                                                overflows=whole.overflows, ms_per_call=[])
+        rec["variants"]["mel_graph_alone"] = dict(what="the text-to-mel graph replayed and its mel taken, no vocoder", ms_per_call=[])
+        rec["variants"]["from_mel_counter_alone"] = dict(what="from_mel(phases=\"counter\") on this batch's mel and lengths, no text-to-mel call",
+                                                         c_abi_entries=2 + 2 * iters, ms_per_call=[])
+        for cap, w in spare.items():
+            rec["variants"][f"one_graph_wav_max_frames_{cap}"] = dict(max_frames=cap, c_abi_entries_inside_the_graph=w.captured_entries,
+                                                                      equals_one_graph_wav=bool(torch.equal(res[f"one_graph_wav_max_frames_{cap}"], res["one_graph_wav"])),
+                                                                      ms_per_call=[])
+        for _ in range(windows):
+            for k, fn in runs.items():
+                torch.cuda.synchronize(); t0 = time.perf_counter(); fn(3); torch.cuda.synchronize()
+                n = max(3, int(opt.seconds / ((time.perf_counter() - t0) / 3)) + 1)
+                torch.cuda.synchronize(); t0 = time.perf_counter(); fn(n); torch.cuda.synchronize()
+                rec["variants"][k]["ms_per_call"].append(round((time.perf_counter() - t0) * 1e3 / n, 4))
+        for v in rec["variants"].values():
+            t = v["ms_per_call"]
+            v["ms_mean"], v["ms_spread"] = round(sum(t) / len(t), 4), round(max(t) - min(t), 4)
+        base = rec["variants"]["mel_graph_then_from_mel_torch"]["ms_mean"]
+        for k, v in rec["variants"].items():
+            if k != "mel_graph_then_from_mel_torch":
+                v["over_mel_graph_then_from_mel_torch_time"] = round(v["ms_mean"] / base, 4)
+        print(f'{name}: ' + "; ".join(f'{k} {v["ms_mean"]:.3f} ms (+- {v["ms_spread"]:.3f})' for k, v in rec["variants"].items()), flush=True)
+        out["shapes"].append(rec)
+        del plain, whole, spare
+    path = opt.json or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "synth_wav_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 def cfg5_main():
     import time
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -462,4 +584,4 @@ def cfg5_main():
         f.write("\n")
 
 
-cfg5_main() if opt.cfg5 else graph_main() if opt.graph else infer_main() if opt.infer else main()
+cfg5_main() if opt.cfg5 else wav_main() if opt.graph and opt.wav else graph_main() if opt.graph else infer_main() if opt.infer else main()
