@@ -36,6 +36,64 @@ class CpuWaveError(_lib.CpuTensorError, ValueError):
     """a CPU waveform: the wrong value for a device op (ValueError), and the CpuTensorError every other op here raises"""
 
 
+class _Cached:
+    """one value derived from buffers, rebuilt when the (data_ptr, _version) of any of them changes (load_state_dict, .to(), an
+    in-place edit): the packed images and mel_pinv"""
+    def __init__(self):
+        self.key, self.value = None, None
+
+    def get(self, tensors, build):
+        key = tuple(v for t in tensors for v in (t.data_ptr(), t._version))
+        if self.key != key:
+            self.value, self.key = build(), key
+        return self.value
+
+
+def _device_rows(y):
+    """waveform rows as the kernels take them (16-byte aligned rows of a 4-element pitch): y itself, or a zero-padded copy"""
+    if not y.is_cuda:
+        raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
+    if y.dim() != 2 or y.dtype not in (torch.float32, torch.int16):
+        raise ValueError(f"waveforms are [B, T] fp32 or int16, got {tuple(y.shape)} {y.dtype}")
+    B, T = y.shape
+    if y.stride(1) != 1 or y.stride(0) % 4 or y.data_ptr() % 16:
+        padded = y.new_zeros(B, (T + 3) // 4 * 4)
+        padded[:, :T] = y
+        y = padded
+    return y
+
+
+def _wav_len_arg(wav_len, y):
+    if wav_len.device != y.device or wav_len.dtype != torch.int32 or wav_len.numel() != y.shape[0]:
+        raise ValueError("wav_len must be int32 [B] on the waveforms' device")
+    return wav_len.contiguous()
+
+
+def _ragged_frames(y, lengths, lengths_host, hop, min_len=None):
+    """padded rows y [B, T] and their sample counts (`lengths`, default T) -> (the counts on y's device, in their own dtype (int32 when
+    defaulted), F_max frames per output row): F_max = 1 + max(lengths) // hop where the host knows the lengths (lengths_host, or CPU
+    `lengths`), else 1 + T // hop with no synchronisation.  TacotronSTFT.mel_spectrogram and YIN.f0 both choose it here.  min_len (mel
+    only: filter_length / 2): a length <= it has no reflect padding, a ValueError where the host knows it."""
+    if not y.is_cuda:
+        raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
+    B, T = y.shape
+    if lengths is None:
+        if min_len is not None and T <= min_len:
+            raise ValueError(f"{T} samples: reflect padding needs more than {min_len}")
+        return torch.full((B,), T, dtype=torch.int32, device=y.device), 1 + T // hop
+    if lengths_host is None and not lengths.is_cuda:
+        lengths_host = lengths.tolist()
+    F_max = 1 + T // hop
+    if lengths_host is not None:
+        lengths_host = [int(v) for v in lengths_host]
+        if len(lengths_host) != B or max(lengths_host) > T:
+            raise ValueError(f"lengths {lengths_host} do not fit waveforms {tuple(y.shape)}")
+        if min_len is not None and min(lengths_host) <= min_len:
+            raise ValueError(f"an utterance of {min(lengths_host)} samples: reflect padding needs more than {min_len}")
+        F_max = 1 + max(lengths_host) // hop
+    return lengths.to(y.device, non_blocking=True), F_max
+
+
 def hann_periodic(win_length):
     """scipy.signal.get_window('hann', win_length, fftbins=True) in float64"""
     return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win_length, dtype=np.float64) / win_length)
@@ -95,44 +153,35 @@ class TacotronSTFT(nn.Module):
         self.n_mel_channels, self.sampling_rate = n_mel_channels, sampling_rate
         self.stft_fn = STFT(filter_length, hop_length, win_length)
         self.register_buffer("mel_basis", torch.from_numpy(mel_filterbank(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax)))
-        self._packed, self._packed_key = None, None
+        self._packed = _Cached()
 
-    # -- the fragment-order image of both buffers, rebuilt when either changes (load_state_dict, .to(), an in-place edit)
+    # -- the fragment-order image of both buffers, rebuilt when either changes
     def _image(self):
         fb, mb = self.stft_fn.forward_basis, self.mel_basis
-        key = (fb.data_ptr(), fb._version, mb.data_ptr(), mb._version)
-        if self._packed_key != key:
+        def build():
             if fb.dtype != torch.float32 or mb.dtype != torch.float32 or not fb.is_contiguous() or not mb.is_contiguous():
                 raise ValueError("forward_basis and mel_basis must be contiguous fp32 buffers")
             if mb.dim() != 2 or mb.shape[1] != self.stft_fn.filter_length // 2 + 1 or fb.shape[0] != 2 * mb.shape[1]:
                 raise ValueError(f"mel_basis {tuple(mb.shape)} does not fit forward_basis {tuple(fb.shape)}")
             packed = torch.empty(call.gt_mel_pack_bytes() // 4, dtype=torch.float32, device=fb.device)
             call.gt_mel_pack(fb, mb, self.stft_fn.filter_length, mb.shape[0], packed, _lib.current_stream(fb.device))
-            self._packed, self._packed_key = packed, key
-        return self._packed
+            return packed
+        return self._packed.get((fb, mb), build)
 
     def transform(self, y, wav_len, F_max, magnitudes=False):
         """the kernel call: y [B, T] fp32 / int16 on the device, wav_len device int32 [B], F_max frames per output row ->
         (mel [B, n_mel, F_max], energy [B, F_max], mag [B, 513, F_max] or None); no host synchronisation, capturable in a graph
         once the image exists (any earlier call)."""
-        if not y.is_cuda:
-            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
-        if y.dim() != 2 or y.dtype not in (torch.float32, torch.int16):
-            raise ValueError(f"waveforms are [B, T] fp32 or int16, got {tuple(y.shape)} {y.dtype}")
-        if wav_len.device != y.device or wav_len.dtype != torch.int32 or wav_len.numel() != y.shape[0]:
-            raise ValueError("wav_len must be int32 [B] on the waveforms' device")
-        B, T = y.shape
-        if y.stride(1) != 1 or y.stride(0) % 4 or y.data_ptr() % 16:          # the kernel takes 16-byte aligned rows of a 4-element pitch
-            padded = y.new_zeros(B, (T + 3) // 4 * 4)
-            padded[:, :T] = y
-            y = padded
+        y = _device_rows(y)
+        wav_len = _wav_len_arg(wav_len, y)
+        B = y.shape[0]
         fs = self.stft_fn
         n_mel = self.mel_basis.shape[0]
         packed = self._image()
         mel = torch.empty(B, n_mel, F_max, dtype=torch.float32, device=y.device)
         energy = torch.empty(B, F_max, dtype=torch.float32, device=y.device)
         mag = torch.empty(B, fs.filter_length // 2 + 1, F_max, dtype=torch.float32, device=y.device) if magnitudes else None
-        call.gt_mel_spectrogram(y, int(y.dtype == torch.int16), y.stride(0), wav_len.contiguous(), B, F_max, packed, fs.filter_length,
+        call.gt_mel_spectrogram(y, int(y.dtype == torch.int16), y.stride(0), wav_len, B, F_max, packed, fs.filter_length,
                                 fs.hop_length, fs.win_length, n_mel, CLIP_VAL, mel, energy, mag, _lib.current_stream(y.device))
         return mel, energy, mag
 
@@ -142,44 +191,13 @@ class TacotronSTFT(nn.Module):
         mel_lengths = 1 + lengths // hop, energy [B, 1, F_max]), every utterance transformed on its own (reflected about its own ends)
         and zero behind its frames.  F_max comes from the lengths when the host knows them (lengths_host, or CPU `lengths`), else from
         T with no synchronisation.  A length <= filter_length / 2 has no reflect padding: ValueError where the host knows it."""
-        if not y.is_cuda:
-            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
-        hop, half = self.stft_fn.hop_length, self.stft_fn.filter_length // 2
-        B, T = y.shape
-        if lengths is None:
-            if T <= half:
-                raise ValueError(f"{T} samples: reflect padding needs more than {half}")
-            wav_len = torch.full((B,), T, dtype=torch.int32, device=y.device)
-            mel, energy, _ = self.transform(y, wav_len, 1 + T // hop)
-            return mel, energy
-        if lengths_host is None and not lengths.is_cuda:
-            lengths_host = lengths.tolist()
-        if lengths_host is not None:
-            lengths_host = [int(v) for v in lengths_host]
-            if len(lengths_host) != B or max(lengths_host) > T:
-                raise ValueError(f"lengths {lengths_host} do not fit waveforms {tuple(y.shape)}")
-            if min(lengths_host) <= half:
-                raise ValueError(f"an utterance of {min(lengths_host)} samples: reflect padding needs more than {half}")
-            F_max = 1 + max(lengths_host) // hop
-        else:
-            F_max = 1 + T // hop
-        lengths = lengths.to(y.device, non_blocking=True)
+        hop = self.stft_fn.hop_length
+        ragged = lengths is not None
+        lengths, F_max = _ragged_frames(y, lengths, lengths_host, hop, min_len=self.stft_fn.filter_length // 2)
         mel, energy, _ = self.transform(y, lengths.to(torch.int32), F_max)
+        if not ragged:
+            return mel, energy
         return mel, 1 + lengths // hop, energy.unsqueeze(1)
-
-
-def _device_rows(y):
-    """waveform rows as the kernels take them (16-byte aligned rows of a 4-element pitch): y itself, or a zero-padded copy"""
-    if not y.is_cuda:
-        raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
-    if y.dim() != 2 or y.dtype not in (torch.float32, torch.int16):
-        raise ValueError(f"waveforms are [B, T] fp32 or int16, got {tuple(y.shape)} {y.dtype}")
-    B, T = y.shape
-    if y.stride(1) != 1 or y.stride(0) % 4 or y.data_ptr() % 16:
-        padded = y.new_zeros(B, (T + 3) // 4 * 4)
-        padded[:, :T] = y
-        y = padded
-    return y
 
 
 class YIN(nn.Module):
@@ -199,13 +217,12 @@ class YIN(nn.Module):
         (f0 [B, F_max], harm or None, argmin_f0 or None); frame i of an utterance lands at position lead + i (lead: pad_frames),
         every other position is 0.  No host synchronisation, capturable in a graph."""
         y = _device_rows(y)
-        if wav_len.device != y.device or wav_len.dtype != torch.int32 or wav_len.numel() != y.shape[0]:
-            raise ValueError("wav_len must be int32 [B] on the waveforms' device")
+        wav_len = _wav_len_arg(wav_len, y)
         B = y.shape[0]
         f0 = torch.empty(B, F_max, dtype=torch.float32, device=y.device)
         harm = torch.empty_like(f0) if aux else None
         amin = torch.empty_like(f0) if aux else None
-        call.gt_yin_f0(y, int(y.dtype == torch.int16), y.stride(0), wav_len.contiguous(), B, F_max, self.frame_length, self.hop_length,
+        call.gt_yin_f0(y, int(y.dtype == torch.int16), y.stride(0), wav_len, B, F_max, self.frame_length, self.hop_length,
                        self.tau_min, self.tau_max, float(self.sampling_rate), float(self.harm_thresh),
                        self.pad_frames if lead is None else lead, f0, harm, amin, _lib.current_stream(y.device))
         return f0, harm, amin
@@ -215,24 +232,8 @@ class YIN(nn.Module):
         chosen as TacotronSTFT.mel_spectrogram(y, lengths) chooses it (from the lengths where the host knows them, else from T with
         no synchronisation): the contour lines up with that call's mel and energy, zero behind every utterance's frames.
         aux=True: (f0, harm [B, 1, F_max], argmin_f0 [B, 1, F_max])."""
-        if not y.is_cuda:
-            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
-        B, T = y.shape
-        if lengths is None:
-            wav_len = torch.full((B,), T, dtype=torch.int32, device=y.device)
-            F_max = 1 + T // self.hop_length
-        else:
-            if lengths_host is None and not lengths.is_cuda:
-                lengths_host = lengths.tolist()
-            if lengths_host is not None:
-                lengths_host = [int(v) for v in lengths_host]
-                if len(lengths_host) != B or max(lengths_host) > T:
-                    raise ValueError(f"lengths {lengths_host} do not fit waveforms {tuple(y.shape)}")
-                F_max = 1 + max(lengths_host) // self.hop_length
-            else:
-                F_max = 1 + T // self.hop_length
-            wav_len = lengths.to(y.device, non_blocking=True).to(torch.int32)
-        f0, harm, amin = self.transform(y, wav_len, F_max, aux=aux)
+        lengths, F_max = _ragged_frames(y, lengths, lengths_host, self.hop_length)
+        f0, harm, amin = self.transform(y, lengths.to(torch.int32), F_max, aux=aux)
         if aux:
             return f0.unsqueeze(1), harm.unsqueeze(1), amin.unsqueeze(1)
         return f0.unsqueeze(1)
@@ -280,7 +281,8 @@ def inverse_basis64(filter_length=1024, hop_length=256, win_length=1024):
 
 
 def spec_unpack(spec, B, F_max):
-    """dev / tests: the kernels' spectrum workspace (include/glowtts_hip.h, gt_gl_*) -> (re, im) [B, 513, F_max]; Im of bin 512 is 0"""
+    """dev / tests: the kernels' spectrum workspace (include/glowtts_hip.h, gt_gl_*) -> (re, im) [B, 513, F_max]; Im of bin 512 is 0.
+    The Python mirror of the layout that csrc/stft_tile.h defines (frames_padded, spec_row_floats, spec_slot, spec_nyq_slot)."""
     tile = call.gt_gl_tile_frames()
     Fp = (F_max + tile - 1) // tile * tile
     rows = spec.view(B, Fp * 1025)
@@ -335,19 +337,18 @@ class InverseSTFT(nn.Module):
         self.filter_length, self.hop_length, self.win_length = filter_length, hop_length, win_length
         basis = inverse_basis64(filter_length, hop_length, win_length).astype(np.float32)
         self.register_buffer("inverse_basis", torch.from_numpy(basis)[:, None, :].contiguous())
-        self._packed, self._packed_key = None, None
+        self._packed = _Cached()
 
     def _image(self):
         ib = self.inverse_basis
-        key = (ib.data_ptr(), ib._version)
-        if self._packed_key != key:
+        def build():
             _check_geometry(self)
             if ib.dtype != torch.float32 or not ib.is_contiguous() or ib.numel() != 1026 * 1024:
                 raise ValueError("inverse_basis must be a contiguous fp32 [1026, 1, 1024] buffer")
             packed = torch.empty(call.gt_gl_pack_bytes() // 4, dtype=torch.float32, device=ib.device)
             call.gt_gl_pack(ib, self.filter_length, packed, _lib.current_stream(ib.device))
-            self._packed, self._packed_key = packed, key
-        return self._packed
+            return packed
+        return self._packed.get((ib,), build)
 
     def workspace(self, B, F_max, device):
         return torch.empty(call.gt_gl_spec_bytes(B, F_max) // 4, dtype=torch.float32, device=device)
@@ -395,21 +396,19 @@ class GriffinLim(nn.Module):
         self.stft_fn = stft.stft_fn if isinstance(stft, TacotronSTFT) else stft
         _check_geometry(self.stft_fn)
         self.istft = InverseSTFT(self.stft_fn.filter_length, self.stft_fn.hop_length, self.stft_fn.win_length)
-        self._fwd_packed, self._fwd_key = None, None
-        self._mel_pinv, self._mel_pinv_key = None, None
+        self._fwd_packed, self._mel_pinv = _Cached(), _Cached()
 
     def _forward_image(self):
         if isinstance(self.stft, TacotronSTFT):
             return self.stft._image()
         fb = self.stft_fn.forward_basis
-        key = (fb.data_ptr(), fb._version)
-        if self._fwd_key != key:                                              # a plain STFT has no mel basis: the image's mel part is zeros
+        def build():                                                          # a plain STFT has no mel basis: the image's mel part is zeros
             if fb.dtype != torch.float32 or not fb.is_contiguous():
                 raise ValueError("forward_basis must be a contiguous fp32 buffer")
             packed = torch.empty(call.gt_mel_pack_bytes() // 4, dtype=torch.float32, device=fb.device)
             call.gt_mel_pack(fb, torch.zeros(1, 513, dtype=torch.float32, device=fb.device), 1024, 1, packed, _lib.current_stream(fb.device))
-            self._fwd_packed, self._fwd_key = packed, key
-        return self._fwd_packed
+            return packed
+        return self._fwd_packed.get((fb,), build)
 
     def project(self, wav, magnitudes, n_frames, spec):
         """kernel call, the analysis half: spec = magnitudes * X / |X|, X the STFT of wav's rows (each reflected about its own ends)"""
@@ -450,11 +449,8 @@ class GriffinLim(nn.Module):
         if not isinstance(self.stft, TacotronSTFT):
             raise ValueError("from_mel needs a TacotronSTFT (a mel basis)")
         mb = self.stft.mel_basis
-        key = (mb.data_ptr(), mb._version)
-        if self._mel_pinv_key != key:
-            pinv = np.linalg.pinv(mb.detach().cpu().numpy().astype(np.float64))
-            self._mel_pinv, self._mel_pinv_key = torch.from_numpy(pinv.astype(np.float32)).to(mb.device), key
-        return self._mel_pinv
+        return self._mel_pinv.get((mb,), lambda: torch.from_numpy(
+            np.linalg.pinv(mb.detach().cpu().numpy().astype(np.float64)).astype(np.float32)).to(mb.device))
 
     def from_mel(self, mel, mel_lengths=None, mel_lengths_host=None, n_iters=30, angles=None, seed=0, phases="torch"):
         """log-mel [B, n_mel, F] (TacotronSTFT.mel_spectrogram's output) -> wav, or (wav, wav_lengths) with mel_lengths.  The

@@ -3,12 +3,13 @@
 // n_fft = win = 1024, hop = 256, in exact fp32 on v_mfma_f32_32x32x2_f32 (k-ordered fmaf chains).
 //
 //   spectrum   the complex spectrum Y [513 bins][F frames] of a batch lives in a device workspace in the FRAGMENT ORDER of the
-//              inverse's B operand: per utterance [Fp / 32 frame groups][64 bin groups][64 lanes][re 4 | im 4] with lane =
-//              32 (bin & 1) + (frame & 31), word = (bin & 7) >> 1, bin group = bin >> 3 (bins 0..511), then Re of bin 512 [Fp];
-//              Fp = F_max rounded up to 64.  gt_gl_polar and gt_gl_project write it (zeros from frame F_b on), gt_istft reads
-//              it with two 16-byte loads per lane, frame tile and 4 K steps.  Im of bins 0 and 512 meets a zero basis row: not kept.
-//   project    the analysis half = mel_front.hip's folded DFT (same packed basis image, same staging, K = 512) with the epilogue
-//              Y = M X / |X| in registers (re and im of a bin sit in one lane); |X|^2 == 0 gives (M, 0).  No atan2f / cosf / sinf.
+//              inverse's B operand (stft_tile.h: the layout is defined there, every index below goes through spec_slot /
+//              spec_nyq_slot but gt_istft's two fragment pointers, which are pinned to spec_slot by a static_assert).  gt_gl_polar
+//              and gt_gl_project write it (zeros from frame F_b on), gt_istft reads it with two 16-byte loads per lane, frame
+//              tile and 4 K steps.
+//   project    the analysis half = stft_tile.h's folded DFT tile, the functions gt_mel_front_kernel runs (same packed basis image,
+//              same staging, K = 512), with the epilogue Y = M X / |X| in registers (re and im of a bin sit in one lane);
+//              |X|^2 == 0 gives (M, 0).  No atan2f / cosf / sinf.
 //   istft      the inverse folds like the forward: the windowed inverse basis is even (cos rows) / odd (sin rows) about n = 512, so
 //                a[n] = sum_k ibc[k][n] Re[k],  b[n] = sum_k ibs[k][n] Im[k],  x[n] = a[n] + b[n],  x[1024 - n] = a[n] - b[n]
 //              for n = 1..512 (x[0] = 0: w[0] = 0; b[512] = 0).  One workgroup = 64 frames h0 - 1 .. h0 + 62 of one utterance = the
@@ -23,27 +24,22 @@
 #include <cfloat>
 #include "common.h"
 #include "internal.h"
+#include "stft_tile.h"
 #include "../../include/glowtts_hip.h"
 
 namespace {
 
-constexpr int NFFT = 1024, HOP = 256, NBIN = 513;
-constexpr int TF = 64;                                   // frames per workgroup (both kernels)
+using namespace gtstft;                                  // TF frames per workgroup (both kernels), the tile, the spectrum layout
+
 constexpr int TH = TF - 3;                               // output hops an istft workgroup completes
-constexpr int SPAN = (TF - 1) * HOP + NFFT;              // samples a project tile spans
-constexpr int LDS_FLOATS = 17220;                        // as mel_front.hip: SPAN + one pad word per 256, rounded to 16 bytes
-static_assert(SPAN - 1 + ((SPAN - 1) >> 8) < LDS_FLOATS, "sample buffer");
-constexpr int MEL_OFF_NYQ = 16 * 64 * 64 * 8;            // gt_mel_pack's image: the folded basis, then bin 512's folded cos row [512]
 
 // the inverse's packed image (floats): basis [16 column tiles][64 bin groups][64 lanes][cos 4 | sin 4], bin 512's row by
 // [column tile][row] [512], the squared window [1024]
-constexpr int OFF_NYQ = 16 * 64 * 64 * 8;
-constexpr int OFF_W2 = OFF_NYQ + 512;
-constexpr int PACK_FLOATS = OFF_W2 + NFFT;
+constexpr int INV_OFF_NYQ = 16 * 64 * 64 * 8;
+constexpr int INV_OFF_W2 = INV_OFF_NYQ + 512;
+constexpr int INV_PACK_FLOATS = INV_OFF_W2 + NFFT;
 constexpr int XS = TF + 1;                               // row pitch of the pass buffer
 constexpr int XBUF_FLOATS = 4 * 2 * 32 * XS;
-
-__device__ __forceinline__ int acc_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 
 // column n of row i of column tile t = 4 pass + wave
 __device__ __forceinline__ int tile_n(int t, int i)
@@ -67,30 +63,27 @@ __device__ __forceinline__ int src_row(int n)
   return (w * 2 + pm) * 32 + ((r - 1) & 31);
 }
 
-__host__ __device__ __forceinline__ int frames_padded(int F_max) { return (F_max + TF - 1) / TF * TF; }
-__device__ __forceinline__ size_t spec_row_floats(int Fp) { return (size_t)Fp * 1025; }
-
 __global__ __launch_bounds__(256) void gt_gl_pack_kernel(const float* __restrict__ ib, float* __restrict__ out)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= PACK_FLOATS) return;
+  if (i >= INV_PACK_FLOATS) return;
   float v;
-  if (i < OFF_NYQ) {
+  if (i < INV_OFF_NYQ) {
     const int s = i & 3, cs = (i >> 2) & 1, lane = (i >> 3) & 63, tg = (i >> 9) & 63, t = i >> 15;
     const int n = tile_n(t, lane & 31), k = 2 * (4 * tg + s) + (lane >> 5);
     if (cs == 0) v = ib[(size_t)k * NFFT + n];
     else v = n == 512 ? 0.f : ib[(size_t)(NBIN + k) * NFFT + n];
-  } else if (i < OFF_W2) {
-    const int idx = i - OFF_NYQ;
+  } else if (i < INV_OFF_W2) {
+    const int idx = i - INV_OFF_NYQ;
     v = ib[(size_t)512 * NFFT + tile_n(idx >> 5, idx & 31)];
   } else {
-    const float w = ib[i - OFF_W2] * 4096.0f;             // row 0 of the inverse basis is the window / (1024 * 4): exact
+    const float w = ib[i - INV_OFF_W2] * 4096.0f;            // row 0 of the inverse basis is the window / (1024 * 4): exact
     v = w * w;
   }
   out[i] = v;
 }
 
-// one thread = one lane's 32 bytes of the spectrum image: bins 8 tg + 2 s + (lane >> 5), s = 0..3, of frame 32 g + (lane & 31)
+// one thread = one slot of the spectrum image: bins spec_bin(tg, lane, s), s = 0..3, of frame spec_frame(g, lane)
 __global__ __launch_bounds__(256) void gt_gl_polar_kernel(const float* __restrict__ mag, const float* __restrict__ phase,
                                                           const int32_t* __restrict__ n_frames, int F_max, int Fp,
                                                           float* __restrict__ spec)
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(256) void gt_gl_polar_kernel(const float* __restric
   const int b = blockIdx.y;
   const int idx = blockIdx.x * 256 + threadIdx.x;         // [Fp / 32][64][64]
   const int lane = idx & 63, tg = (idx >> 6) & 63, g = idx >> 12;
-  const int f = g * 32 + (lane & 31), hk = lane >> 5;
+  const int f = spec_frame(g, lane);
   int Fb = n_frames[b];
   Fb = Fb < 2 ? 0 : (Fb < F_max ? Fb : F_max);
   float* sb = spec + (size_t)b * spec_row_floats(Fp);
@@ -107,7 +100,7 @@ __global__ __launch_bounds__(256) void gt_gl_polar_kernel(const float* __restric
     float m[4], p[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const size_t a = ((size_t)b * NBIN + 8 * tg + 2 * s + hk) * F_max + f;
+      const size_t a = ((size_t)b * NBIN + spec_bin(tg, lane, s)) * F_max + f;
       m[s] = mag[a]; p[s] = phase[a];
     }
 #pragma unroll
@@ -117,16 +110,16 @@ __global__ __launch_bounds__(256) void gt_gl_polar_kernel(const float* __restric
       re[s] = m[s] * cs; im[s] = m[s] * sn;
     }
   }
-  float4* o = reinterpret_cast<float4*>(sb) + (size_t)idx * 2;
+  float4* o = reinterpret_cast<float4*>(sb) + spec_slot(g, tg, lane);
   o[0] = make_float4(re[0], re[1], re[2], re[3]);
   o[1] = make_float4(im[0], im[1], im[2], im[3]);
-  if (tg == 0 && hk == 0) {
+  if (tg == 0 && lane < 32) {
     float v = 0.f;
     if (f < Fb) {
       const size_t a = ((size_t)b * NBIN + 512) * F_max + f;
       v = mag[a] * cosf(phase[a]);
     }
-    sb[(size_t)Fp * 1024 + f] = v;
+    sb[spec_nyq_slot(Fp, f)] = v;
   }
 }
 
@@ -144,54 +137,20 @@ __global__ __launch_bounds__(256, 2) void gt_gl_project_kernel(const float* __re
   Fb = Fb < 2 ? 0 : Fb;
   const int L = HOP * (Fb - 1);                          // samples of this utterance
   float* sb = spec + (size_t)b * spec_row_floats(Fp);
-  float4* img = reinterpret_cast<float4*>(sb) + (size_t)(f0 >> 5) * 4096 * 2;   // the tile's two frame groups
+  float4* sb4 = reinterpret_cast<float4*>(sb);
+  const int g0 = f0 >> 5;                                // the tile's two frame groups: g0, g0 + 1
 
   if (f0 >= Fb) {                                        // a tile past the utterance's end: zeros, no sample is read
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int idx = tid; idx < 2 * 4096 * 2; idx += 256) img[idx] = z;
-    if (tid < TF) sb[(size_t)Fp * 1024 + f0 + tid] = 0.f;
+    float4* img = sb4 + spec_slot(g0, 0, 0);
+    for (int idx = tid; idx < 2 * SPEC_GROUP_F4; idx += 256) img[idx] = z;
+    if (tid < TF) sb[spec_nyq_slot(Fp, f0 + tid)] = 0.f;
     return;
   }
 
-  // ---- stage the tile's samples: reflected about the utterance's own ends, the index clamped into [0, L) whatever L is
-  {
-    const int s0 = f0 * HOP - NFFT / 2;
-    const float* wf = wav + (size_t)b * ld_wav;
-    constexpr int TRIPS = SPAN / 256, UNR = 8;            // 67 samples per thread, 8 loads in flight at a time
-    static_assert(TRIPS * 256 == SPAN, "whole trips");
-#pragma unroll
-    for (int t0 = 0; t0 < TRIPS; t0 += UNR) {
-      float v[UNR];
-#pragma unroll
-      for (int u = 0; u < UNR; ++u)
-        if (t0 + u < TRIPS) {
-          int s = s0 + (t0 + u) * 256 + tid;
-          if (s < 0) s = -s;
-          if (s >= L) s = 2 * (L - 1) - s;
-          s = s < 0 ? 0 : (s > L - 1 ? L - 1 : s);
-          v[u] = wf[s];
-        }
-#pragma unroll
-      for (int u = 0; u < UNR; ++u)
-        if (t0 + u < TRIPS) {
-          const int p = (t0 + u) * 256 + tid;
-          lds[p + (p >> 8)] = v[u];
-        }
-    }
-  }
+  stage_tile(lds, wav + (size_t)b * ld_wav, L, f0, tid);
   __syncthreads();
-
-  // ---- bin 512 on the VALU: thread (frame tid & 63, quarter w) sums 128 folded samples in m order
-  float nyq_part = 0.f;
-  {
-    const int base = lane * 257;
-    const float* nq = packed + MEL_OFF_NYQ + w * 128;
-#pragma unroll 16
-    for (int m = 0; m < 128; ++m) {
-      const int n = 1 + w * 128 + m, nd = NFFT - n;
-      nyq_part = fmaf(nq[m], lds[base + n + (n >> 8)] + lds[base + nd + (nd >> 8)], nyq_part);
-    }
-  }
+  const float nyq_part = nyquist_partial(lds, packed, lane, w);
 
   // ---- the DFT: wave w, bin tiles 4 w .. 4 w + 3, 64 frames each; then Y = M X / |X| where it stands
   const int j = lane & 31, h = lane >> 5;
@@ -199,46 +158,7 @@ __global__ __launch_bounds__(256, 2) void gt_gl_project_kernel(const float* __re
   for (int pass = 0; pass < 4; ++pass) {
     const int bt = w * 4 + pass;
     f32x16_t ac[2], as[2];
-#pragma unroll
-    for (int ft = 0; ft < 2; ++ft)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { ac[ft][e] = 0.f; as[ft][e] = 0.f; }
-    const float4* ip = reinterpret_cast<const float4*>(packed) + ((size_t)bt * 64 * 64 + lane) * 2;
-    // the software pipeline of gt_mel_front_kernel, pinned the same way: the next group's basis fragments are requested before
-    // this group's 16 MFMAs, the next step's four samples before this step's four MFMAs
-    const auto samples = [&](int t, float (&xa)[2], float (&xd)[2]) {
-      const int n = 1 + 2 * t + h, nd = NFFT - n;
-      const int oa = n + (n >> 8), od = nd + (nd >> 8);
-#pragma unroll
-      for (int ft = 0; ft < 2; ++ft) {
-        const int base = (ft * 32 + j) * 257;
-        xa[ft] = lds[base + oa]; xd[ft] = lds[base + od];
-      }
-    };
-    float4 c4 = ip[0], s4 = ip[1];
-    float xa[2], xd[2];
-    samples(0, xa, xd);
-    for (int tg = 0; tg < 64; ++tg) {
-      const int tn = tg < 63 ? tg + 1 : tg;
-      const float4 nc = ip[(size_t)tn * 128], ns = ip[(size_t)tn * 128 + 1];
-      const float cc[4] = {c4.x, c4.y, c4.z, c4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        float nxa[2], nxd[2];
-        samples(4 * tg + s + 1, nxa, nxd);               // step 256 (behind the last) reads inside the frame and is dropped
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ft = 0; ft < 2; ++ft) {
-          ac[ft] = __builtin_amdgcn_mfma_f32_32x32x2f32(cc[s], xa[ft] + xd[ft], ac[ft], 0, 0, 0);
-          as[ft] = __builtin_amdgcn_mfma_f32_32x32x2f32(ss[s], xa[ft] - xd[ft], as[ft], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ft = 0; ft < 2; ++ft) { xa[ft] = nxa[ft]; xd[ft] = nxd[ft]; }
-      }
-      c4 = nc; s4 = ns;
-    }
+    dft_tile(lds, packed, bt, lane, ac, as);
     // register e of lane half h is bin k = 32 bt + acc_row(e, h): bin group 4 bt + (e >> 2), lane 32 (e & 1) + j, word
     // 2 h + ((e & 3) >> 1) — registers e and e + 2 (e & 3 < 2) are neighbours: one 8-byte store each for re and im
 #pragma unroll
@@ -258,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void gt_gl_project_kernel(const float* __re
 #pragma unroll
       for (int e = 0; e < 16; ++e)
         if ((e & 3) < 2) {
-          float* o = reinterpret_cast<float*>(img + (((size_t)ft * 64 + bt * 4 + (e >> 2)) * 64 + (e & 1) * 32 + j) * 2) + 2 * h;
+          float* o = reinterpret_cast<float*>(sb4 + spec_slot(g0 + ft, bt * 4 + (e >> 2), (e & 1) * 32 + j)) + 2 * h;
           *reinterpret_cast<float2*>(o) = make_float2(yr[e], yr[e + 2]);
           *reinterpret_cast<float2*>(o + 4) = make_float2(yi[e], yi[e + 2]);
         }
@@ -278,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void gt_gl_project_kernel(const float* __re
       const float m = mb[(size_t)512 * F_max + f];
       y = x < 0.f ? -m : m;
     }
-    sb[(size_t)Fp * 1024 + f] = y;
+    sb[spec_nyq_slot(Fp, f)] = y;
   }
 }
 
@@ -309,8 +229,11 @@ __global__ __launch_bounds__(256, 2) void gt_istft_kernel(const float* __restric
     const int f = fbase + ft * 32 + j;
     ok[ft] = f >= 0 && f < Fb;
     const int fc = ok[ft] ? f : 0;
+    // = spec_slot(fc >> 5, 0, h * 32 + (fc & 31)), bin group 0 (the loop strides 128), WRITTEN OUT: through the function this kernel is
+    // allocated differently and measured 1.2 % slower at B = 32 (profiles/stft_tile_bench.json); so it stays the parent's kernel
+    static_assert(spec_slot(3, 0, 37) == ((size_t)3 * 4096 + 37) * 2, "the written-out index is stft_tile.h's");
     yp[ft] = reinterpret_cast<const float4*>(sb) + ((size_t)(fc >> 5) * 4096 + h * 32 + (fc & 31)) * 2;
-    re512[ft] = ok[ft] ? sb[(size_t)Fp * 1024 + fc] : 0.f;
+    re512[ft] = ok[ft] ? sb[spec_nyq_slot(Fp, fc)] : 0.f;
   }
   const auto keep = [](bool k, const float4 v) { return make_float4(k ? v.x : 0.f, k ? v.y : 0.f, k ? v.z : 0.f, k ? v.w : 0.f); };
 
@@ -352,7 +275,7 @@ __global__ __launch_bounds__(256, 2) void gt_istft_kernel(const float* __restric
       for (int ft = 0; ft < 2; ++ft) { r4[ft] = keep(ok[ft], nr[ft]); i4[ft] = keep(ok[ft], ni[ft]); }
     }
     // bin 512 closes the cos chain; then x[n] = a + b and x[1024 - n] = a - b go to the pass buffer
-    const float* nq = packed + OFF_NYQ + t * 32;
+    const float* nq = packed + INV_OFF_NYQ + t * 32;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int row = acc_row(e, h);
@@ -377,7 +300,7 @@ __global__ __launch_bounds__(256, 2) void gt_istft_kernel(const float* __restric
       for (int q = 0; q < 4; ++q) {
         const int n = r + 256 * q;
         row[q] = n ? src_row(n) * XS : -1;               // n = 0: w[0] = 0, nothing to add
-        w2[q] = packed[OFF_W2 + n];
+        w2[q] = packed[INV_OFF_W2 + n];
       }
       for (int hl = w; hl < hops; hl += 4) {
         const int hop = h0 + hl;
@@ -401,17 +324,15 @@ __global__ __launch_bounds__(256, 2) void gt_istft_kernel(const float* __restric
 
 #define GT_ST(s) static_cast<hipStream_t>(s)
 
-bool gl_shape_bad(int B, int F_max) { return B <= 0 || B > GT_MEL_MAX_B || F_max <= 0 || F_max > GT_MEL_MAX_FRAMES; }
-
 }  // namespace
 
-extern "C" size_t gt_gl_pack_bytes(void) { return (size_t)PACK_FLOATS * sizeof(float); }
+extern "C" size_t gt_gl_pack_bytes(void) { return (size_t)INV_PACK_FLOATS * sizeof(float); }
 extern "C" int gt_gl_tile_frames(void) { return TF; }
 extern "C" int gt_gl_tile_hops(void) { return TH; }
 extern "C" size_t gt_gl_spec_bytes(int B, int F_max)
 {
   if (gl_shape_bad(B, F_max)) return 0;
-  return (size_t)B * frames_padded(F_max) * 1025 * sizeof(float);
+  return (size_t)B * spec_row_floats(frames_padded(F_max)) * sizeof(float);
 }
 
 extern "C" int gt_gl_pack(const float* inverse_basis, int n_fft, void* packed, void* stream)
@@ -419,7 +340,7 @@ extern "C" int gt_gl_pack(const float* inverse_basis, int n_fft, void* packed, v
   if (!inverse_basis || !packed) return GT_E_INVAL;
   if (n_fft != NFFT) return GT_E_UNSUPPORTED;
   if (!al16(inverse_basis) || !al16(packed)) return GT_E_ALIGN;
-  hipLaunchKernelGGL(gt_gl_pack_kernel, dim3((PACK_FLOATS + 255) / 256), dim3(256), 0, GT_ST(stream), inverse_basis,
+  hipLaunchKernelGGL(gt_gl_pack_kernel, dim3((INV_PACK_FLOATS + 255) / 256), dim3(256), 0, GT_ST(stream), inverse_basis,
                      static_cast<float*>(packed));
   return gt_launch_status(__func__);
 }

@@ -7,6 +7,9 @@
 
 static inline bool al16(const void* p) { return !((uintptr_t)p & 15); }   // NULL counts as aligned: optional pointers pass
 
+// the batch and frame limits every entry point on the spectrum workspace shares (griffin_lim.hip, gl_mel.hip)
+static inline bool gl_shape_bad(int B, int F_max) { return B <= 0 || B > GT_MEL_MAX_B || F_max <= 0 || F_max > GT_MEL_MAX_FRAMES; }
+
 // Dropout probability -> what the kernels take: keep an element when its 32-bit hash >= thresh = p * 2^32 (common.h drop_keep),
 // then scale by 1 / (1 - p); p <= 0 is no dropout (0, 1).  oracle/dropmask.py restates this rule: every kernel must agree with it.
 // p >= 1 is the caller's to refuse.

@@ -2,45 +2,26 @@
 // with the semantics of the reference's TacotronSTFT (stft.py:78-101 CUDA branch, commons.py:298-317, audio_processing.py:78-84)
 // applied to every utterance on its own: reflect padding about the utterance's own ends, n_fft = win = 1024, hop = 256.
 //
-// A framed, windowed DFT is a GEMM, here in exact fp32 on v_mfma_f32_32x32x2_f32 (a k-ordered fmaf chain, as in gt_logp_f32):
+// The framed, windowed DFT in exact fp32 is stft_tile.h's folded tile (the fold, the staged 64-frame tile, the MFMA operands and the
+// packed image's offsets are described and defined there; gt_gl_project_kernel runs the same functions).  This kernel's own:
 //
-//   fold      the periodic Hann window and cos are even about n = 512, sin is odd, and w[0] = 0, so
-//               re[k] = sum_{n=1..512} C[k][n] (x[n] + x[1024-n])      C[k][n] = basis[k][n], C[k][512] = basis[k][512] / 2 (exact)
-//               im[k] = sum_{n=1..511} S[k][n] (x[n] - x[1024-n])      S[k][n] = basis[513+k][n]
-//             K drops from 1024 to 512.  Bin 512 has no imaginary part (sin(pi n) = 0) and is a VALU dot product per frame.
-//   tile      one workgroup (4 waves) = 64 frames of one utterance x all 513 bins.  The 17 152 samples the 64 frames span are staged
-//             ONCE in LDS (reflected, int16 scaled by 1/32768) and the MFMA's frame operand is read from them in place: frame i,
-//             sample n is word 257 i + n + (n >> 8) (one pad word per 256: the 32 frames of a ds_read_b32 lane group fall on 32 banks).
-//   operands  A = the basis (bin on the lane row), straight from global memory in fragment order (gt_mel_pack: 32 bytes per lane and
-//             4 K steps, cos then sin); B = the folded samples (frame on the lane column).  So an accumulator holds its frame on the
-//             lane and 16 bins in its registers, cos and sin of one bin in the same lane: mag = sqrt(re^2 + im^2) needs no exchange,
+//   mag       an accumulator holds its frame on the lane and 16 bins in its registers, cos and sin of one bin in the same lane:
+//             mag = sqrt(re^2 + im^2) needs no exchange,
 //   mel       and the 32 x 32 magnitude tile IS the B operand of the projection mel[m][f] += melb[m][bin] mag[bin][f] (register e of
-//             lane half h is bin (e & 3) + 8 (e >> 2) + 4 h: the mel image is packed in that k order) — no LDS, no transposition.
+//             lane half h is bin acc_row(e, h): the mel image is packed in that k order) — no LDS, no transposition.
 //   walk      wave w walks bin tiles 4 w .. 4 w + 3 and keeps the partial energy and mel of its 128 bins in registers; the four
 //             partials meet in LDS (the sample buffer, behind a barrier) in the order ((w0 + w1) + w2) + w3, then bin 512, then
 //             sqrt / log.  No atomics; the order of every sum depends on nothing but the frame's index within its utterance.
-#include <type_traits>
 #include "common.h"
 #include "internal.h"
+#include "stft_tile.h"
 #include "../../include/glowtts_hip.h"
 
 namespace {
 
-constexpr int NFFT = 1024, HOP = 256, NBIN = 513;
-constexpr int TF = 64;                                   // frames per workgroup
-constexpr int SPAN = (TF - 1) * HOP + NFFT;              // samples the tile spans
-constexpr int LDS_FLOATS = 17220;                        // SPAN + one pad word per 256, rounded to 16 bytes
-static_assert(SPAN - 1 + ((SPAN - 1) >> 8) < LDS_FLOATS, "sample buffer");
+using namespace gtstft;
 
-// the packed image (floats): basis [16 bin tiles][64 step groups][64 lanes][cos 4 | sin 4], bin 512's folded cos row [512],
-// mel [16 bin tiles][4 mel tiles][64 lanes][16], mel_basis[:, 512] [128]
-constexpr int OFF_NYQ = 16 * 64 * 64 * 8;
-constexpr int OFF_MEL = OFF_NYQ + 512;
-constexpr int OFF_MELNYQ = OFF_MEL + 16 * 4 * 64 * 16;
-constexpr int PACK_FLOATS = OFF_MELNYQ + 128;
 static_assert(4 * 32 * TF + 2 * 4 * TF <= LDS_FLOATS, "the reduction buffers alias the sample buffer");
-
-__device__ __forceinline__ int acc_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 
 __global__ __launch_bounds__(256) void gt_mel_pack_kernel(const float* __restrict__ basis, const float* __restrict__ melb, int n_mel,
                                                           float* __restrict__ out)
@@ -96,49 +77,10 @@ __global__ __launch_bounds__(256, 2) void gt_mel_front_kernel(const void* __rest
     return;
   }
 
-  // ---- stage the tile's samples: reflected about the utterance's own ends, the index clamped into [0, L) whatever L is
-  {
-    const int s0 = f0 * HOP - NFFT / 2;
-    const float* wf = static_cast<const float*>(wav) + (size_t)b * ld_wav;
-    const int16_t* wi = static_cast<const int16_t*>(wav) + (size_t)b * ld_wav;
-    const auto stage = [&](auto i16) {                    // 67 samples per thread, 8 loads in flight at a time: a load per trip
-      constexpr int TRIPS = SPAN / 256, UNR = 8;          // would pay 67 dependent memory round trips before the first MFMA
-      static_assert(TRIPS * 256 == SPAN, "whole trips");
-#pragma unroll
-      for (int t0 = 0; t0 < TRIPS; t0 += UNR) {
-        float v[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u)
-          if (t0 + u < TRIPS) {
-            int s = s0 + (t0 + u) * 256 + tid;
-            if (s < 0) s = -s;
-            if (s >= L) s = 2 * (L - 1) - s;
-            s = s < 0 ? 0 : (s > L - 1 ? L - 1 : s);
-            v[u] = decltype(i16)::value ? (float)wi[s] * (1.0f / 32768.0f) : wf[s];
-          }
-#pragma unroll
-        for (int u = 0; u < UNR; ++u)
-          if (t0 + u < TRIPS) {
-            const int p = (t0 + u) * 256 + tid;
-            lds[p + (p >> 8)] = v[u];
-          }
-      }
-    };
-    if (is_i16) stage(std::true_type{}); else stage(std::false_type{});
-  }
+  if (is_i16) stage_tile(lds, static_cast<const int16_t*>(wav) + (size_t)b * ld_wav, L, f0, tid);
+  else stage_tile(lds, static_cast<const float*>(wav) + (size_t)b * ld_wav, L, f0, tid);
   __syncthreads();
-
-  // ---- bin 512 on the VALU: thread (frame tid & 63, quarter w) sums 128 folded samples; the quarters meet in the reduction
-  float nyq_part = 0.f;
-  {
-    const int base = lane * 257;
-    const float* nq = packed + OFF_NYQ + w * 128;
-#pragma unroll 16
-    for (int m = 0; m < 128; ++m) {                      // one chain in m order; unrolled so that the LDS reads run ahead of it
-      const int n = 1 + w * 128 + m, nd = NFFT - n;
-      nyq_part = fmaf(nq[m], lds[base + n + (n >> 8)] + lds[base + nd + (nd >> 8)], nyq_part);
-    }
-  }
+  const float nyq_part = nyquist_partial(lds, packed, lane, w);       // bin 512: the quarters meet in the reduction
 
   // ---- the DFT: wave w, bin tiles 4 w .. 4 w + 3, 64 frames each
   const int j = lane & 31, h = lane >> 5;
@@ -154,47 +96,7 @@ __global__ __launch_bounds__(256, 2) void gt_mel_front_kernel(const void* __rest
   for (int pass = 0; pass < 4; ++pass) {
     const int bt = w * 4 + pass;
     f32x16_t ac[2], as[2];
-#pragma unroll
-    for (int ft = 0; ft < 2; ++ft)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { ac[ft][e] = 0.f; as[ft][e] = 0.f; }
-    const float4* ip = reinterpret_cast<const float4*>(packed) + ((size_t)bt * 64 * 64 + lane) * 2;
-    // Software pipeline, pinned with scheduling barriers (left to itself the compiler sinks every load to its first use and one
-    // wave per SIMD then waits out a memory round trip per group): the NEXT group's basis fragments are requested before this
-    // group's 16 MFMAs, the NEXT step's four samples before this step's four MFMAs.
-    const auto samples = [&](int t, float (&xa)[2], float (&xd)[2]) {     // K step t: sample n = 1 + 2 t + h and its mirror 1024 - n
-      const int n = 1 + 2 * t + h, nd = NFFT - n;
-      const int oa = n + (n >> 8), od = nd + (nd >> 8);
-#pragma unroll
-      for (int ft = 0; ft < 2; ++ft) {
-        const int base = (ft * 32 + j) * 257;
-        xa[ft] = lds[base + oa]; xd[ft] = lds[base + od];
-      }
-    };
-    float4 c4 = ip[0], s4 = ip[1];
-    float xa[2], xd[2];
-    samples(0, xa, xd);
-    for (int tg = 0; tg < 64; ++tg) {
-      const int tn = tg < 63 ? tg + 1 : tg;
-      const float4 nc = ip[(size_t)tn * 128], ns = ip[(size_t)tn * 128 + 1];
-      const float cc[4] = {c4.x, c4.y, c4.z, c4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        float nxa[2], nxd[2];
-        samples(4 * tg + s + 1, nxa, nxd);               // step 256 (behind the last) reads inside the frame and is dropped
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ft = 0; ft < 2; ++ft) {
-          ac[ft] = __builtin_amdgcn_mfma_f32_32x32x2f32(cc[s], xa[ft] + xd[ft], ac[ft], 0, 0, 0);
-          as[ft] = __builtin_amdgcn_mfma_f32_32x32x2f32(ss[s], xa[ft] - xd[ft], as[ft], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ft = 0; ft < 2; ++ft) { xa[ft] = nxa[ft]; xd[ft] = nxd[ft]; }
-      }
-      c4 = nc; s4 = ns;
-    }
+    dft_tile(lds, packed, bt, lane, ac, as);
     // magnitudes of the tile: frame on the lane, bin bt * 32 + acc_row(e, h) in register e
     float mg[2][16];
 #pragma unroll

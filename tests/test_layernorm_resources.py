@@ -2,30 +2,25 @@
 (geometry, a, y, dout_f32, dout_bf16) presence — 3 + 2 x 9 instantiations —, none with scratch or spilled registers, the forward
 without LDS, the backward with its fold buffer of 2 x waves x 256 floats (32 KB at 16 waves, 8 KB at 4), and registers that leave the
 residency DESIGN.md 4.10 (5) states: a 16-wave workgroup is resident only as a whole, so its kernels must allow at least 4 waves per
-SIMD (at most 128 registers); the 4-wave x 4-row form holds the loads of four rows in at most 140 VGPRs, which still is 3 waves per SIMD.  The ceilings are asserted as register counts, so growth shows before it costs a whole occupancy step.  Same parsing
-as tests/test_dds_layer_resources.py."""
+SIMD (at most 128 registers); the 4-wave x 4-row form holds the loads of four rows in at most 140 VGPRs, which still is 3 waves per SIMD.  The ceilings are asserted as register counts, so growth shows before it costs a whole occupancy step.  Parsing:
+tests/kernel_resources.py; the checks are this file's own (instantiations told apart by their template arguments)."""
 import os
 import re
+import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REPORT = os.path.join(ROOT, "glow-tts_amd", "build", "encoder_ops.resources.txt")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernel_resources as KR  # noqa: E402
+
 GEOMETRIES = {(16, 2), (4, 4)}        # (waves, rows per wave): the atomics form from 2048 rows on; the partials form and the atomics form below
 
 
-def _fields(line):
-    fields = dict(re.findall(r"([A-Za-z][A-Za-z ]*(?:\[[^\]]*\])?)=(\S+)", line.split(None, 1)[1]))
-    return {k.strip(): v for k, v in fields.items()}
-
-
 def test_layernorm_kernels_resources(built):
-    with open(REPORT) as f:
-        lines = [l.strip() for l in f if "gt_layernorm_" in l]
+    lines = KR.report_lines("encoder_ops", only="gt_layernorm_")
     fwd, bwd = set(), set()
     for line in lines:
         name = line.split()[0]
-        fields = _fields(line)
-        assert fields["ScratchSize [bytes/lane]"] == "0", line
-        assert fields["VGPRs Spill"] == "0" and fields["SGPRs Spill"] == "0", line
+        fields = KR.fields(line)
+        KR.no_scratch_no_spills(fields, line)
         occ, lds = int(fields["Occupancy [waves/SIMD]"]), int(fields["LDS Size [bytes/block]"])
         m = re.search(r"gt_layernorm_fwd_kernelILb([01])ELb([01])E", name)
         if m:
