@@ -207,6 +207,10 @@ PROTOTYPES = {
     "gt_gl_project": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gt_istft": (STATUS, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "gt_gl_from_mel": (STATUS, [c_void_p, c_i64, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_u32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gt_resample_tile_out": (c_int, []),
+    "gt_resample_taps": (c_int, [c_int, c_int]),
+    "gt_resample_lds_bytes": (c_size_t, [c_int, c_int]),
+    "gt_resample": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
 }
 c_void_p = ctypes.c_void_p
 

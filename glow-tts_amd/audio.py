@@ -19,6 +19,10 @@ run by ONE HIP kernel (csrc/mel_front.hip: gt_mel_pack once, gt_mel_spectrogram 
                     magnitudes and the initial spectrum, phases keyed by (seed, utterance, frame, bin); `mel_workspace` /
                     `run_from_mel` are its capacity-sized form for graph callers (synthesis.Synthesizer).
   griffin_lim       the reference's signature.
+  Resample          rational-rate conversion of padded batches by ONE kernel (csrc/resample.hip: gt_resample) with the
+                    definition of scipy.signal.resample_poly (default window, zero padding); carries the fp32 phase `bank`.
+                    `mel_spectrogram(..., sampling_rate=)` and `YIN.f0(..., sampling_rate=)` resample first; `resample_poly` is scipy's
+                    signature for one device waveform, `resample_filter64` / `resample_bank64` the float64 prototype and its phases.
 
 Waveforms are fp32 in [-1, 1] or int16 (scaled by 1/32768 in the kernel = the reference's audio / max_wav_value).  There is no CPU
 path: a CPU tensor raises."""
@@ -94,6 +98,152 @@ def _ragged_frames(y, lengths, lengths_host, hop, min_len=None):
     return lengths.to(y.device, non_blocking=True), F_max
 
 
+# ---- sample-rate conversion: scipy.signal.resample_poly's definition on csrc/resample.hip -----------------------
+def _reduced(up, down):
+    up, down = int(up), int(down)
+    if up <= 0 or down <= 0:
+        raise ValueError(f"up and down are positive integers, got {up}, {down}")
+    g = int(np.gcd(up, down))
+    return up // g, down // g
+
+
+def resample_filter64(up, down):
+    """float64 [20 max(up, down) + 1]: the prototype filter of scipy.signal.resample_poly(x, up, down) with its default window —
+    firwin(2 half + 1, 1 / max(up, down), window=('kaiser', 5.0)) * up with half = 10 max(up, down): fc sinc(fc n) times the
+    symmetric Kaiser window (beta = 5), normalised to unit sum, times up.  (up, down) is reduced first.  Our own restatement: the
+    product does not import scipy (tests/test_resample_host.py compares the two)."""
+    up, down = _reduced(up, down)
+    m = max(up, down)
+    half = 10 * m
+    n = np.arange(-half, half + 1, dtype=np.float64)
+    h = np.sinc(n / m) / m * np.kaiser(2 * half + 1, 5.0)
+    return h / h.sum() * up
+
+
+def resample_bank64(up, down):
+    """float64 [up, T]: the phases of resample_filter64, bank[p, j] = h[p + j up] and 0 past the end of h, T = ceil(len(h) / up)"""
+    up, down = _reduced(up, down)
+    h = resample_filter64(up, down)
+    T = -(-len(h) // up)
+    full = np.zeros(up * T)
+    full[:len(h)] = h
+    return np.ascontiguousarray(full.reshape(T, up).T)
+
+
+def resample_out_len(length, up, down):
+    """ceil(length up / down): the samples resample_poly returns for `length` (a Python int: no overflow)"""
+    return -(-int(length) * up // down)
+
+
+class Resample(nn.Module):
+    """Rational-rate conversion orig_freq -> new_freq of padded batches by ONE HIP kernel (csrc/resample.hip: gt_resample), every
+    utterance resampled on its own with the definition of scipy.signal.resample_poly(x, up, down) (default window, zero padding),
+    up / down = new_freq / orig_freq reduced.  Carries the fp32 `bank` [up, taps] (resample_bank64 rounded once).  A pair of rates
+    the kernel does not take (its bank and a tile's input span do not fit the LDS) is a ValueError here."""
+
+    def __init__(self, orig_freq, new_freq):
+        super().__init__()
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self.up, self.down = _reduced(self.new_freq, self.orig_freq)
+        self.taps = call.gt_resample_taps(self.up, self.down)
+        if self.taps == 0:
+            raise ValueError(f"{orig_freq} -> {new_freq} Hz (up {self.up}, down {self.down}) is outside what gt_resample takes")
+        self.register_buffer("bank", torch.from_numpy(resample_bank64(self.up, self.down).astype(np.float32)))
+
+    def out_len(self, length):
+        return resample_out_len(length, self.up, self.down)
+
+    def transform(self, y, wav_len, L_cap):
+        """the kernel call: y [B, T] fp32 / int16 on the device, wav_len device int32 [B], L_cap samples per output row ->
+        (out [B, L_cap] fp32, out_len device int32 [B] = min(ceil(wav_len up / down), L_cap)), row b zero behind its samples; rows at a
+        pitch of L_cap rounded up to 4.  No host synchronisation, capturable in a graph."""
+        y = _device_rows(y)
+        wav_len = _wav_len_arg(wav_len, y)
+        bank = self.bank
+        if bank.device != y.device or bank.dtype != torch.float32 or tuple(bank.shape) != (self.up, self.taps) or not bank.is_contiguous():
+            raise ValueError(f"bank must be a contiguous fp32 [{self.up}, {self.taps}] buffer on the waveforms' device")
+        if L_cap <= 0:
+            raise ValueError(f"L_cap = {L_cap}: no output sample")
+        B = y.shape[0]
+        ld = (L_cap + 3) // 4 * 4
+        out = torch.empty(B, ld, dtype=torch.float32, device=y.device)
+        out_len = torch.empty(B, dtype=torch.int32, device=y.device)
+        call.gt_resample(y, int(y.dtype == torch.int16), y.stride(0), wav_len, B, bank, self.up, self.down, self.taps, out, ld, out_len,
+                         _lib.current_stream(y.device))
+        if ld != L_cap:                                                       # the kernel's capacity is the pitch
+            out, out_len = out[:, :L_cap], out_len.clamp_(max=L_cap)
+        return out, out_len
+
+    def host_lengths(self, y, lengths, lengths_host):
+        """the output lengths where the host knows the input's (lengths_host, CPU `lengths`, or no lengths at all), else None"""
+        if lengths is None:
+            return [self.out_len(y.shape[1])] * y.shape[0]
+        if lengths_host is None and not lengths.is_cuda:
+            lengths_host = lengths.tolist()
+        return None if lengths_host is None else [self.out_len(v) for v in lengths_host]
+
+    def forward(self, y, lengths=None, lengths_host=None):
+        """y [B, T] (lengths: sample counts of the padded rows, default T) -> (out [B, L_cap] fp32, out_lengths int32 [B] on the
+        device = ceil(lengths up / down)); L_cap = max(out_lengths) where the host knows the lengths (lengths_host, or CPU `lengths`),
+        else ceil(T up / down) with no synchronisation — as _ragged_frames chooses F_max.  Equal rates: the input as fp32 (int16
+        scaled by 1/32768) and its lengths, no launch."""
+        if not y.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
+        if y.dim() != 2 or y.dtype not in (torch.float32, torch.int16):
+            raise ValueError(f"waveforms are [B, T] fp32 or int16, got {tuple(y.shape)} {y.dtype}")
+        B, T = y.shape
+        if lengths is None:
+            wav_len = torch.full((B,), T, dtype=torch.int32, device=y.device)
+        else:
+            if lengths.numel() != B:
+                raise ValueError("lengths must be [B]")
+            wav_len = lengths.to(y.device, non_blocking=True).to(torch.int32)
+        if lengths_host is None and lengths is not None and not lengths.is_cuda:
+            lengths_host = lengths.tolist()
+        if lengths_host is not None and (len(lengths_host) != B or max(int(v) for v in lengths_host) > T):
+            raise ValueError(f"lengths {list(lengths_host)} do not fit waveforms {tuple(y.shape)}")
+        if self.up == self.down:
+            return (y if y.dtype == torch.float32 else y.float() / 32768.0), wav_len
+        out_host = self.host_lengths(y, lengths, lengths_host)
+        L_cap = max(out_host) if out_host is not None else self.out_len(T)
+        return self.transform(y, wav_len, max(L_cap, 1))
+
+
+def resample_poly(x, up, down):
+    """scipy.signal.resample_poly's signature (default window and padding) for ONE device waveform x [L] (fp32 or int16) ->
+    fp32 [ceil(L up / down)]"""
+    if x.dim() != 1:
+        raise ValueError(f"resample_poly takes one waveform [L], got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
+    up, down = _reduced(up, down)
+    if x.shape[0] == 0:
+        return torch.empty(0, dtype=torch.float32, device=x.device)
+    out, _ = Resample(down, up).to(x.device)(x.unsqueeze(0))
+    return out[0, :resample_out_len(x.shape[0], up, down)]
+
+
+class _RateCache:
+    """the Resample modules of a front end, one per (input rate, device), built at the first call that names the rate.  Not a
+    submodule: the front end's parameters, buffers and state_dict stay what they are."""
+
+    def __init__(self, new_freq):
+        self.new_freq, self.mods = new_freq, {}
+
+    def convert(self, y, lengths, lengths_host, sampling_rate):
+        """(y, lengths, lengths_host) at `sampling_rate` -> the same at the front end's rate: the device out_len of the kernel as
+        the lengths, the host's count beside it where the host knows the input's"""
+        if not y.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
+        key = (int(sampling_rate), y.device)
+        if key not in self.mods:
+            self.mods[key] = Resample(sampling_rate, self.new_freq).to(y.device)
+        mod = self.mods[key]
+        out_host = mod.host_lengths(y, lengths, lengths_host)
+        out, out_len = mod(y, lengths, lengths_host)
+        return out, (None if lengths is None else out_len), (None if lengths is None else out_host)
+
+
 def hann_periodic(win_length):
     """scipy.signal.get_window('hann', win_length, fftbins=True) in float64"""
     return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win_length, dtype=np.float64) / win_length)
@@ -154,6 +304,7 @@ class TacotronSTFT(nn.Module):
         self.stft_fn = STFT(filter_length, hop_length, win_length)
         self.register_buffer("mel_basis", torch.from_numpy(mel_filterbank(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax)))
         self._packed = _Cached()
+        self._rates = _RateCache(sampling_rate)
 
     # -- the fragment-order image of both buffers, rebuilt when either changes
     def _image(self):
@@ -185,12 +336,16 @@ class TacotronSTFT(nn.Module):
                                 fs.hop_length, fs.win_length, n_mel, CLIP_VAL, mel, energy, mag, _lib.current_stream(y.device))
         return mel, energy, mag
 
-    def mel_spectrogram(self, y, lengths=None, lengths_host=None):
+    def mel_spectrogram(self, y, lengths=None, lengths_host=None, sampling_rate=None):
         """mel_spectrogram(y): the reference's call, y [B, T] -> (mel [B, n_mel, F], energy [B, F]), F = 1 + T // hop.
         mel_spectrogram(y, lengths[, lengths_host]): padded rows of a batch with their sample counts -> (mel [B, n_mel, F_max],
         mel_lengths = 1 + lengths // hop, energy [B, 1, F_max]), every utterance transformed on its own (reflected about its own ends)
         and zero behind its frames.  F_max comes from the lengths when the host knows them (lengths_host, or CPU `lengths`), else from
-        T with no synchronisation.  A length <= filter_length / 2 has no reflect padding: ValueError where the host knows it."""
+        T with no synchronisation.  A length <= filter_length / 2 has no reflect padding: ValueError where the host knows it.
+        sampling_rate: the rate of y where it is not this module's — y is resampled first (audio.Resample, cached per rate; its
+        device out_len are the lengths of the transform), and everything above holds for the resampled batch."""
+        if sampling_rate is not None and int(sampling_rate) != int(self.sampling_rate):
+            y, lengths, lengths_host = self._rates.convert(y, lengths, lengths_host, sampling_rate)
         hop = self.stft_fn.hop_length
         ragged = lengths is not None
         lengths, F_max = _ragged_frames(y, lengths, lengths_host, hop, min_len=self.stft_fn.filter_length // 2)
@@ -211,6 +366,7 @@ class YIN(nn.Module):
         self.f0_min, self.f0_max, self.harm_thresh = f0_min, f0_max, harm_thresh
         self.tau_min, self.tau_max = int(sampling_rate / f0_max), int(sampling_rate / f0_min)
         self.pad_frames = int((frame_length / hop_length) / 2) if pad_frames is None else pad_frames
+        self._rates = _RateCache(sampling_rate)
 
     def transform(self, y, wav_len, F_max, aux=False, lead=None):
         """the kernel call: y [B, T] fp32 / int16 on the device, wav_len device int32 [B], F_max positions per output row ->
@@ -227,11 +383,15 @@ class YIN(nn.Module):
                        self.pad_frames if lead is None else lead, f0, harm, amin, _lib.current_stream(y.device))
         return f0, harm, amin
 
-    def f0(self, y, lengths=None, lengths_host=None, aux=False):
+    def f0(self, y, lengths=None, lengths_host=None, aux=False, sampling_rate=None):
         """y [B, T] (lengths: sample counts of the padded rows, default T) -> f0 [B, 1, F_max] with F_max = 1 + max(lengths) // hop,
         chosen as TacotronSTFT.mel_spectrogram(y, lengths) chooses it (from the lengths where the host knows them, else from T with
         no synchronisation): the contour lines up with that call's mel and energy, zero behind every utterance's frames.
-        aux=True: (f0, harm [B, 1, F_max], argmin_f0 [B, 1, F_max])."""
+        aux=True: (f0, harm [B, 1, F_max], argmin_f0 [B, 1, F_max]).
+        sampling_rate: the rate of y where it is not this module's — y is resampled first, as mel_spectrogram(..., sampling_rate=)
+        does: the two still line up."""
+        if sampling_rate is not None and int(sampling_rate) != int(self.sampling_rate):
+            y, lengths, lengths_host = self._rates.convert(y, lengths, lengths_host, sampling_rate)
         lengths, F_max = _ragged_frames(y, lengths, lengths_host, self.hop_length)
         f0, harm, amin = self.transform(y, lengths.to(torch.int32), F_max, aux=aux)
         if aux:

@@ -1072,6 +1072,39 @@ int gt_istft(const float* spec, const int32_t* n_frames, int B, int F_max, const
 int gt_gl_from_mel(const float* mel, int64_t stride_b, int64_t stride_c, const int32_t* n_frames, int B, int F_max, int n_mel,
                    const float* mel_pinv, uint32_t seed, const uint32_t* seed_dev, float* mag, float* spec, void* stream);
 
+/* ---- device sample-rate conversion (csrc/resample.hip): a rational-rate polyphase resampler for ragged batches ----
+ * The definition of scipy.signal.resample_poly(x, up, down) with its default window ('kaiser', 5.0) and zero padding, applied to every
+ * utterance of a padded batch on its own, in exact fp32.  (up, down) is reduced; half = 10 max(up, down); the prototype filter h has
+ * 2 half + 1 taps (firwin(2 half + 1, 1 / max(up, down), window=('kaiser', 5.0)) * up); taps = ceil((2 half + 1) / up).  Utterance b
+ * with L = wav_len[b] samples (clamped to [0, min(ld_wav, GT_RESAMPLE_MAX_LEN)]) has n_b = ceil(L up / down) outputs, and with
+ * q = n down + half, p = q mod up, k0 = q div up
+ *   out[b][n] = sum_{j = 0}^{taps - 1} bank[p][j] x[k0 - j],   x[k] = 0 outside [0, L)   (nothing at or beyond index L is read)
+ * as ONE fmaf chain over j ascending.  Row b of out holds min(n_b, ld_out) samples and zeros behind them up to ld_out: every element
+ * of [B, ld_out] is written.
+ *   wav      [B rows, pitch ld_wav elements] fp32, or int16 when is_i16 != 0 (scaled by 1/32768 in the kernel).
+ *   wav_len  device int32 [B].
+ *   bank     fp32 [up, taps], bank[p][j] = h[p + j up] and 0 past the end of h: built on the host in float64 and rounded once.
+ *   out_len  optional device int32 [B]: min(n_b, ld_out) — the wav_len of a gt_mel_spectrogram / gt_yin_f0 call that follows, with
+ *            no host synchronisation.
+ * Asynchronous, no allocation, no atomics, capturable in a graph; the summation order of an output depends on (n, up, down) alone,
+ * not on B, ld_out, the tile or the row: a batch row is bit-identical to the utterance computed alone, an int16 input to its fp32
+ * image.  n down + half is formed in 64 bits.
+ * Supported: every reduced (up, down) whose bank (rows at the odd pitch taps | 1) plus the input span of one tile of
+ * gt_resample_tile_out() outputs, (up - 1 + (tile - 1) down) div up + taps samples, fit 64 KB of LDS — each rounded up to 16 bytes;
+ * gt_resample_lds_bytes(up, down) is that sum, gt_resample_taps(up, down) the taps per phase, both 0 for a pair that is refused (not
+ * reduced, non-positive, or too large).
+ * Refusals, before any launch and in this order: NULL wav / wav_len / bank / out, B outside [1, GT_MEL_MAX_B], ld_wav, ld_out, up,
+ * down or taps <= 0: GT_E_INVAL; taps != ceil((20 max(up, down) + 1) / up): GT_E_INVAL; a pair gt_resample_taps refuses, or
+ * ld_out > GT_RESAMPLE_MAX_OUT: GT_E_UNSUPPORTED; wav, bank, out not 16-byte (wav_len, out_len: 4-byte) aligned, ld_wav or ld_out no
+ * multiple of 4: GT_E_ALIGN. */
+#define GT_RESAMPLE_MAX_LEN 268435456
+#define GT_RESAMPLE_MAX_OUT 1073741824
+int gt_resample_tile_out(void);
+int gt_resample_taps(int up, int down);
+size_t gt_resample_lds_bytes(int up, int down);
+int gt_resample(const void* wav, int is_i16, int ld_wav, const int32_t* wav_len, int B, const float* bank, int up, int down,
+                int taps, float* out, int ld_out, int32_t* out_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
