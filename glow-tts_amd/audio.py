@@ -24,6 +24,11 @@ run by ONE HIP kernel (csrc/mel_front.hip: gt_mel_pack once, gt_mel_spectrogram 
                     `mel_spectrogram(..., sampling_rate=)` and `YIN.f0(..., sampling_rate=)` resample first; `resample_poly` is scipy's
                     signature for one device waveform, `resample_filter64` / `resample_bank64` the float64 prototype and its phases.
 
+  HiFiGAN           the published HiFi-GAN generator (eval mode, weight norm folded) from log-mel to samples, every layer by ONE kernel
+                    (csrc/hifigan.hip: gt_voc_conv), every utterance of a ragged batch on its own; loads the original
+                    checkpoints (`load_generator_state`, `from_config`); `workspace` / `run` are its capacity-sized form for graph
+                    callers (synthesis.Synthesizer).  `transposed_as_conv`, `voc_pack`: the weight forms it runs on.
+
 Waveforms are fp32 in [-1, 1] or int16 (scaled by 1/32768 in the kernel = the reference's audio / max_wav_value).  There is no CPU
 path: a CPU tensor raises."""
 import numpy as np
@@ -681,3 +686,269 @@ def griffin_lim(magnitudes, stft_fn, n_iters=30, **kw):
     """the reference's signature; stft_fn is an audio.STFT / TacotronSTFT (a GriffinLim is built for the call) or a GriffinLim"""
     gl = stft_fn if isinstance(stft_fn, GriffinLim) else GriffinLim(stft_fn).to(magnitudes.device)
     return gl(magnitudes, n_iters=n_iters, **kw)
+
+
+# ---- neural vocoder (DESIGN.md 4.23): the HiFi-GAN generator on csrc/hifigan.hip ---------------------------------------------------
+LRELU_SLOPE = 0.1                    # the generator's; conv_post's input takes F.leaky_relu's default 0.01 (a quirk of the original)
+
+
+def transposed_as_conv(w, u):
+    """ConvTranspose1d weight [Cin, Cout, 2u] (stride u even, padding u / 2) -> the 3-tap convolution weight [u * Cout, Cin, 3] with
+    W3[r * Cout + c, ci, j] = w[ci, c, r + u / 2 + u (1 - j)] where that index lies in [0, 2u) and 0 elsewhere: output u q + r of the
+    transposed convolution reads inputs q - 1, q, q + 1 only, and [L, u * Cout] channels-last IS [u L, Cout]"""
+    Cin, Cout, k = w.shape
+    if k != 2 * u or u % 2:
+        raise ValueError(f"transposed convolutions are k = 2u with u even, got k = {k}, u = {u}")
+    W3 = w.new_zeros(u, Cout, Cin, 3)
+    for j in range(3):
+        for r in range(u):
+            idx = r + u // 2 + u * (1 - j)
+            if 0 <= idx < k:
+                W3[r, :, :, j] = w[:, :, idx].t()
+    return W3.reshape(u * Cout, Cin, 3)
+
+
+def voc_pack(w):
+    """conv weight [N, Cin, taps] (any float dtype) -> gt_voc_conv's bf16 image [taps][Np / 32][Kp / 16][64 lanes][8], lane 32 h + r and
+    element e holding W[j][32 nt + r][16 ks + 8 h + e] rounded to nearest even, zeros in the padding (include/glowtts_hip.h)"""
+    N, Cin, taps = w.shape
+    kc = call.gt_voc_k_chunk(Cin)
+    if not kc:
+        raise ValueError(f"{Cin} input channels: a multiple of 16 is needed")
+    Np, Kp = (N + 31) // 32 * 32, (Cin + kc - 1) // kc * kc
+    full = torch.zeros(taps, Np, Kp, dtype=torch.bfloat16, device=w.device)
+    full[:, :N, :Cin] = w.detach().permute(2, 0, 1).to(torch.bfloat16)
+    return full.view(taps, Np // 32, 32, Kp // 16, 2, 8).permute(0, 1, 3, 4, 2, 5).contiguous().view(-1)
+
+
+def fold_weight_norm(g, v):
+    """weight_norm's w = g v / ||v|| (norm over every dim but 0) in float64, rounded to fp32 once"""
+    v64, g64 = v.detach().double().cpu(), g.detach().double().cpu()
+    norm = v64.reshape(v64.shape[0], -1).norm(dim=1).reshape(-1, *([1] * (v64.dim() - 1)))
+    return (g64 * v64 / norm).float()
+
+
+class _ResBlock(nn.Module):
+    """parameter holder under the original generator's names: convs1 / convs2 (resblock "1") or convs ("2")"""
+
+    def __init__(self, kind, C, k, dilations):
+        super().__init__()
+        mk = lambda d: nn.Conv1d(C, C, k, dilation=d, padding=d * (k - 1) // 2)  # noqa: E731
+        if kind == "1":
+            self.convs1 = nn.ModuleList(mk(d) for d in dilations)
+            self.convs2 = nn.ModuleList(mk(1) for _ in dilations)
+        else:
+            self.convs = nn.ModuleList(mk(d) for d in dilations)
+
+
+class HiFiGAN(nn.Module):
+    """The published HiFi-GAN `Generator` (eval mode, weight norm folded) from log-mel to waveform, every layer by ONE HIP kernel
+    (csrc/hifigan.hip: gt_voc_conv), applied to every utterance of a ragged batch ON ITS OWN: utterance b is
+    Generator(mel[b:b+1, :, :F_b]), every convolution zero-padded at that utterance's own ends, so its samples do not depend on the
+    batch it is in.  F_b frames give U F_b samples, U the product of the upsample rates (256 for V1 — not Griffin-Lim's 256 (F_b - 1)).
+
+      conv_pre (k 7) -> per stage: lrelu 0.1, transposed conv (k = 2u, stride u even, padding u / 2: run as a 3-tap convolution to
+      u * Cout channels read back as u times the positions), the mean of the resblocks -> lrelu 0.01, conv_post (k 7, 1 channel), tanh.
+
+    Parameters are fp32 under the original names (conv_pre, ups.{i}, resblocks.{i K + j}.convs1.{m} / .convs2.{m} or .convs.{m},
+    conv_post; transposed weights stay [Cin, Cout, k]); `load_generator_state` takes a checkpoint with or without weight norm.
+    Operands are bf16 (the packed images, and the activations after the leaky ReLU), accumulation fp32; the residual stream and the
+    resblock sum stay fp32, only the tensor between a resblock's two convolutions is bf16.  `launches` gt_voc_conv calls per run: 78
+    for V1.  Any other (k, u), channels that are no multiple of 16, an even or > 11 resblock kernel: ValueError."""
+
+    def __init__(self, resblock="1", upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4), upsample_initial_channel=512,
+                 resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5),) * 3, n_mel_channels=80):
+        super().__init__()
+        resblock = str(resblock)
+        rates, kernels = tuple(int(u) for u in upsample_rates), tuple(int(k) for k in upsample_kernel_sizes)
+        rk, rd = tuple(int(k) for k in resblock_kernel_sizes), tuple(tuple(int(d) for d in ds) for ds in resblock_dilation_sizes)
+        C0 = int(upsample_initial_channel)
+        if resblock not in ("1", "2"):
+            raise ValueError(f'resblock is "1" or "2", got {resblock!r}')
+        if not rates or len(rates) != len(kernels) or not rk or len(rk) != len(rd) or any(not ds for ds in rd):
+            raise ValueError("upsample_rates / upsample_kernel_sizes and resblock_kernel_sizes / resblock_dilation_sizes must pair up")
+        for u, k in zip(rates, kernels):
+            if k != 2 * u or u % 2 or u < 2:
+                raise ValueError(f"transposed convolutions are k = 2u with u even, got k = {k}, u = {u}")
+        for k in rk:
+            if k % 2 == 0 or k < 1 or k > 11:
+                raise ValueError(f"resblock kernels are odd and at most 11, got {k}")
+        if any(d < 1 for ds in rd for d in ds):
+            raise ValueError("dilations are >= 1")
+        chans = [C0 >> i for i in range(len(rates) + 1)]
+        if n_mel_channels % 16 or any(c % 16 or c < 16 for c in chans) or C0 % (1 << len(rates)):
+            raise ValueError(f"channel counts must be multiples of 16, got mel {n_mel_channels} and stages {chans}")
+        self.resblock, self.upsample_rates, self.upsample_kernel_sizes = resblock, rates, kernels
+        self.resblock_kernel_sizes, self.resblock_dilation_sizes = rk, rd
+        self.n_mel_channels, self.channels = int(n_mel_channels), chans
+        self.hop_length = int(np.prod(rates))                                      # U: samples per frame
+        self.conv_pre = nn.Conv1d(self.n_mel_channels, C0, 7, padding=3)
+        self.ups = nn.ModuleList(nn.ConvTranspose1d(chans[i], chans[i + 1], k, u, padding=(k - u) // 2)
+                                 for i, (u, k) in enumerate(zip(rates, kernels)))
+        self.resblocks = nn.ModuleList(_ResBlock(resblock, chans[i + 1], k, ds) for i in range(len(rates)) for k, ds in zip(rk, rd))
+        self.conv_post = nn.Conv1d(chans[-1], 1, 7, padding=3)
+        per_block = sum((2 if resblock == "1" else 1) * len(ds) for ds in rd)
+        self.launches = 2 + len(rates) * (1 + per_block)
+        self._images = _Cached()
+        for p in self.parameters():
+            p.requires_grad_(False)
+
+    @classmethod
+    def from_config(cls, cfg):
+        """from the original config.json's keys (num_mels optional: 80)"""
+        return cls(resblock=cfg["resblock"], upsample_rates=cfg["upsample_rates"], upsample_kernel_sizes=cfg["upsample_kernel_sizes"],
+                   upsample_initial_channel=cfg["upsample_initial_channel"], resblock_kernel_sizes=cfg["resblock_kernel_sizes"],
+                   resblock_dilation_sizes=cfg["resblock_dilation_sizes"], n_mel_channels=cfg.get("num_mels", 80))
+
+    def load_generator_state(self, sd):
+        """a checkpoint's sd["generator"] or the dict itself, with weight norm (weight_g / weight_v, folded g v / ||v|| over dim 0 in
+        float64 and rounded once) or after remove_weight_norm; strict"""
+        sd = sd.get("generator", sd) if isinstance(sd, dict) else sd
+        out = {}
+        for k, t in sd.items():
+            if k.endswith(".weight_g"):
+                out[k[:-2]] = fold_weight_norm(t, sd[k[:-1] + "v"])
+            elif not k.endswith(".weight_v"):
+                out[k] = t.detach().float()
+        return self.load_state_dict(out, strict=True)
+
+    # ---- the packed images: one per launch, in launch order ---------------------------------------------------------------------------
+    def _convs(self):
+        """[(weight as a conv [N, Cin, taps] builder, bias builder)] in launch order"""
+        K = len(self.resblock_kernel_sizes)
+        seq = [self.conv_pre]
+        for i in range(len(self.ups)):
+            seq.append(self.ups[i])
+            for j in range(K):
+                rb = self.resblocks[i * K + j]
+                if self.resblock == "1":
+                    for c1, c2 in zip(rb.convs1, rb.convs2):
+                        seq += [c1, c2]
+                else:
+                    seq += list(rb.convs)
+        return seq + [self.conv_post]
+
+    def images(self):
+        """[(bf16 image, fp32 bias)] per launch, rebuilt when any parameter's (data_ptr, _version) changes"""
+        params = list(self.parameters())
+
+        def build():
+            out = []
+            for m in self._convs():
+                if isinstance(m, nn.ConvTranspose1d):
+                    u = m.stride[0]
+                    out.append((voc_pack(transposed_as_conv(m.weight.detach().float(), u)), m.bias.detach().float().repeat(u).contiguous()))
+                else:
+                    out.append((voc_pack(m.weight.detach().float()), m.bias.detach().float().contiguous()))
+            return out
+        return self._images.get(params, build)
+
+    # ---- capacity-sized form ------------------------------------------------------------------------------------------------------------
+    def _width(self):
+        U, w = 1, self.channels[0]
+        for i, u in enumerate(self.upsample_rates):
+            U *= u
+            w = max(w, U * self.channels[i + 1])
+        return w
+
+    def workspace_bytes(self, B, F_max):
+        """(14 E, resblock "2": 16 E) + 4 B U F_max with E = B F_max W, W = max(C_0, max_i U_i C_i) elements per frame (8192 for V1)"""
+        return (14 if self.resblock == "1" else 16) * B * F_max * self._width() + 4 * B * self.hop_length * F_max
+
+    @property
+    def t_dtype(self):
+        """the fourth buffer: bf16 between a resblock "1"'s two convolutions; for resblock "2" a second fp32 residual stream"""
+        return torch.bfloat16 if self.resblock == "1" else torch.float32
+
+    def workspace(self, B, F_max, device):
+        """the buffers of one run at capacity (B utterances of up to F_max frames): three fp32 streams u, r, s (a stage's input, a
+        resblock's residual stream, the resblock sum / the stage's output) and one bf16 t (between a resblock's two convolutions) of
+        E = B F_max W elements each, W = max(C_0, max_i U_i C_i) (U_i the product of the first i rates, C_i the channels behind them:
+        8192 for V1), reused across the stages, and wav fp32 [B, U F_max]: 14 E + 4 B U F_max bytes — 2.94 GB + 26 MB for V1 at 32 x 800
+        frames.  Resblock "2" has no tensor between two convolutions but reads its own residual stream through a halo, which cannot be
+        updated in place: its t is a second fp32 stream (16 E).  B F_max W must stay below 2^31."""
+        E = B * F_max * self._width()
+        if B < 1 or F_max < 1 or E >= 2 ** 31:
+            raise ValueError(f"workspace for {B} x {F_max} frames: B F_max W = {E} must lie in [1, 2^31)")
+        f32 = lambda: torch.empty(E, dtype=torch.float32, device=device)  # noqa: E731
+        return dict(u=f32(), r=f32(), s=f32(), t=torch.empty(E, dtype=self.t_dtype, device=device),
+                    wav=torch.empty(B, self.hop_length * F_max, dtype=torch.float32, device=device))
+
+    def _launch(self, dev, n_frames, B, L, mul, X, img, Y, Cin, N, taps, dil, slope, x_sb, y_sb, ldy, x_sc=0, x_mel=0, x_bf16=0,
+                y_bf16=0, res=None, acc=None, scale=1.0, tanh=0):
+        a = _lib.fill_args(_lib.VocConvArgs, X=X, x_stride_b=x_sb, x_stride_c=x_sc, W=img[0], bias=img[1], res=res, acc=acc, Y=Y,
+                           y_stride_b=y_sb, ldy=ldy, len_mul=mul, n_frames=n_frames, B=B, L_cap=L, Cin=Cin, N=N, taps=taps, dil=dil,
+                           x_bf16=x_bf16, x_mel=x_mel, y_bf16=y_bf16, tanh_out=tanh, slope=slope, scale=scale)
+        call.gt_voc_conv(a, _lib.current_stream(dev))
+
+    def run(self, mel, n_frames, bufs):
+        """kernel calls, the capacity-sized form for graph callers: fp32 log-mel [B, n_mel, >= F_max] (any batch / channel pitch, frames
+        contiguous), device int32 [B] frame counts and workspace's buffers (B and F_max are theirs) -> bufs["wav"] [B, U F_max], row b
+        zero behind its U F_b samples.  `launches` gt_voc_conv calls; nothing is allocated once the images exist, n_frames is never
+        looked at on the host, every grid is sized by F_max."""
+        wav = bufs["wav"]
+        B, U = wav.shape[0], self.hop_length
+        F = wav.shape[1] // U
+        if not mel.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
+        if mel.dtype != torch.float32 or mel.dim() != 3 or mel.stride(2) != 1:
+            raise ValueError("run takes a device fp32 log-mel [B, n_mel, F] with contiguous frames")
+        if mel.shape[0] != B or mel.shape[1] != self.n_mel_channels or mel.shape[2] < F:
+            raise ValueError(f"mel {tuple(mel.shape)} does not fit buffers for [{B}, {self.n_mel_channels}, {F}]")
+        if n_frames.dtype != torch.int32 or n_frames.numel() != B or not n_frames.is_cuda or not n_frames.is_contiguous():
+            raise ValueError("n_frames must be a contiguous int32 [B] on the device")
+        if self.conv_pre.weight.device != mel.device:
+            raise ValueError("the vocoder's parameters are not on the mel's device")
+        dev, imgs = mel.device, iter(self.images())
+        u_, r_, s_, t_ = bufs["u"], bufs["r"], bufs["s"], bufs["t"]
+        K, ch = len(self.resblock_kernel_sizes), self.channels
+        go = lambda *a, **k: self._launch(dev, n_frames, B, *a, **k)  # noqa: E731
+        L, mul, C = F, 1, ch[0]
+        go(L, mul, mel, next(imgs), s_, self.n_mel_channels, C, 7, 1, 1.0, mel.stride(0) if B > 1 else max(mel.stride(0), F), L * C, C,
+           x_sc=mel.stride(1) if self.n_mel_channels > 1 else max(mel.stride(1), F), x_mel=1)
+        for i, u in enumerate(self.upsample_rates):
+            Cn = ch[i + 1]
+            go(L, mul, s_, next(imgs), u_, C, u * Cn, 3, 1, LRELU_SLOPE, L * C, L * u * Cn, u * Cn)
+            L, mul, C = L * u, mul * u, Cn
+            sb = L * C
+            for j, (k, ds) in enumerate(zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes)):
+                src = u_
+                for m, d in enumerate(ds):
+                    last = m == len(ds) - 1
+                    tail = dict(res=src, acc=s_ if j else None, scale=1.0 / K if j == K - 1 else 1.0) if last else dict(res=src)
+                    # "1": r in place (Y may alias res, X is t); "2": the conv reads its own residual stream, so r and t take turns
+                    dst = s_ if last else (r_ if self.resblock == "1" or m % 2 == 0 else t_)
+                    if self.resblock == "1":
+                        go(L, mul, src, next(imgs), t_, C, C, k, d, LRELU_SLOPE, sb, sb, C, y_bf16=1)
+                        go(L, mul, t_, next(imgs), dst, C, C, k, 1, LRELU_SLOPE, sb, sb, C, x_bf16=1, **tail)
+                    else:
+                        go(L, mul, src, next(imgs), dst, C, C, k, d, LRELU_SLOPE, sb, sb, C, **tail)
+                    src = dst
+        go(L, mul, s_, next(imgs), wav, C, 1, 7, 1, 0.01, L * C, wav.stride(0), 1, tanh=1)
+        return wav
+
+    def forward(self, mel, mel_lengths=None, mel_lengths_host=None):
+        """log-mel [B, n_mel, F] -> wav [B, U F]; with mel_lengths (frames per utterance) the ragged form -> (wav, wav_lengths =
+        U mel_lengths), zero behind each utterance.  mel_lengths_host spares the host a look at a device tensor."""
+        if not mel.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
+        if mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
+            raise ValueError(f"mel is [B, {self.n_mel_channels}, F], got {tuple(mel.shape)}")
+        if mel.dtype != torch.float32 or mel.stride(2) != 1:
+            mel = mel.float().contiguous()
+        B, _, F = mel.shape
+        if mel_lengths is None:
+            n_frames = torch.full((B,), F, dtype=torch.int32, device=mel.device)
+        else:
+            if mel_lengths_host is None and not mel_lengths.is_cuda:
+                mel_lengths_host = mel_lengths.tolist()
+            if mel_lengths.numel() != B or (mel_lengths_host is not None and (len(mel_lengths_host) != B or max(mel_lengths_host) > F)):
+                raise ValueError(f"frame counts do not fit a [{B}, {self.n_mel_channels}, {F}] mel")
+            n_frames = mel_lengths.to(mel.device, non_blocking=True).to(torch.int32).contiguous()
+        if F == 0 or B == 0:
+            wav = mel.new_zeros(B, self.hop_length * F)
+        else:
+            wav = self.run(mel, n_frames, self.workspace(B, F, mel.device))
+        if mel_lengths is None:
+            return wav
+        return wav, n_frames.clamp(min=0, max=F) * self.hop_length

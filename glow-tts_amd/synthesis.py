@@ -295,7 +295,9 @@ class SynthesisHandle:
         return out
 
     def wav(self, clone=False, fallback=True):
-        """compile_synthesis(vocoder=): (wav [B, 256 (T - 1)] fp32, wav_lengths) with T = max(lengths) rounded down to even (the mel's
+        """With an audio.HiFiGAN: (wav [B, U T] fp32, wav_lengths = [U 2 (lengths[b] // 2)]), bit-identical to vocoder(mel,
+        2 (lengths // 2)) (after an overflow: that eager call on the eager mel), under the rules below.  With an audio.GriffinLim:
+        compile_synthesis(vocoder=): (wav [B, 256 (T - 1)] fp32, wav_lengths) with T = max(lengths) rounded down to even (the mel's
         frames) and wav_lengths[b] = 256 max(2 (lengths[b] // 2) - 1, 0) (a host list) — the call's samples, zero behind every
         utterance's, bit-identical to GriffinLim.from_mel(mel, 2 (lengths // 2), n_iters=vocoder_iters, seed=the call's seed,
         phases="counter").  A view of the synthesiser's static buffer under mel()'s stream-order rules (clone=True: a copy that outlives
@@ -311,18 +313,26 @@ class SynthesisHandle:
         if s.vocoder is None:
             raise RuntimeError("compile_synthesis(vocoder=audio.GriffinLim(...)) keeps the samples")
         lens, status = self._wait()
-        hop = s.vocoder.stft_fn.hop_length
-        wav_lengths = [hop * max(2 * (v // 2) - 1, 0) for v in lens]
+        if s.neural:                                                     # audio.HiFiGAN: U samples per frame, no frame lost
+            hop = s.vocoder.hop_length
+            wav_lengths = [hop * 2 * (v // 2) for v in lens]
+            n = hop * (max(lens) // 2 * 2)
+        else:
+            hop = s.vocoder.stft_fn.hop_length
+            wav_lengths = [hop * max(2 * (v // 2) - 1, 0) for v in lens]
+            n = hop * max(max(lens) // 2 * 2 - 1, 0)
         if status != 0:
             mel = self._fallback(fallback)[0][0]
             if self._eager_wav is None:
-                if mel.shape[2] < 2:
+                if s.neural:
+                    frames = torch.tensor([2 * (v // 2) for v in lens], dtype=torch.int32).to(s.device)
+                    self._eager_wav = s.vocoder(mel, frames, mel_lengths_host=[2 * (v // 2) for v in lens])[0]
+                elif mel.shape[2] < 2:
                     self._eager_wav = mel.new_zeros(mel.shape[0], 0)
                 else:
                     frames = torch.tensor([2 * (v // 2) for v in lens], dtype=torch.int32).to(s.device)
                     self._eager_wav = s.vocoder.from_mel(mel, frames, n_iters=s.vocoder_iters, seed=self._call.seed, phases="counter")[0]
             return self._eager_wav, wav_lengths
-        n = hop * max(max(lens) // 2 * 2 - 1, 0)
         if self._saved is not None:
             return self._from_saved()[3][:, :n], wav_lengths
         if self._done and s._latest is not None and s._latest() is not self:
@@ -387,7 +397,10 @@ class Synthesizer:
     [batch] = 2 * the squeezed lengths), wav_static [batch, 256 (max_frames - 1)] and voc_bufs (mag [batch, 513, max_frames], the
     spectrum workspace, wav_static) — 4 batch (513 max_frames + 1025 Fp + 256 (max_frames - 1)) bytes with Fp = max_frames rounded up
     to 64: 52 + 109 + 26 MB at batch 32 and 800 frames.  vocoder_iters is fixed at capture; every launch of the loop is sized by
-    max_frames, so a call of short utterances pays the loop of the capacity (tiles behind an utterance's end only write zeros)."""
+    max_frames, so a call of short utterances pays the loop of the capacity (tiles behind an utterance's end only write zeros).
+    vocoder=audio.HiFiGAN puts the neural generator there instead (vocoder_iters is ignored): wav_static
+    [batch, U max_frames] with U the product of its upsample rates, voc_bufs = HiFiGAN.workspace's buffers as static buffers
+    (14 batch max_frames W + 4 batch U max_frames bytes, W = 8192 for V1), captured_entries grows by vocoder.launches."""
 
     RING = 8
 
@@ -396,15 +409,25 @@ class Synthesizer:
         self.stochastic = bool(stochastic)
         if vocoder is not None:                                          # refused before any allocation
             from . import audio
-            if not isinstance(vocoder, audio.GriffinLim) or not isinstance(vocoder.stft, audio.TacotronSTFT):
-                raise TypeError("compile_synthesis(vocoder=) takes an audio.GriffinLim built over an audio.TacotronSTFT")
-            if vocoder.stft.mel_basis.device != next(gen.parameters()).device or vocoder.istft.inverse_basis.device != next(gen.parameters()).device:
+            self.neural = isinstance(vocoder, audio.HiFiGAN)
+            if self.neural:                                              # vocoder_iters is not its business
+                if any(p.device != next(gen.parameters()).device for p in vocoder.parameters()):
+                    raise ValueError("compile_synthesis(vocoder=): the vocoder's parameters are not on the model's device")
+                if vocoder.n_mel_channels != gen.out_channels:
+                    raise ValueError(f"compile_synthesis(vocoder=): the vocoder takes {vocoder.n_mel_channels} mel channels, the "
+                                     f"model writes {gen.out_channels}")
+                vocoder_iters = 0
+            elif not isinstance(vocoder, audio.GriffinLim) or not isinstance(vocoder.stft, audio.TacotronSTFT):
+                raise TypeError("compile_synthesis(vocoder=) takes an audio.HiFiGAN, or an audio.GriffinLim built over an audio.TacotronSTFT")
+            elif vocoder.stft.mel_basis.device != next(gen.parameters()).device or vocoder.istft.inverse_basis.device != next(gen.parameters()).device:
                 raise ValueError("compile_synthesis(vocoder=): the vocoder's buffers are not on the model's device")
-            if vocoder.stft.mel_basis.shape[0] != gen.out_channels:
+            elif vocoder.stft.mel_basis.shape[0] != gen.out_channels:
                 raise ValueError(f"compile_synthesis(vocoder=): the vocoder inverts {vocoder.stft.mel_basis.shape[0]} mel channels, the "
                                  f"model writes {gen.out_channels}")
-            if int(vocoder_iters) != vocoder_iters or vocoder_iters < 0:
+            elif int(vocoder_iters) != vocoder_iters or vocoder_iters < 0:
                 raise ValueError("compile_synthesis: vocoder_iters is a non-negative integer")
+        else:
+            self.neural = False
         self.vocoder, self.vocoder_iters = vocoder, int(vocoder_iters)
         if not self.stochastic and (gen.use_sdp or gen.use_spp or gen.use_sep or gen.use_emo_embeds):
             raise NotImplementedError("compile_synthesis covers the deterministic duration predictor with optional speaker / language "
@@ -489,7 +512,17 @@ class Synthesizer:
                 self.energy_static, self.esig = self._static(B * Ty, torch.float32).view(B, Ty), self._static(R * 2, torch.float32).view(R, 2)
         # ---- the waveform back end: magnitudes, the spectrum workspace, the samples, the frame counts the mel has
         self.wav_static = self.voc_bufs = self.n_frames = self._voc_images = None
-        if vocoder is not None:
+        if self.neural:
+            # three fp32 streams and one bf16 of B max_frames W elements (HiFiGAN.workspace) and the samples
+            self.n_frames = self._static(B, torch.int32)
+            E = B * Ty * vocoder._width()
+            if E >= 2 ** 31:
+                raise ValueError(f"compile_synthesis(vocoder=): batch * max_frames * {vocoder._width()} = {E} elements per buffer, 2^31 or more")
+            self.wav_static = self._static(B * vocoder.hop_length * Ty, torch.float32).view(B, vocoder.hop_length * Ty)
+            self.voc_bufs = dict(u=self._static(E, torch.float32), r=self._static(E, torch.float32), s=self._static(E, torch.float32),
+                                 t=self._static(E, vocoder.t_dtype), wav=self.wav_static)
+            self._voc_images = vocoder.images()                          # kept: the graph holds their addresses
+        elif vocoder is not None:
             self.n_frames = self._static(B, torch.int32)
             self.wav_static = self._static(B * 256 * (Ty - 1), torch.float32).view(B, 256 * (Ty - 1))
             self.voc_bufs = dict(mag=self._static(B * 513 * Ty, torch.float32).view(B, 513, Ty),
@@ -544,7 +577,10 @@ class Synthesizer:
         if self.vocoder is not None:
             # the frames the mel really has (the squeeze drops an odd trailing frame); the phases' seed is the call block's first word
             torch.mul(rcy.lengths, 2, out=self.n_frames)
-            self.vocoder.run_from_mel(self.mel_static, self.n_frames, self.voc_bufs, self.vocoder_iters, seed_dev=self.call[:1])
+            if self.neural:
+                self.vocoder.run(self.mel_static, self.n_frames, self.voc_bufs)
+            else:
+                self.vocoder.run_from_mel(self.mel_static, self.n_frames, self.voc_bufs, self.vocoder_iters, seed_dev=self.call[:1])
         if self.aux:
             a["logw"] = logw
         return xm, xs, xl, dur, logw                                     # kept: the graph replays into these

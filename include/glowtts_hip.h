@@ -1105,6 +1105,46 @@ size_t gt_resample_lds_bytes(int up, int down);
 int gt_resample(const void* wav, int is_i16, int ld_wav, const int32_t* wav_len, int B, const float* bank, int up, int down,
                 int taps, float* out, int ld_out, int32_t* out_len, void* stream);
 
+/* ---- HiFi-GAN generator (csrc/hifigan.hip): one dilated-convolution MFMA kernel for every layer --------------------
+ * gt_voc_conv: a dilated 1-D convolution of a ragged batch on dense channels-last activations, bf16 operands, fp32 accumulation,
+ * every utterance zero-padded at its own ends:
+ *   Y[b, t, n] = epi( sum_{j < taps} sum_{ci < Cin} bf16( lrelu( X[b, t + (j - taps / 2) dil, ci] ) ) W[j][n][ci] )      t < len_b
+ *   len_b = min(max(n_frames[b], 0) len_mul, L_cap).  A tap outside [0, len_b) contributes 0 and is never read (whatever lies there);
+ *   Y at positions [len_b, L_cap) is written as 0; nothing beyond L_cap is touched.  The host never reads n_frames.
+ *   X        fp32 (x_bf16 == 0) or bf16 [B, L_cap, Cin], element (b, t, c) at X[b x_stride_b + t Cin + c]; or, x_mel != 0 (fp32 only),
+ *            the channel-major log-mel of the decoder, element (b, c, t) at X[b x_stride_b + c x_stride_c + t] (gt_gl_from_mel's form).
+ *   lrelu    v < 0 ? v slope : v in fp32 (slope = 1: none), then round-to-nearest-even to bf16: that value is the MFMA operand.
+ *   W        bf16 image in MFMA-fragment order, [taps][Np / 32][Kp / 16][64 lanes][8]: lane 32 h + r, element e holds
+ *            W[j][32 nt + r][16 ks + 8 h + e], zeros for n >= N and ci >= Cin; Np = N rounded up to 32, Kp = Cin rounded up to
+ *            gt_voc_k_chunk(Cin) (64 where 64 divides Cin, else 32).  Packed once per weight version by the caller.
+ *   epi(s)   (s + bias[n] + res[b, t, n] + acc[b, t, n]) scale, then tanh when tanh_out != 0 (the kernels' fast tanh); res and acc
+ *            are optional fp32 with Y's geometry.  Y is fp32 or bf16 (y_bf16), element (b, t, n) at Y[b y_stride_b + t ldy + n].
+ *            Y may alias res and / or acc (each element is read and written by the same lane); Y may not alias X.
+ * Asynchronous, no allocation, no atomics, capturable in a graph; the grid is sized by L_cap.  The summation order of an element
+ * depends on (t, n, Cin, taps) alone: a batch row is bit-identical to the utterance computed alone, in a buffer of any capacity.
+ * A workgroup owns gt_voc_tile_positions() positions and stages them plus (taps - 1) dil halo rows of one Cin chunk in
+ * gt_voc_lds_bytes(Cin, taps, dil) bytes of LDS = (tile + (taps - 1) dil) (2 chunk + 16), at most 64 KB (0 for a shape that is refused).
+ * Refusals, before any launch and in this order: args or X / W / bias / Y / n_frames NULL; B, L_cap, Cin, N, dil or len_mul <= 0; taps
+ * <= 0 or even; ldy < N, y_stride_b < L_cap ldy; x_stride_b < L_cap Cin (x_mel: x_stride_b or x_stride_c < L_cap, or x_bf16 set);
+ * Y == X: GT_E_INVAL.  taps > GT_VOC_MAX_TAPS, Cin no multiple of 16, B > 65535, B L_cap max(Cin, N) >= 2^31, a halo past the LDS
+ * bound: GT_E_UNSUPPORTED.  W not 16-byte, bias / n_frames / Y / res / acc not 4-byte aligned, X not 16-byte aligned or x_stride_b no
+ * multiple of 8 (x_mel: X not 4-byte aligned): GT_E_ALIGN. */
+#define GT_VOC_MAX_TAPS 11
+typedef struct gt_voc_conv_args {
+  const void* X; int64_t x_stride_b; int64_t x_stride_c;
+  const void* W; const float* bias; const float* res; const float* acc;
+  void* Y; int64_t y_stride_b; int ldy;
+  int len_mul; const int32_t* n_frames;
+  int B; int L_cap; int Cin; int N; int taps; int dil;
+  int x_bf16; int x_mel; int y_bf16; int tanh_out;
+  float slope; float scale;
+} gt_voc_conv_args;
+int gt_voc_conv(const gt_voc_conv_args* args, void* stream);
+int gt_voc_conv_args_size(void);                /* sizeof(gt_voc_conv_args): lets a binding check its mirror of the struct */
+int gt_voc_tile_positions(void);
+int gt_voc_k_chunk(int Cin);
+size_t gt_voc_lds_bytes(int Cin, int taps, int dil);
+
 #ifdef __cplusplus
 }
 #endif
