@@ -52,6 +52,7 @@ PROTOTYPES = {
                                    c_int, c_int, c_int, c_int, c_void_p]),
     "gt_conv_wgrad_batched": (STATUS, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gt_weightnorm_bwd_batched": (STATUS, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gt_conv_wgrad_paired": (STATUS, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "gt_adamw_flat": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "gt_colsum": (STATUS, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "gt_squeeze_rows_f32": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -43,6 +43,15 @@ __device__ __forceinline__ void glds16(const void* src, unsigned dst_base) {
                "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(src), "s"(dst_base) : "memory");
 }
+// The same with a wave-uniform base and a 32-bit byte offset per lane: the paired form keeps each lane's offsets within a stage in
+// registers and moves the base from stage to stage with scalar arithmetic (no 64-bit vector address per load).  s_nop 4: the base may
+// come from a v_readfirstlane.
+__device__ __forceinline__ void glds16s(const void* base, unsigned off, unsigned dst_base) {
+  unsigned keep;
+  asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(off), "s"(base), "s"(dst_base) : "memory");
+}
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
 // Geometry of one ring stage: KB rows of the dY tile (128 columns = 256 B per row) and KB + TAPS - 1 rows of the X tile (64 NJ columns =
@@ -291,6 +300,252 @@ template <int TAPS> static int wgrad_lds_attr()
   if (gt_allow_lds<&gt_conv_wgrad_kernel<TAPS>>(WgGeoT<TAPS>::LDS) || gt_allow_lds<&gt_conv_wgrad_batched_kernel<TAPS>>(WgGeoT<TAPS>::LDS)) return GT_E_LAUNCH;
   return 0;
 }
+
+// ---- paired form (TAPS = 5, 3): one 512-thread workgroup computes TWO 128 co x 64 ci tiles of one (job, slab) from one ring.
+// Wave group g = wave >> 2 is the 2 x 2 of 64 co x 32 ci waves of wgrad_tile and owns one of the tiles:
+//   KIND 0, same-co pair: both groups read the one dY block [co0, co0 + 128); group g reads X columns [ci0 + 64 g, +64).  The X stage
+//           has 256-byte rows and takes dY's source-side swizzle (c ^ 4 (r & 3)).  A group whose columns start at or past Cin is
+//           dead (a SINGLE: the leftover tile of an odd x odd grid): it issues its share of the loads and executes every barrier,
+//           but reads no fragment, issues no MFMA and stores nothing.
+//   KIND 1, same-ci pair: both groups read the one X block [ci0, ci0 + 64) (wgrad_tile's layout); group g reads dY block
+//           [co0 + 128 g, +128), block g of the stage.
+// The 4-wave form stages every dY block once per ci tile and every X block once per co tile; here a stage is 33 KB (KIND 0) or 40.5 KB
+// (KIND 1) for two tiles where two 4-wave workgroups staged 2 x 24.5 KB.  One workgroup per CU has the whole LDS: KIND 0 runs a
+// 4-deep ring (132 KB), KIND 1 a 3-deep one (121.5 KB; 4 stages would be 162 KB).  Each accumulator sees the fragments wgrad_tile
+// gives it, in the same ascending 16-row k-steps of the same 64-row stages: partials are bit-identical to the 4-wave form.
+template <int TAPS, int KIND> struct WgGeo8 {
+  static constexpr int KB = 64, NST = KIND ? 3 : 4;
+  static constexpr int NY = KIND ? 2 : 1;            // dY blocks of 128 columns per stage
+  static constexpr int XR = KB + TAPS - 1;
+  static constexpr int XCH = KIND ? 8 : 16;          // 16-byte chunks per X row
+  static constexpr int YB = NY * KB * 256, XB = XR * XCH * 16, STAGE = YB + XB;
+  static constexpr int YI = NY * KB * 16 / 512;      // dY LDS-DMA instructions per wave and stage
+  static constexpr int NWX = XR * XCH / 8;           // X chunks per wave and stage
+  static constexpr int XI = (NWX + 63) / 64;         // ... instructions (the last one partially masked; every wave has a lane in each)
+  static constexpr int NLD = YI + XI;
+  static constexpr int LDS = NST * STAGE;
+  static_assert((XR * XCH) % 8 == 0, "X chunks split evenly over the waves");
+  static_assert(NWX > 64 * (XI - 1), "every wave issues all XI instructions");
+  static_assert(STAGE % 256 == 0 && YB % 256 == 0, "stages keep the bank phase");
+  static_assert(LDS <= 160 * 1024, "one workgroup per CU");
+  static_assert((NST - 2) * NLD <= 63, "vmcnt field");
+};
+
+template <int TAPS, int KIND>
+__device__ __forceinline__ void wgrad_pair_tile(
+    const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ dY, int ldy,
+    float* __restrict__ part, float* __restrict__ part_bias, int R, int Cin, int Cout, int slab_rows,
+    int co0, int ci0, int slab, int co_begin, int Ncols)
+{
+  using G = WgGeo8<TAPS, KIND>;
+  constexpr int KB = G::KB, NST = G::NST, NB = TAPS;
+  extern __shared__ __attribute__((aligned(1024))) unsigned char ring[];       // [NST][STAGE]
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  constexpr int padl = TAPS >> 1;
+  const int mbeg = slab * slab_rows;
+  const int mend = min(R, mbeg + slab_rows);
+  const int nst = (mend - mbeg + KB - 1) / KB;
+  const int grp = wave >> 2, wco = (wave >> 1) & 1, wci = wave & 1;
+  const int gco0 = co0 + (KIND ? grp * 128 : 0), gci0 = ci0 + (KIND ? 0 : grp * 64);      // this group's tile
+  const bool live = KIND ? gco0 < Ncols : gci0 < Cin;                                     // wave-uniform
+  // column sums of dY: wave (wco, wci) sums the columns of its dY^T fragment wci (wgrad_tile: the wci = 0 waves sum both fragments and
+  // are the last at every barrier); the additions of a column and their order are the same
+  const bool do_bias = live && (gci0 == 0) && part_bias;
+
+  f32x16_t acc[NB][2];
+  float bsum = 0.f;
+#pragma unroll
+  for (int t = 0; t < NB; ++t)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[t][j][e] = 0.0f;
+
+  // ---- what this lane fetches per stage: chunk L of the stage's dY part is row (L >> 4) & 63 of block L >> 10; the X part as in wgrad_tile
+  int yrow[G::YI], ycol[G::YI], xrow[G::XI], xcol[G::XI];
+  bool xact[G::XI];
+#pragma unroll
+  for (int j = 0; j < G::YI; ++j) {
+    const int L = j * 512 + tid, r = (L >> 4) & 63, c = (L & 15) ^ ((r & 3) << 2);
+    yrow[j] = r; ycol[j] = min(co0 + (L >> 10) * 128 + c * 8, Ncols - 8);
+  }
+#pragma unroll
+  for (int j = 0; j < G::XI; ++j) {
+    const int Lw = j * 64 + lane, L = wave * G::NWX + Lw, r = L / G::XCH, cc = L - r * G::XCH;
+    const int c = KIND ? cc ^ (((r >> 1) & 1) << 2) : cc ^ ((r & 3) << 2);
+    xact[j] = Lw < G::NWX;
+    xrow[j] = r - padl; xcol[j] = min(ci0 + c * 8, Cin - 8);
+  }
+  const unsigned ring0 = lds_off(ring);
+  unsigned yoff[G::YI], xoff[G::XI];                  // byte offsets from the stage's first dY row / first X row (row mb - padl)
+#pragma unroll
+  for (int j = 0; j < G::YI; ++j) yoff[j] = (unsigned)(yrow[j] * ldy + ycol[j]) * 2u;
+#pragma unroll
+  for (int j = 0; j < G::XI; ++j) xoff[j] = (unsigned)((xrow[j] + padl) * ldx + xcol[j]) * 2u;
+
+  auto issue = [&](int s, int sl_i) {
+    const int mb = mbeg + s * KB;
+    const unsigned slot = ring0 + (unsigned)sl_i * G::STAGE;
+    const bool edge = (mb - padl < 0) || (mb + KB + padl > R) || (mb + KB > mend);       // workgroup-uniform
+    if (!edge) {
+      const bf16_t* ys = dY + (size_t)mb * ldy;
+      const bf16_t* xs = X + (size_t)(mb - padl) * ldx;
+#pragma unroll
+      for (int j = 0; j < G::YI; ++j) glds16s(ys, yoff[j], slot + (unsigned)(j * 512 + wave * 64) * 16);
+#pragma unroll
+      for (int j = 0; j < G::XI; ++j)
+        if (xact[j]) glds16s(xs, xoff[j], slot + G::YB + (unsigned)(wave * G::NWX + j * 64) * 16);
+    } else {
+      // as in wgrad_tile: plain loads, zero rows; the compiler's vmcnt(0) in front of the LDS writes retires every LDS-DMA before
+      unsigned char* sl = ring + (size_t)sl_i * G::STAGE;
+#pragma unroll
+      for (int j = 0; j < G::YI; ++j) {
+        const int m = mb + yrow[j];
+        u32x4_t v = {0u, 0u, 0u, 0u};
+        if (m < mend) v = *reinterpret_cast<const u32x4_t*>(dY + (size_t)m * ldy + ycol[j]);
+        *reinterpret_cast<u32x4_t*>(sl + (size_t)(j * 512 + tid) * 16) = v;
+      }
+#pragma unroll
+      for (int j = 0; j < G::XI; ++j) {
+        const int m = mb + xrow[j];
+        u32x4_t v = {0u, 0u, 0u, 0u};
+        if (xact[j]) {
+          if (m >= 0 && m < R) v = *reinterpret_cast<const u32x4_t*>(X + (size_t)m * ldx + xcol[j]);
+          *reinterpret_cast<u32x4_t*>(sl + G::YB + (size_t)(wave * G::NWX + j * 64 + lane) * 16) = v;
+        }
+      }
+    }
+  };
+
+  const int li = lane & 15, q = li >> 2, p = li & 3;
+  const int colhalf = ((lane >> 4) & 1) * 16;
+  const int h = lane >> 5;
+  constexpr int NOX = TAPS < 4 ? TAPS : 4;             // distinct row phases of the X swizzle
+  int offA[2], offX[NOX];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int ch = wco * 8 + i * 4 + (colhalf >> 3) + (p >> 1);
+    offA[i] = (KIND ? grp * KB * 256 : 0) + (8 * h + q) * 256 + ((ch ^ (q << 2)) << 4) + (p & 1) * 8;
+  }
+#pragma unroll
+  for (int t = 0; t < NOX; ++t) {
+    const int ch = (KIND ? 0 : grp * 8) + wci * 4 + (colhalf >> 3) + (p >> 1);
+    const int sw = KIND ? (((q + t) >> 1) & 1) << 2 : ((q + t) & 3) << 2;
+    offX[t] = (8 * h + q) * (G::XCH * 16) + ((ch ^ sw) << 4) + (p & 1) * 8;
+  }
+
+  // Fragments one k-step ahead.  The two waves of a SIMD run this same program behind the same barrier, so with wgrad_tile's order
+  // (all reads of a k-step, then its MFMAs) both wait for their reads together and the matrix pipe idles meanwhile.  Here the dY^T
+  // fragments are double-buffered (8 registers) and each X fragment is re-read for the NEXT k-step right behind the two MFMAs that
+  // consume it, so the reads of k-step i + 1 travel under the MFMAs of k-step i.  The step to the next stage (wait, barrier, issue)
+  // sits in front of a stage's LAST k-step, whose fragments are in registers by then, so the prefetch runs across stages too.
+  bf16x8_t af[2][2], bfg[NB];
+  auto read_a = [&](int buf, const unsigned char* yb, int ks) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const unsigned char* ya = yb + offA[i] + ks * 16 * 256;
+      af[buf][i] = tr_frag(ya, ya + 4 * 256);
+    }
+  };
+  auto read_b = [&](int t, const unsigned char* xb, int ks) {
+    const unsigned char* xa = xb + offX[t & 3] + (ks * 16 + t) * (G::XCH * 16);
+    bfg[t] = tr_frag(xa, xa + 4 * (G::XCH * 16));
+  };
+  // k-step ks on the fragments in registers; meanwhile fetch those of k-step ksn of the stage at (ybn, xbn)
+  auto kstep = [&](int ks, const unsigned char* ybn, const unsigned char* xbn, int ksn) {
+    const int cur = ks & 1;
+    read_a(cur ^ 1, ybn, ksn);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) acc[t][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][i], bfg[t], acc[t][i], 0, 0, 0);
+      read_b(t, xbn, ksn);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (do_bias) {
+      const u32x4_t w4 = __builtin_bit_cast(u32x4_t, wci ? af[cur][1] : af[cur][0]);
+#pragma unroll
+      for (int d = 0; d < 4; ++d) bsum += __uint_as_float(w4[d] << 16) + __uint_as_float(w4[d] & 0xffff0000u);
+    }
+  };
+
+#pragma unroll 1
+  for (int s = 0; s < NST - 1 && s < nst; ++s) issue(s, s);
+  int cslot = 0, islot = NST - 1;
+  int pend_s = -1, pend_slot = 0;                               // group 1: the stage to issue, deferred (below)
+  // Step to stage s: this wave's share of it has landed when at most (stages issued after s) x NLD of its LDS-DMAs are in flight; behind
+  // the barrier everyone's share has and everyone has read the last fragment of stage s - 1, whose slot stage s + NST - 1 goes to.
+  // Every wave, live or dead, runs this nst times: the wait counts, the barriers and the issues depend on s and nst alone.
+  // Group 0 issues its share right behind the barrier, group 1 three k-steps later (the slot stays free until the next barrier, and
+  // the share is issued before this wave's next wait either way): issuing together, the two waves of a SIMD left its matrix pipe idle
+  // (measured: 303 -> 293 us for the decoder's launch, `profiles/wgrad_pair_variants.txt`).
+  auto advance = [&](int s) {
+    const int after = min(nst - 1, s + NST - 2) - s;
+    if (after >= NST - 2) wait_vm<(NST - 2) * G::NLD>();
+    else wait_vm<0>();
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (s + NST - 1 < nst) {
+      if (grp == 0) issue(s + NST - 1, islot);
+      else { pend_s = s + NST - 1; pend_slot = islot; }
+    }
+    islot = islot + 1 == NST ? 0 : islot + 1;
+  };
+  advance(0);
+  const unsigned char* yb = ring;
+  if (live) {
+    read_a(0, yb, 0);
+#pragma unroll
+    for (int t = 0; t < NB; ++t) read_b(t, yb + G::YB, 0);
+  }
+#pragma unroll 1
+  for (int s = 0; s < nst; ++s) {
+    if (live) {
+#pragma unroll
+      for (int ks = 0; ks < KB / 16 - 1; ++ks) kstep(ks, yb, yb + G::YB, ks + 1);
+    }
+    if (pend_s >= 0) { issue(pend_s, pend_slot); pend_s = -1; }
+    if (s + 1 < nst) advance(s + 1);
+    cslot = cslot + 1 == NST ? 0 : cslot + 1;
+    yb = ring + (size_t)cslot * G::STAGE;
+    // (behind the job's last stage this fetches fragments nobody uses, from a ring slot no LDS-DMA is in flight to)
+    if (live) kstep(KB / 16 - 1, yb, yb + G::YB, 0);
+  }
+  if (!live) return;                                   // (past the last barrier)
+
+  const int r = lane & 31;
+#pragma unroll
+  for (int t = 0; t < TAPS; ++t) {
+    const int ci = gci0 + wci * 32 + r;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      if (ci >= Cin) continue;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int co = gco0 + wco * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (co < Ncols) part[(((size_t)slab * TAPS + t) * Cout + co_begin + co) * Cin + ci] = acc[t][i][e];
+      }
+    }
+  }
+  if (do_bias) {
+    const float tot = bsum + __shfl_xor(bsum, 32);
+    const int co = gco0 + wco * 64 + wci * 32 + r;
+    if (h == 0 && co < Ncols) part_bias[(size_t)slab * Cout + co_begin + co] = tot;
+  }
+}
+
+template <int TAPS>
+__global__ __launch_bounds__(512, 1) void gt_conv_wgrad_paired_kernel(
+    const gt_wgrad_job* __restrict__ jobs, const gt_wgrad_pair* __restrict__ pairs)
+{
+  const gt_wgrad_pair t = pairs[blockIdx.x];
+  const gt_wgrad_job j = jobs[t.job];
+  const bf16_t* x = static_cast<const bf16_t*>(j.X); const bf16_t* dy = static_cast<const bf16_t*>(j.dY);
+  if (t.kind == 0) wgrad_pair_tile<TAPS, 0>(x, j.ldx, dy, j.ldy, j.part, j.part_bias, j.R, j.Cin, j.Cout, j.slab_rows, t.co0, t.ci0, t.slab, j.co_begin, j.co_count);
+  else             wgrad_pair_tile<TAPS, 1>(x, j.ldx, dy, j.ldy, j.part, j.part_bias, j.R, j.Cin, j.Cout, j.slab_rows, t.co0, t.ci0, t.slab, j.co_begin, j.co_count);
+}
+
+template <int TAPS> constexpr int wgrad_pair_lds() { return WgGeo8<TAPS, 0>::LDS > WgGeo8<TAPS, 1>::LDS ? WgGeo8<TAPS, 0>::LDS : WgGeo8<TAPS, 1>::LDS; }
 
 // Sum the S slab partials and map to the parameter gradient(s).  One WAVE per output channel co (4 per workgroup):
 //   plain conv:   dw[co][ci][tap] (+)= dW
@@ -682,6 +937,18 @@ extern "C" int gt_conv_wgrad_batched(const void* jobs_device, const void* tiles_
   if (n_tiles5) hipLaunchKernelGGL(gt_conv_wgrad_batched_kernel<5>, dim3(n_tiles5), dim3(256), WgGeoT<5>::LDS, st, jobs, tiles);
   if (n_tiles3) hipLaunchKernelGGL(gt_conv_wgrad_batched_kernel<3>, dim3(n_tiles3), dim3(256), WgGeoT<3>::LDS, st, jobs, tiles + n_tiles5);
   if (n_tiles1) hipLaunchKernelGGL(gt_conv_wgrad_batched_kernel<1>, dim3(n_tiles1), dim3(256), WgGeoT<1>::LDS, st, jobs, tiles + n_tiles5 + n_tiles3);
+  return gt_launch_status(__func__);
+}
+
+extern "C" int gt_conv_wgrad_paired(const void* jobs_device, const void* pairs_device, int n_pairs5, int n_pairs3, void* stream)
+{
+  if (!jobs_device || !pairs_device || n_pairs5 < 0 || n_pairs3 < 0) return GT_E_INVAL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const gt_wgrad_job* jobs = static_cast<const gt_wgrad_job*>(jobs_device);
+  const gt_wgrad_pair* pairs = static_cast<const gt_wgrad_pair*>(pairs_device);
+  if (gt_allow_lds<&gt_conv_wgrad_paired_kernel<5>>(wgrad_pair_lds<5>()) || gt_allow_lds<&gt_conv_wgrad_paired_kernel<3>>(wgrad_pair_lds<3>())) return GT_E_LAUNCH;
+  if (n_pairs5) hipLaunchKernelGGL(gt_conv_wgrad_paired_kernel<5>, dim3(n_pairs5), dim3(512), wgrad_pair_lds<5>(), st, jobs, pairs);
+  if (n_pairs3) hipLaunchKernelGGL(gt_conv_wgrad_paired_kernel<3>, dim3(n_pairs3), dim3(512), wgrad_pair_lds<3>(), st, jobs, pairs + n_pairs5);
   return gt_launch_status(__func__);
 }
 

@@ -24,8 +24,9 @@ TILE = np.dtype([("job", "i4"), ("co0", "i4"), ("ci0", "i4"), ("slab", "i4")])
 WNB = np.dtype([("part", "u8"), ("part_bias", "u8"), ("v", "u8"), ("g", "u8"), ("inv_norm", "u8"), ("dv", "u8"), ("dg", "u8"),
                 ("dbias", "u8"), ("S", "i4"), ("Cout", "i4"), ("Cin", "i4"), ("taps", "i4"), ("row_start", "i4"),
                 ("accumulate", "i4"), ("pad0_", "i4"), ("pad1_", "i4")])
-assert JOB.itemsize == 64 and TILE.itemsize == 16 and WNB.itemsize == 96
-C_STRUCTS = {"gt_wgrad_job": JOB, "gt_wgrad_tile": TILE, "gt_wnb_job": WNB}      # include/glowtts_hip.h; layouts checked in tests/test_cabi.py
+PAIR = np.dtype([("job", "i4"), ("co0", "i4"), ("ci0", "i4"), ("slab", "i4"), ("kind", "i4"), ("pad0_", "i4"), ("pad1_", "i4"), ("pad2_", "i4")])
+assert JOB.itemsize == 64 and TILE.itemsize == 16 and WNB.itemsize == 96 and PAIR.itemsize == 32
+C_STRUCTS = {"gt_wgrad_job": JOB, "gt_wgrad_tile": TILE, "gt_wnb_job": WNB, "gt_wgrad_pair": PAIR}      # include/glowtts_hip.h; layouts checked in tests/test_cabi.py
 
 # Row slabs per job.  A launch's workgroups (tiles x slabs) run two per CU — SLOTS at a time —, each walks its slab's rows at about
 # ROW_US per row whatever the tap count (operand latency, not MFMA, sets it; measured 0.033 us with both slots of a CU busy), and every
@@ -40,6 +41,12 @@ MAX_SLABS = 32
 XCDS = 8
 CI_TILE = {5: 64, 3: 64, 1: 192}      # input channels per workgroup tile (conv_wgrad.hip WgSel; checked against the library at flush time)
 FORCE_SLABS = int(os.environ.get("GT_WGRAD_SLABS", "0"))           # dev knob: the same slab count for every job
+# PAIRED: the k = 5 and k = 3 launches run 512-thread workgroups that compute two tiles of a (job, slab) from one staged copy of the
+# rows they share (gt_conv_wgrad_paired); False (dev knob GT_WGRAD_PAIRED=0) = the 4-wave form everywhere, the comparison path of
+# tests/test_wgrad_paired_gpu.py.  A launch with fewer than PAIR_MIN_WGS paired workgroups keeps the 4-wave form: one 8-wave
+# workgroup per CU cannot fill the chip with less.
+PAIRED = os.environ.get("GT_WGRAD_PAIRED", "1") != "0"
+PAIR_MIN_WGS = int(os.environ.get("GT_WGRAD_PAIR_MIN", "128"))
 
 # ASYNC (process-level dev knob GT_WGRAD_ASYNC=1, read once at import; off by default): flush() launches on a side stream, so the batched weight-gradient kernels of the
 # decoder overlap with whatever the backward does next (the rest of the data-gradient chain, the text encoder's
@@ -120,6 +127,18 @@ def choose_slabs(base_tiles, R, part_bytes):
         costs.append((cost, S))
         best = cost if best is None else min(best, cost)
     return min(S for cost, S in costs if cost <= 1.05 * best)
+
+
+def pair_grid(nco, nci):
+    """The nco x nci tile grid of one (job, slab) as paired workgroups [(co, ci, kind)], heavy first: same-co pairs (kind 0: tiles
+    (co, ci) and (co, ci + 1) share the dY rows) over the even part of every row; an odd last column goes to same-ci pairs (kind 1:
+    tiles (co, ci) and (co + 1, ci) share the X rows) and, if nco is odd too, one single (kind 0 whose second tile lies past Cin)."""
+    out = [(co, ci, 0) for co in range(nco) for ci in range(0, nci - 1, 2)]
+    if nci & 1:
+        out += [(co, nci - 1, 1) for co in range(0, nco - 1, 2)]
+        if nco & 1:
+            out.append((nco - 1, nci - 1, 0))
+    return out
 
 
 def single_slabs(R, Cin, Cout, taps):
@@ -361,41 +380,53 @@ class WgradQueue:
                 if self.site is not None:
                     object.__setattr__(self.site, "_wgrad_tables", cache)
         # tiles depend on shapes only
-        skey = tuple((t, tuple(x[2:] for x in tiles[t]), tuple(j[6:] for j in jobs)) for t in (5, 3, 1))
+        skey = tuple((t, tuple(x[2:] for x in tiles[t]), tuple(j[6:] for j in jobs)) for t in (5, 3, 1)) + (PAIRED, PAIR_MIN_WGS)
         if cache.get("skey") != skey:
-            tl, counts = [], []
+            tl, counts, pl, pcounts = [], [], [], []
             for taps in (5, 3, 1):
-                n = 0
                 order = sorted(range(len(tiles[taps])), key=lambda i: -tiles[taps][i][0])       # heavy tiles first
+                paired = PAIRED and taps != 1 and sum(len(pair_grid(x[2], x[3])) * x[4] for x in tiles[taps]) >= PAIR_MIN_WGS
                 # XCD-aware order: workgroup i of a launch lands on XCD i % 8 (each XCD has its own L2).  The nco x nci tiles of one
                 # (job, slab) read the same dY / X rows — nci tiles share every dY block, nco tiles every X block — so they are dealt
                 # to ONE XCD (consecutive slots of its queue); dealt round-robin, each of them pulled its own copy over the fabric
-                # (3x the bytes for the decoder's 384 x 192 convs).
+                # (3x the bytes for the decoder's 384 x 192 convs).  The paired workgroups of a (job, slab) are dealt the same way.
                 queues = [[] for _ in range(XCDS)]
                 for i in order:
                     _, jid, nco, nci, S = tiles[taps][i]
                     for sl in range(S):
                         q = min(queues, key=len)
-                        q += [(jid, co * 128, ci * CI_TILE[taps], sl) for co in range(nco) for ci in range(nci)]
+                        if paired:
+                            q += [(jid, co * 128, ci * CI_TILE[taps], sl, kind) for co, ci, kind in pair_grid(nco, nci)]
+                        else:
+                            q += [(jid, co * 128, ci * CI_TILE[taps], sl) for co in range(nco) for ci in range(nci)]
                 flat = [q[pos] for pos in range(max(map(len, queues), default=0)) for q in queues if pos < len(q)]
+                t = np.zeros(len(flat), dtype=PAIR if paired else TILE)
                 if flat:
-                    t = np.zeros(len(flat), dtype=TILE)
                     a = np.array(flat, dtype=np.int64)
                     t["job"], t["co0"], t["ci0"], t["slab"] = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
-                    tl.append(t)
-                    n = len(flat)
-                counts.append(n)
-            ta = np.concatenate(tl) if tl else np.zeros(1, dtype=TILE)
-            cache["skey"], cache["tiles"], cache["counts"] = skey, upload(ta), counts
+                    if paired:
+                        t["kind"] = a[:, 4]
+                    (pl if paired else tl).append(t)
+                counts.append(0 if paired else len(flat))
+                if taps != 1:
+                    pcounts.append(len(flat) if paired else 0)
+            # one table: the 4-wave tiles, then (256-byte aligned) the pairs
+            ta = (np.concatenate(tl) if tl else np.zeros(1, dtype=TILE)).view(np.uint8)
+            pair_off = (ta.size + 255) & ~255
+            if pl:
+                ta = np.concatenate([ta, np.zeros(pair_off - ta.size, dtype=np.uint8), np.concatenate(pl).view(np.uint8)])
+            cache["skey"], cache["tiles"], cache["counts"], cache["pcounts"], cache["pair_off"] = skey, upload(ta), counts, pcounts, pair_off
             cache["pkey"] = None
         pkey = (base, tuple(j[:4] for j in jobs), tuple(w[2:8] for w in wnbs), self.accumulate)
         if cache.get("pkey") != pkey:
             ja = np.array([(j[0], j[1], base + j[2], (base + j[3]) if j[3] >= 0 else 0) + j[4:] for j in jobs], dtype=JOB)
             wa = np.array([(base + w[0], base + w[1]) + w[2:] for w in wnbs], dtype=WNB)
             cache["pkey"], cache["jobs"], cache["wnb"] = pkey, upload(ja), upload(wa)
-        counts = cache["counts"]
+        counts, pcounts = cache["counts"], cache["pcounts"]
         st = _lib.current_stream(dev)
         assert all(call.gt_conv_wgrad_ci_tile(t) == w for t, w in CI_TILE.items()), "wgrad.CI_TILE does not match the library's tile widths"
+        if any(pcounts):
+            call.gt_conv_wgrad_paired(cache["jobs"], cache["tiles"][cache["pair_off"]:], pcounts[0], pcounts[1], st)
         call.gt_conv_wgrad_batched(cache["jobs"], cache["tiles"], counts[0], counts[1], counts[2], st)
         call.gt_weightnorm_bwd_batched(cache["wnb"], len(wnbs), rows, max_n, st)
         if capturing:

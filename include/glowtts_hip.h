@@ -246,6 +246,15 @@ int gt_conv_wgrad_batched(const void* jobs_device, const void* tiles_device, int
                           int n_tiles1, void* stream);
 int gt_weightnorm_bwd_batched(const void* jobs_device, int n_jobs, int total_rows, int max_row_elems, void* stream);
 
+/* Paired form of the batched weight gradient for taps 5 and 3: one 512-thread workgroup computes two 128 x 64 tiles of one (job, slab)
+ * from one staged copy of the operand rows they share.  Jobs are gt_wgrad_job as above; partials are bit-identical to
+ * gt_conv_wgrad_batched over the same tiles.
+ *   pair, kind 0: tiles (co0, ci0) and (co0, ci0 + 64) share the dY rows; with ci0 + 64 >= Cin it is the single tile (co0, ci0).
+ *   pair, kind 1: tiles (co0, ci0) and (co0 + 128, ci0) share the X rows; with co0 + 128 >= co_count it is the single tile (co0, ci0).
+ *   pairs are ordered taps 5, then 3; every tile of a job's grid must be covered exactly once. */
+typedef struct gt_wgrad_pair { int32_t job, co0, ci0, slab, kind, pad0_, pad1_, pad2_; } gt_wgrad_pair;
+int gt_conv_wgrad_paired(const void* jobs_device, const void* pairs_device, int n_pairs5, int n_pairs3, void* stream);
+
 /* out[n] += sum_m Y[m,n]  (bias gradients); Y bf16 (is_f32 == 0) or fp32 rows. */
 int gt_colsum(const void* Y, int ldy, int is_f32, float* out, int R, int N, void* stream);
 
