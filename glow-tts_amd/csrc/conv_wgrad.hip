@@ -35,17 +35,12 @@ __device__ __forceinline__ bf16x8_t tr_frag(const unsigned char* p0, const unsig
   return __builtin_bit_cast(bf16x8_t, v);
 }
 
-// LDS-DMA: 16 bytes per lane from `src` to LDS bytes [dst_base + 16 * lane, +16) — no VGPR destination, so the ring below costs no
-// registers; in inline asm because hipcc drains vmcnt(0) in front of every LDS read while a builtin glds is in flight.
-__device__ __forceinline__ void glds16(const void* src, unsigned dst_base) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-               "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst_base) : "memory");
-}
-// The same with a wave-uniform base and a 32-bit byte offset per lane: the paired form keeps each lane's offsets within a stage in
-// registers and moves the base from stage to stage with scalar arithmetic (no 64-bit vector address per load).  s_nop 4: the base may
-// come from a v_readfirstlane.
+// LDS-DMA: 16 bytes per lane from `base` + `off` bytes to LDS bytes [dst_base + 16 * lane, +16) — no VGPR destination, so the ring below
+// costs no registers; in inline asm because hipcc drains vmcnt(0) in front of every LDS read while a builtin glds is in flight.
+// A wave-uniform base and a 32-bit byte offset per lane: each lane's offsets within a stage stay in registers and the base moves from
+// stage to stage with scalar arithmetic (no 64-bit vector address per load; measured against that form in
+// `profiles/wgrad_pair_variants.txt` for the paired tile and `profiles/wgrad_share_bench.txt` for the 4-wave one).  s_nop 4: the base
+// may come from a v_readfirstlane.
 __device__ __forceinline__ void glds16s(const void* base, unsigned off, unsigned dst_base) {
   unsigned keep;
   asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
@@ -54,92 +49,133 @@ __device__ __forceinline__ void glds16s(const void* base, unsigned off, unsigned
 }
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
-// Geometry of one ring stage: KB rows of the dY tile (128 columns = 256 B per row) and KB + TAPS - 1 rows of the X tile (64 NJ columns =
-// 128 NJ B per row, NJ = 1 or 3), both DENSE — an LDS-DMA instruction writes 64 lanes x 16 B to consecutive LDS bytes, so rows shorter
-// than 1 KB cannot be padded.  Bank conflicts of the transposing reads (a 32-lane group reads 4 rows x 64 B in one LDS cycle if they fall
-// into four different 64-byte windows of the 256-byte bank period) are avoided by permuting the 16-byte chunks of a row on the SOURCE
-// side instead: LDS chunk c' of dY row r holds global chunk c' ^ 4 (r & 3) (rows alias every 256 B), LDS chunk c' of X row r holds global
-// chunk c' ^ 4 ((r >> 1) & 1) (rows of 128 B or 384 B alias every second row; rows r, r + 1 sit in different halves of the period anyway).
-template <int TAPS, int NJ, int KB_, int NST_> struct WgGeo {
-  static constexpr int KB = KB_, NST = NST_;
+// Geometry of one ring stage: KB rows of NY dY blocks (128 columns = 256 B per row and block) and KB + TAPS - 1 rows of the X tile (XCH
+// 16-byte chunks per row: 64 NJ columns, NJ = 1 or 3, or two 64-column blocks side by side), both DENSE — an LDS-DMA instruction writes
+// 64 lanes x 16 B to consecutive LDS bytes, so rows shorter than 1 KB cannot be padded.  Bank conflicts of the transposing reads (a
+// 32-lane group reads 4 rows x 64 B in one LDS cycle if they fall into four different 64-byte windows of the 256-byte bank period) are
+// avoided by permuting the 16-byte chunks of a row on the SOURCE side instead: LDS chunk c' of row r holds global chunk c' ^ 4 phase(r).
+// Rows of 256 B (dY; X with two blocks) alias every row: phase r & 3.  Rows of 128 B or 384 B alias every second row, and rows r, r + 1
+// sit in different halves of the period anyway: phase (r >> 1) & 1.
+// NW waves form NW / 4 groups, each the 2 x 2 of 64 co x 32 ci waves that owns one 128 co x 64 NJ ci tile: group g takes dY block g of
+// the stage if there are two, X block g if there are two.
+template <int TAPS_, int NJ_, int KB_, int NST_, int NW_, int NY_, int XCH_> struct WgGeo {
+  static constexpr int TAPS = TAPS_, NJ = NJ_, KB = KB_, NST = NST_, NW = NW_, NY = NY_, XCH = XCH_;
+  static constexpr int NT = 64 * NW;                 // threads
   static constexpr int XR = KB + TAPS - 1;
-  static constexpr int XCH = 8 * NJ;                 // 16-byte chunks per X row
-  static constexpr int YB = KB * 256, XB = XR * XCH * 16, STAGE = YB + XB;
-  static constexpr int YI = KB / 16;                 // dY LDS-DMA instructions per wave and stage (KB * 16 chunks over 256 lanes)
-  static constexpr int NWX = XR * XCH / 4;           // X chunks per wave and stage
-  static constexpr int XI = (NWX + 63) / 64;         // ... instructions (the last one partially masked)
+  static constexpr bool XSW4 = XCH * 16 == 256;      // X rows take dY's row phase
+  static constexpr int YB = NY * KB * 256, XB = XR * XCH * 16, STAGE = YB + XB;
+  static constexpr int YI = NY * KB * 16 / NT;       // dY LDS-DMA instructions per wave and stage
+  static constexpr int NWX = XR * XCH / NW;          // X chunks per wave and stage
+  static constexpr int XI = (NWX + 63) / 64;         // ... instructions (the last one partially masked; every wave has a lane in each)
   static constexpr int NLD = YI + XI;                // LDS-DMA instructions one wave has in flight per stage
   static constexpr int NB = TAPS * NJ;               // X fragments (= MFMA pairs) per k-step and wave
   static constexpr int LDS = NST * STAGE;
+  static constexpr int GA = NY == 2 ? KB * 256 : 0;                 // group g: byte offset of its dY block in the stage ...
+  static constexpr int GX = XCH == 16 * NJ ? 8 : 0;                 // ... chunk offset of its X block in a row
+  static constexpr int GCO = NY == 2 ? 128 : 0, GCI = GX * 8;       // ... and its tile's origin relative to (co0, ci0)
   static_assert(KB % 16 == 0 && SLAB_Q % KB == 0, "stage rows");
-  static_assert((XR * XCH) % 4 == 0, "X chunks split evenly over the waves");
-  static_assert(LDS <= 80 * 1024, "two workgroups per CU");
+  static_assert((NY * KB * 16) % NT == 0 && (XR * XCH) % NW == 0, "chunks split evenly over the waves");
+  static_assert(NWX > 64 * (XI - 1), "every wave issues all XI instructions");
+  static_assert(STAGE % 256 == 0 && YB % 256 == 0, "stages keep the bank phase");
+  static_assert(LDS <= (NW == 4 ? 80 : 160) * 1024, "two 4-wave workgroups or one 8-wave workgroup per CU");
   static_assert((NST - 2) * NLD <= 63, "vmcnt field");
   static_assert(TAPS == 1 || NJ == 1, "taps or channel groups");
+  static_assert(NW == 4 * NY * (GX ? 2 : 1) && XCH == 8 * NJ * (GX ? 2 : 1), "one group per tile");
+  static __device__ __forceinline__ int xphase(int r) { return XSW4 ? r & 3 : (r >> 1) & 1; }
 };
 
-// One workgroup: 128 output channels [co0, co0+128) of the dY view (Ncols columns wide; dY column c is output channel co_begin + c of a
-// conv with Cout channels) x 64 NJ input channels x all taps, rows of one slab.  Wave (wco, wci) owns 64 output channels x (32 input
-// channels of every 64-group) x all taps: per 16-row k-step 2 dY^T fragments + NB X fragments for 2 NB MFMAs.
+// One (job, tile, slab): the dY view is Ncols columns wide; dY column c is output channel co_begin + c of a conv with Cout channels.
+struct WgArgs {
+  const bf16_t* X; int ldx; const bf16_t* dY; int ldy;
+  float* part; float* part_bias; int R, Cin, Cout, slab_rows, co0, ci0, slab, co_begin, Ncols;
+};
+__device__ __forceinline__ WgArgs wg_args(const gt_wgrad_job& j, int co0, int ci0, int slab)
+{
+  return {static_cast<const bf16_t*>(j.X), j.ldx, static_cast<const bf16_t*>(j.dY), j.ldy, j.part, j.part_bias, j.R, j.Cin, j.Cout,
+          j.slab_rows, co0, ci0, slab, j.co_begin, j.co_count};
+}
+
+// column sums of dY ride along: VALU adds on a dY^T fragment
+__device__ __forceinline__ void bias_add(float& bsum, const bf16x8_t& a)
+{
+  const u32x4_t w4 = __builtin_bit_cast(u32x4_t, a);
+#pragma unroll
+  for (int d = 0; d < 4; ++d) bsum += __uint_as_float(w4[d] << 16) + __uint_as_float(w4[d] & 0xffff0000u);
+}
+
+// What every form of the tile does the same way: the stage filler, the ring's wait, the fragment reads and the stores.  Wave (wco, wci)
+// of a group owns 64 output channels x (32 input channels of every 64-group) x all taps: per 16-row k-step 2 dY^T fragments + NB X
+// fragments for 2 NB MFMAs.  The k-loops over these pieces are wgrad_tile and wgrad_pair_tile below.
 //
 // Round 3: the operands come through an NST-deep LDS ring filled by LDS-DMA.  The round-2 form (64-row stages staged through
 // registers, one stage ahead) took 2.0 us per stage whatever the tap count — 0.53 us of MFMA work at k = 5, 0.1 us at k = 1: one
 // HBM/L2 round trip per stage with nothing else in flight (serial profile of the step: 480 us for the decoder's k = 5 launch, 322 us
 // for its k = 1 launch).  Now NST - 1 stages are in flight per workgroup, none of them holds a register, with <= 256 registers two
-// workgroups share a CU, and the k = 1 tile spans 192 input channels (2 + 3 fragments for 6 MFMAs instead of 2 + 1 for 2).
-template <int TAPS, int NJ, int KB_, int NST_>
-__device__ __forceinline__ void wgrad_tile(
-    const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ dY, int ldy,
-    float* __restrict__ part, float* __restrict__ part_bias, int R, int Cin, int Cout, int slab_rows,
-    int co0, int ci0, int slab, int co_begin, int Ncols)
-{
-  using G = WgGeo<TAPS, NJ, KB_, NST_>;
-  constexpr int KB = G::KB, NST = G::NST, NB = G::NB;
-  extern __shared__ __attribute__((aligned(1024))) unsigned char ring[];       // [NST][STAGE]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  constexpr int padl = TAPS >> 1;
-  const int mbeg = slab * slab_rows;
-  const int mend = min(R, mbeg + slab_rows);
-  const int nst = (mend - mbeg + KB - 1) / KB;
-  const int wco = wave >> 1, wci = wave & 1;
-  const bool do_bias = (ci0 == 0) && part_bias && wci == 0;     // column sums of dY ride along (VALU adds on the A fragments)
-
-  f32x16_t acc[NB][2];
-  float bsum[2] = {0.f, 0.f};
-#pragma unroll
-  for (int t = 0; t < NB; ++t)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[t][j][e] = 0.0f;
-
-  // ---- what this lane fetches per stage (element offsets relative to the stage's first row; same chunk <-> lane map in both fill paths)
-  int yrow[G::YI], ycol[G::YI], xrow[G::XI], xcol[G::XI];
+// 4-wave workgroups share a CU, and the k = 1 tile spans 192 input channels (2 + 3 fragments for 6 MFMAs instead of 2 + 1 for 2).
+template <class G> struct WgTile {
+  static constexpr int KB = G::KB, NST = G::NST, TAPS = G::TAPS, NJ = G::NJ, NB = G::NB, padl = TAPS >> 1;
+  static constexpr int NOX = TAPS < 4 ? TAPS : 4;      // distinct row phases of the X swizzle over the taps
+  const WgArgs a;
+  unsigned char* const ring;                           // [NST][STAGE]
+  const int tid, lane, wave, grp, wco, wci;
+  const int gco0, gci0;                                // this group's tile
+  const int mbeg, mend, nst;
+  const int h;                                         // k half (rows 8h..8h+7 of a 16-row step)
+  int yrow[G::YI], xrow[G::XI];                        // this lane's chunks of a stage: rows relative to the stage's first dY row ...
+  unsigned yoff[G::YI], xoff[G::XI];                   // ... and byte offsets from the stage's first dY row / first X row (row mb - padl)
   bool xact[G::XI];
-#pragma unroll
-  for (int j = 0; j < G::YI; ++j) {
-    const int L = j * 256 + tid, r = L >> 4, c = (L & 15) ^ ((r & 3) << 2);
-    yrow[j] = r; ycol[j] = min(co0 + c * 8, Ncols - 8);          // columns past the view: a valid chunk whose products nobody stores
-  }
-#pragma unroll
-  for (int j = 0; j < G::XI; ++j) {
-    const int Lw = j * 64 + lane, L = wave * G::NWX + Lw, r = L / G::XCH, c = (L - r * G::XCH) ^ (((r >> 1) & 1) << 2);
-    xact[j] = Lw < G::NWX;
-    xrow[j] = r - padl; xcol[j] = min(ci0 + c * 8, Cin - 8);
-  }
-  const unsigned ring0 = lds_off(ring);
+  int offA[2], offX[NOX];
 
-  auto issue = [&](int s, int sl_i) {                          // stage s into ring slot sl_i (= s % NST, tracked by the caller)
+  __device__ __forceinline__ WgTile(const WgArgs& a_, unsigned char* ring_)
+      : a(a_), ring(ring_), tid(threadIdx.x), lane(tid & 63), wave(__builtin_amdgcn_readfirstlane(tid >> 6)),
+        grp(G::NW == 8 ? wave >> 2 : 0), wco((wave >> 1) & 1), wci(wave & 1),
+        gco0(a.co0 + grp * G::GCO), gci0(a.ci0 + grp * G::GCI),
+        mbeg(a.slab * a.slab_rows), mend(min(a.R, mbeg + a.slab_rows)), nst((mend - mbeg + KB - 1) / KB), h(lane >> 5)
+  {
+    // ---- what this lane fetches per stage (the same rows and offsets in both fill paths): chunk L of the stage's dY part is row (L >> 4) % KB of block L / (16 KB), chunk L of its X part is row L / XCH
+#pragma unroll
+    for (int j = 0; j < G::YI; ++j) {
+      const int L = j * G::NT + tid, r = (L >> 4) & (KB - 1), c = (L & 15) ^ ((r & 3) << 2);
+      const int col = min(a.co0 + (G::NY == 2 ? L / (16 * KB) * 128 : 0) + c * 8, a.Ncols - 8);   // columns past the view: a valid chunk whose products nobody stores
+      yrow[j] = r; yoff[j] = (unsigned)(r * a.ldy + col) * 2u;
+    }
+#pragma unroll
+    for (int j = 0; j < G::XI; ++j) {
+      const int Lw = j * 64 + lane, L = wave * G::NWX + Lw, r = L / G::XCH, c = (L - r * G::XCH) ^ (G::xphase(r) << 2);
+      xact[j] = Lw < G::NWX;
+      xrow[j] = r - padl; xoff[j] = (unsigned)(r * a.ldx + min(a.ci0 + c * 8, a.Cin - 8)) * 2u;
+    }
+    // ---- lane geometry of the transposing read (see cdna guide T10): within a 16-lane group lane
+    // 4q+p supplies the address of block row q, columns 4p..4p+3 and receives column (lane&15).
+    const int li = lane & 15, q = li >> 2, p = li & 3;
+    const int colhalf = ((lane >> 4) & 1) * 16;          // which 16 columns of the 32-wide MFMA block
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int ch = wco * 8 + i * 4 + (colhalf >> 3) + (p >> 1);
+      offA[i] = grp * G::GA + (8 * h + q) * 256 + ((ch ^ (q << 2)) << 4) + (p & 1) * 8;
+    }
+#pragma unroll
+    for (int t = 0; t < NOX; ++t) {
+      const int ch = grp * G::GX + wci * 4 + (colhalf >> 3) + (p >> 1);
+      offX[t] = (8 * h + q) * (G::XCH * 16) + ((ch ^ (G::xphase(q + t) << 2)) << 4) + (p & 1) * 8;
+    }
+  }
+
+  static __device__ __forceinline__ int next_slot(int sl) { return sl + 1 == NST ? 0 : sl + 1; }
+  __device__ __forceinline__ const unsigned char* stage(int sl) const { return ring + (size_t)sl * G::STAGE; }
+
+  __device__ __forceinline__ void issue(int s, int sl_i) const {        // stage s into ring slot sl_i (= s % NST, tracked by the caller)
     const int mb = mbeg + s * KB;
-    const unsigned slot = ring0 + (unsigned)sl_i * G::STAGE;
-    const bool edge = (mb - padl < 0) || (mb + KB + padl > R) || (mb + KB > mend);       // workgroup-uniform
+    const unsigned slot = lds_off(ring) + (unsigned)sl_i * G::STAGE;
+    const bool edge = (mb - padl < 0) || (mb + KB + padl > a.R) || (mb + KB > mend);       // workgroup-uniform
+    const unsigned char* ys = reinterpret_cast<const unsigned char*>(a.dY + (size_t)mb * a.ldy);
+    const unsigned char* xs = reinterpret_cast<const unsigned char*>(a.X + (ptrdiff_t)(mb - padl) * a.ldx);
     if (!edge) {
 #pragma unroll
-      for (int j = 0; j < G::YI; ++j)
-        glds16(dY + (size_t)(mb + yrow[j]) * ldy + ycol[j], slot + (unsigned)(j * 256 + wave * 64) * 16);
+      for (int j = 0; j < G::YI; ++j) glds16s(ys, yoff[j], slot + (unsigned)(j * G::NT + wave * 64) * 16);
 #pragma unroll
       for (int j = 0; j < G::XI; ++j)
-        if (xact[j]) glds16(X + (ptrdiff_t)(mb + xrow[j]) * ldx + xcol[j], slot + G::YB + (unsigned)(wave * G::NWX + j * 64) * 16);
+        if (xact[j]) glds16s(xs, xoff[j], slot + G::YB + (unsigned)(wave * G::NWX + j * 64) * 16);
     } else {
       // first stage of the tensor / last stage of a job: rows outside [0, R) and dY rows past the slab read as zero (plain loads; the
       // compiler's vmcnt(0) in front of the LDS writes also retires every LDS-DMA issued before)
@@ -148,118 +184,73 @@ __device__ __forceinline__ void wgrad_tile(
       for (int j = 0; j < G::YI; ++j) {
         const int m = mb + yrow[j];
         u32x4_t v = {0u, 0u, 0u, 0u};
-        if (m < mend) v = *reinterpret_cast<const u32x4_t*>(dY + (size_t)m * ldy + ycol[j]);
-        *reinterpret_cast<u32x4_t*>(sl + (size_t)(j * 256 + tid) * 16) = v;
+        if (m < mend) v = *reinterpret_cast<const u32x4_t*>(ys + yoff[j]);
+        *reinterpret_cast<u32x4_t*>(sl + (size_t)(j * G::NT + tid) * 16) = v;
       }
 #pragma unroll
       for (int j = 0; j < G::XI; ++j) {
         const int m = mb + xrow[j];
         u32x4_t v = {0u, 0u, 0u, 0u};
         if (xact[j]) {
-          if (m >= 0 && m < R) v = *reinterpret_cast<const u32x4_t*>(X + (size_t)m * ldx + xcol[j]);
+          if (m >= 0 && m < a.R) v = *reinterpret_cast<const u32x4_t*>(xs + xoff[j]);
           *reinterpret_cast<u32x4_t*>(sl + G::YB + (size_t)(wave * G::NWX + j * 64 + lane) * 16) = v;
         }
       }
     }
-  };
-
-  // lane geometry of the transposing read (see cdna guide T10): within a 16-lane group lane
-  // 4q+p supplies the address of block row q, columns 4p..4p+3 and receives column (lane&15).
-  const int li = lane & 15, q = li >> 2, p = li & 3;
-  const int colhalf = ((lane >> 4) & 1) * 16;          // which 16 columns of the 32-wide MFMA block
-  const int h = lane >> 5;                             // k half (rows 8h..8h+7 of a 16-row step)
-  constexpr int NOX = TAPS < 4 ? TAPS : 4;             // distinct row phases (q + t) & 3 of the X swizzle
-  int offA[2], offX[NOX];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int ch = wco * 8 + i * 4 + (colhalf >> 3) + (p >> 1);
-    offA[i] = (8 * h + q) * 256 + ((ch ^ (q << 2)) << 4) + (p & 1) * 8;
   }
-#pragma unroll
-  for (int t = 0; t < NOX; ++t) {
-    const int ch = wci * 4 + (colhalf >> 3) + (p >> 1);
-    offX[t] = (8 * h + q) * (G::XCH * 16) + ((ch ^ ((((q + t) >> 1) & 1) << 2)) << 4) + (p & 1) * 8;
+  __device__ __forceinline__ void prefill() const {
+#pragma unroll 1
+    for (int s = 0; s < NST - 1 && s < nst; ++s) issue(s, s);
+  }
+  // This wave's share of stage s has landed when at most (stages issued after s) x NLD of its LDS-DMAs are still in flight; behind the
+  // barrier everyone's share has and everyone has read the last fragment of stage s - 1, whose slot stage s + NST - 1 goes to.
+  __device__ __forceinline__ void wait_stage(int s) const {
+    const int after = min(nst - 1, s + NST - 2) - s;
+    if (after >= NST - 2) wait_vm<(NST - 2) * G::NLD>();
+    else wait_vm<0>();
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
 
-  bf16x8_t af[2], bfg[NB];
-  auto load_frags = [&](const unsigned char* yb, const unsigned char* xb, int ks) {
+  // fragments of k-step ks of the stage whose dY part is at yb and X part at xb: the wave's two dY^T fragments; its X fragment (t, j)
+  __device__ __forceinline__ void read_a(bf16x8_t (&af)[2], const unsigned char* yb, int ks) const {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const unsigned char* ya = yb + offA[i] + ks * 16 * 256;
       af[i] = tr_frag(ya, ya + 4 * 256);
     }
+  }
+  __device__ __forceinline__ bf16x8_t read_b(const unsigned char* xb, int ks, int t, int j) const {
+    const unsigned char* xa = xb + offX[t & 3] + (ks * 16 + t) * (G::XCH * 16) + j * 128;
+    return tr_frag(xa, xa + 4 * (G::XCH * 16));
+  }
+
+  // ---- slab partial: part[slab][tap][co][ci], lane = ci (128-byte rows per register)
+  __device__ __forceinline__ void store_part(const f32x16_t (&acc)[NB][2]) const {
+    const size_t row0 = (size_t)a.slab * TAPS * a.Cout + a.co_begin;           // of tap 0, column 0 of the view
 #pragma unroll
     for (int t = 0; t < TAPS; ++t)
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        const unsigned char* xa = xb + offX[t & 3] + (ks * 16 + t) * (G::XCH * 16) + j * 128;
-        bfg[t * NJ + j] = tr_frag(xa, xa + 4 * (G::XCH * 16));
+        const int ci = gci0 + j * 64 + wci * 32 + (lane & 31);
+        if (ci >= a.Cin) continue;
+        float* pt = a.part + (row0 + (size_t)t * a.Cout) * a.Cin + ci;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int co = gco0 + wco * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            if (co < a.Ncols) pt[(size_t)co * a.Cin] = acc[t * NJ + j][i][e];
+          }
       }
-  };
-  auto mfmas = [&]() {
-#pragma unroll
-    for (int t = 0; t < NB; ++t)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) acc[t][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfg[t], acc[t][i], 0, 0, 0);
-    if (do_bias) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const u32x4_t w4 = __builtin_bit_cast(u32x4_t, af[i]);
-#pragma unroll
-        for (int d = 0; d < 4; ++d) bsum[i] += __uint_as_float(w4[d] << 16) + __uint_as_float(w4[d] & 0xffff0000u);
-      }
-    }
-  };
-
-#pragma unroll 1
-  for (int s = 0; s < NST - 1 && s < nst; ++s) issue(s, s);
-  int cslot = 0, islot = NST - 1;                               // ring slots of the stage computed / the stage issued in this iteration
-#pragma unroll 1
-  for (int s = 0; s < nst; ++s) {
-    // this wave's share of stage s has landed when at most (stages issued after s) x NLD of its LDS-DMAs are still in flight
-    const int after = min(nst - 1, s + NST - 2) - s;
-    if (after >= NST - 2) wait_vm<(NST - 2) * G::NLD>();
-    else wait_vm<0>();
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // everyone's share has; everyone is done with stage s - 1
-    if (s + NST - 1 < nst) issue(s + NST - 1, islot);                     // ... whose slot the next stage goes to
-    const unsigned char* yb = ring + (size_t)cslot * G::STAGE;
-    const unsigned char* xb = yb + G::YB;
-    cslot = cslot + 1 == NST ? 0 : cslot + 1;
-    islot = islot + 1 == NST ? 0 : islot + 1;
-#pragma unroll
-    for (int ks = 0; ks < KB / 16; ++ks) {
-      load_frags(yb, xb, ks);                  // all 2 + NB fragment reads of the k-step go out back to back; the MFMAs start as they
-      __builtin_amdgcn_sched_barrier(0);       // arrive (counted lgkmcnt), the other workgroup of the CU computes meanwhile
-      mfmas();
-    }
   }
-
-  // ---- slab partial: part[slab][tap][co][ci], lane = ci (128-byte rows per register)
-  const int r = lane & 31;
-#pragma unroll
-  for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int ci = ci0 + j * 64 + wci * 32 + r;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if (ci >= Cin) continue;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int co = co0 + wco * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-          if (co < Ncols) part[(((size_t)slab * TAPS + t) * Cout + co_begin + co) * Cin + ci] = acc[t * NJ + j][i][e];
-        }
-      }
-    }
-  if (do_bias) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float tot = bsum[i] + __shfl_xor(bsum[i], 32);            // the two k halves of a column live 32 lanes apart
-      const int co = co0 + wco * 64 + i * 32 + r;
-      if (h == 0 && co < Ncols) part_bias[(size_t)slab * Cout + co_begin + co] = tot;
-    }
+  // ---- column sums of the wave's dY^T fragment i
+  __device__ __forceinline__ bool has_bias() const { return gci0 == 0 && a.part_bias; }
+  __device__ __forceinline__ void store_bias(float bsum, int i) const {
+    const float tot = bsum + __shfl_xor(bsum, 32);            // the two k halves of a column live 32 lanes apart
+    const int co = gco0 + wco * 64 + i * 32 + (lane & 31);
+    if (h == 0 && co < a.Ncols) a.part_bias[(size_t)a.slab * a.Cout + a.co_begin + co] = tot;
   }
-}
+};
 
 template <int TAPS> struct WgSel;
 // Per tap count: rows per ring stage (KB), ring depth (NST), input-channel groups of 64 per workgroup tile (NJ).
@@ -269,88 +260,78 @@ template <int TAPS> struct WgSel;
 template <> struct WgSel<5> { static constexpr int NJ = 1, KB = 64, NST = 3; };
 template <> struct WgSel<3> { static constexpr int NJ = 1, KB = 64, NST = 3; };
 template <> struct WgSel<1> { static constexpr int NJ = 3, KB = 32, NST = 3; };
-template <int TAPS> using WgGeoT = WgGeo<TAPS, WgSel<TAPS>::NJ, WgSel<TAPS>::KB, WgSel<TAPS>::NST>;
-
-template <int TAPS>
-__global__ __launch_bounds__(256, 2) void gt_conv_wgrad_kernel(
-    const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ dY, int ldy,
-    float* __restrict__ part, float* __restrict__ part_bias, int R, int Cin, int Cout, int slab_rows)
-{
-  using S = WgSel<TAPS>;
-  wgrad_tile<TAPS, S::NJ, S::KB, S::NST>(X, ldx, dY, ldy, part, part_bias, R, Cin, Cout, slab_rows,
-                                         blockIdx.x * 128, blockIdx.y * 64 * S::NJ, blockIdx.z, 0, Cout);
-}
-
-// Batched form: every workgroup reads its (job, tile) from device tables, so ONE launch per tap count
-// covers the weight gradients of a whole network (the jobs' X / dY rows stay resident until then).
-template <int TAPS>
-__global__ __launch_bounds__(256, 2) void gt_conv_wgrad_batched_kernel(
-    const gt_wgrad_job* __restrict__ jobs, const gt_wgrad_tile* __restrict__ tiles)
-{
-  using S = WgSel<TAPS>;
-  const gt_wgrad_tile t = tiles[blockIdx.x];
-  const gt_wgrad_job j = jobs[t.job];
-  wgrad_tile<TAPS, S::NJ, S::KB, S::NST>(static_cast<const bf16_t*>(j.X), j.ldx, static_cast<const bf16_t*>(j.dY), j.ldy,
-                                         j.part, j.part_bias, j.R, j.Cin, j.Cout, j.slab_rows, t.co0, t.ci0, t.slab, j.co_begin, j.co_count);
-}
-
-template <int TAPS> static int wgrad_lds_attr()
-{
-  // > 64 KiB of dynamic LDS needs the attribute once per kernel (outside graph capture: run one eager step first, INTEGRATION.md section 4)
-  if (gt_allow_lds<&gt_conv_wgrad_kernel<TAPS>>(WgGeoT<TAPS>::LDS) || gt_allow_lds<&gt_conv_wgrad_batched_kernel<TAPS>>(WgGeoT<TAPS>::LDS)) return GT_E_LAUNCH;
-  return 0;
-}
-
-// ---- paired form (TAPS = 5, 3): one 512-thread workgroup computes TWO 128 co x 64 ci tiles of one (job, slab) from one ring.
-// Wave group g = wave >> 2 is the 2 x 2 of 64 co x 32 ci waves of wgrad_tile and owns one of the tiles:
+// The 4-wave tile: one workgroup = 128 output channels [co0, co0 + 128) x 64 NJ input channels x all taps, rows of one slab.
+template <int TAPS> using WgGeo4 = WgGeo<TAPS, WgSel<TAPS>::NJ, WgSel<TAPS>::KB, WgSel<TAPS>::NST, 4, 1, 8 * WgSel<TAPS>::NJ>;
+// The paired tile (TAPS = 5, 3): one 512-thread workgroup computes TWO 128 co x 64 ci tiles of one (job, slab) from one ring.
 //   KIND 0, same-co pair: both groups read the one dY block [co0, co0 + 128); group g reads X columns [ci0 + 64 g, +64).  The X stage
-//           has 256-byte rows and takes dY's source-side swizzle (c ^ 4 (r & 3)).  A group whose columns start at or past Cin is
-//           dead (a SINGLE: the leftover tile of an odd x odd grid): it issues its share of the loads and executes every barrier,
-//           but reads no fragment, issues no MFMA and stores nothing.
-//   KIND 1, same-ci pair: both groups read the one X block [ci0, ci0 + 64) (wgrad_tile's layout); group g reads dY block
-//           [co0 + 128 g, +128), block g of the stage.
+//           has 256-byte rows.  A group whose columns start at or past Cin is dead (a SINGLE: the leftover tile of an odd x odd grid):
+//           it issues its share of the loads and executes every barrier, but reads no fragment, issues no MFMA and stores nothing.
+//   KIND 1, same-ci pair: both groups read the one X block [ci0, ci0 + 64); group g reads dY block [co0 + 128 g, +128).
 // The 4-wave form stages every dY block once per ci tile and every X block once per co tile; here a stage is 33 KB (KIND 0) or 40.5 KB
 // (KIND 1) for two tiles where two 4-wave workgroups staged 2 x 24.5 KB.  One workgroup per CU has the whole LDS: KIND 0 runs a
-// 4-deep ring (132 KB), KIND 1 a 3-deep one (121.5 KB; 4 stages would be 162 KB).  Each accumulator sees the fragments wgrad_tile
-// gives it, in the same ascending 16-row k-steps of the same 64-row stages: partials are bit-identical to the 4-wave form.
-template <int TAPS, int KIND> struct WgGeo8 {
-  static constexpr int KB = 64, NST = KIND ? 3 : 4;
-  static constexpr int NY = KIND ? 2 : 1;            // dY blocks of 128 columns per stage
-  static constexpr int XR = KB + TAPS - 1;
-  static constexpr int XCH = KIND ? 8 : 16;          // 16-byte chunks per X row
-  static constexpr int YB = NY * KB * 256, XB = XR * XCH * 16, STAGE = YB + XB;
-  static constexpr int YI = NY * KB * 16 / 512;      // dY LDS-DMA instructions per wave and stage
-  static constexpr int NWX = XR * XCH / 8;           // X chunks per wave and stage
-  static constexpr int XI = (NWX + 63) / 64;         // ... instructions (the last one partially masked; every wave has a lane in each)
-  static constexpr int NLD = YI + XI;
-  static constexpr int LDS = NST * STAGE;
-  static_assert((XR * XCH) % 8 == 0, "X chunks split evenly over the waves");
-  static_assert(NWX > 64 * (XI - 1), "every wave issues all XI instructions");
-  static_assert(STAGE % 256 == 0 && YB % 256 == 0, "stages keep the bank phase");
-  static_assert(LDS <= 160 * 1024, "one workgroup per CU");
-  static_assert((NST - 2) * NLD <= 63, "vmcnt field");
-};
+// 4-deep ring (132 KB), KIND 1 a 3-deep one (121.5 KB; 4 stages would be 162 KB).
+template <int TAPS, int KIND> using WgGeo8 = WgGeo<TAPS, 1, 64, KIND ? 3 : 4, 8, KIND ? 2 : 1, KIND ? 8 : 16>;
 
-template <int TAPS, int KIND>
-__device__ __forceinline__ void wgrad_pair_tile(
-    const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ dY, int ldy,
-    float* __restrict__ part, float* __restrict__ part_bias, int R, int Cin, int Cout, int slab_rows,
-    int co0, int ci0, int slab, int co_begin, int Ncols)
+// The 4-wave k-loop: all fragment reads of a k-step, then its MFMAs.  The wci = 0 waves sum the columns of both dY^T fragments.
+template <class G> __device__ __forceinline__ void wgrad_tile(const WgArgs& a)
 {
-  using G = WgGeo8<TAPS, KIND>;
-  constexpr int KB = G::KB, NST = G::NST, NB = TAPS;
-  extern __shared__ __attribute__((aligned(1024))) unsigned char ring[];       // [NST][STAGE]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  constexpr int padl = TAPS >> 1;
-  const int mbeg = slab * slab_rows;
-  const int mend = min(R, mbeg + slab_rows);
-  const int nst = (mend - mbeg + KB - 1) / KB;
-  const int grp = wave >> 2, wco = (wave >> 1) & 1, wci = wave & 1;
-  const int gco0 = co0 + (KIND ? grp * 128 : 0), gci0 = ci0 + (KIND ? 0 : grp * 64);      // this group's tile
-  const bool live = KIND ? gco0 < Ncols : gci0 < Cin;                                     // wave-uniform
+  constexpr int KB = G::KB, NST = G::NST, NB = G::NB;
+  extern __shared__ __attribute__((aligned(1024))) unsigned char ring[];
+  const WgTile<G> T(a, ring);
+  const bool do_bias = T.has_bias() && T.wci == 0;
+
+  f32x16_t acc[NB][2];
+  float bsum[2] = {0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < NB; ++t)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[t][j][e] = 0.0f;
+  bf16x8_t af[2], bfg[NB];
+
+  T.prefill();
+  int cslot = 0, islot = NST - 1;                               // ring slots of the stage computed / the stage issued in this iteration
+#pragma unroll 1
+  for (int s = 0; s < T.nst; ++s) {
+    T.wait_stage(s);
+    if (s + NST - 1 < T.nst) T.issue(s + NST - 1, islot);
+    const unsigned char* yb = T.stage(cslot);
+    const unsigned char* xb = yb + G::YB;
+    cslot = T.next_slot(cslot);
+    islot = T.next_slot(islot);
+#pragma unroll
+    for (int ks = 0; ks < KB / 16; ++ks) {
+      // all 2 + NB fragment reads of the k-step go out back to back; the MFMAs start as they arrive (counted lgkmcnt), the other
+      // workgroup of the CU computes meanwhile
+      T.read_a(af, yb, ks);
+#pragma unroll
+      for (int t = 0; t < G::TAPS; ++t)
+#pragma unroll
+        for (int j = 0; j < G::NJ; ++j) bfg[t * G::NJ + j] = T.read_b(xb, ks, t, j);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int t = 0; t < NB; ++t)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) acc[t][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfg[t], acc[t][i], 0, 0, 0);
+      if (do_bias) { bias_add(bsum[0], af[0]); bias_add(bsum[1], af[1]); }
+    }
+  }
+  T.store_part(acc);
+  if (do_bias) { T.store_bias(bsum[0], 0); T.store_bias(bsum[1], 1); }
+}
+
+// The paired k-loop.  Each accumulator sees the fragments wgrad_tile gives it, in the same ascending 16-row k-steps of the same 64-row
+// stages: partials are bit-identical to the 4-wave form.
+template <class G> __device__ __forceinline__ void wgrad_pair_tile(const WgArgs& a)
+{
+  constexpr int KB = G::KB, NST = G::NST, NB = G::NB;
+  extern __shared__ __attribute__((aligned(1024))) unsigned char ring[];
+  const WgTile<G> T(a, ring);
+  const bool live = G::NY == 2 ? T.gco0 < a.Ncols : T.gci0 < a.Cin;                       // wave-uniform
   // column sums of dY: wave (wco, wci) sums the columns of its dY^T fragment wci (wgrad_tile: the wci = 0 waves sum both fragments and
   // are the last at every barrier); the additions of a column and their order are the same
-  const bool do_bias = live && (gci0 == 0) && part_bias;
+  const bool do_bias = live && T.has_bias();
 
   f32x16_t acc[NB][2];
   float bsum = 0.f;
@@ -361,177 +342,84 @@ __device__ __forceinline__ void wgrad_pair_tile(
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[t][j][e] = 0.0f;
 
-  // ---- what this lane fetches per stage: chunk L of the stage's dY part is row (L >> 4) & 63 of block L >> 10; the X part as in wgrad_tile
-  int yrow[G::YI], ycol[G::YI], xrow[G::XI], xcol[G::XI];
-  bool xact[G::XI];
-#pragma unroll
-  for (int j = 0; j < G::YI; ++j) {
-    const int L = j * 512 + tid, r = (L >> 4) & 63, c = (L & 15) ^ ((r & 3) << 2);
-    yrow[j] = r; ycol[j] = min(co0 + (L >> 10) * 128 + c * 8, Ncols - 8);
-  }
-#pragma unroll
-  for (int j = 0; j < G::XI; ++j) {
-    const int Lw = j * 64 + lane, L = wave * G::NWX + Lw, r = L / G::XCH, cc = L - r * G::XCH;
-    const int c = KIND ? cc ^ (((r >> 1) & 1) << 2) : cc ^ ((r & 3) << 2);
-    xact[j] = Lw < G::NWX;
-    xrow[j] = r - padl; xcol[j] = min(ci0 + c * 8, Cin - 8);
-  }
-  const unsigned ring0 = lds_off(ring);
-  unsigned yoff[G::YI], xoff[G::XI];                  // byte offsets from the stage's first dY row / first X row (row mb - padl)
-#pragma unroll
-  for (int j = 0; j < G::YI; ++j) yoff[j] = (unsigned)(yrow[j] * ldy + ycol[j]) * 2u;
-#pragma unroll
-  for (int j = 0; j < G::XI; ++j) xoff[j] = (unsigned)((xrow[j] + padl) * ldx + xcol[j]) * 2u;
-
-  auto issue = [&](int s, int sl_i) {
-    const int mb = mbeg + s * KB;
-    const unsigned slot = ring0 + (unsigned)sl_i * G::STAGE;
-    const bool edge = (mb - padl < 0) || (mb + KB + padl > R) || (mb + KB > mend);       // workgroup-uniform
-    if (!edge) {
-      const bf16_t* ys = dY + (size_t)mb * ldy;
-      const bf16_t* xs = X + (size_t)(mb - padl) * ldx;
-#pragma unroll
-      for (int j = 0; j < G::YI; ++j) glds16s(ys, yoff[j], slot + (unsigned)(j * 512 + wave * 64) * 16);
-#pragma unroll
-      for (int j = 0; j < G::XI; ++j)
-        if (xact[j]) glds16s(xs, xoff[j], slot + G::YB + (unsigned)(wave * G::NWX + j * 64) * 16);
-    } else {
-      // as in wgrad_tile: plain loads, zero rows; the compiler's vmcnt(0) in front of the LDS writes retires every LDS-DMA before
-      unsigned char* sl = ring + (size_t)sl_i * G::STAGE;
-#pragma unroll
-      for (int j = 0; j < G::YI; ++j) {
-        const int m = mb + yrow[j];
-        u32x4_t v = {0u, 0u, 0u, 0u};
-        if (m < mend) v = *reinterpret_cast<const u32x4_t*>(dY + (size_t)m * ldy + ycol[j]);
-        *reinterpret_cast<u32x4_t*>(sl + (size_t)(j * 512 + tid) * 16) = v;
-      }
-#pragma unroll
-      for (int j = 0; j < G::XI; ++j) {
-        const int m = mb + xrow[j];
-        u32x4_t v = {0u, 0u, 0u, 0u};
-        if (xact[j]) {
-          if (m >= 0 && m < R) v = *reinterpret_cast<const u32x4_t*>(X + (size_t)m * ldx + xcol[j]);
-          *reinterpret_cast<u32x4_t*>(sl + G::YB + (size_t)(wave * G::NWX + j * 64 + lane) * 16) = v;
-        }
-      }
-    }
-  };
-
-  const int li = lane & 15, q = li >> 2, p = li & 3;
-  const int colhalf = ((lane >> 4) & 1) * 16;
-  const int h = lane >> 5;
-  constexpr int NOX = TAPS < 4 ? TAPS : 4;             // distinct row phases of the X swizzle
-  int offA[2], offX[NOX];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int ch = wco * 8 + i * 4 + (colhalf >> 3) + (p >> 1);
-    offA[i] = (KIND ? grp * KB * 256 : 0) + (8 * h + q) * 256 + ((ch ^ (q << 2)) << 4) + (p & 1) * 8;
-  }
-#pragma unroll
-  for (int t = 0; t < NOX; ++t) {
-    const int ch = (KIND ? 0 : grp * 8) + wci * 4 + (colhalf >> 3) + (p >> 1);
-    const int sw = KIND ? (((q + t) >> 1) & 1) << 2 : ((q + t) & 3) << 2;
-    offX[t] = (8 * h + q) * (G::XCH * 16) + ((ch ^ sw) << 4) + (p & 1) * 8;
-  }
-
   // Fragments one k-step ahead.  The two waves of a SIMD run this same program behind the same barrier, so with wgrad_tile's order
   // (all reads of a k-step, then its MFMAs) both wait for their reads together and the matrix pipe idles meanwhile.  Here the dY^T
   // fragments are double-buffered (8 registers) and each X fragment is re-read for the NEXT k-step right behind the two MFMAs that
   // consume it, so the reads of k-step i + 1 travel under the MFMAs of k-step i.  The step to the next stage (wait, barrier, issue)
   // sits in front of a stage's LAST k-step, whose fragments are in registers by then, so the prefetch runs across stages too.
   bf16x8_t af[2][2], bfg[NB];
-  auto read_a = [&](int buf, const unsigned char* yb, int ks) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const unsigned char* ya = yb + offA[i] + ks * 16 * 256;
-      af[buf][i] = tr_frag(ya, ya + 4 * 256);
-    }
-  };
-  auto read_b = [&](int t, const unsigned char* xb, int ks) {
-    const unsigned char* xa = xb + offX[t & 3] + (ks * 16 + t) * (G::XCH * 16);
-    bfg[t] = tr_frag(xa, xa + 4 * (G::XCH * 16));
-  };
-  // k-step ks on the fragments in registers; meanwhile fetch those of k-step ksn of the stage at (ybn, xbn)
-  auto kstep = [&](int ks, const unsigned char* ybn, const unsigned char* xbn, int ksn) {
+  // k-step ks on the fragments in registers; meanwhile fetch those of k-step ksn of the stage at ybn
+  auto kstep = [&](int ks, const unsigned char* ybn, int ksn) {
     const int cur = ks & 1;
-    read_a(cur ^ 1, ybn, ksn);
+    T.read_a(af[cur ^ 1], ybn, ksn);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < NB; ++t) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) acc[t][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][i], bfg[t], acc[t][i], 0, 0, 0);
-      read_b(t, xbn, ksn);
+      bfg[t] = T.read_b(ybn + G::YB, ksn, t, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (do_bias) {
-      const u32x4_t w4 = __builtin_bit_cast(u32x4_t, wci ? af[cur][1] : af[cur][0]);
-#pragma unroll
-      for (int d = 0; d < 4; ++d) bsum += __uint_as_float(w4[d] << 16) + __uint_as_float(w4[d] & 0xffff0000u);
-    }
+    if (do_bias) bias_add(bsum, T.wci ? af[cur][1] : af[cur][0]);
   };
 
-#pragma unroll 1
-  for (int s = 0; s < NST - 1 && s < nst; ++s) issue(s, s);
+  T.prefill();
   int cslot = 0, islot = NST - 1;
   int pend_s = -1, pend_slot = 0;                               // group 1: the stage to issue, deferred (below)
-  // Step to stage s: this wave's share of it has landed when at most (stages issued after s) x NLD of its LDS-DMAs are in flight; behind
-  // the barrier everyone's share has and everyone has read the last fragment of stage s - 1, whose slot stage s + NST - 1 goes to.
-  // Every wave, live or dead, runs this nst times: the wait counts, the barriers and the issues depend on s and nst alone.
+  // Step to stage s.  Every wave, live or dead, runs this nst times: the wait counts, the barriers and the issues depend on s and nst alone.
   // Group 0 issues its share right behind the barrier, group 1 three k-steps later (the slot stays free until the next barrier, and
   // the share is issued before this wave's next wait either way): issuing together, the two waves of a SIMD left its matrix pipe idle
   // (measured: 303 -> 293 us for the decoder's launch, `profiles/wgrad_pair_variants.txt`).
   auto advance = [&](int s) {
-    const int after = min(nst - 1, s + NST - 2) - s;
-    if (after >= NST - 2) wait_vm<(NST - 2) * G::NLD>();
-    else wait_vm<0>();
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (s + NST - 1 < nst) {
-      if (grp == 0) issue(s + NST - 1, islot);
+    T.wait_stage(s);
+    if (s + NST - 1 < T.nst) {
+      if (T.grp == 0) T.issue(s + NST - 1, islot);
       else { pend_s = s + NST - 1; pend_slot = islot; }
     }
-    islot = islot + 1 == NST ? 0 : islot + 1;
+    islot = T.next_slot(islot);
   };
   advance(0);
   const unsigned char* yb = ring;
   if (live) {
-    read_a(0, yb, 0);
+    T.read_a(af[0], yb, 0);
 #pragma unroll
-    for (int t = 0; t < NB; ++t) read_b(t, yb + G::YB, 0);
+    for (int t = 0; t < NB; ++t) bfg[t] = T.read_b(yb + G::YB, 0, t, 0);
   }
 #pragma unroll 1
-  for (int s = 0; s < nst; ++s) {
+  for (int s = 0; s < T.nst; ++s) {
     if (live) {
 #pragma unroll
-      for (int ks = 0; ks < KB / 16 - 1; ++ks) kstep(ks, yb, yb + G::YB, ks + 1);
+      for (int ks = 0; ks < KB / 16 - 1; ++ks) kstep(ks, yb, ks + 1);
     }
-    if (pend_s >= 0) { issue(pend_s, pend_slot); pend_s = -1; }
-    if (s + 1 < nst) advance(s + 1);
-    cslot = cslot + 1 == NST ? 0 : cslot + 1;
-    yb = ring + (size_t)cslot * G::STAGE;
+    if (pend_s >= 0) { T.issue(pend_s, pend_slot); pend_s = -1; }
+    if (s + 1 < T.nst) advance(s + 1);
+    cslot = T.next_slot(cslot);
+    yb = T.stage(cslot);
     // (behind the job's last stage this fetches fragments nobody uses, from a ring slot no LDS-DMA is in flight to)
-    if (live) kstep(KB / 16 - 1, yb, yb + G::YB, 0);
+    if (live) kstep(KB / 16 - 1, yb, 0);
   }
   if (!live) return;                                   // (past the last barrier)
+  T.store_part(acc);
+  if (do_bias) T.store_bias(bsum, T.wci);
+}
 
-  const int r = lane & 31;
-#pragma unroll
-  for (int t = 0; t < TAPS; ++t) {
-    const int ci = gci0 + wci * 32 + r;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (ci >= Cin) continue;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int co = gco0 + wco * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (co < Ncols) part[(((size_t)slab * TAPS + t) * Cout + co_begin + co) * Cin + ci] = acc[t][i][e];
-      }
-    }
-  }
-  if (do_bias) {
-    const float tot = bsum + __shfl_xor(bsum, 32);
-    const int co = gco0 + wco * 64 + wci * 32 + r;
-    if (h == 0 && co < Ncols) part_bias[(size_t)slab * Cout + co_begin + co] = tot;
-  }
+template <int TAPS>
+__global__ __launch_bounds__(256, 2) void gt_conv_wgrad_kernel(
+    const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ dY, int ldy,
+    float* __restrict__ part, float* __restrict__ part_bias, int R, int Cin, int Cout, int slab_rows)
+{
+  wgrad_tile<WgGeo4<TAPS>>({X, ldx, dY, ldy, part, part_bias, R, Cin, Cout, slab_rows,
+                            (int)blockIdx.x * 128, (int)blockIdx.y * 64 * WgSel<TAPS>::NJ, (int)blockIdx.z, 0, Cout});
+}
+
+// Batched form: every workgroup reads its (job, tile) from device tables, so ONE launch per tap count
+// covers the weight gradients of a whole network (the jobs' X / dY rows stay resident until then).
+template <int TAPS>
+__global__ __launch_bounds__(256, 2) void gt_conv_wgrad_batched_kernel(
+    const gt_wgrad_job* __restrict__ jobs, const gt_wgrad_tile* __restrict__ tiles)
+{
+  const gt_wgrad_tile t = tiles[blockIdx.x];
+  wgrad_tile<WgGeo4<TAPS>>(wg_args(jobs[t.job], t.co0, t.ci0, t.slab));
 }
 
 template <int TAPS>
@@ -539,12 +427,17 @@ __global__ __launch_bounds__(512, 1) void gt_conv_wgrad_paired_kernel(
     const gt_wgrad_job* __restrict__ jobs, const gt_wgrad_pair* __restrict__ pairs)
 {
   const gt_wgrad_pair t = pairs[blockIdx.x];
-  const gt_wgrad_job j = jobs[t.job];
-  const bf16_t* x = static_cast<const bf16_t*>(j.X); const bf16_t* dy = static_cast<const bf16_t*>(j.dY);
-  if (t.kind == 0) wgrad_pair_tile<TAPS, 0>(x, j.ldx, dy, j.ldy, j.part, j.part_bias, j.R, j.Cin, j.Cout, j.slab_rows, t.co0, t.ci0, t.slab, j.co_begin, j.co_count);
-  else             wgrad_pair_tile<TAPS, 1>(x, j.ldx, dy, j.ldy, j.part, j.part_bias, j.R, j.Cin, j.Cout, j.slab_rows, t.co0, t.ci0, t.slab, j.co_begin, j.co_count);
+  const WgArgs a = wg_args(jobs[t.job], t.co0, t.ci0, t.slab);
+  if (t.kind == 0) wgrad_pair_tile<WgGeo8<TAPS, 0>>(a);
+  else             wgrad_pair_tile<WgGeo8<TAPS, 1>>(a);
 }
 
+template <int TAPS> static int wgrad_lds_attr()
+{
+  // > 64 KiB of dynamic LDS needs the attribute once per kernel (outside graph capture: run one eager step first, INTEGRATION.md section 4)
+  if (gt_allow_lds<&gt_conv_wgrad_kernel<TAPS>>(WgGeo4<TAPS>::LDS) || gt_allow_lds<&gt_conv_wgrad_batched_kernel<TAPS>>(WgGeo4<TAPS>::LDS)) return GT_E_LAUNCH;
+  return 0;
+}
 template <int TAPS> constexpr int wgrad_pair_lds() { return WgGeo8<TAPS, 0>::LDS > WgGeo8<TAPS, 1>::LDS ? WgGeo8<TAPS, 0>::LDS : WgGeo8<TAPS, 1>::LDS; }
 
 // Sum the S slab partials and map to the parameter gradient(s).  One WAVE per output channel co (4 per workgroup):
@@ -904,9 +797,9 @@ extern "C" int gt_conv_wgrad_bf16(const void* X, int ldx, const void* dY, int ld
   float* part = static_cast<float*>(workspace);
   float* pb = part + (size_t)S * taps * Cout * Cin;
   if (wgrad_lds_attr<5>() || wgrad_lds_attr<3>() || wgrad_lds_attr<1>()) return GT_E_LAUNCH;
-  if (taps == 5)      hipLaunchKernelGGL(gt_conv_wgrad_kernel<5>, grid, dim3(256), WgGeoT<5>::LDS, st, x, ldx, dy, ldy, part, pb, R, Cin, Cout, slab_rows);
-  else if (taps == 3) hipLaunchKernelGGL(gt_conv_wgrad_kernel<3>, grid, dim3(256), WgGeoT<3>::LDS, st, x, ldx, dy, ldy, part, pb, R, Cin, Cout, slab_rows);
-  else                hipLaunchKernelGGL(gt_conv_wgrad_kernel<1>, grid, dim3(256), WgGeoT<1>::LDS, st, x, ldx, dy, ldy, part, pb, R, Cin, Cout, slab_rows);
+  if (taps == 5)      hipLaunchKernelGGL(gt_conv_wgrad_kernel<5>, grid, dim3(256), WgGeo4<5>::LDS, st, x, ldx, dy, ldy, part, pb, R, Cin, Cout, slab_rows);
+  else if (taps == 3) hipLaunchKernelGGL(gt_conv_wgrad_kernel<3>, grid, dim3(256), WgGeo4<3>::LDS, st, x, ldx, dy, ldy, part, pb, R, Cin, Cout, slab_rows);
+  else                hipLaunchKernelGGL(gt_conv_wgrad_kernel<1>, grid, dim3(256), WgGeo4<1>::LDS, st, x, ldx, dy, ldy, part, pb, R, Cin, Cout, slab_rows);
   return gt_launch_status(__func__);
 }
 
@@ -934,9 +827,9 @@ extern "C" int gt_conv_wgrad_batched(const void* jobs_device, const void* tiles_
   const gt_wgrad_job* jobs = static_cast<const gt_wgrad_job*>(jobs_device);
   const gt_wgrad_tile* tiles = static_cast<const gt_wgrad_tile*>(tiles_device);
   if (wgrad_lds_attr<5>() || wgrad_lds_attr<3>() || wgrad_lds_attr<1>()) return GT_E_LAUNCH;
-  if (n_tiles5) hipLaunchKernelGGL(gt_conv_wgrad_batched_kernel<5>, dim3(n_tiles5), dim3(256), WgGeoT<5>::LDS, st, jobs, tiles);
-  if (n_tiles3) hipLaunchKernelGGL(gt_conv_wgrad_batched_kernel<3>, dim3(n_tiles3), dim3(256), WgGeoT<3>::LDS, st, jobs, tiles + n_tiles5);
-  if (n_tiles1) hipLaunchKernelGGL(gt_conv_wgrad_batched_kernel<1>, dim3(n_tiles1), dim3(256), WgGeoT<1>::LDS, st, jobs, tiles + n_tiles5 + n_tiles3);
+  if (n_tiles5) hipLaunchKernelGGL(gt_conv_wgrad_batched_kernel<5>, dim3(n_tiles5), dim3(256), WgGeo4<5>::LDS, st, jobs, tiles);
+  if (n_tiles3) hipLaunchKernelGGL(gt_conv_wgrad_batched_kernel<3>, dim3(n_tiles3), dim3(256), WgGeo4<3>::LDS, st, jobs, tiles + n_tiles5);
+  if (n_tiles1) hipLaunchKernelGGL(gt_conv_wgrad_batched_kernel<1>, dim3(n_tiles1), dim3(256), WgGeo4<1>::LDS, st, jobs, tiles + n_tiles5 + n_tiles3);
   return gt_launch_status(__func__);
 }
 

@@ -79,3 +79,36 @@ def test_wgrad_single_and_batched_vs_float64(built, Cin, Cout, k, wn):
     finally:
         for p in params:
             del p._gt_flat_grad
+
+
+# the k = 1 shapes of CASES on fewer rows than the k = 1 ring holds (32-row stages, 3 deep): less than a stage, exactly one, two and a
+# ragged third
+SHORT_K1 = [c for c in CASES if c[2] == 1]
+SHORT_R = [20, 32, 70]
+
+
+@pytest.mark.parametrize("R", SHORT_R)
+@pytest.mark.parametrize("Cin,Cout,k,wn", SHORT_K1)
+def test_wgrad_k1_short_jobs_vs_float64(built, Cin, Cout, k, wn, R):
+    """The k = 1 tile (3 channel groups, 32-row stages, 3-deep ring) on jobs shorter than its ring, through the single-conv form and
+    through a WgradQueue, under the rule at one slab.  The queue plans one slab for each R, so 20 and 32 rows are one zero-filled stage
+    and 70 rows two stages and a ragged third that is; the single-conv entry plans by ceil(R / 64) and cuts 70 rows into 64 + 6, which
+    the one-slab bound (71 terms a sum, not 72) covers with room."""
+    from glow_tts_amd import flow_impl, wgrad
+    from glow_tts_amd.modules import ConvP, WNConvP
+    torch.manual_seed(Cin + 3 * Cout + R)
+    conv = (WNConvP if wn else ConvP)(Cin, Cout, k).to(dev())
+    conv.prepare()
+    g = torch.Generator().manual_seed(R + Cin)
+    x = torch.randn(R, Cin, generator=g).to(dev()).to(torch.bfloat16)
+    dy = torch.randn(R, Cout, generator=g).to(dev()).to(torch.bfloat16)
+    tag = f"wgrad k=1 {Cin}->{Cout} {'wn' if wn else 'plain'} R={R}"
+    assert wgrad.single_slabs(R, Cin, Cout, k) == (1 if R <= 64 else 2)
+    g1 = flow_impl.conv_param_grads(conv, x, dy, R)
+    torch.cuda.synchronize()
+    rows64.check_conv_param_grads(f"{tag} single", conv, g1, x, dy, 1)
+    with wgrad.WgradQueue(dev()) as q:
+        g2 = flow_impl.conv_param_grads(conv, x, dy, R)
+        assert q.slab_plan() == [(1, (R + 63) // 64 * 64)], q.slab_plan()
+    torch.cuda.synchronize()
+    rows64.check_conv_param_grads(f"{tag} batched", conv, g2, x, dy, 1)
