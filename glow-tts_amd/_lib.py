@@ -115,6 +115,9 @@ PROTOTYPES = {
     "gt_mle_finish": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gt_duration_loss_fwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "gt_duration_loss_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gt_align_loss_fwd": (STATUS, [c_void_p] * 11 + [c_int, c_int, c_int, c_int, c_void_p]),
+    "gt_align_loss_finish": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gt_align_loss_bwd": (STATUS, [c_void_p] * 14 + [c_int, c_int, c_int, c_int, c_void_p]),
     "gt_prior_expand_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "gt_mle_sums": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gt_mle_bwd": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),

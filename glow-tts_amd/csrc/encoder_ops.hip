@@ -912,6 +912,195 @@ __global__ void gt_duration_loss_bwd_kernel(const float* __restrict__ logw, cons
   }
 }
 
+// ------------------------------------------------------------------ alignment -> loss chain in three launches
+// Everything between MAS and the decoder's backward is elementwise, a gather or a segmented sum over the same [B, C, T_y] index
+// space; as launches of their own (prior_expand, mle_sums, mle_finish, sum, add, mle_bwd, prior_expand_bwd, duration loss and its
+// backward) each paid its in-graph launch cost on a stretch where both streams are joined.  The arithmetic below is the unfused
+// kernels' own, expression for expression and in their summation order: every output is bit-identical to theirs.
+//
+// Forward.  Workgroups 0 .. GT_MLE_PARTS-1: gt_mle_sums_kernel's index map (float4 i of the flat space -> thread i mod
+// (GT_MLE_PARTS * 256)) with m (and logs) gathered through frame2token and stored as z_m (z_logs) on the way.  T_y % 4 == 0: a
+// float4 never straddles two rows.  Workgroups GT_MLE_PARTS .. GT_MLE_PARTS+B-1 (logw given): gt_duration_loss_fwd_kernel in wave 0.
+__global__ __launch_bounds__(256) void gt_align_loss_fwd_kernel(const float* __restrict__ z, const float* __restrict__ xm,
+                                                                const float* __restrict__ xlogs, const int32_t* __restrict__ f2t,
+                                                                const float* __restrict__ logw, const float* __restrict__ w,
+                                                                const int32_t* __restrict__ len, float* __restrict__ zm,
+                                                                float* __restrict__ zlogs, float* __restrict__ acc,
+                                                                float* __restrict__ l_length, int B, int C, int Tx, int Ty)
+{
+  if (blockIdx.x >= GT_MLE_PARTS) {
+    const int b = blockIdx.x - GT_MLE_PARTS, lane = threadIdx.x;
+    if (lane >= 64) return;
+    float tot = 0.f;
+    for (int i = lane; i < B; i += 64) tot += (float)len[i];
+    tot = wave_sum(tot);
+    float a = 0.f;
+    const int n = len[b];
+    for (int t = lane; t < Tx; t += 64) {
+      const float lw = logw[(size_t)b * Tx + t];
+      const float ref = t < n ? __logf(w[(size_t)b * Tx + t] + 1e-8f) : 0.f;
+      const float d = lw - ref;
+      a += d * d;
+    }
+    a = wave_sum(a);
+    if (lane == 0) l_length[b] = a / tot;
+    return;
+  }
+  __shared__ float red[2][4];
+  float a0 = 0.f, a1 = 0.f;
+  const unsigned ty4 = (unsigned)Ty >> 2;
+  const unsigned n4 = (unsigned)B * C * ty4;                   // B * C * T_y < 2^31 (the entry refuses more)
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n4; i += GT_MLE_PARTS * 256) {
+    const unsigned bc = i / ty4, j4 = i - bc * ty4, b = bc / C;
+    const int4 t = reinterpret_cast<const int4*>(f2t)[(size_t)b * ty4 + j4];
+    const bool v0 = (unsigned)t.x < (unsigned)Tx, v1 = (unsigned)t.y < (unsigned)Tx, v2 = (unsigned)t.z < (unsigned)Tx,
+               v3 = (unsigned)t.w < (unsigned)Tx;                // -1 = padded frame
+    const float* xr = xm + (size_t)bc * Tx;
+    const float4 zz = reinterpret_cast<const float4*>(z)[i];
+    const float4 mm = make_float4(v0 ? xr[t.x] : 0.f, v1 ? xr[t.y] : 0.f, v2 ? xr[t.z] : 0.f, v3 ? xr[t.w] : 0.f);
+    float4 ll = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (xlogs) {
+      const float* sr = xlogs + (size_t)bc * Tx;
+      ll = make_float4(v0 ? sr[t.x] : 0.f, v1 ? sr[t.y] : 0.f, v2 ? sr[t.z] : 0.f, v3 ? sr[t.w] : 0.f);
+      reinterpret_cast<float4*>(zlogs)[i] = ll;
+    }
+    reinterpret_cast<float4*>(zm)[i] = mm;
+    const float d0 = zz.x - mm.x, d1 = zz.y - mm.y, d2 = zz.z - mm.z, d3 = zz.w - mm.w;
+    a0 += ll.x + ll.y + ll.z + ll.w;
+    a1 += __expf(-2.0f * ll.x) * d0 * d0 + __expf(-2.0f * ll.y) * d1 * d1 + __expf(-2.0f * ll.z) * d2 * d2 + __expf(-2.0f * ll.w) * d3 * d3;
+  }
+  a0 = wave_sum(a0); a1 = wave_sum(a1);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a0; red[1][threadIdx.x >> 6] = a1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    acc[2 * blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    acc[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  }
+}
+
+// The scalars.  out[0], out[1]: gt_mle_finish_kernel's body.  out[2] = sum_b l_length[b] in the order ATen's sum gives a short
+// contiguous fp32 vector (B < 128): lane t < nt = the largest power of two <= min(B, 64) adds l_length[t], l_length[t + nt], ...,
+// then a shuffle-down tree over the nt lanes — so that the total equals mle + torch.sum(l_length) bit for bit.  out[3] = out[0] + out[2].
+__global__ __launch_bounds__(1024) void gt_align_loss_finish_kernel(const float* __restrict__ acc, const float* __restrict__ logdet,
+                                                                    const float* __restrict__ mask, int n_mask,
+                                                                    const float* __restrict__ l_length, int B, int C, float* __restrict__ out)
+{
+  __shared__ float red[2][16];
+  __shared__ float red2[2];
+  {
+    float p0 = 0.f, p1 = 0.f;
+    for (int i = threadIdx.x; i < GT_MLE_PARTS; i += 1024) { const float2 v = reinterpret_cast<const float2*>(acc)[i]; p0 += v.x; p1 += v.y; }
+    p0 = wave_sum(p0); p1 = wave_sum(p1);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = p0; red[1][threadIdx.x >> 6] = p1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      p0 = 0.f; p1 = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { p0 += red[0][i]; p1 += red[1][i]; }
+      red2[0] = p0; red2[1] = p1;
+    }
+    __syncthreads();
+  }
+  float sl = 0.f, sn = 0.f;
+  for (int b = threadIdx.x; b < B; b += 1024) sl += logdet[b];
+  const int n4 = ((reinterpret_cast<uintptr_t>(mask) & 15) == 0) ? n_mask >> 2 : 0;
+  for (int i = threadIdx.x; i < n4; i += 1024) { const float4 v = reinterpret_cast<const float4*>(mask)[i]; sn += (v.x + v.y) + (v.z + v.w); }
+  for (int i = (n4 << 2) + threadIdx.x; i < n_mask; i += 1024) sn += mask[i];
+  sl = wave_sum(sl); sn = wave_sum(sn);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sl; red[1][threadIdx.x >> 6] = sn; }
+  float ll = 0.f;
+  if (l_length && threadIdx.x < 64) {                          // wave 0 (wave-uniform branch)
+    int nt = 1;
+    while (nt * 2 <= B && nt < 64) nt <<= 1;
+    if ((int)threadIdx.x < nt)
+      for (int i = threadIdx.x; i < B; i += nt) ll += l_length[i];
+    for (int off = 1; off < nt; off <<= 1) ll += __shfl_down(ll, off);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    sl = 0.f; sn = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { sl += red[0][i]; sn += red[1][i]; }
+    const float denom = sn * (float)C;
+    const float mle = (red2[0] + 0.5f * red2[1] - sl) / denom + 0.91893853320467274f;
+    out[0] = mle;
+    out[1] = denom;
+    out[2] = ll;
+    out[3] = mle + ll;
+  }
+}
+
+// Backward.  gt_prior_expand_bwd_kernel's geometry — one wave per (b, c) row, 64 frames at a time, segmented wave scan, fixed-order
+// LDS token accumulators — with gt_mle_bwd_kernel's v = g e d formed in the wave (g = *gscale / *gdenom): dz = v is stored, -v goes
+// into the scan (what dm was), and with logs g (1 - e d^2) goes into a second accumulator strip (what dlogs was).  Past the row
+// workgroups: one sets dlogdet[b] = -g, B more do gt_duration_loss_bwd_kernel's work in wave 0 with g[b] = *gscale.
+template <bool LOGS>
+__global__ __launch_bounds__(256) void gt_align_loss_bwd_kernel(const float* __restrict__ z, const float* __restrict__ zm,
+                                                                const float* __restrict__ zlogs, const int32_t* __restrict__ f2t,
+                                                                const float* __restrict__ logw, const float* __restrict__ w,
+                                                                const int32_t* __restrict__ len, const float* __restrict__ gscale,
+                                                                const float* __restrict__ gdenom, float* __restrict__ dz,
+                                                                float* __restrict__ dxm, float* __restrict__ dxlogs,
+                                                                float* __restrict__ dlogdet, float* __restrict__ dlogw,
+                                                                int B, int C, int Tx, int Ty, int row_blocks)
+{
+  __shared__ float acc[LOGS ? 2 : 1][4][512];
+  if ((int)blockIdx.x >= row_blocks) {
+    const int e = blockIdx.x - row_blocks;
+    if (e == 0) {
+      const float g = *gscale / *gdenom;
+      for (int b = threadIdx.x; b < B; b += 256) dlogdet[b] = -g;
+      return;
+    }
+    const int b = e - 1, lane = threadIdx.x;
+    if (lane >= 64) return;
+    float tot = 0.f;
+    for (int i = lane; i < B; i += 64) tot += (float)len[i];
+    tot = wave_sum(tot);
+    const int n = len[b];
+    const float gb = 2.0f * *gscale / tot;
+    for (int t = lane; t < Tx; t += 64) {
+      const float lw = logw[(size_t)b * Tx + t];
+      const float ref = t < n ? __logf(w[(size_t)b * Tx + t] + 1e-8f) : 0.f;
+      dlogw[(size_t)b * Tx + t] = gb * (lw - ref);
+    }
+    return;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int bc = blockIdx.x * 4 + wave;
+  if (bc >= B * C) return;                                  // waves are independent: no workgroup barrier below
+  const int b = bc / C;
+  const float g = *gscale / *gdenom;
+  float* am = acc[0][wave];
+  float* as = acc[LOGS ? 1 : 0][wave];
+  for (int i = lane; i < Tx; i += 64) { am[i] = 0.f; if (LOGS) as[i] = 0.f; }
+  for (int j0 = 0; j0 < Ty; j0 += 64) {
+    const int j = j0 + lane;
+    int t = -1; float vm = 0.f, vs = 0.f;
+    if (j < Ty) {
+      const size_t i = (size_t)bc * Ty + j;
+      t = f2t[(size_t)b * Ty + j];
+      const float l = LOGS ? zlogs[i] : 0.f, e = __expf(-2.0f * l), d = z[i] - zm[i];
+      const float v = g * e * d;
+      dz[i] = v;
+      vm = -v;
+      if (LOGS) vs = g * (1.0f - e * d * d);
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float um = __shfl_up(vm, off), us = LOGS ? __shfl_up(vs, off) : 0.f;
+      const int tt = __shfl_up(t, off);
+      if (lane >= off && tt == t) { vm += um; if (LOGS) vs += us; }
+    }
+    const int tn = __shfl_down(t, 1);
+    if (t >= 0 && t < Tx && (lane == 63 || tn != t)) { am[t] += vm; if (LOGS) as[t] += vs; }   // a run that crosses the chunk boundary continues in the next chunk
+  }
+  for (int i = lane; i < Tx; i += 64) {
+    dxm[(size_t)bc * Tx + i] = am[i];
+    if (LOGS) dxlogs[(size_t)bc * Tx + i] = as[i];
+  }
+}
+
 }  // namespace
 
 #define GT_ST(s) static_cast<hipStream_t>(s)
@@ -1307,6 +1496,49 @@ extern "C" int gt_duration_loss_bwd(const float* logw, const float* w, const int
 {
   if (!logw || !w || !x_lengths || !g || !dlogw || B <= 0 || Tx <= 0) return GT_E_INVAL;
   hipLaunchKernelGGL(gt_duration_loss_bwd_kernel, dim3(B), dim3(64), 0, GT_ST(stream), logw, w, x_lengths, g, B, Tx, dlogw);
+  GT_RET();
+}
+extern "C" int gt_align_loss_fwd(const float* z, const float* x_m, const float* x_logs, const int32_t* frame2token, const float* logw,
+                                 const float* w, const int32_t* x_lengths, float* z_m, float* z_logs, float* acc2, float* l_length,
+                                 int B, int C, int Tx, int Ty, void* stream)
+{
+  if (!z || !x_m || !frame2token || !z_m || !acc2 || (x_logs && !z_logs) || B <= 0 || C <= 0 || Tx <= 0 || Ty <= 0) return GT_E_INVAL;
+  if ((logw != nullptr) != (w != nullptr) || (logw && (!x_lengths || !l_length))) return GT_E_INVAL;
+  if (Tx > 512) return GT_E_UNSUPPORTED;                      // gt_align_loss_bwd's token accumulators end there: the unfused entries go on
+  if ((size_t)B * C * Ty > 0x7fffffffu) return GT_E_UNSUPPORTED;
+  if (Ty & 3) return GT_E_ALIGN;                              // a float4 of the flat index space must not straddle two rows
+  if (((uintptr_t)z | (uintptr_t)z_m | (uintptr_t)z_logs | (uintptr_t)frame2token) & 15) return GT_E_ALIGN;
+  if ((uintptr_t)acc2 & 7) return GT_E_ALIGN;
+  hipLaunchKernelGGL(gt_align_loss_fwd_kernel, dim3(GT_MLE_PARTS + (logw ? B : 0)), dim3(256), 0, GT_ST(stream), z, x_m, x_logs, frame2token,
+                     logw, w, x_lengths, z_m, z_logs, acc2, l_length, B, C, Tx, Ty);
+  GT_RET();
+}
+extern "C" int gt_align_loss_finish(const float* acc2, const float* logdet, const float* mask, int n_mask, const float* l_length, int B, int C,
+                                    float* out4, void* stream)
+{
+  if (!acc2 || !logdet || !mask || !out4 || B <= 0 || C <= 0 || n_mask <= 0) return GT_E_INVAL;
+  if ((uintptr_t)acc2 & 7) return GT_E_ALIGN;
+  hipLaunchKernelGGL(gt_align_loss_finish_kernel, dim3(1), dim3(1024), 0, GT_ST(stream), acc2, logdet, mask, n_mask, l_length, B, C, out4);
+  GT_RET();
+}
+extern "C" int gt_align_loss_bwd(const float* z, const float* z_m, const float* z_logs, const int32_t* frame2token, const float* logw,
+                                 const float* w, const int32_t* x_lengths, const float* gscale, const float* gdenom, float* dz, float* dx_m,
+                                 float* dx_logs, float* dlogdet, float* dlogw, int B, int C, int Tx, int Ty, void* stream)
+{
+  if (!z || !z_m || !frame2token || !gscale || !gdenom || !dz || !dx_m || !dlogdet || (z_logs && !dx_logs) || B <= 0 || C <= 0 || Tx <= 0 ||
+      Ty <= 0)
+    return GT_E_INVAL;
+  if ((logw != nullptr) != (w != nullptr) || (logw && (!x_lengths || !dlogw))) return GT_E_INVAL;
+  if (Tx > 512) return GT_E_UNSUPPORTED;                      // acc[..][4][512]: past it gt_prior_expand_bwd's long form (the unfused chain)
+  if ((size_t)B * C * Ty > 0x7fffffffu) return GT_E_UNSUPPORTED;
+  const int row_blocks = (int)(((size_t)B * C + 3) / 4);
+  const dim3 grid(row_blocks + 1 + (logw ? B : 0));
+  if (z_logs)
+    hipLaunchKernelGGL(gt_align_loss_bwd_kernel<true>, grid, dim3(256), 0, GT_ST(stream), z, z_m, z_logs, frame2token, logw, w, x_lengths, gscale,
+                       gdenom, dz, dx_m, dx_logs, dlogdet, dlogw, B, C, Tx, Ty, row_blocks);
+  else
+    hipLaunchKernelGGL(gt_align_loss_bwd_kernel<false>, grid, dim3(256), 0, GT_ST(stream), z, z_m, z_logs, frame2token, logw, w, x_lengths, gscale,
+                       gdenom, dz, dx_m, dx_logs, dlogdet, dlogw, B, C, Tx, Ty, row_blocks);
   GT_RET();
 }
 extern "C" int gt_mle_bwd(const float* z, const float* m, const float* logs, const float* gscale, float* dz, float* dm, float* dlogs,

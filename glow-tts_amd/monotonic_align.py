@@ -28,7 +28,7 @@ class MASResult:
 
 
 def maximum_path_lengths(value, t_x, t_y, mask=None, out_dtype=None, want_durations=False,
-                         want_frame2token=False, validate=False, keep_workspace=False, allow_long=False):
+                         want_frame2token=False, validate=False, keep_workspace=False, allow_long=False, want_path=True):
     """MAS from explicit lengths (the native form: no mask traffic).
 
     value: [b, t_x_max, t_y_max] float tensor on the GPU (fp32 is used as is; other float
@@ -38,6 +38,8 @@ def maximum_path_lengths(value, t_x, t_y, mask=None, out_dtype=None, want_durati
            (__init__.py:11) on the fly.
     allow_long: a lattice gt_mas_f32 refuses (t_x_max > 512, or gt_mas_lds_bytes > 160 KiB) goes to gt_mas_long_f32
            instead of raising; every lattice gt_mas_f32 accepts is still computed by it.
+    want_path: False skips the dense path (no expand launch; ``path`` is then None) — for callers that read the durations and the
+           frame -> token map only.
     Returns MASResult; ``path`` has dtype ``out_dtype`` (default value.dtype).
     """
     _lib.require_cuda(value, t_x, t_y, mask)
@@ -60,7 +62,7 @@ def maximum_path_lengths(value, t_x, t_y, mask=None, out_dtype=None, want_durati
             v = v.contiguous()
     t_x = t_x.to(device=v.device, dtype=torch.int32).contiguous()
     t_y = t_y.to(device=v.device, dtype=torch.int32).contiguous()
-    path = torch.empty((B, T_x, T_y), dtype=out_dtype, device=v.device)
+    path = torch.empty((B, T_x, T_y), dtype=out_dtype, device=v.device) if want_path else None
     dur = torch.empty((B, T_x), dtype=torch.float32, device=v.device) if want_durations else None
     f2t = torch.empty((B, T_y), dtype=torch.int32, device=v.device) if want_frame2token else None
     status = torch.zeros((1,), dtype=torch.int32, device=v.device) if validate else None

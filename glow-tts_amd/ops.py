@@ -220,6 +220,10 @@ class RowsConfig:
         # backward then starts behind the likelihood terms, beside the predictors' forward, instead of behind it
         self.dp_balance = os.environ.get("GT_DP_BALANCE", "1") != "0"        # long texts: the duration predictor on the caller's stream (text_models)
         self.join_predictors = True
+        # the alignment -> loss chain as one autograd node of three launches (text_models._AlignLossFn): forward() then returns no
+        # dense attention path and (for mean_only) no z_logs, and leaves (total, l_mle) in model._fused_loss.  Off: forward() returns
+        # what it always did; train.Trainer turns it on around its own steps
+        self.fused_align_loss = False
         self.front_stream = os.environ.get("GT_FRONT_STREAM", "1") != "0"    # the conditioning front end (and its backward) on a stream of its own
 
 

@@ -258,7 +258,9 @@ class _LogpMasFn:
     """no_grad block of models.py:1076-1083: logp lattice + MAS on the device."""
 
     @staticmethod
-    def run(x_m, x_logs, z, x_lengths, y_lengths, mean_only):
+    def run(x_m, x_logs, z, x_lengths, y_lengths, mean_only, want_path=True):
+        """x_lengths / y_lengths: int32 tensors are used as they are (any other dtype costs a cast launch each);
+        want_path=False: no dense path (mas.path is None)"""
         B, C, Tx = x_m.shape
         Ty = z.shape[2]
         dev = z.device
@@ -268,7 +270,8 @@ class _LogpMasFn:
         zz = z.detach().float().contiguous()
         call.gt_logp_f32(xm, xs, zz, logp, B, C, Tx, Ty, _lib.current_stream(dev))
         r = monotonic_align.maximum_path_lengths(logp, x_lengths.to(torch.int32), y_lengths.to(torch.int32),
-                                                 want_durations=True, want_frame2token=True, keep_workspace=True, allow_long=True)
+                                                 want_durations=True, want_frame2token=True, keep_workspace=True, allow_long=True,
+                                                 want_path=want_path)
         return logp, r
 
 
@@ -351,6 +354,56 @@ class _DurationLossFn(torch.autograd.Function):
         d = torch.empty(shape, dtype=torch.float32, device=lw.device)
         call.gt_duration_loss_bwd(lw, wc, xl, gc, B, Tx, d, _lib.current_stream(lw.device))
         return d, None, None
+
+
+class _AlignLossFn(torch.autograd.Function):
+    """_PriorExpandFn + _MleLossFn + _DurationLossFn + their sum as ONE node: three launches forward and backward together
+    (gt_align_loss_fwd / _finish / _bwd, csrc/encoder_ops.hip) instead of twelve, bit-identical to them.  Differentiable inputs:
+    z, x_m, x_logs (None = mean_only), logdet, logw (None: the duration term is not part of this node).  -> (total, l_mle, z_m,
+    z_logs or None, l_length or None); only `total` = l_mle + sum(l_length) carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, z, x_m, x_logs, logdet, logw, w, f2t, x_len32, mask):
+        dev = z.device
+        B, C, Tx = x_m.shape
+        Ty = z.shape[2]
+        st = _lib.current_stream(dev)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)      # noqa: E731
+        zc, xm = z.detach().float().contiguous(), x_m.detach().float().contiguous()
+        xs = None if x_logs is None else x_logs.detach().float().contiguous()
+        lw = None if logw is None else logw.detach().float().contiguous()
+        wc = None if logw is None else w.detach().float().contiguous()
+        z_m = new(B, C, Ty)
+        z_logs = None if xs is None else new(B, C, Ty)
+        l_length = None if lw is None else new(B)
+        acc = new(2 * _lib.MLE_PARTS)
+        call.gt_align_loss_fwd(zc, xm, xs, f2t, lw, wc, x_len32, z_m, z_logs, acc, l_length, B, C, Tx, Ty, st)
+        ld = logdet.detach().float().contiguous()
+        mk = mask.detach().float().contiguous()
+        out = new(4)
+        call.gt_align_loss_finish(acc, ld, mk, mk.numel(), l_length, ld.numel(), C, out, st)
+        ctx.saved = (zc, z_m, z_logs, f2t, lw, wc, x_len32, out, (B, C, Tx, Ty), logdet.shape, None if logw is None else logw.shape)
+        res = (out[3], out[0], z_m, z_logs, l_length)
+        ctx.mark_non_differentiable(*[t for t in res[1:] if t is not None])
+        ctx.set_materialize_grads(False)                         # (else autograd fills a zero gradient per unused output: z_m's is 8 MB)
+        return res
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        if g is None:
+            return (None,) * 9
+        zc, z_m, z_logs, f2t, lw, wc, x_len32, out, (B, C, Tx, Ty), ld_shape, lw_shape = ctx.saved
+        dev = zc.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)      # noqa: E731
+        gs = g.float().reshape(1).contiguous()                   # divided by the denominator (out[1]) inside the kernel
+        dz = torch.empty_like(zc)
+        dx_m = new(B, C, Tx)
+        dx_logs = None if z_logs is None else new(B, C, Tx)
+        dlogdet = new(ld_shape)
+        dlogw = None if lw is None else new(lw_shape)
+        call.gt_align_loss_bwd(zc, z_m, z_logs, f2t, lw, wc, x_len32, gs, out[1:].data_ptr(), dz, dx_m, dx_logs, dlogdet, dlogw,
+                               B, C, Tx, Ty, _lib.current_stream(dev))
+        return dz, dx_m, dx_logs, dlogdet, dlogw, None, None, None, None
 
 
 def mle_loss(z, m, logs, logdet, mask):
@@ -745,7 +798,9 @@ class FlowGenerator(nn.Module):
         decoder's (and the predictors') gradients only and `backward_encoder()` runs the rest later — the data-parallel
         trainer all-reduces the decoder's 90 % of the gradient bytes while the encoder's backward runs.
         noise = (e_w [b,2,t_x], e_p [b,1,t_y], e_e [b,1,t_y]): the predictors' torch.randn draws (models.py:288,383,457),
-        injected by the parity tests."""
+        injected by the parity tests.
+        With rows_cfg.fused_align_loss on (train.Trainer's steps; off by default) and a supported shape, the loss is computed here
+        (self._fused_loss, see _AlignLossFn) and attn is None, as is z_logs for mean_only models."""
         # The conditioning front end (speaker / emotion / language embeddings: ~40 small launches on [B, <= 512] tensors) runs on a
         # stream of its own when the step forks anyway: autograd then replays its BACKWARD there too — it needs the conditioning
         # vector's gradient from every consumer, so on the caller's stream it queued behind the decoder's weight gradients, optimizer
@@ -819,6 +874,13 @@ class FlowGenerator(nn.Module):
                 leaf = x_logs.detach().requires_grad_(True)
                 self._deferred.append((x_logs, leaf)); x_logs = leaf
         y, y_lengths, y_max_length = self.preprocess(y, y_lengths, y.size(2))
+        # rows_cfg.fused_align_loss (train.Trainer's steps): everything between MAS and the decoder's backward as ONE autograd node of
+        # three launches (_AlignLossFn) — that stretch runs with both streams joined, every launch in it is serial step time.  Decided
+        # on the padded shapes; `path=` (the test hook), long texts and a T_y off the float4 grid take the separate launches.
+        self._fused_loss = None
+        fused = bool(self.rows_cfg.fused_align_loss) and path is None and x.is_cuda and x.shape[1] <= 512 and y_max_length % 4 == 0
+        # MAS reads int32 lengths: the text side's are the row context's own; the mel side's are cast HERE, ahead of the decoder
+        y_len32 = y_lengths.to(torch.int32) if fused else None
         z_mask = ops.length_mask(y_lengths, y_max_length, x_mask.dtype)
         pitch_norm, energy_norm = self._contour(pitch, y_max_length), self._contour(energy, y_max_length)
         ops.mark("dec fwd begin")
@@ -832,19 +894,24 @@ class FlowGenerator(nn.Module):
             if dp_here:
                 logw = self._predict_logw(g, l)
                 ops.mark("dp fwd end")
+        rcx, xb = self.encoder._last_rows
         with torch.no_grad():
-            logp, mas = _LogpMasFn.run(x_m, x_logs, z, x_lengths, y_lengths, self.mean_only)
+            if fused:                                                         # no length casts, no dense path: nothing of the step reads it
+                logp, mas = _LogpMasFn.run(x_m, x_logs, z, rcx.lengths, y_len32, self.mean_only, want_path=False)
+            else:
+                logp, mas = _LogpMasFn.run(x_m, x_logs, z, x_lengths, y_lengths, self.mean_only)
             self._last_mas_path = mas.path                                    # (the searched alignment, whatever `path` says)
             if path is not None:                                              # test hook: a given alignment [b, t_x, t_y] instead
                 mas = monotonic_align.result_from_path(path.reshape(mas.path.shape).to(mas.path.dtype), x_lengths.to(torch.int32),
                                                        y_lengths.to(torch.int32))
-            attn = mas.path.unsqueeze(1)
+            attn = None if mas.path is None else mas.path.unsqueeze(1)
         ops.mark("mas done")
         w = mas.durations.unsqueeze(1)                                        # attn.sum(3): models.py:1085
-        rcx, xb = self.encoder._last_rows
         # The stochastic predictors need the alignment, but nothing after them does except the loss: they go onto the
         # encoder's stream, so that autograd replays their (long, row-wise) backward there too, beside the decoder's.
         pfork = fork and self.rows_cfg.predictor_branch and (self.use_sdp or self.use_spp or self.use_sep)
+        # the deterministic predictor's loss is part of the fused node unless it lives on the predictors' stream
+        dur_fused = fused and not self.use_sdp and not pfork
         if pfork:
             enc_stream.wait_stream(main)
             for t_ in (w, mas.frame2token, mas.durations, pitch_norm, energy_norm, z_mask, x_mask, y_lengths):
@@ -853,7 +920,8 @@ class FlowGenerator(nn.Module):
         with (torch.cuda.stream(enc_stream) if pfork else contextlib.nullcontext()):
             l_length, l_pitch, l_energy, logw = self._predictor_losses(rcx, xb, w, x_mask, x_lengths, z_mask, g, l, logw, noise, mas, y_lengths,
                                                                        y_max_length, pitch_norm, energy_norm,
-                                                                       energy_stream=main if (pfork and self.rows_cfg.energy_on_main) else None)
+                                                                       energy_stream=main if (pfork and self.rows_cfg.energy_on_main) else None,
+                                                                       skip_duration_loss=dur_fused)
         # which stream each loss term was produced on; None = the caller's (joined below, or never forked)
         self._loss_streams = None
         if pfork and self.rows_cfg.join_predictors:
@@ -865,14 +933,24 @@ class FlowGenerator(nn.Module):
             # no join: l_length / l_pitch (and l_energy unless its chain ran on the caller's stream) stay on the encoder's stream;
             # the caller seeds the backward per stream (train.Trainer._loss_roots) and joins the streams after it
             self._loss_streams = {"stream": enc_stream, "energy_on_caller": bool(self.rows_cfg.energy_on_main and self.use_spp and self.use_sep)}
+        self.last_logp = logp
+        if fused:
+            # (total, l_mle, whether the duration term is in total): what train.Trainer._loss takes in place of mle_loss + sum.
+            # z_logs is None for mean_only models (no [B, C, T_y] fill of zeros that the loss then replaces by None again)
+            total, l_mle, z_m, z_logs, ll = _AlignLossFn.apply(z, x_m, None if self.mean_only else x_logs, logdet, logw if dur_fused else None,
+                                                               w if dur_fused else None, mas.frame2token, rcx.lengths, z_mask)
+            if dur_fused:
+                l_length = ll
+            self._fused_loss = (total, l_mle, dur_fused)
+            return (z, z_m, z_logs, logdet, z_mask), (x_m, x_logs, x_mask), (attn, l_length, l_pitch, l_energy), (None, None, None, None), None
         z_m = _PriorExpandFn.apply(x_m, mas.frame2token, mas.workspace)
         z_logs = torch.zeros_like(z_m) if self.mean_only else _PriorExpandFn.apply(x_logs, mas.frame2token, mas.workspace)
-        self.last_logp = logp
         return (z, z_m, z_logs, logdet, z_mask), (x_m, x_logs, x_mask), (attn, l_length, l_pitch, l_energy), (None, None, None, None), None
 
     def _predictor_losses(self, rcx, xb, w, x_mask, x_lengths, z_mask, g, l, logw, noise, mas, y_lengths, y_max_length, pitch_norm, energy_norm,
-                          energy_stream=None):
+                          energy_stream=None, skip_duration_loss=False):
         """l_length, l_pitch, l_energy of models.py:1086-1115 (+ logw of the deterministic duration predictor).
+        skip_duration_loss: the deterministic predictor's l_length is left to the caller (None here; logw is still predicted).
         energy_stream: the energy predictor's chain goes there (the caller's main stream, idle between MAS and the loss) instead of
         queueing behind the duration and pitch predictors on the current (encoder) stream."""
         # The frame-rate features both prosody predictors read come FIRST and the event behind them is what the energy chain on the
@@ -895,7 +973,7 @@ class FlowGenerator(nn.Module):
         else:                                                                  # models.py:1089-1092
             if logw is None:
                 logw = self._predict_logw(g, l)
-            l_length = _DurationLossFn.apply(logw, w, x_lengths)
+            l_length = None if skip_duration_loss else _DurationLossFn.apply(logw, w, x_lengths)
         if self.use_spp or self.use_sep:
             if self.use_spp:
                 pp = self.proj_pitch

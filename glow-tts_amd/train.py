@@ -448,14 +448,16 @@ class Trainer:
     def __init__(self, model, lr=2e-4, betas=(0.9, 0.98), eps=1e-9, world=1, graph=False, total_steps=None,
                  split_graph=None, ragged=None, max_graphs=8, pad_tx=16, pad_ty=32, kernel_stamps=False, grad_wire="fp32",
                  force_collectives=False, capture_after=2, ty_boundaries=None, row_round=None, early_decoder_adam=True, pack_in_tail=True, split_roots=True,
-                 attn_keep_p=None):
+                 attn_keep_p=None, fused_align_loss=True):
         """total_steps: length of the OneCycleLR schedule the reference runs (train_ms_emo_lang_pitch.py:161);
         None keeps lr / betas constant.  split_graph=True selects the phased form (the decoder's gradient slice on the wire while the
         encoder's backward runs: three graphs); the default at any world size is ONE backward — the encoder's backward beside the
         decoder's, which is worth 1.16 ms of a 4.84 ms step (bench.py --split-graph 1 at N = 1: 6.0 ms) — and then the whole flat
         buffer on the wire (114 MB fp32: ~0.3-0.7 ms exposed on an 8-GPU xGMI node) between the two graphs.
         attn_keep_p: None leaves model.rows_cfg.attn_keep_p as it is (True: every encoder layer keeps its softmax P for the backward);
-        False trains texts past 505 tokens without it (ops.RowsConfig.attn_keep_p), eagerly and under the captured step alike."""
+        False trains texts past 505 tokens without it (ops.RowsConfig.attn_keep_p), eagerly and under the captured step alike.
+        fused_align_loss: this trainer's steps run the chain from the alignment to the loss and back as one node of three launches
+        (ops.RowsConfig.fused_align_loss; same numbers bit for bit); False keeps the separate launches."""
         from collections import OrderedDict
         self.model = model
         self.world = world
@@ -465,6 +467,7 @@ class Trainer:
         self.pack_in_tail = bool(pack_in_tail)
         # cfg-5-like models (stochastic predictors on the encoder's stream): the single-backward step does not join that branch at the
         # end of the forward; the backward gets one root per stream (_loss_roots)
+        self.fused_align_loss = bool(fused_align_loss)
         self.split_roots = bool(split_roots)   # ... followed by the next step's packing of the decoder's weights (see _early_decoder_update)
         self._dec_fresh_version = None        # flat_p._version at which the decoder's packed weight images were last made at a step's end
         self._head_rest = self._tail_packed = False
@@ -538,8 +541,13 @@ class Trainer:
         """The reference's training loss (train_ms_emo_lang_pitch.py:295-306): mle + sum(l_length) [+ 0.5 l_pitch + 0.5 l_energy]."""
         m = self.model
         (z, z_m, z_logs, logdet, z_mask), _, (attn, l_length, l_pitch, l_energy), _, _ = outs
-        l_mle = models.mle_loss(z, z_m, None if m.mean_only else z_logs, logdet, z_mask)
-        loss = l_mle + torch.sum(l_length)
+        fl = m.__dict__.pop("_fused_loss", None)
+        if fl is not None:                               # (total, l_mle, total includes sum(l_length)) of text_models._AlignLossFn
+            l_mle = fl[1]
+            loss = fl[0] if fl[2] else fl[0] + torch.sum(l_length)
+        else:
+            l_mle = models.mle_loss(z, z_m, None if m.mean_only else z_logs, logdet, z_mask)
+            loss = l_mle + torch.sum(l_length)
         if l_pitch is not None:
             loss = loss + 0.5 * l_pitch
         if l_energy is not None:
@@ -557,8 +565,11 @@ class Trainer:
             loss, l_mle = self._loss(outs)
             return [loss], l_mle
         (z, z_m, z_logs, logdet, z_mask), _, (attn, l_length, l_pitch, l_energy), _, _ = outs
-        l_mle = models.mle_loss(z, z_m, None if m.mean_only else z_logs, logdet, z_mask)
-        here = l_mle
+        fl = m.__dict__.pop("_fused_loss", None)             # (the duration term is never part of it here: it lives on the other stream)
+        if fl is not None:
+            here, l_mle = fl[0], fl[1]
+        else:
+            here = l_mle = models.mle_loss(z, z_m, None if m.mean_only else z_logs, logdet, z_mask)
         with torch.cuda.stream(ls["stream"]):
             there = torch.sum(l_length)
             if l_pitch is not None:
@@ -638,11 +649,13 @@ class Trainer:
         rows_cfg = getattr(self.model, "rows_cfg", None)
         if rows_cfg is not None:
             rows_cfg.join_predictors = not self.split_roots
+            rows_cfg.fused_align_loss = self.fused_align_loss
         try:
             roots, l_mle = self._loss_roots(self.model(ids, t_x, y, t_y, lengths_host=lengths_host, **(cond or {})))
         finally:
             if rows_cfg is not None:
                 rows_cfg.join_predictors = True
+                rows_cfg.fused_align_loss = False
         ops.mark("loss")
         dec = getattr(self.model, "decoder", None)
         early = early_update and self.early_decoder_adam and dec is not None and not self.buckets.collect and ids.is_cuda
@@ -683,8 +696,15 @@ class Trainer:
     def _phase1(self, ids, t_x, y, t_y, lengths_host=None, cond=None):
         """forward + the backward of everything but the text encoder; the decoder's gradients are then in the flat buffer."""
         self._begin(ids.device)
-        loss, l_mle = self._loss(self.model(ids, t_x, y, t_y, lengths_host=lengths_host, defer_encoder_backward=True,
-                                            **(cond or {})))
+        rows_cfg = getattr(self.model, "rows_cfg", None)
+        if rows_cfg is not None:
+            rows_cfg.fused_align_loss = self.fused_align_loss
+        try:
+            loss, l_mle = self._loss(self.model(ids, t_x, y, t_y, lengths_host=lengths_host, defer_encoder_backward=True,
+                                                **(cond or {})))
+        finally:
+            if rows_cfg is not None:
+                rows_cfg.fused_align_loss = False
         loss.backward()
         self.buckets.gather(self.dec0, None)
         return loss.detach(), l_mle.detach()

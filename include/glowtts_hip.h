@@ -490,6 +490,26 @@ int gt_mle_finish(const float* acc2, const float* logdet, const float* mask, int
 int gt_duration_loss_fwd(const float* logw, const float* w, const int32_t* x_lengths, int B, int Tx, float* l_length, void* stream);
 int gt_duration_loss_bwd(const float* logw, const float* w, const int32_t* x_lengths, const float* g, int B, int Tx, float* dlogw, void* stream);
 
+/* The alignment -> loss chain of a training step in three launches; every output is bit-identical to the chain of entries above
+ * (gt_prior_expand, gt_mle_sums, gt_mle_finish, gt_duration_loss_fwd; gt_mle_bwd, gt_prior_expand_bwd, gt_duration_loss_bwd).
+ * gt_align_loss_fwd: z [B,C,Ty], x_m (x_logs, NULL = mean_only) [B,C,Tx], frame2token [B,Ty] (-1 = padded frame) -> z_m (z_logs with
+ *   x_logs) [B,C,Ty] and the GT_MLE_PARTS partial pairs in acc2; with logw and w ([B,Tx]; both or neither) and x_lengths also
+ *   l_length [B].  GT_E_ALIGN: Ty % 4 != 0, or z / z_m / z_logs / frame2token off a 16-byte boundary; GT_E_UNSUPPORTED: Tx > 512 or
+ *   B C Ty >= 2^31; nothing is written then (the callers go on with the unfused entries).
+ * gt_align_loss_finish: out4[0] = mle loss, out4[1] = its denominator (both as gt_mle_finish), out4[2] = sum_b l_length[b] in the
+ *   order ATen's sum gives a contiguous fp32 vector of B < 128 elements (l_length NULL: 0), out4[3] = out4[0] + out4[2].
+ * gt_align_loss_bwd: with g = *gscale / *gdenom: dz = g e^{-2 z_logs}(z - z_m), dx_m = segment sums of -dz, dx_logs (with z_logs) =
+ *   segment sums of g (1 - e^{-2 z_logs}(z - z_m)^2), dlogdet[b] = -g, and with logw / w: dlogw = *gscale * 2 (logw - logw_) /
+ *   sum(mask).  One launch; Tx <= 512 (GT_E_UNSUPPORTED past it). */
+int gt_align_loss_fwd(const float* z, const float* x_m, const float* x_logs, const int32_t* frame2token, const float* logw, const float* w,
+                      const int32_t* x_lengths, float* z_m, float* z_logs, float* acc2, float* l_length, int B, int C, int Tx, int Ty,
+                      void* stream);
+int gt_align_loss_finish(const float* acc2, const float* logdet, const float* mask, int n_mask, const float* l_length, int B, int C,
+                         float* out4, void* stream);
+int gt_align_loss_bwd(const float* z, const float* z_m, const float* z_logs, const int32_t* frame2token, const float* logw, const float* w,
+                      const int32_t* x_lengths, const float* gscale, const float* gdenom, float* dz, float* dx_m, float* dx_logs,
+                      float* dlogdet, float* dlogw, int B, int C, int Tx, int Ty, void* stream);
+
 /* [B, C, T] <-> rows at the public boundary (fp32 or bf16 on either side: *_f32 = 1 / 0), one launch each:
  *   gt_rows_from_bct: rows[m, c] = x[b, c, t] for the frame rows of utterance b (row base(b) + HALO + t, 0 <= t < T), 0 elsewhere;
  *   gt_bct_from_rows: x[b, c, t] = rows[base(b) + HALO + t, c] for t < lengths[b], 0 beyond.  row0 == NULL: uniform layout. */
