@@ -220,6 +220,9 @@ PROTOTYPES = {
     "gt_voc_tile_positions": (c_int, []),
     "gt_voc_k_chunk": (c_int, [c_int]),
     "gt_voc_lds_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gt_voc_snake": (STATUS, [c_void_p, c_void_p]),
+    "gt_voc_snake_args_size": (c_int, []),
+    "gt_voc_snake_tile_positions": (c_int, []),
 }
 c_void_p = ctypes.c_void_p
 
@@ -361,12 +364,19 @@ class VocConvArgs(ctypes.Structure):
                 ("x_bf16", c_int), ("x_mel", c_int), ("y_bf16", c_int), ("tanh_out", c_int), ("slope", c_float), ("scale", c_float)]
 
 
+class VocSnakeArgs(ctypes.Structure):
+    """struct gt_voc_snake_args (include/glowtts_hip.h); its size is checked against gt_voc_snake_args_size() (tests/test_voc_snake_cabi.py)"""
+    _fields_ = [("X", c_void_p), ("x_stride_b", c_i64), ("P", c_void_p), ("Y", c_void_p), ("y_stride_b", c_i64), ("len_mul", c_int),
+                ("n_frames", c_void_p), ("B", c_int), ("L_cap", c_int), ("C", c_int)]
+
+
 # mirror -> its C struct in include/glowtts_hip.h (tests/test_cabi.py compares every size and field offset with a C compiler's)
 C_STRUCTS = {PackDesc: "gt_pack_desc", StepCopy: "gt_step_copy", StepCtx: "gt_step_ctx", StepInputsArgs: "gt_step_inputs_args",
              PartialsJob: "gt_partials_job", PartialsArgs: "gt_partials_args", StepZeroArgs: "gt_step_zero_args",
              WnStackFwdArgs: "gt_wn_stack_fwd_args", WnStackBwdArgs: "gt_wn_stack_bwd_args", BoundaryFwdArgs: "gt_boundary_fwd_args",
              BoundaryBwdArgs: "gt_boundary_bwd_args", BoundaryRevArgs: "gt_boundary_rev_args", SynthPriorArgs: "gt_synth_prior_args",
-             SynthCall: "gt_synth_call", SynthCallExt: "gt_synth_call_ext", VocConvArgs: "gt_voc_conv_args"}
+             SynthCall: "gt_synth_call", SynthCallExt: "gt_synth_call_ext", VocConvArgs: "gt_voc_conv_args",
+             VocSnakeArgs: "gt_voc_snake_args"}
 
 
 def fill_args(cls, **kw):

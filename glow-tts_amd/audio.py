@@ -29,6 +29,10 @@ run by ONE HIP kernel (csrc/mel_front.hip: gt_mel_pack once, gt_mel_spectrogram 
                     checkpoints (`load_generator_state`, `from_config`); `workspace` / `run` are its capacity-sized form for graph
                     callers (synthesis.Synthesizer).  `transposed_as_conv`, `voc_pack`: the weight forms it runs on.
 
+  BigVGAN           the published BigVGAN generator: HiFiGAN (which it subclasses) with the anti-aliased snake activation, ONE launch of
+                    the stand-alone kernel gt_voc_snake (csrc/voc_snake.hip) in front of every convolution but the
+                    transposed ones; the original parameter tree and checkpoints; a 24-channel stage runs padded to 32.
+
 Waveforms are fp32 in [-1, 1] or int16 (scaled by 1/32768 in the kernel = the reference's audio / max_wav_value).  There is no CPU
 path: a CPU tensor raises."""
 import numpy as np
@@ -756,6 +760,8 @@ class HiFiGAN(nn.Module):
     resblock sum stay fp32, only the tensor between a resblock's two convolutions is bf16.  `launches` gt_voc_conv calls per run: 78
     for V1.  Any other (k, u), channels that are no multiple of 16, an even or > 11 resblock kernel: ValueError."""
 
+    CHANNEL_MULTIPLE = 16                # of every stage's channel count (BigVGAN pads its images instead: 1)
+
     def __init__(self, resblock="1", upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4), upsample_initial_channel=512,
                  resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5),) * 3, n_mel_channels=80):
         super().__init__()
@@ -776,7 +782,7 @@ class HiFiGAN(nn.Module):
         if any(d < 1 for ds in rd for d in ds):
             raise ValueError("dilations are >= 1")
         chans = [C0 >> i for i in range(len(rates) + 1)]
-        if n_mel_channels % 16 or any(c % 16 or c < 16 for c in chans) or C0 % (1 << len(rates)):
+        if n_mel_channels % 16 or any(c % self.CHANNEL_MULTIPLE or c < self.CHANNEL_MULTIPLE for c in chans) or C0 % (1 << len(rates)):
             raise ValueError(f"channel counts must be multiples of 16, got mel {n_mel_channels} and stages {chans}")
         self.resblock, self.upsample_rates, self.upsample_kernel_sizes = resblock, rates, kernels
         self.resblock_kernel_sizes, self.resblock_dilation_sizes = rk, rd
@@ -859,6 +865,14 @@ class HiFiGAN(nn.Module):
     def t_dtype(self):
         """the fourth buffer: bf16 between a resblock "1"'s two convolutions; for resblock "2" a second fp32 residual stream"""
         return torch.bfloat16 if self.resblock == "1" else torch.float32
+
+    def buffer_spec(self):
+        """[(name, dtype)] of the streams of E = B F_max W elements a run takes next to wav: what workspace and compile_synthesis allocate"""
+        return [("u", torch.float32), ("r", torch.float32), ("s", torch.float32), ("t", self.t_dtype)]
+
+    def held(self):
+        """what a captured graph of run() reads besides the buffers: its holder keeps it alive (the vocoder drops it when it repacks)"""
+        return self.images()
 
     def workspace(self, B, F_max, device):
         """the buffers of one run at capacity (B utterances of up to F_max frames): three fp32 streams u, r, s (a stage's input, a
@@ -952,3 +966,264 @@ class HiFiGAN(nn.Module):
         if mel_lengths is None:
             return wav
         return wav, n_frames.clamp(min=0, max=F) * self.hop_length
+
+
+# ---- BigVGAN: the HiFi-GAN generator with anti-aliased snake activations, csrc/voc_snake.hip in front of gt_voc_conv ----
+def kaiser_sinc_filter64(cutoff=0.25, half_width=0.3, kernel_size=12):
+    """BigVGAN's kaiser_sinc_filter1d in float64 [kernel_size]: the one filter of both resamplers of Activation1d"""
+    A = 2.285 * (kernel_size // 2 - 1) * np.pi * 4 * half_width + 7.95
+    beta = 0.1102 * (A - 8.7) if A > 50 else (0.5842 * (A - 21) ** 0.4 + 0.07886 * (A - 21) if A >= 21 else 0.0)
+    time = np.arange(-(kernel_size // 2), kernel_size // 2) + 0.5 if kernel_size % 2 == 0 else np.arange(kernel_size) - kernel_size // 2
+    f = 2 * cutoff * np.kaiser(kernel_size, beta) * np.sinc(2 * cutoff * time)
+    return f / f.sum()
+
+
+def _pad16(c):
+    return (c + 15) // 16 * 16
+
+
+def _padded(t, shape):
+    """t in the leading corner of zeros of `shape`"""
+    if tuple(t.shape) == tuple(shape):
+        return t
+    out = t.new_zeros(shape)
+    out[tuple(slice(0, n) for n in t.shape)] = t
+    return out
+
+
+class _Snake(nn.Module):
+    """parameter holder: Snake (alpha) or SnakeBeta (alpha, beta), per channel"""
+
+    def __init__(self, C, kind, logscale):
+        super().__init__()
+        init = torch.zeros if logscale else torch.ones
+        self.alpha = nn.Parameter(init(C))
+        if kind == "snakebeta":
+            self.beta = nn.Parameter(init(C))
+
+
+class _Filter(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.register_buffer("filter", torch.from_numpy(kaiser_sinc_filter64()).float().view(1, 1, 12))
+
+
+class _DownSample(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.lowpass = _Filter()
+
+
+class _Activation1d(nn.Module):
+    """holder under the original names: act.alpha (act.beta), upsample.filter, downsample.lowpass.filter"""
+
+    def __init__(self, C, kind, logscale):
+        super().__init__()
+        self.act, self.upsample, self.downsample = _Snake(C, kind, logscale), _Filter(), _DownSample()
+
+
+class _AMPBlock(_ResBlock):
+    def __init__(self, kind, C, k, dilations, act, logscale):
+        super().__init__(kind, C, k, dilations)
+        n = (2 if kind == "1" else 1) * len(dilations)
+        self.activations = nn.ModuleList(_Activation1d(C, act, logscale) for _ in range(n))
+
+
+class BigVGAN(HiFiGAN):
+    """The published BigVGAN generator (eval mode, weight norm folded) from log-mel to waveform: HiFi-GAN's generator with every leaky
+    ReLU replaced by the anti-aliased periodic activation Activation1d (2x up-sampling FIR -> snake -> 2x down-sampling FIR per channel)
+    and NO activation in front of the transposed convolutions.  The convolutions are gt_voc_conv's, untouched (slope 1, bf16 input);
+    each activation is ONE launch of the stand-alone kernel gt_voc_snake (csrc/voc_snake.hip), which writes the bf16
+    operand the next convolution reads.  Every utterance of a ragged batch on its own, as for HiFiGAN.
+
+      conv_pre -> per stage: ups[i][0] (transposed, no activation), the mean of the AMP blocks -> activation_post -> conv_post -> tanh
+      (use_tanh_at_final False: clamp to [-1, 1]; use_bias_at_final False: conv_post without bias)
+      AMPBlock1: x = convs2[m](acts[2m + 1](convs1[m](acts[2m](x)))) + x;  AMPBlock2: x = convs[m](acts[m](x)) + x
+
+    Parameters and buffers carry the published names (ups.{i}.0, resblocks.{j}.activations.{m}.act.alpha / .act.beta /
+    .upsample.filter / .downsample.lowpass.filter, activation_post...), so state_dict() round-trips with the original generator's.
+    A stage whose channel count is no multiple of 16 (the 24 channels the 112 M configurations end at) runs at the next multiple, padded
+    on the host: zero weight rows / columns, zero bias, alpha' = 1, 1 / beta' = 0 — a padded channel is exactly 0 everywhere.
+    `launches` C-ABI calls per run: 78 convolutions + 73 activations = 151 for the base shape."""
+
+    CHANNEL_MULTIPLE = 1
+
+    def __init__(self, resblock="1", upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4), upsample_initial_channel=512,
+                 resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5),) * 3, n_mel_channels=80, activation="snakebeta",
+                 snake_logscale=True, use_tanh_at_final=True, use_bias_at_final=True):
+        if activation not in ("snake", "snakebeta"):
+            raise ValueError(f'activation is "snake" or "snakebeta", got {activation!r}')
+        super().__init__(resblock, upsample_rates, upsample_kernel_sizes, upsample_initial_channel, resblock_kernel_sizes,
+                         resblock_dilation_sizes, n_mel_channels)
+        self.activation, self.snake_logscale = activation, bool(snake_logscale)
+        self.use_tanh_at_final, self.use_bias_at_final = bool(use_tanh_at_final), bool(use_bias_at_final)
+        ch, rk, rd = self.channels, self.resblock_kernel_sizes, self.resblock_dilation_sizes
+        self.padded_channels = [_pad16(c) for c in ch]
+        self.ups = nn.ModuleList(nn.ModuleList([up]) for up in self.ups)
+        self.resblocks = nn.ModuleList(_AMPBlock(self.resblock, ch[i + 1], k, ds, activation, self.snake_logscale)
+                                       for i in range(len(self.upsample_rates)) for k, ds in zip(rk, rd))
+        self.activation_post = _Activation1d(ch[-1], activation, self.snake_logscale)
+        self.conv_post = nn.Conv1d(ch[-1], 1, 7, padding=3, bias=self.use_bias_at_final)
+        self.conv_launches = self.launches
+        self.snake_launches = len(self.upsample_rates) * sum(len(rb.activations) for rb in self.resblocks[:len(rk)]) + 1
+        self.launches = self.conv_launches + self.snake_launches
+        for p in self.parameters():
+            p.requires_grad_(False)
+
+    @classmethod
+    def from_config(cls, cfg):
+        """from the published config.json's keys (num_mels optional: 80; the activation keys default to the published base model's)"""
+        return cls(resblock=cfg["resblock"], upsample_rates=cfg["upsample_rates"], upsample_kernel_sizes=cfg["upsample_kernel_sizes"],
+                   upsample_initial_channel=cfg["upsample_initial_channel"], resblock_kernel_sizes=cfg["resblock_kernel_sizes"],
+                   resblock_dilation_sizes=cfg["resblock_dilation_sizes"], n_mel_channels=cfg.get("num_mels", 80),
+                   activation=cfg.get("activation", "snakebeta"), snake_logscale=cfg.get("snake_logscale", True),
+                   use_tanh_at_final=cfg.get("use_tanh_at_final", True), use_bias_at_final=cfg.get("use_bias_at_final", True))
+
+    # ---- images and parameter blocks, in launch order, at the padded widths ----------------------------------------------------------------
+    def _convs(self):
+        K = len(self.resblock_kernel_sizes)
+        seq = [self.conv_pre]
+        for i in range(len(self.ups)):
+            seq.append(self.ups[i][0])
+            for j in range(K):
+                rb = self.resblocks[i * K + j]
+                if self.resblock == "1":
+                    for c1, c2 in zip(rb.convs1, rb.convs2):
+                        seq += [c1, c2]
+                else:
+                    seq += list(rb.convs)
+        return seq + [self.conv_post]
+
+    def _activations(self):
+        return [act for rb in self.resblocks for act in rb.activations] + [self.activation_post]
+
+    def snake_block64(self, act):
+        """gt_voc_snake's parameter block of one Activation1d in float64, at the padded width Cp: [Cp] alpha', [Cp] 1 / (beta' + 1e-9),
+        [12] the module's up-sampling filter, [12] its down-sampling filter; padding alpha' = 1, 1 / beta' = 0"""
+        al = act.act.alpha.detach().double().cpu()
+        be = act.act.beta.detach().double().cpu() if self.activation == "snakebeta" else al
+        if self.snake_logscale:
+            al, be = al.exp(), be.exp()
+        C = al.numel()
+        Cp = _pad16(C)
+        a, ib = torch.ones(Cp, dtype=torch.float64), torch.zeros(Cp, dtype=torch.float64)
+        a[:C], ib[:C] = al, 1.0 / (be + 1e-9)
+        return torch.cat([a, ib, act.upsample.filter.detach().double().cpu().reshape(-1),
+                          act.downsample.lowpass.filter.detach().double().cpu().reshape(-1)])
+
+    def _packed(self):
+        """([(bf16 image, fp32 bias)] per convolution, [fp32 parameter block] per activation), both in launch order, rebuilt when any
+        parameter's or buffer's (data_ptr, _version) changes"""
+        def build():
+            dev, imgs = self.conv_pre.weight.device, []
+            for m in self._convs():
+                w = m.weight.detach().float()
+                b = m.bias.detach().float() if m.bias is not None else w.new_zeros(1)
+                if isinstance(m, nn.ConvTranspose1d):
+                    u = m.stride[0]
+                    w = _padded(w, (_pad16(w.shape[0]), _pad16(w.shape[1]), w.shape[2]))
+                    imgs.append((voc_pack(transposed_as_conv(w, u)), _padded(b, (w.shape[1],)).repeat(u).contiguous()))
+                else:
+                    N = w.shape[0] if m is self.conv_post else _pad16(w.shape[0])
+                    imgs.append((voc_pack(_padded(w, (N, _pad16(w.shape[1]), w.shape[2]))), _padded(b, (N,)).contiguous()))
+            blocks64 = [self.snake_block64(act) for act in self._activations()]
+            flat = torch.cat(blocks64).float().to(dev)                 # float64 on the host, rounded once
+            offs = np.cumsum([0] + [b.numel() for b in blocks64])
+            return imgs, [flat[offs[i]:offs[i + 1]] for i in range(len(blocks64))]
+        return self._images.get(list(self.parameters()) + list(self.buffers()), build)
+
+    def images(self):
+        return self._packed()[0]
+
+    def snake_blocks(self):
+        return self._packed()[1]
+
+    def held(self):
+        return self._packed()
+
+    # ---- capacity-sized form ------------------------------------------------------------------------------------------------------------
+    def _width(self):
+        U, w = 1, self.padded_channels[0]
+        for i, u in enumerate(self.upsample_rates):
+            U *= u
+            w = max(w, U * self.padded_channels[i + 1])
+        return w
+
+    def workspace_bytes(self, B, F_max):
+        """18 E + 4 B U F_max with E = B F_max W, W = max(C_0, max_i U_i C_i) over the padded channel counts (8192 for the base shape)"""
+        return 18 * B * F_max * self._width() + 4 * B * self.hop_length * F_max
+
+    @property
+    def t_dtype(self):
+        """fp32: the tensor between an AMP block's two convolutions is the second activation's input"""
+        return torch.float32
+
+    def buffer_spec(self):
+        return super().buffer_spec() + [("a", torch.bfloat16)]
+
+    def workspace(self, B, F_max, device):
+        """HiFiGAN's u, r, s and a t of fp32, one bf16 stream a (every activation's output: the operand of the convolution behind it) of
+        E = B F_max W elements each, and wav fp32 [B, U F_max]: 18 E + 4 B U F_max bytes.  B F_max W must stay below 2^31."""
+        E = B * F_max * self._width()
+        if B < 1 or F_max < 1 or E >= 2 ** 31:
+            raise ValueError(f"workspace for {B} x {F_max} frames: B F_max W = {E} must lie in [1, 2^31)")
+        bufs = {name: torch.empty(E, dtype=dtype, device=device) for name, dtype in self.buffer_spec()}
+        bufs["wav"] = torch.empty(B, self.hop_length * F_max, dtype=torch.float32, device=device)
+        return bufs
+
+    def _snake(self, dev, n_frames, B, L, mul, X, P, Y, C):
+        a = _lib.fill_args(_lib.VocSnakeArgs, X=X, x_stride_b=L * C, P=P, Y=Y, y_stride_b=L * C, len_mul=mul, n_frames=n_frames, B=B,
+                           L_cap=L, C=C)
+        call.gt_voc_snake(a, _lib.current_stream(dev))
+
+    def run(self, mel, n_frames, bufs):
+        """kernel calls, the capacity-sized form for graph callers (HiFiGAN.run's contract): `launches` C-ABI calls — conv_launches
+        gt_voc_conv and snake_launches gt_voc_snake — nothing allocated once the images and parameter blocks exist, n_frames never
+        looked at on the host, every grid sized by F_max.  Without tanh one in-place torch clamp follows (capturable, not counted)."""
+        wav = bufs["wav"]
+        B, U = wav.shape[0], self.hop_length
+        F = wav.shape[1] // U
+        if not mel.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
+        if mel.dtype != torch.float32 or mel.dim() != 3 or mel.stride(2) != 1:
+            raise ValueError("run takes a device fp32 log-mel [B, n_mel, F] with contiguous frames")
+        if mel.shape[0] != B or mel.shape[1] != self.n_mel_channels or mel.shape[2] < F:
+            raise ValueError(f"mel {tuple(mel.shape)} does not fit buffers for [{B}, {self.n_mel_channels}, {F}]")
+        if n_frames.dtype != torch.int32 or n_frames.numel() != B or not n_frames.is_cuda or not n_frames.is_contiguous():
+            raise ValueError("n_frames must be a contiguous int32 [B] on the device")
+        if self.conv_pre.weight.device != mel.device:
+            raise ValueError("the vocoder's parameters are not on the mel's device")
+        dev = mel.device
+        packed = self._packed()
+        imgs, blocks = iter(packed[0]), iter(packed[1])
+        u_, r_, s_, t_, a_ = bufs["u"], bufs["r"], bufs["s"], bufs["t"], bufs["a"]
+        K, ch = len(self.resblock_kernel_sizes), self.padded_channels
+        go = lambda *a, **k: self._launch(dev, n_frames, B, *a, **k)  # noqa: E731
+        act = lambda L, mul, X, C: self._snake(dev, n_frames, B, L, mul, X, next(blocks), a_, C)  # noqa: E731
+        L, mul, C = F, 1, ch[0]
+        go(L, mul, mel, next(imgs), s_, self.n_mel_channels, C, 7, 1, 1.0, mel.stride(0) if B > 1 else max(mel.stride(0), F), L * C, C,
+           x_sc=mel.stride(1) if self.n_mel_channels > 1 else max(mel.stride(1), F), x_mel=1)
+        for i, u in enumerate(self.upsample_rates):
+            Cn = ch[i + 1]
+            go(L, mul, s_, next(imgs), u_, C, u * Cn, 3, 1, 1.0, L * C, L * u * Cn, u * Cn)      # no activation in front
+            L, mul, C = L * u, mul * u, Cn
+            sb = L * C
+            for j, (k, ds) in enumerate(zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes)):
+                src = u_
+                for m, d in enumerate(ds):
+                    last = m == len(ds) - 1
+                    tail = dict(res=src, acc=s_ if j else None, scale=1.0 / K if j == K - 1 else 1.0) if last else dict(res=src)
+                    dst = s_ if last else r_                               # X is a: Y may alias res
+                    act(L, mul, src, C)
+                    if self.resblock == "1":
+                        go(L, mul, a_, next(imgs), t_, C, C, k, d, 1.0, sb, sb, C, x_bf16=1)
+                        act(L, mul, t_, C)
+                        go(L, mul, a_, next(imgs), dst, C, C, k, 1, 1.0, sb, sb, C, x_bf16=1, **tail)
+                    else:
+                        go(L, mul, a_, next(imgs), dst, C, C, k, d, 1.0, sb, sb, C, x_bf16=1, **tail)
+                    src = dst
+        act(L, mul, s_, C)
+        go(L, mul, a_, next(imgs), wav, C, 1, 7, 1, 1.0, L * C, wav.stride(0), 1, x_bf16=1, tanh=int(self.use_tanh_at_final))
+        if not self.use_tanh_at_final:
+            wav.clamp_(-1.0, 1.0)
+        return wav

@@ -400,7 +400,9 @@ class Synthesizer:
     max_frames, so a call of short utterances pays the loop of the capacity (tiles behind an utterance's end only write zeros).
     vocoder=audio.HiFiGAN puts the neural generator there instead (vocoder_iters is ignored): wav_static
     [batch, U max_frames] with U the product of its upsample rates, voc_bufs = HiFiGAN.workspace's buffers as static buffers
-    (14 batch max_frames W + 4 batch U max_frames bytes, W = 8192 for V1), captured_entries grows by vocoder.launches."""
+    (14 batch max_frames W + 4 batch U max_frames bytes, W = 8192 for V1), captured_entries grows by vocoder.launches.  An
+    audio.BigVGAN is an audio.HiFiGAN here: the vocoder names its buffers (buffer_spec: one more bf16 stream, 18
+    batch max_frames W bytes at its padded width) and its launches count both of its kernels."""
 
     RING = 8
 
@@ -418,7 +420,7 @@ class Synthesizer:
                                      f"model writes {gen.out_channels}")
                 vocoder_iters = 0
             elif not isinstance(vocoder, audio.GriffinLim) or not isinstance(vocoder.stft, audio.TacotronSTFT):
-                raise TypeError("compile_synthesis(vocoder=) takes an audio.HiFiGAN, or an audio.GriffinLim built over an audio.TacotronSTFT")
+                raise TypeError("compile_synthesis(vocoder=) takes an audio.HiFiGAN (or audio.BigVGAN), or an audio.GriffinLim built over an audio.TacotronSTFT")
             elif vocoder.stft.mel_basis.device != next(gen.parameters()).device or vocoder.istft.inverse_basis.device != next(gen.parameters()).device:
                 raise ValueError("compile_synthesis(vocoder=): the vocoder's buffers are not on the model's device")
             elif vocoder.stft.mel_basis.shape[0] != gen.out_channels:
@@ -513,15 +515,15 @@ class Synthesizer:
         # ---- the waveform back end: magnitudes, the spectrum workspace, the samples, the frame counts the mel has
         self.wav_static = self.voc_bufs = self.n_frames = self._voc_images = None
         if self.neural:
-            # three fp32 streams and one bf16 of B max_frames W elements (HiFiGAN.workspace) and the samples
+            # the vocoder names its streams of B max_frames W elements (buffer_spec) and the samples
             self.n_frames = self._static(B, torch.int32)
             E = B * Ty * vocoder._width()
             if E >= 2 ** 31:
                 raise ValueError(f"compile_synthesis(vocoder=): batch * max_frames * {vocoder._width()} = {E} elements per buffer, 2^31 or more")
             self.wav_static = self._static(B * vocoder.hop_length * Ty, torch.float32).view(B, vocoder.hop_length * Ty)
-            self.voc_bufs = dict(u=self._static(E, torch.float32), r=self._static(E, torch.float32), s=self._static(E, torch.float32),
-                                 t=self._static(E, vocoder.t_dtype), wav=self.wav_static)
-            self._voc_images = vocoder.images()                          # kept: the graph holds their addresses
+            self.voc_bufs = {name: self._static(E, dtype) for name, dtype in vocoder.buffer_spec()}
+            self.voc_bufs["wav"] = self.wav_static
+            self._voc_images = vocoder.held()                            # kept: the graph holds their addresses
         elif vocoder is not None:
             self.n_frames = self._static(B, torch.int32)
             self.wav_static = self._static(B * 256 * (Ty - 1), torch.float32).view(B, 256 * (Ty - 1))

@@ -1174,6 +1174,38 @@ int gt_voc_tile_positions(void);
 int gt_voc_k_chunk(int Cin);
 size_t gt_voc_lds_bytes(int Cin, int taps, int dil);
 
+/* ---- BigVGAN's anti-aliased snake activation (csrc/voc_snake.hip): one memory-bound kernel in front of gt_voc_conv ------
+ * gt_voc_snake: Activation1d (2x up-sampling FIR -> snake -> 2x down-sampling FIR, per channel) of a ragged batch on dense channels-last
+ * activations, fp32 in, bf16 out (the x_bf16 operand of the next gt_voc_conv), every utterance on its own [0, len_b):
+ *   u[2q]   = 2 sum_{j < 6} fu[11 - 2j] x[cl(q - 3 + j)]      u[2q + 1] = 2 sum_{j < 6} fu[10 - 2j] x[cl(q - 2 + j)]      cl(i) = min(max(i, 0), len_b - 1)
+ *   v[i]    = u[i] + ib[c] sin^2(a[c] u[i])
+ *   Y[b, t, c] = bf16( sum_{k < 12} fd[k] v[min(max(2t + k - 5, 0), 2 len_b - 1)] )                                        t < len_b
+ *   len_b = min(max(n_frames[b], 0) len_mul, L_cap).  x is replicated at the utterance's ends and so is v: v's INDEX is clamped, v is
+ *   not evaluated outside [0, 2 len_b).  Nothing at or behind len_b is read (whatever lies there); Y at positions [len_b, L_cap) is
+ *   written as bf16 zero; nothing beyond L_cap is touched.  The host never reads n_frames.
+ *   X        fp32 [B, L_cap, C], element (b, t, c) at X[b x_stride_b + t C + c].
+ *   Y        bf16 [B, L_cap, C], element (b, t, c) at Y[b y_stride_b + t C + c]; Y may not alias X.
+ *   P        fp32 parameter block of 2 C + 24 values: [C] a = alpha', [C] ib = 1 / (beta' + 1e-9), [12] fu (the up-sampling filter),
+ *            [12] fd (the down-sampling filter).  Built by the caller (exp of log-scale parameters, the reciprocal): the kernel evaluates
+ *            no exp and no division.
+ * Arithmetic is fp32: fmaf chains with j ascending for u and k ascending for y, sin by the device library's sinf, one rounding to
+ * nearest even to bf16.  The order depends on (t, c) alone: a batch row is bit-identical to the utterance computed alone, in a buffer
+ * of any capacity.  Asynchronous, no allocation, no atomics, no LDS, capturable in a graph; the grid is sized by L_cap: a workgroup
+ * owns gt_voc_snake_tile_positions() positions x 32 channels, a thread a strip of 16 positions of two channels.
+ * Refusals, before any launch and in this order: args or X / Y / P / n_frames NULL; B, L_cap, C or len_mul <= 0; x_stride_b or
+ * y_stride_b < L_cap C; Y == X: GT_E_INVAL.  C no multiple of 16, B > 65535, B L_cap C >= 2^31: GT_E_UNSUPPORTED.  X not 16-byte, Y not
+ * 8-byte, P or n_frames not 4-byte aligned, x_stride_b or y_stride_b no multiple of 8: GT_E_ALIGN. */
+typedef struct gt_voc_snake_args {
+  const float* X; int64_t x_stride_b;
+  const float* P;
+  void* Y; int64_t y_stride_b;
+  int len_mul; const int32_t* n_frames;
+  int B; int L_cap; int C;
+} gt_voc_snake_args;
+int gt_voc_snake(const gt_voc_snake_args* args, void* stream);
+int gt_voc_snake_args_size(void);               /* sizeof(gt_voc_snake_args): lets a binding check its mirror of the struct */
+int gt_voc_snake_tile_positions(void);
+
 #ifdef __cplusplus
 }
 #endif
