@@ -88,3 +88,5 @@ static inline int gt_launch_status(const char* what) {
   fprintf(stderr, "[glowtts_hip] %s: HIP error %d (%s)\n", what, (int)e, hipGetErrorString(e));
   return -4;
 }
+#define GT_ST(s) static_cast<hipStream_t>(s)
+#define GT_RET() return gt_launch_status(__func__)

@@ -251,7 +251,6 @@ __global__ __launch_bounds__(256) void gt_dds_layer_bwd_kernel(
   }
 }
 
-#define GT_ST(s) static_cast<hipStream_t>(s)
 inline int tiles(int R) { return (R + TILE - 1) / TILE; }
 inline bool pow3(int d) { if (d <= 0) return false; while (d % 3 == 0) d /= 3; return d == 1; }
 

@@ -509,8 +509,6 @@ __global__ __launch_bounds__(192 * CAG_PH) void gt_cond_affine_grads_kernel(cons
 }  // namespace
 
 
-#define GT_ST(s) static_cast<hipStream_t>(s)
-#define GT_RET() return gt_launch_status(__func__)
 
 extern "C" int gt_squeeze_rows_f32(const float* y, float* rows, const int32_t* len_sq, int B, int C, int Ty, int Tp,
                                    const int32_t* row0, void* stream)

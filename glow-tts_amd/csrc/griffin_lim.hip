@@ -322,7 +322,6 @@ __global__ __launch_bounds__(256, 2) void gt_istft_kernel(const float* __restric
   }
 }
 
-#define GT_ST(s) static_cast<hipStream_t>(s)
 
 }  // namespace
 

@@ -163,7 +163,6 @@ __global__ __launch_bounds__(256, 2) void gt_mel_front_kernel(const void* __rest
   }
 }
 
-#define GT_ST(s) static_cast<hipStream_t>(s)
 
 }  // namespace
 

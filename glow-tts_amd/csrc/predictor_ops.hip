@@ -756,8 +756,6 @@ __global__ __launch_bounds__(256) void gt_rows_split3_kernel(const void* __restr
   o[c] = hi; o[C + c] = hi; o[2 * C + c] = f2bf(v - bf2f(hi));
 }
 
-#define GT_ST(s) static_cast<hipStream_t>(s)
-#define GT_RET() return gt_launch_status(__func__)
 inline int wg_rows(int R) { return (R + 4 * RPW - 1) / (4 * RPW); }
 inline int wg_rows_b(int R) { return (R + 4 * RPB - 1) / (4 * RPB); }
 

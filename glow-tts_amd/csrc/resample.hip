@@ -131,7 +131,6 @@ __global__ __launch_bounds__(NT) void gt_resample_kernel(const void* __restrict_
   }
 }
 
-#define GT_ST(s) static_cast<hipStream_t>(s)
 
 }  // namespace
 

@@ -7,8 +7,6 @@
 #include "internal.h"
 
 #define HALO GT_HALO
-#define GT_ST(s) static_cast<hipStream_t>(s)
-#define GT_RET() return gt_launch_status(__func__)
 
 #define SF_TX_MAX 512        // tokens per utterance (gt_prior_expand's and gt_mas_f32's limit)
 #define SF_C_MAX 80          // mel channels

@@ -8,8 +8,6 @@
 #include "internal.h"
 
 #define HALO GT_HALO
-#define GT_ST(s) static_cast<hipStream_t>(s)
-#define GT_RET() return gt_launch_status(__func__)
 
 // One thread per (row, column pair).  The row's utterance comes from a binary search over row0 (uniform rows: a division).
 // CALL: seed / scale come from the gt_synth_call_ext block in device memory; the only difference between the two instantiations.

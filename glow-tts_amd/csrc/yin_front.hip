@@ -251,7 +251,6 @@ __global__ __launch_bounds__(NT) void gt_yin_f0_kernel(const void* __restrict__ 
   }
 }
 
-#define GT_ST(s) static_cast<hipStream_t>(s)
 
 }  // namespace
 

@@ -358,7 +358,7 @@ class _DurationLossFn(torch.autograd.Function):
 
 class _AlignLossFn(torch.autograd.Function):
     """_PriorExpandFn + _MleLossFn + _DurationLossFn + their sum as ONE node: three launches forward and backward together
-    (gt_align_loss_fwd / _finish / _bwd, csrc/encoder_ops.hip) instead of twelve, bit-identical to them.  Differentiable inputs:
+    (gt_align_loss_fwd / _finish / _bwd, csrc/align_loss.hip) instead of twelve, bit-identical to them.  Differentiable inputs:
     z, x_m, x_logs (None = mean_only), logdet, logw (None: the duration term is not part of this node).  -> (total, l_mle, z_m,
     z_logs or None, l_length or None); only `total` = l_mle + sum(l_length) carries a gradient."""
 

@@ -1,6 +1,6 @@
-"""TEST INFRASTRUCTURE ONLY — float64 restatement of the fp32 kernels between the decoder and the loss (csrc/encoder_ops.hip:
-gt_logp_f32, gt_mle_sums / _finish / _bwd, gt_duration_loss_fwd / _bwd, gt_prior_expand / _bwd, gt_embedding_fwd / _bwd,
-gt_rows_add_cond, gt_rows_utt_sum, gt_length_mask) and of the layout kernels (csrc/flow_ops.hip: gt_rows_from_bct, gt_bct_from_rows,
+"""TEST INFRASTRUCTURE ONLY — float64 restatement of the fp32 kernels between the decoder and the loss (csrc/align_loss.hip:
+gt_logp_f32, gt_mle_sums / _finish / _bwd, gt_duration_loss_fwd / _bwd, gt_prior_expand / _bwd, gt_length_mask; csrc/encoder_ops.hip:
+gt_embedding_fwd / _bwd, gt_rows_add_cond, gt_rows_utt_sum) and of the layout kernels (csrc/flow_ops.hip: gt_rows_from_bct, gt_bct_from_rows,
 gt_squeeze_rows_f32, gt_unsqueeze_rows_f32, gt_rows_f32_to_bf16, gt_rows_add_bf16), each written from the comment above its kernel.
 
 The rule, gamma, RHO, FAST_FN, check and check_with_control are oracle/rows64.py's.  Arithmetic operators return the float64

@@ -118,7 +118,7 @@ def dur_defects(B, Tx):
 
 
 # ----------------------------------------------------------------------------- gt_prior_expand / _bwd
-PRIOR_SHAPES = [(1, 1), (3, 200), (150, 447), (512, 640)]
+PRIOR_SHAPES = [(1, 1), (3, 200), (150, 447), (512, 640), (513, 640)]      # 512: the last Tx of acc[4][512]; 513: the first in dynamic LDS
 PRIOR_B, PRIOR_C = 2, 3                                                      # B C = 6: the last workgroup of 4 waves holds 2
 
 

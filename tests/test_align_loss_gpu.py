@@ -1,4 +1,4 @@
-"""The alignment -> loss chain in three launches (csrc/encoder_ops.hip: gt_align_loss_fwd / _finish / _bwd) against the chain of
+"""The alignment -> loss chain in three launches (csrc/align_loss.hip: gt_align_loss_fwd / _finish / _bwd) against the chain of
 entries it replaces — gt_prior_expand, gt_mle_sums, gt_mle_finish, gt_duration_loss_fwd, torch.sum and the add; gt_mle_bwd,
 gt_prior_expand_bwd, gt_duration_loss_bwd — BIT for bit on the same operands, against float64 (oracle/loss64.py) under the bounds
 tests/test_loss_kernels_fp64_gpu.py holds the unfused kernels to, its refusals, and one eager Trainer step with the switch on

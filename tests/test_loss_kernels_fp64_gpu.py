@@ -1,5 +1,6 @@
-"""The fp32 kernels between the decoder and the loss (csrc/encoder_ops.hip: gt_logp_f32, gt_mle_sums / _finish / _bwd,
-gt_duration_loss_fwd / _bwd, gt_prior_expand / _bwd, gt_embedding_fwd / _bwd, gt_rows_add_cond, gt_rows_utt_sum, gt_length_mask)
+"""The fp32 kernels between the decoder and the loss (csrc/align_loss.hip: gt_logp_f32, gt_mle_sums / _finish / _bwd,
+gt_duration_loss_fwd / _bwd, gt_prior_expand / _bwd, gt_length_mask; csrc/encoder_ops.hip: gt_embedding_fwd / _bwd, gt_rows_add_cond,
+gt_rows_utt_sum)
 against float64 on hand-made operands, under the rule of oracle/rows64.py with the operators of oracle/loss64.py.  The shapes,
 operands and planted defects are oracle/loss_cases.py's, the ones tests/test_loss64.py validates on the float32 twin.
 
