@@ -223,6 +223,16 @@ PROTOTYPES = {
     "gt_voc_snake": (STATUS, [c_void_p, c_void_p]),
     "gt_voc_snake_args_size": (c_int, []),
     "gt_voc_snake_tile_positions": (c_int, []),
+    "gt_vocos_norm": (STATUS, [c_void_p, c_void_p]),
+    "gt_vocos_norm_args_size": (c_int, []),
+    "gt_vocos_norm_tile_positions": (c_int, []),
+    "gt_vocos_mlp": (STATUS, [c_void_p, c_void_p]),
+    "gt_vocos_mlp_args_size": (c_int, []),
+    "gt_vocos_tile_positions": (c_int, []),
+    "gt_vocos_hidden_chunk": (c_int, []),
+    "gt_vocos_mlp_lds_bytes": (c_size_t, [c_int]),
+    "gt_vocos_polar": (STATUS, [c_void_p, c_void_p]),
+    "gt_vocos_polar_args_size": (c_int, []),
 }
 c_void_p = ctypes.c_void_p
 
@@ -370,13 +380,34 @@ class VocSnakeArgs(ctypes.Structure):
                 ("n_frames", c_void_p), ("B", c_int), ("L_cap", c_int), ("C", c_int)]
 
 
+class VocosNormArgs(ctypes.Structure):
+    """struct gt_vocos_norm_args (include/glowtts_hip.h); its size is checked against gt_vocos_norm_args_size() (tests/test_vocos_cabi.py)"""
+    _fields_ = [("X", c_void_p), ("x_stride_b", c_i64), ("wd", c_void_p), ("bd", c_void_p), ("g", c_void_p), ("be", c_void_p),
+                ("Y", c_void_p), ("y_stride_b", c_i64), ("n_frames", c_void_p), ("B", c_int), ("L_cap", c_int), ("C", c_int),
+                ("y_bf16", c_int), ("eps", c_float)]
+
+
+class VocosMlpArgs(ctypes.Structure):
+    """struct gt_vocos_mlp_args (include/glowtts_hip.h); its size is checked against gt_vocos_mlp_args_size() (tests/test_vocos_cabi.py)"""
+    _fields_ = [("A", c_void_p), ("a_stride_b", c_i64), ("W1", c_void_p), ("b1", c_void_p), ("W2", c_void_p), ("b2", c_void_p),
+                ("R", c_void_p), ("r_stride_b", c_i64), ("Y", c_void_p), ("y_stride_b", c_i64), ("U", c_void_p), ("u_stride_b", c_i64),
+                ("n_frames", c_void_p), ("B", c_int), ("L_cap", c_int), ("C", c_int), ("H", c_int)]
+
+
+class VocosPolarArgs(ctypes.Structure):
+    """struct gt_vocos_polar_args (include/glowtts_hip.h); its size is checked against gt_vocos_polar_args_size() (tests/test_vocos_cabi.py)"""
+    _fields_ = [("O", c_void_p), ("o_stride_b", c_i64), ("n_frames", c_void_p), ("spec", c_void_p), ("B", c_int), ("F_max", c_int),
+                ("n_fft", c_int)]
+
+
 # mirror -> its C struct in include/glowtts_hip.h (tests/test_cabi.py compares every size and field offset with a C compiler's)
 C_STRUCTS = {PackDesc: "gt_pack_desc", StepCopy: "gt_step_copy", StepCtx: "gt_step_ctx", StepInputsArgs: "gt_step_inputs_args",
              PartialsJob: "gt_partials_job", PartialsArgs: "gt_partials_args", StepZeroArgs: "gt_step_zero_args",
              WnStackFwdArgs: "gt_wn_stack_fwd_args", WnStackBwdArgs: "gt_wn_stack_bwd_args", BoundaryFwdArgs: "gt_boundary_fwd_args",
              BoundaryBwdArgs: "gt_boundary_bwd_args", BoundaryRevArgs: "gt_boundary_rev_args", SynthPriorArgs: "gt_synth_prior_args",
              SynthCall: "gt_synth_call", SynthCallExt: "gt_synth_call_ext", VocConvArgs: "gt_voc_conv_args",
-             VocSnakeArgs: "gt_voc_snake_args"}
+             VocSnakeArgs: "gt_voc_snake_args", VocosNormArgs: "gt_vocos_norm_args", VocosMlpArgs: "gt_vocos_mlp_args",
+             VocosPolarArgs: "gt_vocos_polar_args"}
 
 
 def fill_args(cls, **kw):

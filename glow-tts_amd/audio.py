@@ -33,6 +33,10 @@ run by ONE HIP kernel (csrc/mel_front.hip: gt_mel_pack once, gt_mel_spectrogram 
                     the stand-alone kernel gt_voc_snake (csrc/voc_snake.hip) in front of every convolution but the
                     transposed ones; the original parameter tree and checkpoints; a 24-channel stage runs padded to 32.
 
+  Vocos             the published Vocos generator (ConvNeXt backbone at frame rate, iSTFT head): csrc/vocos.hip's gt_vocos_norm,
+                    gt_vocos_mlp (the block's MLP with the hidden activation kept on the chip) and gt_vocos_polar next to gt_voc_conv and
+                    gt_istft; the published parameter tree (`load_vocos_state`, `from_config`), the capacity-sized form.
+
 Waveforms are fp32 in [-1, 1] or int16 (scaled by 1/32768 in the kernel = the reference's audio / max_wav_value).  There is no CPU
 path: a CPU tensor raises."""
 import numpy as np
@@ -1227,3 +1231,237 @@ class BigVGAN(HiFiGAN):
         if not self.use_tanh_at_final:
             wav.clamp_(-1.0, 1.0)
         return wav
+
+
+# ---- Vocos: a frame-rate ConvNeXt backbone and an iSTFT head on csrc/vocos.hip, gt_voc_conv and gt_istft -------------
+VOCOS_EPS = 1e-6                     # every LayerNorm of the published model
+VOCOS_BINS = 513                     # n_fft / 2 + 1 of the one geometry gt_istft implements
+
+
+class _ConvNeXtBlock(nn.Module):
+    """parameter holder under the published names: dwconv, norm, pwconv1, pwconv2, gamma"""
+
+    def __init__(self, dim, intermediate_dim, layer_scale):
+        super().__init__()
+        self.dwconv = nn.Conv1d(dim, dim, 7, padding=3, groups=dim)
+        self.norm = nn.LayerNorm(dim, eps=VOCOS_EPS)
+        self.pwconv1 = nn.Linear(dim, intermediate_dim)
+        self.pwconv2 = nn.Linear(intermediate_dim, dim)
+        self.gamma = nn.Parameter(layer_scale * torch.ones(dim))
+
+
+class _VocosBackbone(nn.Module):
+    def __init__(self, input_channels, dim, intermediate_dim, num_layers):
+        super().__init__()
+        self.embed = nn.Conv1d(input_channels, dim, 7, padding=3)
+        self.norm = nn.LayerNorm(dim, eps=VOCOS_EPS)
+        self.convnext = nn.ModuleList(_ConvNeXtBlock(dim, intermediate_dim, 1.0 / num_layers) for _ in range(num_layers))
+        self.final_layer_norm = nn.LayerNorm(dim, eps=VOCOS_EPS)
+
+
+class _VocosHead(nn.Module):
+    def __init__(self, dim, n_fft):
+        super().__init__()
+        self.out = nn.Linear(dim, n_fft + 2)
+
+
+def fold_layer_scale(gamma, w2, b2):
+    """ConvNeXt's layer scale folded into its second Linear: (gamma[:, None] w2, gamma b2) formed in float64 and rounded to fp32 once"""
+    g = gamma.detach().double()
+    return (g[:, None] * w2.detach().double()).float(), (g * b2.detach().double()).float()
+
+
+class Vocos(nn.Module):
+    """The published Vocos generator (Siuzdak 2023: `VocosBackbone` + `ISTFTHead`, padding="center") from log-mel to waveform.  The whole
+    network runs at FRAME rate, every utterance of a ragged batch ON ITS OWN: utterance b is Vocos(mel[b:b+1, :, :F_b]), every
+    convolution zero-padded at that utterance's own ends; F_b frames give 256 (F_b - 1) samples (none below 2 frames: gt_istft's rule).
+
+      embed (k 7, gt_voc_conv on the channel-major mel) -> LayerNorm (gt_vocos_norm) -> per block: depthwise k 7 + LayerNorm
+      (gt_vocos_norm, bf16 out), Linear -> GELU -> Linear, layer scale, residual (gt_vocos_mlp, the hidden activation never in global
+      memory) -> LayerNorm (gt_vocos_norm) -> Linear to 513 log-magnitudes + 513 phases (gt_voc_conv, taps 1) -> gt_vocos_polar ->
+      gt_istft: `launches` = 6 + 2 num_layers, 22 for the published model.
+
+    Parameters are fp32 under the published names (backbone.embed, backbone.norm, backbone.convnext.{i}.dwconv / .norm / .pwconv1 /
+    .pwconv2 / .gamma, backbone.final_layer_norm, head.out); `load_vocos_state` takes a published checkpoint.  Operands of the matrix
+    products are bf16 (the packed images; the mel, every block's normalised input, the hidden activation, the head's input),
+    accumulation, the residual stream, the LayerNorms and the head's nonlinearity fp32, the inverse STFT exact fp32.
+    Refused with ValueError: padding="same", a conditional backbone (adanorm_num_embeddings), n_fft / hop_length other than 1024 / 256,
+    a dim other than 128 / 256 / 512, an intermediate_dim that is no multiple of gt_vocos_hidden_chunk() or above 2048."""
+
+    def __init__(self, input_channels=80, dim=512, intermediate_dim=1536, num_layers=8, n_fft=1024, hop_length=256, padding="center",
+                 adanorm_num_embeddings=None):
+        super().__init__()
+        input_channels, dim, intermediate_dim, num_layers = int(input_channels), int(dim), int(intermediate_dim), int(num_layers)
+        if padding != "center":
+            raise ValueError(f'Vocos: padding is "center" (torch.istft(center=True)), got {padding!r}')
+        if adanorm_num_embeddings:
+            raise ValueError("Vocos: a conditional backbone (AdaLayerNorm, the EnCodec variant) is not supported")
+        if (int(n_fft), int(hop_length)) != (1024, 256):
+            raise ValueError(f"Vocos: the inverse STFT takes n_fft = 1024, hop_length = 256, got {n_fft} / {hop_length}")
+        if input_channels < 1 or num_layers < 1:
+            raise ValueError("Vocos: input_channels and num_layers are positive")
+        chunk = call.gt_vocos_hidden_chunk()
+        if not call.gt_vocos_mlp_lds_bytes(dim):
+            raise ValueError(f"Vocos: dim is 128, 256 or 512, got {dim}")
+        if intermediate_dim < chunk or intermediate_dim % chunk or intermediate_dim > 2048:
+            raise ValueError(f"Vocos: intermediate_dim is a multiple of {chunk} up to 2048, got {intermediate_dim}")
+        self.input_channels, self.dim, self.intermediate_dim, self.num_layers = input_channels, dim, intermediate_dim, num_layers
+        self.n_fft, self.hop_length, self.padding = 1024, 256, padding
+        self.padded_channels = _pad16(input_channels)
+        self.backbone = _VocosBackbone(input_channels, dim, intermediate_dim, num_layers)
+        self.head = _VocosHead(dim, self.n_fft)
+        object.__setattr__(self, "istft", InverseSTFT())                       # not a submodule: the state dict keeps the published names
+        self.launches = 6 + 2 * num_layers
+        self._images = _Cached()
+        for p in self.parameters():
+            p.requires_grad_(False)
+
+    def _apply(self, fn, *args, **kw):
+        super()._apply(fn, *args, **kw)
+        self.istft._apply(fn, *args, **kw)
+        return self
+
+    @classmethod
+    def from_config(cls, cfg):
+        """from the published config.yaml as a dict: the init_args of its `backbone` and `head` entries (the feature extractor's
+        n_mels is the backbone's input_channels)"""
+        b, h = dict(cfg["backbone"].get("init_args", {})), dict(cfg["head"].get("init_args", {}))
+        if "dim" in h and "dim" in b and int(h["dim"]) != int(b["dim"]):
+            raise ValueError(f"Vocos: the head's dim {h['dim']} is not the backbone's {b['dim']}")
+        return cls(input_channels=b.get("input_channels", 80), dim=b.get("dim", 512), intermediate_dim=b.get("intermediate_dim", 1536),
+                   num_layers=b.get("num_layers", 8), n_fft=h.get("n_fft", 1024), hop_length=h.get("hop_length", 256),
+                   padding=h.get("padding", "same"), adanorm_num_embeddings=b.get("adanorm_num_embeddings"))
+
+    def load_vocos_state(self, sd):
+        """a published checkpoint's state dict: feature_extractor.* and head.istft.window are dropped, the rest is loaded strictly"""
+        keep = {k: t.detach().float() for k, t in sd.items() if not k.startswith("feature_extractor.") and k != "head.istft.window"}
+        return self.load_state_dict(keep, strict=True)
+
+    # ---- the images: everything a run reads, per parameter version ----------------------------------------------------------------------
+    def images(self):
+        """dict(embed=(image, bias), norm=(g, b), blocks=[dict(wd, bd, g, b, W1, b1, W2, b2)], final=(g, b), head=(image, bias)): bf16
+        images in gt_voc_conv's fragment order (the embedding's input channels zero-padded to a multiple of 16, the layer scale folded
+        into W2 / b2), fp32 vectors; rebuilt when any parameter's (data_ptr, _version) changes"""
+        params = list(self.parameters())
+
+        def build():
+            f = lambda t: t.detach().float().contiguous()  # noqa: E731
+            bb = self.backbone
+            we = bb.embed.weight.detach().float()
+            out = dict(embed=(voc_pack(_padded(we, (self.dim, self.padded_channels, 7))), f(bb.embed.bias)),
+                       norm=(f(bb.norm.weight), f(bb.norm.bias)), blocks=[],
+                       final=(f(bb.final_layer_norm.weight), f(bb.final_layer_norm.bias)),
+                       head=(voc_pack(self.head.out.weight.detach().float()[:, :, None]), f(self.head.out.bias)))
+            for blk in bb.convnext:
+                w2, b2 = fold_layer_scale(blk.gamma, blk.pwconv2.weight, blk.pwconv2.bias)
+                out["blocks"].append(dict(wd=f(blk.dwconv.weight).view(self.dim, 7), bd=f(blk.dwconv.bias), g=f(blk.norm.weight),
+                                          b=f(blk.norm.bias), W1=voc_pack(blk.pwconv1.weight.detach().float()[:, :, None]),
+                                          b1=f(blk.pwconv1.bias), W2=voc_pack(w2[:, :, None]), b2=b2.contiguous()))
+            return out
+        return self._images.get(params, build)
+
+    def held(self):
+        """what a captured graph of run() reads besides the buffers: its holder keeps it alive (the vocoder drops it when it repacks)"""
+        return self.images(), self.istft._image()
+
+    # ---- capacity-sized form ------------------------------------------------------------------------------------------------------------
+    def buffer_spec(self, B, F_max):
+        """[(name, dtype, elements)] of the buffers a run takes next to wav [B, 256 (F_max - 1)]: the fp32 residual stream x [B, F, C],
+        the bf16 operand a [B, F, C], the head's fp32 output o [B, F, 1026] and the spectrum workspace spec"""
+        E = B * F_max * self.dim
+        return [("x", torch.float32, E), ("a", torch.bfloat16, E), ("o", torch.float32, B * F_max * 2 * VOCOS_BINS),
+                ("spec", torch.float32, call.gt_gl_spec_bytes(B, F_max) // 4)]
+
+    def workspace_bytes(self, B, F_max):
+        """6 B F C + 4104 B F + 4100 B Fp + 1024 B (F - 1) with Fp = F rounded up to 64: 12.3 KB per frame at C = 512"""
+        return sum(n * torch.empty(0, dtype=dt).element_size() for _, dt, n in self.buffer_spec(B, F_max)) + 4 * B * 256 * (F_max - 1)
+
+    def workspace(self, B, F_max, device):
+        """the buffers of one run at capacity (B utterances of up to F_max >= 2 frames): buffer_spec's and wav"""
+        if B < 1 or F_max < 2 or B * F_max * 2 * VOCOS_BINS >= 2 ** 31:
+            raise ValueError(f"workspace for {B} x {F_max} frames: B >= 1, F_max >= 2 and B F_max 1026 < 2^31")
+        bufs = {name: torch.empty(n, dtype=dt, device=device) for name, dt, n in self.buffer_spec(B, F_max)}
+        bufs["wav"] = torch.empty(B, 256 * (F_max - 1), dtype=torch.float32, device=device)
+        return bufs
+
+    def run(self, mel, n_frames, bufs):
+        """kernel calls, the capacity-sized form for graph callers: fp32 log-mel [B, input_channels, >= F_max] (any batch / channel pitch,
+        frames contiguous; input_channels a multiple of 16), device int32 [B] frame counts and workspace's buffers (B and F_max are
+        theirs) -> bufs["wav"] [B, 256 (F_max - 1)], row b zero behind its 256 (F_b - 1) samples.  `launches` C-ABI calls; nothing is
+        allocated once the images exist, n_frames is never looked at on the host, every grid is sized by F_max."""
+        if self.input_channels % 16:
+            raise ValueError(f"run takes a mel of a multiple of 16 channels; forward pads the {self.input_channels} of this model")
+        return self._run(mel, n_frames, bufs)
+
+    def _run(self, mel, n_frames, bufs):
+        wav = bufs["wav"]
+        B, F, C, H = wav.shape[0], wav.shape[1] // 256 + 1, self.dim, self.intermediate_dim
+        if not mel.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
+        if mel.dtype != torch.float32 or mel.dim() != 3 or mel.stride(2) != 1:
+            raise ValueError("run takes a device fp32 log-mel [B, n_mel, F] with contiguous frames")
+        if mel.shape[0] != B or mel.shape[1] != self.padded_channels or mel.shape[2] < F:
+            raise ValueError(f"mel {tuple(mel.shape)} does not fit buffers for [{B}, {self.padded_channels}, {F}]")
+        if n_frames.dtype != torch.int32 or n_frames.numel() != B or not n_frames.is_cuda or not n_frames.is_contiguous():
+            raise ValueError("n_frames must be a contiguous int32 [B] on the device")
+        if self.head.out.weight.device != mel.device:
+            raise ValueError("the vocoder's parameters are not on the mel's device")
+        dev, im = mel.device, self.images()
+        st = _lib.current_stream(dev)
+        x, a_, o, spec = bufs["x"], bufs["a"], bufs["o"], bufs["spec"]
+        sb = F * C
+
+        def conv(X, img, Y, Cin, N, taps, x_sb, y_sb, **kw):
+            call.gt_voc_conv(_lib.fill_args(_lib.VocConvArgs, X=X, x_stride_b=x_sb, W=img[0], bias=img[1], res=None, acc=None, Y=Y,
+                                            y_stride_b=y_sb, ldy=N, len_mul=1, n_frames=n_frames, B=B, L_cap=F, Cin=Cin, N=N, taps=taps,
+                                            dil=1, y_bf16=0, tanh_out=0, slope=1.0, scale=1.0, **kw), st)
+
+        def norm(gb, Y, y_bf16, wd=None, bd=None):
+            call.gt_vocos_norm(_lib.fill_args(_lib.VocosNormArgs, X=x, x_stride_b=sb, wd=wd, bd=bd, g=gb[0], be=gb[1], Y=Y, y_stride_b=sb,
+                                              n_frames=n_frames, B=B, L_cap=F, C=C, y_bf16=y_bf16, eps=VOCOS_EPS), st)
+
+        conv(mel, im["embed"], x, self.padded_channels, C, 7, mel.stride(0) if B > 1 else max(mel.stride(0), F), sb,
+             x_stride_c=mel.stride(1) if self.padded_channels > 1 else max(mel.stride(1), F), x_mel=1, x_bf16=0)
+        norm(im["norm"], x, 0)
+        for blk in im["blocks"]:
+            norm((blk["g"], blk["b"]), a_, 1, wd=blk["wd"], bd=blk["bd"])
+            call.gt_vocos_mlp(_lib.fill_args(_lib.VocosMlpArgs, A=a_, a_stride_b=sb, W1=blk["W1"], b1=blk["b1"], W2=blk["W2"], b2=blk["b2"],
+                                             R=x, r_stride_b=sb, Y=x, y_stride_b=sb, U=None, u_stride_b=0, n_frames=n_frames, B=B, L_cap=F,
+                                             C=C, H=H), st)
+        norm(im["final"], a_, 1)
+        conv(a_, im["head"], o, C, 2 * VOCOS_BINS, 1, sb, F * 2 * VOCOS_BINS, x_stride_c=0, x_mel=0, x_bf16=1)
+        call.gt_vocos_polar(_lib.fill_args(_lib.VocosPolarArgs, O=o, o_stride_b=F * 2 * VOCOS_BINS, n_frames=n_frames, spec=spec, B=B,
+                                           F_max=F, n_fft=self.n_fft), st)
+        self.istft.synthesize(spec, n_frames, B, F, out=wav)
+        return wav
+
+    def forward(self, mel, mel_lengths=None, mel_lengths_host=None):
+        """log-mel [B, input_channels, F] -> wav [B, 256 (F - 1)]; with mel_lengths (frames per utterance) the ragged form -> (wav,
+        wav_lengths = 256 max(mel_lengths - 1, 0)), zero behind each utterance.  mel_lengths_host spares the host a look at a device
+        tensor.  A channel count that is no multiple of 16 (the 100-band models) is copied into a zero-padded mel first."""
+        if not mel.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
+        if mel.dim() != 3 or mel.shape[1] != self.input_channels:
+            raise ValueError(f"mel is [B, {self.input_channels}, F], got {tuple(mel.shape)}")
+        if mel.dtype != torch.float32 or mel.stride(2) != 1:
+            mel = mel.float().contiguous()
+        B, _, F = mel.shape
+        if mel_lengths is None:
+            n_frames = torch.full((B,), F, dtype=torch.int32, device=mel.device)
+        else:
+            if mel_lengths_host is None and not mel_lengths.is_cuda:
+                mel_lengths_host = mel_lengths.tolist()
+            if mel_lengths.numel() != B or (mel_lengths_host is not None and (len(mel_lengths_host) != B or max(mel_lengths_host) > F)):
+                raise ValueError(f"frame counts do not fit a [{B}, {self.input_channels}, {F}] mel")
+            n_frames = mel_lengths.to(mel.device, non_blocking=True).to(torch.int32).contiguous()
+        if F < 2 or B == 0:
+            wav = mel.new_zeros(B, 256 * max(F - 1, 0))
+        else:
+            if self.padded_channels != self.input_channels:
+                padded = mel.new_zeros(B, self.padded_channels, F)
+                padded[:, :self.input_channels] = mel
+                mel = padded
+            wav = self._run(mel, n_frames, self.workspace(B, F, mel.device))
+        if mel_lengths is None:
+            return wav
+        return wav, (n_frames.clamp(min=1, max=max(F, 1)) - 1) * 256

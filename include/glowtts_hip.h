@@ -1206,6 +1206,85 @@ int gt_voc_snake(const gt_voc_snake_args* args, void* stream);
 int gt_voc_snake_args_size(void);               /* sizeof(gt_voc_snake_args): lets a binding check its mirror of the struct */
 int gt_voc_snake_tile_positions(void);
 
+/* ---- Vocos vocoder (csrc/vocos.hip): the frame-rate ConvNeXt backbone's kernels and the iSTFT head's nonlinearity ----
+ * One run of L blocks is gt_voc_conv (embedding, taps 7, x_mel), gt_vocos_norm, L x (gt_vocos_norm, gt_vocos_mlp), gt_vocos_norm,
+ * gt_voc_conv (head Linear, taps 1, N = 1026), gt_vocos_polar, gt_istft: 6 + 2 L launches.
+ * Shared by the three: activations are dense channels-last; len_b = min(max(n_frames[b], 0), L_cap), the host never reads n_frames;
+ * nothing at or behind len_b is read (whatever lies there); outputs at [len_b, L_cap) are written as zero and nothing beyond L_cap is
+ * touched; asynchronous, no allocation, no atomics, capturable in a graph, the grid sized by L_cap; the summation order of an element
+ * depends on its position within its utterance and the shape alone: a batch row is bit-identical to the utterance computed alone, in
+ * a buffer of any capacity.
+ *
+ * gt_vocos_norm: depthwise k = 7 convolution (optional) + LayerNorm over the C channels of every position:
+ *   h[b, t, c] = bd[c] + sum_{j < 7} wd[c][j] X[b, t + j - 3, c]   one fp32 fmaf chain, j ascending; a tap outside [0, len_b) contributes
+ *                0 and is not read.  wd == NULL (then bd == NULL too): h = X.
+ *   Y = (h - mean) rstd g[c] + be[c], mean = sum h / C, rstd = rsqrtf(sum (h - mean)^2 / C + eps), fp32.
+ *   X fp32 [B, L_cap, C] (b at x_stride_b elements); Y fp32 or bf16 (y_bf16, round to nearest even) at y_stride_b; wd fp32 [C][7].
+ *   Y may be X only with wd == NULL and fp32 out.  One wave per row, a lane owns the C / 64 channels lane + 64 j;
+ *   gt_vocos_norm_tile_positions() positions per workgroup.
+ * Refusals, before any launch and in this order: args or X / g / be / Y / n_frames NULL; exactly one of wd / bd NULL; B, L_cap or C <= 0;
+ * eps negative or NaN; x_stride_b or y_stride_b < L_cap C; Y == X with wd != NULL or y_bf16: GT_E_INVAL.  C no multiple of 64 or > 512,
+ * B > 65535, B L_cap C >= 2^31: GT_E_UNSUPPORTED.  A pointer not 4-byte (a bf16 Y: 2-byte) aligned: GT_E_ALIGN. */
+typedef struct gt_vocos_norm_args {
+  const float* X; int64_t x_stride_b;
+  const float* wd; const float* bd; const float* g; const float* be;
+  void* Y; int64_t y_stride_b;
+  const int32_t* n_frames;
+  int B; int L_cap; int C; int y_bf16;
+  float eps;
+} gt_vocos_norm_args;
+int gt_vocos_norm(const gt_vocos_norm_args* args, void* stream);
+int gt_vocos_norm_args_size(void);              /* sizeof(gt_vocos_norm_args) */
+int gt_vocos_norm_tile_positions(void);
+
+/* gt_vocos_mlp: a ConvNeXt block's pointwise MLP with its residual; the hidden activation u stays on the chip:
+ *   u[b, t, h] = bf16( gelu( b1[h] + sum_c A[b, t, c] W1[h][c] ) )       gelu(x) = 0.5 x (1 + erff(x / sqrt 2)) in fp32
+ *   Y[b, t, n] = (b2[n] + sum_h u[b, t, h] W2[n][h]) + R[b, t, n]          fp32 MFMA accumulation, c and h ascending in 16-deep steps
+ *   A        bf16 [B, L_cap, C] (gt_vocos_norm's output), b at a_stride_b elements.
+ *   W1, W2   bf16 images of [H, C, 1] and [C, H, 1] in gt_voc_conv's fragment order (taps = 1); the caller folds the layer scale into
+ *            W2 and b2.  b1 fp32 [H], b2 fp32 [C].
+ *   R, Y     fp32 [B, L_cap, C] at r_stride_b / y_stride_b; Y may be R (an element is read and written by the same lane).
+ *   U        optional (tests): bf16 [B, L_cap, H] at u_stride_b, receives u at positions < len_b (nothing else of it is written);
+ *            Y is bit-identical with and without it.
+ * A workgroup owns gt_vocos_tile_positions() positions, keeps their A tile in LDS and walks H in chunks of gt_vocos_hidden_chunk()
+ * units through a double buffer: gt_vocos_mlp_lds_bytes(C) = tile (2 C + 16) + 2 tile (2 chunk + 16) bytes (0 for a C that is refused).
+ * Refusals, before any launch and in this order: args or A / W1 / b1 / W2 / b2 / R / Y / n_frames NULL; B, L_cap, C or H <= 0; a_stride_b,
+ * r_stride_b or y_stride_b < L_cap C; U with u_stride_b < L_cap H; Y == A, U == Y, R or A: GT_E_INVAL.  C not 128, 256 or 512, H no
+ * multiple of the hidden chunk or > 2048, B > 65535, B L_cap max(C, H) >= 2^31: GT_E_UNSUPPORTED.  A, W1 or W2 not 16-byte aligned,
+ * a_stride_b no multiple of 8, b1 / b2 / R / Y / n_frames not 4-byte, U not 8-byte aligned or u_stride_b no multiple of 4: GT_E_ALIGN. */
+typedef struct gt_vocos_mlp_args {
+  const void* A; int64_t a_stride_b;
+  const void* W1; const float* b1; const void* W2; const float* b2;
+  const float* R; int64_t r_stride_b;
+  float* Y; int64_t y_stride_b;
+  void* U; int64_t u_stride_b;
+  const int32_t* n_frames;
+  int B; int L_cap; int C; int H;
+} gt_vocos_mlp_args;
+int gt_vocos_mlp(const gt_vocos_mlp_args* args, void* stream);
+int gt_vocos_mlp_args_size(void);               /* sizeof(gt_vocos_mlp_args) */
+int gt_vocos_tile_positions(void);
+int gt_vocos_hidden_chunk(void);
+size_t gt_vocos_mlp_lds_bytes(int C);
+
+/* gt_vocos_polar: the iSTFT head's nonlinearity into the spectrum workspace gt_istft reads (gt_gl_spec_bytes(B, F_max) bytes, the
+ * fragment order described with gt_gl_polar):
+ *   m = fminf(expf(O[b, f, k]), 100),  (re, im)[k] = m (cosf, sinf)(O[b, f, 513 + k]),  k < 513, f < F_b
+ *   O fp32 [B, F_max, 1026] (b at o_stride_b elements): 513 log-magnitudes, then 513 phases (unbounded: the accurate library functions).
+ *   F_b = min(n_frames[b], F_max), 0 below 2 frames (gt_istft's rule).  ALL of spec is defined: zeros from frame F_b on, the padded
+ *   frames included.  Im of bin 0 is stored as gt_gl_polar stores it; Im of bin 512 is not kept.
+ * Refusals, before any launch and in this order: args or O / n_frames / spec NULL, B outside [1, GT_MEL_MAX_B], F_max outside
+ * [1, GT_MEL_MAX_FRAMES], o_stride_b < 1026 F_max: GT_E_INVAL; n_fft != 1024: GT_E_UNSUPPORTED; O or n_frames not 4-byte, spec not
+ * 16-byte aligned: GT_E_ALIGN. */
+typedef struct gt_vocos_polar_args {
+  const float* O; int64_t o_stride_b;
+  const int32_t* n_frames;
+  float* spec;
+  int B; int F_max; int n_fft;
+} gt_vocos_polar_args;
+int gt_vocos_polar(const gt_vocos_polar_args* args, void* stream);
+int gt_vocos_polar_args_size(void);             /* sizeof(gt_vocos_polar_args) */
+
 #ifdef __cplusplus
 }
 #endif
