@@ -37,6 +37,9 @@ run by ONE HIP kernel (csrc/mel_front.hip: gt_mel_pack once, gt_mel_spectrogram 
                     gt_vocos_mlp (the block's MLP with the hidden activation kept on the chip) and gt_vocos_polar next to gt_voc_conv and
                     gt_istft; the published parameter tree (`load_vocos_state`, `from_config`), the capacity-sized form.
 
+  The three generators meet one contract, `_MelVocoder`: mel_channels, wav_len, buffer_spec(B, F_max), held, and the
+  shared forward / workspace / workspace_bytes / run that compile_synthesis(vocoder=) uses.
+
 Waveforms are fp32 in [-1, 1] or int16 (scaled by 1/32768 in the kernel = the reference's audio / max_wav_value).  There is no CPU
 path: a CPU tensor raises."""
 import numpy as np
@@ -696,6 +699,107 @@ def griffin_lim(magnitudes, stft_fn, n_iters=30, **kw):
     return gl(magnitudes, n_iters=n_iters, **kw)
 
 
+# ---- the neural vocoders' contract: what HiFiGAN, BigVGAN and Vocos share, and all the synthesiser knows of them -------
+def _pad16(c):
+    return (c + 15) // 16 * 16
+
+
+def _padded(t, shape):
+    """t in the leading corner of zeros of `shape`"""
+    if tuple(t.shape) == tuple(shape):
+        return t
+    out = t.new_zeros(shape)
+    out[tuple(slice(0, n) for n in t.shape)] = t
+    return out
+
+
+class _MelVocoder(nn.Module):
+    """A generator from log-mel to waveform that vocodes every utterance of a ragged batch on its own, in eager mode (`forward`) and in
+    its capacity-sized form for graph callers (`buffer_spec` / `workspace` / `run`, synthesis.Synthesizer).  A subclass sets
+      hop_length, min_frames   F frames give wav_len(F) = hop_length (F - (min_frames - 1)) samples, none below min_frames
+      mel_channels             what run takes per frame; forward takes mel_channels - mel_padding and zero-pads
+      launches                 C-ABI calls per run
+    and supplies buffer_spec(B, F_max) (through _check_capacity), held() and _walk(mel, n_frames, bufs, B, F): the kernel calls."""
+
+    min_frames, mel_padding = 1, 0
+
+    def wav_len(self, frames):
+        """samples of an utterance (or a buffer row) of `frames` frames"""
+        return self.hop_length * max(frames - (self.min_frames - 1), 0)
+
+    def check_graph_input(self):
+        """ValueError where run cannot take the mel a synthesis graph writes (the model's own channel count)"""
+
+    def _check_capacity(self, B, F_max, elements, bound):
+        """the one capacity check: `elements`, the largest element index a run forms at (B, F_max), stays below 2^31"""
+        if B < 1 or F_max < self.min_frames or elements >= 2 ** 31:
+            raise ValueError(f"workspace for {B} x {F_max} frames: {bound}")
+
+    def workspace_bytes(self, B, F_max):
+        """bytes of workspace(B, F_max): buffer_spec's buffers and the samples"""
+        return sum(n * dt.itemsize for _, dt, n in self.buffer_spec(B, F_max)) + 4 * B * self.wav_len(F_max)
+
+    def workspace(self, B, F_max, device):
+        """the buffers of one run at capacity (B utterances of up to F_max frames): buffer_spec's by name and wav fp32
+        [B, wav_len(F_max)]"""
+        bufs = {name: torch.empty(n, dtype=dt, device=device) for name, dt, n in self.buffer_spec(B, F_max)}
+        bufs["wav"] = torch.empty(B, self.wav_len(F_max), dtype=torch.float32, device=device)
+        return bufs
+
+    def run(self, mel, n_frames, bufs):
+        """kernel calls, the capacity-sized form for graph callers: fp32 log-mel [B, mel_channels, >= F_max] (any batch / channel pitch,
+        frames contiguous), device int32 [B] frame counts and workspace's buffers (B and F_max are theirs) -> bufs["wav"]
+        [B, wav_len(F_max)], row b zero behind its wav_len(F_b) samples.  `launches` C-ABI calls; nothing is allocated once the images
+        exist, n_frames is never looked at on the host, every grid is sized by F_max."""
+        wav = bufs["wav"]
+        B, F, C = wav.shape[0], wav.shape[1] // self.hop_length + self.min_frames - 1, self.mel_channels
+        if not mel.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
+        if mel.dtype != torch.float32 or mel.dim() != 3 or mel.stride(2) != 1:
+            raise ValueError("run takes a device fp32 log-mel [B, n_mel, F] with contiguous frames")
+        if mel.shape[0] != B or mel.shape[1] != C or mel.shape[2] < F:
+            raise ValueError(f"mel {tuple(mel.shape)} does not fit buffers for [{B}, {C}, {F}]")
+        if n_frames.dtype != torch.int32 or n_frames.numel() != B or not n_frames.is_cuda or not n_frames.is_contiguous():
+            raise ValueError("n_frames must be a contiguous int32 [B] on the device")
+        if next(self.parameters()).device != mel.device:
+            raise ValueError("the vocoder's parameters are not on the mel's device")
+        return self._walk(mel, n_frames, bufs, B, F)
+
+    def forward(self, mel, mel_lengths=None, mel_lengths_host=None):
+        """log-mel [B, mel_channels - mel_padding, F] -> wav [B, wav_len(F)]; with mel_lengths (frames per utterance) the ragged form
+        -> (wav, wav_lengths = wav_len(mel_lengths)), zero behind each utterance.  mel_lengths_host spares the host a look at a device
+        tensor.  With mel_padding (Vocos's 100-band models) the mel is copied into a zero-padded one first."""
+        C = self.mel_channels - self.mel_padding
+        if not mel.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
+        if mel.dim() != 3 or mel.shape[1] != C:
+            raise ValueError(f"mel is [B, {C}, F], got {tuple(mel.shape)}")
+        if mel.dtype != torch.float32 or mel.stride(2) != 1:
+            mel = mel.float().contiguous()
+        B, _, F = mel.shape
+        if mel_lengths is None:
+            n_frames = torch.full((B,), F, dtype=torch.int32, device=mel.device)
+        else:
+            if mel_lengths_host is None and not mel_lengths.is_cuda:
+                mel_lengths_host = mel_lengths.tolist()
+            if mel_lengths.numel() != B or (mel_lengths_host is not None and (len(mel_lengths_host) != B or max(mel_lengths_host) > F)):
+                raise ValueError(f"frame counts do not fit a [{B}, {C}, {F}] mel")
+            n_frames = mel_lengths.to(mel.device, non_blocking=True).to(torch.int32).contiguous()
+        if F < self.min_frames or B == 0:
+            wav = mel.new_zeros(B, self.wav_len(F))
+        else:
+            if self.mel_padding:
+                padded = mel.new_zeros(B, self.mel_channels, F)
+                padded[:, :C] = mel
+                mel = padded
+            wav = _MelVocoder.run(self, mel, n_frames, self.workspace(B, F, mel.device))    # not a subclass's refusal of a padded model
+        if mel_lengths is None:
+            return wav
+        lost = self.min_frames - 1
+        n = n_frames.clamp(min=lost, max=max(F, lost))
+        return wav, (n - lost if lost else n) * self.hop_length
+
+
 # ---- neural vocoder (DESIGN.md 4.23): the HiFi-GAN generator on csrc/hifigan.hip ---------------------------------------------------
 LRELU_SLOPE = 0.1                    # the generator's; conv_post's input takes F.leaky_relu's default 0.01 (a quirk of the original)
 
@@ -749,7 +853,7 @@ class _ResBlock(nn.Module):
             self.convs = nn.ModuleList(mk(d) for d in dilations)
 
 
-class HiFiGAN(nn.Module):
+class HiFiGAN(_MelVocoder):
     """The published HiFi-GAN `Generator` (eval mode, weight norm folded) from log-mel to waveform, every layer by ONE HIP kernel
     (csrc/hifigan.hip: gt_voc_conv), applied to every utterance of a ragged batch ON ITS OWN: utterance b is
     Generator(mel[b:b+1, :, :F_b]), every convolution zero-padded at that utterance's own ends, so its samples do not depend on the
@@ -765,6 +869,8 @@ class HiFiGAN(nn.Module):
     for V1.  Any other (k, u), channels that are no multiple of 16, an even or > 11 resblock kernel: ValueError."""
 
     CHANNEL_MULTIPLE = 16                # of every stage's channel count (BigVGAN pads its images instead: 1)
+    UP_SLOPE = LRELU_SLOPE               # in front of a transposed convolution
+    use_tanh_at_final = True
 
     def __init__(self, resblock="1", upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4), upsample_initial_channel=512,
                  resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5),) * 3, n_mel_channels=80):
@@ -791,6 +897,7 @@ class HiFiGAN(nn.Module):
         self.resblock, self.upsample_rates, self.upsample_kernel_sizes = resblock, rates, kernels
         self.resblock_kernel_sizes, self.resblock_dilation_sizes = rk, rd
         self.n_mel_channels, self.channels = int(n_mel_channels), chans
+        self.mel_channels, self.padded_channels = self.n_mel_channels, [_pad16(c) for c in chans]   # what the kernels run at
         self.hop_length = int(np.prod(rates))                                      # U: samples per frame
         self.conv_pre = nn.Conv1d(self.n_mel_channels, C0, 7, padding=3)
         self.ups = nn.ModuleList(nn.ConvTranspose1d(chans[i], chans[i + 1], k, u, padding=(k - u) // 2)
@@ -828,7 +935,7 @@ class HiFiGAN(nn.Module):
         K = len(self.resblock_kernel_sizes)
         seq = [self.conv_pre]
         for i in range(len(self.ups)):
-            seq.append(self.ups[i])
+            seq += [m for m in self.ups[i].modules() if isinstance(m, nn.ConvTranspose1d)]         # ups[i], or BigVGAN's ups[i][0]
             for j in range(K):
                 rb = self.resblocks[i * K + j]
                 if self.resblock == "1":
@@ -838,59 +945,53 @@ class HiFiGAN(nn.Module):
                     seq += list(rb.convs)
         return seq + [self.conv_post]
 
+    def _conv_images(self):
+        """[(bf16 image, fp32 bias)] per convolution at the padded widths: zero weight rows / columns and bias in the padding (none for
+        a HiFi-GAN), one zero for a convolution without bias"""
+        imgs = []
+        for m in self._convs():
+            w = m.weight.detach().float()
+            b = m.bias.detach().float() if m.bias is not None else w.new_zeros(1)
+            if isinstance(m, nn.ConvTranspose1d):
+                u = m.stride[0]
+                w = _padded(w, (_pad16(w.shape[0]), _pad16(w.shape[1]), w.shape[2]))
+                imgs.append((voc_pack(transposed_as_conv(w, u)), _padded(b, (w.shape[1],)).repeat(u).contiguous()))
+            else:
+                N = w.shape[0] if m is self.conv_post else _pad16(w.shape[0])
+                imgs.append((voc_pack(_padded(w, (N, _pad16(w.shape[1]), w.shape[2]))), _padded(b, (N,)).contiguous()))
+        return imgs
+
     def images(self):
         """[(bf16 image, fp32 bias)] per launch, rebuilt when any parameter's (data_ptr, _version) changes"""
-        params = list(self.parameters())
-
-        def build():
-            out = []
-            for m in self._convs():
-                if isinstance(m, nn.ConvTranspose1d):
-                    u = m.stride[0]
-                    out.append((voc_pack(transposed_as_conv(m.weight.detach().float(), u)), m.bias.detach().float().repeat(u).contiguous()))
-                else:
-                    out.append((voc_pack(m.weight.detach().float()), m.bias.detach().float().contiguous()))
-            return out
-        return self._images.get(params, build)
+        return self._images.get(list(self.parameters()), self._conv_images)
 
     # ---- capacity-sized form ------------------------------------------------------------------------------------------------------------
     def _width(self):
-        U, w = 1, self.channels[0]
+        U, w = 1, self.padded_channels[0]
         for i, u in enumerate(self.upsample_rates):
             U *= u
-            w = max(w, U * self.channels[i + 1])
+            w = max(w, U * self.padded_channels[i + 1])
         return w
-
-    def workspace_bytes(self, B, F_max):
-        """(14 E, resblock "2": 16 E) + 4 B U F_max with E = B F_max W, W = max(C_0, max_i U_i C_i) elements per frame (8192 for V1)"""
-        return (14 if self.resblock == "1" else 16) * B * F_max * self._width() + 4 * B * self.hop_length * F_max
 
     @property
     def t_dtype(self):
         """the fourth buffer: bf16 between a resblock "1"'s two convolutions; for resblock "2" a second fp32 residual stream"""
         return torch.bfloat16 if self.resblock == "1" else torch.float32
 
-    def buffer_spec(self):
-        """[(name, dtype)] of the streams of E = B F_max W elements a run takes next to wav: what workspace and compile_synthesis allocate"""
-        return [("u", torch.float32), ("r", torch.float32), ("s", torch.float32), ("t", self.t_dtype)]
+    def buffer_spec(self, B, F_max):
+        """[(name, dtype, elements)] of the buffers a run takes next to wav [B, U F_max]: three fp32 streams u, r, s (a stage's input,
+        a resblock's residual stream, the resblock sum / the stage's output) and one bf16 t (between a resblock's two convolutions) of
+        E = B F_max W elements each, W = max(C_0, max_i U_i C_i) (U_i the product of the first i rates, C_i the channels behind them:
+        8192 for V1), reused across the stages: 14 E + 4 B U F_max bytes — 2.94 GB + 26 MB for V1 at 32 x 800 frames.  Resblock "2" has
+        no tensor between two convolutions but reads its own residual stream through a halo, which cannot be updated in place: its t
+        is a second fp32 stream (16 E).  B F_max W must stay below 2^31."""
+        E = B * F_max * self._width()
+        self._check_capacity(B, F_max, E, f"B F_max W = {E} must lie in [1, 2^31)")
+        return [("u", torch.float32, E), ("r", torch.float32, E), ("s", torch.float32, E), ("t", self.t_dtype, E)]
 
     def held(self):
         """what a captured graph of run() reads besides the buffers: its holder keeps it alive (the vocoder drops it when it repacks)"""
         return self.images()
-
-    def workspace(self, B, F_max, device):
-        """the buffers of one run at capacity (B utterances of up to F_max frames): three fp32 streams u, r, s (a stage's input, a
-        resblock's residual stream, the resblock sum / the stage's output) and one bf16 t (between a resblock's two convolutions) of
-        E = B F_max W elements each, W = max(C_0, max_i U_i C_i) (U_i the product of the first i rates, C_i the channels behind them:
-        8192 for V1), reused across the stages, and wav fp32 [B, U F_max]: 14 E + 4 B U F_max bytes — 2.94 GB + 26 MB for V1 at 32 x 800
-        frames.  Resblock "2" has no tensor between two convolutions but reads its own residual stream through a halo, which cannot be
-        updated in place: its t is a second fp32 stream (16 E).  B F_max W must stay below 2^31."""
-        E = B * F_max * self._width()
-        if B < 1 or F_max < 1 or E >= 2 ** 31:
-            raise ValueError(f"workspace for {B} x {F_max} frames: B F_max W = {E} must lie in [1, 2^31)")
-        f32 = lambda: torch.empty(E, dtype=torch.float32, device=device)  # noqa: E731
-        return dict(u=f32(), r=f32(), s=f32(), t=torch.empty(E, dtype=self.t_dtype, device=device),
-                    wav=torch.empty(B, self.hop_length * F_max, dtype=torch.float32, device=device))
 
     def _launch(self, dev, n_frames, B, L, mul, X, img, Y, Cin, N, taps, dil, slope, x_sb, y_sb, ldy, x_sc=0, x_mel=0, x_bf16=0,
                 y_bf16=0, res=None, acc=None, scale=1.0, tanh=0):
@@ -899,34 +1000,26 @@ class HiFiGAN(nn.Module):
                            x_bf16=x_bf16, x_mel=x_mel, y_bf16=y_bf16, tanh_out=tanh, slope=slope, scale=scale)
         call.gt_voc_conv(a, _lib.current_stream(dev))
 
-    def run(self, mel, n_frames, bufs):
-        """kernel calls, the capacity-sized form for graph callers: fp32 log-mel [B, n_mel, >= F_max] (any batch / channel pitch, frames
-        contiguous), device int32 [B] frame counts and workspace's buffers (B and F_max are theirs) -> bufs["wav"] [B, U F_max], row b
-        zero behind its U F_b samples.  `launches` gt_voc_conv calls; nothing is allocated once the images exist, n_frames is never
-        looked at on the host, every grid is sized by F_max."""
-        wav = bufs["wav"]
-        B, U = wav.shape[0], self.hop_length
-        F = wav.shape[1] // U
-        if not mel.is_cuda:
-            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
-        if mel.dtype != torch.float32 or mel.dim() != 3 or mel.stride(2) != 1:
-            raise ValueError("run takes a device fp32 log-mel [B, n_mel, F] with contiguous frames")
-        if mel.shape[0] != B or mel.shape[1] != self.n_mel_channels or mel.shape[2] < F:
-            raise ValueError(f"mel {tuple(mel.shape)} does not fit buffers for [{B}, {self.n_mel_channels}, {F}]")
-        if n_frames.dtype != torch.int32 or n_frames.numel() != B or not n_frames.is_cuda or not n_frames.is_contiguous():
-            raise ValueError("n_frames must be a contiguous int32 [B] on the device")
-        if self.conv_pre.weight.device != mel.device:
-            raise ValueError("the vocoder's parameters are not on the mel's device")
-        dev, imgs = mel.device, iter(self.images())
+    def _activation(self, dev, n_frames, B, bufs):
+        """act(L, mul, X, C, slope) -> (operand, slope): what the convolution behind an activation of the stream X reads.  Here the
+        stream itself, the leaky ReLU being the kernel's prologue"""
+        return lambda L, mul, X, C, slope: (X, slope)
+
+    def _walk(self, mel, n_frames, bufs, B, F):
+        """run's launches (`launches` of them): conv_pre, per stage the transposed convolution and the resblocks, conv_post.  A bf16
+        operand or destination says so by its dtype"""
+        dev, imgs, wav = mel.device, iter(self.images()), bufs["wav"]
         u_, r_, s_, t_ = bufs["u"], bufs["r"], bufs["s"], bufs["t"]
-        K, ch = len(self.resblock_kernel_sizes), self.channels
-        go = lambda *a, **k: self._launch(dev, n_frames, B, *a, **k)  # noqa: E731
+        K, ch, n_mel = len(self.resblock_kernel_sizes), self.padded_channels, self.n_mel_channels
+        act = self._activation(dev, n_frames, B, bufs)
+        bf16 = lambda t: int(t.dtype == torch.bfloat16)  # noqa: E731
+        go = lambda L, mul, X, Y, *a, **k: self._launch(dev, n_frames, B, L, mul, X, next(imgs), Y, *a, x_bf16=bf16(X), **k)  # noqa: E731
         L, mul, C = F, 1, ch[0]
-        go(L, mul, mel, next(imgs), s_, self.n_mel_channels, C, 7, 1, 1.0, mel.stride(0) if B > 1 else max(mel.stride(0), F), L * C, C,
-           x_sc=mel.stride(1) if self.n_mel_channels > 1 else max(mel.stride(1), F), x_mel=1)
+        go(L, mul, mel, s_, n_mel, C, 7, 1, 1.0, mel.stride(0) if B > 1 else max(mel.stride(0), F), L * C, C,
+           x_sc=mel.stride(1) if n_mel > 1 else max(mel.stride(1), F), x_mel=1)
         for i, u in enumerate(self.upsample_rates):
             Cn = ch[i + 1]
-            go(L, mul, s_, next(imgs), u_, C, u * Cn, 3, 1, LRELU_SLOPE, L * C, L * u * Cn, u * Cn)
+            go(L, mul, s_, u_, C, u * Cn, 3, 1, self.UP_SLOPE, L * C, L * u * Cn, u * Cn)
             L, mul, C = L * u, mul * u, Cn
             sb = L * C
             for j, (k, ds) in enumerate(zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes)):
@@ -934,42 +1027,20 @@ class HiFiGAN(nn.Module):
                 for m, d in enumerate(ds):
                     last = m == len(ds) - 1
                     tail = dict(res=src, acc=s_ if j else None, scale=1.0 / K if j == K - 1 else 1.0) if last else dict(res=src)
-                    # "1": r in place (Y may alias res, X is t); "2": the conv reads its own residual stream, so r and t take turns
-                    dst = s_ if last else (r_ if self.resblock == "1" or m % 2 == 0 else t_)
+                    X, slope = act(L, mul, src, C, LRELU_SLOPE)
                     if self.resblock == "1":
-                        go(L, mul, src, next(imgs), t_, C, C, k, d, LRELU_SLOPE, sb, sb, C, y_bf16=1)
-                        go(L, mul, t_, next(imgs), dst, C, C, k, 1, LRELU_SLOPE, sb, sb, C, x_bf16=1, **tail)
-                    else:
-                        go(L, mul, src, next(imgs), dst, C, C, k, d, LRELU_SLOPE, sb, sb, C, **tail)
+                        go(L, mul, X, t_, C, C, k, d, slope, sb, sb, C, y_bf16=bf16(t_))
+                        (X, slope), d = act(L, mul, t_, C, LRELU_SLOPE), 1
+                    # Y may alias res, but not a stream that X is: a convolution that reads its own residual stream through the halo
+                    # ("2" without an activation kernel in between) takes r and t in turns
+                    dst = s_ if last else (t_ if X is src and m % 2 else r_)
+                    go(L, mul, X, dst, C, C, k, d, slope, sb, sb, C, **tail)
                     src = dst
-        go(L, mul, s_, next(imgs), wav, C, 1, 7, 1, 0.01, L * C, wav.stride(0), 1, tanh=1)
+        X, slope = act(L, mul, s_, C, 0.01)
+        go(L, mul, X, wav, C, 1, 7, 1, slope, L * C, wav.stride(0), 1, tanh=int(self.use_tanh_at_final))
+        if not self.use_tanh_at_final:
+            wav.clamp_(-1.0, 1.0)                                          # capturable, not counted in `launches`
         return wav
-
-    def forward(self, mel, mel_lengths=None, mel_lengths_host=None):
-        """log-mel [B, n_mel, F] -> wav [B, U F]; with mel_lengths (frames per utterance) the ragged form -> (wav, wav_lengths =
-        U mel_lengths), zero behind each utterance.  mel_lengths_host spares the host a look at a device tensor."""
-        if not mel.is_cuda:
-            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
-        if mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
-            raise ValueError(f"mel is [B, {self.n_mel_channels}, F], got {tuple(mel.shape)}")
-        if mel.dtype != torch.float32 or mel.stride(2) != 1:
-            mel = mel.float().contiguous()
-        B, _, F = mel.shape
-        if mel_lengths is None:
-            n_frames = torch.full((B,), F, dtype=torch.int32, device=mel.device)
-        else:
-            if mel_lengths_host is None and not mel_lengths.is_cuda:
-                mel_lengths_host = mel_lengths.tolist()
-            if mel_lengths.numel() != B or (mel_lengths_host is not None and (len(mel_lengths_host) != B or max(mel_lengths_host) > F)):
-                raise ValueError(f"frame counts do not fit a [{B}, {self.n_mel_channels}, {F}] mel")
-            n_frames = mel_lengths.to(mel.device, non_blocking=True).to(torch.int32).contiguous()
-        if F == 0 or B == 0:
-            wav = mel.new_zeros(B, self.hop_length * F)
-        else:
-            wav = self.run(mel, n_frames, self.workspace(B, F, mel.device))
-        if mel_lengths is None:
-            return wav
-        return wav, n_frames.clamp(min=0, max=F) * self.hop_length
 
 
 # ---- BigVGAN (DESIGN.md 4.24): the HiFi-GAN generator with anti-aliased snake activations, csrc/voc_snake.hip in front of gt_voc_conv ----
@@ -980,19 +1051,6 @@ def kaiser_sinc_filter64(cutoff=0.25, half_width=0.3, kernel_size=12):
     time = np.arange(-(kernel_size // 2), kernel_size // 2) + 0.5 if kernel_size % 2 == 0 else np.arange(kernel_size) - kernel_size // 2
     f = 2 * cutoff * np.kaiser(kernel_size, beta) * np.sinc(2 * cutoff * time)
     return f / f.sum()
-
-
-def _pad16(c):
-    return (c + 15) // 16 * 16
-
-
-def _padded(t, shape):
-    """t in the leading corner of zeros of `shape`"""
-    if tuple(t.shape) == tuple(shape):
-        return t
-    out = t.new_zeros(shape)
-    out[tuple(slice(0, n) for n in t.shape)] = t
-    return out
 
 
 class _Snake(nn.Module):
@@ -1048,9 +1106,12 @@ class BigVGAN(HiFiGAN):
     .upsample.filter / .downsample.lowpass.filter, activation_post...), so state_dict() round-trips with the original generator's.
     A stage whose channel count is no multiple of 16 (the 24 channels the 112 M configurations end at) runs at the next multiple, padded
     on the host: zero weight rows / columns, zero bias, alpha' = 1, 1 / beta' = 0 — a padded channel is exactly 0 everywhere.
-    `launches` C-ABI calls per run: 78 convolutions + 73 activations = 151 for the base shape."""
+    `launches` C-ABI calls per run — conv_launches gt_voc_conv and snake_launches gt_voc_snake: 78 convolutions + 73 activations =
+    151 for the base shape.  The stage walk is HiFiGAN's: this class supplies what a convolution reads (_activation) and the fifth
+    buffer."""
 
     CHANNEL_MULTIPLE = 1
+    UP_SLOPE = 1.0                       # no activation in front of the transposed convolutions
 
     def __init__(self, resblock="1", upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4), upsample_initial_channel=512,
                  resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5),) * 3, n_mel_channels=80, activation="snakebeta",
@@ -1062,8 +1123,7 @@ class BigVGAN(HiFiGAN):
         self.activation, self.snake_logscale = activation, bool(snake_logscale)
         self.use_tanh_at_final, self.use_bias_at_final = bool(use_tanh_at_final), bool(use_bias_at_final)
         ch, rk, rd = self.channels, self.resblock_kernel_sizes, self.resblock_dilation_sizes
-        self.padded_channels = [_pad16(c) for c in ch]
-        self.ups = nn.ModuleList(nn.ModuleList([up]) for up in self.ups)
+        self.ups =nn.ModuleList(nn.ModuleList([up]) for up in self.ups)
         self.resblocks = nn.ModuleList(_AMPBlock(self.resblock, ch[i + 1], k, ds, activation, self.snake_logscale)
                                        for i in range(len(self.upsample_rates)) for k, ds in zip(rk, rd))
         self.activation_post = _Activation1d(ch[-1], activation, self.snake_logscale)
@@ -1084,20 +1144,6 @@ class BigVGAN(HiFiGAN):
                    use_tanh_at_final=cfg.get("use_tanh_at_final", True), use_bias_at_final=cfg.get("use_bias_at_final", True))
 
     # ---- images and parameter blocks, in launch order, at the padded widths ----------------------------------------------------------------
-    def _convs(self):
-        K = len(self.resblock_kernel_sizes)
-        seq = [self.conv_pre]
-        for i in range(len(self.ups)):
-            seq.append(self.ups[i][0])
-            for j in range(K):
-                rb = self.resblocks[i * K + j]
-                if self.resblock == "1":
-                    for c1, c2 in zip(rb.convs1, rb.convs2):
-                        seq += [c1, c2]
-                else:
-                    seq += list(rb.convs)
-        return seq + [self.conv_post]
-
     def _activations(self):
         return [act for rb in self.resblocks for act in rb.activations] + [self.activation_post]
 
@@ -1119,19 +1165,8 @@ class BigVGAN(HiFiGAN):
         """([(bf16 image, fp32 bias)] per convolution, [fp32 parameter block] per activation), both in launch order, rebuilt when any
         parameter's or buffer's (data_ptr, _version) changes"""
         def build():
-            dev, imgs = self.conv_pre.weight.device, []
-            for m in self._convs():
-                w = m.weight.detach().float()
-                b = m.bias.detach().float() if m.bias is not None else w.new_zeros(1)
-                if isinstance(m, nn.ConvTranspose1d):
-                    u = m.stride[0]
-                    w = _padded(w, (_pad16(w.shape[0]), _pad16(w.shape[1]), w.shape[2]))
-                    imgs.append((voc_pack(transposed_as_conv(w, u)), _padded(b, (w.shape[1],)).repeat(u).contiguous()))
-                else:
-                    N = w.shape[0] if m is self.conv_post else _pad16(w.shape[0])
-                    imgs.append((voc_pack(_padded(w, (N, _pad16(w.shape[1]), w.shape[2]))), _padded(b, (N,)).contiguous()))
-            blocks64 = [self.snake_block64(act) for act in self._activations()]
-            flat = torch.cat(blocks64).float().to(dev)                 # float64 on the host, rounded once
+            imgs, blocks64 = self._conv_images(), [self.snake_block64(act) for act in self._activations()]
+            flat = torch.cat(blocks64).float().to(self.conv_pre.weight.device)                 # float64 on the host, rounded once
             offs = np.cumsum([0] + [b.numel() for b in blocks64])
             return imgs, [flat[offs[i]:offs[i + 1]] for i in range(len(blocks64))]
         return self._images.get(list(self.parameters()) + list(self.buffers()), build)
@@ -1146,91 +1181,30 @@ class BigVGAN(HiFiGAN):
         return self._packed()
 
     # ---- capacity-sized form ------------------------------------------------------------------------------------------------------------
-    def _width(self):
-        U, w = 1, self.padded_channels[0]
-        for i, u in enumerate(self.upsample_rates):
-            U *= u
-            w = max(w, U * self.padded_channels[i + 1])
-        return w
-
-    def workspace_bytes(self, B, F_max):
-        """18 E + 4 B U F_max with E = B F_max W, W = max(C_0, max_i U_i C_i) over the padded channel counts (8192 for the base shape)"""
-        return 18 * B * F_max * self._width() + 4 * B * self.hop_length * F_max
-
     @property
     def t_dtype(self):
         """fp32: the tensor between an AMP block's two convolutions is the second activation's input"""
         return torch.float32
 
-    def buffer_spec(self):
-        return super().buffer_spec() + [("a", torch.bfloat16)]
-
-    def workspace(self, B, F_max, device):
-        """HiFiGAN's u, r, s and a t of fp32, one bf16 stream a (every activation's output: the operand of the convolution behind it) of
-        E = B F_max W elements each, and wav fp32 [B, U F_max]: 18 E + 4 B U F_max bytes.  B F_max W must stay below 2^31."""
-        E = B * F_max * self._width()
-        if B < 1 or F_max < 1 or E >= 2 ** 31:
-            raise ValueError(f"workspace for {B} x {F_max} frames: B F_max W = {E} must lie in [1, 2^31)")
-        bufs = {name: torch.empty(E, dtype=dtype, device=device) for name, dtype in self.buffer_spec()}
-        bufs["wav"] = torch.empty(B, self.hop_length * F_max, dtype=torch.float32, device=device)
-        return bufs
+    def buffer_spec(self, B, F_max):
+        """HiFiGAN's u, r, s and a t of fp32, and one bf16 stream a (every activation's output: the operand of the convolution behind
+        it) of E = B F_max W elements each, W over the padded channel counts (8192 for the base shape): 18 E + 4 B U F_max bytes"""
+        spec = super().buffer_spec(B, F_max)
+        return spec + [("a", torch.bfloat16, spec[0][2])]
 
     def _snake(self, dev, n_frames, B, L, mul, X, P, Y, C):
         a = _lib.fill_args(_lib.VocSnakeArgs, X=X, x_stride_b=L * C, P=P, Y=Y, y_stride_b=L * C, len_mul=mul, n_frames=n_frames, B=B,
                            L_cap=L, C=C)
         call.gt_voc_snake(a, _lib.current_stream(dev))
 
-    def run(self, mel, n_frames, bufs):
-        """kernel calls, the capacity-sized form for graph callers (HiFiGAN.run's contract): `launches` C-ABI calls — conv_launches
-        gt_voc_conv and snake_launches gt_voc_snake — nothing allocated once the images and parameter blocks exist, n_frames never
-        looked at on the host, every grid sized by F_max.  Without tanh one in-place torch clamp follows (capturable, not counted)."""
-        wav = bufs["wav"]
-        B, U = wav.shape[0], self.hop_length
-        F = wav.shape[1] // U
-        if not mel.is_cuda:
-            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
-        if mel.dtype != torch.float32 or mel.dim() != 3 or mel.stride(2) != 1:
-            raise ValueError("run takes a device fp32 log-mel [B, n_mel, F] with contiguous frames")
-        if mel.shape[0] != B or mel.shape[1] != self.n_mel_channels or mel.shape[2] < F:
-            raise ValueError(f"mel {tuple(mel.shape)} does not fit buffers for [{B}, {self.n_mel_channels}, {F}]")
-        if n_frames.dtype != torch.int32 or n_frames.numel() != B or not n_frames.is_cuda or not n_frames.is_contiguous():
-            raise ValueError("n_frames must be a contiguous int32 [B] on the device")
-        if self.conv_pre.weight.device != mel.device:
-            raise ValueError("the vocoder's parameters are not on the mel's device")
-        dev = mel.device
-        packed = self._packed()
-        imgs, blocks = iter(packed[0]), iter(packed[1])
-        u_, r_, s_, t_, a_ = bufs["u"], bufs["r"], bufs["s"], bufs["t"], bufs["a"]
-        K, ch = len(self.resblock_kernel_sizes), self.padded_channels
-        go = lambda *a, **k: self._launch(dev, n_frames, B, *a, **k)  # noqa: E731
-        act = lambda L, mul, X, C: self._snake(dev, n_frames, B, L, mul, X, next(blocks), a_, C)  # noqa: E731
-        L, mul, C = F, 1, ch[0]
-        go(L, mul, mel, next(imgs), s_, self.n_mel_channels, C, 7, 1, 1.0, mel.stride(0) if B > 1 else max(mel.stride(0), F), L * C, C,
-           x_sc=mel.stride(1) if self.n_mel_channels > 1 else max(mel.stride(1), F), x_mel=1)
-        for i, u in enumerate(self.upsample_rates):
-            Cn = ch[i + 1]
-            go(L, mul, s_, next(imgs), u_, C, u * Cn, 3, 1, 1.0, L * C, L * u * Cn, u * Cn)      # no activation in front
-            L, mul, C = L * u, mul * u, Cn
-            sb = L * C
-            for j, (k, ds) in enumerate(zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes)):
-                src = u_
-                for m, d in enumerate(ds):
-                    last = m == len(ds) - 1
-                    tail = dict(res=src, acc=s_ if j else None, scale=1.0 / K if j == K - 1 else 1.0) if last else dict(res=src)
-                    dst = s_ if last else r_                               # X is a: Y may alias res
-                    act(L, mul, src, C)
-                    if self.resblock == "1":
-                        go(L, mul, a_, next(imgs), t_, C, C, k, d, 1.0, sb, sb, C, x_bf16=1)
-                        act(L, mul, t_, C)
-                        go(L, mul, a_, next(imgs), dst, C, C, k, 1, 1.0, sb, sb, C, x_bf16=1, **tail)
-                    else:
-                        go(L, mul, a_, next(imgs), dst, C, C, k, d, 1.0, sb, sb, C, x_bf16=1, **tail)
-                    src = dst
-        act(L, mul, s_, C)
-        go(L, mul, a_, next(imgs), wav, C, 1, 7, 1, 1.0, L * C, wav.stride(0), 1, x_bf16=1, tanh=int(self.use_tanh_at_final))
-        if not self.use_tanh_at_final:
-            wav.clamp_(-1.0, 1.0)
-        return wav
+    def _activation(self, dev, n_frames, B, bufs):
+        """one gt_voc_snake launch per activation, in launch order: the convolution reads its bf16 output a at slope 1"""
+        blocks, a_ = iter(self.snake_blocks()), bufs["a"]
+
+        def act(L, mul, X, C, slope):
+            self._snake(dev, n_frames, B, L, mul, X, next(blocks), a_, C)
+            return a_, 1.0
+        return act
 
 
 # ---- Vocos (DESIGN.md 4.25): a frame-rate ConvNeXt backbone and an iSTFT head on csrc/vocos.hip, gt_voc_conv and gt_istft -------------
@@ -1271,7 +1245,7 @@ def fold_layer_scale(gamma, w2, b2):
     return (g[:, None] * w2.detach().double()).float(), (g * b2.detach().double()).float()
 
 
-class Vocos(nn.Module):
+class Vocos(_MelVocoder):
     """The published Vocos generator (Siuzdak 2023: `VocosBackbone` + `ISTFTHead`, padding="center") from log-mel to waveform.  The whole
     network runs at FRAME rate, every utterance of a ragged batch ON ITS OWN: utterance b is Vocos(mel[b:b+1, :, :F_b]), every
     convolution zero-padded at that utterance's own ends; F_b frames give 256 (F_b - 1) samples (none below 2 frames: gt_istft's rule).
@@ -1287,6 +1261,8 @@ class Vocos(nn.Module):
     accumulation, the residual stream, the LayerNorms and the head's nonlinearity fp32, the inverse STFT exact fp32.
     Refused with ValueError: padding="same", a conditional backbone (adanorm_num_embeddings), n_fft / hop_length other than 1024 / 256,
     a dim other than 128 / 256 / 512, an intermediate_dim that is no multiple of gt_vocos_hidden_chunk() or above 2048."""
+
+    min_frames = 2
 
     def __init__(self, input_channels=80, dim=512, intermediate_dim=1536, num_layers=8, n_fft=1024, hop_length=256, padding="center",
                  adanorm_num_embeddings=None):
@@ -1307,7 +1283,8 @@ class Vocos(nn.Module):
             raise ValueError(f"Vocos: intermediate_dim is a multiple of {chunk} up to 2048, got {intermediate_dim}")
         self.input_channels, self.dim, self.intermediate_dim, self.num_layers = input_channels, dim, intermediate_dim, num_layers
         self.n_fft, self.hop_length, self.padding = 1024, 256, padding
-        self.padded_channels = _pad16(input_channels)
+        self.mel_channels = self.padded_channels = _pad16(input_channels)
+        self.mel_padding = self.padded_channels - input_channels
         self.backbone = _VocosBackbone(input_channels, dim, intermediate_dim, num_layers)
         self.head = _VocosHead(dim, self.n_fft)
         object.__setattr__(self, "istft", InverseSTFT())                       # not a submodule: the state dict keeps the published names
@@ -1365,47 +1342,27 @@ class Vocos(nn.Module):
         return self.images(), self.istft._image()
 
     # ---- capacity-sized form ------------------------------------------------------------------------------------------------------------
+    def check_graph_input(self):
+        if self.mel_padding:
+            raise ValueError(f"compile_synthesis(vocoder=): {self.input_channels} mel channels, the graph takes multiples of 16")
+
     def buffer_spec(self, B, F_max):
         """[(name, dtype, elements)] of the buffers a run takes next to wav [B, 256 (F_max - 1)]: the fp32 residual stream x [B, F, C],
-        the bf16 operand a [B, F, C], the head's fp32 output o [B, F, 1026] and the spectrum workspace spec"""
+        the bf16 operand a [B, F, C], the head's fp32 output o [B, F, 1026] and the spectrum workspace spec: 6 B F C + 4104 B F +
+        4100 B Fp + 1024 B (F - 1) bytes with Fp = F rounded up to 64, 12.3 KB per frame at C = 512"""
+        self._check_capacity(B, F_max, B * F_max * 2 * VOCOS_BINS, "B >= 1, F_max >= 2 and B F_max 1026 < 2^31")
         E = B * F_max * self.dim
         return [("x", torch.float32, E), ("a", torch.bfloat16, E), ("o", torch.float32, B * F_max * 2 * VOCOS_BINS),
                 ("spec", torch.float32, call.gt_gl_spec_bytes(B, F_max) // 4)]
 
-    def workspace_bytes(self, B, F_max):
-        """6 B F C + 4104 B F + 4100 B Fp + 1024 B (F - 1) with Fp = F rounded up to 64: 12.3 KB per frame at C = 512"""
-        return sum(n * torch.empty(0, dtype=dt).element_size() for _, dt, n in self.buffer_spec(B, F_max)) + 4 * B * 256 * (F_max - 1)
-
-    def workspace(self, B, F_max, device):
-        """the buffers of one run at capacity (B utterances of up to F_max >= 2 frames): buffer_spec's and wav"""
-        if B < 1 or F_max < 2 or B * F_max * 2 * VOCOS_BINS >= 2 ** 31:
-            raise ValueError(f"workspace for {B} x {F_max} frames: B >= 1, F_max >= 2 and B F_max 1026 < 2^31")
-        bufs = {name: torch.empty(n, dtype=dt, device=device) for name, dt, n in self.buffer_spec(B, F_max)}
-        bufs["wav"] = torch.empty(B, 256 * (F_max - 1), dtype=torch.float32, device=device)
-        return bufs
-
     def run(self, mel, n_frames, bufs):
-        """kernel calls, the capacity-sized form for graph callers: fp32 log-mel [B, input_channels, >= F_max] (any batch / channel pitch,
-        frames contiguous; input_channels a multiple of 16), device int32 [B] frame counts and workspace's buffers (B and F_max are
-        theirs) -> bufs["wav"] [B, 256 (F_max - 1)], row b zero behind its 256 (F_b - 1) samples.  `launches` C-ABI calls; nothing is
-        allocated once the images exist, n_frames is never looked at on the host, every grid is sized by F_max."""
-        if self.input_channels % 16:
+        """_MelVocoder.run for a model whose own channel count is a multiple of 16 (forward pads the others' mel)"""
+        if self.mel_padding:
             raise ValueError(f"run takes a mel of a multiple of 16 channels; forward pads the {self.input_channels} of this model")
-        return self._run(mel, n_frames, bufs)
+        return super().run(mel, n_frames, bufs)
 
-    def _run(self, mel, n_frames, bufs):
-        wav = bufs["wav"]
-        B, F, C, H = wav.shape[0], wav.shape[1] // 256 + 1, self.dim, self.intermediate_dim
-        if not mel.is_cuda:
-            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
-        if mel.dtype != torch.float32 or mel.dim() != 3 or mel.stride(2) != 1:
-            raise ValueError("run takes a device fp32 log-mel [B, n_mel, F] with contiguous frames")
-        if mel.shape[0] != B or mel.shape[1] != self.padded_channels or mel.shape[2] < F:
-            raise ValueError(f"mel {tuple(mel.shape)} does not fit buffers for [{B}, {self.padded_channels}, {F}]")
-        if n_frames.dtype != torch.int32 or n_frames.numel() != B or not n_frames.is_cuda or not n_frames.is_contiguous():
-            raise ValueError("n_frames must be a contiguous int32 [B] on the device")
-        if self.head.out.weight.device != mel.device:
-            raise ValueError("the vocoder's parameters are not on the mel's device")
+    def _walk(self, mel, n_frames, bufs, B, F):
+        C, H, Cm, wav = self.dim, self.intermediate_dim, self.mel_channels, bufs["wav"]
         dev, im = mel.device, self.images()
         st = _lib.current_stream(dev)
         x, a_, o, spec = bufs["x"], bufs["a"], bufs["o"], bufs["spec"]
@@ -1420,8 +1377,8 @@ class Vocos(nn.Module):
             call.gt_vocos_norm(_lib.fill_args(_lib.VocosNormArgs, X=x, x_stride_b=sb, wd=wd, bd=bd, g=gb[0], be=gb[1], Y=Y, y_stride_b=sb,
                                               n_frames=n_frames, B=B, L_cap=F, C=C, y_bf16=y_bf16, eps=VOCOS_EPS), st)
 
-        conv(mel, im["embed"], x, self.padded_channels, C, 7, mel.stride(0) if B > 1 else max(mel.stride(0), F), sb,
-             x_stride_c=mel.stride(1) if self.padded_channels > 1 else max(mel.stride(1), F), x_mel=1, x_bf16=0)
+        conv(mel, im["embed"], x, Cm, C, 7, mel.stride(0) if B > 1 else max(mel.stride(0), F), sb,
+             x_stride_c=mel.stride(1) if Cm > 1 else max(mel.stride(1), F), x_mel=1, x_bf16=0)
         norm(im["norm"], x, 0)
         for blk in im["blocks"]:
             norm((blk["g"], blk["b"]), a_, 1, wd=blk["wd"], bd=blk["bd"])
@@ -1434,34 +1391,3 @@ class Vocos(nn.Module):
                                            F_max=F, n_fft=self.n_fft), st)
         self.istft.synthesize(spec, n_frames, B, F, out=wav)
         return wav
-
-    def forward(self, mel, mel_lengths=None, mel_lengths_host=None):
-        """log-mel [B, input_channels, F] -> wav [B, 256 (F - 1)]; with mel_lengths (frames per utterance) the ragged form -> (wav,
-        wav_lengths = 256 max(mel_lengths - 1, 0)), zero behind each utterance.  mel_lengths_host spares the host a look at a device
-        tensor.  A channel count that is no multiple of 16 (the 100-band models) is copied into a zero-padded mel first."""
-        if not mel.is_cuda:
-            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
-        if mel.dim() != 3 or mel.shape[1] != self.input_channels:
-            raise ValueError(f"mel is [B, {self.input_channels}, F], got {tuple(mel.shape)}")
-        if mel.dtype != torch.float32 or mel.stride(2) != 1:
-            mel = mel.float().contiguous()
-        B, _, F = mel.shape
-        if mel_lengths is None:
-            n_frames = torch.full((B,), F, dtype=torch.int32, device=mel.device)
-        else:
-            if mel_lengths_host is None and not mel_lengths.is_cuda:
-                mel_lengths_host = mel_lengths.tolist()
-            if mel_lengths.numel() != B or (mel_lengths_host is not None and (len(mel_lengths_host) != B or max(mel_lengths_host) > F)):
-                raise ValueError(f"frame counts do not fit a [{B}, {self.input_channels}, {F}] mel")
-            n_frames = mel_lengths.to(mel.device, non_blocking=True).to(torch.int32).contiguous()
-        if F < 2 or B == 0:
-            wav = mel.new_zeros(B, 256 * max(F - 1, 0))
-        else:
-            if self.padded_channels != self.input_channels:
-                padded = mel.new_zeros(B, self.padded_channels, F)
-                padded[:, :self.input_channels] = mel
-                mel = padded
-            wav = self._run(mel, n_frames, self.workspace(B, F, mel.device))
-        if mel_lengths is None:
-            return wav
-        return wav, (n_frames.clamp(min=1, max=max(F, 1)) - 1) * 256

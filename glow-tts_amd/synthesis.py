@@ -295,10 +295,10 @@ class SynthesisHandle:
         return out
 
     def wav(self, clone=False, fallback=True):
-        """With an audio.HiFiGAN: (wav [B, U T] fp32, wav_lengths = [U 2 (lengths[b] // 2)]), bit-identical to vocoder(mel,
-        2 (lengths // 2)) (after an overflow: that eager call on the eager mel), under the rules below.  With an audio.Vocos: the
-        same bit-identity to vocoder(mel, 2 (lengths // 2)), with Griffin-Lim's shapes and lengths (next).  With an audio.GriffinLim:
-        compile_synthesis(vocoder=): (wav [B, 256 (T - 1)] fp32, wav_lengths) with T = max(lengths) rounded down to even (the mel's
+        """With a neural vocoder (audio.HiFiGAN, BigVGAN, Vocos: DESIGN.md 4.26): (wav [B, vocoder.wav_len(T)] fp32, wav_lengths =
+        [vocoder.wav_len(2 (lengths[b] // 2))]), bit-identical to vocoder(mel, 2 (lengths // 2)) (after an overflow: that eager call on
+        the eager mel), under the rules below; wav_len(F) is U F for HiFi-GAN and BigVGAN and Griffin-Lim's 256 (F - 1) for Vocos.
+        With an audio.GriffinLim: (wav [B, 256 (T - 1)] fp32, wav_lengths) with T = max(lengths) rounded down to even (the mel's
         frames) and wav_lengths[b] = 256 max(2 (lengths[b] // 2) - 1, 0) (a host list) — the call's samples, zero behind every
         utterance's, bit-identical to GriffinLim.from_mel(mel, 2 (lengths // 2), n_iters=vocoder_iters, seed=the call's seed,
         phases="counter").  A view of the synthesiser's static buffer under mel()'s stream-order rules (clone=True: a copy that outlives
@@ -314,18 +314,16 @@ class SynthesisHandle:
         if s.vocoder is None:
             raise RuntimeError("compile_synthesis(vocoder=audio.GriffinLim(...)) keeps the samples")
         lens, status = self._wait()
-        if s.neural:                                                     # audio.HiFiGAN: U samples per frame, no frame lost
-            hop = s.vocoder.hop_length
-            wav_lengths = [hop * 2 * (v // 2) for v in lens]
-            n = hop * (max(lens) // 2 * 2)
-        else:                                                            # audio.GriffinLim and audio.Vocos: 256 (frames - 1) samples
-            hop = s.vocoder.hop_length if s.vocos else s.vocoder.stft_fn.hop_length
-            wav_lengths = [hop * max(2 * (v // 2) - 1, 0) for v in lens]
-            n = hop * max(max(lens) // 2 * 2 - 1, 0)
+        if s.neural:                                                     # the vocoder's own rule
+            wav_len = s.vocoder.wav_len
+        else:                                                            # audio.GriffinLim: 256 (frames - 1) samples
+            wav_len = lambda f: s.vocoder.stft_fn.hop_length * max(f - 1, 0)  # noqa: E731
+        wav_lengths = [wav_len(2 * (v // 2)) for v in lens]
+        n = wav_len(max(lens) // 2 * 2)
         if status != 0:
             mel = self._fallback(fallback)[0][0]
             if self._eager_wav is None:
-                if s.neural or s.vocos:
+                if s.neural:
                     frames = torch.tensor([2 * (v // 2) for v in lens], dtype=torch.int32).to(s.device)
                     self._eager_wav = s.vocoder(mel, frames, mel_lengths_host=[2 * (v // 2) for v in lens])[0]
                 elif mel.shape[2] < 2:
@@ -399,14 +397,11 @@ class Synthesizer:
     spectrum workspace, wav_static) — 4 batch (513 max_frames + 1025 Fp + 256 (max_frames - 1)) bytes with Fp = max_frames rounded up
     to 64: 52 + 109 + 26 MB at batch 32 and 800 frames.  vocoder_iters is fixed at capture; every launch of the loop is sized by
     max_frames, so a call of short utterances pays the loop of the capacity (tiles behind an utterance's end only write zeros).
-    vocoder=audio.HiFiGAN puts the neural generator there instead (vocoder_iters is ignored): wav_static
-    [batch, U max_frames] with U the product of its upsample rates, voc_bufs = HiFiGAN.workspace's buffers as static buffers
-    (14 batch max_frames W + 4 batch U max_frames bytes, W = 8192 for V1), captured_entries grows by vocoder.launches.  An
-    audio.BigVGAN is an audio.HiFiGAN here: the vocoder names its buffers (buffer_spec: one more bf16 stream, 18
-    batch max_frames W bytes at its padded width) and its launches count both of its kernels.
-    vocoder=audio.Vocos runs its 6 + 2 L launches there: wav_static [batch, 256 (max_frames - 1)] with Griffin-Lim's
-    length rule, voc_bufs = Vocos.buffer_spec's buffers (residual stream, bf16 operand, head output, spectrum workspace) and
-    wav_static; captured_entries grows by vocoder.launches.  Its input_channels must be the model's mel channels and a multiple of 16."""
+    vocoder=audio.HiFiGAN, audio.BigVGAN or audio.Vocos puts a neural generator there instead, through the one
+    contract of DESIGN.md 4.26 (vocoder_iters is ignored): wav_static [batch, vocoder.wav_len(max_frames)], voc_bufs =
+    vocoder.buffer_spec(batch, max_frames)'s buffers as static buffers and wav_static (vocoder.workspace_bytes(batch, max_frames)
+    bytes: 14 batch max_frames W + 4 batch U max_frames with W = 8192 for HiFi-GAN V1), captured_entries grows by vocoder.launches.
+    Its mel_channels must be the model's mel channels (Vocos: its input_channels, a multiple of 16)."""
 
     RING = 8
 
@@ -415,21 +410,13 @@ class Synthesizer:
         self.stochastic = bool(stochastic)
         if vocoder is not None:                                          # refused before any allocation
             from . import audio
-            self.neural, self.vocos = isinstance(vocoder, audio.HiFiGAN), isinstance(vocoder, audio.Vocos)
-            if self.vocos:                                               # DESIGN.md 4.25; vocoder_iters is not its business either
+            self.neural = isinstance(vocoder, audio._MelVocoder)         # the contract is all that is used of it
+            if self.neural:                                              # vocoder_iters is not its business
                 if any(p.device != next(gen.parameters()).device for p in vocoder.parameters()):
                     raise ValueError("compile_synthesis(vocoder=): the vocoder's parameters are not on the model's device")
-                if vocoder.input_channels % 16:
-                    raise ValueError(f"compile_synthesis(vocoder=): {vocoder.input_channels} mel channels, the graph takes multiples of 16")
-                if vocoder.input_channels != gen.out_channels:
-                    raise ValueError(f"compile_synthesis(vocoder=): the vocoder takes {vocoder.input_channels} mel channels, the "
-                                     f"model writes {gen.out_channels}")
-                vocoder_iters = 0
-            elif self.neural:                                              # vocoder_iters is not its business
-                if any(p.device != next(gen.parameters()).device for p in vocoder.parameters()):
-                    raise ValueError("compile_synthesis(vocoder=): the vocoder's parameters are not on the model's device")
-                if vocoder.n_mel_channels != gen.out_channels:
-                    raise ValueError(f"compile_synthesis(vocoder=): the vocoder takes {vocoder.n_mel_channels} mel channels, the "
+                vocoder.check_graph_input()
+                if vocoder.mel_channels != gen.out_channels:
+                    raise ValueError(f"compile_synthesis(vocoder=): the vocoder takes {vocoder.mel_channels} mel channels, the "
                                      f"model writes {gen.out_channels}")
                 vocoder_iters = 0
             elif not isinstance(vocoder, audio.GriffinLim) or not isinstance(vocoder.stft, audio.TacotronSTFT):
@@ -442,7 +429,7 @@ class Synthesizer:
             elif int(vocoder_iters) != vocoder_iters or vocoder_iters < 0:
                 raise ValueError("compile_synthesis: vocoder_iters is a non-negative integer")
         else:
-            self.neural = self.vocos = False
+            self.neural = False
         self.vocoder, self.vocoder_iters = vocoder, int(vocoder_iters)
         if not self.stochastic and (gen.use_sdp or gen.use_spp or gen.use_sep or gen.use_emo_embeds):
             raise NotImplementedError("compile_synthesis covers the deterministic duration predictor with optional speaker / language "
@@ -528,22 +515,12 @@ class Synthesizer:
         # ---- the waveform back end: magnitudes, the spectrum workspace, the samples, the frame counts the mel has
         self.wav_static = self.voc_bufs = self.n_frames = self._voc_images = None
         if self.neural:
-            # the vocoder names its streams of B max_frames W elements (buffer_spec) and the samples
+            # the vocoder names its buffers and their sizes (buffer_spec, which refuses a capacity past its kernels'
+            # 2^31 elements) and the samples a frame count gives (wav_len)
+            spec = vocoder.buffer_spec(B, Ty)
             self.n_frames = self._static(B, torch.int32)
-            E = B * Ty * vocoder._width()
-            if E >= 2 ** 31:
-                raise ValueError(f"compile_synthesis(vocoder=): batch * max_frames * {vocoder._width()} = {E} elements per buffer, 2^31 or more")
-            self.wav_static = self._static(B * vocoder.hop_length * Ty, torch.float32).view(B, vocoder.hop_length * Ty)
-            self.voc_bufs = {name: self._static(E, dtype) for name, dtype in vocoder.buffer_spec()}
-            self.voc_bufs["wav"] = self.wav_static
-            self._voc_images = vocoder.held()                            # kept: the graph holds their addresses
-        elif self.vocos:
-            # the vocoder names its buffers and their sizes (buffer_spec), the samples are Griffin-Lim's 256 (frames - 1)
-            if B * Ty * 1026 >= 2 ** 31:
-                raise ValueError(f"compile_synthesis(vocoder=): batch * max_frames * 1026 = {B * Ty * 1026} elements, 2^31 or more")
-            self.n_frames = self._static(B, torch.int32)
-            self.wav_static = self._static(B * 256 * (Ty - 1), torch.float32).view(B, 256 * (Ty - 1))
-            self.voc_bufs = {name: self._static(n, dtype) for name, dtype, n in vocoder.buffer_spec(B, Ty)}
+            self.wav_static = self._static(B * vocoder.wav_len(Ty), torch.float32).view(B, vocoder.wav_len(Ty))
+            self.voc_bufs = {name: self._static(n, dtype) for name, dtype, n in spec}
             self.voc_bufs["wav"] = self.wav_static
             self._voc_images = vocoder.held()                            # kept: the graph holds their addresses
         elif vocoder is not None:
@@ -601,7 +578,7 @@ class Synthesizer:
         if self.vocoder is not None:
             # the frames the mel really has (the squeeze drops an odd trailing frame); the phases' seed is the call block's first word
             torch.mul(rcy.lengths, 2, out=self.n_frames)
-            if self.neural or self.vocos:
+            if self.neural:
                 self.vocoder.run(self.mel_static, self.n_frames, self.voc_bufs)
             else:
                 self.vocoder.run_from_mel(self.mel_static, self.n_frames, self.voc_bufs, self.vocoder_iters, seed_dev=self.call[:1])

@@ -589,7 +589,10 @@ class FlowGenerator(nn.Module):
         by the call's seed, read from the call block) and vocoder_iters (fixed here) Griffin-Lim iterations behind the decoder;
         `h.wav()` -> (wav [batch, 256 (T - 1)], wav_lengths), bit-identical to vocoder.from_mel(mel, 2 (lengths // 2),
         n_iters=vocoder_iters, seed=seed, phases="counter").  Static memory: 4 batch (513 max_frames + 1025 Fp + 256 (max_frames - 1))
-        bytes, Fp = max_frames rounded up to 64 — about 52 + 109 + 26 MB at batch 32 and 800 frames."""
+        bytes, Fp = max_frames rounded up to 64 — about 52 + 109 + 26 MB at batch 32 and 800 frames.
+        vocoder=audio.HiFiGAN / BigVGAN / Vocos: a neural generator in that place, through the one contract of DESIGN.md 4.26
+        (vocoder_iters is ignored): `h.wav()` -> (wav [batch, vocoder.wav_len(T)], wav_lengths), bit-identical to vocoder(mel,
+        2 (lengths // 2)); static memory vocoder.workspace_bytes(batch, max_frames)."""
         from .synthesis import Synthesizer
         return Synthesizer(self, batch, max_tokens, max_frames, max_rows=max_rows, aux=aux, stochastic=stochastic,
                            max_frame_rows=max_frame_rows, vocoder=vocoder, vocoder_iters=vocoder_iters)

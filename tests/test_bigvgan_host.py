@@ -135,13 +135,14 @@ def test_from_config_on_the_published_base_config():
     assert voc.activation == "snakebeta" and voc.snake_logscale and voc.use_tanh_at_final and voc.use_bias_at_final
     assert voc.workspace_bytes(32, 800) == 18 * 32 * 800 * 8192 + 4 * 32 * 256 * 800
     assert voc.t_dtype == torch.float32
-    assert voc.buffer_spec() == [("u", torch.float32), ("r", torch.float32), ("s", torch.float32), ("t", torch.float32),
-                                 ("a", torch.bfloat16)]
+    E = 32 * 800 * 8192
+    assert voc.buffer_spec(32, 800) == [("u", torch.float32, E), ("r", torch.float32, E), ("s", torch.float32, E), ("t", torch.float32, E),
+                                        ("a", torch.bfloat16, E)]
     big = audio.BigVGAN.from_config(dict(G.BASE_CONFIG, upsample_rates=[4, 4, 2, 2, 2, 2], upsample_kernel_sizes=[8, 8, 4, 4, 4, 4],
                                          upsample_initial_channel=1536, use_tanh_at_final=False, use_bias_at_final=False))
     assert big.channels[-1] == 24 and big.padded_channels[-1] == 32 and big.conv_post.bias is None and not big.use_tanh_at_final
     hv1 = audio.HiFiGAN(**H.V1)                                                     # HiFi-GAN's own description is unchanged
-    assert hv1.buffer_spec() == [("u", torch.float32), ("r", torch.float32), ("s", torch.float32), ("t", torch.bfloat16)]
+    assert hv1.buffer_spec(32, 800) == [("u", torch.float32, E), ("r", torch.float32, E), ("s", torch.float32, E), ("t", torch.bfloat16, E)]
 
 
 @pytest.mark.parametrize("kw", [

@@ -75,7 +75,8 @@ def test_wav_equals_the_eager_vocoder(built):
     graph = synth.graph
     assert synth.wav_static.shape == (B, U * MAX_FRAMES)
     assert {k: (v.dtype, v.numel()) for k, v in synth.voc_bufs.items() if k != "wav"} == \
-        {name: (dtype, B * MAX_FRAMES * 128) for name, dtype in vocoder().buffer_spec()} and "a" in synth.voc_bufs
+        {name: (dtype, n) for name, dtype, n in vocoder().buffer_spec(B, MAX_FRAMES)} and "a" in synth.voc_bufs
+    assert [(name, n) for name, _, n in vocoder().buffer_spec(B, MAX_FRAMES)] == [(name, B * MAX_FRAMES * 128) for name in "ursta"]
     assert synth.captured_entries == plain.captured_entries + vocoder().launches == plain.captured_entries + 40 + 37
     for i, (ids, xl) in enumerate(tx):
         for j, (seed, ns, ls) in enumerate(CALLS):
