@@ -233,6 +233,12 @@ PROTOTYPES = {
     "gt_vocos_mlp_lds_bytes": (c_size_t, [c_int]),
     "gt_vocos_polar": (STATUS, [c_void_p, c_void_p]),
     "gt_vocos_polar_args_size": (c_int, []),
+    "gt_dtw_lds_bytes": (c_size_t, [c_int, c_int]),
+    "gt_dtw_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gt_mel_cepstrum": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gt_dtw_f32": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int,
+                            c_void_p, c_size_t, c_void_p, c_void_p]),
+    "gt_dtw_f0_stats": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 c_void_p = ctypes.c_void_p
 

@@ -1285,6 +1285,61 @@ typedef struct gt_vocos_polar_args {
 int gt_vocos_polar(const gt_vocos_polar_args* args, void* stream);
 int gt_vocos_polar_args_size(void);             /* sizeof(gt_vocos_polar_args) */
 
+/* ---- objective synthesis metrics (csrc/dtw.hip): mel cepstra, dynamic time warping, F0 statistics along the path ----
+ * gt_mel_cepstrum: the cepstrum of every frame of a ragged log-mel batch,
+ *   out[b][f][k] = sum_{n < N} dct[k][n] mel[b][n][f]      k < K, f < len[b]      (ONE mul + add chain over n ascending, no fma)
+ * and 0 for k in [K, 16) and for f in [len[b], F_max): every element of [B, F_max, 16] is written, no frame at or beyond len[b] is read.
+ *   mel      fp32 [B, N, ld], the decoder's channel-major layout (TacotronSTFT's natural log).
+ *   len      device int32 [B], clamped to [0, F_max].
+ *   dct      fp32 [K, N]: rows 1..K of the orthonormal DCT-II, dct[k - 1][n] = sqrt(2 / N) cos(pi k (n + 1/2) / N), built on the host in
+ *            float64 and rounded once (c0 is dropped: a gain in the log domain costs nothing).
+ *   out      fp32 [B, F_max, 16]: rows of 64 bytes, the form gt_dtw_f32 takes.
+ * Refusals, before any launch and in this order: NULL mel / len / dct / out, B outside [1, GT_MEL_MAX_B], N, K or F_max <= 0,
+ * F_max > GT_MEL_MAX_FRAMES, ld < F_max: GT_E_INVAL; N > GT_MEL_MAX_N_MEL or K > 16: GT_E_UNSUPPORTED; out not 16-byte, mel, len or dct
+ * not 4-byte aligned: GT_E_ALIGN.
+ *
+ * gt_dtw_f32: dynamic time warping of a[b] (a_len[b] rows) against b[b] (b_len[b] rows), every utterance on its own:
+ *   d(i, j) = alpha sqrt(sum_{k < 16} (a[i][k] - b[j][k])^2)      (differences, products and a sum over k ascending, correctly rounded sqrt)
+ *   D(0, 0) = d(0, 0),  D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)), a missing predecessor +infinity; on equal values the
+ *   first of that order wins.  cost[b] = D(a_len - 1, b_len - 1), the DP's own last cell; the path runs from (0, 0) to that cell,
+ *   max(a_len, b_len) <= path_len[b] <= a_len + b_len - 1.
+ *   a, b     fp32 [B, Fa_max, 16] / [B, Fb_max, 16] (feature vectors shorter than 16 padded with zeros).
+ *   a_len, b_len  device int32 [B].  A length of 0 on either side: cost 0, path_len 0.  A length below 0 or above its capacity is
+ *            treated as 0 and sets GT_DTW_ST_BAD_LEN in *status (optional device int32, OR-ed).
+ *   path     int32 [B, ld_path, 2]: (i, j) forward from (0, 0), -1 from path_len[b] to ld_path; ld_path >= Fa_max + Fb_max - 1.
+ *   workspace  gt_dtw_workspace_bytes(B, Fa_max, Fb_max) = 4 (B Fa_max nq + B round64(Fa_max + Fb_max)) bytes rounded up to 256, with
+ *            nq = ceil(Fb_max / 16) rounded up to 4: two direction bits per cell (the fp32 lattice is never stored) and the path in walk
+ *            order.  Needs no initialisation.
+ * Two launches: the DP, one workgroup of min(ceil(Fa_max / 64), 16) waves per utterance with gt_dtw_lds_bytes(Fa_max, Fb_max) bytes of
+ * dynamic LDS, and the walk back along the direction bits, one workgroup of four waves per utterance.  The DP's LDS: a ring of
+ * 512 bytes per wave, 4 Fb_max bytes (rounded up to 16) where Fa_max > 1024, and the image of b's features, 64 Fb_max bytes, where all
+ * of it fits 160 KB (else b is read from global memory: the same arithmetic).  Both helpers return 0 for a shape that is refused.
+ * Asynchronous, no allocation, no host synchronisation, capturable in a graph; every element of cost, path_len and path
+ * is written; no value depends on B, the capacities or the schedule: a batch row is bit-identical to the utterance alone.
+ * Refusals, before any launch and in this order: NULL a / b / a_len / b_len / cost / path_len / path / workspace, B outside
+ * [1, GT_MEL_MAX_B], Fa_max or Fb_max <= 0, ld_path < Fa_max + Fb_max - 1, workspace_bytes below gt_dtw_workspace_bytes: GT_E_INVAL;
+ * Fa_max or Fb_max > GT_DTW_MAX_F: GT_E_UNSUPPORTED; a, b, path or workspace not 16-byte, a_len, b_len, cost, path_len or status not
+ * 4-byte aligned: GT_E_ALIGN.
+ *
+ * gt_dtw_f0_stats: over the path_len[b] (clamped to [0, ld_path]) steps (i, j) of path[b], with x = f0_a[b][i], y = f0_b[b][j] in Hz and
+ * 0 = unvoiced (gt_yin_f0's form): counts[b] = {n_vv: both voiced; n_vu: exactly one voiced; n_gross: both voiced and
+ * |x - y| > 0.2 y (compared in fp64)}, sums[b] = {sum (x - y)^2, sum (1200 log2(x / y))^2} over the both-voiced steps, the cents
+ * term formed in fp64 and rounded once.  One workgroup per utterance, per-thread sums at a stride of 256 steps and one fixed tree: no
+ * atomics, a batch row is the utterance alone.  A step outside [0, ld_a) x [0, ld_b) is skipped.
+ * Refusals, before any launch and in this order: a NULL pointer, B outside [1, GT_MEL_MAX_B], ld_path, ld_a or ld_b <= 0: GT_E_INVAL;
+ * path not 8-byte, any other pointer not 4-byte aligned: GT_E_ALIGN. */
+#define GT_DTW_MAX_F 4096
+#define GT_DTW_ST_BAD_LEN 1
+size_t gt_dtw_lds_bytes(int Fa_max, int Fb_max);
+size_t gt_dtw_workspace_bytes(int B, int Fa_max, int Fb_max);
+int gt_mel_cepstrum(const float* mel, int ld, const int32_t* len, const float* dct, int B, int N, int K, int F_max, float* out,
+                    void* stream);
+int gt_dtw_f32(const float* a, const float* b, const int32_t* a_len, const int32_t* b_len, int B, int Fa_max, int Fb_max, float alpha,
+               float* cost, int32_t* path_len, int32_t* path, int ld_path, void* workspace, size_t workspace_bytes, int32_t* status,
+               void* stream);
+int gt_dtw_f0_stats(const int32_t* path, int ld_path, const int32_t* path_len, const float* f0_a, int ld_a, const float* f0_b, int ld_b,
+                    int B, int32_t* counts, float* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
