@@ -12,6 +12,9 @@
 //                          converted pairwise to bf16 and fed as B; V^T comes from LDS through
 //                          ds_read_b64_tr_b16 (pitch 192 B) in the permuted k order that map requires.
 //   O^T += Ev^T band(P)^T  the relative-value term as one K=16 MFMA per 32 channels.
+// Each of these steps is one piece of attn_frag.h, shared with attn_long.hip; a kernel owns where its operands live, its tile
+// loops and its barriers.  The two kernels of the cfg 2 training step (gt_attn_fwd_mfma_kernel, gt_attn_bwd_fused_kernel) call the
+// leaves only: row geometry, Ek / Ev stagers, rel-table chain, band MFMA, store_row96, dE contraction, Acc flush.
 #include <stdlib.h>
 #include <type_traits>
 #include "attn_frag.h"
@@ -34,6 +37,30 @@ __device__ unsigned long long g_attn_ph[8 * 128 * 16];
 #define APH(i) do { } while (0)
 #endif
 
+// rows 0 .. n - 1 of a [rows][ld] operand (head h) into an LDS image of pitch pa, rows >= T zero; nth threads
+GT_ATTN_DEV void stage_rows(bf16_t* A, int pa, const bf16_t* a, int lda, int n, int T, int h, const Rows& rows, int tid, int nth) {
+  for (int i = tid; i < n * (D / 8); i += nth) {
+    const int j = i / (D / 8), c8 = i - j * (D / 8);
+    uint4 aa = make_uint4(0, 0, 0, 0);
+    if (j < T) aa = *reinterpret_cast<const uint4*>(a + rows.rw(j) * lda + h * D + c8 * 8);
+    *reinterpret_cast<uint4*>(A + j * pa + c8 * 8) = aa;
+  }
+}
+// ... of two operands in one walk, both loads of a row in flight together
+GT_ATTN_DEV void stage_rows2(bf16_t* A, int pa, const bf16_t* a, int lda, bf16_t* B, int pb, const bf16_t* b_, int ldb,
+                             int n, int T, int h, const Rows& rows, int tid, int nth) {
+  for (int i = tid; i < n * (D / 8); i += nth) {
+    const int j = i / (D / 8), c8 = i - j * (D / 8);
+    uint4 aa = make_uint4(0, 0, 0, 0), bb = aa;
+    if (j < T) {
+      aa = *reinterpret_cast<const uint4*>(a + rows.rw(j) * lda + h * D + c8 * 8);
+      bb = *reinterpret_cast<const uint4*>(b_ + rows.rw(j) * ldb + h * D + c8 * 8);
+    }
+    *reinterpret_cast<uint4*>(A + j * pa + c8 * 8) = aa;
+    *reinterpret_cast<uint4*>(B + j * pb + c8 * 8) = bb;
+  }
+}
+
 template <int NT>   // key tiles of 32 (T <= 32*NT)
 __global__ __launch_bounds__(256, 1) void gt_attn_fwd_mfma_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,
@@ -53,27 +80,24 @@ __global__ __launch_bounds__(256, 1) void gt_attn_fwd_mfma_kernel(
 
   const int b = blockIdx.z, h = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int r = lane & 31, hh = lane >> 5;
+  const Lane ln(lane);
+  const int r = ln.r, hh = ln.hh;
   const int len = lens[b];
-  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
-  // rows this utterance owns behind rbase (frames + trailing halo): in the ragged layout frame indices past them belong
-  // to the NEXT utterance — reads are clamped onto the (zero) trailing halo row, stores are dropped
-  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;
-  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
+  const Rows rows(row0, b, Tp);
 
   // ---- stage K, V (zero rows >= T), Ek, Ev^T
   for (int i = tid; i < TPAD * (D / 8); i += 256) {
     const int j = i / (D / 8), c8 = i - j * (D / 8);
     uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
     if (j < T) {
-      kk = *reinterpret_cast<const uint4*>(k + RW(j) * ld + h * D + c8 * 8);
-      vv = *reinterpret_cast<const uint4*>(v + RW(j) * ld + h * D + c8 * 8);
+      kk = *reinterpret_cast<const uint4*>(k + rows.rw(j) * ld + h * D + c8 * 8);
+      vv = *reinterpret_cast<const uint4*>(v + rows.rw(j) * ld + h * D + c8 * 8);
     }
     *reinterpret_cast<uint4*>(Ks + j * KP + c8 * 8) = kk;
     *reinterpret_cast<uint4*>(Vs + j * VP + c8 * 8) = vv;
   }
-  for (int i = tid; i < 32 * D; i += 256) { const int rr = i / D, c = i - rr * D; Eks[rr * KP + c] = rr < NW ? f2bf(Ek[rr * D + c]) : (bf16_t)0; }
-  for (int i = tid; i < D * 16; i += 256) { const int d = i >> 4, rr = i & 15; EvT[i] = rr < NW ? f2bf(Ev[rr * D + d]) : (bf16_t)0; }
+  stage_rel_rows(Eks, Ek, tid, 256);
+  stage_rel_tr(EvT, Ev, tid, 256);
   for (int i = tid; i < 4 * 32 * 16; i += 256) PB[i] = 0;
   __syncthreads();
 
@@ -84,28 +108,15 @@ __global__ __launch_bounds__(256, 1) void gt_attn_fwd_mfma_kernel(
   float* qe = QE + w * 32 * NW;
   bf16_t* pb = PB + w * 32 * 16;
 
-  // ---- Q^T fragments straight from HBM: lane (query r, k-half hh), 6 k-steps of 16 channels
+  // ---- Q^T fragments straight from HBM: lane (query r, k-half hh), 6 k-steps of 16 channels; QE = Ek Q^T
   bf16x8_t qf[6];
 #pragma unroll
   for (int ks = 0; ks < 6; ++ks)
-    qf[ks] = *reinterpret_cast<const bf16x8_t*>(q + RW(ic) * ld + h * D + ks * 16 + 8 * hh);
+    qf[ks] = *reinterpret_cast<const bf16x8_t*>(q + rows.rw(ic) * ld + h * D + ks * 16 + 8 * hh);
+  rel_table(qe, Eks, qf, ln);
 
-  // ---- QE = Ek Q^T  (rows r' < 9 used)
-  {
-    f32x16_t acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 6; ++ks) {
-      const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(Eks + r * KP + ks * 16 + 8 * hh);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, qf[ks], acc, 0, 0, 0);
-    }
-    // D layout: column = query (lane&31), row r' = (e&3) + 8*(e>>2) + 4*hh
-#pragma unroll
-    for (int e = 0; e < 4; ++e) qe[r * NW + e + 4 * hh] = acc[e];
-    if (hh == 0) qe[r * NW + 8] = acc[4];
-  }
-
+  // The tile loops below are this kernel's own text (it is on the cfg 2 training step and <8> has no register to give): of
+  // attn_frag.h it takes the leaves only
   // ---- S^T = K Q^T
   f32x16_t s[NT];
 #pragma unroll
@@ -197,24 +208,8 @@ __global__ __launch_bounds__(256, 1) void gt_attn_fwd_mfma_kernel(
         o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, pf, o[dt], 0, 0, 0);
       }
     }
-  {
-    const bf16x8_t bfp = *reinterpret_cast<const bf16x8_t*>(pb + r * 16 + 8 * hh);      // band(P)^T: k = rel
-#pragma unroll
-    for (int dt = 0; dt < 3; ++dt) {
-      const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(EvT + (32 * dt + r) * 16 + 8 * hh);
-      o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfp, o[dt], 0, 0, 0);
-    }
-  }
-  if (i < T && i <= nv1) {
-#pragma unroll
-    for (int dt = 0; dt < 3; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = 32 * dt + 8 * g + 4 * hh;
-        *reinterpret_cast<uint2*>(out + (rbase + i) * ldo + h * D + d) =
-            make_uint2(pack2bf(o[dt][4 * g], o[dt][4 * g + 1]), pack2bf(o[dt][4 * g + 2], o[dt][4 * g + 3]));
-      }
-  }
+  band_mfma(o, EvT, pb, ln);
+  if (i < T && rows.owns(i)) store_row96(out + (rows.rbase + i) * ldo + h * D, o, hh);
 }
 
 template <int NT>
@@ -251,21 +246,15 @@ __global__ __launch_bounds__(256, 1) void gt_attn_fwd_mfma_long_kernel(
   bf16_t* PB  = reinterpret_cast<bf16_t*>(QE + 4 * 32 * NW);     // [4 waves][32][16]
 
   const int b = blockIdx.z, h = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int r = lane & 31, hh = lane >> 5;
+  const int tid = threadIdx.x, w = tid >> 6;
+  const Lane ln(tid & 63);
+  const int r = ln.r, hh = ln.hh;
   const int len = lens[b];
-  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
-  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;          // see gt_attn_fwd_mfma_kernel
-  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
+  const Rows rows(row0, b, Tp);
 
-  for (int i = tid; i < TPAD * (D / 8); i += 256) {
-    const int j = i / (D / 8), c8 = i - j * (D / 8);
-    uint4 vv = make_uint4(0, 0, 0, 0);
-    if (j < T) vv = *reinterpret_cast<const uint4*>(v + RW(j) * ld + h * D + c8 * 8);
-    *reinterpret_cast<uint4*>(Vs + j * VP + c8 * 8) = vv;
-  }
-  for (int i = tid; i < 32 * D; i += 256) { const int rr = i / D, c = i - rr * D; Eks[rr * KP + c] = rr < NW ? f2bf(Ek[rr * D + c]) : (bf16_t)0; }
-  for (int i = tid; i < D * 16; i += 256) { const int d = i >> 4, rr = i & 15; EvT[i] = rr < NW ? f2bf(Ev[rr * D + d]) : (bf16_t)0; }
+  stage_rows(Vs, VP, v, ld, TPAD, T, h, rows, tid, 256);
+  stage_rel_rows(Eks, Ek, tid, 256);
+  stage_rel_tr(EvT, Ev, tid, 256);
   for (int i = tid; i < 4 * 32 * 16; i += 256) PB[i] = 0;
   __syncthreads();
 
@@ -277,161 +266,54 @@ __global__ __launch_bounds__(256, 1) void gt_attn_fwd_mfma_long_kernel(
   bf16_t* pb = PB + w * 32 * 16;
 
   bf16x8_t qf[6];
-#pragma unroll
-  for (int ks = 0; ks < 6; ++ks)
-    qf[ks] = *reinterpret_cast<const bf16x8_t*>(q + RW(ic) * ld + h * D + ks * 16 + 8 * hh);
-  {
-    f32x16_t acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 6; ++ks) {
-      const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(Eks + r * KP + ks * 16 + 8 * hh);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, qf[ks], acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) qe[r * NW + e + 4 * hh] = acc[e];
-    if (hh == 0) qe[r * NW + 8] = acc[4];
-  }
+  load_frag6(qf, q + rows.rw(ic) * ld + h * D, hh);
+  rel_table(qe, Eks, qf, ln);
   __builtin_amdgcn_wave_barrier();
 
   const int nt = (T + 31) >> 5;                                  // key tiles that hold keys (wave-uniform)
   const float inv_sqrt = rsqrtf((float)D);
-  // K fragments of key tile t: lane (key r of the tile, k-half hh); rows >= T are zero
-  auto load_k = [&](int t, bf16x8_t* kf) {
-    const int j = 32 * t + r;
-    if (j < T) {
-#pragma unroll
-      for (int ks = 0; ks < 6; ++ks) kf[ks] = *reinterpret_cast<const bf16x8_t*>(k + RW(j) * ld + h * D + ks * 16 + 8 * hh);
-    } else {
-      const uint4 z = make_uint4(0, 0, 0, 0);
-#pragma unroll
-      for (int ks = 0; ks < 6; ++ks) kf[ks] = __builtin_bit_cast(bf16x8_t, z);
-    }
-  };
-  // masked, scaled scores of one tile (element e <-> key 32t + (e&3) + 8(e>>2) + 4hh)
+  // masked, scaled scores of one tile from its K fragments (L2, one tile ahead)
   auto scores = [&](int t, const bf16x8_t* kf, f32x16_t& st) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) st[e] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 6; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], st, 0, 0, 0);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int j = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-      float sc = st[e];
-      const int rel = j - i + WIN;
-      if ((unsigned)rel <= 2u * WIN) sc += qe[r * NW + rel];
-      sc *= inv_sqrt;
-      if (j >= T) sc = -3.0e38f;                                 // not a key at all
-      else if (j >= len || i >= len) sc = -1e4f;                 // masked_fill(mask == 0, -1e4), attentions.py:260
-      st[e] = sc;
-    }
+    mfma6(st, kf, qf);
+    score_tile(st, t, qe + r * NW, i, hh, T, len, inv_sqrt);
   };
 
   // ---- pass 1: online max / denominator over this lane's keys, then the two lane halves are merged
   float mx = -3.0e38f, den = 0.f;
   bf16x8_t kf[6], kn[6];
-  load_k(0, kf);
+  load_tile_frag6(kf, k, ld, h, 0, T, rows, ln);
 #pragma unroll 1
   for (int t = 0; t < nt; ++t) {
-    if (t + 1 < nt) load_k(t + 1, kn);
+    if (t + 1 < nt) load_tile_frag6(kn, k, ld, h, t + 1, T, rows, ln);
     f32x16_t st;
     scores(t, kf, st);
-    float tm = st[0];
-#pragma unroll
-    for (int e = 1; e < 16; ++e) tm = fmaxf(tm, st[e]);
-    const float mn = fmaxf(mx, tm);
-    float add = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) add += __expf(st[e] - mn);
-    den = den * __expf(mx - mn) + add;
-    mx = mn;
-#pragma unroll
-    for (int ks = 0; ks < 6; ++ks) kf[ks] = kn[ks];
+    online_tile(st, mx, den);
+    copy_frag6(kf, kn);
   }
-  {
-    const float mo = __shfl_xor(mx, 32), dn = __shfl_xor(den, 32);
-    const float mm = fmaxf(mx, mo);
-    den = den * __expf(mx - mm) + dn * __expf(mo - mm);
-    mx = mm;
-  }
+  online_merge(mx, den);
   const float rden = 1.0f / den;
 
   // ---- pass 2: P = softmax, dropout, O^T = V^T P^T (+ Ev^T band(P)^T)
   float* prow = Pout + (((size_t)b * H + h) * T + ic) * T;
-  const uint32_t drow = (uint32_t)((b * H + h) * T + i);
-  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
+  const Drop drop{drop_thresh, drop_seed, (uint32_t)((b * H + h) * T + i), drop_scale};
   const bool vec = (T & 3) == 0;
   f32x16_t o[3];
-#pragma unroll
-  for (int dt = 0; dt < 3; ++dt) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
-  }
-  load_k(0, kf);
+  zero3(o);
+  load_tile_frag6(kf, k, ld, h, 0, T, rows, ln);
 #pragma unroll 1
   for (int t = 0; t < nt; ++t) {
-    if (t + 1 < nt) load_k(t + 1, kn);
+    if (t + 1 < nt) load_tile_frag6(kn, k, ld, h, t + 1, T, rows, ln);
     f32x16_t st;
     scores(t, kf, st);
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int j0 = 32 * t + 8 * g + 4 * hh;
-      float p4[4];
-#pragma unroll
-      for (int e2 = 0; e2 < 4; ++e2) p4[e2] = __expf(st[4 * g + e2] - mx) * rden;
-      if (i < T) {
-        if (vec && j0 + 3 < T) *reinterpret_cast<float4*>(prow + j0) = make_float4(p4[0], p4[1], p4[2], p4[3]);
-        else {
-#pragma unroll
-          for (int e2 = 0; e2 < 4; ++e2) if (j0 + e2 < T) prow[j0 + e2] = p4[e2];
-        }
-      }
-#pragma unroll
-      for (int e2 = 0; e2 < 4; ++e2) {
-        const int j = j0 + e2;
-        float pd = p4[e2];
-        if (drop_thresh) pd = drop_keep(drop_seed, drow, j, drop_thresh) ? pd * drop_scale : 0.f;
-        st[4 * g + e2] = pd;
-        const int rel = j - i + WIN;
-        if ((unsigned)rel <= 2u * WIN && j < T) pb[r * 16 + rel] = f2bf(pd);
-      }
-    }
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      float f8[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) f8[e] = st[8 * s2 + e];
-      const bf16x8_t pf = pack8(f8);
-#pragma unroll
-      for (int dt = 0; dt < 3; ++dt) {
-        const bf16_t* va = Vs + (32 * t + 16 * s2 + 4 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
-        const bf16x8_t af = tr_frag8(va, va + 8 * VP);
-        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, pf, o[dt], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int ks = 0; ks < 6; ++ks) kf[ks] = kn[ks];
+    for (int e = 0; e < 16; ++e) st[e] = __expf(st[e] - mx) * rden;
+    p_tile_out<true>(st, t, prow, vec, i, ln, T, drop, pb);
+    acc_operand(o, st, Vs + 32 * t * VP, ln);
+    copy_frag6(kf, kn);
   }
   __builtin_amdgcn_wave_barrier();
-  {
-    const bf16x8_t bfp = *reinterpret_cast<const bf16x8_t*>(pb + r * 16 + 8 * hh);      // band(P)^T: k = rel
-#pragma unroll
-    for (int dt = 0; dt < 3; ++dt) {
-      const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(EvT + (32 * dt + r) * 16 + 8 * hh);
-      o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfp, o[dt], 0, 0, 0);
-    }
-  }
-  if (i < T && i <= nv1) {
-#pragma unroll
-    for (int dt = 0; dt < 3; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = 32 * dt + 8 * g + 4 * hh;
-        *reinterpret_cast<uint2*>(out + (rbase + i) * ldo + h * D + d) =
-            make_uint2(pack2bf(o[dt][4 * g], o[dt][4 * g + 1]), pack2bf(o[dt][4 * g + 2], o[dt][4 * g + 3]));
-      }
-  }
+  band_mfma(o, EvT, pb, ln);
+  if (i < T && rows.owns(i)) store_row96(out + (rows.rbase + i) * ldo + h * D, o, hh);
 }
 
 template <int NT>
@@ -474,33 +356,22 @@ __global__ __launch_bounds__(64 * WV, 1) void gt_attn_bwd_q_mfma_kernel(
   float*  Acc = reinterpret_cast<float*>(EkT + D * 16);          // [2][NW][D]  block-local dEk | dEv
   float*  DOE = Acc + 2 * NW * D;                                // [WV][32][NW]
   bf16_t* WB  = reinterpret_cast<bf16_t*>(DOE + WV * 32 * NW);   // per wave: dSB[32][16] | dSBT[16][BTP] | PdBT[16][BTP] | Qw[32][VP] | dOw[32][VP]
-  constexpr int WBN = 32 * 16 + 2 * 16 * BTP + 2 * 32 * VP;
+  constexpr int WBN = BAND_TABLES + 2 * 32 * VP;
 
   const int b = blockIdx.z, h = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int r = lane & 31, hh = lane >> 5;
+  const Lane ln(lane);
+  const int r = ln.r, hh = ln.hh;
   const int len = lens[b];
-  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
-  // rows this utterance owns behind rbase (frames + trailing halo): in the ragged layout frame indices past them belong
-  // to the NEXT utterance — reads are clamped onto the (zero) trailing halo row, stores are dropped
-  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;
-  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
+  const Rows rows(row0, b, Tp);
 
-  for (int i = tid; i < TPAD * (D / 8); i += NTH) {
-    const int j = i / (D / 8), c8 = i - j * (D / 8);
-    uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
-    if (j < T) {
-      kk = *reinterpret_cast<const uint4*>(k + RW(j) * ld + h * D + c8 * 8);
-      if (!VG) vv = *reinterpret_cast<const uint4*>(v + RW(j) * ld + h * D + c8 * 8);
-    }
-    *reinterpret_cast<uint4*>(Ks + j * VP + c8 * 8) = kk;
-    if (!VG) *reinterpret_cast<uint4*>(Vs + j * KP + c8 * 8) = vv;
-  }
-  for (int i = tid; i < 32 * D; i += NTH) { const int rr = i / D, c = i - rr * D; Evs[rr * KP + c] = rr < NW ? f2bf(Ev[rr * D + c]) : (bf16_t)0; }
-  for (int i = tid; i < D * 16; i += NTH) { const int d = i >> 4, rr = i & 15; EkT[i] = rr < NW ? f2bf(Ek[rr * D + d]) : (bf16_t)0; }
+  if (VG) stage_rows(Ks, VP, k, ld, TPAD, T, h, rows, tid, NTH);
+  else stage_rows2(Ks, VP, k, ld, Vs, KP, v, ld, TPAD, T, h, rows, tid, NTH);
+  stage_rel_rows(Evs, Ev, tid, NTH);
+  stage_rel_tr(EkT, Ek, tid, NTH);
   for (int i = tid; i < 2 * NW * D; i += NTH) Acc[i] = 0.f;
-  for (int i = tid; i < WV * (32 * 16 + 2 * 16 * BTP); i += NTH) {            // band tables start at zero
-    const int ww = i / (32 * 16 + 2 * 16 * BTP), o = i - ww * (32 * 16 + 2 * 16 * BTP);
+  for (int i = tid; i < WV * BAND_TABLES; i += NTH) {            // band tables start at zero
+    const int ww = i / BAND_TABLES, o = i - ww * BAND_TABLES;
     WB[ww * WBN + o] = 0;
   }
   __syncthreads();
@@ -510,12 +381,9 @@ __global__ __launch_bounds__(64 * WV, 1) void gt_attn_bwd_q_mfma_kernel(
   const int i = i0 + r;
   const int ic = i < T ? i : T - 1;
   float* doe = DOE + w * 32 * NW;
-  bf16_t* dSB = WB + w * WBN;
-  bf16_t* dSBT = dSB + 32 * 16;
-  bf16_t* PdBT = dSBT + 16 * BTP;
-  bf16_t* Qw = PdBT + 16 * BTP;
+  bf16_t* bt = WB + w * WBN;                                     // dSB | dSBT | PdBT
+  bf16_t* Qw = bt + BAND_TABLES;
   bf16_t* dOw = Qw + 32 * VP;
-  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
 
   if (active) {
     // per-wave Q / dO tiles (rows >= T zero) for the dEk / dEv contraction
@@ -523,185 +391,98 @@ __global__ __launch_bounds__(64 * WV, 1) void gt_attn_bwd_q_mfma_kernel(
       const int rr = c / (D / 8), c8 = c - rr * (D / 8);
       uint4 qq = make_uint4(0, 0, 0, 0), dd = qq;
       if (i0 + rr < T) {
-        qq = *reinterpret_cast<const uint4*>(q + RW(i0 + rr) * ld + h * D + c8 * 8);
-        dd = *reinterpret_cast<const uint4*>(dout + RW(i0 + rr) * lddo + h * D + c8 * 8);
+        qq = *reinterpret_cast<const uint4*>(q + rows.rw(i0 + rr) * ld + h * D + c8 * 8);
+        dd = *reinterpret_cast<const uint4*>(dout + rows.rw(i0 + rr) * lddo + h * D + c8 * 8);
       }
       *reinterpret_cast<uint4*>(Qw + rr * VP + c8 * 8) = qq;
       *reinterpret_cast<uint4*>(dOw + rr * VP + c8 * 8) = dd;
     }
     bf16x8_t dof[6];
-#pragma unroll
-    for (int ks = 0; ks < 6; ++ks)
-      dof[ks] = *reinterpret_cast<const bf16x8_t*>(dout + RW(ic) * lddo + h * D + ks * 16 + 8 * hh);
-    {
-      f32x16_t acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 6; ++ks) {
-        const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(Evs + r * KP + ks * 16 + 8 * hh);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, dof[ks], acc, 0, 0, 0);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) doe[r * NW + e + 4 * hh] = acc[e];
-      if (hh == 0) doe[r * NW + 8] = acc[4];
-    }
+    load_frag6(dof, dout + rows.rw(ic) * lddo + h * D, hh);
+    rel_table(doe, Evs, dof, ln);
     const float inv_sqrt = rsqrtf((float)D);
     const float* prow = P + (((size_t)b * H + h) * T + ic) * T;
-    const uint32_t drow = (uint32_t)((b * H + h) * T + i);
-    const bool vec = (T & 3) == 0;
+    const Drop drop{drop_thresh, drop_seed, (uint32_t)((b * H + h) * T + i), drop_scale};
+    const int palign = (T & 3) == 0 ? 4 : 1;
     bf16_t* dst_base = dST + ((size_t)b * H + h) * T * TI;
     bf16_t* pdt_base = PdT + ((size_t)b * H + h) * T * TI;
     f32x16_t o[3];
-#pragma unroll
-    for (int dt = 0; dt < 3; ++dt) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
-    }
-    {
-      // 161 <= T <= 384 (T <= 160: gt_attn_bwd_fused_kernel below): holding all NT score tiles of a wave (NT*16 accumulators)
-      // next to P and the dropout masks does not fit the register file.  One tile at a time instead: pass A walks the key tiles for Dsum only, pass B
-      // RECOMPUTES each tile's dPd^T (6 MFMAs, operands already in LDS / registers), turns it into dS^T, stores it and
-      // feeds dQ^T straight away — live state is one tile + the dQ^T accumulators, whatever NT is.
-      auto dp_tile = [&](int t, f32x16_t& st) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) st[e] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 6; ++ks) {
-          bf16x8_t af;
-          if (VG) {
-            const uint4 z = make_uint4(0, 0, 0, 0);
-            af = 32 * t + r < T ? *reinterpret_cast<const bf16x8_t*>(v + RW(32 * t + r) * ld + h * D + ks * 16 + 8 * hh)
-                                : __builtin_bit_cast(bf16x8_t, z);
-          } else {
-            af = *reinterpret_cast<const bf16x8_t*>(Vs + (32 * t + r) * KP + ks * 16 + 8 * hh);
-          }
-          st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, dof[ks], st, 0, 0, 0);
-        }
-      };
-      auto load_p4 = [&](int j0, float* p4) {
-        p4[0] = p4[1] = p4[2] = p4[3] = 0.f;
-        if (vec && j0 + 3 < T) { const float4 pv = *reinterpret_cast<const float4*>(prow + j0); p4[0] = pv.x; p4[1] = pv.y; p4[2] = pv.z; p4[3] = pv.w; }
-        else {
-#pragma unroll
-          for (int e2 = 0; e2 < 4; ++e2) if (j0 + e2 < T) p4[e2] = prow[j0 + e2];
-        }
-      };
-      auto dp_elem = [&](float dp, int j) {
-        const int rel = j - i + WIN;
-        if ((unsigned)rel <= 2u * WIN) dp += doe[r * NW + rel];
-        if (drop_thresh) dp = drop_keep(drop_seed, drow, j, drop_thresh) ? dp * drop_scale : 0.f;
-        return j >= T ? 0.f : dp;
-      };
-      __builtin_amdgcn_wave_barrier();
-      float dsum = 0.f;
+    zero3(o);
+    // 161 <= T <= 384 (T <= 160: gt_attn_bwd_fused_kernel below): holding all NT score tiles of a wave (NT*16 accumulators)
+    // next to P and the dropout masks does not fit the register file.  One tile at a time instead: pass A walks the key tiles for Dsum only, pass B
+    // RECOMPUTES each tile's dPd^T (6 MFMAs, operands already in LDS / registers), turns it into dS^T, stores it and
+    // feeds dQ^T straight away — live state is one tile + the dQ^T accumulators, whatever NT is.
+    auto dp_tile = [&](int t, f32x16_t& st) {
+      if (VG) {
+        bf16x8_t vf[6];
+        load_tile_frag6(vf, v, ld, h, t, T, rows, ln);
+        mfma6(st, vf, dof);
+      } else {
+        mfma6(st, Vs + (32 * t + r) * KP, dof, hh);
+      }
+    };
+    __builtin_amdgcn_wave_barrier();
+    float dsum = 0.f;
 #pragma unroll 1
-      for (int t = 0; t < NT; ++t) {
-        if (32 * t >= T) break;                                      // wave-uniform
-        f32x16_t st;
-        dp_tile(t, st);
+    for (int t = 0; t < NT; ++t) {
+      if (32 * t >= T) break;                                      // wave-uniform
+      f32x16_t st;
+      dp_tile(t, st);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int j0 = 32 * t + 8 * g + 4 * hh;
-          float p4[4];
-          load_p4(j0, p4);
+      for (int g = 0; g < 4; ++g) {
+        const int j0 = 32 * t + 8 * g + 4 * hh;
+        float p4[4];
+        load_p4(prow, j0, T, palign, p4);
 #pragma unroll
-          for (int e2 = 0; e2 < 4; ++e2) dsum += dp_elem(st[4 * g + e2], j0 + e2) * p4[e2];
-        }
+        for (int e2 = 0; e2 < 4; ++e2) dsum += dp_elem(st[4 * g + e2], doe + r * NW, i, j0 + e2, T, drop) * p4[e2];
       }
-      dsum += __shfl_xor(dsum, 32);
+    }
+    dsum += __shfl_xor(dsum, 32);
 #pragma unroll 1
-      for (int t = 0; t < NT; ++t) {
-        if (32 * t >= T) break;
-        f32x16_t st;
-        dp_tile(t, st);
+    for (int t = 0; t < NT; ++t) {
+      if (32 * t >= T) break;
+      f32x16_t st;
+      dp_tile(t, st);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int j0 = 32 * t + 8 * g + 4 * hh;
-          float p4[4];
-          load_p4(j0, p4);
+      for (int g = 0; g < 4; ++g) {
+        const int j0 = 32 * t + 8 * g + 4 * hh;
+        float p4[4];
+        load_p4(prow, j0, T, palign, p4);
 #pragma unroll
-          for (int e2 = 0; e2 < 4; ++e2) {
-            const int j = j0 + e2;
-            float ds = p4[e2] * (dp_elem(st[4 * g + e2], j) - dsum) * inv_sqrt;
-            float pd = p4[e2];
-            if (drop_thresh) pd = drop_keep(drop_seed, drow, j, drop_thresh) ? pd * drop_scale : 0.f;
-            if (j >= T || j >= len || i >= len || i >= T) ds = 0.f;          // masked_fill blocks the gradient
-            if (i >= len || i >= T) pd = 0.f;                                // padded queries carry no upstream gradient
-            st[4 * g + e2] = ds;
-            if (j < T) {
-              dst_base[(size_t)j * TI + i] = f2bf(ds);
-              pdt_base[(size_t)j * TI + i] = f2bf(pd);
-              const int rel = j - i + WIN;
-              if ((unsigned)rel <= 2u * WIN) { const bf16_t db = f2bf(ds); dSB[r * 16 + rel] = db; dSBT[rel * BTP + r] = db; PdBT[rel * BTP + r] = f2bf(pd); }
-            }
-          }
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          float f8[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) f8[e] = st[8 * s2 + e];
-          const bf16x8_t pf = pack8(f8);
-#pragma unroll
-          for (int dt = 0; dt < 3; ++dt) {
-            const bf16_t* ka = Ks + (32 * t + 16 * s2 + 4 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
-            const bf16x8_t af = tr_frag8(ka, ka + 8 * VP);
-            o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, pf, o[dt], 0, 0, 0);
+        for (int e2 = 0; e2 < 4; ++e2) {
+          const int j = j0 + e2;
+          float pd;
+          const float ds = ds_elem(p4[e2], dp_elem(st[4 * g + e2], doe + r * NW, i, j, T, drop), dsum, inv_sqrt, i, j, T, len, drop, pd);
+          st[4 * g + e2] = ds;
+          if (j < T) {
+            dst_base[(size_t)j * TI + i] = f2bf(ds);
+            pdt_base[(size_t)j * TI + i] = f2bf(pd);
+            band_tables(bt, r, i, j, ds, pd);
           }
         }
       }
-      __builtin_amdgcn_wave_barrier();
-    }
-    {
-      const bf16x8_t bfp = *reinterpret_cast<const bf16x8_t*>(dSB + r * 16 + 8 * hh);
 #pragma unroll
-      for (int dt = 0; dt < 3; ++dt) {
-        const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(EkT + (32 * dt + r) * 16 + 8 * hh);
-        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfp, o[dt], 0, 0, 0);
+      for (int s2 = 0; s2 < 2; ++s2) {                             // acc_operand, kept here: through the call both instances take 10 more VGPRs and lose their third wave
+        float f8[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f8[e] = st[8 * s2 + e];
+        const bf16x8_t pf = pack8(f8);
+#pragma unroll
+        for (int dt = 0; dt < 3; ++dt) {
+          const bf16_t* ka = Ks + (32 * t + 16 * s2 + 4 * hh) * VP + 32 * dt + ln.tr;
+          o[dt] = mfma(tr_frag8(ka, ka + 8 * VP), pf, o[dt]);
+        }
       }
     }
-    if (i < T && i <= nv1) {
-#pragma unroll
-      for (int dt = 0; dt < 3; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int d = 32 * dt + 8 * g + 4 * hh;
-          *reinterpret_cast<uint2*>(dq + (rbase + i) * lddq + h * D + d) =
-              make_uint2(pack2bf(o[dt][4 * g], o[dt][4 * g + 1]), pack2bf(o[dt][4 * g + 2], o[dt][4 * g + 3]));
-        }
-    }
+    __builtin_amdgcn_wave_barrier();
+    band_mfma(o, EkT, bt, ln);
+    if (i < T && rows.owns(i)) store_row96(dq + (rows.rbase + i) * lddq + h * D, o, hh);
     // dEk[r'][d] += sum_i dSBT[r'][i] Q[i][d];  dEv[r'][d] += sum_i PdBT[r'][i] dO[i][d]   (K = 32 queries)
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-      const bf16_t* At = which ? PdBT : dSBT;
-      const bf16_t* Bt = which ? dOw : Qw;
-#pragma unroll
-      for (int dt = 0; dt < 3; ++dt) {
-        f32x16_t acc;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(At + (r & 15) * BTP + 16 * ks + 8 * hh);
-          if (r >= 16) { const uint4 z = make_uint4(0, 0, 0, 0); af = __builtin_bit_cast(bf16x8_t, z); }
-          const bf16_t* ba = Bt + (16 * ks + 8 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
-          const bf16x8_t bf_ = tr_frag8(ba, ba + 4 * VP);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf_, acc, 0, 0, 0);
-        }
-        float* dstA = Acc + which * NW * D;
-        const int d = 32 * dt + r;                                   // D layout: column = d (lane&31), row r' = (e&3)+8(e>>2)+4hh
-#pragma unroll
-        for (int e = 0; e < 4; ++e) atomicAdd(dstA + (e + 4 * hh) * D + d, acc[e]);
-        if (hh == 0) atomicAdd(dstA + 8 * D + d, acc[4]);
-      }
-    }
+    de_contract(Acc, bt + 32 * 16, Qw, ln);
+    de_contract(Acc + NW * D, bt + 32 * 16 + 16 * BTP, dOw, ln);
   }
   __syncthreads();
-  for (int x = tid; x < NW * D; x += NTH) {
-    if (Acc[x] != 0.f) atomicAdd(dEk + x, Acc[x]);
-    if (Acc[NW * D + x] != 0.f) atomicAdd(dEv + x, Acc[NW * D + x]);
-  }
+  acc_flush(Acc, dEk, dEv, tid, NTH);
 }
 
 template <int NT>
@@ -715,59 +496,35 @@ __global__ __launch_bounds__(256, 1) void gt_attn_bwd_kv_mfma_kernel(
   bf16_t* Qs  = reinterpret_cast<bf16_t*>(smem);                 // [TPAD][VP]
   bf16_t* dOs = Qs + TPAD * VP;                                  // [TPAD][VP]
   const int b = blockIdx.z, h = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int r = lane & 31, hh = lane >> 5;
-  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
-  // rows this utterance owns behind rbase (frames + trailing halo): in the ragged layout frame indices past them belong
-  // to the NEXT utterance — reads are clamped onto the (zero) trailing halo row, stores are dropped
-  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;
-  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
-  for (int i = tid; i < TPAD * (D / 8); i += 256) {
-    const int j = i / (D / 8), c8 = i - j * (D / 8);
-    uint4 qq = make_uint4(0, 0, 0, 0), dd = qq;
-    if (j < T) {
-      qq = *reinterpret_cast<const uint4*>(q + RW(j) * ld + h * D + c8 * 8);
-      dd = *reinterpret_cast<const uint4*>(dout + RW(j) * lddo + h * D + c8 * 8);
-    }
-    *reinterpret_cast<uint4*>(Qs + j * VP + c8 * 8) = qq;
-    *reinterpret_cast<uint4*>(dOs + j * VP + c8 * 8) = dd;
-  }
+  const int tid = threadIdx.x, w = tid >> 6;
+  const Lane ln(tid & 63);
+  const int r = ln.r, hh = ln.hh;
+  const Rows rows(row0, b, Tp);
+  stage_rows2(Qs, VP, q, ld, dOs, VP, dout, lddo, TPAD, T, h, rows, tid, 256);
   __syncthreads();
   const int j0 = blockIdx.x * 128 + 32 * w;
   if (j0 >= T) return;
   const int j = j0 + r, jc = j < T ? j : T - 1;
-  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
   const bf16_t* dsr = dST + (((size_t)b * H + h) * T + jc) * TI;
   const bf16_t* pdr = PdT + (((size_t)b * H + h) * T + jc) * TI;
   f32x16_t ak[3], av[3];
-#pragma unroll
-  for (int dt = 0; dt < 3; ++dt) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { ak[dt][e] = 0.f; av[dt][e] = 0.f; }
-  }
+  zero3(ak);
+  zero3(av);
   const int nks = TI / 16;
   for (int ks = 0; ks < nks; ++ks) {
     const bf16x8_t bds = *reinterpret_cast<const bf16x8_t*>(dsr + 16 * ks + 8 * hh);     // dS[i = 16ks+8hh.., j]
     const bf16x8_t bpd = *reinterpret_cast<const bf16x8_t*>(pdr + 16 * ks + 8 * hh);
 #pragma unroll
-    for (int dt = 0; dt < 3; ++dt) {
-      const bf16_t* qa = Qs + (16 * ks + 8 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
-      const bf16_t* da = dOs + (16 * ks + 8 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
-      ak[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag8(qa, qa + 4 * VP), bds, ak[dt], 0, 0, 0);
-      av[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag8(da, da + 4 * VP), bpd, av[dt], 0, 0, 0);
+    for (int dt = 0; dt < 3; ++dt) {                              // kv_pair, kept here: through the call <8> and <12> swap their occupancy (3 <-> 4)
+      const bf16_t* qa = Qs + (16 * ks + 8 * hh) * VP + 32 * dt + ln.tr;
+      const bf16_t* da = dOs + (16 * ks + 8 * hh) * VP + 32 * dt + ln.tr;
+      ak[dt] = mfma(tr_frag8(qa, qa + 4 * VP), bds, ak[dt]);
+      av[dt] = mfma(tr_frag8(da, da + 4 * VP), bpd, av[dt]);
     }
   }
-  if (j < T && j <= nv1) {
-#pragma unroll
-    for (int dt = 0; dt < 3; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = 32 * dt + 8 * g + 4 * hh;
-        *reinterpret_cast<uint2*>(dk + RW(j) * lddk + h * D + d) =
-            make_uint2(pack2bf(ak[dt][4 * g], ak[dt][4 * g + 1]), pack2bf(ak[dt][4 * g + 2], ak[dt][4 * g + 3]));
-        *reinterpret_cast<uint2*>(dv + RW(j) * lddk + h * D + d) =
-            make_uint2(pack2bf(av[dt][4 * g], av[dt][4 * g + 1]), pack2bf(av[dt][4 * g + 2], av[dt][4 * g + 3]));
-      }
+  if (j < T && rows.owns(j)) {
+    store_row96(dk + rows.rw(j) * lddk + h * D, ak, hh);
+    store_row96(dv + rows.rw(j) * lddk + h * D, av, hh);
   }
 }
 
@@ -784,12 +541,14 @@ __global__ __launch_bounds__(256, 1) void gt_attn_bwd_kv_mfma_kernel(
 //            contraction of query tiles {0, 3}, {1, 4}, {2} (one LDS accumulation per wave, one global atomic per address); all waves then
 //            store the dS^T rows (16-byte segments, LDS -> workspace) — last, because a store in front of a load holds that load's
 //            wait (one counter for both).
+// The tile loops, with the dropout bits kept between the passes and the tile index a compile-time constant, are this kernel's own;
+// of attn_frag.h it takes the leaves that have no loop over tiles.
 // LDS (bytes): K|Q [160][VP] 30720, V|dO [160][KP] 33280, dS^T [160][DSP] 53760, EkT 3072, Ev [9][KP] 1872 and DOE [5][32][9] 5760
 // (the dE accumulators alias these two in phase 2), band tables 5 x 3584, P'^T stage 5 x 2560: 159184.
 constexpr int FNT = 5, FTP = FNT * 32, FTH = 512;
 constexpr int DSP = 168;           // dS^T pitch in halfs (336 B): conflict-free ds_read_b128 over 16 rows, 16-byte row segments
 constexpr int PWP = 40;            // pitch of the per-wave P'^T stage [32 keys][32 queries + pad]
-constexpr int FBAND = 32 * 16 + 2 * 16 * BTP;
+constexpr int FBAND = BAND_TABLES;
 constexpr size_t FUSED_LDS = (size_t)FTP * VP * 2 + FTP * KP * 2 + FTP * DSP * 2 + D * 16 * 2 + NW * KP * 2 + FNT * 32 * NW * 4 +
                              FNT * FBAND * 2 + FNT * 32 * PWP * 2;
 static_assert(2 * NW * D * 4 <= NW * KP * 2 + FNT * 32 * NW * 4, "the dE accumulators alias Ev | DOE");
@@ -820,30 +579,27 @@ __global__ __launch_bounds__(FTH, 1) void gt_attn_bwd_fused_kernel(
 
   const int b = blockIdx.y, h = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, hh = lane >> 5;
+  const Lane ln(lane);
+  const int r = ln.r, hh = ln.hh;
   const int len = lens[b];
-  const size_t rbase = (size_t)gt_row_base(row0, b, Tp) + HALO;
-  // rows this utterance owns behind rbase (frames + trailing halo): in the ragged layout frame indices past them belong
-  // to the NEXT utterance — reads are clamped onto the (zero) trailing halo row, stores are dropped
-  const int nv1 = gt_row_count(row0, b, Tp) - HALO - 1;
-  auto RW = [&](int t) { return rbase + (size_t)(t < nv1 ? t : nv1); };
-  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
+  const Rows rows(row0, b, Tp);
   bf16_t* dst_base = dST + ((size_t)b * H + h) * T * TI;
   bf16_t* pdt_base = PdT + ((size_t)b * H + h) * T * TI;
+  const int li = lane & 15, qd = li >> 2, pp = li & 3, colhalf = ((lane >> 4) & 1) * 16;
   const bool tile = w < FNT && 32 * w < T;                       // wave-uniform: this wave owns query tile w, later key tile w
 
   for (int x = tid; x < FTP * (D / 8); x += FTH) {
     const int j = x / (D / 8), c8 = x - j * (D / 8);
     uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
     if (j < T) {
-      kk = *reinterpret_cast<const uint4*>(k + RW(j) * ld + h * D + c8 * 8);
-      vv = *reinterpret_cast<const uint4*>(v + RW(j) * ld + h * D + c8 * 8);
+      kk = *reinterpret_cast<const uint4*>(k + rows.rw(j) * ld + h * D + c8 * 8);
+      vv = *reinterpret_cast<const uint4*>(v + rows.rw(j) * ld + h * D + c8 * 8);
     }
     *reinterpret_cast<uint4*>(Ks + j * VP + c8 * 8) = kk;
     *reinterpret_cast<uint4*>(Vs + j * KP + c8 * 8) = vv;
   }
-  for (int x = tid; x < NW * D; x += FTH) { const int rr = x / D, c = x - rr * D; Evs[rr * KP + c] = f2bf(Ev[x]); }
-  for (int x = tid; x < D * 16; x += FTH) { const int d = x >> 4, rr = x & 15; EkT[x] = rr < NW ? f2bf(Ek[rr * D + d]) : (bf16_t)0; }
+  for (int x = tid; x < NW * D; x += FTH) { const int rr = x / D, c = x - rr * D; Evs[rr * KP + c] = f2bf(Ev[x]); }   // own image: no zero rows kept
+  stage_rel_tr(EkT, Ek, tid, FTH);
   for (int x = tid; x < FNT * FBAND; x += FTH) WB[x] = 0;         // band tables start at zero
   __syncthreads();
   APH(1);
@@ -879,8 +635,8 @@ __global__ __launch_bounds__(FTH, 1) void gt_attn_bwd_fused_kernel(
     bf16x8_t dof[6];
 #pragma unroll
     for (int ks = 0; ks < 6; ++ks)
-      dof[ks] = *reinterpret_cast<const bf16x8_t*>(dout + RW(ic) * lddo + h * D + ks * 16 + 8 * hh);
-    {
+      dof[ks] = *reinterpret_cast<const bf16x8_t*>(dout + rows.rw(ic) * lddo + h * D + ks * 16 + 8 * hh);
+    {                                                            // the rel-table chain over this kernel's 9-row Ev image
       f32x16_t acc;
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[e] = 0.f;
@@ -891,9 +647,7 @@ __global__ __launch_bounds__(FTH, 1) void gt_attn_bwd_fused_kernel(
         if (r < NW) af = *reinterpret_cast<const bf16x8_t*>(Evs + r * KP + ks * 16 + 8 * hh);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, dof[ks], acc, 0, 0, 0);
       }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) doe[r * NW + e + 4 * hh] = acc[e];
-      if (hh == 0) doe[r * NW + 8] = acc[4];
+      rel_store(doe, acc, ln);
     }
     const float inv_sqrt = rsqrtf((float)D);
     const uint32_t drow = (uint32_t)((b * H + h) * T + i);
@@ -1013,24 +767,8 @@ __global__ __launch_bounds__(FTH, 1) void gt_attn_bwd_fused_kernel(
     }
     tiles(pass_b);
     APH(4);
-    {
-      const bf16x8_t bfp = *reinterpret_cast<const bf16x8_t*>(dSB + r * 16 + 8 * hh);
-#pragma unroll
-      for (int dt = 0; dt < 3; ++dt) {
-        const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(EkT + (32 * dt + r) * 16 + 8 * hh);
-        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfp, o[dt], 0, 0, 0);
-      }
-    }
-    if (i < T && i <= nv1) {
-#pragma unroll
-      for (int dt = 0; dt < 3; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int d = 32 * dt + 8 * g + 4 * hh;
-          *reinterpret_cast<uint2*>(dq + (rbase + i) * lddq + h * D + d) =
-              make_uint2(pack2bf(o[dt][4 * g], o[dt][4 * g + 1]), pack2bf(o[dt][4 * g + 2], o[dt][4 * g + 3]));
-        }
-    }
+    band_mfma(o, EkT, dSB, ln);
+    if (i < T && rows.owns(i)) store_row96(dq + (rows.rbase + i) * lddq + h * D, o, hh);
   }
   APH(5);
   __syncthreads();                                               // with its workgroup-scope fences: the P'^T rows stored above are read back below by other waves of this workgroup
@@ -1055,8 +793,8 @@ __global__ __launch_bounds__(FTH, 1) void gt_attn_bwd_fused_kernel(
     const int j = x / (D / 8), c8 = x - j * (D / 8);
     uint4 qq = make_uint4(0, 0, 0, 0), dd = qq;
     if (j < T) {
-      qq = *reinterpret_cast<const uint4*>(q + RW(j) * ld + h * D + c8 * 8);
-      dd = *reinterpret_cast<const uint4*>(dout + RW(j) * lddo + h * D + c8 * 8);
+      qq = *reinterpret_cast<const uint4*>(q + rows.rw(j) * ld + h * D + c8 * 8);
+      dd = *reinterpret_cast<const uint4*>(dout + rows.rw(j) * lddo + h * D + c8 * 8);
     }
     *reinterpret_cast<uint4*>(Qs + j * VP + c8 * 8) = qq;
     *reinterpret_cast<uint4*>(dOs + j * VP + c8 * 8) = dd;
@@ -1087,17 +825,9 @@ __global__ __launch_bounds__(FTH, 1) void gt_attn_bwd_fused_kernel(
         }
       }
     }
-    if (j < T && j <= nv1) {
-#pragma unroll
-      for (int dt = 0; dt < 3; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int d = 32 * dt + 8 * g + 4 * hh;
-          *reinterpret_cast<uint2*>(dk + RW(j) * lddq + h * D + d) =
-              make_uint2(pack2bf(ak[dt][4 * g], ak[dt][4 * g + 1]), pack2bf(ak[dt][4 * g + 2], ak[dt][4 * g + 3]));
-          *reinterpret_cast<uint2*>(dv + RW(j) * lddq + h * D + d) =
-              make_uint2(pack2bf(av[dt][4 * g], av[dt][4 * g + 1]), pack2bf(av[dt][4 * g + 2], av[dt][4 * g + 3]));
-        }
+    if (j < T && rows.owns(j)) {
+      store_row96(dk + rows.rw(j) * lddq + h * D, ak, hh);
+      store_row96(dv + rows.rw(j) * lddq + h * D, av, hh);
     }
   }
   APH(9);
@@ -1109,26 +839,11 @@ __global__ __launch_bounds__(FTH, 1) void gt_attn_bwd_fused_kernel(
 #pragma unroll
       for (int dt = 0; dt < 3; ++dt) {
         f32x16_t acc;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+        zero16(acc);
 #pragma unroll 1
-        for (int x = w - FNT; x < FNT && 32 * x < T; x += 8 - FNT) {
-          const bf16_t* At = WB + x * FBAND + 32 * 16 + (which ? 16 * BTP : 0);
-          const bf16_t* Bt = (which ? dOs : Qs) + 32 * x * VP;
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) {
-            bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(At + (r & 15) * BTP + 16 * ks + 8 * hh);
-            if (r >= 16) { const uint4 z = make_uint4(0, 0, 0, 0); af = __builtin_bit_cast(bf16x8_t, z); }
-            const bf16_t* ba = Bt + (16 * ks + 8 * hh + qd) * VP + 32 * dt + colhalf + 4 * pp;
-            const bf16x8_t bf_ = tr_frag8(ba, ba + 4 * VP);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf_, acc, 0, 0, 0);
-          }
-        }
-        float* dstA = Acc + which * NW * D;
-        const int d = 32 * dt + r;                                   // D layout: column = d (lane&31), row r' = (e&3)+8(e>>2)+4hh
-#pragma unroll
-        for (int e = 0; e < 4; ++e) atomicAdd(dstA + (e + 4 * hh) * D + d, acc[e]);
-        if (hh == 0) atomicAdd(dstA + 8 * D + d, acc[4]);
+        for (int x = w - FNT; x < FNT && 32 * x < T; x += 8 - FNT)
+          de_chain(acc, WB + x * FBAND + 32 * 16 + (which ? 16 * BTP : 0), (which ? dOs : Qs) + 32 * x * VP, dt, ln);
+        de_add(Acc + which * NW * D, acc, dt, ln);
       }
     }
   }
@@ -1141,10 +856,7 @@ __global__ __launch_bounds__(FTH, 1) void gt_attn_bwd_fused_kernel(
     }
   }
   __syncthreads();
-  for (int y = tid; y < NW * D; y += FTH) {
-    if (Acc[y] != 0.f) atomicAdd(dEk + y, Acc[y]);
-    if (Acc[NW * D + y] != 0.f) atomicAdd(dEv + y, Acc[NW * D + y]);
-  }
+  acc_flush(Acc, dEk, dEv, tid, FTH);
   APH(11);
 }
 
@@ -1162,7 +874,7 @@ template <int NT, int WV>
 int launch_bwd(const gt_attn_call& c)
 {
   constexpr int TPAD = NT * 32;
-  constexpr int WBN = 32 * 16 + 2 * 16 * BTP + 2 * 32 * VP;
+  constexpr int WBN = BAND_TABLES + 2 * 32 * VP;
   constexpr size_t lds1 = (NT > 8 ? 0 : (size_t)TPAD * KP * 2) + (size_t)TPAD * VP * 2 + 32 * KP * 2 + D * 16 * 2 + 2 * NW * D * 4 +
                           (size_t)WV * 32 * NW * 4 + (size_t)WV * WBN * 2;
   constexpr size_t lds2 = (size_t)2 * TPAD * VP * 2;
