@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "internal.h"
+#include "flow_rows.h"
 #include "../../include/glowtts_hip.h"
 
 namespace {
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(256) void gt_actnorm_invconv_fwd_kernel(
   // log-det bookkeeping of this flow pair rides along in workgroup 0 (it used to be a launch of its own on the
   // decoder's dependent chain): logdet[b] += (sum logs + G * logdet W) * len_b
   if (logdet && blockIdx.x == 0) {
-    const float per_frame = scal[0] + (float)G * scal[1];
+    const float per_frame = fr::pair_logdet_per_frame(scal, G);
     for (int b = threadIdx.x; b < B; b += 256) logdet[b] += per_frame * (float)len[b];
   }
   const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -120,11 +121,12 @@ __global__ __launch_bounds__(256) void gt_actnorm_invconv_fwd_kernel(
   const float rm = rowmask[m];
   const float2 xa = *reinterpret_cast<const float2*>(x + (size_t)m * C + 2 * g);
   const float2 xb = *reinterpret_cast<const float2*>(x + (size_t)m * C + half + 2 * g);
-  const float a0 = bias[2 * g] + __expf(logs[2 * g]) * xa.x, a1 = bias[2 * g + 1] + __expf(logs[2 * g + 1]) * xa.y;
-  const float a2 = bias[half + 2 * g] + __expf(logs[half + 2 * g]) * xb.x, a3 = bias[half + 2 * g + 1] + __expf(logs[half + 2 * g + 1]) * xb.y;
-  float o[4];
+  const float xv[4] = {xa.x, xa.y, xb.x, xb.y};
+  int ch[4]; fr::group_channels(g, half, ch);
+  float el[4], bs[4], o[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) o[k] = (W[k * 4] * a0 + W[k * 4 + 1] * a1 + W[k * 4 + 2] * a2 + W[k * 4 + 3] * a3) * rm;
+  for (int k = 0; k < 4; ++k) { el[k] = __expf(logs[ch[k]]); bs[k] = bias[ch[k]]; }
+  fr::actnorm_invconv_fwd(xv, el, bs, W, rm, o);
   *reinterpret_cast<float2*>(y + (size_t)m * C + 2 * g) = make_float2(o[0], o[1]);
   *reinterpret_cast<float2*>(y + (size_t)m * C + half + 2 * g) = make_float2(o[2], o[3]);
   if (y0_bf16) *reinterpret_cast<uint32_t*>(y0_bf16 + (size_t)m * ld0 + 2 * g) = pack2bf(o[0], o[1]);
@@ -145,15 +147,11 @@ __global__ __launch_bounds__(256) void gt_actnorm_invconv_rev_kernel(
   const float2 ya = *reinterpret_cast<const float2*>(y + (size_t)m * C + 2 * g);
   const float2 yb = *reinterpret_cast<const float2*>(y + (size_t)m * C + half + 2 * g);
   const float yv[4] = {ya.x, ya.y, yb.x, yb.y};
-  const int ch[4] = {2 * g, 2 * g + 1, half + 2 * g, half + 2 * g + 1};
-  float o[4];
+  int ch[4]; fr::group_channels(g, half, ch);
+  float eli[4], bs[4], o[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    float a = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) a += scal[2 + 4 * j + k] * yv[j];
-    o[k] = (a * rm - bias[ch[k]]) * __expf(-logs[ch[k]]) * rm;
-  }
+  for (int k = 0; k < 4; ++k) { eli[k] = __expf(-logs[ch[k]]); bs[k] = bias[ch[k]]; }
+  fr::actnorm_invconv_inv<true>(yv, eli, bs, scal + 2, rm, o);
   *reinterpret_cast<float2*>(x + (size_t)m * C + 2 * g) = make_float2(o[0], o[1]);
   *reinterpret_cast<float2*>(x + (size_t)m * C + half + 2 * g) = make_float2(o[2], o[3]);
   if (x0_bf16) *reinterpret_cast<uint32_t*>(x0_bf16 + (size_t)m * ld0 + 2 * g) = pack2bf(o[0], o[1]);
@@ -168,19 +166,12 @@ __global__ __launch_bounds__(256) void gt_actnorm_invconv_bwd_kernel(
     const float* __restrict__ scal, const int32_t* __restrict__ len, const float* __restrict__ dlogdet, int B)
 {
   // block: 256 threads = 4 row phases x 64 "group lanes" (G = C/4 <= 64); loops over its row slab
-  __shared__ float sW[4][16];
+  __shared__ __attribute__((aligned(16))) float sW[4 * 16], sL[4 * 64 * 4], sB[4 * 64 * 4];
   // backward of the log-det bookkeeping, in workgroup 0 (formerly its own launch): with s = sum_b dlogdet[b] * len_b,
   // dlogs[c] += s and dW += (C/4) * s * W^{-T}; atomics, because every workgroup accumulates into dlogs / dW
   if (dlogdet && blockIdx.x == 0) {
     __shared__ float sred[4];
-    float sv = 0.f;
-    for (int b = threadIdx.x; b < B; b += 256) sv += dlogdet[b] * (float)len[b];
-    sv = wave_sum(sv);
-    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = sv;
-    __syncthreads();
-    sv = sred[0] + sred[1] + sred[2] + sred[3];
-    for (int c = threadIdx.x; c < C; c += 256) atomicAdd(dlogs + c, sv);
-    if (threadIdx.x < 16) atomicAdd(dW + threadIdx.x, (float)(C >> 2) * sv * scal[2 + threadIdx.x]);
+    fr::pair_logdet_bwd_atomics(dlogs, dW, scal, fr::dlogdet_len_sum(dlogdet, len, B, sred), C);
   }
   const int G = C >> 2, half = C >> 1;
   const int g = threadIdx.x & 63, ph = threadIdx.x >> 6;
@@ -189,7 +180,7 @@ __global__ __launch_bounds__(256) void gt_actnorm_invconv_bwd_kernel(
 #pragma unroll
   for (int i = 0; i < 16; ++i) accW[i] = 0.f;
   if (g < G) {
-    const int ch[4] = {2 * g, 2 * g + 1, half + 2 * g, half + 2 * g + 1};
+    int ch[4]; fr::group_channels(g, half, ch);
     float el[4], bs[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) { el[k] = __expf(logs[ch[k]]); bs[k] = bias[ch[k]]; }
@@ -201,43 +192,16 @@ __global__ __launch_bounds__(256) void gt_actnorm_invconv_bwd_kernel(
       const float2 db = *reinterpret_cast<const float2*>(dy + (size_t)m * C + half + 2 * g);
       const float xv[4] = {xa.x, xa.y, xb.x, xb.y};
       const float dym[4] = {da.x * rm, da.y * rm, db.x * rm, db.y * rm};
-      float a[4], d_a[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) a[k] = bs[k] + el[k] * xv[k];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) d_a[i] = W[i] * dym[0] + W[4 + i] * dym[1] + W[8 + i] * dym[2] + W[12 + i] * dym[3];
-#pragma unroll
-      for (int o = 0; o < 4; ++o)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) accW[o * 4 + i] += dym[o] * a[i];
       float dxv[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { accB[k] += d_a[k]; accL[k] += d_a[k] * xv[k] * el[k]; dxv[k] = d_a[k] * el[k]; }
+      fr::actnorm_invconv_bwd(xv, dym, el, bs, W, accW, accL, accB, dxv);
       *reinterpret_cast<float2*>(dx + (size_t)m * C + 2 * g) = make_float2(dxv[0], dxv[1]);
       *reinterpret_cast<float2*>(dx + (size_t)m * C + half + 2 * g) = make_float2(dxv[2], dxv[3]);
     }
   }
-  // Same-address float atomics serialise at L2 (~50 ns each): fold the 4 row phases in LDS first, so every
-  // channel sees ONE add per workgroup (and workgroups cover 128 rows).
-  __shared__ float sL[4][64][4], sB[4][64][4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { sL[ph][g][k] = accL[k]; sB[ph][g][k] = accB[k]; }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) accW[i] = wave_sum(accW[i]);
-  if (g == 0) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) sW[ph][i] = accW[i];
-  }
+  // the row phases fold in LDS, then one atomic per channel (workgroups cover up to 128 rows)
+  fr::param_fold(sL, sB, sW, ph, g, accL, accB, accW);
   __syncthreads();
-  if (ph == 0 && g < G) {
-    const int ch[4] = {2 * g, 2 * g + 1, half + 2 * g, half + 2 * g + 1};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      atomicAdd(dlogs + ch[k], sL[0][g][k] + sL[1][g][k] + sL[2][g][k] + sL[3][g][k]);
-      atomicAdd(dbias + ch[k], sB[0][g][k] + sB[1][g][k] + sB[2][g][k] + sB[3][g][k]);
-    }
-  }
-  if (threadIdx.x < 16) atomicAdd(dW + threadIdx.x, sW[0][threadIdx.x] + sW[1][threadIdx.x] + sW[2][threadIdx.x] + sW[3][threadIdx.x]);
+  fr::param_fold_atomics(dlogs, dbias, dW, sL, sB, sW, ph, g, G, half);
 }
 
 // ------------------------------------------------------------------ affine coupling
@@ -263,11 +227,10 @@ __global__ __launch_bounds__(256) void gt_coupling_fwd_kernel(const float* __res
     const float rm = rowmask[m];
     for (int c = lane; c < half; c += 64) {
       const float mm = out[(size_t)m * C + c];
-      float lg = out[(size_t)m * C + half + c];
-      if (sigmoid_scale) lg = __logf(1e-6f + sigmoidf_(lg + 2.0f));
+      const float lg = fr::coupling_lg(out[(size_t)m * C + half + c], sigmoid_scale);
       const float x1 = x[(size_t)m * C + half + c];
       z[(size_t)m * C + c] = x[(size_t)m * C + c];
-      z[(size_t)m * C + half + c] = (mm + __expf(lg) * x1) * rm;
+      z[(size_t)m * C + half + c] = fr::coupling_fwd(mm, lg, x1, rm);
       s += lg * rm;
     }
   }
@@ -286,10 +249,9 @@ __global__ __launch_bounds__(256) void gt_coupling_rev_kernel(const float* __res
   if (idx >= R * half) return;
   const int m = idx / half, c = idx - m * half;
   const float mm = out[(size_t)m * C + c];
-  float lg = out[(size_t)m * C + half + c];
-  if (sigmoid_scale) lg = __logf(1e-6f + sigmoidf_(lg + 2.0f));
+  const float lg = fr::coupling_lg(out[(size_t)m * C + half + c], sigmoid_scale);
   x[(size_t)m * C + c] = z[(size_t)m * C + c];
-  x[(size_t)m * C + half + c] = (z[(size_t)m * C + half + c] - mm) * __expf(-lg) * rowmask[m];
+  x[(size_t)m * C + half + c] = fr::coupling_inv(mm, lg, z[(size_t)m * C + half + c], rowmask[m]);
 }
 
 // backward: dz -> dx (x0 part passed through, the start-conv contribution is added later),
@@ -304,16 +266,13 @@ __global__ __launch_bounds__(256) void gt_coupling_bwd_kernel(const float* __res
   if (idx >= R * half) return;
   const int m = idx / half, c = idx - m * half;
   const float rm = rowmask[m];
-  const float lraw = out[(size_t)m * C + half + c];
-  float lg = lraw, dl_draw = 1.0f;
-  if (sigmoid_scale) { const float sg = sigmoidf_(lraw + 2.0f); lg = __logf(1e-6f + sg); dl_draw = sg * (1.0f - sg) / (1e-6f + sg); }
-  const float e = __expf(lg), x1 = x[(size_t)m * C + half + c];
-  const float dz1 = dz[(size_t)m * C + half + c] * rm;
-  const float d_m = dz1;
-  const float d_lg = (dz1 * e * x1 + dlogdet[gt_row_batch(row0, B, m, Tp)] * rm) * dl_draw;
+  float dl_draw, dx1, d_lg;
+  const float lg = fr::coupling_lg(out[(size_t)m * C + half + c], sigmoid_scale, dl_draw);
+  const float dz1 = dz[(size_t)m * C + half + c] * rm;                    // = d m
+  fr::coupling_bwd(dz1, lg, dl_draw, x[(size_t)m * C + half + c], dlogdet[gt_row_batch(row0, B, m, Tp)] * rm, dx1, d_lg);
   dx[(size_t)m * C + c] = dz[(size_t)m * C + c];
-  dx[(size_t)m * C + half + c] = dz1 * e;
-  dout_bf16[(size_t)m * C + c] = f2bf(d_m);
+  dx[(size_t)m * C + half + c] = dx1;
+  dout_bf16[(size_t)m * C + c] = f2bf(dz1);
   dout_bf16[(size_t)m * C + half + c] = f2bf(d_lg);
 }
 
@@ -507,8 +466,6 @@ __global__ __launch_bounds__(192 * CAG_PH) void gt_cond_affine_grads_kernel(cons
 }
 
 }  // namespace
-
-
 
 extern "C" int gt_squeeze_rows_f32(const float* y, float* rows, const int32_t* len_sq, int B, int C, int Ty, int Tp,
                                    const int32_t* row0, void* stream)

@@ -23,9 +23,11 @@
 // L2 (every workgroup reads the same 0.4 MB: L2-resident), B = the bf16 LDS tile; accumulators e = 4g + j of lane (r, h)
 // are row r, column 32 * block + 8g + 4h + j.  What leaves for HBM is what the batched weight gradients and the next
 // pass read anyway (wn_out, y0, d out, d wn_out) plus the fp32 flow state.
+// The row maths are flow_rows.h's, shared with flow_ops.hip; what the three kernels do alike to a tile is a step below ("tile steps").
 #include "common.h"
 #include "internal.h"
 #include "mfma_frag.h"
+#include "flow_rows.h"
 #include "../../include/glowtts_hip.h"
 
 namespace {
@@ -106,10 +108,13 @@ __device__ __forceinline__ void utt_atomic_add(float* __restrict__ dst, float s,
 
 // layer slice L of the skip GEMM (K = 4H in four LDS tiles): registers -> LDS, barrier, 12 k-steps; the weight ring runs
 // across the slices (L is a template parameter so that every ring / staging index is a compile-time constant)
+struct Lane { int lane, r, h, wm, wn; };   // lane (r, h) of wave (wm, wn): rows 32 wm .., column blocks 3 wn .. (2 wn .. where N = 80)
+
 template <int L>
-__device__ __forceinline__ void skip_slice(const u32x4_t (&xr)[6], bf16_t* As, const bf16_t* __restrict__ Wskip, int wm, int wn, int r, int h,
-                                           int lane, uint4 (&ring)[RD][3], f32x16_t (&acc)[3])
+__device__ __forceinline__ void skip_slice(const u32x4_t (&xr)[6], bf16_t* As, const bf16_t* __restrict__ Wskip, const Lane& t,
+                                           uint4 (&ring)[RD][3], f32x16_t (&acc)[3])
 {
+  const int wm = t.wm, wn = t.wn, r = t.r, h = t.h, lane = t.lane;
   constexpr int KK = NL * H / 16, kbase = L * (H / 16);
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
@@ -137,21 +142,6 @@ __device__ __forceinline__ void skip_slice(const u32x4_t (&xr)[6], bf16_t* As, c
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-}
-
-// commons.squeeze / unsqueeze (commons.py:339-364, n_sqz = 2) folded into the first / last kernels of a pass: squeezed frame t of
-// utterance b, channel p * 80 + c  <->  y[b, c, 2 t + p] of the [B, 80, T] tensor at the decoder's public boundary
-__device__ __forceinline__ float4 sq_gather4(const float* __restrict__ y, int b, int t, int c, int T)
-{
-  const int p = c >= HALF, cc = c - HALF * p;
-  const float* src = y + ((size_t)b * HALF + cc) * T + 2 * t + p;
-  return make_float4(src[0], src[(size_t)T], src[2 * (size_t)T], src[3 * (size_t)T]);
-}
-__device__ __forceinline__ void sq_scatter4(float* __restrict__ y, int b, int t, int c, int T, const float4& v)
-{
-  const int p = c >= HALF, cc = c - HALF * p;
-  float* dst = y + ((size_t)b * HALF + cc) * T + 2 * t + p;
-  dst[0] = v.x; dst[(size_t)T] = v.y; dst[2 * (size_t)T] = v.z; dst[3 * (size_t)T] = v.w;
 }
 
 // A finished [64][AP] bf16 tile -> global rows m0 .. m0 + 63 (row stride ld, 192 channels): 16 bytes per lane, consecutive lanes on
@@ -206,6 +196,127 @@ __device__ __forceinline__ void prefetch_images(const void* const (&ptr)[16], co
   if (KEEP) asm volatile("" :: "v"(acc));                               // consumes the loads; emits nothing
 }
 
+// ------------------------------------------------------------------------------------------------ tile steps
+// Barriers stay in the bodies except start_conv_stage's; the forward's stamps 1, 9, 10 fall inside a step: written there under STAMP.
+// b_skip [192] | b_end [160 (+ 32 zero)] | b_start [192] -> Bs, the tile's row mask -> Bs + 3 H, staged once: from global memory the biases
+// cost an L2 round trip per (block, group) in the epilogues, and a mask load in a loop that also stores waits for those stores
+template <bool TAIL, bool HEAD>
+__device__ __forceinline__ void stage_bias_mask(float* Bs, const float* b_skip, const float* b_end, const float* b_start, const float* rowmask, int m0, int R)
+{
+  if (threadIdx.x < 3 * H / 4) {
+    const int which = threadIdx.x / (H / 4), o = threadIdx.x - which * (H / 4);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (which == 0) { if (TAIL) v = reinterpret_cast<const float4*>(b_skip)[o]; }
+    else if (which == 1) { if (TAIL && o < C / 4) v = reinterpret_cast<const float4*>(b_end)[o]; }
+    else if (HEAD) v = reinterpret_cast<const float4*>(b_start)[o];
+    reinterpret_cast<float4*>(Bs)[threadIdx.x] = v;
+  }
+  if (threadIdx.x >= 192) {
+    const int row = threadIdx.x - 192;
+    Bs[3 * H + row] = m0 + row < R ? rowmask[m0 + row] : 0.0f;
+  }
+}
+
+// the tile's gated activations, all four layers: 6 x 16 B per thread and slice, in flight together (plain vector: stays in registers)
+__device__ __forceinline__ void load_acts(u32x4_t (&xr)[NL][6], const bf16_t* acts, int ldacts, int m0, int R)
+{
+#pragma unroll
+  for (int l = 0; l < NL; ++l)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      const int chunk = threadIdx.x + 256 * i, row = chunk / 24, c8 = chunk - row * 24;
+      const int gm = m0 + row < R ? m0 + row : R - 1;
+      xr[l][i] = *reinterpret_cast<const u32x4_t*>(acts + (size_t)gm * ldacts + l * H + c8 * 8);
+    }
+}
+
+// skip GEMM: acc = acts @ Wskip^T (K = 768: 48 k-steps, four slices through LDS); three barriers behind it every wave is past slices 0..2
+template <bool STAMP>
+__device__ __forceinline__ void skip_gemm(const u32x4_t (&xr)[NL][6], bf16_t* As, const bf16_t* Wskip, const Lane& t, f32x16_t (&acc)[3])
+{
+  acc_zero<3>(acc);
+  constexpr int KK = NL * H / 16;
+  uint4 ring[RD][3];
+#pragma unroll
+  for (int p = 0; p < RD; ++p)
+#pragma unroll
+    for (int bn = 0; bn < 3; ++bn) ring[p][bn] = ldfrag(Wskip, (3 * t.wn + bn) * KK + p, t.lane);
+  if (STAMP) PH(1);
+  skip_slice<0>(xr[0], As, Wskip, t, ring, acc);
+  skip_slice<1>(xr[1], As, Wskip, t, ring, acc);
+  skip_slice<2>(xr[2], As, Wskip, t, ring, acc);
+  skip_slice<3>(xr[3], As, Wskip, t, ring, acc);
+}
+
+// accumulators (+ bias, * the lane's row mask) -> bf16 -> a [64][AP] LDS tile: the GEMM epilogues that end in bf16 (the backward's
+// mask-only one keeps its own copy, see there)
+template <bool BIAS, bool MASK>
+__device__ __forceinline__ void pack_tile(const f32x16_t (&acc)[3], const float* bias, float rm_l, bf16_t* tile, const Lane& t)
+{
+#pragma unroll
+  for (int bn = 0; bn < 3; ++bn)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int n = 32 * (3 * t.wn + bn) + 8 * g + 4 * t.h;
+      float v[4] = {acc[bn][4 * g], acc[bn][4 * g + 1], acc[bn][4 * g + 2], acc[bn][4 * g + 3]};
+      if (BIAS) { const float4 b4 = *reinterpret_cast<const float4*>(bias + n); v[0] = v[0] + b4.x; v[1] = v[1] + b4.y; v[2] = v[2] + b4.z; v[3] = v[3] + b4.w; }
+      if (MASK) { v[0] = v[0] * rm_l; v[1] = v[1] * rm_l; v[2] = v[2] * rm_l; v[3] = v[3] * rm_l; }
+      *reinterpret_cast<uint2*>(tile + (32 * t.wm + t.r) * AP + n) = pack4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+// the end conv's accumulators + bias -> the fp32 [m | logs] tile (N = 160: blocks 0..4, block 5 is the image's zero padding)
+__device__ __forceinline__ void end_epilogue(const f32x16_t (&acc)[3], const float* bias, float* Ot, const Lane& t)
+{
+#pragma unroll
+  for (int bn = 0; bn < 3; ++bn)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int n = 32 * (3 * t.wn + bn) + 8 * g + 4 * t.h;
+      if (n < C) {
+        const float4 b4 = *reinterpret_cast<const float4*>(bias + n);
+        *reinterpret_cast<float4*>(Ot + (32 * t.wm + t.r) * ZP + n) =
+            make_float4(acc[bn][4 * g] + b4.x, acc[bn][4 * g + 1] + b4.y, acc[bn][4 * g + 2] + b4.z, acc[bn][4 * g + 3] + b4.w);
+      }
+    }
+}
+
+// start conv: h = (y0 @ Wstart^T + b) * mask (K = 80: 5 k-steps, fragments prefetched into ring) from the bf16 y0 tile, out through Hst
+template <bool STAMP>
+__device__ __forceinline__ void start_conv_stage(const bf16_t* Wstart, int ks_start, WRing<3, HALF / 16>& ring, const bf16_t* X0t, const float* bias,
+                                                 float rm_l, bf16_t* Hst, bf16_t* h_next, int m0, int R, const Lane& t)
+{
+  f32x16_t acc[3];
+  acc_zero<3>(acc);
+  gemm_run<3, HALF / 16>(Wstart, ks_start, 3 * t.wn, X0t + (32 * t.wm + t.r) * XP + 8 * t.h, t.lane, ring, acc);
+  if (STAMP) PH(9);
+  pack_tile<true, true>(acc, bias, rm_l, Hst, t);
+  __syncthreads();
+  if (STAMP) PH(10);
+  coop_store_rows(h_next, H, Hst, m0, R);
+}
+
+// first kernel of a pass: the tile's rows, read as rows or gathered from [B, 80, T] (then also kept in rows_out); put() fills the tile
+template <bool KEPT, class Put>
+__device__ __forceinline__ void first_rows(const float* bct, const float* rows_in, float* rows_out,
+                                           const int64_t* rowbatch, const int32_t* rowframe, const int32_t* len,
+                                           int T, int m0, int R, Put put)
+{
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    const int item = threadIdx.x + 256 * k, row = item / 40, c = 4 * (item - row * 40), gm = m0 + row;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (gm < R) {
+      if (bct) {
+        const int b = (int)rowbatch[gm], t = rowframe[gm];
+        if (t >= 0 && t < len[b]) v = fr::sq_gather4(bct, b, t, c, T, HALF);
+        if (KEPT || rows_out) *reinterpret_cast<float4*>(rows_out + (size_t)gm * C + c) = v;   // KEPT: the entry has checked rows_out
+      } else v = *reinterpret_cast<const float4*>(rows_in + (size_t)gm * C + c);
+    }
+    put(row, c, v);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ forward
 constexpr int F_AS = 0;                                    // acts slices [4][64][AP] bf16; later At [64][AP] (slice 0) / y0 tile
 constexpr int F_O = BM * AP * 2;                           // m | logs tile [64][ZP] fp32 (over slices 1, 2 once they are dead)
@@ -215,8 +326,9 @@ constexpr int F_BIAS = F_RS + BM * 4;                      // b_skip [192] | b_e
 constexpr int FWD_LDS = F_BIAS + 3 * H * 4 + BM * 4;       // + the tile's row mask [64]
 static_assert(F_O + BM * ZP * 4 <= 3 * BM * AP * 2, "the m | logs tile must stay clear of acts slice 3");
 
+// (waves_per_eu: 110 KB of tiles admit one workgroup per CU whatever the registers; without the ceiling <0,1> stops at 120 + 48, three waves, for 124 + 48)
 template <bool TAIL, bool HEAD>
-__global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd_args a)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd_args a)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int n_tiles = (a.R + BM - 1) / BM;
@@ -228,73 +340,30 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
   float* Ot = reinterpret_cast<float*>(smem + F_O);
   float* Zt = reinterpret_cast<float*>(smem + F_Z);
   float* rowsum = reinterpret_cast<float*>(smem + F_RS);
+  const Lane ln{lane, r, h, wm, wn};
   const int mrow = m0 + 32 * wm + r;                        // this lane's row in the MFMA epilogues
   const float rm_l = mrow < R ? a.rowmask[mrow] : 0.0f;
-  // the three convs' biases: read from global memory inside the MFMA epilogues they cost an L2 round trip per (block, group)
   float* Bs = reinterpret_cast<float*>(smem + F_BIAS);
-  if (threadIdx.x < 3 * H / 4) {
-    const int which = threadIdx.x / (H / 4), o = threadIdx.x - which * (H / 4);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (which == 0) { if (TAIL) v = reinterpret_cast<const float4*>(a.b_skip)[o]; }
-    else if (which == 1) { if (TAIL && o < C / 4) v = reinterpret_cast<const float4*>(a.b_end)[o]; }
-    else if (HEAD) v = reinterpret_cast<const float4*>(a.b_start)[o];
-    reinterpret_cast<float4*>(Bs)[threadIdx.x] = v;
-  }
-  float* Rm = Bs + 3 * H;                                    // the tile's row mask (a global load inside a loop that also stores waits
-  if (threadIdx.x >= 192) {                                  // for those stores: vector-memory operations retire in order)
-    const int row = threadIdx.x - 192;
-    Rm[row] = m0 + row < R ? a.rowmask[m0 + row] : 0.0f;
-  }
+  float* Rm = Bs + 3 * H;
+  stage_bias_mask<TAIL, HEAD>(Bs, a.b_skip, a.b_end, a.b_start, a.rowmask, m0, R);
   PH(0);
 
   if (TAIL) {
-    const bf16_t* acts = static_cast<const bf16_t*>(a.acts);
-    const bf16_t* Wskip = static_cast<const bf16_t*>(a.w_skip);
-    // the tile's gated activations, all four layers: 6 x 16 B per thread per layer slice, in flight together
-    u32x4_t xr[NL][6];                                      // (plain vector: staging arrays of it stay in registers)
-#pragma unroll
-    for (int l = 0; l < NL; ++l)
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const int chunk = threadIdx.x + 256 * i, row = chunk / 24, c8 = chunk - row * 24;
-        const int gm = m0 + row < R ? m0 + row : R - 1;
-        xr[l][i] = *reinterpret_cast<const u32x4_t*>(acts + (size_t)gm * a.ldacts + l * H + c8 * 8);
-      }
+    u32x4_t xr[NL][6];
+    load_acts(xr, static_cast<const bf16_t*>(a.acts), a.ldacts, m0, R);
     if (threadIdx.x < BM) rowsum[threadIdx.x] = 0.0f;
-    // skip GEMM: wn_out = (acts @ Wskip^T + b) * mask;  wave (wm, wn): rows 32 wm .., column blocks 3 wn ..
+    // skip GEMM: wn_out = (acts @ Wskip^T + b) * mask
     f32x16_t acc[3];
-    acc_zero<3>(acc);
-    constexpr int KK = NL * H / 16;                         // 48 k-steps
-    uint4 ring[RD][3];
-#pragma unroll
-    for (int p = 0; p < RD; ++p)
-#pragma unroll
-      for (int bn = 0; bn < 3; ++bn) ring[p][bn] = ldfrag(Wskip, (3 * wn + bn) * KK + p, lane);
-    PH(1);
-    skip_slice<0>(xr[0], As, Wskip, wm, wn, r, h, lane, ring, acc);
-    skip_slice<1>(xr[1], As, Wskip, wm, wn, r, h, lane, ring, acc);
-    skip_slice<2>(xr[2], As, Wskip, wm, wn, r, h, lane, ring, acc);
-    skip_slice<3>(xr[3], As, Wskip, wm, wn, r, h, lane, ring, acc);
+    skip_gemm<true>(xr, As, static_cast<const bf16_t*>(a.w_skip), ln, acc);
     PH(2);
     // the end conv's first weight fragments fly under this epilogue
     WRing<3, H / 16> ring2;
     gemm_prefetch<3, H / 16>(static_cast<const bf16_t*>(a.w_end), a.ks_end, 3 * wn, lane, ring2);
-    // every wave is past slices 0..2 (the barrier before slice 3): At = slice 0's region
-    bf16_t* wn_out = static_cast<bf16_t*>(a.wn_out);
-#pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
-        const float4 b4 = *reinterpret_cast<const float4*>(Bs + n);
-        const uint2 v = pack4((acc[bn][4 * g] + b4.x) * rm_l, (acc[bn][4 * g + 1] + b4.y) * rm_l,
-                              (acc[bn][4 * g + 2] + b4.z) * rm_l, (acc[bn][4 * g + 3] + b4.w) * rm_l);
-        *reinterpret_cast<uint2*>(As + (32 * wm + r) * AP + n) = v;
-      }
+    pack_tile<true, true>(acc, Bs, rm_l, As, ln);                    // At = slice 0's region
     __syncthreads();
     PH(3);
-    coop_store_rows(wn_out, H, As, m0, R);                           // whole rows from the tile (see coop_store_rows)
-    // end conv: [m | logs] = wn_out @ Wend^T + b   (N = 160: blocks 0..4, block 5 is the image's zero padding)
+    coop_store_rows(static_cast<bf16_t*>(a.wn_out), H, As, m0, R);   // whole rows from the tile (see coop_store_rows)
+    // end conv: [m | logs] = wn_out @ Wend^T + b
     // the coupling's inputs (this block's y, written by the previous launch) fly under the end conv
     float4 cy0[5], cy1[5];
     float crm[5];
@@ -309,17 +378,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
     acc_zero<3>(acc2);
     gemm_run<3, H / 16>(static_cast<const bf16_t*>(a.w_end), a.ks_end, 3 * wn, As + (32 * wm + r) * AP + 8 * h, lane, ring2, acc2);
     PH(4);
-#pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
-        if (n < C) {
-          const float4 b4 = *reinterpret_cast<const float4*>(Bs + H + n);
-          *reinterpret_cast<float4*>(Ot + (32 * wm + r) * ZP + n) =
-              make_float4(acc2[bn][4 * g] + b4.x, acc2[bn][4 * g + 1] + b4.y, acc2[bn][4 * g + 2] + b4.z, acc2[bn][4 * g + 3] + b4.w);
-        }
-      }
+    end_epilogue(acc2, Bs + H, Ot, ln);
     __syncthreads();
     PH(5);
     // affine coupling on (row, 4 channels): z = [y0 | (m + exp(logs) y1) mask]
@@ -333,20 +392,16 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
         const float4 lr = *reinterpret_cast<const float4*>(Ot + row * ZP + HALF + c);
         z0 = cy0[k];
         const float4 y1 = cy1[k];
-        float lg[4] = {lr.x, lr.y, lr.z, lr.w};
-        if (a.sigmoid_scale) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) lg[j] = __logf(1e-6f + sigmoidf_(lg[j] + 2.0f));
-        }
-        z1 = make_float4((mm.x + __expf(lg[0]) * y1.x) * rm, (mm.y + __expf(lg[1]) * y1.y) * rm,
-                         (mm.z + __expf(lg[2]) * y1.z) * rm, (mm.w + __expf(lg[3]) * y1.w) * rm);
+        float lg[4] = {lr.x, lr.y, lr.z, lr.w}; fr::coupling_lg(lg, a.sigmoid_scale);
+        z1 = make_float4(fr::coupling_fwd(mm.x, lg[0], y1.x, rm), fr::coupling_fwd(mm.y, lg[1], y1.y, rm),
+                         fr::coupling_fwd(mm.z, lg[2], y1.z, rm), fr::coupling_fwd(mm.w, lg[3], y1.w, rm));
         if (a.z) {
           *reinterpret_cast<float4*>(a.z + (size_t)gm * C + c) = z0;
           *reinterpret_cast<float4*>(a.z + (size_t)gm * C + HALF + c) = z1;
         }
         if (a.z_bct) {                                             // the unsqueeze: straight into [B, 80, T] (pre-zeroed by the caller)
           const int b = (int)a.rowbatch[gm], t = a.rowframe[gm];
-          if (t >= 0 && t < a.len[b]) { sq_scatter4(a.z_bct, b, t, c, a.T, z0); sq_scatter4(a.z_bct, b, t, HALF + c, a.T, z1); }
+          if (t >= 0 && t < a.len[b]) { fr::sq_scatter4(a.z_bct, b, t, c, a.T, HALF, z0); fr::sq_scatter4(a.z_bct, b, t, HALF + c, a.T, HALF, z1); }
         }
         *reinterpret_cast<float4*>(a.logs_raw + (size_t)gm * HALF + c) = lr;       // the backward needs logs only
         const float s = (lg[0] + lg[1] + lg[2] + lg[3]) * rm;
@@ -367,25 +422,14 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
     }
     PH(7);
   } else {
-    // first block: the squeezed mel rows are the flow state
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-      const int item = threadIdx.x + 256 * k, row = item / 40, c = 4 * (item - row * 40), gm = m0 + row;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (gm < R) {
-        if (a.y_bct) {                                             // the squeeze: straight from [B, 80, T]
-          const int b = (int)a.rowbatch[gm], t = a.rowframe[gm];
-          if (t >= 0 && t < a.len[b]) v = sq_gather4(a.y_bct, b, t, c, a.T);
-          if (a.z) *reinterpret_cast<float4*>(a.z + (size_t)gm * C + c) = v;    // the squeezed rows: ActNorm's input, kept for the backward
-        } else v = *reinterpret_cast<const float4*>(a.x_in + (size_t)gm * C + c);
-      }
-      *reinterpret_cast<float4*>(Zt + row * ZP + c) = v;
-    }
+    // first block: the squeezed mel rows are the flow state (gathered, they are ActNorm's input and kept in z for the backward)
+    first_rows<false>(a.y_bct, a.x_in, a.z, a.rowbatch, a.rowframe, a.len, a.T, m0, R,
+               [&](int row, int c, const float4& v) { *reinterpret_cast<float4*>(Zt + row * ZP + c) = v; });
     __syncthreads();
   }
   if (!HEAD) return;
 
-  // ActNorm + InvConvNear of the next block on (row, channel group g): members {2g, 2g+1, 80+2g, 80+2g+1}
+  // ActNorm + InvConvNear of the next block on (row, channel group g)
   bf16_t* X0t = reinterpret_cast<bf16_t*>(smem + F_AS);      // At is dead: every wave is past the end conv
   WRing<3, HALF / 16> ring3;                                 // the start conv's weights fly under the ActNorm / InvConvNear phase
   gemm_prefetch<3, HALF / 16>(static_cast<const bf16_t*>(a.w_start), a.ks_start, 3 * wn, lane, ring3);
@@ -399,9 +443,9 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
     constexpr int NPH = 256 / G;                               // 6 row phases of 40 threads (16 threads idle)
     const int g = threadIdx.x % G, ph = threadIdx.x / G;
     if (ph < NPH) {
-      const float e0 = __expf(a.an_logs[2 * g]), e1 = __expf(a.an_logs[2 * g + 1]);
-      const float e2 = __expf(a.an_logs[HALF + 2 * g]), e3 = __expf(a.an_logs[HALF + 2 * g + 1]);
-      const float c0 = a.an_bias[2 * g], c1 = a.an_bias[2 * g + 1], c2 = a.an_bias[HALF + 2 * g], c3 = a.an_bias[HALF + 2 * g + 1];
+      int ch[4]; fr::group_channels(g, HALF, ch);
+      const float el[4] = {__expf(a.an_logs[ch[0]]), __expf(a.an_logs[ch[1]]), __expf(a.an_logs[ch[2]]), __expf(a.an_logs[ch[3]])};
+      const float bs[4] = {a.an_bias[ch[0]], a.an_bias[ch[1]], a.an_bias[ch[2]], a.an_bias[ch[3]]};
 #pragma unroll
       for (int k = 0; k < (BM + NPH - 1) / NPH; ++k) {
         const int row = ph + NPH * k, gm = m0 + row;
@@ -409,10 +453,9 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
           const float rm = Rm[row];
           const float2 xa = *reinterpret_cast<const float2*>(Zt + row * ZP + 2 * g);
           const float2 xb = *reinterpret_cast<const float2*>(Zt + row * ZP + HALF + 2 * g);
-          const float a0 = c0 + e0 * xa.x, a1 = c1 + e1 * xa.y, a2 = c2 + e2 * xb.x, a3 = c3 + e3 * xb.y;
+          const float xv[4] = {xa.x, xa.y, xb.x, xb.y};
           float o[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) o[q] = (Wm[q * 4] * a0 + Wm[q * 4 + 1] * a1 + Wm[q * 4 + 2] * a2 + Wm[q * 4 + 3] * a3) * rm;
+          fr::actnorm_invconv_fwd(xv, el, bs, Wm, rm, o);
           const uint32_t p01 = pack2bf(o[0], o[1]);
           if (gm < R) {
             *reinterpret_cast<float2*>(a.y_next + (size_t)gm * C + 2 * g) = make_float2(o[0], o[1]);
@@ -426,45 +469,25 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_fwd_kernel(gt_boundary_fwd
   }
   __syncthreads();
   PH(8);
-  // start conv: h = (y0 @ Wstart^T + b) * mask   (K = 80: 5 k-steps)
-  {
-    f32x16_t acc3[3];
-    acc_zero<3>(acc3);
-    gemm_run<3, HALF / 16>(static_cast<const bf16_t*>(a.w_start), a.ks_start, 3 * wn, X0t + (32 * wm + r) * XP + 8 * h, lane, ring3, acc3);
-    PH(9);
-    bf16_t* h0 = static_cast<bf16_t*>(a.h_next);
-    bf16_t* Hst = reinterpret_cast<bf16_t*>(smem + F_O);             // the m | logs tile is dead: the h tile on its way out
-#pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
-        const float4 b4 = *reinterpret_cast<const float4*>(Bs + 2 * H + n);
-        *reinterpret_cast<uint2*>(Hst + (32 * wm + r) * AP + n) =
-            pack4((acc3[bn][4 * g] + b4.x) * rm_l, (acc3[bn][4 * g + 1] + b4.y) * rm_l,
-                  (acc3[bn][4 * g + 2] + b4.z) * rm_l, (acc3[bn][4 * g + 3] + b4.w) * rm_l);
-      }
-    __syncthreads();
-    PH(10);
-    coop_store_rows(h0, H, Hst, m0, R);
-  }
+  // start conv through the dead m | logs tile
+  start_conv_stage<true>(static_cast<const bf16_t*>(a.w_start), a.ks_start, ring3, X0t, Bs + 2 * H, rm_l, reinterpret_cast<bf16_t*>(smem + F_O),
+                   static_cast<bf16_t*>(a.h_next), m0, R, ln);
   if (TAIL && wave == 0) {                                   // the coupling's log-det (row sums folded in LDS above)
     const int gm = m0 + lane < R ? m0 + lane : R - 1;
     utt_atomic_add(a.logdet, rowsum[lane], a.rowutt[gm], lane);
   }
-  if (blockIdx.x == 0) {                                     // ActNorm + InvConvNear's log-det: (sum logs + (C/4) logdet W) * len_b
-    const float per_frame = a.scal[0] + (float)G * a.scal[1];
+  if (blockIdx.x == 0) {                                     // ActNorm + InvConvNear's log-det
+    const float per_frame = fr::pair_logdet_per_frame(a.scal, G);
     for (int b = threadIdx.x; b < a.B; b += 256) atomicAdd(a.logdet + b, per_frame * (float)a.len[b]);
   }
   PH(11);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
-// ActNorm / InvConvNear parameter gradients of one workgroup: the four row phases' sums (sL, sB [4][64][4], sW [4][16] in LDS) ->
-// one atomic per channel
 constexpr int PG = 2 * C + 16;                 // a workgroup's partial sums: d logs [C] | d bias [C] | d W [16]
 
-// The same sums as ONE ROW of partials per workgroup (plain stores; gt_boundary_param_reduce adds the rows up after the pass):
+// ActNorm / InvConvNear parameter gradients of one workgroup, from the four row phases' sums in LDS (fr::param_fold): as atomics
+// (fr::param_fold_atomics), or as ONE ROW of partials per workgroup (plain stores; gt_boundary_param_reduce adds the rows up after the pass):
 // 152 workgroups adding to the same 336 addresses serialise at L2 — ~10 us per launch that either sit in front of every later
 // wait (issued mid-kernel) or hold the kernel open (issued at its end).  extra = this launch's log-det bookkeeping term (workgroup 0).
 __device__ __forceinline__ void param_grad_partials(const gt_boundary_bwd_args& a, const float* sL, const float* sB, const float* sW, float extra)
@@ -474,27 +497,14 @@ __device__ __forceinline__ void param_grad_partials(const gt_boundary_bwd_args& 
     if (t < 2 * C) {
       const int c = t < C ? t : t - C, hi = c >= HALF, cc = c - HALF * hi, g = cc >> 1, k = 2 * hi + (cc & 1);
       const float* sp = t < C ? sL : sB;
-      float v = sp[g * 4 + k] + sp[(64 + g) * 4 + k] + sp[(128 + g) * 4 + k] + sp[(192 + g) * 4 + k];
+      float v = fr::fold4(sp, g, k);
       if (t < C) v += extra;
       row[t] = v;
     } else {
       const int i = t - 2 * C;
-      row[t] = sW[i] + sW[16 + i] + sW[32 + i] + sW[48 + i] + (float)G * extra * a.scal[2 + i];
+      row[t] = fr::fold4W(sW, i) + (float)G * extra * a.scal[2 + i];
     }
   }
-}
-
-__device__ __forceinline__ void param_grad_atomics(const gt_boundary_bwd_args& a, const float* sL, const float* sB, const float* sW, int ph, int g)
-{
-  if (ph == 0 && g < G) {
-    const int ch[4] = {2 * g, 2 * g + 1, HALF + 2 * g, HALF + 2 * g + 1};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      atomicAdd(a.d_an_logs + ch[k], sL[g * 4 + k] + sL[(64 + g) * 4 + k] + sL[(128 + g) * 4 + k] + sL[(192 + g) * 4 + k]);
-      atomicAdd(a.d_an_bias + ch[k], sB[g * 4 + k] + sB[(64 + g) * 4 + k] + sB[(128 + g) * 4 + k] + sB[(192 + g) * 4 + k]);
-    }
-  }
-  if (threadIdx.x < 16) atomicAdd(a.d_w_ic + threadIdx.x, sW[threadIdx.x] + sW[16 + threadIdx.x] + sW[32 + threadIdx.x] + sW[48 + threadIdx.x]);
 }
 
 constexpr int B_DH = 0;                                    // d h tile [64][AP] bf16; later d wn_out tile
@@ -515,6 +525,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
   bf16_t* Dh = reinterpret_cast<bf16_t*>(smem + B_DH);
   float* Dt = reinterpret_cast<float*>(smem + B_D);
   bf16_t* Dout = reinterpret_cast<bf16_t*>(smem + B_DO);
+  const Lane ln{lane, r, h, wm, wn};
   const int mrow = m0 + 32 * wm + r;
   const float rm_l = mrow < R ? a.rowmask[mrow] : 0.0f;
   PH(0);
@@ -551,25 +562,17 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
     float* sW = sB + 4 * 64 * 4;
     float* sred = sW + 4 * 16;
     float extra = 0.f;
-    if (blockIdx.x == 0) {                                   // backward of the log-det bookkeeping (see flow_ops.hip)
-      float sv = 0.f;
-      for (int b = threadIdx.x; b < a.B; b += 256) sv += a.dlogdet[b] * (float)a.len[b];
-      sv = wave_sum(sv);
-      if (lane == 0) sred[wave] = sv;
-      __syncthreads();
-      sv = sred[0] + sred[1] + sred[2] + sred[3];
+    if (blockIdx.x == 0) {                                   // backward of the log-det bookkeeping
+      const float sv = fr::dlogdet_len_sum(a.dlogdet, a.len, a.B, sred);
       if (a.pg_partial) extra = sv;
-      else {
-        for (int c = threadIdx.x; c < C; c += 256) atomicAdd(a.d_an_logs + c, sv);
-        if (threadIdx.x < 16) atomicAdd(a.d_w_ic + threadIdx.x, (float)G * sv * a.scal[2 + threadIdx.x]);
-      }
+      else fr::pair_logdet_bwd_atomics(a.d_an_logs, a.d_w_ic, a.scal, sv, C);
     }
     const int g = lane, ph = wave;
     float accW[16], accL[4] = {0, 0, 0, 0}, accB[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int i = 0; i < 16; ++i) accW[i] = 0.f;
     if (g < G) {
-      const int ch[4] = {2 * g, 2 * g + 1, HALF + 2 * g, HALF + 2 * g + 1};
+      int ch[4]; fr::group_channels(g, HALF, ch);
       float el[4], bs[4], Wm[16];
 #pragma unroll
       for (int k = 0; k < 4; ++k) { el[k] = __expf(a.an_logs[ch[k]]); bs[k] = a.an_bias[ch[k]]; }
@@ -597,6 +600,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
           const float2 ds = *reinterpret_cast<const float2*>(Dt + row * ZP + 2 * g);
           const float xv[4] = {xa[u].x, xa[u].y, xb[u].x, xb[u].y};
           const float dym[4] = {(da[u].x + ds.x) * rm, (da[u].y + ds.y) * rm, db[u].x * rm, db[u].y * rm};
+          // (fr::actnorm_invconv_bwd's text: through the leaf other pairs are packed, other products contract, the last bits change)
           float av[4], d_a[4], dxv[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) av[k] = bs[k] + el[k] * xv[k];
@@ -614,8 +618,8 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
           } else if (gm < R) {
             if (a.dx_bct) {                                        // the unsqueeze of the decoder's input gradient
               const int b = (int)a.rowbatch[gm], t = a.rowframe[gm];
-              if (t >= 0 && t < a.len[b]) {
-                float* d0 = a.dx_bct + ((size_t)b * HALF + 2 * g) * a.T + 2 * t;
+              if (t >= 0 && t < a.len[b]) {                      // (fr::unsq_scatter_group's text: through the leaf <1,0>'s row loads merge
+                float* d0 = a.dx_bct + ((size_t)b * HALF + 2 * g) * a.T + 2 * t;   // otherwise and its launch is 0.2 - 0.5 us slower)
                 d0[0] = dxv[0]; d0[(size_t)a.T] = dxv[1]; d0[1] = dxv[2]; d0[(size_t)a.T + 1] = dxv[3];
               }
             } else {
@@ -628,14 +632,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
     }
     PH(3);
     // one atomic per channel per workgroup (same-address float atomics serialise at L2): fold the row phases in LDS
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { sL[(ph * 64 + g) * 4 + k] = accL[k]; sB[(ph * 64 + g) * 4 + k] = accB[k]; }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) accW[i] = wave_sum(accW[i]);
-    if (g == 0) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) sW[ph * 16 + i] = accW[i];
-    }
+    fr::param_fold(sL, sB, sW, ph, g, accL, accB, accW);
     __syncthreads();
     // The workgroup's 336 parameter-gradient atomics (152 workgroups add to the same 336 addresses: they serialise at L2 and take
     // microseconds to retire) are issued at the END of the kernel: vector-memory operations retire in order, so issued here every
@@ -644,23 +641,13 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
     PH(4);
     if (a.pg_partial) param_grad_partials(a, sL, sB, sW, extra);     // plain stores: nothing later waits long for them
     if (!TAILB) {
-      if (!a.pg_partial) param_grad_atomics(a, sL, sB, sW, wave, lane);
+      if (!a.pg_partial) fr::param_fold_atomics(a.d_an_logs, a.d_an_bias, a.d_w_ic, sL, sB, sW, wave, lane, G, HALF);
       return;
     }
   } else {
     // last block: the squeezed gradient of the decoder's output is d z
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-      const int item = threadIdx.x + 256 * k, row = item / 40, c = 4 * (item - row * 40), gm = m0 + row;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (gm < R) {
-        if (a.dz_bct) {
-          const int b = (int)a.rowbatch[gm], t = a.rowframe[gm];
-          if (t >= 0 && t < a.len[b]) v = sq_gather4(a.dz_bct, b, t, c, a.T);
-        } else v = *reinterpret_cast<const float4*>(a.dz_in + (size_t)gm * C + c);
-      }
-      *reinterpret_cast<float4*>(Dt + row * ZP + c) = v;
-    }
+    first_rows<false>(a.dz_bct, a.dz_in, nullptr, a.rowbatch, a.rowframe, a.len, a.T, m0, R,
+               [&](int row, int c, const float4& v) { *reinterpret_cast<float4*>(Dt + row * ZP + c) = v; });
     __syncthreads();
   }
 
@@ -693,11 +680,9 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
         float dx1[4], dlg[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          float lg = lraw[j], dl_draw = 1.0f;
-          if (a.sigmoid_scale) { const float sg = sigmoidf_(lraw[j] + 2.0f); lg = __logf(1e-6f + sg); dl_draw = sg * (1.0f - sg) / (1e-6f + sg); }
-          const float e = __expf(lg);
-          dx1[j] = dz1[j] * e;
-          dlg[j] = (dz1[j] * e * y1v[j] + dld) * dl_draw;
+          float dl_draw;
+          const float lg = fr::coupling_lg(lraw[j], a.sigmoid_scale, dl_draw);
+          fr::coupling_bwd(dz1[j], lg, dl_draw, y1v[j], dld, dx1[j], dlg[j]);
         }
         *reinterpret_cast<float4*>(a.dx_out + (size_t)gm * C + c) = dz0;
         *reinterpret_cast<float4*>(a.dx_out + (size_t)gm * C + HALF + c) = make_float4(dx1[0], dx1[1], dx1[2], dx1[3]);
@@ -726,6 +711,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
     for (int p = 0; p < RD; ++p)                             // the skip stage's first fragments fly under this epilogue
 #pragma unroll
       for (int bn = 0; bn < 3; ++bn) ring3[p][bn] = ldfrag(Wsd, (6 * (p / KS2) + 3 * wn + bn) * a.ks_skip_d + p % KS2, lane);
+    // (its own copy of pack_tile<false, true>: through the shared step <false, true> takes 218 VGPRs and loses its second wave)
 #pragma unroll
     for (int bn = 0; bn < 3; ++bn)
 #pragma unroll
@@ -740,6 +726,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
   coop_store_rows(static_cast<bf16_t*>(a.dwn_out), H, At, m0, R);
   PH(8);
   // skip data gradient: d acts_l (skip path) = d wn_out @ Wskip_l, one layer window per pass
+  // (its own ring loop, not skip_gemm's: four ACCUMULATOR windows over one resident tile, fragment address 6 (st / 12) + 3 wn + bn)
   bf16_t* via = static_cast<bf16_t*>(a.via_skip);
   const bf16_t* brow = At + (32 * wm + r) * AP + 8 * h;
 #pragma unroll
@@ -769,20 +756,14 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_bwd_kernel(gt_boundary_bwd
     }
     // out through one of two dead tiles (the fp32 gradient tile / the d[m | logs] tile), alternating: one barrier per layer window
     bf16_t* Vst = reinterpret_cast<bf16_t*>(smem + ((l & 1) ? B_DO : B_D));
-#pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
-        *reinterpret_cast<uint2*>(Vst + (32 * wm + r) * AP + n) = pack4(acc[bn][4 * g], acc[bn][4 * g + 1], acc[bn][4 * g + 2], acc[bn][4 * g + 3]);
-      }
+    pack_tile<false, false>(acc, nullptr, 0.0f, Vst, ln);
     __syncthreads();
     coop_store_rows(via + l * H, a.ldvs, Vst, m0, R);
     PH(9 + l);
   }
   if (HEADB && !a.pg_partial) {
     const float* sL = reinterpret_cast<const float*>(smem + B_RED);
-    param_grad_atomics(a, sL, sL + 4 * 64 * 4, sL + 2 * 4 * 64 * 4, wave, lane);
+    fr::param_fold_atomics(a.d_an_logs, a.d_an_bias, a.d_w_ic, sL, sL + 4 * 64 * 4, sL + 2 * 4 * 64 * 4, wave, lane, G, HALF);
   }
 }
 
@@ -810,7 +791,7 @@ __global__ __launch_bounds__(384) void gt_boundary_param_reduce_kernel(const flo
 //   [head of block b-1]  x0 = bf16(x[:, :C/2]) -> start conv (K = 80) -> h (HBM: the next WaveNet's input)
 // No log-det and nothing kept for a backward: wn_out, m | logs and x0 never leave LDS.  Same tiles, pitches, weight rings and
 // rounding points (bf16 acts, wn_out, x0) as the forward kernel and as the launch sequence it replaces (gt_conv_gemm_bf16 x 3,
-// gt_coupling_rev, gt_actnorm_invconv_rev), whose elementwise formulas are restated here term by term.
+// gt_coupling_rev, gt_actnorm_invconv_rev), whose elementwise formulas are flow_rows.h's (coupling_inv, actnorm_invconv_inv).
 constexpr int REV_LDS = FWD_LDS;               // the forward's layout: acts slices / At / x0 tile, m | logs tile, u tile, biases, row mask
 
 template <bool TAIL, bool HEAD>
@@ -826,62 +807,23 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_rev_kernel(gt_boundary_rev
   float* Ot = reinterpret_cast<float*>(smem + F_O);
   float* Zt = reinterpret_cast<float*>(smem + F_Z);
   bf16_t* X0t = reinterpret_cast<bf16_t*>(smem + F_AS);      // the x0 tile takes At's place once the end conv is done
+  const Lane ln{lane, r, h, wm, wn};
   const int mrow = m0 + 32 * wm + r;                        // this lane's row in the MFMA epilogues
   const float rm_l = mrow < R ? a.rowmask[mrow] : 0.0f;
-  float* Bs = reinterpret_cast<float*>(smem + F_BIAS);       // b_skip [192] | b_end [160 (+ 32 zero)] | b_start [192], staged once
-  if (threadIdx.x < 3 * H / 4) {
-    const int which = threadIdx.x / (H / 4), o = threadIdx.x - which * (H / 4);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (which == 0) { if (TAIL) v = reinterpret_cast<const float4*>(a.b_skip)[o]; }
-    else if (which == 1) { if (TAIL && o < C / 4) v = reinterpret_cast<const float4*>(a.b_end)[o]; }
-    else if (HEAD) v = reinterpret_cast<const float4*>(a.b_start)[o];
-    reinterpret_cast<float4*>(Bs)[threadIdx.x] = v;
-  }
-  float* Rm = Bs + 3 * H;                                    // the tile's row mask
-  if (threadIdx.x >= 192) {
-    const int row = threadIdx.x - 192;
-    Rm[row] = m0 + row < R ? a.rowmask[m0 + row] : 0.0f;
-  }
+  float* Bs = reinterpret_cast<float*>(smem + F_BIAS);
+  float* Rm = Bs + 3 * H;
+  stage_bias_mask<TAIL, HEAD>(Bs, a.b_skip, a.b_end, a.b_start, a.rowmask, m0, R);
   WRing<3, HALF / 16> ring3;                                 // the start conv's weights: they depend on nothing computed here
 
   if (TAIL) {
-    const bf16_t* acts = static_cast<const bf16_t*>(a.acts);
-    const bf16_t* Wskip = static_cast<const bf16_t*>(a.w_skip);
-    u32x4_t xr[NL][6];                                      // the tile's gated activations, all four layers, in flight together
-#pragma unroll
-    for (int l = 0; l < NL; ++l)
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const int chunk = threadIdx.x + 256 * i, row = chunk / 24, c8 = chunk - row * 24;
-        const int gm = m0 + row < R ? m0 + row : R - 1;
-        xr[l][i] = *reinterpret_cast<const u32x4_t*>(acts + (size_t)gm * a.ldacts + l * H + c8 * 8);
-      }
-    // skip GEMM: wn_out = bf16((acts @ Wskip^T + b) * mask);  wave (wm, wn): rows 32 wm .., column blocks 3 wn ..
+    u32x4_t xr[NL][6];
+    load_acts(xr, static_cast<const bf16_t*>(a.acts), a.ldacts, m0, R);
+    // skip GEMM: wn_out = bf16((acts @ Wskip^T + b) * mask)
     f32x16_t acc[3];
-    acc_zero<3>(acc);
-    constexpr int KK = NL * H / 16;                         // 48 k-steps
-    uint4 ring[RD][3];
-#pragma unroll
-    for (int p = 0; p < RD; ++p)
-#pragma unroll
-      for (int bn = 0; bn < 3; ++bn) ring[p][bn] = ldfrag(Wskip, (3 * wn + bn) * KK + p, lane);
-    skip_slice<0>(xr[0], As, Wskip, wm, wn, r, h, lane, ring, acc);
-    skip_slice<1>(xr[1], As, Wskip, wm, wn, r, h, lane, ring, acc);
-    skip_slice<2>(xr[2], As, Wskip, wm, wn, r, h, lane, ring, acc);
-    skip_slice<3>(xr[3], As, Wskip, wm, wn, r, h, lane, ring, acc);
+    skip_gemm<false>(xr, As, static_cast<const bf16_t*>(a.w_skip), ln, acc);
     WRing<3, H / 16> ring2;                                 // the end conv's first weight fragments fly under this epilogue
     gemm_prefetch<3, H / 16>(static_cast<const bf16_t*>(a.w_end), a.ks_end, 3 * wn, lane, ring2);
-    // every wave is past slices 0..2 (the barrier before slice 3): At = slice 0's region
-#pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
-        const float4 b4 = *reinterpret_cast<const float4*>(Bs + n);
-        *reinterpret_cast<uint2*>(As + (32 * wm + r) * AP + n) =
-            pack4((acc[bn][4 * g] + b4.x) * rm_l, (acc[bn][4 * g + 1] + b4.y) * rm_l,
-                  (acc[bn][4 * g + 2] + b4.z) * rm_l, (acc[bn][4 * g + 3] + b4.w) * rm_l);
-      }
+    pack_tile<true, true>(acc, Bs, rm_l, As, ln);                    // At = slice 0's region
     __syncthreads();
     // the coupling's input (the flow state the previous launch wrote) flies under the end conv
     // (written out item by item: as an array filled in a loop the ten values were given a stack slot)
@@ -904,39 +846,24 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_rev_kernel(gt_boundary_rev
       *reinterpret_cast<float4*>(Zt + row * ZP + HALF + c) = v1;
     };
     z_put(0, za0, zb0); z_put(1, za1, zb1); z_put(2, za2, zb2); z_put(3, za3, zb3); z_put(4, za4, zb4);
-#pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
-        if (n < C) {
-          const float4 b4 = *reinterpret_cast<const float4*>(Bs + H + n);
-          *reinterpret_cast<float4*>(Ot + (32 * wm + r) * ZP + n) =
-              make_float4(acc2[bn][4 * g] + b4.x, acc2[bn][4 * g + 1] + b4.y, acc2[bn][4 * g + 2] + b4.z, acc2[bn][4 * g + 3] + b4.w);
-        }
-      }
+    end_epilogue(acc2, Bs + H, Ot, ln);
     __syncthreads();
-    // inverse coupling on (row, 4 channels): u = [z0 | (z1 - m) exp(-logs) mask]   (attentions.py:178-180, as gt_coupling_rev)
+    // inverse coupling on (row, 4 channels): u = [z0 | (z1 - m) exp(-logs) mask]   (attentions.py:178-180)
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
       const int item = threadIdx.x + 256 * k, row = item / 20, c = 4 * (item - row * 20);
       const float rm = Rm[row];
       const float4 mm = *reinterpret_cast<const float4*>(Ot + row * ZP + c);
       const float4 lr = *reinterpret_cast<const float4*>(Ot + row * ZP + HALF + c);
-      float lg[4] = {lr.x, lr.y, lr.z, lr.w};
-      if (a.sigmoid_scale) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) lg[j] = __logf(1e-6f + sigmoidf_(lg[j] + 2.0f));
-      }
+      float lg[4] = {lr.x, lr.y, lr.z, lr.w}; fr::coupling_lg(lg, a.sigmoid_scale);
       const float4 z1 = *reinterpret_cast<const float4*>(Zt + row * ZP + HALF + c);
       *reinterpret_cast<float4*>(Zt + row * ZP + HALF + c) =
-          make_float4((z1.x - mm.x) * __expf(-lg[0]) * rm, (z1.y - mm.y) * __expf(-lg[1]) * rm,
-                      (z1.z - mm.z) * __expf(-lg[2]) * rm, (z1.w - mm.w) * __expf(-lg[3]) * rm);
+          make_float4(fr::coupling_inv(mm.x, lg[0], z1.x, rm), fr::coupling_inv(mm.y, lg[1], z1.y, rm),
+                      fr::coupling_inv(mm.z, lg[2], z1.z, rm), fr::coupling_inv(mm.w, lg[3], z1.w, rm));
     }
     __syncthreads();
-    // InvConvNear^-1 then ActNorm^-1 on (row, channel group g), members {2g, 2g+1, 80+2g, 80+2g+1} (modules.py:647-652, 592-594, as
-    // gt_actnorm_invconv_rev): x = ((W^-1 u) mask - bias) exp(-logs) mask, W^-1[k][j] = scal[2 + 4 j + k].  thread = (group, row
-    // phase): the group's sixteen weights, four scales and four biases are formed once per thread
+    // InvConvNear^-1 then ActNorm^-1 on (row, channel group g) (modules.py:647-652, 592-594).  thread = (group, row phase): the group's
+    // sixteen weights, four scales and four biases are formed once per thread
     {
       constexpr int NPH = 256 / G;                             // 6 row phases of 40 threads (16 threads idle)
       const int g = threadIdx.x % G, ph = threadIdx.x / G;
@@ -944,9 +871,9 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_rev_kernel(gt_boundary_rev
         float Wi[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) Wi[i] = a.scal[2 + i];
-        const float e0 = __expf(-a.an_logs[2 * g]), e1 = __expf(-a.an_logs[2 * g + 1]);
-        const float e2 = __expf(-a.an_logs[HALF + 2 * g]), e3 = __expf(-a.an_logs[HALF + 2 * g + 1]);
-        const float c0 = a.an_bias[2 * g], c1 = a.an_bias[2 * g + 1], c2 = a.an_bias[HALF + 2 * g], c3 = a.an_bias[HALF + 2 * g + 1];
+        int ch[4]; fr::group_channels(g, HALF, ch);
+        const float eli[4] = {__expf(-a.an_logs[ch[0]]), __expf(-a.an_logs[ch[1]]), __expf(-a.an_logs[ch[2]]), __expf(-a.an_logs[ch[3]])};
+        const float bs[4] = {a.an_bias[ch[0]], a.an_bias[ch[1]], a.an_bias[ch[2]], a.an_bias[ch[3]]};
 #pragma unroll
         for (int k = 0; k < (BM + NPH - 1) / NPH; ++k) {
           const int row = ph + NPH * k, gm = m0 + row;
@@ -954,10 +881,9 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_rev_kernel(gt_boundary_rev
             const float rm = Rm[row];
             const float2 ua = *reinterpret_cast<const float2*>(Zt + row * ZP + 2 * g);
             const float2 ub = *reinterpret_cast<const float2*>(Zt + row * ZP + HALF + 2 * g);
+            const float uv[4] = {ua.x, ua.y, ub.x, ub.y};
             float o[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = (Wi[q] * ua.x + Wi[4 + q] * ua.y + Wi[8 + q] * ub.x + Wi[12 + q] * ub.y) * rm;
-            o[0] = (o[0] - c0) * e0 * rm; o[1] = (o[1] - c1) * e1 * rm; o[2] = (o[2] - c2) * e2 * rm; o[3] = (o[3] - c3) * e3 * rm;
+            fr::actnorm_invconv_inv<false>(uv, eli, bs, Wi, rm, o);
             if (gm < R) {
               if (a.x) {
                 *reinterpret_cast<float2*>(a.x + (size_t)gm * C + 2 * g) = make_float2(o[0], o[1]);
@@ -965,10 +891,7 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_rev_kernel(gt_boundary_rev
               }
               if (!HEAD && a.x_bct) {                                // the unsqueeze: straight into [B, 80, T] (pre-zeroed by the caller)
                 const int b = (int)a.rowbatch[gm], t = a.rowframe[gm];
-                if (t >= 0 && t < a.len[b]) {
-                  float* d0 = a.x_bct + ((size_t)b * HALF + 2 * g) * a.T + 2 * t;
-                  d0[0] = o[0]; d0[(size_t)a.T] = o[1]; d0[1] = o[2]; d0[(size_t)a.T + 1] = o[3];
-                }
+                if (t >= 0 && t < a.len[b]) fr::unsq_scatter_group(a.x_bct, b, t, g, a.T, HALF, o);
               }
             }
             if (HEAD) *reinterpret_cast<uint32_t*>(X0t + row * XP + 2 * g) = pack2bf(o[0], o[1]);
@@ -979,41 +902,27 @@ __global__ __launch_bounds__(256) void gt_wn_boundary_rev_kernel(gt_boundary_rev
   } else {
     // first launch of the pass: the squeezed latent rows are the flow state; only the start conv of the last block runs
     gemm_prefetch<3, HALF / 16>(static_cast<const bf16_t*>(a.w_start), a.ks_start, 3 * wn, lane, ring3);
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-      const int item = threadIdx.x + 256 * k, row = item / 40, c = 4 * (item - row * 40), gm = m0 + row;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (gm < R) {
-        if (a.z_bct) {                                             // the squeeze: straight from [B, 80, T]
-          const int b = (int)a.rowbatch[gm], t = a.rowframe[gm];
-          if (t >= 0 && t < a.len[b]) v = sq_gather4(a.z_bct, b, t, c, a.T);
-          *reinterpret_cast<float4*>(a.x + (size_t)gm * C + c) = v;  // the squeezed rows: what the next launch's tail reads
-        } else v = *reinterpret_cast<const float4*>(a.x_in + (size_t)gm * C + c);
-      }
+    // (gathered, the squeezed rows also go to x: what the next launch's tail reads)
+    first_rows<true>(a.z_bct, a.x_in, a.x, a.rowbatch, a.rowframe, a.len, a.T, m0, R, [&](int row, int c, const float4& v) {
       if (c < HALF) *reinterpret_cast<uint2*>(X0t + row * XP + c) = pack4(v.x, v.y, v.z, v.w);
-    }
+    });
   }
   if (!HEAD) return;
   __syncthreads();
-  // start conv of block b-1: h = (x0 @ Wstart^T + b) * mask   (K = 80: 5 k-steps)
-  {
-    f32x16_t acc3[3];
-    acc_zero<3>(acc3);
-    gemm_run<3, HALF / 16>(static_cast<const bf16_t*>(a.w_start), a.ks_start, 3 * wn, X0t + (32 * wm + r) * XP + 8 * h, lane, ring3, acc3);
-    bf16_t* Hst = reinterpret_cast<bf16_t*>(smem + F_O);             // the m | logs tile is dead: the h tile on its way out
-#pragma unroll
-    for (int bn = 0; bn < 3; ++bn)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n = 32 * (3 * wn + bn) + 8 * g + 4 * h;
-        const float4 b4 = *reinterpret_cast<const float4*>(Bs + 2 * H + n);
-        *reinterpret_cast<uint2*>(Hst + (32 * wm + r) * AP + n) =
-            pack4((acc3[bn][4 * g] + b4.x) * rm_l, (acc3[bn][4 * g + 1] + b4.y) * rm_l,
-                  (acc3[bn][4 * g + 2] + b4.z) * rm_l, (acc3[bn][4 * g + 3] + b4.w) * rm_l);
-      }
-    __syncthreads();
-    coop_store_rows(static_cast<bf16_t*>(a.h_next), H, Hst, m0, R);
-  }
+  // start conv of block b-1 through the dead m | logs tile
+  start_conv_stage<false>(static_cast<const bf16_t*>(a.w_start), a.ks_start, ring3, X0t, Bs + 2 * H, rm_l, reinterpret_cast<bf16_t*>(smem + F_O),
+                   static_cast<bf16_t*>(a.h_next), m0, R, ln);
+}
+
+// the three entries' launch: LDS opt-in (> 64 KB, once per process), the prefetch list's alignment, the grid, the form the halves select
+template <auto K11, auto K10, auto K01, class Args>
+int launch_boundary(const Args& a, bool first, bool second, int lds, void* stream, const char* who)
+{
+  if (gt_allow_lds<K11>(lds) || gt_allow_lds<K10>(lds) || gt_allow_lds<K01>(lds)) return GT_E_LAUNCH;
+  for (int i = 0; i < 16; ++i) if (a.pf_ptr[i] && (!al16(a.pf_ptr[i]) || (a.pf_bytes[i] & 15))) return GT_E_ALIGN;
+  const dim3 grid((a.R + BM - 1) / BM + (a.pf_ptr[0] ? PF_WGS : 0)), block(256);
+  hipLaunchKernelGGL(first && second ? K11 : (first ? K10 : K01), grid, block, lds, static_cast<hipStream_t>(stream), a);
+  return gt_launch_status(who);
 }
 
 }  // namespace
@@ -1048,16 +957,8 @@ extern "C" int gt_wn_boundary_fwd(const gt_boundary_fwd_args* args, void* stream
     if (a.ks_start < HALF / 16) return GT_E_INVAL;
     if (!al16(a.y_next) || !al16(a.y0_bf16) || !al16(a.w_start) || !al16(a.b_start) || !al16(a.h_next)) return GT_E_ALIGN;
   }
-  // > 64 KB of LDS: opt in once per process
-  if (gt_allow_lds<&gt_wn_boundary_fwd_kernel<true, true>>(FWD_LDS) || gt_allow_lds<&gt_wn_boundary_fwd_kernel<true, false>>(FWD_LDS) ||
-      gt_allow_lds<&gt_wn_boundary_fwd_kernel<false, true>>(FWD_LDS)) return GT_E_LAUNCH;
-  for (int i = 0; i < 16; ++i) if (a.pf_ptr[i] && (!al16(a.pf_ptr[i]) || (a.pf_bytes[i] & 15))) return GT_E_ALIGN;
-  const dim3 grid((a.R + BM - 1) / BM + (a.pf_ptr[0] ? PF_WGS : 0)), block(256);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (tail && head) hipLaunchKernelGGL((gt_wn_boundary_fwd_kernel<true, true>), grid, block, FWD_LDS, st, a);
-  else if (tail)    hipLaunchKernelGGL((gt_wn_boundary_fwd_kernel<true, false>), grid, block, FWD_LDS, st, a);
-  else              hipLaunchKernelGGL((gt_wn_boundary_fwd_kernel<false, true>), grid, block, FWD_LDS, st, a);
-  return gt_launch_status(__func__);
+  return launch_boundary<&gt_wn_boundary_fwd_kernel<true, true>, &gt_wn_boundary_fwd_kernel<true, false>, &gt_wn_boundary_fwd_kernel<false, true>>(
+      a, tail, head, FWD_LDS, stream, __func__);
 }
 
 extern "C" int gt_boundary_rev_args_size(void) { return (int)sizeof(gt_boundary_rev_args); }
@@ -1087,16 +988,8 @@ extern "C" int gt_wn_boundary_rev(const gt_boundary_rev_args* args, void* stream
     if (!a.w_start || !a.b_start || a.ks_start < HALF / 16) return GT_E_INVAL;
     if (!al16(a.w_start) || !al16(a.b_start) || !al16(a.h_next)) return GT_E_ALIGN;
   }
-  for (int i = 0; i < 16; ++i) if (a.pf_ptr[i] && (!al16(a.pf_ptr[i]) || (a.pf_bytes[i] & 15))) return GT_E_ALIGN;
-  // > 64 KB of LDS: opt in once per process
-  if (gt_allow_lds<&gt_wn_boundary_rev_kernel<true, true>>(REV_LDS) || gt_allow_lds<&gt_wn_boundary_rev_kernel<true, false>>(REV_LDS) ||
-      gt_allow_lds<&gt_wn_boundary_rev_kernel<false, true>>(REV_LDS)) return GT_E_LAUNCH;
-  const dim3 grid((a.R + BM - 1) / BM + (a.pf_ptr[0] ? PF_WGS : 0)), block(256);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (tail && head) hipLaunchKernelGGL((gt_wn_boundary_rev_kernel<true, true>), grid, block, REV_LDS, st, a);
-  else if (tail)    hipLaunchKernelGGL((gt_wn_boundary_rev_kernel<true, false>), grid, block, REV_LDS, st, a);
-  else              hipLaunchKernelGGL((gt_wn_boundary_rev_kernel<false, true>), grid, block, REV_LDS, st, a);
-  return gt_launch_status(__func__);
+  return launch_boundary<&gt_wn_boundary_rev_kernel<true, true>, &gt_wn_boundary_rev_kernel<true, false>, &gt_wn_boundary_rev_kernel<false, true>>(
+      a, tail, head, REV_LDS, stream, __func__);
 }
 
 extern "C" int gt_boundary_param_partials(void) { return PG; }
@@ -1133,13 +1026,6 @@ extern "C" int gt_wn_boundary_bwd(const gt_boundary_bwd_args* args, void* stream
     if (!al16(a.logs_raw) || !al16(a.y) || !al16(a.dout) || !al16(a.w_end_d) || !al16(a.dwn_out) || !al16(a.w_skip_d) || !al16(a.via_skip))
       return GT_E_ALIGN;
   }
-  if (gt_allow_lds<&gt_wn_boundary_bwd_kernel<true, true>>(BWD_LDS) || gt_allow_lds<&gt_wn_boundary_bwd_kernel<true, false>>(BWD_LDS) ||
-      gt_allow_lds<&gt_wn_boundary_bwd_kernel<false, true>>(BWD_LDS)) return GT_E_LAUNCH;
-  for (int i = 0; i < 16; ++i) if (a.pf_ptr[i] && (!al16(a.pf_ptr[i]) || (a.pf_bytes[i] & 15))) return GT_E_ALIGN;
-  const dim3 grid((a.R + BM - 1) / BM + (a.pf_ptr[0] ? PF_WGS : 0)), block(256);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (headb && tailb) hipLaunchKernelGGL((gt_wn_boundary_bwd_kernel<true, true>), grid, block, BWD_LDS, st, a);
-  else if (headb)     hipLaunchKernelGGL((gt_wn_boundary_bwd_kernel<true, false>), grid, block, BWD_LDS, st, a);
-  else                hipLaunchKernelGGL((gt_wn_boundary_bwd_kernel<false, true>), grid, block, BWD_LDS, st, a);
-  return gt_launch_status(__func__);
+  return launch_boundary<&gt_wn_boundary_bwd_kernel<true, true>, &gt_wn_boundary_bwd_kernel<true, false>, &gt_wn_boundary_bwd_kernel<false, true>>(
+      a, headb, tailb, BWD_LDS, stream, __func__);
 }

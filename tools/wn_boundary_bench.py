@@ -1,5 +1,6 @@
 """dev: per-launch time of the fused between-WaveNets kernels (csrc/wn_boundary.hip), graph-replayed on cfg2-shaped rows:
-the launches of one real decoder forward + backward are recorded (flow_impl.BOUNDARY_TRACE) and replayed back to back."""
+the launches of one real decoder forward + backward (train mode) and of one reverse pass (decoder_rev_fused, eval mode) are recorded
+(flow_impl.BOUNDARY_TRACE) and replayed back to back."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -25,6 +26,9 @@ z, blocks = flow_impl.decoder_fwd_fused(rc, dec, rows, [None] * nb, ld, True, 7)
 dld = torch.zeros(rc.B, device=dev)
 with wgrad.WgradQueue(dev, site=dec):
     flow_impl.decoder_bwd_fused(rc, dec, blocks, torch.randn_like(rows) * rc.rowmask[:, None], dld, False)
+dec.eval()
+flow_impl.decoder_rev_fused(rc, dec, torch.randn_like(rows) * rc.rowmask[:, None], [None] * nb)
+dec.train()
 torch.cuda.synchronize()
 flow_impl.BOUNDARY_TRACE = None
 st = lambda: _lib.current_stream(dev)
@@ -52,6 +56,7 @@ def timeit(name, calls, replays=20):
 
 fw = [t for t in trace if t[0].endswith("fwd")]
 bw = [t for t in trace if t[0].endswith("bwd")]
+rv = [t for t in trace if t[0].endswith("rev")]
 timeit("fwd tail + head (blocks 1..11)", fw[1:-1])
 
 
@@ -69,3 +74,6 @@ timeit("fwd tail only", [(fn, _lib.fill_args(_lib.BoundaryFwdArgs, **{k: v for k
 timeit("bwd head + tail", bw[1:-1])
 timeit("bwd tail only (dz_in = dx_in)", [(fn, _lib.fill_args(_lib.BoundaryBwdArgs, **{k: v for k, v in dict(kw, dh=None, dz_in=kw["dx_in"]).items() if v is not None}), kw) for fn, a, kw in bw[1:-1]])
 timeit("bwd head only", [(fn, _lib.fill_args(_lib.BoundaryBwdArgs, **{k: v for k, v in dict(kw, dout=None).items() if v is not None}), kw) for fn, a, kw in bw[1:-1]])
+timeit("rev tail + head (blocks 11..1)", rv[1:-1])
+timeit("rev head only (first launch, 11 times)", [rv[0]] * 11)
+timeit("rev tail only (last launch, 11 times)", [rv[-1]] * 11)
