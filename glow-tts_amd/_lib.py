@@ -239,6 +239,12 @@ PROTOTYPES = {
     "gt_dtw_f32": (STATUS, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int,
                             c_void_p, c_size_t, c_void_p, c_void_p]),
     "gt_dtw_f0_stats": (STATUS, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gt_wg_gate": (STATUS, [c_void_p, c_void_p]),
+    "gt_wg_gate_args_size": (c_int, []),
+    "gt_wg_tile_positions": (c_int, []),
+    "gt_wg_gate_lds_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gt_wg_boundary": (STATUS, [c_void_p, c_void_p]),
+    "gt_wg_boundary_args_size": (c_int, []),
 }
 c_void_p = ctypes.c_void_p
 
@@ -406,6 +412,24 @@ class VocosPolarArgs(ctypes.Structure):
                 ("n_fft", c_int)]
 
 
+class WgGateArgs(ctypes.Structure):
+    """struct gt_wg_gate_args (include/glowtts_hip.h); its size is checked against gt_wg_gate_args_size() (tests/test_waveglow_cabi.py)"""
+    _fields_ = [("X", c_void_p), ("x_stride_b", c_i64), ("ldx", c_int), ("Cs", c_int), ("S", c_void_p), ("s_stride_b", c_i64),
+                ("W_in", c_void_p), ("W_cond", c_void_p), ("b_in", c_void_p), ("b_cond", c_void_p), ("G", c_void_p), ("g_stride_b", c_i64),
+                ("len_mul", c_int), ("n_frames", c_void_p), ("B", c_int), ("L_cap", c_int), ("C", c_int), ("taps", c_int), ("dil", c_int)]
+
+
+class WgBoundaryArgs(ctypes.Structure):
+    """struct gt_wg_boundary_args (include/glowtts_hip.h); its size is checked against gt_wg_boundary_args_size() (tests/test_waveglow_cabi.py)"""
+    _fields_ = [("state", c_void_p), ("st_stride_b", c_i64), ("ld", c_int), ("C", c_int), ("A", c_void_p), ("a_stride_b", c_i64),
+                ("w_end", c_void_p), ("b_end", c_void_p), ("w_inv", c_void_p), ("w_start", c_void_p), ("b_start", c_void_p),
+                ("n_frames", c_void_p), ("seed_dev", c_void_p), ("seed", c_u32), ("sigma", c_float), ("len_mul", c_int), ("B", c_int),
+                ("L_cap", c_int), ("c_in", c_int), ("c_out", c_int)]
+
+
+WG_NOISE_STREAM, WG_MAX_C = 5, 512               # GT_WG_NOISE_STREAM, GT_WG_MAX_C
+
+
 # mirror -> its C struct in include/glowtts_hip.h (tests/test_cabi.py compares every size and field offset with a C compiler's)
 C_STRUCTS = {PackDesc: "gt_pack_desc", StepCopy: "gt_step_copy", StepCtx: "gt_step_ctx", StepInputsArgs: "gt_step_inputs_args",
              PartialsJob: "gt_partials_job", PartialsArgs: "gt_partials_args", StepZeroArgs: "gt_step_zero_args",
@@ -413,7 +437,7 @@ C_STRUCTS = {PackDesc: "gt_pack_desc", StepCopy: "gt_step_copy", StepCtx: "gt_st
              BoundaryBwdArgs: "gt_boundary_bwd_args", BoundaryRevArgs: "gt_boundary_rev_args", SynthPriorArgs: "gt_synth_prior_args",
              SynthCall: "gt_synth_call", SynthCallExt: "gt_synth_call_ext", VocConvArgs: "gt_voc_conv_args",
              VocSnakeArgs: "gt_voc_snake_args", VocosNormArgs: "gt_vocos_norm_args", VocosMlpArgs: "gt_vocos_mlp_args",
-             VocosPolarArgs: "gt_vocos_polar_args"}
+             VocosPolarArgs: "gt_vocos_polar_args", WgGateArgs: "gt_wg_gate_args", WgBoundaryArgs: "gt_wg_boundary_args"}
 
 
 def fill_args(cls, **kw):

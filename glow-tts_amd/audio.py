@@ -37,7 +37,12 @@ run by ONE HIP kernel (csrc/mel_front.hip: gt_mel_pack once, gt_mel_spectrogram 
                     gt_vocos_mlp (the block's MLP with the hidden activation kept on the chip) and gt_vocos_polar next to gt_voc_conv and
                     gt_istft; the published parameter tree (`load_vocos_state`, `from_config`), the capacity-sized form.
 
-  The three generators meet one contract, `_MelVocoder`: mel_channels, wav_len, buffer_spec(B, F_max), held, and the
+  WaveGlow          the published WaveGlow network in its `infer` direction (the vocoder Glow-TTS was published with): csrc/waveglow.hip's
+                    gt_wg_gate (a WaveNet layer's in_layer + conditioning slice + gate as one implicit GEMM) and gt_wg_boundary
+                    (everything between two WaveNets) next to gt_voc_conv (DESIGN.md 4.28); a seeded latent from the counter generator;
+                    the published parameter tree (`load_waveglow_state`, `from_config`), the capacity-sized form.
+
+  The generators meet one contract, `_MelVocoder`: mel_channels, wav_len, buffer_spec(B, F_max), held, and the
   shared forward / workspace / workspace_bytes / run that compile_synthesis(vocoder=) uses.
 
 Waveforms are fp32 in [-1, 1] or int16 (scaled by 1/32768 in the kernel = the reference's audio / max_wav_value).  There is no CPU
@@ -719,9 +724,12 @@ class _MelVocoder(nn.Module):
       hop_length, min_frames   F frames give wav_len(F) = hop_length (F - (min_frames - 1)) samples, none below min_frames
       mel_channels             what run takes per frame; forward takes mel_channels - mel_padding and zero-pads
       launches                 C-ABI calls per run
+      seeded                   True for a generator that draws a latent (WaveGlow): forward takes `seed`, run `seed_dev` / `seed`, and
+                               _walk receives both
     and supplies buffer_spec(B, F_max) (through _check_capacity), held() and _walk(mel, n_frames, bufs, B, F): the kernel calls."""
 
     min_frames, mel_padding = 1, 0
+    seeded = False
 
     def wav_len(self, frames):
         """samples of an utterance (or a buffer row) of `frames` frames"""
@@ -746,11 +754,14 @@ class _MelVocoder(nn.Module):
         bufs["wav"] = torch.empty(B, self.wav_len(F_max), dtype=torch.float32, device=device)
         return bufs
 
-    def run(self, mel, n_frames, bufs):
+    def run(self, mel, n_frames, bufs, seed_dev=None, seed=0):
         """kernel calls, the capacity-sized form for graph callers: fp32 log-mel [B, mel_channels, >= F_max] (any batch / channel pitch,
         frames contiguous), device int32 [B] frame counts and workspace's buffers (B and F_max are theirs) -> bufs["wav"]
         [B, wav_len(F_max)], row b zero behind its wav_len(F_b) samples.  `launches` C-ABI calls; nothing is allocated once the images
-        exist, n_frames is never looked at on the host, every grid is sized by F_max."""
+        exist, n_frames is never looked at on the host, every grid is sized by F_max.  A seeded vocoder draws its latent from `seed`,
+        or (seed_dev: a device uint32 / int32 word) from the word read on the device; the others take neither."""
+        if not self.seeded and (seed_dev is not None or seed):
+            raise ValueError(f"{type(self).__name__} draws no latent: it takes no seed")
         wav = bufs["wav"]
         B, F, C = wav.shape[0], wav.shape[1] // self.hop_length + self.min_frames - 1, self.mel_channels
         if not mel.is_cuda:
@@ -763,12 +774,14 @@ class _MelVocoder(nn.Module):
             raise ValueError("n_frames must be a contiguous int32 [B] on the device")
         if next(self.parameters()).device != mel.device:
             raise ValueError("the vocoder's parameters are not on the mel's device")
+        if self.seeded:
+            return self._walk(mel, n_frames, bufs, B, F, seed_dev=seed_dev, seed=seed)
         return self._walk(mel, n_frames, bufs, B, F)
 
-    def forward(self, mel, mel_lengths=None, mel_lengths_host=None):
+    def forward(self, mel, mel_lengths=None, mel_lengths_host=None, seed=0):
         """log-mel [B, mel_channels - mel_padding, F] -> wav [B, wav_len(F)]; with mel_lengths (frames per utterance) the ragged form
         -> (wav, wav_lengths = wav_len(mel_lengths)), zero behind each utterance.  mel_lengths_host spares the host a look at a device
-        tensor.  With mel_padding (Vocos's 100-band models) the mel is copied into a zero-padded one first."""
+        tensor.  With mel_padding (Vocos's 100-band models) the mel is copied into a zero-padded one first.  `seed`: a seeded vocoder's."""
         C = self.mel_channels - self.mel_padding
         if not mel.is_cuda:
             raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU tensor); there is no CPU fallback")
@@ -792,7 +805,7 @@ class _MelVocoder(nn.Module):
                 padded = mel.new_zeros(B, self.mel_channels, F)
                 padded[:, :C] = mel
                 mel = padded
-            wav = _MelVocoder.run(self, mel, n_frames, self.workspace(B, F, mel.device))    # not a subclass's refusal of a padded model
+            wav = _MelVocoder.run(self, mel, n_frames, self.workspace(B, F, mel.device), seed=seed)   # not a subclass's refusal of a padded model
         if mel_lengths is None:
             return wav
         lost = self.min_frames - 1
@@ -1390,4 +1403,241 @@ class Vocos(_MelVocoder):
         call.gt_vocos_polar(_lib.fill_args(_lib.VocosPolarArgs, O=o, o_stride_b=F * 2 * VOCOS_BINS, n_frames=n_frames, spec=spec, B=B,
                                            F_max=F, n_fft=self.n_fft), st)
         self.istft.synthesize(spec, n_frames, B, F, out=wav)
+        return wav
+
+
+# ---- WaveGlow: the reverse flow on csrc/waveglow.hip next to gt_voc_conv ------------------------------------------------
+WG_GROUP = 8                         # samples per group position: the one n_group the kernels implement
+WG_UP_KERNEL, WG_UP_STRIDE = 1024, 256
+
+
+def transposed_tail_as_conv(w, u):
+    """ConvTranspose1d weight [Cin, Cout, m u] (stride u, no padding, the last (m - 1) u outputs dropped: WaveGlow's upsampler) -> the
+    centred (2m - 1)-tap convolution weight [u * Cout, Cin, 2m - 1] with W[r * Cout + c, ci, m - 1 - j] = w[ci, c, r + u j] for j < m
+    and 0 in the m - 1 taps that look ahead: output u q + r reads inputs q - (m - 1) .. q only, w[., ., r + u j] meeting input q - j.
+    transposed_as_conv's generalisation to a kernel of m strides."""
+    Cin, Cout, k = w.shape
+    if u < 1 or k % u or k < u:
+        raise ValueError(f"the kernel is a multiple of the stride, got k = {k}, u = {u}")
+    m = k // u
+    W = w.new_zeros(u, Cout, Cin, 2 * m - 1)
+    W[..., :m] = w.detach().view(Cin, Cout, m, u).permute(3, 1, 0, 2).flip(3)
+    return W.reshape(u * Cout, Cin, 2 * m - 1)
+
+
+def gate_interleave(C):
+    """row order of gt_wg_gate's images: packed row 64 q + r is channel 32 q + r, packed row 64 q + 32 + r channel C + 32 q + r"""
+    return torch.arange(2 * C).view(2, C // 32, 32).permute(1, 0, 2).reshape(-1)
+
+
+class _WaveGlowWN(nn.Module):
+    """parameter holder under the published names: start, in_layers, cond_layer (the v5 layout: one 640 -> 2C n convolution),
+    res_skip_layers, end"""
+
+    def __init__(self, n_in, n_cond, n_layers, C, k):
+        super().__init__()
+        self.start = nn.Conv1d(n_in, C, 1)
+        self.in_layers = nn.ModuleList(nn.Conv1d(C, 2 * C, k, dilation=2 ** i, padding=2 ** i * (k - 1) // 2) for i in range(n_layers))
+        self.cond_layer = nn.Conv1d(n_cond, 2 * C * n_layers, 1)
+        self.res_skip_layers = nn.ModuleList(nn.Conv1d(C, 2 * C if i < n_layers - 1 else C, 1) for i in range(n_layers))
+        self.end = nn.Conv1d(C, 2 * n_in, 1)
+
+
+class _InvConv(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.conv = nn.Conv1d(c, c, 1, bias=False)
+
+
+class WaveGlow(_MelVocoder):
+    """The published WaveGlow network (Prenger et al. 2018) in its `infer` direction, eval mode, weight norm folded: from log-mel and a
+    seeded latent to waveform, every utterance of a ragged batch ON ITS OWN (utterance b is infer(mel[b:b+1, :, :F_b]) on its own rows of
+    the latent); F_b frames give 256 F_b samples.
+
+      upsample (ConvTranspose1d 80 -> 80, k 1024, stride 256, the last 768 outputs dropped: gt_voc_conv as a 7-tap convolution at frame
+      rate whose 20480 outputs per frame ARE spect [32 F, 640], channel 8 band + sample % 8) -> the latent's last n_remaining channels
+      (gt_wg_boundary, first form) -> per flow j = n_flows - 1 .. 0: WN_j as n x (gt_wg_gate: in_layer + conditioning slice + gate;
+      gt_voc_conv: res_skip onto the x | skip state) and one gt_wg_boundary (end, coupling inverse, inverse 1x1, early-output concat,
+      the next start): `launches` = 1 + n_flows 2 n + n_flows + 1, 206 for the published config.
+
+    Z[b, l, 2p], Z[b, l, 2p + 1] = sigma (e0, e1) of randn_pair(randn_key(seed, 5, b), l, p) (csrc/common.h, stream id 5): the flow starts
+    from Z[..., 8 - n_remaining:], every early-output point prepends the next two channels towards channel 0.  `seed` is forward's /
+    run's argument, or run's device word `seed_dev`.
+
+    Parameters are fp32 under the published names (upsample, WN.{j}.start / .in_layers.{i} / .cond_layer / .res_skip_layers.{i} / .end,
+    convinv.{j}.conv.weight); `load_waveglow_state` takes a published state dict.  Operands of the matrix products are bf16 (the packed
+    images; the mel, the residual stream as staged, spect, the gate's output), accumulation, the residual stream, the skip sum and
+    everything between two WaveNets fp32; the inverse of every 1x1 weight is formed on the host in float64.
+    Refused with ValueError: n_group != 8, kernel_size != 3, n_channels no multiple of 64 (or above 512), n_layers > 8, an upsampler
+    other than 1024 / 256, n_early_size != 2, an n_flows / n_early_every whose channel count leaves [2, 8], n_mel_channels != 80."""
+
+    seeded = True
+    hop_length, min_frames, mel_channels = WG_UP_STRIDE, 1, 80
+
+    def __init__(self, n_mel_channels=80, n_flows=12, n_group=8, n_early_every=4, n_early_size=2, n_layers=8, n_channels=256,
+                 kernel_size=3, sigma=0.666, upsample_kernel_size=1024, upsample_stride=256):
+        super().__init__()
+        n_flows, n_early_every, n_layers, C = int(n_flows), int(n_early_every), int(n_layers), int(n_channels)
+        if int(n_group) != WG_GROUP:
+            raise ValueError(f"WaveGlow: n_group is {WG_GROUP} (the kernels' 8 slots per position), got {n_group}")
+        if int(kernel_size) != 3:
+            raise ValueError(f"WaveGlow: kernel_size is 3, got {kernel_size}")
+        if C < 64 or C % 64 or C > _lib.WG_MAX_C:
+            raise ValueError(f"WaveGlow: n_channels is a multiple of 64 up to {_lib.WG_MAX_C}, got {n_channels}")
+        if n_layers < 1 or n_layers > 8:
+            raise ValueError(f"WaveGlow: n_layers is 1 .. 8 (dilation 2^7 = 128 is what the gate kernel's LDS holds), got {n_layers}")
+        if (int(upsample_kernel_size), int(upsample_stride)) != (WG_UP_KERNEL, WG_UP_STRIDE):
+            raise ValueError(f"WaveGlow: the upsampler is ConvTranspose1d(k = 1024, stride = 256), got {upsample_kernel_size} / {upsample_stride}")
+        if int(n_early_size) != 2:
+            raise ValueError(f"WaveGlow: n_early_size is 2, got {n_early_size}")
+        if int(n_mel_channels) != 80:
+            raise ValueError(f"WaveGlow: 80 mel bands, got {n_mel_channels}")
+        if n_flows < 1 or n_early_every < 1:
+            raise ValueError("WaveGlow: n_flows and n_early_every are positive")
+        # channels of flow k, as the original's constructor counts them: two fewer from every early-output point on
+        self.flow_channels = [WG_GROUP - 2 * len([e for e in range(1, k + 1) if e % n_early_every == 0]) for k in range(n_flows)]
+        if min(self.flow_channels) < 2:
+            raise ValueError(f"WaveGlow: n_flows = {n_flows} with n_early_every = {n_early_every} leaves {min(self.flow_channels)} channels "
+                             "for the last flows; the count must stay within [2, 8]")
+        self.n_flows, self.n_group, self.n_early_every, self.n_early_size = n_flows, WG_GROUP, n_early_every, 2
+        self.n_layers, self.n_channels, self.kernel_size, self.sigma = n_layers, C, 3, float(sigma)
+        if not self.sigma >= 0.0:
+            raise ValueError(f"WaveGlow: sigma is non-negative, got {sigma}")
+        self.n_mel_channels, self.n_cond = 80, 80 * WG_GROUP
+        self.n_remaining = self.flow_channels[-1]
+        self.upsample = nn.ConvTranspose1d(80, 80, WG_UP_KERNEL, stride=WG_UP_STRIDE)
+        self.WN = nn.ModuleList(_WaveGlowWN(c // 2, self.n_cond, n_layers, C, 3) for c in self.flow_channels)
+        self.convinv = nn.ModuleList(_InvConv(c) for c in self.flow_channels)
+        self.launches = 1 + n_flows * 2 * n_layers + n_flows + 1
+        self._images = _Cached()
+        for p in self.parameters():
+            p.requires_grad_(False)
+
+    @classmethod
+    def from_config(cls, cfg):
+        """from NVIDIA's config.json as a dict (its `waveglow_config` entry, or that entry itself); sigma where the dict has one"""
+        w = dict(cfg.get("waveglow_config", cfg))
+        wn = dict(w.get("WN_config", {}))
+        kw = dict(sigma=w["sigma"]) if "sigma" in w else {}
+        return cls(n_mel_channels=w.get("n_mel_channels", 80), n_flows=w.get("n_flows", 12), n_group=w.get("n_group", 8),
+                   n_early_every=w.get("n_early_every", 4), n_early_size=w.get("n_early_size", 2), n_layers=wn.get("n_layers", 8),
+                   n_channels=wn.get("n_channels", 256), kernel_size=wn.get("kernel_size", 3), **kw)
+
+    def load_waveglow_state(self, sd):
+        """a state dict under the published names.  The published .pt files pickle the whole module: the caller passes
+        ckpt["model"].state_dict().  Both conditioning layouts load — `WN.j.cond_layer` (the universal v5 checkpoints: one 640 -> 2C n
+        convolution) and the older per-layer `WN.j.cond_layers.i` (concatenated along the outputs, which is the same function) — each
+        with weight norm (weight_g / weight_v, folded g v / ||v|| in float64 and rounded once) or a folded weight; strict."""
+        flat = {}
+        for k, t in sd.items():
+            if k.endswith(".weight_g"):
+                flat[k[:-2]] = fold_weight_norm(t, sd[k[:-1] + "v"])
+            elif not k.endswith(".weight_v"):
+                flat[k] = t.detach().float().cpu()
+        out = {k: t for k, t in flat.items() if ".cond_layers." not in k}
+        for j in range(self.n_flows):
+            for kind in ("weight", "bias"):
+                parts = [flat.get(f"WN.{j}.cond_layers.{i}.{kind}") for i in range(self.n_layers)]
+                if all(p is not None for p in parts):
+                    out[f"WN.{j}.cond_layer.{kind}"] = torch.cat(parts, 0)
+                elif any(p is not None for p in parts):
+                    raise KeyError(f"WN.{j}.cond_layers: {kind} of some layers is missing")
+        extra = [k for k in flat if ".cond_layers." in k and int(k.split(".")[3]) >= self.n_layers]
+        if extra:
+            raise KeyError(f"unexpected keys {extra}")
+        return self.load_state_dict(out, strict=True)
+
+    # ---- the images: everything a run reads, per parameter version ----------------------------------------------------------------------
+    def inverse64(self, j):
+        """float64 [c, c]: the inverse of convinv.j.conv.weight, formed on the host as store_inverse does for the decoder"""
+        return torch.linalg.inv(self.convinv[j].conv.weight.detach().double().cpu()[:, :, 0])
+
+    def images(self):
+        """dict(up=(image, bias), flows=[dict(start=(w [C][8], b), layers=[dict(W_in, W_cond, b_in, b_cond, res=(image, bias))],
+        end=(w [C][8], b [8]), inv=w [8][8])]): bf16 images in gt_voc_conv's fragment order (the gate's rows interleaved), the
+        boundary's fp32 matrices in slot order (include/glowtts_hip.h); rebuilt when any parameter's (data_ptr, _version) changes"""
+        params = list(self.parameters())
+
+        def build():
+            dev, C, n = params[0].device, self.n_channels, self.n_layers
+            f = lambda t: t.detach().float().contiguous().to(dev)  # noqa: E731
+            # output 256 q + 8 l + i of band m is channel 640 l + 8 m + i of frame q: spect at the group rate
+            W7 = transposed_tail_as_conv(self.upsample.weight.detach().float(), WG_UP_STRIDE)           # [256 * 80, 80, 7], row r * 80 + m
+            W7 = W7.view(32, WG_GROUP, 80, 80, 7).permute(0, 2, 1, 3, 4).reshape(32 * 80 * WG_GROUP, 80, 7)
+            bias = self.upsample.bias.detach().float().view(1, 80, 1).expand(32, 80, WG_GROUP).reshape(-1)
+            out = dict(up=(voc_pack(W7), f(bias)), flows=[])
+            perm = gate_interleave(C).to(dev)
+            for j, c in enumerate(self.flow_channels):
+                wn, lo, h = self.WN[j], WG_GROUP - c, c // 2
+                w_start = torch.zeros(C, 8)
+                w_start[:, lo:lo + h] = wn.start.weight.detach().float().cpu()[:, :, 0]
+                we = wn.end.weight.detach().float().cpu()[:, :, 0]
+                be = wn.end.bias.detach().float().cpu()
+                w_end, b_end = torch.zeros(C, 8), torch.zeros(8)                       # column s - 4: slot s's shift, column s: its log-scale
+                w_end[:, lo + h - 4:4], w_end[:, lo + h:8] = we[:h].t(), we[h:].t()
+                b_end[lo + h - 4:4], b_end[lo + h:8] = be[:h], be[h:]
+                w_inv = torch.zeros(8, 8, dtype=torch.float64)
+                w_inv[lo:, lo:] = self.inverse64(j)
+                layers = []
+                for i in range(n):
+                    wc = wn.cond_layer.weight.detach().float()[2 * C * i:2 * C * (i + 1)]
+                    rs = wn.res_skip_layers[i]
+                    layers.append(dict(W_in=voc_pack(wn.in_layers[i].weight.detach().float()[perm]), W_cond=voc_pack(wc[perm]),
+                                       b_in=f(wn.in_layers[i].bias), b_cond=f(wn.cond_layer.bias.detach()[2 * C * i:2 * C * (i + 1)]),
+                                       res=(voc_pack(rs.weight.detach().float()), f(rs.bias))))
+                out["flows"].append(dict(start=(f(w_start), f(wn.start.bias)), layers=layers, end=(f(w_end), f(b_end)), inv=f(w_inv)))
+            return out
+        return self._images.get(params, build)
+
+    def held(self):
+        """what a captured graph of run() reads besides the buffers: its holder keeps it alive (the vocoder drops it when it repacks)"""
+        return self.images()
+
+    # ---- capacity-sized form ------------------------------------------------------------------------------------------------------------
+    def buffer_spec(self, B, F_max):
+        """[(name, dtype, elements)] of the buffers a run takes next to wav [B, 256 F_max] (which doubles as the flow's 8 audio slots
+        per group position), with L = 32 F_max group positions: the fp32 state x | skip [B, L, 2C], the gate's bf16 output g [B, L, C]
+        and the bf16 spect [B, L, 640]: B L (10 C + 1280) + 1024 B F_max bytes, 123 KB per frame at C = 256 — 3.17 GB at 32 x 800
+        frames.  B L max(2C, 640) must stay below 2^31."""
+        L, C = 32 * F_max, self.n_channels
+        E = B * L * max(2 * C, self.n_cond)
+        self._check_capacity(B, F_max, E, f"B >= 1, F_max >= 1 and 32 B F_max max(2C, 640) = {E} < 2^31")
+        return [("state", torch.float32, B * L * 2 * C), ("g", torch.bfloat16, B * L * C), ("spect", torch.bfloat16, B * L * self.n_cond)]
+
+    def _walk(self, mel, n_frames, bufs, B, F, seed_dev=None, seed=0):
+        C, n, Cs, wav = self.n_channels, self.n_layers, self.n_cond, bufs["wav"]
+        dev, im = mel.device, self.images()
+        st = _lib.current_stream(dev)
+        state, g, spect = bufs["state"], bufs["g"], bufs["spect"]
+        L = 32 * F
+
+        def conv(X, img, Y, Cin, N, taps, L_cap, mul, x_sb, y_sb, ldy, **kw):
+            call.gt_voc_conv(_lib.fill_args(_lib.VocConvArgs, X=X, x_stride_b=x_sb, W=img[0], bias=img[1], res=None, Y=Y, y_stride_b=y_sb,
+                                            ldy=ldy, len_mul=mul, n_frames=n_frames, B=B, L_cap=L_cap, Cin=Cin, N=N, taps=taps, dil=1,
+                                            tanh_out=0, slope=1.0, scale=1.0, **kw), st)
+
+        def boundary(prev, nxt, c_in, c_out):
+            call.gt_wg_boundary(_lib.fill_args(
+                _lib.WgBoundaryArgs, state=state, st_stride_b=L * 2 * C, ld=2 * C, C=C, A=wav, a_stride_b=wav.stride(0),
+                w_end=prev["end"][0] if prev else None, b_end=prev["end"][1] if prev else None, w_inv=prev["inv"] if prev else None,
+                w_start=nxt["start"][0] if nxt else None, b_start=nxt["start"][1] if nxt else None, n_frames=n_frames, seed_dev=seed_dev,
+                seed=int(seed) & 0xFFFFFFFF, sigma=self.sigma, len_mul=32, B=B, L_cap=L, c_in=c_in, c_out=c_out), st)
+
+        N_up = 32 * Cs
+        conv(mel, im["up"], spect, 80, N_up, 7, F, 1, mel.stride(0) if B > 1 else max(mel.stride(0), F), F * N_up, N_up,
+             x_stride_c=max(mel.stride(1), F), x_mel=1, x_bf16=0, y_bf16=1, acc=None)
+        chans, flows = self.flow_channels, im["flows"]
+        boundary(None, flows[-1], 0, chans[-1])
+        for j in range(self.n_flows - 1, -1, -1):
+            fl = flows[j]
+            for i, ly in enumerate(fl["layers"]):
+                call.gt_wg_gate(_lib.fill_args(_lib.WgGateArgs, X=state, x_stride_b=L * 2 * C, ldx=2 * C, Cs=Cs, S=spect, s_stride_b=L * Cs,
+                                               W_in=ly["W_in"], W_cond=ly["W_cond"], b_in=ly["b_in"], b_cond=ly["b_cond"], G=g,
+                                               g_stride_b=L * C, len_mul=32, n_frames=n_frames, B=B, L_cap=L, C=C, taps=3, dil=2 ** i), st)
+                # x += r[:C], skip += r[C:] in one call on the state (Y aliases acc); the last layer's C outputs go to the skip half
+                Y = state if i < n - 1 else state[C:]
+                conv(g, ly["res"], Y, C, 2 * C if i < n - 1 else C, 1, L, 32, L * C, L * 2 * C, 2 * C, x_stride_c=0, x_mel=0, x_bf16=1,
+                     y_bf16=0, acc=Y)
+            c_out = chans[j - 1] if j else WG_GROUP
+            boundary(fl, flows[j - 1] if j else None, chans[j], c_out)
         return wav

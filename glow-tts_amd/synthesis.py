@@ -295,9 +295,9 @@ class SynthesisHandle:
         return out
 
     def wav(self, clone=False, fallback=True):
-        """With a neural vocoder (audio.HiFiGAN, BigVGAN, Vocos: DESIGN.md 4.26): (wav [B, vocoder.wav_len(T)] fp32, wav_lengths =
-        [vocoder.wav_len(2 (lengths[b] // 2))]), bit-identical to vocoder(mel, 2 (lengths // 2)) (after an overflow: that eager call on
-        the eager mel), under the rules below; wav_len(F) is U F for HiFi-GAN and BigVGAN and Griffin-Lim's 256 (F - 1) for Vocos.
+        """With a neural vocoder (audio.HiFiGAN, BigVGAN, Vocos, WaveGlow: DESIGN.md 4.26): (wav [B, vocoder.wav_len(T)] fp32, wav_lengths =
+        [vocoder.wav_len(2 (lengths[b] // 2))]), bit-identical to vocoder(mel, 2 (lengths // 2)) — for a seeded vocoder (WaveGlow) with
+        seed=the call's seed — (after an overflow: that eager call on the eager mel), under the rules below; wav_len(F) is U F for HiFi-GAN and BigVGAN and Griffin-Lim's 256 (F - 1) for Vocos.
         With an audio.GriffinLim: (wav [B, 256 (T - 1)] fp32, wav_lengths) with T = max(lengths) rounded down to even (the mel's
         frames) and wav_lengths[b] = 256 max(2 (lengths[b] // 2) - 1, 0) (a host list) — the call's samples, zero behind every
         utterance's, bit-identical to GriffinLim.from_mel(mel, 2 (lengths // 2), n_iters=vocoder_iters, seed=the call's seed,
@@ -325,7 +325,8 @@ class SynthesisHandle:
             if self._eager_wav is None:
                 if s.neural:
                     frames = torch.tensor([2 * (v // 2) for v in lens], dtype=torch.int32).to(s.device)
-                    self._eager_wav = s.vocoder(mel, frames, mel_lengths_host=[2 * (v // 2) for v in lens])[0]
+                    kw = dict(seed=self._call.seed) if s.vocoder.seeded else {}
+                    self._eager_wav = s.vocoder(mel, frames, mel_lengths_host=[2 * (v // 2) for v in lens], **kw)[0]
                 elif mel.shape[2] < 2:
                     self._eager_wav = mel.new_zeros(mel.shape[0], 0)
                 else:
@@ -397,7 +398,8 @@ class Synthesizer:
     spectrum workspace, wav_static) — 4 batch (513 max_frames + 1025 Fp + 256 (max_frames - 1)) bytes with Fp = max_frames rounded up
     to 64: 52 + 109 + 26 MB at batch 32 and 800 frames.  vocoder_iters is fixed at capture; every launch of the loop is sized by
     max_frames, so a call of short utterances pays the loop of the capacity (tiles behind an utterance's end only write zeros).
-    vocoder=audio.HiFiGAN, audio.BigVGAN or audio.Vocos puts a neural generator there instead, through the one
+    vocoder=audio.HiFiGAN, audio.BigVGAN, audio.Vocos or audio.WaveGlow (WaveGlow's latent is seeded by the
+    call's seed, read from the call block on the device) puts a neural generator there instead, through the one
     contract of DESIGN.md 4.26 (vocoder_iters is ignored): wav_static [batch, vocoder.wav_len(max_frames)], voc_bufs =
     vocoder.buffer_spec(batch, max_frames)'s buffers as static buffers and wav_static (vocoder.workspace_bytes(batch, max_frames)
     bytes: 14 batch max_frames W + 4 batch U max_frames with W = 8192 for HiFi-GAN V1), captured_entries grows by vocoder.launches.
@@ -420,7 +422,7 @@ class Synthesizer:
                                      f"model writes {gen.out_channels}")
                 vocoder_iters = 0
             elif not isinstance(vocoder, audio.GriffinLim) or not isinstance(vocoder.stft, audio.TacotronSTFT):
-                raise TypeError("compile_synthesis(vocoder=) takes an audio.HiFiGAN (or audio.BigVGAN), an audio.Vocos, or an audio.GriffinLim built over an audio.TacotronSTFT")
+                raise TypeError("compile_synthesis(vocoder=) takes an audio.HiFiGAN (or audio.BigVGAN), an audio.Vocos, an audio.WaveGlow, or an audio.GriffinLim built over an audio.TacotronSTFT")
             elif vocoder.stft.mel_basis.device != next(gen.parameters()).device or vocoder.istft.inverse_basis.device != next(gen.parameters()).device:
                 raise ValueError("compile_synthesis(vocoder=): the vocoder's buffers are not on the model's device")
             elif vocoder.stft.mel_basis.shape[0] != gen.out_channels:
@@ -579,7 +581,8 @@ class Synthesizer:
             # the frames the mel really has (the squeeze drops an odd trailing frame); the phases' seed is the call block's first word
             torch.mul(rcy.lengths, 2, out=self.n_frames)
             if self.neural:
-                self.vocoder.run(self.mel_static, self.n_frames, self.voc_bufs)
+                kw = dict(seed_dev=self.call[:1]) if self.vocoder.seeded else {}     # the latent's seed: the call block's first word
+                self.vocoder.run(self.mel_static, self.n_frames, self.voc_bufs, **kw)
             else:
                 self.vocoder.run_from_mel(self.mel_static, self.n_frames, self.voc_bufs, self.vocoder_iters, seed_dev=self.call[:1])
         if self.aux:

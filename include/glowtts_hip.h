@@ -1340,6 +1340,89 @@ int gt_dtw_f32(const float* a, const float* b, const int32_t* a_len, const int32
 int gt_dtw_f0_stats(const int32_t* path, int ld_path, const int32_t* path_len, const float* f0_a, int ld_a, const float* f0_b, int ld_b,
                     int B, int32_t* counts, float* sums, void* stream);
 
+/* ---- WaveGlow vocoder (csrc/waveglow.hip): the reverse flow's two kernels next to gt_voc_conv --------------------------
+ * One run of n_flows WaveNets of n layers is gt_voc_conv (the upsampling transposed convolution as a 7-tap convolution at frame rate,
+ * x_mel, N = 20480 = spect [B, 32 F, 640] bf16), gt_wg_boundary (first form), per flow n x (gt_wg_gate, gt_voc_conv res_skip, taps 1, Y
+ * aliasing acc on the state) and one gt_wg_boundary: 1 + n_flows 2 n + n_flows + 1 launches.  Positions are GROUPS of 8 samples:
+ * len_b = min(max(n_frames[b], 0) len_mul, L_cap) with len_mul = 32; nothing at or behind len_b is read, the host never reads n_frames.
+ *
+ * gt_wg_gate: one WaveNet layer's dilated in_layer + its slice of the conditioning layer + the gate, as ONE implicit GEMM:
+ *   acts[b, t, m] = b_in[m] + b_cond[m] + sum_{j < taps} sum_{c < C} bf16( X[b, t + (j - taps / 2) dil, c] ) W_in[j][m][c]
+ *                                       + sum_{c < Cs} S[b, t, c] W_cond[m][c]                                  m < 2C, t < len_b
+ *   G[b, t, n]    = bf16( tanhf_(acts[b, t, n]) * sigmoidf_(acts[b, t, n + C]) )                                  n < C    (csrc/common.h)
+ *   A tap outside [0, len_b) contributes 0 and is never read; G at positions [len_b, L_cap) is written as bf16 zero.
+ *   X        fp32 residual stream, element (b, t, c) at X[b x_stride_b + t ldx + c] (ldx = 2C on the x | skip state); rounded to
+ *            nearest even to bf16 when staged: that value is the MFMA operand.
+ *   S        bf16 spect, element (b, t, c) at S[b s_stride_b + t Cs + c]; no halo.
+ *   W_in     bf16 image of [2C', C, taps] in gt_voc_conv's fragment order, W_cond of [2C', Cs, 1], where the 2C output rows are
+ *            INTERLEAVED in groups of 32: packed row 64 q + r is channel 32 q + r, packed row 64 q + 32 + r is channel C + 32 q + r
+ *            (q < C / 32, r < 32).  A lane then holds acts[n] and acts[n + C] of the same positions: the gate needs no LDS round trip.
+ *   b_in, b_cond  fp32 [2C] in the natural channel order.
+ *   G        bf16 [B, L_cap, C], element (b, t, n) at G[b g_stride_b + t C + n]; G may not alias X or S.
+ * A workgroup of four waves owns gt_wg_tile_positions() positions x 128 gate channels (a wave: all positions x 32 channels = two
+ * 32-column accumulator tiles), stages 64-channel chunks of X with (taps - 1) dil halo rows, then of S, in
+ * gt_wg_gate_lds_bytes(C, taps, dil) = (tile + (taps - 1) dil) 144 bytes of LDS, at most 64 KB (0 for a shape that is refused).
+ * Asynchronous, no allocation, no atomics, capturable in a graph; the grid is sized by L_cap.  fp32 accumulation in the MFMA over
+ * (X chunk, tap, k-step) then (S chunk, k-step) ascending: the summation order depends on (t, n, C, taps) alone — a batch row is
+ * bit-identical to the utterance computed alone, in a buffer of any capacity.
+ * Refusals, before any launch and in this order: args or X / S / W_in / W_cond / b_in / b_cond / G / n_frames NULL; B, L_cap, C, Cs, dil
+ * or len_mul <= 0; taps <= 0 or even; ldx < C, x_stride_b < L_cap ldx, s_stride_b < L_cap Cs, g_stride_b < L_cap C; G == X or G == S:
+ * GT_E_INVAL.  taps > GT_VOC_MAX_TAPS, C or Cs no multiple of 64, B > 65535, B L_cap max(ldx, Cs) >= 2^31, a halo past the LDS bound:
+ * GT_E_UNSUPPORTED.  X, S, W_in or W_cond not 16-byte, b_in / b_cond / G / n_frames not 4-byte aligned, ldx or x_stride_b no multiple
+ * of 4, s_stride_b no multiple of 8: GT_E_ALIGN. */
+typedef struct gt_wg_gate_args {
+  const float* X; int64_t x_stride_b; int ldx;
+  int Cs; const void* S; int64_t s_stride_b;
+  const void* W_in; const void* W_cond; const float* b_in; const float* b_cond;
+  void* G; int64_t g_stride_b;
+  int len_mul; const int32_t* n_frames;
+  int B; int L_cap; int C; int taps; int dil;
+} gt_wg_gate_args;
+int gt_wg_gate(const gt_wg_gate_args* args, void* stream);
+int gt_wg_gate_args_size(void);                 /* sizeof(gt_wg_gate_args): lets a binding check its mirror of the struct */
+int gt_wg_tile_positions(void);
+size_t gt_wg_gate_lds_bytes(int C, int taps, int dil);
+
+/* gt_wg_boundary: everything between two WaveNets of the reverse flow, per group position t < len_b, in fp32 on the vector ALU.  The
+ * audio lives in 8 SLOTS per position, A[b a_stride_b + 8 t + s]: the c current channels are slots [8 - c, 8) (slot s is channel s of
+ * the latent Z, so an early output is prepended by widening the window downwards), and with c = 8 the buffer IS the waveform,
+ * wav[b, 8 t + s].  With c_in channels before and c_out after (lo = 8 - c_in, h = c_in / 2, lo' = 8 - c_out, h' = c_out / 2), in order:
+ *   1. end     e[r] = b_end[r] + sum_{c < C} skip[b, t, c] w_end[c][r],  r = s - 4 (the shift of slot s) and s (its log-scale) for the
+ *              coupled slots s in [lo + h, 8) (never below 4): per lane an fmaf chain over c = lane, lane + 64, ... ascending, then
+ *              the xor butterfly of the wave (offsets 32, 16, ..., 1), then the bias.  skip[b, t, c] = state[b st_stride_b + t ld + C + c].
+ *   2. couple  a[s] = (a[s] - e[s - 4]) expf(-e[s])   for s in [lo + h, 8)   (the device library's expf)
+ *   3. 1x1     a'[s] = sum_{k = lo}^{7} w_inv[s][k] a[k]   for s in [lo, 8): ONE fmaf chain over k ascending from 0 (w_inv is the
+ *              8 x 8 image of the c_in x c_in inverse, zero outside its block; slots below lo enter as 0)
+ *   4. concat  a'[2p], a'[2p + 1] = sigma (e0, e1) of randn_pair(randn_key(seed, 5, b), t, p) for the new slots [lo', lo)
+ *              (csrc/common.h; stream id 5); seed by value, or (seed_dev != NULL) *seed_dev read on the device.
+ *   5. start   x[b, t, n] = b_start[n] + sum_{s = lo'}^{lo' + h' - 1} w_start[n][s] a'[s],  n < C: ONE fmaf chain over s ascending from
+ *              the bias, written to state[b st_stride_b + t ld + n]; skip[b, t, :] is cleared to 0 in the same pass.
+ *   A[b, t, 0..8) is written whole (slots below lo' as 0).
+ * Forms: w_end == NULL (with b_end, w_inv NULL and c_in = 0) is the FIRST form: steps 1-3 are skipped, the c_out slots are drawn.
+ * w_start == NULL (with b_start NULL, c_out = 8) is the LAST form: step 5 is skipped, the state is not touched, and A at positions
+ * [len_b, L_cap) is written as 0 — the samples, zero behind the utterance.  In the other forms nothing at or behind len_b is written.
+ *   w_end    fp32 [C][8], b_end fp32 [8] (columns of uncoupled slots are not used); w_inv fp32 [8][8]; w_start fp32 [C][8], b_start [C].
+ * A wave owns 8 consecutive positions, a workgroup of four waves 32; no LDS.  Asynchronous, no allocation, no atomics, capturable in a
+ * graph; the grid is sized by L_cap; every order above depends on (t, C) alone: a batch row is bit-identical to the utterance alone.
+ * Refusals, before any launch and in this order: args or state / A / n_frames NULL; B, L_cap, C or len_mul <= 0; ld < 2C,
+ * st_stride_b < L_cap ld, a_stride_b < 8 L_cap; c_in or c_out odd or outside [0, 8], c_out < 2, c_out < c_in; w_end, b_end and w_inv
+ * not all NULL or all set, or set with c_in == 0, or NULL with c_in > 0; w_start and b_start not both NULL or both set, or NULL with
+ * c_out != 8; sigma negative or NaN: GT_E_INVAL.  C no multiple of 64 or > GT_WG_MAX_C, B > 65535, B L_cap ld >= 2^31:
+ * GT_E_UNSUPPORTED.  A, w_end, w_inv or w_start not 16-byte, any other pointer not 4-byte aligned, ld, st_stride_b or a_stride_b no
+ * multiple of 4: GT_E_ALIGN. */
+#define GT_WG_MAX_C 512
+#define GT_WG_NOISE_STREAM 5
+typedef struct gt_wg_boundary_args {
+  float* state; int64_t st_stride_b; int ld;
+  int C; float* A; int64_t a_stride_b;
+  const float* w_end; const float* b_end; const float* w_inv; const float* w_start; const float* b_start;
+  const int32_t* n_frames; const uint32_t* seed_dev;
+  uint32_t seed; float sigma;
+  int len_mul; int B; int L_cap; int c_in; int c_out;
+} gt_wg_boundary_args;
+int gt_wg_boundary(const gt_wg_boundary_args* args, void* stream);
+int gt_wg_boundary_args_size(void);             /* sizeof(gt_wg_boundary_args) */
+
 #ifdef __cplusplus
 }
 #endif
