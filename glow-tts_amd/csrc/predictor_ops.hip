@@ -907,7 +907,8 @@ extern "C" int gt_rows_gather_tokens(const void* x_rows, int ldx, const int32_t*
                                      const int32_t* utt_f, const int32_t* row0_f, int Tp_f, const float* rowmask_f, void* out, int R_f, int C,
                                      void* stream)
 {
-  if (!x_rows || !frame2token || !utt_f || !rowmask_f || !out || R_f <= 0 || C <= 0 || (C & 7) || (ldx & 7)) return GT_E_INVAL;
+  if (!x_rows || !frame2token || !utt_f || !rowmask_f || !out || R_f <= 0 || C <= 0 || (C & 7) || (ldx & 7) || ldx < C) return GT_E_INVAL;
+  if (((uintptr_t)x_rows | (uintptr_t)out) & 15) return GT_E_ALIGN;           // 16-byte loads and stores
   const int C8 = C / 8;
   hipLaunchKernelGGL(gt_rows_gather_tokens_kernel, dim3((R_f * C8 + 255) / 256), dim3(256), 0, GT_ST(stream), static_cast<const bf16_t*>(x_rows), ldx,
                      frame2token, Ty, row0_x, Tp_x, utt_f, row0_f, Tp_f, rowmask_f, static_cast<bf16_t*>(out), R_f, C8);

@@ -845,7 +845,10 @@ int gt_nll_gauss_fwd(const float* z, const float* rowmask, const int32_t* utt, f
 int gt_nll_gauss_bwd(const float* z, const float* gacc, const float* rowmask, const int32_t* utt, float* dz, int R, void* stream);
 
 /* x_feature = x @ attn (models.py:1094) for the hard MAS path: frame row m of utterance b takes the token row
- * frame2token[b, t] (bf16 rows, C % 8 == 0); *_x describe the text-side rows, *_f the frame-rate rows. */
+ * frame2token[b, t] (bf16 rows, C % 8 == 0); *_x describe the text-side rows, *_f the frame-rate rows.  Rows with rowmask_f == 0
+ * are written as zeros and read neither frame2token nor x_rows.  The kernel moves 16 bytes per thread:
+ *   GT_E_INVAL  a NULL x_rows / frame2token / utt_f / rowmask_f / out, R_f <= 0, C <= 0, C % 8 != 0, ldx % 8 != 0, ldx < C;
+ *   GT_E_ALIGN  x_rows or out not 16-byte aligned. */
 int gt_rows_gather_tokens(const void* x_rows, int ldx, const int32_t* frame2token, int Ty, const int32_t* row0_x, int Tp_x,
                           const int32_t* utt_f, const int32_t* row0_f, int Tp_f, const float* rowmask_f, void* out, int R_f, int C,
                           void* stream);
