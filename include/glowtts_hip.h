@@ -759,7 +759,15 @@ int gt_dds_out_fwd(const float* h2, const float* x, int ldx, const float* gamma,
                    float* out, void* out_bf16, int R, int C, float eps, float drop_p, uint32_t seed, const uint32_t* seed_dev, void* stream);
 /* The three backward kernels accumulate their parameter gradients with one atomic per address and workgroup — or, with `partials`
  * (then the gradient pointers may be NULL), store the workgroup's sums to row w of partials [gt_dds_bwd_partial_rows(R)][W], W = 2 C
- * (gamma | beta) for out / sep, 4 C (dw[C][3] | db[C]) for dw; gt_param_partials_reduce adds the column sums later. */
+ * (gamma | beta) for out / sep, 4 C (dw[C][3] | db[C]) for dw; gt_param_partials_reduce adds the column sums later.
+ * gt_dds_bwd_partial_rows(R) = ceil(R / 8) (one row per workgroup of 8 rows), 0 for R <= 0.
+ *
+ * Refusals of gt_rows_split3 and the five gt_dds_* entries (tests/test_dds_ops_cabi.py), all before any launch.  GT_E_INVAL first:
+ * a required pointer NULL (optional: rowmask of gt_rows_split3, out_bf16, seed_dev, and dgamma / dbeta / dw / db when `partials` is
+ * given; without `partials` both gradient pointers of a backward are required), R <= 0, dilation <= 0 (sep_fwd, sep_bwd, dw_bwd),
+ * lda < 3 C (sep_fwd), ldo < 3 C or C <= 0 (gt_rows_split3), drop_p outside [0, 1) (out_fwd, out_bwd).  Then GT_E_UNSUPPORTED for
+ * C != 192 (the gt_dds_* entries; gt_rows_split3 takes any C > 0).  ldx and ldi are not checked: a row of x / in starts every ldx /
+ * ldi elements and only its first C are read. */
 int gt_dds_bwd_partial_rows(int R);
 int gt_dds_out_bwd(const float* h2, const float* dy, const float* gamma, const float* beta, const float* rowmask,
                    void* dh2_bf16, float* dgamma, float* dbeta, float* partials, int R, int C, float eps, float drop_p, uint32_t seed,
