@@ -242,7 +242,8 @@ def crn_bwd(rc, crn, saved_all, dx1, dxb1, grads):
         hin, s_ln = saved[i]
         _, dc = _ln_bwd(rc, crn.norm_layers[i], s_ln, None, dh, False, True, grads)
         grads.update(conv_param_grads(crn.conv_layers[i], hin, dc, R))
-        dh = conv_rows(dc, crn.conv_layers[i].pc, rc, dgrad=True)
+        # the k-tap data gradient spills into the halo / padded rows next to the frames: the returned dxb0 is masked, as dx0 is
+        dh = conv_rows(dc, crn.conv_layers[i].pc, rc, dgrad=True, mask=i == 0)
     return dx0, dh
 
 

@@ -32,6 +32,7 @@ def grad_ok(a, b, tol, atol=2e-3, name=""):
     yardstick downstream of a ReLU: a pre-activation within bf16 rounding of zero switches the unit
     on/off relative to the fp32 oracle, which moves single elements by their full magnitude while the
     tensor as a whole stays within tolerance.
+    (tests/test_encoder_chain_fp64_gpu.py holds the backward chains to float64 at the kernels' own saved activations: no flips, a few 1e-3.)
     The key bias of a softmax attention has a mathematically zero gradient (a constant added to every
     key cancels in the softmax): both sides hold rounding noise only."""
     if name.endswith("conv_k.bias"):
