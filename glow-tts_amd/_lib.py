@@ -245,6 +245,8 @@ PROTOTYPES = {
     "gt_wg_gate_lds_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gt_wg_boundary": (STATUS, [c_void_p, c_void_p]),
     "gt_wg_boundary_args_size": (c_int, []),
+    "gt_denoise_spec": (STATUS, [c_void_p, c_void_p]),
+    "gt_denoise_spec_args_size": (c_int, []),
 }
 c_void_p = ctypes.c_void_p
 
@@ -427,6 +429,13 @@ class WgBoundaryArgs(ctypes.Structure):
                 ("L_cap", c_int), ("c_in", c_int), ("c_out", c_int)]
 
 
+class DenoiseSpecArgs(ctypes.Structure):
+    """struct gt_denoise_spec_args (include/glowtts_hip.h); its size is checked against gt_denoise_spec_args_size() (tests/test_denoise_cabi.py)"""
+    _fields_ = [("wav", c_void_p), ("bias", c_void_p), ("strength", c_void_p), ("n_frames", c_void_p), ("mel_packed", c_void_p),
+                ("spec", c_void_p), ("frames_out", c_void_p), ("ld_wav", c_int), ("lost", c_int), ("B", c_int), ("F_max", c_int),
+                ("n_fft", c_int), ("hop", c_int), ("win", c_int)]
+
+
 WG_NOISE_STREAM, WG_MAX_C = 5, 512               # GT_WG_NOISE_STREAM, GT_WG_MAX_C
 
 
@@ -437,7 +446,8 @@ C_STRUCTS = {PackDesc: "gt_pack_desc", StepCopy: "gt_step_copy", StepCtx: "gt_st
              BoundaryBwdArgs: "gt_boundary_bwd_args", BoundaryRevArgs: "gt_boundary_rev_args", SynthPriorArgs: "gt_synth_prior_args",
              SynthCall: "gt_synth_call", SynthCallExt: "gt_synth_call_ext", VocConvArgs: "gt_voc_conv_args",
              VocSnakeArgs: "gt_voc_snake_args", VocosNormArgs: "gt_vocos_norm_args", VocosMlpArgs: "gt_vocos_mlp_args",
-             VocosPolarArgs: "gt_vocos_polar_args", WgGateArgs: "gt_wg_gate_args", WgBoundaryArgs: "gt_wg_boundary_args"}
+             VocosPolarArgs: "gt_vocos_polar_args", WgGateArgs: "gt_wg_gate_args", WgBoundaryArgs: "gt_wg_boundary_args",
+             DenoiseSpecArgs: "gt_denoise_spec_args"}
 
 
 def fill_args(cls, **kw):

@@ -42,6 +42,11 @@ run by ONE HIP kernel (csrc/mel_front.hip: gt_mel_pack once, gt_mel_spectrogram 
                     (everything between two WaveNets) next to gt_voc_conv (DESIGN.md 4.28); a seeded latent from the counter generator;
                     the published parameter tree (`load_waveglow_state`, `from_config`), the capacity-sized form.
 
+  Denoiser          NVIDIA's WaveGlow `Denoiser` (spectral subtraction of the network's own bias spectrum, mode "zeros") by csrc/denoise.hip's
+                    gt_denoise_spec (the analysis with the subtraction as its epilogue) and gt_istft; `from_vocoder`
+                    measures the bias, `denoise` is the stand-alone use, `workspace` / `run` the capacity-sized form.
+  Denoised          a vocoder with a Denoiser behind it, itself a `_MelVocoder`: compile_synthesis(vocoder=Denoised(WaveGlow(...))).
+
   The generators meet one contract, `_MelVocoder`: mel_channels, wav_len, buffer_spec(B, F_max), held, and the
   shared forward / workspace / workspace_bytes / run that compile_synthesis(vocoder=) uses.
 
@@ -566,6 +571,15 @@ class InverseSTFT(nn.Module):
     forward = inverse
 
 
+def _plain_stft_image(fb):
+    """gt_mel_pack's image of a plain STFT's forward basis: it has no mel basis, the image's mel part is zeros"""
+    if fb.dtype != torch.float32 or not fb.is_contiguous():
+        raise ValueError("forward_basis must be a contiguous fp32 buffer")
+    packed = torch.empty(call.gt_mel_pack_bytes() // 4, dtype=torch.float32, device=fb.device)
+    call.gt_mel_pack(fb, torch.zeros(1, 513, dtype=torch.float32, device=fb.device), 1024, 1, packed, _lib.current_stream(fb.device))
+    return packed
+
+
 class GriffinLim(nn.Module):
     """The reference's griffin_lim (audio_processing.py:59-75) on the device: gt_gl_polar, gt_istft, then per iteration gt_gl_project
     (analysis, Y = M X / |X|) and gt_istft — 2 + 2 n_iters launches, no host synchronisation.  `stft` is an audio.STFT or a
@@ -583,13 +597,7 @@ class GriffinLim(nn.Module):
         if isinstance(self.stft, TacotronSTFT):
             return self.stft._image()
         fb = self.stft_fn.forward_basis
-        def build():                                                          # a plain STFT has no mel basis: the image's mel part is zeros
-            if fb.dtype != torch.float32 or not fb.is_contiguous():
-                raise ValueError("forward_basis must be a contiguous fp32 buffer")
-            packed = torch.empty(call.gt_mel_pack_bytes() // 4, dtype=torch.float32, device=fb.device)
-            call.gt_mel_pack(fb, torch.zeros(1, 513, dtype=torch.float32, device=fb.device), 1024, 1, packed, _lib.current_stream(fb.device))
-            return packed
-        return self._fwd_packed.get((fb,), build)
+        return self._fwd_packed.get((fb,), lambda: _plain_stft_image(fb))
 
     def project(self, wav, magnitudes, n_frames, spec):
         """kernel call, the analysis half: spec = magnitudes * X / |X|, X the STFT of wav's rows (each reflected about its own ends)"""
@@ -1641,3 +1649,203 @@ class WaveGlow(_MelVocoder):
             c_out = chans[j - 1] if j else WG_GROUP
             boundary(fl, flows[j - 1] if j else None, chans[j], c_out)
         return wav
+
+
+# ---- spectral-subtraction denoiser: NVIDIA's WaveGlow `Denoiser` on csrc/denoise.hip and gt_istft ----------------------
+class Denoiser(nn.Module):
+    """NVIDIA's WaveGlow `Denoiser` (denoiser.py, mode="zeros") on the device:
+    denoised = STFT.inverse(clamp(|X| - strength * bias_spec, min=0), angle X), X = STFT(audio), by TWO C-ABI calls — gt_denoise_spec
+    (csrc/denoise.hip: the analysis with Y = X max(|X| - c, 0) / |X| as its epilogue, no atan2 / cos / sin) and gt_istft — every
+    utterance of a ragged batch on its own.  Owns `stft` (an audio.STFT at 1024 / 256 / 1024; its forward basis image), `istft` (an
+    InverseSTFT), the buffer `bias_spec` fp32 [513] (zeros until from_vocoder / load_state_dict / an assignment fills it) and the
+    one-element fp32 buffer `strength_dev` the kernel reads: `set_strength` between two replays of a captured graph changes the next one.
+    Samples come in hops of 256: an utterance of L samples is denoised over its first 256 (L // 256)."""
+
+    def __init__(self, stft=None, bias_spec=None, strength=0.1):
+        super().__init__()
+        self.stft = STFT() if stft is None else stft
+        if not isinstance(self.stft, STFT):
+            raise TypeError("Denoiser(stft=) takes an audio.STFT")
+        _check_geometry(self.stft)
+        self.istft = InverseSTFT(self.stft.filter_length, self.stft.hop_length, self.stft.win_length)
+        bias = torch.zeros(513) if bias_spec is None else bias_spec.detach().to(torch.float32).reshape(-1).clone()
+        if bias.numel() != 513:
+            raise ValueError(f"bias_spec is [513], got {bias.numel()} values")
+        self.register_buffer("bias_spec", bias)
+        self.register_buffer("strength_dev", torch.zeros(1, dtype=torch.float32, device=bias.device), persistent=False)
+        self._fwd_packed, self._bias, self._source = _Cached(), _Cached(), None
+        self.set_strength(strength)
+
+    # -- the strength: checked on the host (the shrinkage is non-expansive for c >= 0 only), kept in the word the kernel reads
+    def set_strength(self, s):
+        s = float(s)
+        if not (np.isfinite(s) and s >= 0.0):
+            raise ValueError(f"Denoiser: strength is finite and non-negative, got {s}")
+        self.strength = s
+        # a blocking copy from the host: the word holds s when this returns, whichever stream a captured graph is replayed on next
+        self.strength_dev.copy_(torch.tensor([s], dtype=torch.float32))
+        return self
+
+    def _forward_image(self):
+        fb = self.stft.forward_basis
+        return self._fwd_packed.get((fb,), lambda: _plain_stft_image(fb))
+
+    def held(self):
+        """what a captured graph of run() reads besides the buffers: the two packed images, the bias and the strength word"""
+        return self._forward_image(), self.istft._image(), self.bias(), self.strength_dev
+
+    # -- the bias spectrum of a vocoder
+    @classmethod
+    def from_vocoder(cls, voc, frames=88, strength=0.1):
+        """the Denoiser of `voc` (a _MelVocoder on the device): bias_spec = frame 0 of |STFT(voc(zeros [1, n_mel, frames]))|, a seeded
+        vocoder (WaveGlow) run at sigma = 0 for that one call.  The vocoder is remembered (in a tuple: not a submodule): bias() rebuilds
+        bias_spec, in place, when a parameter of the vocoder has changed (_Cached, as the packed images are)."""
+        if not isinstance(voc, _MelVocoder):
+            raise TypeError("Denoiser.from_vocoder takes one of audio's vocoders")
+        if voc.hop_length != 256:
+            raise ValueError(f"Denoiser: the STFT has a hop of 256 samples, the vocoder's is {voc.hop_length}")
+        den = cls(strength=strength).to(next(voc.parameters()).device)
+        den._source = (voc, int(frames))
+        den.bias()
+        return den
+
+    def bias(self):
+        """bias_spec: as it stands, or (from_vocoder) brought up to date with the vocoder's parameters first"""
+        if self._source is None:
+            return self.bias_spec
+        voc, frames = self._source
+        return self._bias.get(tuple(voc.parameters()), lambda: self._measure_bias(voc, frames))
+
+    def _measure_bias(self, voc, frames):
+        dev = self.bias_spec.device
+        mel = torch.zeros(1, voc.mel_channels - voc.mel_padding, frames, dtype=torch.float32, device=dev)
+        sigma = getattr(voc, "sigma", None)
+        try:
+            if voc.seeded:
+                voc.sigma = 0.0                                               # the attribute _walk reads; the vocoder itself is unchanged
+            wav = voc(mel)
+        finally:
+            if voc.seeded:
+                voc.sigma = sigma
+        hops = wav.shape[1] // 256
+        if hops < 1:
+            raise ValueError(f"{frames} frames give the vocoder no sample to take a bias spectrum from")
+        strength = self.strength
+        try:
+            self.set_strength(0.0)                                            # strength 0: the kernel writes X itself
+            bufs = self.workspace(1, hops, dev)
+            self.analyse(wav[:, :256 * hops].contiguous(), torch.full((1,), hops, dtype=torch.int32, device=dev), 0, bufs)
+        finally:
+            self.set_strength(strength)
+        re, im = spec_unpack(bufs["dn_spec"], 1, hops + 1)
+        self.bias_spec.copy_(torch.hypot(re[0, :, 0], im[0, :, 0]))
+        return self.bias_spec
+
+    # -- capacity-sized form
+    def buffer_spec(self, B, F_max, lost=0):
+        """[(name, dtype, elements)] of a run behind a vocoder of capacity (B, F_max mel frames): the spectrum workspace at
+        Fa_max = F_max - lost + 1 analysis frames and the int32 [B] analysis frame counts"""
+        n = call.gt_gl_spec_bytes(B, F_max - lost + 1) // 4
+        if n == 0:
+            raise ValueError(f"denoiser workspace for {B} x {F_max} frames: outside what gt_denoise_spec takes")
+        return [("dn_spec", torch.float32, n), ("dn_frames", torch.int32, B)]
+
+    def workspace(self, B, F_max, device, lost=0):
+        return {name: torch.empty(n, dtype=dt, device=device) for name, dt, n in self.buffer_spec(B, F_max, lost)}
+
+    def analyse(self, wav, n_frames, lost, bufs):
+        """kernel call: bufs["dn_spec"] = the denoised spectrum of wav's rows, bufs["dn_frames"] = their analysis frame counts"""
+        B = wav.shape[0]
+        F_max = wav.shape[1] // 256 + lost
+        call.gt_denoise_spec(_lib.fill_args(_lib.DenoiseSpecArgs, wav=wav, bias=self.bias_spec, strength=self.strength_dev,
+                                            n_frames=n_frames, mel_packed=self._forward_image(), spec=bufs["dn_spec"],
+                                            frames_out=bufs["dn_frames"], ld_wav=wav.stride(0), lost=lost, B=B, F_max=F_max, n_fft=1024,
+                                            hop=256, win=1024), _lib.current_stream(wav.device))
+        return F_max - lost + 1
+
+    def run(self, wav, n_frames, lost, bufs):
+        """kernel calls, the capacity-sized form for graph callers: wav fp32 [B, 256 (F_max - lost)] (a vocoder's workspace rows: row b
+        holds 256 max(n_frames[b] - lost, 0) samples), device int32 [B] MEL frame counts, lost = the vocoder's min_frames - 1 and
+        workspace's buffers -> wav, denoised in place, zero behind each utterance.  gt_denoise_spec, gt_istft: nothing is allocated once
+        the images exist, nothing is looked at on the host, both grids are sized by the capacity."""
+        if not wav.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
+        if wav.dim() != 2 or wav.dtype != torch.float32 or wav.stride(1) != 1 or wav.shape[1] % 256 or wav.shape[1] == 0:
+            raise ValueError(f"run takes fp32 rows of a multiple of 256 samples, got {tuple(wav.shape)} {wav.dtype}")
+        if lost not in (0, 1):
+            raise ValueError(f"lost is 0 or 1, got {lost}")
+        if n_frames.dtype != torch.int32 or n_frames.numel() != wav.shape[0] or not n_frames.is_cuda or not n_frames.is_contiguous():
+            raise ValueError("n_frames must be a contiguous int32 [B] on the device")
+        bias = self.bias()                                                    # from_vocoder: up to date with the vocoder's parameters
+        if bias.device != wav.device or bias.dtype != torch.float32 or not bias.is_contiguous() or self.strength_dev.dtype != torch.float32:
+            raise ValueError("the denoiser's buffers are contiguous fp32 on the waveforms' device")
+        Fa_max = self.analyse(wav, n_frames, lost, bufs)
+        self.istft.synthesize(bufs["dn_spec"], bufs["dn_frames"], wav.shape[0], Fa_max, out=wav)
+        return wav
+
+    def denoise(self, wav, lengths=None, lengths_host=None, strength=None):
+        """the stand-alone use, on any waveform: padded fp32 rows [B, T] (lengths: their sample counts, default T) -> wav_d [B, T], or
+        (wav_d, lengths floored to a multiple of 256) with lengths; zero behind each utterance.  `strength` sets the module's first."""
+        if not wav.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
+        if wav.dim() != 2 or wav.dtype != torch.float32:
+            raise ValueError(f"waveforms are [B, T] fp32, got {tuple(wav.shape)} {wav.dtype}")
+        if strength is not None:
+            self.set_strength(strength)
+        B, T = wav.shape
+        if lengths is None:
+            hops = torch.full((B,), T // 256, dtype=torch.int32, device=wav.device)
+        else:
+            if lengths_host is None and not lengths.is_cuda:
+                lengths_host = lengths.tolist()
+            if lengths.numel() != B or (lengths_host is not None and (len(lengths_host) != B or max(lengths_host, default=0) > T)):
+                raise ValueError(f"lengths do not fit waveforms {tuple(wav.shape)}")
+            hops = (lengths.to(wav.device, non_blocking=True) // 256).to(torch.int32).contiguous()
+        F_max = T // 256
+        if B and F_max:
+            rows = torch.empty(B, 256 * F_max, dtype=torch.float32, device=wav.device)    # run works in place: never on the caller's rows
+            self.run(rows.copy_(wav[:, :256 * F_max]), hops, 0, self.workspace(B, F_max, wav.device))
+            out = rows if T == 256 * F_max else torch.cat([rows, rows.new_zeros(B, T - 256 * F_max)], 1)
+        else:
+            out = wav.new_zeros(B, T)
+        if lengths is None:
+            return out
+        return out, hops.clamp(min=0, max=F_max) * 256
+
+    forward = denoise
+
+
+class Denoised(_MelVocoder):
+    """A vocoder with the spectral-subtraction Denoiser behind it, itself a _MelVocoder: everything the
+    contract names is the inner vocoder's, `launches` two more, buffer_spec / held the denoiser's on top, and _walk the inner walk
+    followed by Denoiser.run on the samples where they stand.  compile_synthesis(vocoder=Denoised(...)) needs nothing else.
+    denoiser=None: Denoiser.from_vocoder(vocoder, strength=strength).  Only 256-sample hops (the STFT's)."""
+
+    def __init__(self, vocoder, denoiser=None, strength=0.1):
+        super().__init__()
+        if not isinstance(vocoder, _MelVocoder):
+            raise TypeError("Denoised wraps one of audio's vocoders")
+        if vocoder.hop_length != 256:
+            raise ValueError(f"Denoised: the denoiser's STFT has a hop of 256 samples, the vocoder's is {vocoder.hop_length}")
+        self.vocoder = vocoder
+        self.denoiser = Denoiser.from_vocoder(vocoder, strength=strength) if denoiser is None else denoiser
+        self.hop_length, self.min_frames = vocoder.hop_length, vocoder.min_frames
+        self.mel_channels, self.mel_padding, self.seeded = vocoder.mel_channels, vocoder.mel_padding, vocoder.seeded
+        self.launches = vocoder.launches + 2
+
+    def set_strength(self, s):
+        self.denoiser.set_strength(s)
+        return self
+
+    def check_graph_input(self):
+        self.vocoder.check_graph_input()
+
+    def buffer_spec(self, B, F_max):
+        return self.vocoder.buffer_spec(B, F_max) + self.denoiser.buffer_spec(B, F_max, self.min_frames - 1)
+
+    def held(self):
+        return self.vocoder.held(), self.denoiser.held()
+
+    def _walk(self, mel, n_frames, bufs, B, F, **seed):
+        wav = self.vocoder._walk(mel, n_frames, bufs, B, F, **seed)
+        return self.denoiser.run(wav, n_frames, self.min_frames - 1, bufs)

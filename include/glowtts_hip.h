@@ -1434,6 +1434,37 @@ typedef struct gt_wg_boundary_args {
 int gt_wg_boundary(const gt_wg_boundary_args* args, void* stream);
 int gt_wg_boundary_args_size(void);             /* sizeof(gt_wg_boundary_args) */
 
+/* ---- spectral-subtraction denoiser behind the vocoders (csrc/denoise.hip) -----------------------------------------
+ * NVIDIA's WaveGlow `Denoiser` (denoiser.py, mode "zeros") is STFT.inverse(clamp(|X| - strength bias_spec, min = 0), angle X) with
+ * X = STFT(audio), n_fft = win = 1024, hop = 256, and bias_spec [513] frame 0 of |STFT| of the network's output for a zero mel at
+ * sigma = 0.  gt_denoise_spec is its analysis half with the subtraction as the epilogue; gt_istft (above) is the other half.
+ *   wav      in, [B rows, pitch ld_wav] fp32: row b holds what a vocoder wrote for n_b = min(n_frames[b], F_max) mel frames,
+ *            L_b = 256 max(n_b - lost, 0) samples (lost = the vocoder's min_frames - 1: 0 or 1; L_b additionally clamped to
+ *            256 (ld_wav / 256)).  Frames are reflected about the utterance's own ends as gt_gl_project takes them; nothing at or
+ *            behind L_b is read.
+ *   frames_out  out, int32 [B]: Fa_b = L_b / 256 + 1 analysis frames, 0 where L_b == 0 — the n_frames of the gt_istft call that
+ *            follows, at the capacity Fa_max = F_max - lost + 1 (its row of 256 (Fa_max - 1) = 256 (F_max - lost) samples).
+ *   spec     out, gt_gl_spec_bytes(B, Fa_max) bytes in the fragment order described with gt_gl_polar, ALL of it defined (zeros from
+ *            frame Fa_b on): Y = X max(|X| - c_k, 0) / |X| with c_k = strength[0] * bias[k] (one fp32 product), X the folded DFT
+ *            with the basis image of gt_mel_pack (mel_packed); |X|^2 == 0 in fp32 gives (max(-c_k, 0), 0), as atan2(0, 0) = 0 does.
+ *            Bin 512 is real: y = sign(x) max(|x| - c_512, 0).  The unit phasor replaces the reference's atan2 / cos / sin (the same
+ *            mathematics).
+ *   bias     fp32 [513]; strength: ONE fp32 word, both read on the device — a captured graph replays with the value the word holds.
+ * Asynchronous, no allocation, no atomics, capturable in a graph; the grid is sized by Fa_max; the summation order of an element
+ * depends on its index within its utterance alone: a batch row is bit-identical to the utterance computed alone.
+ * Refusals, before any launch and in this order: args or a pointer NULL, lost outside {0, 1}, ld_wav <= 0, B outside
+ * [1, GT_MEL_MAX_B], F_max or F_max - lost + 1 outside [1, GT_MEL_MAX_FRAMES]: GT_E_INVAL; n_fft != 1024, hop != 256 or win != 1024:
+ * GT_E_UNSUPPORTED; wav, mel_packed or spec not 16-byte, bias, strength, n_frames or frames_out not 4-byte aligned, ld_wav no
+ * multiple of 4: GT_E_ALIGN. */
+typedef struct gt_denoise_spec_args {
+  const float* wav; const float* bias; const float* strength;
+  const int32_t* n_frames; const void* mel_packed;
+  float* spec; int32_t* frames_out;
+  int ld_wav; int lost; int B; int F_max; int n_fft; int hop; int win;
+} gt_denoise_spec_args;
+int gt_denoise_spec(const gt_denoise_spec_args* args, void* stream);
+int gt_denoise_spec_args_size(void);            /* sizeof(gt_denoise_spec_args) */
+
 #ifdef __cplusplus
 }
 #endif
