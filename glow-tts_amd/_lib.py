@@ -247,6 +247,11 @@ PROTOTYPES = {
     "gt_wg_boundary_args_size": (c_int, []),
     "gt_denoise_spec": (STATUS, [c_void_p, c_void_p]),
     "gt_denoise_spec_args_size": (c_int, []),
+    "gt_loudness_measure": (STATUS, [c_void_p, c_void_p]),
+    "gt_loudness_apply": (STATUS, [c_void_p, c_void_p]),
+    "gt_loudness_args_size": (c_int, []),
+    "gt_loudness_chunk": (c_int, [c_int]),
+    "gt_loudness_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
 }
 c_void_p = ctypes.c_void_p
 
@@ -436,6 +441,14 @@ class DenoiseSpecArgs(ctypes.Structure):
                 ("n_fft", c_int), ("hop", c_int), ("win", c_int)]
 
 
+class LoudnessArgs(ctypes.Structure):
+    """struct gt_loudness_args (include/glowtts_hip.h); its size is checked against gt_loudness_args_size() (tests/test_loudness_cabi.py)"""
+    _fields_ = [("wav", c_void_p), ("n_frames", c_void_p), ("params", c_void_p), ("stats", c_void_p), ("ws", c_void_p), ("out", c_void_p),
+                ("ws_bytes", c_i64), ("ld", c_int), ("ld_out", c_int), ("is_i16", c_int), ("hop", c_int), ("lost", c_int), ("B", c_int),
+                ("L_cap", c_int), ("fs", c_int)]
+
+
+LOUD_STATS, LOUD_PARAMS = 8, 64                  # GT_LOUD_STATS, GT_LOUD_PARAMS
 WG_NOISE_STREAM, WG_MAX_C = 5, 512               # GT_WG_NOISE_STREAM, GT_WG_MAX_C
 
 
@@ -447,7 +460,7 @@ C_STRUCTS = {PackDesc: "gt_pack_desc", StepCopy: "gt_step_copy", StepCtx: "gt_st
              SynthCall: "gt_synth_call", SynthCallExt: "gt_synth_call_ext", VocConvArgs: "gt_voc_conv_args",
              VocSnakeArgs: "gt_voc_snake_args", VocosNormArgs: "gt_vocos_norm_args", VocosMlpArgs: "gt_vocos_mlp_args",
              VocosPolarArgs: "gt_vocos_polar_args", WgGateArgs: "gt_wg_gate_args", WgBoundaryArgs: "gt_wg_boundary_args",
-             DenoiseSpecArgs: "gt_denoise_spec_args"}
+             DenoiseSpecArgs: "gt_denoise_spec_args", LoudnessArgs: "gt_loudness_args"}
 
 
 def fill_args(cls, **kw):

@@ -47,11 +47,20 @@ run by ONE HIP kernel (csrc/mel_front.hip: gt_mel_pack once, gt_mel_spectrogram 
                     measures the bias, `denoise` is the stand-alone use, `workspace` / `run` the capacity-sized form.
   Denoised          a vocoder with a Denoiser behind it, itself a `_MelVocoder`: compile_synthesis(vocoder=Denoised(WaveGlow(...))).
 
+  Loudness          ITU-R BS.1770-4 integrated loudness (K-weighting, 400 ms blocks, both gates) and normalisation to a target under a
+                    sample peak ceiling, by csrc/loudness.hip's gt_loudness_measure and gt_loudness_apply: a serial
+                    IIR run in parallel over chunks, exactly, in double; `measure` / `normalize` are the stand-alone uses on padded
+                    fp32 or int16 batches, `workspace` / `run` the capacity-sized form.  `kweighting64`, `kweighting_transition64`:
+                    the float64 coefficients and the chunk transition matrix the kernels read.
+  Normalized        a vocoder with a Loudness stage behind it, itself a `_MelVocoder`: Normalized(Denoised(WaveGlow(...))).
+
   The generators meet one contract, `_MelVocoder`: mel_channels, wav_len, buffer_spec(B, F_max), held, and the
   shared forward / workspace / workspace_bytes / run that compile_synthesis(vocoder=) uses.
 
 Waveforms are fp32 in [-1, 1] or int16 (scaled by 1/32768 in the kernel = the reference's audio / max_wav_value).  There is no CPU
 path: a CPU tensor raises."""
+from fractions import Fraction
+
 import numpy as np
 import torch
 from torch import nn
@@ -1849,3 +1858,233 @@ class Denoised(_MelVocoder):
     def _walk(self, mel, n_frames, bufs, B, F, **seed):
         wav = self.vocoder._walk(mel, n_frames, bufs, B, F, **seed)
         return self.denoiser.run(wav, n_frames, self.min_frames - 1, bufs)
+
+
+# ---- ITU-R BS.1770-4 integrated loudness and normalisation on csrc/loudness.hip ---------------------------------------
+KW_SHELF_DB, KW_SHELF_Q, KW_SHELF_HZ, KW_SHELF_VB = 3.99984385397, 0.7071752369554193, 1681.9744509555319, 0.499666774155
+KW_HP_Q, KW_HP_HZ = 0.5003270373253953, 38.13547087613982
+LOUD_SCAN_RUN = 16                   # the state scan's fan-in: the kernels read M, M^16 and M^256
+
+
+def kweighting64(fs):
+    """the K-weighting cascade at sampling rate fs in float64: ((b, a) of the high shelf, (b, a) of the high-pass), a[0] = 1.  At
+    48 kHz the recommendation's table to 1e-11."""
+    fs = float(fs)
+    K = np.tan(np.pi * KW_SHELF_HZ / fs)
+    Vh = 10.0 ** (KW_SHELF_DB / 20.0)
+    Vb = Vh ** KW_SHELF_VB
+    a0 = 1.0 + K / KW_SHELF_Q + K * K
+    shelf = (np.array([(Vh + Vb * K / KW_SHELF_Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / KW_SHELF_Q + K * K) / a0]),
+             np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / KW_SHELF_Q + K * K) / a0]))
+    K = np.tan(np.pi * KW_HP_HZ / fs)
+    a0 = 1.0 + K / KW_HP_Q + K * K
+    hp = (np.array([1.0, -2.0, 1.0]), np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / KW_HP_Q + K * K) / a0]))
+    return shelf, hp
+
+
+def kweighting_transition64(fs, n):
+    """M [4, 4] float64: the cascade's state after n samples of zero input is M times its state before them.  The state is the
+    kernel's: (s1, s2) of the shelf, then of the high-pass, each biquad in transposed direct form II (y = b0 x + s1;
+    s1 = b1 x - a1 y + s2; s2 = b2 x - a2 y), the shelf's output the high-pass's input.  The n-th power of the one-sample matrix of
+    kweighting64's float64 coefficients is taken in 400-bit fixed point (integer arithmetic, square and multiply) and rounded once:
+    every entry is within half an ulp, or 2^-390 where that is more, of the filter's own transition — a float64 product of n factors
+    loses 1e-11 of the largest entry by n = 800, and 1e-6 by n = 12 800, to the cancellation in the high-pass's near-double pole."""
+    (_, a), (c, d) = kweighting64(fs)
+    a1, a2, c0, c1, c2, d1, d2 = (Fraction(float(v)) for v in (a[1], a[2], c[0], c[1], c[2], d[1], d[2]))
+    # one sample of zero input: y = s1; s1' = -a1 y + s2; s2' = -a2 y; z = c0 y + t1; t1' = c1 y - d1 z + t2; t2' = c2 y - d2 z
+    A = [[-a1, 1, 0, 0], [-a2, 0, 0, 0], [c1 - d1 * c0, 0, -d1, 1], [c2 - d2 * c0, 0, -d2, 0]]
+    P = 400                                                # float64 coefficients and their products are exact at this scale
+    base = [[int(Fraction(v) * (1 << P)) for v in row] for row in A]
+
+    def mul(X, Y):
+        return [[sum(X[i][k] * Y[k][j] for k in range(4)) >> P for j in range(4)] for i in range(4)]
+
+    R, k = [[int(i == j) << P for j in range(4)] for i in range(4)], int(n)
+    while k:
+        if k & 1:
+            R = mul(R, base)
+        base, k = mul(base, base), k >> 1
+    return np.array([[R[i][j] / (1 << P) for j in range(4)] for i in range(4)])        # int / int: correctly rounded
+
+
+def loudness_chunk(fs):
+    """the chunk length csrc/loudness.hip cuts utterances into at sampling rate fs (the largest divisor of fs / 10 in [16, 50]); 0 for a
+    rate the kernels do not take"""
+    return call.gt_loudness_chunk(int(fs)) if float(fs) == int(fs) else 0
+
+
+class Loudness(nn.Module):
+    """ITU-R BS.1770-4 integrated loudness (mono: K-weighting, 400 ms blocks at 75 % overlap, the -70 LKFS and the relative -10 LU
+    gate) of every utterance of a ragged batch on its own, and normalisation to `target_lufs` (EBU R 128: -23) under a SAMPLE peak
+    ceiling of `peak_dbfs`, by TWO C-ABI calls: gt_loudness_measure (four launches, all in double) and gt_loudness_apply (one).  An
+    utterance shorter than 400 ms is one block over all its samples; silence and no sample read -inf and are left as they are (g = 1).
+    Owns `params`, the float64 words the kernels read on the device: coefficients, the chunk transition matrices, the target and the
+    ceiling — `set_target` between two replays of a captured graph changes the next one."""
+
+    launches = 2                     # C-ABI calls of run(): gt_loudness_measure, gt_loudness_apply
+    kernels = 5                      # kernel launches behind them
+    STATS = ("lufs", "peak", "gain", "blocks", "gated_abs", "gated_rel", "gamma", "samples")   # the columns of a stats row
+
+    def __init__(self, sampling_rate=22050, target_lufs=-23.0, peak_dbfs=-1.0):
+        super().__init__()
+        if float(sampling_rate) != int(sampling_rate) or not loudness_chunk(sampling_rate):
+            raise ValueError(f"Loudness: csrc/loudness.hip takes no sampling rate of {sampling_rate} Hz (a multiple of 10 in "
+                             "[8000, 192000] whose tenth has a divisor in [16, 50])")
+        self.sampling_rate, self.chunk = int(sampling_rate), loudness_chunk(sampling_rate)
+        (b, a), (c, d) = kweighting64(self.sampling_rate)
+        p = np.zeros(_lib.LOUD_PARAMS)
+        p[0:5], p[5:10] = (*b, a[1], a[2]), (*c, d[1], d[2])
+        p[10:26] = kweighting_transition64(self.sampling_rate, self.chunk).reshape(-1)
+        p[26:42] = kweighting_transition64(self.sampling_rate, self.chunk * LOUD_SCAN_RUN).reshape(-1)
+        p[44:60] = kweighting_transition64(self.sampling_rate, self.chunk * LOUD_SCAN_RUN ** 2).reshape(-1)
+        self.register_buffer("params", torch.from_numpy(p), persistent=False)
+        self.set_target(target_lufs, peak_dbfs)
+
+    def set_target(self, lufs, peak_dbfs=None):
+        """the target in LUFS and (peak_dbfs: not None) the sample peak ceiling in dBFS, checked on the host, kept in the words the
+        kernel reads"""
+        lufs = float(lufs)
+        peak_dbfs = getattr(self, "peak_dbfs", None) if peak_dbfs is None else float(peak_dbfs)
+        if not np.isfinite(lufs) or peak_dbfs is None or not np.isfinite(peak_dbfs):
+            raise ValueError(f"Loudness: the target and the peak ceiling are finite, got {lufs} LUFS, {peak_dbfs} dBFS")
+        self.target_lufs, self.peak_dbfs = lufs, peak_dbfs
+        # a blocking copy from the host: the words hold the values when this returns, whichever stream a graph is replayed on next
+        self.params[42:44].copy_(torch.tensor([lufs, 10.0 ** (peak_dbfs / 20.0)], dtype=torch.float64))
+        return self
+
+    def held(self):
+        """what a captured graph of run() reads besides the buffers: the parameter words"""
+        return (self.params,)
+
+    # -- capacity-sized form
+    def buffer_spec(self, B, F_max, hop=1, lost=0):
+        """[(name, dtype, elements)] of a run on rows of hop (F_max - lost) samples: the workspace and the stats rows"""
+        n = call.gt_loudness_ws_bytes(B, hop * (F_max - lost), self.sampling_rate) // 4
+        if n == 0:
+            raise ValueError(f"loudness workspace for {B} x {hop * (F_max - lost)} samples: outside what gt_loudness_measure takes")
+        return [("ld_ws", torch.float32, n), ("ld_stats", torch.float32, _lib.LOUD_STATS * B)]
+
+    def workspace(self, B, F_max, device, hop=1, lost=0):
+        return {name: torch.empty(n, dtype=dt, device=device) for name, dt, n in self.buffer_spec(B, F_max, hop, lost)}
+
+    def chunk_sums(self, bufs, B, L_cap):
+        """dev / tests: the workspace's per-chunk sums of z^2 after a measurement at capacity (B, L_cap samples): a float64 view
+        [B, ceil(L_cap / chunk)]; the entries of chunks an utterance does not have are undefined"""
+        Kc = -(-L_cap // self.chunk)
+        return bufs["ld_ws"].view(torch.float64)[4 * B * Kc:5 * B * Kc].view(B, Kc)
+
+    def _args(self, wav, n_frames, hop, lost, bufs, out=None):
+        if self.params.dtype != torch.float64 or self.params.device != wav.device or not self.params.is_contiguous():
+            raise ValueError("the loudness parameters are float64 on the waveforms' device")
+        return _lib.fill_args(_lib.LoudnessArgs, wav=wav, n_frames=n_frames, params=self.params, stats=bufs["ld_stats"], ws=bufs["ld_ws"],
+                              out=out, ws_bytes=bufs["ld_ws"].numel() * 4, ld=wav.stride(0) if wav.shape[0] > 1 else wav.shape[1],
+                              ld_out=0 if out is None else out.stride(0) if out.shape[0] > 1 else out.shape[1],
+                              is_i16=int(wav.dtype == torch.int16), hop=hop, lost=lost, B=wav.shape[0], L_cap=wav.shape[1],
+                              fs=self.sampling_rate)
+
+    def run(self, wav, n_frames, hop, lost, bufs):
+        """kernel calls, the capacity-sized form for graph callers: wav fp32 [B, hop (F_max - lost)] (a vocoder's workspace rows: row b
+        holds hop max(n_frames[b] - lost, 0) samples), device int32 [B] frame counts and workspace's buffers -> wav, normalised in
+        place, zero behind each utterance; bufs["ld_stats"] holds the stats rows.  Nothing is allocated, nothing is looked at on the
+        host, every grid is sized by the capacity."""
+        if not wav.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
+        if hop < 1 or lost < 0:
+            raise ValueError(f"hop is positive and lost non-negative, got {hop}, {lost}")
+        if wav.dim() != 2 or wav.dtype != torch.float32 or wav.stride(1) != 1 or wav.shape[1] == 0 or wav.shape[1] % hop:
+            raise ValueError(f"run takes fp32 rows of a multiple of {hop} samples, got {tuple(wav.shape)} {wav.dtype}")
+        if n_frames.dtype != torch.int32 or n_frames.numel() != wav.shape[0] or not n_frames.is_cuda or not n_frames.is_contiguous():
+            raise ValueError("n_frames must be a contiguous int32 [B] on the device")
+        st = _lib.current_stream(wav.device)
+        args = self._args(wav, n_frames, hop, lost, bufs)
+        call.gt_loudness_measure(args, st)
+        call.gt_loudness_apply(args, st)
+        return wav
+
+    # -- the stand-alone uses, on any padded batch
+    def _lengths(self, wav, lengths, lengths_host, dtypes):
+        if not wav.is_cuda:
+            raise CpuWaveError("glow_tts_amd.audio runs on the MI355X only (got a CPU waveform); there is no CPU fallback")
+        if wav.dim() != 2 or wav.dtype not in dtypes:
+            raise ValueError(f"waveforms are [B, T] {' or '.join(str(d) for d in dtypes)}, got {tuple(wav.shape)} {wav.dtype}")
+        B, T = wav.shape
+        if lengths is None:
+            return torch.full((B,), T, dtype=torch.int32, device=wav.device)
+        if lengths_host is None and not lengths.is_cuda:
+            lengths_host = lengths.tolist()
+        if lengths.numel() != B or (lengths_host is not None and (len(lengths_host) != B or max(lengths_host, default=0) > T)):
+            raise ValueError(f"lengths do not fit waveforms {tuple(wav.shape)}")
+        return lengths.to(wav.device, non_blocking=True).to(torch.int32).clamp(min=0, max=T).contiguous()
+
+    def _measure(self, wav, n):
+        """-> (stats fp32 [B, 8], the buffers) of rows that hold samples; rows of no sample are written on the host's side"""
+        B, T = wav.shape
+        if B == 0 or T == 0:
+            row = torch.tensor([-np.inf, 0.0, 1.0, 0.0, 0.0, 0.0, -np.inf, 0.0], dtype=torch.float32, device=wav.device)
+            return row.repeat(B, 1), None
+        if wav.stride(1) != 1:
+            wav = wav.contiguous()
+        bufs = self.workspace(B, T, wav.device)
+        call.gt_loudness_measure(self._args(wav, n, 1, 0, bufs), _lib.current_stream(wav.device))
+        return bufs["ld_stats"].view(B, _lib.LOUD_STATS), bufs
+
+    def measure(self, wav, lengths=None, lengths_host=None):
+        """padded fp32 or int16 rows [B, T] (lengths: their sample counts, default T) -> dict of per-utterance fp32 device tensors:
+        lufs (-inf for silence), peak, gain (what normalize would apply), blocks, gated_abs, gated_rel (the counts J, |A|, |R|), gamma,
+        samples, and `stats` [B, 8], the rows as the kernel wrote them.  No host synchronisation where lengths is a device tensor."""
+        n = self._lengths(wav, lengths, lengths_host, (torch.float32, torch.int16))
+        stats, _ = self._measure(wav, n)
+        out = {name: stats[:, i] for i, name in enumerate(self.STATS)}
+        out["stats"] = stats
+        return out
+
+    def normalize(self, wav, lengths=None, lengths_host=None):
+        """padded fp32 rows [B, T] -> wav_n [B, T] (a new tensor: never the caller's rows), or (wav_n, lengths) with lengths; every
+        utterance at the target, or at the peak ceiling where the target would pass it; zero behind each utterance."""
+        n = self._lengths(wav, lengths, lengths_host, (torch.float32,))
+        B, T = wav.shape
+        out = torch.empty(B, T, dtype=torch.float32, device=wav.device)
+        if B and T:
+            src = wav if wav.stride(1) == 1 else wav.contiguous()
+            _, bufs = self._measure(src, n)
+            call.gt_loudness_apply(self._args(src, n, 1, 0, bufs, out=out), _lib.current_stream(wav.device))
+        return out if lengths is None else (out, n)
+
+    forward = normalize
+
+
+class Normalized(_MelVocoder):
+    """A vocoder with the Loudness stage behind it, itself a _MelVocoder: everything the contract names is the
+    inner vocoder's, `launches` the Loudness stage's more, buffer_spec / held the stage's on top, and _walk the inner walk followed by
+    Loudness.run on the samples where they stand.  Any hop; around Denoised too: Normalized(Denoised(WaveGlow(...))).
+    loudness=None: Loudness(22050, target_lufs, peak_dbfs) on the vocoder's device."""
+
+    def __init__(self, vocoder, loudness=None, target_lufs=-23.0, peak_dbfs=-1.0):
+        super().__init__()
+        if not isinstance(vocoder, _MelVocoder):
+            raise TypeError("Normalized wraps one of audio's vocoders")
+        if loudness is None:
+            loudness = Loudness(target_lufs=target_lufs, peak_dbfs=peak_dbfs).to(next(vocoder.parameters()).device)
+        if not isinstance(loudness, Loudness):
+            raise TypeError("Normalized(loudness=) takes an audio.Loudness")
+        self.vocoder, self.loudness = vocoder, loudness
+        self.hop_length, self.min_frames = vocoder.hop_length, vocoder.min_frames
+        self.mel_channels, self.mel_padding, self.seeded = vocoder.mel_channels, vocoder.mel_padding, vocoder.seeded
+        self.launches = vocoder.launches + loudness.launches
+
+    def set_target(self, lufs, peak_dbfs=None):
+        self.loudness.set_target(lufs, peak_dbfs)
+        return self
+
+    def check_graph_input(self):
+        self.vocoder.check_graph_input()
+
+    def buffer_spec(self, B, F_max):
+        return self.vocoder.buffer_spec(B, F_max) + self.loudness.buffer_spec(B, F_max, self.hop_length, self.min_frames - 1)
+
+    def held(self):
+        return self.vocoder.held(), self.loudness.held()
+
+    def _walk(self, mel, n_frames, bufs, B, F, **seed):
+        wav = self.vocoder._walk(mel, n_frames, bufs, B, F, **seed)
+        return self.loudness.run(wav, n_frames, self.hop_length, self.min_frames - 1, bufs)

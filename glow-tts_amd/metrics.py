@@ -205,10 +205,22 @@ class Evaluator:
         s = ev.score(mel_syn, mel_syn_lengths, wav_ref, wav_ref_lengths, wav_syn, wav_syn_lengths)
 
     -> dict of per-utterance device tensors: mcd (MCD-DTW in dB), cost, path_len, path, status, and — with a yin and a synthesised
-    waveform — rmse_hz, rmse_cents, vde, gpe, n_voiced.  No host synchronisation where the lengths are device tensors."""
+    waveform — rmse_hz, rmse_cents, vde, gpe, n_voiced; with loudness=audio.Loudness(...) (at the stft's rate) and a synthesised
+    waveform also lufs_ref, lufs_syn and lufs_diff = lufs_syn - lufs_ref (BS.1770-4 integrated loudness; -inf for
+    silence), the other outputs unchanged.  No host synchronisation where the lengths are device tensors."""
 
-    def __init__(self, stft, yin=None, n_coef=13):
-        self.stft, self.yin, self.n_coef = stft, yin, n_coef
+    def __init__(self, stft, yin=None, n_coef=13, loudness=None):
+        self.stft, self.yin, self.n_coef, self.loudness = stft, yin, n_coef, loudness
+        self._meters = {}
+
+    def _meter(self, rate, device):
+        """self.loudness, or its like at another sampling rate (kept per rate)"""
+        if rate is None or int(rate) == self.loudness.sampling_rate:
+            return self.loudness
+        if (int(rate), device) not in self._meters:
+            from . import audio
+            self._meters[int(rate), device] = audio.Loudness(int(rate), self.loudness.target_lufs, self.loudness.peak_dbfs).to(device)
+        return self._meters[int(rate), device]
 
     def score(self, mel_syn, mel_syn_lengths, wav_ref, wav_ref_lengths, wav_syn=None, wav_syn_lengths=None, sampling_rate=None):
         """mel_syn [B, n_mel, F] with its frame counts; wav_ref [B, T] (fp32 or int16) with its sample counts, at `sampling_rate`
@@ -229,4 +241,9 @@ class Evaluator:
             f0_syn = self.yin.f0(wav_syn, wav_syn_lengths)
             f0_ref = self.yin.f0(wav_ref, wav_ref_lengths, sampling_rate=sampling_rate)
             out.update(f0_errors(f0_syn, f0_ref, res))
+        if self.loudness is not None and wav_syn is not None:
+            # the same meter on both waveforms, each at its own rate (BS.1770's filter is defined per rate: nothing is resampled)
+            out["lufs_ref"] = self._meter(sampling_rate, wav_ref.device).measure(wav_ref, wav_ref_lengths)["lufs"]
+            out["lufs_syn"] = self.loudness.measure(wav_syn, wav_syn_lengths)["lufs"]
+            out["lufs_diff"] = out["lufs_syn"] - out["lufs_ref"]
         return out

@@ -1465,6 +1465,49 @@ typedef struct gt_denoise_spec_args {
 int gt_denoise_spec(const gt_denoise_spec_args* args, void* stream);
 int gt_denoise_spec_args_size(void);            /* sizeof(gt_denoise_spec_args) */
 
+/* ---- ITU-R BS.1770-4 integrated loudness and normalisation behind the vocoders (csrc/loudness.hip) ------------------
+ * Mono.  z = the K-weighting cascade (two biquads, zero initial state) of x; Ns = fs / 10, Nb = 4 Ns; an utterance of N >= Nb samples
+ * has J = N / Ns - 3 blocks of mean square z_j over samples [j Ns, j Ns + Nb), one of N < Nb has ONE block over all its samples (the
+ * recommendation is silent below 400 ms), N = 0 none; l_j = -0.691 + 10 log10 z_j; A = {l_j > -70}, Gamma = l(mean_A z) - 10,
+ * R = {j in A: l_j > Gamma}, L = l(mean_R z), -inf where A is empty.  peak = max |x| (the sample peak);
+ * g = 10^((target - L) / 20), lowered to ceiling / peak where g peak > ceiling, 1 where L = -inf.
+ *   wav      [B rows, pitch ld elements] fp32, or (is_i16) int16 scaled by 1 / 32768.  Row b holds N_b = min(hop max(n_frames[b] -
+ *            lost, 0), L_cap) samples (a vocoder's row: hop and lost = min_frames - 1 are its own; stand-alone callers pass hop = 1,
+ *            lost = 0 and sample counts).  Nothing at or behind N_b is read.
+ *   params   GT_LOUD_PARAMS doubles read on the device: [0..4] the shelf's b0 b1 b2 a1 a2, [5..9] the high-pass's, [10..25] M, the
+ *            4 x 4 row-major transition of the cascade's state (s1, s2 of the shelf, s1, s2 of the high-pass, transposed direct form
+ *            II) over gt_loudness_chunk(fs) samples, [26..41] M^16, [42] the target in LUFS, [43] the peak ceiling, linear,
+ *            [44..59] M^256.  A captured graph replays with the values the words hold.
+ *   stats    out, fp32 [B][GT_LOUD_STATS]: L, peak, g, J, |A|, |R|, Gamma (-inf where A is empty), N_b.
+ *   ws       gt_loudness_ws_bytes(B, L_cap, fs) bytes, 16-byte aligned: chunk states (double [B][Kc][4], Kc = ceil(L_cap / Lc)), chunk
+ *            sums of z^2 (double [B][Kc]), segment sums (double [B][L_cap / Ns + 1]), chunk peaks (float [B][Kc]), in this order.
+ * gt_loudness_measure: four launches (chunk end states from zero; the state scan; chunk sums from the true start states; blocks,
+ * gates and gain), the recurrence, every sum and the gating in double.  gt_loudness_apply: one launch, fp32 rows only: y = g x for
+ * the N_b samples and 0 from there to L_cap, g = stats[b][2]; written over wav, or (out != NULL) to out [B rows, pitch ld_out] with
+ * wav only read.  params and ws are not looked at by gt_loudness_apply.
+ * gt_loudness_chunk(fs): the chunk length Lc, the largest divisor of fs / 10 in [16, 50]; 0 for a rate the kernels do not take
+ * (fs outside [8000, 192000], no multiple of 10, or no such divisor).  16000, 22050, 24000, 44100, 48000 give 50, 49, 50, 49, 50.
+ * gt_loudness_ws_bytes: 0 outside what the kernels take (such a rate, B outside [1, GT_MEL_MAX_B], L_cap <= 0, 4 B Kc >= 2^31).
+ * Asynchronous, no allocation, no atomics, capturable in a graph; grids are sized by B and L_cap; the order of every sum depends on
+ * the index within the utterance alone: a batch row, stats and samples, is bit-identical to the utterance computed alone.
+ * Refusals, before any launch and in this order: args, wav, n_frames or stats NULL, (measure) params or ws NULL, B outside
+ * [1, GT_MEL_MAX_B], L_cap <= 0, ld < L_cap, hop <= 0, lost < 0, (apply, out != NULL) ld_out < L_cap, (measure) ws_bytes below
+ * gt_loudness_ws_bytes: GT_E_INVAL; a rate or a capacity the kernels do not take, (apply) is_i16: GT_E_UNSUPPORTED; wav not aligned
+ * to its element, n_frames, stats or out not 4-byte, (measure) params not 8-byte or ws not 16-byte aligned: GT_E_ALIGN. */
+#define GT_LOUD_STATS 8
+#define GT_LOUD_PARAMS 64
+typedef struct gt_loudness_args {
+  void* wav; const int32_t* n_frames; const double* params;
+  float* stats; void* ws; float* out;
+  int64_t ws_bytes;
+  int ld; int ld_out; int is_i16; int hop; int lost; int B; int L_cap; int fs;
+} gt_loudness_args;
+int gt_loudness_measure(const gt_loudness_args* args, void* stream);
+int gt_loudness_apply(const gt_loudness_args* args, void* stream);
+int gt_loudness_args_size(void);                /* sizeof(gt_loudness_args) */
+int gt_loudness_chunk(int fs);
+size_t gt_loudness_ws_bytes(int B, int L_cap, int fs);
+
 #ifdef __cplusplus
 }
 #endif
